@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the windowed-transform hot path.  Headline = batched STFT (BASELINE.json configs[1]) in audio
-Msamples/s; the same JSON line carries every other BASELINE config under "configs".
+Msamples/s.  A plain run sets up, warms up, times the K steps, optionally writes the last step's output
+(--dump-outputs DIR) and prints its JSON line; --full adds everything else: every other BASELINE config under
+"configs" and the extra geometries (--kind all), parity against the NumPy oracle, CPU baselines, one-by-one kernel
+times, live HBM traffic, the placement survey, PCIe figures and the bench_detail.json record.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--kind all|stft|istft|mdct|imdct|mel|mfcc|cqt|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--kind all|stft|istft|mdct|imdct|mel|mfcc|cqt|...]
     <any launcher that sets RANK / LOCAL_RANK / WORLD_SIZE, one process per GPU> bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: 1024 clips x 10 s @ 44.1 kHz per GPU (config 5, CQT: 1024
@@ -27,8 +30,12 @@ FIRST allocation of every buffer, as a caller of the library gets it; where the 
 the STFT by up to 12 %, so the line also reports a survey of further allocations (`config.placement`).
 
 `roofline.achieved` = algorithmic bytes (or flops) per launch / mean kernel duration measured with HIP events on
-the plan's stream over the timed region.  `cpu_baseline` = the NumPy oracle (a port of zaf.py, same NumPy calls per
-clip) timed on this host, rank 0, N = 1 only, bounded samples.
+the plan's stream over the timed region.  `cpu_baseline` (--full) = the NumPy oracle (a port of zaf.py, same NumPy calls
+per clip) timed on this host, rank 0, N = 1 only, bounded samples.
+
+--dump-outputs DIR writes DIR/<kind>.npy after the timed steps: the headline's output as the last timed step left it on
+the device (complex values as float pairs on a trailing axis; of the 7.25 GB STFT output, 8 whole clips chosen by a fixed
+seed, DUMP_SEED).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -610,8 +617,8 @@ def prewarm(plan, d_in, d_out, n_clips, n_in, seconds=None):
 
 def time_workload(wl, steps, warmup, rdzv):
     """Contract timing: W untimed steps, then EXACTLY K steps between (device sync + barrier) pairs, MAX over ranks;
-    the HIP-event stopwatch of the plan's stream wraps the same K launches.  A second, separate pass times the K
-    launches one by one (min / median of the kernel duration)."""
+    the HIP-event stopwatch of the plan's stream wraps the same K launches.  On return the output buffer holds what
+    the last timed step wrote."""
     plan, B, n_in = wl["plan"], wl["n_clips"], wl["n_in"]
 
     def sync_all():
@@ -630,20 +637,59 @@ def time_workload(wl, steps, warmup, rdzv):
     kernel_ms = plan.timer_stop() / max(steps, 1)
     sync_all()
     elapsed = time.perf_counter() - t0
+    vals = [elapsed, kernel_ms]
+    per_rank = [kernel_ms]
+    if rdzv is not None:
+        import struct
+        per_rank = [struct.unpack("<d", b)[0] for b in rdzv.all_gather(struct.pack("<d", kernel_ms))]
+        vals = rdzv.all_reduce_max(vals)
+    return {"elapsed_s": vals[0], "kernel_ms": vals[1], "kernel_ms_min": None, "kernel_ms_median": None,
+            "kernel_ms_per_rank": [round(v, 4) for v in per_rank],
+            "segments": [["prewarm", n_pre], ["warmup", warmup], ["timed", steps]]}
+
+
+def time_each(wl, steps, rdzv, tm):
+    """--full: a second, separate pass after the timed region times the K launches one by one (min / median of the
+    kernel duration, MAX over ranks) and records them in `tm`."""
+    plan, B, n_in = wl["plan"], wl["n_clips"], wl["n_in"]
     each = []
     for _ in range(steps):
         plan.timer_start()
         plan.execute(wl["d_in"], wl["d_out"], B, n_in)
         each.append(plan.timer_stop())
-    vals = [elapsed, kernel_ms, -min(each), float(np.median(each))]
-    per_rank = [kernel_ms]
+    vals = [-min(each), float(np.median(each))]
     if rdzv is not None:
-        import struct
-        per_rank = [struct.unpack("<d", b)[0] for b in rdzv.all_gather(struct.pack("<d", kernel_ms))]
         vals = rdzv.all_reduce_max(vals)   # (-min: the MAX over ranks of -min is the smallest step anywhere)
-    return {"elapsed_s": vals[0], "kernel_ms": vals[1], "kernel_ms_min": -vals[2], "kernel_ms_median": vals[3],
-            "kernel_ms_per_rank": [round(v, 4) for v in per_rank],
-            "segments": [["prewarm", n_pre], ["warmup", warmup], ["timed", steps], ["each", steps]]}
+    tm.update(kernel_ms_min=-vals[0], kernel_ms_median=vals[1])
+    tm["segments"].append(["each", steps])
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs: at most this much of the output, as float32 / float64
+DUMP_SEED = 20240611            # which clips of a larger output are written (fixed: the same clips on every run)
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs DIR: what the last timed step wrote, as DIR/<kind>.npy.  Complex results become float pairs on a
+    trailing axis of 2 (complex64 -> float32, complex128 -> float64); rows padded on the device are cut to the frames a
+    caller receives.  An output larger than DUMP_LIMIT_BYTES is written as a fixed, seeded sample of whole clips (sorted
+    clip indices).  -> (path, clip indices)."""
+    d_out, B = wl["d_out"], wl["n_clips"]
+    per_clip = d_out.nbytes // max(B, 1)
+    n = max(1, min(B, DUMP_LIMIT_BYTES // max(per_clip, 1)))
+    clips = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    arr = d_out.download() if n == B else np.concatenate([d_out.download(int(c), 1) for c in clips])
+    from zafx import LAYOUT_FT
+    plan = wl["plan"]
+    rows, frames = plan.out_dims(wl["n_in"])
+    if arr.ndim == 3 and plan.layout == LAYOUT_FT and arr.shape[1] == rows and arr.shape[2] > frames:
+        arr = arr[:, :, :frames]   # (row pitch padded to 128-byte lines on the device)
+    if np.iscomplexobj(arr):
+        arr = np.stack([arr.real, arr.imag], axis=-1)
+    arr = np.ascontiguousarray(arr, dtype=np.float64 if arr.dtype == np.float64 else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, wl["kind"] + ".npy")
+    np.save(path, arr)
+    return path, clips
 
 
 INNER_LOG = []   # {"kind", "kernel", "launches", "segments"} in launch order, written to $ZAFX_BENCH_INNER_LOG (profiled runs: which dispatches were the timed ones)
@@ -673,7 +719,7 @@ def live_traffic(kinds):
             log = os.path.join(work, counter + ".log")
             env = dict(os.environ, TMPDIR="/tmp", ZAFX_BENCH_INNER="1", ZAFX_BENCH_INNER_LOG=log)
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--",
-                   sys.executable, os.path.abspath(__file__), "--kind", ",".join(kinds), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+                   sys.executable, os.path.abspath(__file__), "--kind", ",".join(kinds), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"]
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300, check=True)
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
             if not files:
@@ -727,8 +773,10 @@ def roofline_of(wl, tm, kind):
     gbs = wl["bytes_per_launch"] / (kernel_ms * 1e-3) / 1e9
     roof = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
             "frac_of_achievable_6290": round(gbs / HBM_ACHIEVABLE_GBS, 4), "traffic": None,
-            "kernel": wl["plan"].last_kernel, "kernel_ms": round(kernel_ms, 4), "kernel_ms_min": round(tm["kernel_ms_min"], 4),
-            "kernel_ms_median": round(tm["kernel_ms_median"], 4), "algorithmic_bytes_per_launch": wl["bytes_per_launch"]}
+            "kernel": wl["plan"].last_kernel, "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": wl["bytes_per_launch"]}
+    for k in ("kernel_ms_min", "kernel_ms_median"):   # (the one-by-one pass of --full)
+        if tm[k] is not None:
+            roof[k] = round(tm[k], 4)
     pmc = os.path.join(ROOT, "profiles", f"pmc_{kind}.json")
     if os.path.exists(pmc):   # a separate rocprofv3 --pmc collection of the same command, committed under profiles/
         with open(pmc) as f:
@@ -822,8 +870,9 @@ def e2e_pcie(device, clips=512):
     return out
 
 
-def run_kind(kind, args, device, rank, world, rdzv, comm, with_cpu):
-    """One config: build the device-resident workload, broadcast its constants, time it, probe parity -> (entry, timing, workload info)."""
+def run_kind(kind, args, device, rank, world, rdzv, comm, with_cpu, dump_dir=None):
+    """One config: build the device-resident workload, broadcast its constants, time it, write its output (dump_dir, rank 0), and
+    with --full time the launches one by one and probe parity -> (entry, timing, workload info)."""
     import zafx
     wl = make_workload(kind, device, args.layout)
     bcast = "none (1 rank)" if world == 1 else "none (no RCCL communicator: every rank built its own constants)"
@@ -840,6 +889,11 @@ def run_kind(kind, args, device, rank, world, rdzv, comm, with_cpu):
             bcast = f"FAILED ({exc}); every rank built its own constants"
     tm = time_workload(wl, args.steps, args.warmup, rdzv)
     tm["broadcast_s"] = bcast_s
+    if dump_dir is not None and rank == 0:
+        path, clips = dump_outputs(wl, dump_dir)
+        tm["dump"] = {"path": path, "clips": clips.tolist() if len(clips) < wl["n_clips"] else "all"}
+    if args.full:
+        time_each(wl, args.steps, rdzv, tm)
     inner = os.environ.get("ZAFX_BENCH_INNER") == "1"
     INNER_LOG.append({"kind": kind, "kernel": wl["plan"].last_kernel, "launches": sum(n for _, n in tm["segments"]), "segments": tm["segments"],
                       "kernel_ms": tm["kernel_ms"]})
@@ -848,7 +902,7 @@ def run_kind(kind, args, device, rank, world, rdzv, comm, with_cpu):
         total = float(wl["n_clips"]) * wl["samples_per_clip"] * world * args.steps
         entry = {"workload": wl["desc"], "value": round(total / tm["elapsed_s"] / 1e6, 1), "unit": "Msamples/s",
                  "ms_per_step": round(tm["elapsed_s"] / args.steps * 1e3, 4), "roofline": roofline_of(wl, tm, kind),
-                 "parity": {} if inner else parity_probe(wl), "constants_broadcast": bcast}
+                 "parity": {} if inner or not args.full else parity_probe(wl), "constants_broadcast": bcast}
         if world > 1 or comm is not None:
             entry["kernel_ms_per_rank"] = tm["kernel_ms_per_rank"]
             entry["constants_broadcast_wall_s"] = None if bcast_s is None else round(bcast_s, 4)
@@ -989,14 +1043,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--kind", default="all", help="all = headline STFT + every other BASELINE config in one line; or one of "
-                    "stft istft mdct imdct mel mfcc cqt dct or an extra: " + " ".join(EXTRA_KINDS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--kind", default=None, help="stft (the headline; the default of a plain run) | all (the default with --full) = "
+                    "headline STFT + every other BASELINE config in one line; or one of stft istft mdct imdct mel mfcc cqt dct or an extra: "
+                    + " ".join(EXTRA_KINDS))
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: every BASELINE config and extra geometry "
+                    "(--kind all), parity against the NumPy oracle, CPU baselines, the one-by-one kernel times, live HBM traffic, the "
+                    "placement survey, PCIe figures and the bench_detail.json record")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the headline's last timed step computed to "
+                    "DIR/<kind>.npy (float32 / float64; complex as a trailing axis of 2; a fixed, seeded sample of whole clips when the "
+                    "output exceeds 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-configs", action="store_true", help="with --kind all: headline only")
     ap.add_argument("--layout", default="FT", choices=["FT", "TF"], help="FT = reference (W, T) memory order (default); TF = frame-major")
     ap.add_argument("--selftest-launch", action="store_true", help="CPU only: run the N-rank control flow (rendezvous, id broadcast, "
                     "clip sharding with the oracle standing in for the device step, barrier, MAX) and print its JSON line")
     args = ap.parse_args()
+    if args.kind is None:
+        args.kind = "all" if args.full else "stft"
+    dump_dir = os.path.abspath(args.dump_outputs) if args.dump_outputs else None
 
     from zafx import launch
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1086,12 +1150,13 @@ def main():
             comm = None
 
     kinds = args.kind.split(",") if args.kind != "all" else ["stft"] + ([] if args.no_configs else list(CONFIG_KINDS) + list(EXTRA_KINDS))
-    with_cpu = world == 1 and not args.no_cpu_baseline
+    with_cpu = world == 1 and args.full and not args.no_cpu_baseline
     entries, extras = {}, {}
     head = head_info = head_tm = None
     for kind in kinds:
-        entry, tm, info = run_kind(kind, args, device, rank, world, rdzv, comm, with_cpu and kind not in EXTRA_KINDS)
-        if head is None:
+        entry, tm, info = run_kind(kind, args, device, rank, world, rdzv, comm, with_cpu and kind not in EXTRA_KINDS,
+                                   dump_dir if head_tm is None else None)
+        if head_tm is None:
             head, head_info, head_tm = entry, info, tm
         elif kind in EXTRA_KINDS:
             extras[kind] = entry
@@ -1103,7 +1168,7 @@ def main():
     if os.environ.get("ZAFX_BENCH_INNER_LOG"):
         with open(os.environ["ZAFX_BENCH_INNER_LOG"], "w") as fh:
             json.dump(INNER_LOG, fh)
-    if rank == 0 and world == 1 and args.kind == "all" and os.environ.get("ZAFX_BENCH_INNER") != "1":
+    if rank == 0 and world == 1 and args.full and args.kind == "all" and os.environ.get("ZAFX_BENCH_INNER") != "1":
         # HBM traffic of the headline and of every BASELINE config from this run's own counters (two profiled child runs)
         measured = [k for k in kinds if k not in EXTRA_KINDS]
         live = live_traffic(measured)
@@ -1157,7 +1222,9 @@ def main():
             out["configs"] = entries
         if extras:
             out["extras"] = extras
-        if world == 1 and hk == "stft" and args.kind == "all" and "placement" not in head:
+        if "dump" in head_tm:
+            out["dump_outputs"] = head_tm["dump"]
+        if world == 1 and hk == "stft" and args.full and args.kind == "all" and "placement" not in head:
             try:
                 out["config"]["placement"] = placement_survey(device, head["roofline"]["kernel_ms"], args.layout) or "first allocation"
             except zafx.ZafxError as exc:
@@ -1170,13 +1237,12 @@ def main():
                 out["end_to_end_pcie"] = e2e_pcie(device)
             except zafx.ZafxError as exc:
                 out["end_to_end_pcie"] = {"error": str(exc)}
-        # the full record (workload prose, flop notes, placement survey, traffic sources) goes beside the script and to stderr;
-        # stdout carries the ONE compact line, last
-        detail = os.path.join(ROOT, "gpurun_out") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else ROOT
-        detail = os.path.join(detail, "bench_detail.json")
+        # the full record (workload prose, flop notes, placement survey, traffic sources) goes to stderr and, with --full, to
+        # bench_detail.json beside the script (or in $ZAFX_BENCH_DETAIL_DIR); stdout carries the ONE compact line, last
+        detail = os.path.join(os.environ.get("ZAFX_BENCH_DETAIL_DIR") or ROOT, "bench_detail.json")
         try:
-            if os.environ.get("ZAFX_BENCH_INNER") == "1":
-                raise OSError("profiled child run: no record")
+            if os.environ.get("ZAFX_BENCH_INNER") == "1" or not args.full:
+                raise OSError("plain or profiled child run: no record")
             with open(detail, "w") as fh:
                 json.dump(out, fh, indent=1)
             out["detail"] = os.path.relpath(detail, ROOT)

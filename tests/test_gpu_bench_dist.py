@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 def run_bench(extra_env, *args, timeout=600):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ZAFX_RDZV_DIR", "ZAFX_RDZV_NS")}
     env.update(extra_env)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--kind", "stft", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *args],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--kind", "stft", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full", *args],
                          env=env, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (res.returncode, res.stdout[-1000:], res.stderr[-2000:])
