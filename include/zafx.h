@@ -187,6 +187,22 @@ int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
 /* Enqueue the transform of n_clips clips on the plan's stream (asynchronous). */
 int zafx_execute(zafx_plan* plan, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in);
 int zafx_sync(zafx_plan* plan);
+/* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
+ * with_mel included, _CQT, _CHROMA; float32 and float64).
+ * Output placement: clip i of lengths[i] samples gets its block of the output array at element out_offsets[i];
+ * out_offsets[n_clips] = total elements.  FT layout: F rows at zafx_plan_row_pitch(plan, lengths[i]); TF: T_i x F compact.
+ * T_i is zafx_plan_out_dims(plan, lengths[i])[1] (a length of 0 gives the reference's single all-zero frame).  The blocks lie
+ * back to back, so every block starts on a 128-byte line when the plan's rows are whole lines and the array does. */
+int zafx_plan_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64_t n_clips, int64_t* out_offsets);
+/* Enqueue the transform of n_clips clips of different lengths on the plan's stream (asynchronous): clip i is lengths[i]
+ * samples at element in_offsets[i] of d_in; its result goes to the block zafx_plan_ragged_layout assigns.  The two host
+ * arrays are copied before return.  Negative lengths or offsets and more than 2^31 - 1 sixteen-frame tiles in all are
+ * rejected.  Float32 plans in ZAFX_LAYOUT_FT whose every clip has rows of whole 128-byte lines (params.row_align = one line)
+ * and a 128-byte aligned d_out run in ONE launch: the STFT at window 256 ... 2048 on k_stft_ft16 (last kernel
+ * "k_stft_ft16_ragged"; |X| / |X|^2 at 2048 on k_mel2), mel / mfcc on k_mel2 where zafx_execute runs them there
+ * ("k_mel2_ragged").  Everything else runs one zafx_execute per clip on the plan's stream ("per-clip <kernel>"). */
+int zafx_execute_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
+                        int64_t n_clips);
 /* Bytes of ONE clip on the input and on the output side of the plan for `n_in` (as zafx_plan_out_dims; rows at the
  * plan's pitch): what a host array of n_clips clips must hold for zafx_run_host. */
 int zafx_plan_clip_bytes(const zafx_plan* plan, int64_t n_in, int64_t* in_bytes, int64_t* out_bytes);

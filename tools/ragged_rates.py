@@ -1,0 +1,104 @@
+"""Rates of ragged batches (zafx_execute_ragged) against the padded batch and an equal-length batch, in one process.
+
+    python tools/ragged_rates.py [--reps 30] [--out FILE]
+
+Batch: 1024 clips, lengths uniform in 5-15 s at 44.1 kHz (even, so that the aligned loads apply as they do for the equal-length batch),
+window 2048, hop 1024.  For the STFT (two-sided, the headline's kind), mel (128 filters), mfcc (20 coefficients) and the one-pass mel + mfcc:
+  ragged   one execute_ragged of the 1024 clips (the table's upload included)
+  padded   the same clips padded to the longest as one execute
+  equal    1024 clips of 10 s as one execute
+each timed with the plan's HIP-event stopwatch, one launch per reading, median (min, max) of --reps readings after warm-up.  All outputs are
+DeviceBuffers (zafx_alloc) with rows on the 128-byte line grid, so placement treats the three alike; Msamples/s counts the clips' own samples.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "zaf-python_amd"))
+import zafx  # noqa: E402
+
+FS, W, HOP, CLIPS = 44100, 2048, 1024, 1024
+
+
+def timed(plan, launch, reps, warm=3):
+    for _ in range(warm):
+        launch()
+    plan.sync()
+    ms = []
+    for _ in range(reps):
+        plan.timer_start()
+        launch()
+        ms.append(plan.timer_stop())
+    return {"median_ms": float(np.median(ms)), "min_ms": float(np.min(ms)), "max_ms": float(np.max(ms))}
+
+
+def inputs(lengths):
+    """The three input arrays, filled once with noise and shared by every kind: the packed ragged batch, the padded batch, the 10 s batch."""
+    rng = np.random.default_rng(1)
+    in_offsets = np.zeros(len(lengths), np.int64)
+    slots = (lengths + 31) // 32 * 32
+    in_offsets[1:] = np.cumsum(slots)[:-1]
+    bufs = {}
+    for key, shape in (("ragged", (int(slots.sum()),)), ("padded", (CLIPS, int(lengths.max()))), ("equal", (CLIPS, 10 * FS))):
+        bufs[key] = zafx.DeviceBuffer(shape, np.float32)
+        bufs[key].upload(rng.standard_normal(shape, dtype=np.float32))   # (the ragged gaps hold noise too: the kernels never read them)
+    return in_offsets, bufs
+
+
+def measure(name, plan, lengths, in_offsets, bufs, reps):
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    out = zafx.DeviceBuffer((int(offs[-1]),), plan.out_dtype)
+    res = {}
+    res["ragged"] = timed(plan, lambda: plan.execute_ragged(bufs["ragged"], in_offsets, lengths, out), reps)
+    res["ragged_kernel"] = plan.last_kernel
+    out.free()
+    for key, n in (("padded", int(lengths.max())), ("equal", 10 * FS)):
+        o = zafx.DeviceBuffer(plan.out_shape(CLIPS, n), plan.out_dtype)
+        res[key] = timed(plan, lambda: plan.execute(bufs[key], o, CLIPS, n), reps)
+        res[key + "_kernel"] = plan.last_kernel
+        o.free()
+    samples = {"ragged": int(lengths.sum()), "padded": int(lengths.sum()), "equal": CLIPS * 10 * FS}
+    for key in ("ragged", "padded", "equal"):
+        res[key]["msamples_per_s"] = samples[key] / (res[key]["median_ms"] * 1e3)
+    res["ragged_over_padded"] = res["ragged"]["median_ms"] / res["padded"]["median_ms"]
+    res["ragged_rate_over_equal_rate"] = res["ragged"]["msamples_per_s"] / res["equal"]["msamples_per_s"]
+    r, p, e = res["ragged"], res["padded"], res["equal"]
+    print(f"{name:9s} ragged {r['median_ms']:7.3f} ms ({r['min_ms']:.3f}-{r['max_ms']:.3f}) {r['msamples_per_s']:8.0f} Ms/s [{res['ragged_kernel']}] | "
+          f"padded {p['median_ms']:7.3f} ms ({p['min_ms']:.3f}-{p['max_ms']:.3f}) [{res['padded_kernel']}] | equal {e['median_ms']:7.3f} ms "
+          f"({e['min_ms']:.3f}-{e['max_ms']:.3f}) {e['msamples_per_s']:8.0f} Ms/s [{res['equal_kernel']}] | ragged / padded "
+          f"{res['ragged_over_padded']:.3f}, rate ragged / equal {res['ragged_rate_over_equal_rate']:.3f}", flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    lengths = rng.integers(5 * FS, 15 * FS + 1, CLIPS).astype(np.int64)
+    lengths -= lengths % 2
+    window = zafx.hamming(W)
+    fb = zafx.melfilterbank(FS, W, 128)
+    plans = {
+        "stft": zafx.stft_plan(window, HOP, row_align=16),
+        "mel": zafx.mel_plan(window, HOP, fb, row_align=32),
+        "mfcc": zafx.mel_plan(window, HOP, fb, 20, row_align=32),
+        "mel+mfcc": zafx.mel_plan(window, HOP, fb, 20, row_align=32, also_mel=True),
+    }
+    result = {"device": zafx.device_name(0), "clips": CLIPS, "window": W, "hop": HOP, "samples": int(lengths.sum()),
+              "longest": int(lengths.max()), "reps": a.reps}
+    in_offsets, bufs = inputs(lengths)
+    for name, plan in plans.items():
+        result[name] = measure(name, plan, lengths, in_offsets, bufs, a.reps)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -1244,6 +1244,9 @@ int zafx_plan_destroy(zafx_plan* pl) {
     if (pl->d_values64) (void)hipFree(pl->d_values64);
     if (pl->d_bhat64) (void)hipFree(pl->d_bhat64);
     if (pl->d_pcm_float) (void)hipFree(pl->d_pcm_float);
+    if (pl->d_ragged) (void)hipFree(pl->d_ragged);
+    if (pl->h_ragged) (void)hipHostFree(pl->h_ragged);
+    if (pl->rg_ev) (void)hipEventDestroy(pl->rg_ev);
     if (pl->d_bs_chirp) (void)hipFree(pl->d_bs_chirp);
     if (pl->d_bs_bhat) (void)hipFree(pl->d_bs_bhat);
     free_band(pl->fb);
@@ -1468,6 +1471,138 @@ int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, 
         if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute", e);
         return (int)e;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// ragged batches: clips of different lengths in one call
+// ---------------------------------------------------------------------------------
+static bool ragged_kind(int kind) {
+    return kind == ZAFX_STFT || kind == ZAFX_MDCT || kind == ZAFX_MEL || kind == ZAFX_MFCC || kind == ZAFX_CQT || kind == ZAFX_CHROMA;
+}
+
+static int64_t out_elem_bytes(const zafx_plan* pl) {
+    const int64_t real = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
+    return pl->kind == ZAFX_STFT && pl->prm.spectrum < ZAFX_SPECTRUM_MAGNITUDE ? 2 * real : real;
+}
+
+// One clip's block of the output (elements) and its frames / row pitch.  Blocks lie back to back, so with rows of whole 128-byte lines every
+// block starts on a line when the array does.
+static int ragged_block(const zafx_plan* pl, int64_t len, int64_t* elems, int64_t* frames, int64_t* pitch) {
+    int64_t dims[2];
+    if (int rc = zafx_plan_out_dims(pl, len, dims)) return rc;
+    if (int rc = zafx_plan_row_pitch(pl, len, pitch)) return rc;
+    *frames = dims[1];
+    *elems = pl->layout == ZAFX_LAYOUT_FT ? dims[0] * *pitch : dims[1] * dims[0];
+    return 0;
+}
+
+int zafx_plan_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int64_t* out_offsets) {
+    if (!pl || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
+    if (n_clips < 0) return fail_msg("negative size");
+    if (!ragged_kind(pl->kind)) return fail_msg("ragged batches: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
+    out_offsets[0] = 0;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        if (lengths[i] < 0) return fail_msg("ragged batch: negative length of clip " + std::to_string(i));
+        int64_t elems = 0, frames = 0, pitch = 0;
+        if (int rc = ragged_block(pl, lengths[i], &elems, &frames, &pitch)) return rc;
+        out_offsets[i + 1] = out_offsets[i] + elems;
+    }
+    return 0;
+}
+
+// The name a per-clip fallback reports ("per-clip <kernel>"): kept for the life of the library (a plan's `ran` holds plain pointers)
+static const char* per_clip_name(const char* kernel) {
+    static std::mutex mu;
+    static std::map<std::string, std::string> names;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = names.emplace(kernel, std::string("per-clip ") + kernel).first;
+    return it->second.c_str();
+}
+
+// The table of a native launch (zafx::RgClip records, then the clip of every 16-frame tile) through the plan's page-locked staging copy onto
+// its device copy, on the plan's stream.  The staging copy is written only once the upload of the previous call has left it (rg_ev); the
+// device copy is overwritten in stream order behind the kernels that read it, and a larger one replaces it only once the stream is idle.
+static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& recs, int64_t total_tiles) {
+    const size_t rec_b = recs.size() * sizeof(zafx::RgClip), need = rec_b + (size_t)total_tiles * sizeof(int);
+    if (!pl->rg_ev) ZAFX_HIP(hipEventCreateWithFlags(&pl->rg_ev, hipEventDisableTiming));
+    else ZAFX_HIP(hipEventSynchronize(pl->rg_ev));
+    if (pl->ragged_host_bytes < need) {
+        if (pl->h_ragged) ZAFX_HIP(hipHostFree(pl->h_ragged));
+        pl->h_ragged = nullptr, pl->ragged_host_bytes = 0;
+        ZAFX_HIP(hipHostMalloc(&pl->h_ragged, need, hipHostMallocDefault));
+        pl->ragged_host_bytes = need;
+    }
+    if (pl->ragged_bytes < need) {
+        ZAFX_HIP(hipStreamSynchronize(pl->stream));
+        if (pl->d_ragged) ZAFX_HIP(hipFree(pl->d_ragged));
+        pl->d_ragged = nullptr, pl->ragged_bytes = 0;
+        ZAFX_HIP(hipMalloc(&pl->d_ragged, need));
+        pl->ragged_bytes = need;
+    }
+    unsigned char* h = static_cast<unsigned char*>(pl->h_ragged);
+    std::memcpy(h, recs.data(), rec_b);
+    int* clip_of = reinterpret_cast<int*>(h + rec_b);
+    for (size_t c = 0; c < recs.size(); ++c) {
+        const int tiles = (recs[c].T + 15) / 16;
+        for (int j = 0; j < tiles; ++j) clip_of[recs[c].first_tile + j] = (int)c;
+    }
+    ZAFX_HIP(hipMemcpyAsync(pl->d_ragged, pl->h_ragged, need, hipMemcpyHostToDevice, pl->stream));
+    ZAFX_HIP(hipEventRecord(pl->rg_ev, pl->stream));
+    return 0;
+}
+
+int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
+    if (!pl) return fail_msg("null plan");
+    if (n_clips < 0) return fail_msg("negative size");
+    if (!ragged_kind(pl->kind)) return fail_msg("zafx_execute_ragged: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
+    if (n_clips == 0) return 0;
+    if (!in_offsets || !lengths) return fail_msg("null argument");
+    if (!d_in || !d_out) return fail_msg("null device pointer");
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] < 0 || in_offsets[i] < 0) return fail_msg("zafx_execute_ragged: negative length or offset of clip " + std::to_string(i));
+    // every clip's place in the output, frames and pitch; the 16-frame tiles of the batch
+    std::vector<zafx::RgClip> recs((size_t)n_clips);
+    const int64_t eb = out_elem_bytes(pl);
+    int64_t out_off = 0, tiles = 0;
+    bool lines = reinterpret_cast<uintptr_t>(d_out) % 128 == 0, short_clips = true, even = pl->H % 2 == 0 && reinterpret_cast<uintptr_t>(d_in) % 8 == 0;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        int64_t elems = 0, frames = 0, pitch = 0;
+        if (int rc = ragged_block(pl, lengths[i], &elems, &frames, &pitch)) return rc;
+        zafx::RgClip& r = recs[(size_t)i];
+        r = {in_offsets[i], lengths[i], out_off, (int)std::min<int64_t>(frames, INT32_MAX), (int)std::min<int64_t>(pitch, INT32_MAX), (int)std::min<int64_t>(tiles, INT32_MAX), 0};
+        lines = lines && pl->layout == ZAFX_LAYOUT_FT && (pitch * eb) % 128 == 0 && pitch < INT32_MAX;
+        short_clips = short_clips && lengths[i] < (1LL << 29);
+        even = even && in_offsets[i] % 2 == 0 && lengths[i] % 2 == 0;
+        out_off += elems;
+        tiles += (frames + 15) / 16;
+        if (tiles >= (1LL << 31)) return fail_msg("zafx_execute_ragged: batch too large for one launch (16-frame tiles >= 2^31)");
+    }
+    ZAFX_HIP(hipSetDevice(pl->device));
+    // native: k_stft_ft16 / k_mel2 in their RAGGED forms (float32, reference layout, every clip's rows whole 128-byte lines)
+    const bool on_mel2 = zafx::mel_ragged_native(*pl);
+    const bool native = pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->d_window && lines &&
+                        (pl->kind == ZAFX_STFT ? zafx::stft_ragged_native(*pl) && (!on_mel2 || short_clips) : on_mel2 && short_clips);
+    if (native) {
+        if (int rc = upload_ragged_table(pl, recs, tiles)) return rc;
+        const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged);
+        const hipError_t e = pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
+                                                   : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even);
+        if (e != hipSuccess) {
+            if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_ragged", e);
+            return (int)e;
+        }
+        return 0;
+    }
+    // everything else: one zafx_execute per clip on the plan's stream, into the same blocks
+    const int64_t ib = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
+    pl->ran.store(nullptr, std::memory_order_release);
+    for (int64_t i = 0; i < n_clips; ++i) {
+        const zafx::RgClip& r = recs[(size_t)i];
+        if (int rc = zafx_execute(pl, (const char*)d_in + r.in_off * ib, (char*)d_out + r.out_off * eb, 1, r.n_samples)) return rc;
+    }
+    const char* last = pl->ran.load(std::memory_order_acquire);
+    pl->ran.store(per_clip_name(last ? last : pl->kernel_name.c_str()), std::memory_order_release);
     return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <atomic>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zafx.h"
@@ -171,6 +172,13 @@ struct zafx_plan {
     int bs_log2m = 0;              // > 0: window that is not a power of two -- Bluestein convolution length 2^bs_log2m (zafx_f64.hip, zafx_bs32.hip)
     void* d_pcm_float = nullptr;   // zafx_execute_pcm's float32 staging for the kinds that do not (grow-only)
     size_t pcm_float_bytes = 0;
+    // zafx_execute_ragged: the batch's table (zafx::RgClip records, then the clip of every tile) on the device and its page-locked staging
+    // copy, both grow-only; rg_ev marks the upload of the last call -- the host waits for it before it writes the staging copy again
+    void* d_ragged = nullptr;
+    size_t ragged_bytes = 0;
+    void* h_ragged = nullptr;
+    size_t ragged_host_bytes = 0;
+    hipEvent_t rg_ev = nullptr;
     int dct_half = 0;              // ZAFX_DCT, types II-IV, N = 4 j with N / 2 not a power of two: N / 2, the points of the transform inside k_dct<.., BS> (zafx_dct.hip)
     long long dct_den2 = 0;        // ZAFX_DCT on the chirp-z form: 2 D, the denominator of its chirp exp(-i pi j^2 / (2 D)) (k_dct_bs32)
     float2* d_bs_chirp = nullptr;  // float32 Bluestein plans: c[n] = exp(-i pi n^2 / W), n < W
@@ -190,6 +198,37 @@ struct zafx_plan {
 };
 
 namespace zafx {
+
+// One clip of a ragged batch (zafx_execute_ragged).  The plan's table on the device is n_clips of these, then one int per 16-frame tile
+// of the batch: the clip it belongs to.  Offsets and lengths in elements of the input / output arrays.
+struct RgClip {
+    long long in_off, n_samples, out_off;
+    int T, TP, first_tile, pad_;
+};
+static_assert(sizeof(RgClip) == 40 && alignof(RgClip) == 8, "RgClip: the layout the host writes");
+// The kernels' RAGGED forms (k_stft_ft16, k_mel2) take the table in the 8-byte slot of n_samples and the clip count in `tiles`: the existing
+// instantiations keep their kernel arguments byte for byte.
+template <bool RAGGED>
+using SamplesArg = std::conditional_t<RAGGED, const RgClip*, long long>;
+// RAGGED ? a field of the tile's record : the kernel's own argument.  A reference: the equal-length instantiations read their arguments
+// where and how they always did, and their code stays the same instruction for instruction.
+template <bool RAGGED, class R, class A>
+__host__ __device__ __forceinline__ const auto& rg_pick(const R& rec, const A& arg) {
+    if constexpr (RAGGED) return rec;
+    else return arg;
+}
+#ifdef __HIPCC__
+// The record of tile `tl` (uniform): its clip from the per-tile part of the table, the record by scalar loads.
+__device__ __forceinline__ RgClip rg_clip(const RgClip* tab, int n_clips, int tl) {
+    const int c = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(tab + n_clips)[tl]);
+    return tab[c];
+}
+#endif
+hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
+hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
+bool spec2_ragged(const zafx_plan& pl);   // |X| / |X|^2 at W = 2048 on k_mel2 (what launch_spec2 takes)
+bool stft_ragged_native(const zafx_plan& pl);   // the plans whose ragged batches have a kernel of their own (zafx_execute_ragged)
+bool mel_ragged_native(const zafx_plan& pl);
 
 // Every launcher enqueues on plan.stream and returns hipGetLastError().
 // Frames between the starts of consecutive rows of a plan's (F, T) array: T rounded up to prm.row_align elements

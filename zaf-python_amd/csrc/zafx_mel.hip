@@ -592,11 +592,19 @@ constexpr int kMel2DualPitch = 1057;   // float2 slots per frame buffer of the o
 // 0 float32 samples; 1 int16 mono (n_samples 2-byte samples per clip: 8 bytes per lane and load instead of 16); 2 int16 stereo
 // (n_samples 4-byte frames per clip: the float32 form's loads, both channels added on the way into the window multiply).  The factor
 // 2^-15 (2^-16: the mean of two channels) is a power of two and rides in the window.
-template <bool ALIGNED, int MODE, int PCM = 0>
+// RAGGED (zafx_execute_ragged): clips of different lengths, as k_stft_ft16's RAGGED form -- `n_samples` carries the batch's table, `tiles` the
+// number of clips; a tile's clip gives its samples (and the base of the aligned form's buffer descriptor), frames, row pitch and output base.
+template <bool ALIGNED, int MODE, int PCM = 0, bool RAGGED = false>
 __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, const float* __restrict__ win, const float2* __restrict__ twp,
                                                    const float2* __restrict__ tws, const float* __restrict__ fb_pack, const int4* __restrict__ fb_whole,
-                                                   const float* __restrict__ dct2, const int* __restrict__ owner2, float* __restrict__ out, long long n_samples, int hop,
+                                                   const float* __restrict__ dct2, const int* __restrict__ owner2, float* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop,
                                                    int T, int TP, int tiles, int total_tiles, int n_filters, int n_coefs, int layout) {
+    static_assert(!RAGGED || PCM == 0, "ragged batches: float32 samples");
+    // samples, frames and row pitch of the tile's clip: the kernel's arguments, or (RAGGED) the fields of the tile's record rc -- read where
+    // they are used, as the arguments always were (rg_pick)
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+#define CLIP_T rg_pick<RAGGED>(rc.T, T)
+#define CLIP_TP rg_pick<RAGGED>(rc.TP, TP)
     using C = FftCfg<10, 4>;
     constexpr bool DUAL = MODE == 4, MFCC = MODE == 1 || DUAL, SPECM = MODE == 2 || MODE == 3, SQUARES = MODE == 1 || MODE == 3 || DUAL;
     // (DUAL: frame buffers 32 slots shorter -- still 2 mod 64 floats apart, the exchange area still holds what the asserts below ask for -- : the 4 KB
@@ -650,14 +658,16 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
         tlv = min(tlv, total_tiles - 1);
         const int p = row_pair_index(lane);
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, tile = tl % tiles;
+        [[maybe_unused]] RgClip rc;
+        if constexpr (RAGGED) rc = rg_clip(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, tile = RAGGED ? tl - rc.first_tile : tl % tiles;
         const int t = tile * FPB + wave;
         const long long s0 = (long long)t * hop - N;
         if constexpr (PCM == 1) {
             // int16 mono: a point (two samples) is one dword; xr[2 i] = the dwords of the points n, n + 1 of load i (xr[2 i + 1] is not used)
-            const short* xc = reinterpret_cast<const short*>(x) + (long long)clip * n_samples;
-            if (ALIGNED && t < T && s0 >= 0 && s0 + W <= n_samples) {   // interior frame (uniform)
-                frx = make_rsrc(xc, (unsigned)std::min<long long>(n_samples * 2, 0xfffffffcLL));
+            const short* xc = reinterpret_cast<const short*>(x) + (long long)clip * CLIP_N;
+            if (ALIGNED && t < CLIP_T && s0 >= 0 && s0 + W <= CLIP_N) {   // interior frame (uniform)
+                frx = make_rsrc(xc, (unsigned)std::min<long long>(CLIP_N * 2, 0xfffffffcLL));
                 const int fvoff = ((int)s0 + 2 * (p & ~1)) * 2 + (p & 1) * (E / 2 * P * 4);
 #pragma unroll
                 for (int i = 0; i < E / 2; ++i) xr[2 * i] = buf_load_f32x2(frx, fvoff, i * P * 4);
@@ -667,17 +677,17 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
 #pragma unroll
             for (int i = 0; i < E; ++i) {   // a frame that touches the clip's ends: sample by sample, packed the way the loads deliver them
                 const long long s = s0 + 2 * (nb + (i >> 1) * P + (i & 1));
-                const unsigned lo = (t < T && s >= 0 && s < n_samples) ? (unsigned short)xc[s] : 0u;
-                const unsigned hi = (t < T && s + 1 >= 0 && s + 1 < n_samples) ? (unsigned short)xc[s + 1] : 0u;
+                const unsigned lo = (t < CLIP_T && s >= 0 && s < CLIP_N) ? (unsigned short)xc[s] : 0u;
+                const unsigned hi = (t < CLIP_T && s + 1 >= 0 && s + 1 < CLIP_N) ? (unsigned short)xc[s + 1] : 0u;
                 const float bits = __builtin_bit_cast(float, lo | hi << 16);
                 if (i & 1) xr[i - 1].y = bits;
                 else xr[i].x = bits;
             }
             return;
         }
-        const float* xc = x + (long long)clip * n_samples;   // (PCM == 2: a "sample" is one frame of two int16, moved as the 4 bytes it is)
-        if (ALIGNED && t < T && s0 >= 0 && s0 + W <= n_samples) {   // interior frame (uniform)
-            frx = make_rsrc(xc, (unsigned)std::min<long long>(n_samples * 4, 0xfffffffcLL));
+        const float* xc = x + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);   // (PCM == 2: a "sample" is one frame of two int16, moved as the 4 bytes it is)
+        if (ALIGNED && t < CLIP_T && s0 >= 0 && s0 + W <= CLIP_N) {   // interior frame (uniform)
+            frx = make_rsrc(xc, (unsigned)std::min<long long>(CLIP_N * 4, 0xfffffffcLL));
             const int fvoff = ((int)s0 + 2 * (p & ~1)) * 4 + (p & 1) * (E / 2 * P * 8);
 #pragma unroll
             for (int i = 0; i < E / 2; ++i) {
@@ -691,8 +701,8 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
 #pragma unroll
         for (int i = 0; i < E; ++i) {   // a frame that touches the clip's ends or lies past its last frame: zero padding (zaf.py:112-125)
             const long long s = s0 + 2 * (nb + (i >> 1) * P + (i & 1));
-            xr[i].x = (t < T && s >= 0 && s < n_samples) ? xc[s] : 0.f;
-            xr[i].y = (t < T && s + 1 >= 0 && s + 1 < n_samples) ? xc[s + 1] : 0.f;
+            xr[i].x = (t < CLIP_T && s >= 0 && s < CLIP_N) ? xc[s] : 0.f;
+            xr[i].y = (t < CLIP_T && s + 1 >= 0 && s + 1 < CLIP_N) ? xc[s + 1] : 0.f;
         }
     };
     // ---- transform of the requested frame; returns 4 |X|^2 (the filterbank carries the 1/2 of |X|) of the bins k = lane + 64 i (mk) and N - k (mn)
@@ -824,17 +834,19 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
     // (SPECM) rows 0 .. N of the tile whose levels are in LDS (2 |X| / 4 |X|^2).  Rows of whole 16-byte pieces (pitch % 4 = 0, base aligned; 8-byte
     // pieces for the other even pitches): thread = four frames (tid & 3) x rows (tid >> 2) + 256 j, one 16-byte store per row -- 5 vector-memory instructions per thread and
     // tile instead of 17 four-byte ones (the youngest waves waited 5.5 k cycles at the store queue).  Else thread = frame x rows, 4 bytes.
-    const int rowv = !SPECM ? 1 : (TP % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0) ? 4 : (TP % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) ? 2 : 1;   // frames per lane and store
+    const int rowv = !SPECM ? 1 : RAGGED ? 4 : (TP % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0) ? 4 : (TP % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) ? 2 : 1;   // frames per lane and store
     auto store_rows = [&](int tlv) {
         int to = tid;
         asm volatile("" : "+v"(to));
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t0 = (tl % tiles) * FPB;
+        [[maybe_unused]] RgClip rc;
+        if constexpr (RAGGED) rc = rg_clip(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, t0 = (RAGGED ? tl - rc.first_tile : tl % tiles) * FPB;
         const float sc = SQUARES ? 0.25f : 0.5f;
-        if (rowv == 4 && t0 + FPB <= T) {   // (uniform) a whole tile, 16-byte pieces
+        if (rowv == 4 && t0 + FPB <= CLIP_T) {   // (uniform) a whole tile, 16-byte pieces
             const int tq = to & 3, kq = to >> 2;
             const float* sf = fall + (size_t)(4 * tq) * (2 * PITCH);
-            float* o = out + (long long)clip * (N + 1) * TP + t0 + 4 * tq;
+            float* o = out + (RAGGED ? rc.out_off : (long long)clip * (N + 1) * CLIP_TP) + t0 + 4 * tq;
             float4 v[5];
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
@@ -843,14 +855,14 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                *reinterpret_cast<float4*>(o + (long long)(kq + 256 * j) * TP) = make_float4(sc * v[j].x, sc * v[j].y, sc * v[j].z, sc * v[j].w);
-            if (kq == 0) *reinterpret_cast<float4*>(o + (long long)N * TP) = make_float4(sc * v[4].x, sc * v[4].y, sc * v[4].z, sc * v[4].w);
+                *reinterpret_cast<float4*>(o + (long long)(kq + 256 * j) * CLIP_TP) = make_float4(sc * v[j].x, sc * v[j].y, sc * v[j].z, sc * v[j].w);
+            if (kq == 0) *reinterpret_cast<float4*>(o + (long long)N * CLIP_TP) = make_float4(sc * v[4].x, sc * v[4].y, sc * v[4].z, sc * v[4].w);
             return;
         }
-        if (rowv == 2 && t0 + FPB <= T) {   // (uniform) a whole tile, 8-byte pieces (an even pitch that is not a multiple of 4)
+        if (rowv == 2 && t0 + FPB <= CLIP_T) {   // (uniform) a whole tile, 8-byte pieces (an even pitch that is not a multiple of 4)
             const int tq = to & 7, kq = to >> 3;
             const float* sf = fall + (size_t)(2 * tq) * (2 * PITCH);
-            float* o = out + (long long)clip * (N + 1) * TP + t0 + 2 * tq;
+            float* o = out + (RAGGED ? rc.out_off : (long long)clip * (N + 1) * CLIP_TP) + t0 + 2 * tq;
             float2 v[9];
 #pragma unroll
             for (int j = 0; j < 9; ++j) {
@@ -858,21 +870,21 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
                 v[j] = make_float2(sf[at], sf[at + 2 * PITCH]);
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) *reinterpret_cast<float2*>(o + (long long)(kq + 128 * j) * TP) = make_float2(sc * v[j].x, sc * v[j].y);
-            if (kq == 0) *reinterpret_cast<float2*>(o + (long long)N * TP) = make_float2(sc * v[8].x, sc * v[8].y);
+            for (int j = 0; j < 8; ++j) *reinterpret_cast<float2*>(o + (long long)(kq + 128 * j) * CLIP_TP) = make_float2(sc * v[j].x, sc * v[j].y);
+            if (kq == 0) *reinterpret_cast<float2*>(o + (long long)N * CLIP_TP) = make_float2(sc * v[8].x, sc * v[8].y);
             return;
         }
         const int t = t0 + (to & 15), kq = to >> 4;
-        if (t >= T) return;
+        if (t >= CLIP_T) return;
         const float* sf = fall + (size_t)(to & 15) * (2 * PITCH);
-        float* o = out + (long long)clip * (N + 1) * TP + t;
+        float* o = out + (RAGGED ? rc.out_off : (long long)clip * (N + 1) * CLIP_TP) + t;
         float v[E + 1];
 #pragma unroll
         for (int j = 0; j < E; ++j) v[j] = sf[kq + 64 * j == 0 ? DCSLOT : kq + 64 * j - 1];
         v[E] = sf[N - 1];
 #pragma unroll
-        for (int j = 0; j < E; ++j) o[(long long)(kq + 64 * j) * TP] = sc * v[j];
-        if (kq == 0) o[(long long)N * TP] = sc * v[E];
+        for (int j = 0; j < E; ++j) o[(long long)(kq + 64 * j) * CLIP_TP] = sc * v[j];
+        if (kq == 0) o[(long long)N * CLIP_TP] = sc * v[E];
     };
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     f32x4v acc[2][2];
@@ -997,7 +1009,9 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
         if constexpr (!MFCC && !ZAFX_MEL2_EARLYOUT) lds_barrier();   // the next tile's levels and the partial tiles are in LDS
         PROF_MARK(5);
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t0 = (tl % tiles) * FPB;
+        [[maybe_unused]] RgClip rc;
+        if constexpr (RAGGED) rc = rg_clip(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, t0 = (RAGGED ? tl - rc.first_tile : tl % tiles) * FPB;
         float* exf = reinterpret_cast<float*>(frames + wave * PITCH + EXOFF);   // (MFCC) this wave's exchange area: free until the barrier that ends the tile
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -1022,8 +1036,9 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
                     for (int h = 0; h < kMel2Slots; ++h)
                         if (mask & (1 << h)) vm += xpart[(kMel2Slots + h) * 256 + e];
                     const int m = 16 * blk + 4 * (lane >> 4) + r;
-                    if (m < n_filters && t < T) {
-                        if (layout == ZAFX_LAYOUT_FT) out[((long long)clip * rows + m) * TP + t] = vm;
+                    if (m < n_filters && t < CLIP_T) {
+                        if constexpr (RAGGED) out[rc.out_off + (long long)m * rc.TP + t] = vm;   // (reference layout only)
+                        else if (layout == ZAFX_LAYOUT_FT) out[((long long)clip * rows + m) * TP + t] = vm;
                         else out[((long long)clip * T + t) * rows + m] = vm;
                     }
                 }
@@ -1049,8 +1064,9 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = 16 * blk + 4 * (lane >> 4) + r;
-                    if (m < n_filters && t < T) {
-                        if (layout == ZAFX_LAYOUT_FT) out[((long long)clip * n_filters + m) * TP + t] = val[r];
+                    if (m < n_filters && t < CLIP_T) {
+                        if constexpr (RAGGED) out[rc.out_off + (long long)m * rc.TP + t] = val[r];
+                        else if (layout == ZAFX_LAYOUT_FT) out[((long long)clip * n_filters + m) * TP + t] = val[r];
                         else out[((long long)clip * T + t) * n_filters + m] = val[r];
                     }
                 }
@@ -1070,9 +1086,10 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
                 float sum = 0.f;
 #pragma unroll
                 for (int bb = 0; bb < 8; ++bb) sum += part[bb];   // (block order: deterministic)
-                if (t < T) {
+                if (t < CLIP_T) {
                     const int rows = DUAL ? n_filters + n_coefs : n_coefs, row = DUAL ? n_filters + q : q;
-                    if (layout == ZAFX_LAYOUT_FT) out[((long long)clip * rows + row) * TP + t] = sum;
+                    if constexpr (RAGGED) out[rc.out_off + (long long)row * rc.TP + t] = sum;
+                    else if (layout == ZAFX_LAYOUT_FT) out[((long long)clip * rows + row) * TP + t] = sum;
                     else out[((long long)clip * T + t) * rows + row] = sum;
                 }
             }
@@ -1082,6 +1099,9 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
     for (; tlv + (int)gridDim.x < total_tiles; tlv += gridDim.x) tile_body(std::true_type{});
     tile_body(std::false_type{});
 }
+#undef CLIP_N
+#undef CLIP_T
+#undef CLIP_TP
 
 template <int LOG2N, bool ALIGNED>
 static hipError_t run_mel(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
@@ -1186,6 +1206,52 @@ bool pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sa
     if (pl.kind == ZAFX_STFT)
         return ZAFX_SPEC2 && pl.layout == ZAFX_LAYOUT_FT && (pl.prm.spectrum == ZAFX_SPECTRUM_MAGNITUDE || pl.prm.spectrum == ZAFX_SPECTRUM_POWER);
     return false;
+}
+
+// ---------------------------------------------------------------------------------
+// zafx_execute_ragged on k_mel2 (RAGGED form): mel / mfcc / the one-pass form of the geometries run_mel sends to k_mel2, and |X| / |X|^2 of an
+// STFT plan at W = 2048 (MODE 2 / 3, what launch_spec2 takes).  Float32, reference layout; the caller checked that every clip's rows are whole
+// 128-byte lines and that the clips are below 2^29 samples (the aligned form's 32-bit offsets inside a clip's buffer descriptor).
+// ---------------------------------------------------------------------------------
+bool spec2_ragged(const zafx_plan& pl) {
+    return ZAFX_SPEC2 && pl.kind == ZAFX_STFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.log2nf == 10 && pl.log2e == 4 &&
+           pl.layout == ZAFX_LAYOUT_FT && kMelFpb == 16 && kMelThreads == 1024 && pl.d_tw_pass && pl.d_tw_aux &&
+           (pl.prm.spectrum == ZAFX_SPECTRUM_MAGNITUDE || pl.prm.spectrum == ZAFX_SPECTRUM_POWER);
+}
+
+bool mel_ragged_native(const zafx_plan& pl) {
+    if (pl.kind == ZAFX_STFT) return spec2_ragged(pl);
+    if (pl.kind != ZAFX_MEL && pl.kind != ZAFX_MFCC) return false;
+    if (!ZAFX_MEL2 || pl.prm.precision != ZAFX_PRECISION_F32 || pl.bs_log2m > 0 || pl.layout != ZAFX_LAYOUT_FT || mel_takes_wide_route(pl)) return false;
+    if (pl.log2nf != 10 || pl.log2e != 4 || kMelFpb != 16 || kMelThreads != 1024) return false;
+    return pl.fb.whole_ok && pl.fb.n_waves == 16 && (pl.kind == ZAFX_MEL || pl.dct.dct2_ok);
+}
+
+template <bool ALIGNED>
+static auto mel2_ragged_kernel(int mode) {
+    switch (mode) {
+        case 1: return k_mel2<ALIGNED, 1, 0, true>;
+        case 2: return k_mel2<ALIGNED, 2, 0, true>;
+        case 3: return k_mel2<ALIGNED, 3, 0, true>;
+        case 4: return k_mel2<false, 4, 0, true>;   // (the aligned one-pass form spills to scratch -- as its equal-length twin does --, this one does not)
+        default: return k_mel2<ALIGNED, 0, 0, true>;
+    }
+}
+
+hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
+    using C = FftCfg<10, 4>;
+    const bool spec = pl.kind == ZAFX_STFT, mfcc = pl.kind == ZAFX_MFCC, dual = mfcc && pl.prm.with_mel;
+    const int mode = spec ? (pl.prm.spectrum == ZAFX_SPECTRUM_POWER ? 3 : 2) : dual ? 4 : mfcc ? 1 : 0;
+    auto k2 = aligned ? mel2_ragged_kernel<true>(mode) : mel2_ragged_kernel<false>(mode);
+    const size_t smem = (size_t)(16 * (dual ? kMel2DualPitch : C::PITCH) + C::TW + C::N + C::N / 2 + 1) * 8 + (dual ? 2 : 1) * kMel2Slots * 1024;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k2), pl.device, smem); e != hipSuccess) return e;
+    if (total_tiles <= 0) return hipSuccess;
+    const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus);
+    pl.ran = "k_mel2_ragged";
+    hipLaunchKernelGGL(k2, dim3((unsigned)grid), dim3(1024), smem, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, spec ? nullptr : pl.fb.d_pack,
+                       spec ? nullptr : pl.fb.d_whole, spec ? nullptr : pl.dct.d_dct2, spec ? nullptr : pl.dct.d_owner2, out, tab, pl.H, 0, 0, (int)n_clips,
+                       (int)total_tiles, spec ? 0 : pl.prm.n_filters, mfcc ? pl.prm.n_coefs : 0, (int)ZAFX_LAYOUT_FT);
+    return hipGetLastError();
 }
 
 const char* mel_kernel_name() { return "k_mel"; }

@@ -223,11 +223,20 @@ struct PcmPoint {
 #ifndef ZAFX_STFT_FAT_OPAQUE
 #define ZAFX_STFT_FAT_OPAQUE(log2n, spec) ((log2n) == 8 || ((log2n) == 9 && (spec) <= 1))
 #endif
-template <int LOG2N, int LOG2E, bool ALIGNED, int SPEC, int FPB_ = kFatFrames, int PCM = 0>
+// RAGGED (zafx_execute_ragged): clips of different lengths.  `n_samples` carries the batch's table and `tiles` the number of clips
+// (SamplesArg, zafx_internal.hpp); a tile's clip, its samples, frames, row pitch and the bases of its input and output come from its
+// record, and everything else -- the fast / edge decision, the zero padding, the XCD order, the store phase -- is the same code.
+template <int LOG2N, int LOG2E, bool ALIGNED, int SPEC, int FPB_ = kFatFrames, int PCM = 0, bool RAGGED = false>
 __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     const float* __restrict__ x, const float* __restrict__ win, const float2* __restrict__ twp,
-    const float2* __restrict__ tws, float2* __restrict__ out, long long n_samples, int hop, int T, int TP, int tiles,
+    const float2* __restrict__ tws, float2* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop, int T, int TP, int tiles,
     int total_tiles) {
+    static_assert(!RAGGED || (PCM == 0 && FPB_ == kFatFrames), "ragged batches: float32 samples, 16-frame tiles");
+    // samples, frames and row pitch of the tile's clip: the kernel's arguments, or (RAGGED) the fields of the tile's record rc -- read where
+    // they are used, as the arguments always were (rg_pick)
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+#define CLIP_T rg_pick<RAGGED>(rc.T, T)
+#define CLIP_TP rg_pick<RAGGED>(rc.TP, TP)
     using C = FftCfg<LOG2N, LOG2E>;
     using F = FatCfg<LOG2N, LOG2E, FPB_>;
     constexpr int N = C::N, P = C::P, E = C::E, W = 2 * N, NT = F::NT, FPB = F::FPB, FPW = F::FPW, PITCH = F::PITCH;
@@ -253,7 +262,7 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     const int wave = tid / P, p_lane = tid % P, p = p_lane;
     const int tt = tid % FPB, kq = tid / FPB;
     const float2* fb = frames + tt * PITCH;
-    const bool lines_whole = TP % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 128 == 0;
+    const bool lines_whole = (RAGGED || TP % 16 == 0) && reinterpret_cast<uintptr_t>(out) % 128 == 0;   // (RAGGED: the launcher admits whole-line rows only)
 
     typename PP::T xr[FPW][E];
     // The fast / edge decision is taken once per TILE (block-uniform): a tile whose 16 frames all lie
@@ -266,13 +275,15 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
         int p = p_lane;   // (opaque at 32 points per thread: the 64-bit sample offsets of the edge path are recomputed, not hoisted)
         if constexpr (E >= 32 || ZAFX_STFT_FAT_OPAQUE(LOG2N, SPEC)) asm volatile("" : "+v"(p));
-        const int clip = tl / tiles, tile = tl % tiles;
-        const float* xc = x + (long long)clip * n_samples;   // (PCM 2: a "sample" is one 4-byte frame of two int16)
+        [[maybe_unused]] RgClip rc;
+        if constexpr (RAGGED) rc = rg_clip(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, tile = RAGGED ? tl - rc.first_tile : tl % tiles;
+        const float* xc = x + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);   // (PCM 2: a "sample" is one 4-byte frame of two int16)
         const long long first = (long long)tile * FPB * hop - N;               // first sample of the tile
         const long long last = first + (long long)(FPB - 1) * hop + W;          // one past its last sample
         if constexpr (PCM == 1) {   // int16 mono: a point is 4 bytes
-            const short* xs = reinterpret_cast<const short*>(x) + (long long)clip * n_samples;
-            if (ALIGNED && first >= 0 && last <= n_samples && tile * FPB + FPB <= T) {
+            const short* xs = reinterpret_cast<const short*>(x) + (long long)clip * CLIP_N;
+            if (ALIGNED && first >= 0 && last <= CLIP_N && tile * FPB + FPB <= CLIP_T) {
                 const short* src = xs + first + (long long)(wave * FPW) * hop + 2 * p;
 #pragma unroll
                 for (int f = 0; f < FPW; ++f) {
@@ -287,13 +298,13 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
 #pragma unroll
                     for (int i = 0; i < E; ++i) {
                         const long long s = s0 + 2 * (p + i * P);
-                        const unsigned lo = (t < T && s >= 0 && s < n_samples) ? (unsigned short)xs[s] : 0u;
-                        const unsigned hi = (t < T && s + 1 >= 0 && s + 1 < n_samples) ? (unsigned short)xs[s + 1] : 0u;
+                        const unsigned lo = (t < CLIP_T && s >= 0 && s < CLIP_N) ? (unsigned short)xs[s] : 0u;
+                        const unsigned hi = (t < CLIP_T && s + 1 >= 0 && s + 1 < CLIP_N) ? (unsigned short)xs[s + 1] : 0u;
                         xr[f][i] = __builtin_bit_cast(float, lo | hi << 16);
                     }
                 }
             }
-        } else if (ALIGNED && first >= 0 && last <= n_samples && tile * FPB + FPB <= T) {
+        } else if (ALIGNED && first >= 0 && last <= CLIP_N && tile * FPB + FPB <= CLIP_T) {
             const float* src = xc + first + (long long)(wave * FPW) * hop + 2 * p;
 #pragma unroll
             for (int f = 0; f < FPW; ++f) {
@@ -308,8 +319,8 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
 #pragma unroll
                 for (int i = 0; i < E; ++i) {
                     const long long s = s0 + 2 * (p + i * P);
-                    xr[f][i].x = (t < T && s >= 0 && s < n_samples) ? xc[s] : 0.f;
-                    xr[f][i].y = (t < T && s + 1 >= 0 && s + 1 < n_samples) ? xc[s + 1] : 0.f;
+                    xr[f][i].x = (t < CLIP_T && s >= 0 && s < CLIP_N) ? xc[s] : 0.f;
+                    xr[f][i].y = (t < CLIP_T && s + 1 >= 0 && s + 1 < CLIP_N) ? xc[s + 1] : 0.f;
                 }
             }
         }
@@ -319,7 +330,9 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     PROF_INIT(g_prof_stft);
     for (; tlv < total_tiles; tlv += gridDim.x) {
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, tile = tl % tiles;
+        [[maybe_unused]] RgClip rc;
+        if constexpr (RAGGED) rc = rg_clip(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, tile = RAGGED ? tl - rc.first_tile : tl % tiles;
         const int t0 = tile * FPB;
         PROF_MARK(0);
         int po = p;   // opaque copy: window and twiddle reads are not hoisted out of the tile loop (at 32 points per
@@ -349,8 +362,8 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         PROF_MARK(2);
         if (!ZAFX_STFT_EARLY) prefetch(tlv + gridDim.x);   // in flight while this tile is stored
         PROF_MARK(3);
-        if (t0 + tt < T) {
-            float2* o = spec_base<SPEC>(out, (long long)clip * ROWS * TP + (t0 + tt));
+        if (t0 + tt < CLIP_T) {
+            float2* o = spec_base<SPEC>(out, (RAGGED ? rc.out_off : (long long)clip * ROWS * TP) + (t0 + tt));
             int kqo = kq;   // (opaque at 32 points per thread: the split roots of the 16 iterations are not carried across tiles)
             if constexpr (E >= 32 || ZAFX_STFT_FAT_OPAQUE(LOG2N, SPEC)) asm volatile("" : "+v"(kqo));
             auto store_tile = [&](auto stream) {
@@ -372,16 +385,16 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
                     if (k == 0) {
                         const float2 z0 = fb[0], zc = fb[phys_t<C::PS>(N / 2)];
                         put_bin<SPEC, ST>(o, 0, make_float2(z0.x + z0.y, 0.f));
-                        put_bin<SPEC, ST>(o, (long long)N * TP, make_float2(z0.x - z0.y, 0.f));
-                        put_bin<SPEC, ST>(o, (long long)(N / 2) * TP, cconj(zc));
-                        if (SPEC == 0) put_bin<SPEC, ST>(o, (long long)(N + N / 2) * TP, zc);
+                        put_bin<SPEC, ST>(o, (long long)N * CLIP_TP, make_float2(z0.x - z0.y, 0.f));
+                        put_bin<SPEC, ST>(o, (long long)(N / 2) * CLIP_TP, cconj(zc));
+                        if (SPEC == 0) put_bin<SPEC, ST>(o, (long long)(N + N / 2) * CLIP_TP, zc);
                     } else {
                         float2 xk, xn;
                         split_pair(fb[phys_t<C::PS>(k)], fb[phys_t<C::PS>(N - k)], tws_l[k], xk, xn);
-                        put_bin<SPEC, ST>(o, (long long)k * TP, xk);
-                        if (SPEC == 0) put_bin<SPEC, ST>(o, (long long)(W - k) * TP, cconj(xk));
-                        put_bin<SPEC, ST>(o, (long long)(N - k) * TP, xn);
-                        if (SPEC == 0) put_bin<SPEC, ST>(o, (long long)(N + k) * TP, cconj(xn));
+                        put_bin<SPEC, ST>(o, (long long)k * CLIP_TP, xk);
+                        if (SPEC == 0) put_bin<SPEC, ST>(o, (long long)(W - k) * CLIP_TP, cconj(xk));
+                        put_bin<SPEC, ST>(o, (long long)(N - k) * CLIP_TP, xn);
+                        if (SPEC == 0) put_bin<SPEC, ST>(o, (long long)(N + k) * CLIP_TP, cconj(xn));
                     }
                 }
             };
@@ -397,6 +410,9 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         lds_barrier();   // LDS reads of the tile are done; its global stores are NOT waited for
     }
 }
+#undef CLIP_N
+#undef CLIP_T
+#undef CLIP_TP
 
 // ---------------------------------------------------------------------------------
 // forward, reference layout, rows that are NOT whole 128-byte lines (T % 16 != 0): k_stft_ft16 with a register carry
@@ -3322,6 +3338,54 @@ hipError_t launch_stft(const zafx_plan& pl, const float* x, float2* out, int64_t
     case L: return dispatch_stft<L>(pl, x, out, n_clips, n_samples, T);
         ZAFX_STFT_SIZES(X)
 #undef X
+    }
+    return hipErrorInvalidValue;
+}
+
+// zafx_execute_ragged: clips of different lengths on k_stft_ft16's RAGGED form, W = 256 ... 2048 in the reference layout, float32, every
+// clip's rows whole 128-byte lines (the caller checked).  W = 1024 two-sided runs here too, where the equal-length path prefers the carry
+// form k_stft_ft16c; |X| / |X|^2 at W = 2048 go to k_mel2 as they do there (launch_mel_ragged).
+bool stft_ragged_native(const zafx_plan& pl) {
+    if (spec2_ragged(pl)) return true;
+    return pl.kind == ZAFX_STFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.layout == ZAFX_LAYOUT_FT && pl.log2nf >= 7 &&
+           pl.log2nf <= 10 && pl.d_tw_pass && pl.d_tw_aux && (pl.log2nf != 10 || !ZAFX_STFT_R32 || pl.d_tw_r32);
+}
+
+template <int LOG2N, bool ALIGNED, int SPEC>
+static hipError_t run_stft_fat_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* tab, int64_t n_clips, long long total_tiles) {
+    constexpr int LOG2E = (ZAFX_STFT_R32 && LOG2N == 10) ? 5 : default_log2e(LOG2N);   // (as run_stft_fat)
+    using F = FatCfg<LOG2N, LOG2E>;
+    auto kern = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, kFatFrames, 0, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, F::SMEM); e != hipSuccess) return e;
+    if (total_tiles <= 0) return hipSuccess;
+    const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
+    const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus * std::max(per_cu, 1));
+    pl.ran = "k_stft_ft16_ragged";
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F::NT), F::SMEM, pl.stream, x, pl.d_window, LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass,
+                       pl.d_tw_aux, out, tab, pl.H, 0, 0, (int)n_clips, (int)total_tiles);
+    return hipGetLastError();
+}
+
+template <int L>
+static hipError_t dispatch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
+#define ZAFX_RAGGED_SPEC(S) \
+    return aligned ? run_stft_fat_ragged<L, true, S>(pl, x, out, tab, n_clips, total_tiles) : run_stft_fat_ragged<L, false, S>(pl, x, out, tab, n_clips, total_tiles)
+    switch (pl.prm.spectrum) {
+        case ZAFX_SPECTRUM_ONE_SIDED: ZAFX_RAGGED_SPEC(1);
+        case ZAFX_SPECTRUM_MAGNITUDE: ZAFX_RAGGED_SPEC(2);
+        case ZAFX_SPECTRUM_POWER: ZAFX_RAGGED_SPEC(3);
+        default: ZAFX_RAGGED_SPEC(0);
+    }
+#undef ZAFX_RAGGED_SPEC
+}
+
+hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
+    if (spec2_ragged(pl)) return launch_mel_ragged(pl, x, reinterpret_cast<float*>(out), tab, n_clips, total_tiles, aligned);
+    switch (pl.log2nf) {
+        case 7: return dispatch_stft_ragged<7>(pl, x, out, tab, n_clips, total_tiles, aligned);
+        case 8: return dispatch_stft_ragged<8>(pl, x, out, tab, n_clips, total_tiles, aligned);
+        case 9: return dispatch_stft_ragged<9>(pl, x, out, tab, n_clips, total_tiles, aligned);
+        case 10: return dispatch_stft_ragged<10>(pl, x, out, tab, n_clips, total_tiles, aligned);
     }
     return hipErrorInvalidValue;
 }

@@ -20,6 +20,20 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def _i64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _as_lengths(values, name="lengths"):
+    a = np.asarray(values)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError(f"{name} must be a 1-D sequence of integers")
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if a.size and int(a.min()) < 0:
+        raise ValueError(f"{name} must not be negative")
+    return a
+
+
 # ======================================================================================
 # device memory
 # ======================================================================================
@@ -376,6 +390,36 @@ class Plan:
     def execute(self, d_in, d_out, n_clips, n_in):
         """Enqueue on the plan's stream (asynchronous); d_in / d_out are DeviceBuffers."""
         _lib.check(_lib.load().zafx_execute(self.handle, d_in.ptr, d_out.ptr, int(n_clips), int(n_in)), "zafx_execute")
+
+    def ragged_layout(self, lengths):
+        """Placement of a ragged batch's results (zafx_plan_ragged_layout) for clips of `lengths` samples: -> (out_offsets, frames, pitch), int64
+        arrays.  Clip i's block of the output array starts at element out_offsets[i] (out_offsets[-1]: elements in all) and holds F rows of
+        pitch[i] elements ("FT"; frames[i] of them are the clip's) or frames[i] x F compact ("TF")."""
+        lengths = _as_lengths(lengths)
+        offs = np.zeros(len(lengths) + 1, np.int64)
+        _lib.check(_lib.load().zafx_plan_ragged_layout(self.handle, _i64p(lengths), len(lengths), _i64p(offs)), "zafx_plan_ragged_layout")
+        frames = np.array([self.out_dims(n)[1] for n in lengths.tolist()], np.int64)
+        pitch = np.array([self.row_pitch(n) for n in lengths.tolist()], np.int64)
+        return offs, frames, pitch
+
+    def execute_ragged(self, d_in, in_offsets, lengths, d_out):
+        """Enqueue one ragged batch on the plan's stream (asynchronous; zafx_execute_ragged): clip i is lengths[i] samples at element in_offsets[i]
+        of d_in, its result goes to the block ragged_layout(lengths) assigns in d_out.  Float32 plans in the "FT" layout whose rows are whole
+        128-byte lines run as one launch where the library has the kernel (last_kernel: k_stft_ft16_ragged / k_mel2_ragged); the others as one
+        execute per clip ("per-clip <kernel>")."""
+        lengths, in_offsets = _as_lengths(lengths), _as_lengths(in_offsets, "in_offsets")
+        if len(in_offsets) != len(lengths):
+            raise ValueError("in_offsets and lengths must have one entry per clip")
+        if d_in.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
+            raise ValueError(f"execute_ragged takes {self.in_dtype} samples and a {self.out_dtype} output buffer")
+        if len(lengths) and int((in_offsets + lengths).max()) > d_in.nbytes // d_in.dtype.itemsize:
+            raise ValueError("a clip reaches past the end of d_in")
+        offs = np.zeros(len(lengths) + 1, np.int64)
+        _lib.check(_lib.load().zafx_plan_ragged_layout(self.handle, _i64p(lengths), len(lengths), _i64p(offs)), "zafx_plan_ragged_layout")
+        if int(offs[-1]) * self.out_dtype.itemsize > d_out.nbytes:
+            raise ValueError("d_out is smaller than the ragged batch's output (ragged_layout)")
+        _lib.check(_lib.load().zafx_execute_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, len(lengths)),
+                   "zafx_execute_ragged")
 
     def sync(self):
         _lib.check(_lib.load().zafx_sync(self.handle), "zafx_sync")
@@ -1035,6 +1079,124 @@ def mel_mfcc_pcm_batch(pcm, window_function, step_length, mel_filterbank, number
     plan = mel_plan(w, step_length, mel_filterbank, number_coefficients, layout, device, also_mel=True)
     return _split_mel_mfcc(plan.run_host_pcm(pcm, out=out), n_filters, layout)
 
+
+# ======================================================================================
+# ragged batches: clips of different lengths in one call (zafx_execute_ragged)
+# ======================================================================================
+_RAGGED_ALIGN = 32   # elements between clip starts in a packed batch: 128 bytes of float32
+
+
+def _as_ragged(clips):
+    """A ragged batch -- a sequence of 1-D real arrays -- validated ahead of any device call."""
+    if isinstance(clips, np.ndarray) and clips.dtype != object and clips.ndim < 2:
+        raise ValueError("a ragged batch is a sequence of 1-D clips, not one array")
+    try:
+        items = list(clips)
+    except TypeError:
+        raise ValueError("a ragged batch is a sequence of 1-D clips") from None
+    if not items:
+        raise ValueError("a ragged batch needs at least one clip")
+    out = []
+    for i, c in enumerate(items):
+        a = np.asarray(c)
+        if a.ndim != 1:
+            raise ValueError(f"clip {i} of the ragged batch must be 1-D, got {a.ndim}-D")
+        if np.iscomplexobj(a) or a.dtype.kind not in "biuf":
+            raise ValueError(f"clip {i} of the ragged batch must be real")
+        out.append(a)
+    return out
+
+
+def pack_ragged(clips, dtype=np.float32):
+    """One contiguous array of a ragged batch: -> (packed, in_offsets, lengths).  Clip i starts at element in_offsets[i], a multiple of 32
+    elements (128 bytes of float32), and the gaps between the clips are zeros -- so that the kernels' aligned loads apply whenever the hop is
+    even (zafx_execute_ragged)."""
+    arrays = _as_ragged(clips)
+    lengths = np.array([len(a) for a in arrays], np.int64)
+    slots = (lengths + _RAGGED_ALIGN - 1) // _RAGGED_ALIGN * _RAGGED_ALIGN
+    offsets = np.zeros(len(arrays), np.int64)
+    offsets[1:] = np.cumsum(slots)[:-1]
+    packed = np.zeros(max(int(slots.sum()), _RAGGED_ALIGN), dtype)
+    for a, o in zip(arrays, offsets.tolist()):
+        packed[o:o + len(a)] = a
+    return packed, offsets, lengths
+
+
+def _run_ragged(plan, clips):
+    """One ragged batch through `plan`: one upload, one execute_ragged, one download.  -> list of per-clip views of the one result buffer,
+    (F, T_i) for the "FT" layout (rows at the plan's pitch), (T_i, F) for "TF"."""
+    x, in_offsets, lengths = pack_ragged(clips, plan.in_dtype)
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    rows = plan.out_dims(0)[0]
+    d_in = DeviceBuffer(x.shape, x.dtype, plan.device).upload(x)
+    d_out = DeviceBuffer((max(int(offs[-1]), 1),), plan.out_dtype, plan.device)
+    try:
+        with plan.lock:
+            plan.execute_ragged(d_in, in_offsets, lengths, d_out)
+            plan.sync()
+            res = d_out.download()
+    finally:
+        d_in.free()
+        d_out.free()
+    if plan.layout == _lib.LAYOUT_FT:
+        return [res[o:o + rows * p].reshape(rows, p)[:, :t] for o, t, p in zip(offs.tolist(), frames.tolist(), pitch.tolist())]
+    return [res[o:o + t * rows].reshape(t, rows) for o, t in zip(offs.tolist(), frames.tolist())]
+
+
+def _ragged_grid(plan, padded_plan):
+    """The plan of a ragged call in the reference layout: rows padded to whole 128-byte lines (as _line_grid), where the native ragged kernels run."""
+    return padded_plan(_line_elements(plan.out_dtype)) if plan.layout == _lib.LAYOUT_FT else plan
+
+
+def _as_f32_views(views, plan, f64):
+    """A plan the library promoted to float64 (short windows, large filterbanks): the float32 / complex64 result the caller asked for."""
+    if f64 or not plan.f64 or not views:
+        return views
+    return [v.astype(np.complex64 if np.iscomplexobj(v) else np.float32) for v in views]
+
+
+def stft_ragged(clips, window_function, step_length, layout="FT", device=0, onesided=False, f64=False):
+    """stft_batch of clips of different lengths in one call: a sequence of 1-D arrays -> a list of (W, T_i) complex64 arrays ["FT"] or (T_i, W)
+    ["TF"] (rows 0..W/2, or |X| / |X|^2 as float32, with `onesided` as in stft_batch; complex128 / float64 with f64), each clip's frames
+    T_i as zaf.stft gives them for that clip alone.  The arrays are views of one result buffer."""
+    clips = _as_ragged(clips)
+    _spectrum_of(onesided)
+    plan = stft_plan(window_function, step_length, layout, device, onesided, f64)
+    plan = _ragged_grid(plan, lambda a: stft_plan(window_function, step_length, layout, device, onesided, f64, row_align=a))
+    return _as_f32_views(_run_ragged(plan, clips), plan, f64)
+
+
+def melspectrogram_ragged(clips, window_function, step_length, mel_filterbank, layout="FT", device=0, f64=False):
+    """melspectrogram_batch of clips of different lengths: -> a list of (n_filters, T_i) float32 arrays (float64 with f64)."""
+    clips = _as_ragged(clips)
+    plan = mel_plan(window_function, step_length, mel_filterbank, None, layout, device, f64=f64)
+    plan = _ragged_grid(plan, lambda a: mel_plan(window_function, step_length, mel_filterbank, None, layout, device, row_align=a, f64=f64))
+    return _as_f32_views(_run_ragged(plan, clips), plan, f64)
+
+
+def mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_coefficients, layout="FT", device=0, f64=False):
+    """mfcc_batch of clips of different lengths: -> a list of (number_coefficients, T_i) float32 arrays (float64 with f64)."""
+    clips = _as_ragged(clips)
+    plan = mel_plan(window_function, step_length, mel_filterbank, number_coefficients, layout, device, f64=f64)
+    plan = _ragged_grid(plan, lambda a: mel_plan(window_function, step_length, mel_filterbank, number_coefficients, layout, device, row_align=a,
+                                                 f64=f64))
+    return _as_f32_views(_run_ragged(plan, clips), plan, f64)
+
+
+def mel_mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_coefficients, layout="FT", device=0, f64=False):
+    """mel_mfcc_batch of clips of different lengths: -> (list of (n_filters, T_i), list of (number_coefficients, T_i)), from one set of
+    transforms where the one-pass kernel takes the geometry (mel_mfcc_supported), else from the two plans."""
+    clips = _as_ragged(clips)
+    w = _as_window(window_function, any_length=True)
+    n_filters = mel_filterbank.shape[0] if hasattr(mel_filterbank, "shape") else 0
+    if not mel_mfcc_supported(len(w), n_filters, int(number_coefficients), f64):
+        return (melspectrogram_ragged(clips, w, step_length, mel_filterbank, layout, device, f64),
+                mfcc_ragged(clips, w, step_length, mel_filterbank, number_coefficients, layout, device, f64))
+    plan = mel_plan(w, step_length, mel_filterbank, number_coefficients, layout, device, also_mel=True)
+    plan = _ragged_grid(plan, lambda a: mel_plan(w, step_length, mel_filterbank, number_coefficients, layout, device, row_align=a, also_mel=True))
+    both = _run_ragged(plan, clips)
+    ft = plan.layout == _lib.LAYOUT_FT
+    return ([b[:n_filters] if ft else b[:, :n_filters] for b in both], [b[n_filters:] if ft else b[:, n_filters:] for b in both])
 
 def cqtspectrogram_batch(clips, sampling_frequency, time_resolution, cqt_kernel, layout="FT", device=0, f64=False, out=None):
     """(B, N) -> (B, n_bins, T) float32 (float64 arrays and arithmetic with f64)."""
