@@ -22,6 +22,13 @@ Two bounds per output, both written here:
     hold 1e-4), every other signal below 8e-6; in float64 (test_signal_in_float64_mel_mfcc_cqt) all of them hold 1e-10 but the tone on a
     bin (7e-9).  Silence has floor 0: every output must be exactly zero, and the MFCCs of silence, DCT(log(eps)) (zaf.py:444-446), may
     differ from the reference's 1e-14 by the rounding of a float32 dot product over 128 equal levels.
+
+Kernel forms.  The STFT / ISTFT / MDCT / IMDCT checks run in both row padding modes: "compact" (fixture `zafx`) keeps the reference's memory
+order, so a frame count off the 128-byte line grid (T = 4, 71) runs the kernels' off-grid forms (k_stft_ft16c, the carry k_mdct_ft32, ...);
+"auto" (fixture `zafx_padded`, the *_padded twin of each test), the *_batch default and the drop-ins' path, pads such rows to whole lines and
+runs the plain forms (k_stft_ft16, ...).  T = 96 (N_GRID, test_signal_on_the_line_grid) is on the grid in both modes.  After every call the
+kernel that ran is asserted against ROUTES, a table read off the dispatch code.  Mel / MFCC / CQT / chroma, the PCM entry points and the ragged
+calls lay out their own rows whatever the mode is, and run once.
 """
 import json
 import os
@@ -41,15 +48,15 @@ EPS32 = float(np.finfo(np.float32).eps)
 C_FLOOR = 2.0
 C_FLOOR_CQT = 8.0
 N_LONG = 1024 * 69 + 300       # 70 frames: whole 16- / 32-frame tiles, an edge tile and rows off the line grid
+N_GRID = 1024 * 94 + 300       # T = 96 STFT and MDCT frames: rows of whole 128-byte lines (16 complex64, 32 float32 elements) in either mode
 
 _report = {}
 
 
 @pytest.fixture(scope="module")
-def zafx():
+def zafx_lib():
     import zafx as z
     assert z.device_count() >= 1
-    z.set_row_padding("compact")   # (the kernels' compact forms are what test_signal_on_the_other_kernels names; the padded default: test_gpu_parity.py)
     yield z
     z.set_row_padding("auto")
     path = os.environ.get("ZAFX_SIGNALS_REPORT")
@@ -58,8 +65,34 @@ def zafx():
             json.dump(_report, f, indent=1, sort_keys=True)
 
 
+def _in_mode(z, mode):
+    z.set_row_padding(mode)
+    yield z
+    z.set_row_padding("auto")
+
+
+@pytest.fixture
+def zafx(zafx_lib):
+    """Row padding "compact": the reference's memory order -- the kernels' off-grid forms at T = 4 and 71.  (set_row_padding decides the device
+    layout of the STFT / MDCT-family *_batch functions only, core._line_grid; mel / MFCC / CQT / chroma write their own rows, the *_pcm_batch
+    functions run Plan.run_host_pcm on the compact plan and the ragged calls always pad to whole lines, core._ragged_grid: those run once.)"""
+    yield from _in_mode(zafx_lib, "compact")
+
+
+@pytest.fixture
+def zafx_padded(zafx_lib):
+    """Row padding "auto", the *_batch default: rows off the line grid padded to whole lines -- the plain forms."""
+    yield from _in_mode(zafx_lib, "auto")
+
+
+@pytest.fixture(params=["compact", "auto"])
+def zafx_mode(request, zafx_lib):
+    yield from _in_mode(zafx_lib, request.param)
+
+
 @pytest.fixture(scope="module")
-def consts(zafx):
+def consts(zafx_lib):
+    zafx = zafx_lib
     ham, kbd = zafx.hamming(sig.W), zafx.kaiser_bessel_derived(sig.W)
     fb = zafx.melfilterbank(sig.FS, sig.W, 128)
     ck = zafx.cqtkernel(sig.FS, 24, 55, 3520)
@@ -71,10 +104,71 @@ def full_spectrum(half):
     return np.concatenate([half, np.conj(half[-2:0:-1])], axis=0)
 
 
-def hops(y):
+def hops(y, hop=sig.HOP):
     """A 1-D output as rows of one hop each (zero-filled at the end)."""
-    n = -(-len(y) // sig.HOP) * sig.HOP
-    return np.pad(y, (0, n - len(y))).reshape(-1, sig.HOP)
+    n = -(-len(y) // hop) * hop
+    return np.pad(y, (0, n - len(y))).reshape(-1, hop)
+
+
+def _forms(off_grid_compact, whole_lines):
+    """{(mode, grid): kernel}: compact rows off the line grid take one form; rows padded to whole lines (mode "auto") or on the grid take the other."""
+    return {("compact", "off"): off_grid_compact, ("auto", "off"): whole_lines, ("compact", "on"): whole_lines, ("auto", "on"): whole_lines}
+
+
+# The kernel each STFT / MDCT-family call of this module runs, read off the dispatch code (zafx_stft.hip run_stft / run_istft, zafx_mel.hip
+# launch_spec2, zafx_mdct.hip run_mdct / run_mdct_p / run_imdct, zafx_bs32.hip), not off last_kernel: a routing change must not move a test
+# off the form it claims to cover.  (W, kind) -> {(mode, grid): kernel}; grid "on" = T is a whole number of 128-byte lines of the rows
+# the kernel writes (forward) or reads (inverse): 16 complex64, 32 float32 elements.
+ROUTES = {
+    # W = 2048 (1024-point FFT): complex rows whose pitch is not a multiple of 16 on the carry form; whole lines on k_stft_ft16, the 32 x 32
+    # radix-32 schedule (twiddle table d_tw_r32) with whole-line streaming stores
+    (2048, "two_sided"): _forms("k_stft_ft16c", "k_stft_ft16"),
+    (2048, "one_sided"): _forms("k_stft_ft16c", "k_stft_ft16"),
+    # |X|, |X|^2: k_mel2 at every pitch; its store takes 4 frames per 16-byte piece at a pitch that is a multiple of 4 (every padded pitch,
+    # T = 96), one frame otherwise (compact T = 71) -- zafx_mel.hip, rowv
+    (2048, "magnitude"): _forms("k_mel2", "k_mel2"),
+    (2048, "power"): _forms("k_mel2", "k_mel2"),
+    (2048, "istft"): _forms("k_istft_ft16", "k_istft_ft16"),
+    (2048, "istft_one_sided"): _forms("k_istft_ft16", "k_istft_ft16"),
+    # k_mdct_ft32 names two forms (run_mdct_p): the carry instantiation when the row pitch is not a multiple of 16 floats (compact T = 4, 22,
+    # 71), the plain one when it is (T = 96, every padded pitch)
+    (2048, "mdct"): _forms("k_mdct_ft32", "k_mdct_ft32"),
+    (2048, "imdct"): _forms("k_imdct", "k_imdct"),
+    # W = 4096: complex rows off the grid on the one-band carry form, whole lines on the two-band kernel; |X| on the two-band kernel at any pitch
+    (4096, "two_sided"): _forms("k_stft_ft16bc", "k_stft_ft16b"),
+    (4096, "magnitude"): _forms("k_stft_ft16b", "k_stft_ft16b"),
+    (4096, "istft"): _forms("k_istft_ft16d", "k_istft_ft16d"),   # hop W / 2: the two-class kernel (16-byte pieces of two frames at an even pitch)
+    (4096, "mdct"): _forms("k_mdct_ft32bc", "k_mdct_ft32b"),     # a pitch that is not a multiple of 16 floats: the carry form
+    (4096, "imdct"): _forms("k_imdct", "k_imdct"),
+    # W = 8192: two-sided rows on the four-class kernel only as whole lines (compact off the grid: generic k_stft; the test's T = 48 is on it);
+    # k_imdct_q at any pitch that is a multiple of 4 (48 compact, 64 padded)
+    (8192, "two_sided"): _forms("k_stft", "k_stft_ft16q"),
+    (8192, "magnitude"): _forms("k_stft_ft16q", "k_stft_ft16q"),
+    (8192, "istft"): _forms("k_istft_ft8q", "k_istft_ft8q"),
+    (8192, "mdct"): _forms("k_mdct_ft32q", "k_mdct_ft32q"),
+    (8192, "imdct"): _forms("k_imdct_q", "k_imdct_q"),
+    # W = 1000: the float32 Bluestein forms, one frame per workgroup at any pitch
+    (1000, "two_sided"): _forms("k_stft_bs32", "k_stft_bs32"),
+    (1000, "magnitude"): _forms("k_stft_bs32", "k_stft_bs32"),
+    (1000, "istft"): _forms("k_ifft_frames_bs32", "k_ifft_frames_bs32"),
+    (1000, "mdct"): _forms("k_mdct_bs32", "k_mdct_bs32"),
+    (1000, "imdct"): _forms("k_imdct_frames_bs32", "k_imdct_frames_bs32"),
+}
+SPEC = {False: "two_sided", True: "one_sided", "magnitude": "magnitude", "power": "power"}
+
+
+def assert_route(zafx, w, kind, t, line, plan_for, out=None):
+    """The call just made on T = t frames ran ROUTES[(w, kind)] in the current mode.  plan_for(row_align) -> that plan family's plan: _line_grid
+    takes the one padded to `line` elements in mode "auto" off the grid, else the compact one.  out: the forward result, whose row stride shows
+    that the call ran on that plan."""
+    mode = zafx.get_row_padding()
+    grid = "off" if t % line else "on"
+    padded = mode == "auto" and grid == "off"
+    ran, want = plan_for(line if padded else 0).last_kernel, ROUTES[(w, kind)][(mode, grid)]
+    assert ran == want, (w, kind, mode, grid, ran, want)
+    if out is not None:
+        pitch = -(-t // line) * line if padded else t
+        assert out.strides[-2] == pitch * out.itemsize, (w, kind, mode, out.strides, pitch)
 
 
 def check(tag, out, ref, tol, floor=None, c=C_FLOOR):
@@ -110,30 +204,66 @@ def check_mfcc(tag, out, ref, half, fbd):
     return g
 
 
-def run_all(zafx, consts, name, x, xq, ref, long_form):
-    """Every function of the path on one signal.  ref: dict of reference outputs (stft = rows 0..W/2)."""
+def run_all(zafx, consts, name, x, ref, label):
+    """Every STFT / MDCT-family function of the path on one signal, in the current row padding mode, each call's kernel asserted (ROUTES).
+    ref: dict of reference outputs (stft = rows 0..W/2)."""
     ham, kbd, fb, ck = consts
-    fbd = fb.toarray()
-    tag = f"{name}{'_long' if long_form else ''}"
+    mode = zafx.get_row_padding()
+    tag = f"{mode}.{name}{label}"
     half = ref["stft"]
-    got = zafx.stft_batch(x[None], ham, sig.HOP)[0]
-    assert got.shape == (sig.W, half.shape[1])
-    assert check(f"{tag}.stft", got[: sig.W // 2 + 1], half, TOL_FFT) <= TOL_FFT
-    assert check(f"{tag}.stft_mirror", got[sig.W // 2 + 1:], np.conj(half[-2:0:-1]), TOL_FFT) <= TOL_FFT
-    got1 = zafx.stft_batch(x[None], ham, sig.HOP, onesided=True)[0]
-    assert check(f"{tag}.stft_onesided", got1, half, TOL_FFT) <= TOL_FFT
+    t, tm = half.shape[1], ref["mdct"].shape[1]
+
+    def stft_for(kind):
+        return lambda a: zafx.stft_plan(ham, sig.HOP, onesided=kind, row_align=a)
+
+    spec = zafx.stft_batch(x[None], ham, sig.HOP)[0]
+    assert_route(zafx, sig.W, "two_sided", t, 16, stft_for(False), spec)
+    assert spec.shape == (sig.W, half.shape[1])
+    assert check(f"{tag}.stft", spec[: sig.W // 2 + 1], half, TOL_FFT) <= TOL_FFT
+    assert check(f"{tag}.stft_mirror", spec[sig.W // 2 + 1:], np.conj(half[-2:0:-1]), TOL_FFT) <= TOL_FFT
+    spec1 = zafx.stft_batch(x[None], ham, sig.HOP, onesided=True)[0]
+    assert_route(zafx, sig.W, "one_sided", t, 16, stft_for(True), spec1)
+    assert check(f"{tag}.stft_onesided", spec1, half, TOL_FFT) <= TOL_FFT
     for kind, p in (("magnitude", 1), ("power", 2)):
         lvl = np.abs(half) ** p
         # |X|^p of a bin carrying an absolute error nu: p |X|^(p-1) nu + nu^p
         nu = bin_noise(half, C_FLOOR, EPS32)
         fl = nu if p == 1 else 2 * np.abs(half) * nu + nu ** 2
         gotm = zafx.stft_batch(x[None], ham, sig.HOP, onesided=kind)[0]
+        assert_route(zafx, sig.W, kind, t, 32, stft_for(kind), gotm)
         assert check(f"{tag}.stft_{kind}", gotm, lvl, TOL_FFT, fl) <= (TOL_FFT if p == 1 else 2 * TOL_FFT)
 
     y = zafx.istft_batch(full_spectrum(half)[None], ham, sig.HOP)[0]
+    assert_route(zafx, sig.W, "istft", t, 16, lambda a: zafx.istft_plan(ham, sig.HOP, row_align=a))
     assert check(f"{tag}.istft", hops(y), hops(ref["istft"]), TOL_FFT) <= TOL_FFT
     assert len(y) == len(ref["istft"])
+    y1 = zafx.istft_batch(half[None], ham, sig.HOP, onesided=True)[0]
+    assert_route(zafx, sig.W, "istft_one_sided", t, 16, lambda a: zafx.istft_plan(ham, sig.HOP, onesided=True, row_align=a))
+    assert len(y1) == len(ref["istft"])
+    assert check(f"{tag}.istft_onesided", hops(y1), hops(ref["istft"]), TOL_FFT) <= TOL_FFT
 
+    coefs = zafx.mdct_batch(x[None], kbd)[0]
+    assert_route(zafx, sig.W, "mdct", tm, 32, lambda a: zafx.mdct_plan(kbd, row_align=a), coefs)
+    assert check(f"{tag}.mdct", coefs, ref["mdct"], TOL_FFT) <= TOL_FFT
+    yi = zafx.imdct_batch(ref["mdct"][None], kbd)[0]
+    assert_route(zafx, sig.W, "imdct", tm, 32, lambda a: zafx.mdct_plan(kbd, inverse=True, row_align=a))
+    assert len(yi) == len(ref["imdct"])
+    assert check(f"{tag}.imdct", hops(yi), hops(ref["imdct"]), TOL_FFT) <= TOL_FFT
+
+    if mode == "auto":
+        # the drop-ins run *_batch in the default mode and hand back its result -- a view of the padded rows -- cast to complex128 / float64
+        assert np.array_equal(zafx.stft(x, ham, sig.HOP), spec.astype(np.complex128))
+        assert np.array_equal(zafx.istft(full_spectrum(half), ham, sig.HOP), y.astype(np.float64))
+        assert np.array_equal(zafx.mdct(x, kbd), coefs.astype(np.float64))
+        assert np.array_equal(zafx.imdct(ref["mdct"], kbd), yi.astype(np.float64))
+
+
+def run_filterbanks(zafx, consts, name, x, xq, ref, label):
+    """Mel / MFCC (and with xq, CQT / chroma) on one signal: outputs whose rows the row padding mode does not lay out."""
+    ham, kbd, fb, ck = consts
+    fbd = fb.toarray()
+    tag = f"{name}{label}"
+    half = ref["stft"]
     # mel bands: FB |X| with every bin off by at most nu
     nu = bin_noise(half, C_FLOOR, EPS32)
     mel_floor = fbd @ np.broadcast_to(nu, (fbd.shape[1], nu.shape[1])) + C_FLOOR * EPS32 * np.abs(ref["mel"])
@@ -142,12 +272,6 @@ def run_all(zafx, consts, name, x, xq, ref, long_form):
     got = zafx.mfcc_batch(x[None], ham, sig.HOP, fb, 20)[0]
     check_mfcc(f"{tag}.mfcc", got, ref["mfcc"], half, fbd)
 
-    got = zafx.mdct_batch(x[None], kbd)[0]
-    assert check(f"{tag}.mdct", got, ref["mdct"], TOL_FFT) <= TOL_FFT
-    y = zafx.imdct_batch(ref["mdct"][None], kbd)[0]
-    assert len(y) == len(ref["imdct"])
-    assert check(f"{tag}.imdct", hops(y), hops(ref["imdct"]), TOL_FFT) <= TOL_FFT
-
     if xq is not None:
         got = zafx.cqtspectrogram_batch(xq[None], sig.FS, 25, ck)[0]
         assert check(f"{tag}.cqt", got, ref["cqt"], TOL_FB, c=C_FLOOR_CQT) <= TOL_FB
@@ -155,35 +279,75 @@ def run_all(zafx, consts, name, x, xq, ref, long_form):
         assert check(f"{tag}.chroma", got, ref["chroma"], TOL_FB, c=C_FLOOR_CQT) <= TOL_FB
 
 
-@pytest.mark.parametrize("name", sig.NAMES)
-def test_signal_against_the_reference(zafx, consts, golden, name):
-    """n = 3072 / 17640 samples: the reference's own outputs."""
+def golden_refs(golden, name):
     g = golden["signals"]
     x, xq = sig.signal(name, sig.N_FRAMES), sig.signal(name, sig.N_CQT)
     assert float(x.astype(np.float64).sum()) == g[f"{name}_x_sum"] and float(np.abs(xq.astype(np.float64)).sum()) == g[f"{name}_xq_abs"]
-    ref = {k: g[f"{name}_{k}"] for k in ("stft", "istft", "mel", "mfcc", "mdct", "imdct", "cqt", "chroma")}
-    run_all(zafx, consts, name, x, xq, ref, False)
+    return x, xq, {k: g[f"{name}_{k}"] for k in ("stft", "istft", "mel", "mfcc", "mdct", "imdct", "cqt", "chroma")}
+
+
+@pytest.mark.parametrize("name", sig.NAMES)
+def test_signal_against_the_reference(zafx, consts, golden, name):
+    """n = 3072 / 17640 samples: the reference's own outputs."""
+    x, xq, ref = golden_refs(golden, name)
+    run_all(zafx, consts, name, x, ref, "")
+    run_filterbanks(zafx, consts, name, x, xq, ref, "")
+
+
+@pytest.mark.parametrize("name", sig.NAMES)
+def test_signal_against_the_reference_padded(zafx_padded, consts, golden, name):
+    """n = 3072 samples (T = 4) on rows padded to whole lines: the reference's own outputs."""
+    x, xq, ref = golden_refs(golden, name)
+    run_all(zafx_padded, consts, name, x, ref, "")
+
+
+def oracle_refs(consts, x):
+    ham, kbd, fb, ck = consts
+    x64 = x.astype(np.float64)
+    s = orc.stft(x64, ham, sig.HOP)
+    m = orc.mdct(x64, kbd)
+    return {"stft": s[: sig.W // 2 + 1], "istft": orc.istft(s, ham, sig.HOP), "mel": orc.melspectrogram(x64, ham, sig.HOP, fb),
+            "mfcc": orc.mfcc(x64, ham, sig.HOP, fb, 20), "mdct": m, "imdct": orc.imdct(m, kbd)}
 
 
 @pytest.mark.parametrize("name", sig.NAMES)
 def test_signal_on_the_whole_tile_kernels(zafx, consts, name):
     """70 frames (the tiled kernels' interior path, an edge tile, rows off the line grid) against the oracle, which
     tests/test_oracle_golden.py holds to the reference on these very signals."""
-    ham, kbd, fb, ck = consts
     x = sig.signal(name, N_LONG)
-    x64 = x.astype(np.float64)
-    s = orc.stft(x64, ham, sig.HOP)
-    m = orc.mdct(x64, kbd)
-    ref = {"stft": s[: sig.W // 2 + 1], "istft": orc.istft(s, ham, sig.HOP), "mel": orc.melspectrogram(x64, ham, sig.HOP, fb),
-           "mfcc": orc.mfcc(x64, ham, sig.HOP, fb, 20), "mdct": m, "imdct": orc.imdct(m, kbd)}
-    run_all(zafx, consts, name, x, None, ref, True)
+    ref = oracle_refs(consts, x)
+    run_all(zafx, consts, name, x, ref, "_long")
+    run_filterbanks(zafx, consts, name, x, None, ref, "_long")
+
+
+@pytest.mark.parametrize("name", sig.NAMES)
+def test_signal_on_the_whole_tile_kernels_padded(zafx_padded, consts, name):
+    """The same 70 frames on rows padded to whole lines (k_stft_ft16, the plain k_mdct_ft32, k_mel2 at 4 frames per store)."""
+    x = sig.signal(name, N_LONG)
+    run_all(zafx_padded, consts, name, x, oracle_refs(consts, x), "_long")
+
+
+@pytest.mark.parametrize("name", sig.NAMES)
+def test_signal_on_the_line_grid(zafx_mode, consts, name):
+    """96 frames: rows of whole lines without padding -- the plain forms in compact mode too."""
+    x = sig.signal(name, N_GRID)
+    run_all(zafx_mode, consts, name, x, oracle_refs(consts, x), "_grid")
 
 
 def test_silence_is_exact(zafx, consts):
     """Digital silence: every linear output is exactly zero (no denormal dust, no -0.0 that a log would turn into nan)."""
+    silence_is_exact(zafx, consts)
+
+
+def test_silence_is_exact_padded(zafx_padded, consts):
+    silence_is_exact(zafx_padded, consts)
+
+
+def silence_is_exact(zafx, consts):
     ham, kbd, fb, ck = consts
     x = np.zeros((2, N_LONG), dtype=np.float32)
     assert not np.any(zafx.stft_batch(x, ham, sig.HOP))
+    assert not np.any(zafx.stft_batch(x, ham, sig.HOP, onesided="power"))
     assert not np.any(zafx.melspectrogram_batch(x, ham, sig.HOP, fb))
     assert not np.any(zafx.mdct_batch(x, kbd))
     assert not np.any(zafx.cqtspectrogram_batch(x[:, :40000], sig.FS, 25, ck))
@@ -219,36 +383,48 @@ def test_signal_on_the_other_kernels(zafx, name, wl, hop):
     """The same signals through the kernels the W = 2048 / hop 1024 cases do not reach -- the two-band forms of W = 4096 (k_stft_ft16b / bc,
     k_istft_ft16d, k_mdct_ft32b / bc, k_mel_ft16b), 75 % overlap, a window that is not a power of two (the Bluestein forms), the four-class
     forms of W = 8192 (k_stft_ft16q, k_mdct_ft32q and, round 6, their inverses k_istft_ft8q, k_imdct_q; 48 frames: rows on the line grid) -- against the
-    oracle with the same two bounds."""
+    oracle with the same two bounds, each call's kernel asserted (ROUTES)."""
+    other_kernels(zafx, name, wl, hop)
+
+
+@pytest.mark.parametrize("name", sig.NAMES)
+@pytest.mark.parametrize("wl,hop", [(4096, 2048), (2048, 512), (1000, 250), (8192, 4096)])
+def test_signal_on_the_other_kernels_padded(zafx_padded, name, wl, hop):
+    """The same on rows padded to whole lines (k_stft_ft16b, k_mdct_ft32b, k_stft_ft16, ...)."""
+    other_kernels(zafx_padded, name, wl, hop)
+
+
+def other_kernels(zafx, name, wl, hop):
     n = 40 * hop + 300 if wl != 8192 else 47 * hop - 100
     x = sig.signal(name, n)
     x64 = x.astype(np.float64)
     ham = zafx.hamming(wl)
     s = orc.stft(x64, ham, hop)
     half = s[: wl // 2 + 1]
-    tag = f"{name}_{wl}_{hop}"
+    t = s.shape[1]
+    tag = f"{zafx.get_row_padding()}.{name}_{wl}_{hop}"
     got = zafx.stft_batch(x[None], ham, hop)[0]
+    assert_route(zafx, wl, "two_sided", t, 16, lambda a: zafx.stft_plan(ham, hop, row_align=a), got)
     assert check(f"{tag}.stft", got, s, TOL_FFT) <= TOL_FFT
-    if wl == 8192:
-        assert zafx.stft_plan(ham, hop).last_kernel == "k_stft_ft16q"
     y = zafx.istft_batch(s[None], ham, hop)[0]
+    assert_route(zafx, wl, "istft", t, 16, lambda a: zafx.istft_plan(ham, hop, row_align=a))
     yref = orc.istft(s, ham, hop)
     assert len(y) == len(yref) and relerr(y, yref) <= TOL_FFT
-    if wl == 8192:
-        assert zafx.istft_plan(ham, hop).last_kernel == "k_istft_ft8q"
-    if wl == 4096:
-        assert zafx.istft_plan(ham, hop).last_kernel == "k_istft_ft16d"   # (hop W / 2: the two-class kernel of round 6)
+    assert check(f"{tag}.istft", hops(y, hop), hops(yref, hop), TOL_FFT) <= TOL_FFT
     nu = bin_noise(half, C_FLOOR, EPS32)
     gotm = zafx.stft_batch(x[None], ham, hop, onesided="magnitude")[0]
+    assert_route(zafx, wl, "magnitude", t, 32, lambda a: zafx.stft_plan(ham, hop, onesided="magnitude", row_align=a), gotm)
     assert check(f"{tag}.magnitude", gotm, np.abs(half), TOL_FFT, nu) <= TOL_FFT
     if wl % 2 == 0:
         kbd = zafx.kaiser_bessel_derived(wl) if wl & (wl - 1) == 0 else zafx.sine(wl)
         m = orc.mdct(x64, kbd)
-        assert check(f"{tag}.mdct", zafx.mdct_batch(x[None], kbd)[0], m, TOL_FFT) <= TOL_FFT
+        coefs = zafx.mdct_batch(x[None], kbd)[0]
+        assert_route(zafx, wl, "mdct", m.shape[1], 32, lambda a: zafx.mdct_plan(kbd, row_align=a), coefs)
+        assert check(f"{tag}.mdct", coefs, m, TOL_FFT) <= TOL_FFT
         yi, yiref = zafx.imdct_batch(m[None], kbd)[0], orc.imdct(m, kbd)
+        assert_route(zafx, wl, "imdct", m.shape[1], 32, lambda a: zafx.mdct_plan(kbd, inverse=True, row_align=a))
         assert len(yi) == len(yiref) and relerr(yi, yiref) <= TOL_FFT
-        if wl == 8192:
-            assert zafx.mdct_plan(kbd).last_kernel == "k_mdct_ft32q" and zafx.mdct_plan(kbd, inverse=True).last_kernel == "k_imdct_q"
+        assert check(f"{tag}.imdct", hops(yi, wl // 2), hops(yiref, wl // 2), TOL_FFT) <= TOL_FFT
     fb = zafx.melfilterbank(sig.FS, wl, 64)
     fbd = fb.toarray()
     mel_floor = fbd @ np.broadcast_to(nu, (fbd.shape[1], nu.shape[1])) + C_FLOOR * EPS32 * np.abs(orc.melspectrogram(x64, ham, hop, fb))
@@ -258,7 +434,17 @@ def test_signal_on_the_other_kernels(zafx, name, wl, hop):
 @pytest.mark.parametrize("name", sig.NAMES)
 def test_signal_in_float64(zafx, consts, name):
     """The float64 mode (the reference's own dtype) on the same signals: 1e-12 normwise on the tiled kernels of W = 2048
-    (k_stft_ft8_f64, k_mdct_ft16_f64) and on the inverse transforms; silence stays exactly zero."""
+    (k_stft_ft8_f64, k_mdct_ft16_f64) and on the inverse transforms; silence stays exactly zero.  (The padded twin: rows of whole lines of 8
+    complex128 / 16 float64 elements.)"""
+    signal_in_float64(zafx, consts, name)
+
+
+@pytest.mark.parametrize("name", sig.NAMES)
+def test_signal_in_float64_padded(zafx_padded, consts, name):
+    signal_in_float64(zafx_padded, consts, name)
+
+
+def signal_in_float64(zafx, consts, name):
     ham, kbd, fb, ck = consts
     x64 = sig.signal(name, N_LONG).astype(np.float64)
     s = orc.stft(x64, ham, sig.HOP)
@@ -310,3 +496,74 @@ def test_signal_in_float64_mel_mfcc_cqt(zafx, consts, name):
         assert excess(cep, ref_cep, fl) <= 1.0, (name, g)
     else:
         assert g <= 1e-10, (name, g)
+
+
+# the nine signals as one ragged batch, every clip of its own length (0 and 1 samples, T = 4, 71 and 96 at W = 2048); silence and the
+# -90 dBFS noise each sit between two full-scale clips, so that a tile reading past its clip, or taking a neighbour's base, shows
+RAGGED = (("dc", 0), ("clipped_pcm", N_LONG), ("silence", N_GRID), ("sine_bin", 44100), ("noise_m90", sig.N_FRAMES), ("two_tones", 2 * sig.W + 1),
+          ("impulse", 1), ("chirp", 1024 * 40 + 7), ("sine_half", 16 * sig.HOP + 3))
+KINDS = [False, True, "magnitude", "power"]
+ZERO_MFCC = 8.0 * EPS32 * 36.05 * np.sqrt(128.0)   # (test_silence_is_exact: DCT rows 1..20 of 128 equal levels log(eps))
+
+
+def ragged_clips():
+    assert len({n for _, n in RAGGED}) == len(RAGGED) and {name for name, _ in RAGGED} == set(sig.NAMES)
+    return [sig.signal(name, n) for name, n in RAGGED]
+
+
+@pytest.mark.parametrize("wl,hop", [(2048, 1024), (1024, 256)])
+def test_signals_in_one_ragged_batch(zafx_lib, wl, hop):
+    """stft_ragged of the nine signals, every spectrum kind (k_stft_ft16_ragged; |X| / |X|^2 at W = 2048: k_mel2_ragged; W = 1024 two-sided, where
+    the equal-length path runs the carry form) against the oracle clip by clip with run_all's bounds; a clip of zeros comes out exactly zero."""
+    zafx = zafx_lib
+    clips = ragged_clips()
+    ham = zafx.hamming(wl)
+    specs = [orc.stft(c.astype(np.float64), ham, hop) for c in clips]
+    for kind in KINDS:
+        got = zafx.stft_ragged(clips, ham, hop, onesided=kind)
+        line = 16 if kind in (False, True) else 32
+        want = "k_mel2_ragged" if wl == 2048 and kind in ("magnitude", "power") else "k_stft_ft16_ragged"
+        assert zafx.stft_plan(ham, hop, onesided=kind, row_align=line).last_kernel == want, kind
+        assert len(got) == len(clips)
+        for (name, n), x, g, s in zip(RAGGED, clips, got, specs):
+            tag = f"ragged.{name}_{n}_{wl}_{hop}.stft_{SPEC[kind]}"
+            half = s[: wl // 2 + 1]
+            if not np.any(x):
+                assert g.shape == (s.shape[0] if kind is False else half.shape[0], s.shape[1]) and not np.any(g), tag
+            if kind is False:
+                assert check(tag, g, s, TOL_FFT) <= TOL_FFT
+            elif kind is True:
+                assert check(tag, g, half, TOL_FFT) <= TOL_FFT
+            else:
+                p = 1 if kind == "magnitude" else 2
+                nu = bin_noise(half, C_FLOOR, EPS32)
+                fl = nu if p == 1 else 2 * np.abs(half) * nu + nu ** 2
+                assert check(tag, g, np.abs(half) ** p, TOL_FFT, fl) <= p * TOL_FFT
+
+
+def test_signals_in_one_ragged_batch_mel_mfcc(zafx_lib, consts):
+    """melspectrogram_ragged / mfcc_ragged / mel_mfcc_ragged (k_mel2_ragged) of the nine signals at W = 2048 against the oracle clip by clip with
+    run_all's bounds; the mel bands of a clip of zeros are exactly zero, its MFCCs those of test_silence_is_exact."""
+    zafx = zafx_lib
+    ham, kbd, fb, ck = consts
+    fbd = fb.toarray()
+    clips = ragged_clips()
+    mel = zafx.melspectrogram_ragged(clips, ham, sig.HOP, fb)
+    assert zafx.mel_plan(ham, sig.HOP, fb, row_align=32).last_kernel == "k_mel2_ragged"
+    cep = zafx.mfcc_ragged(clips, ham, sig.HOP, fb, 20)
+    assert zafx.mel_plan(ham, sig.HOP, fb, 20, row_align=32).last_kernel == "k_mel2_ragged"
+    both_mel, both_cep = zafx.mel_mfcc_ragged(clips, ham, sig.HOP, fb, 20)
+    assert zafx.mel_plan(ham, sig.HOP, fb, 20, row_align=32, also_mel=True).last_kernel == "k_mel2_ragged"
+    for i, ((name, n), x) in enumerate(zip(RAGGED, clips)):
+        x64 = x.astype(np.float64)
+        half = orc.stft(x64, ham, sig.HOP)[: sig.W // 2 + 1]
+        ref_mel, ref_cep = orc.melspectrogram(x64, ham, sig.HOP, fb), orc.mfcc(x64, ham, sig.HOP, fb, 20)
+        nu = bin_noise(half, C_FLOOR, EPS32)
+        mel_floor = fbd @ np.broadcast_to(nu, (fbd.shape[1], nu.shape[1])) + C_FLOOR * EPS32 * np.abs(ref_mel)
+        for form, m, c in (("", mel[i], cep[i]), ("_one_pass", both_mel[i], both_cep[i])):
+            tag = f"ragged.{name}_{n}{form}"
+            if not np.any(x):
+                assert m.shape == ref_mel.shape and not np.any(m), tag
+                assert np.all(np.isfinite(c)) and np.abs(c).max() <= ZERO_MFCC, tag
+            assert check(f"{tag}.mel", m, ref_mel, TOL_FB, mel_floor) <= TOL_FB
+            check_mfcc(f"{tag}.mfcc", c, ref_cep, half, fbd)
