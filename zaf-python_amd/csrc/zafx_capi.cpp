@@ -1088,6 +1088,13 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
             e = upload(&pl->d_tw_r32, tw5.data(), tw5.size() * sizeof(cf32));
         }
     }
+    if (e == hipSuccess && kind == ZAFX_STFT && pl->prm.precision == ZAFX_PRECISION_F32) {
+        // k_stft_ft16 with its tiles claimed at run time: the plan's counters, zero from here on between launches
+        const std::vector<int> zeros((size_t)zafx::kClaimInts, 0);
+        e = upload(&pl->d_claim, zeros.data(), zeros.size() * sizeof(int));
+        const char* sw = std::getenv("ZAFX_STFT_DYNAMIC");   // 0: the static split (to time both forms in one process: tools/stft_dyn_ab.py)
+        pl->stft_dynamic = !(sw && sw[0] == '0' && sw[1] == 0);
+    }
     if (e == hipSuccess && (kind == ZAFX_STFT || kind == ZAFX_ISTFT || kind == ZAFX_MEL || kind == ZAFX_MFCC) && pl->log2nf == 11 && pl->prm.precision == ZAFX_PRECISION_F32) {
         const auto sub = build_pass_twiddles(10, 4);   // the two 1024-point band transforms of k_stft_ft16b
         e = upload(&pl->d_tw_sub, sub.data(), sub.size() * sizeof(cf32));
@@ -1210,6 +1217,8 @@ int zafx_plan_destroy(zafx_plan* pl) {
     if (pl->d_wfold) (void)hipFree(pl->d_wfold);
     if (pl->d_tw_pass) (void)hipFree(pl->d_tw_pass);
     if (pl->d_tw_r32) (void)hipFree(pl->d_tw_r32);
+    if (pl->d_claim) (void)hipFree(pl->d_claim);
+    if (pl->d_tail) (void)hipFree(pl->d_tail);
     if (pl->d_tw_quad) (void)hipFree(pl->d_tw_quad);
     if (pl->d_tw_sub) (void)hipFree(pl->d_tw_sub);
     if (pl->d_tw_band) (void)hipFree(pl->d_tw_band);

@@ -462,6 +462,32 @@ ZAFX_HD void regs_read(float2* v, const float2* buf, int p) {
     for (int i = 0; i < C::E; ++i) v[i] = buf[phys_off<C::P, C::PS>(pp, p, i * C::P)];
 }
 
+// ---------------------------------------------------------------- tiles claimed at run time (k_stft_ft16's DYN form)
+// Eight queues, one per XCD, over the contiguous ranges xcd_order (below) gives the XCDs of a persistent grid: queue x holds the tiles
+// claim_first(x) ... + claim_len(x) - 1 and hands them out in that order through one counter.  Shared with the host: tests/host_emu/claim_emu.cpp
+// walks the same functions.
+constexpr int kClaimQueues = 8;
+constexpr int kClaimStride = 32;                                  // ints between two counters: a 128-byte line each
+constexpr int kClaimInts = (kClaimQueues + 1) * kClaimStride;     // + the count of the workgroups that have left
+constexpr int kClaimLdsBytes = 16;                                // the LDS words that carry the claimed indices to the waves: two in turn, one for the first tile
+ZAFX_HD int claim_len(int x, int total) { return (total >> 3) + (x < (total & 7) ? 1 : 0); }
+ZAFX_HD int claim_first(int x, int total) {
+    const int q = total >> 3, r = total & 7;
+    return x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
+}
+// The tile behind ticket v of queue q, or -- the queue has run out -- the next queue's next ticket (`draw(queue)`: the counter's value before
+// it is raised by one), and so on round once from `home`; -1 once every queue is empty.  q stays on the queue that served the claim: counters
+// only rise during a launch, so a queue found empty is never asked again, and a workgroup that got -1 draws no more.
+template <class Draw>
+ZAFX_HD int claim_finish(int& q, int home, int total, int v, Draw draw) {
+    for (;;) {
+        if (v < claim_len(q, total)) return claim_first(q, total) + v;
+        q = (q + 1) & (kClaimQueues - 1);
+        if (q == home) return -1;
+        v = draw(q);
+    }
+}
+
 }  // namespace zafx
 
 #if !defined(ZAFX_HOST_EMU) && defined(__HIPCC__)   // (device code: not for the host-only g++ build of the C-ABI layer, `make asan`)

@@ -193,6 +193,12 @@ struct zafx_plan {
     std::vector<int32_t> h_indptr, h_indices;
     std::vector<zafx::cf32> h_values;
 
+    // k_stft_ft16's DYN form (tiles claimed at run time): eight queue counters and the count of the workgroups that have left, each on a
+    // 128-byte line of its own (zafx::kClaimInts ints, zero between launches: the last workgroup of a launch puts them back).
+    // ZAFX_STFT_DYNAMIC=0 in the environment at plan creation keeps the plan on the static split.
+    int* d_claim = nullptr;
+    bool stft_dynamic = false;
+    unsigned long long* d_tail = nullptr;   // ZAFX_PROF builds: per-workgroup finish times of k_stft_ft16 (zafx_debug_stft_tail_bind)
     std::string kernel_name;            // the kernel this plan is expected to run (set at creation)
     mutable std::atomic<const char*> ran{nullptr};  // the kernel the last execute really launched (routes depend on T, alignment and hop); zafx_plan_last_kernel_name
 };
@@ -216,6 +222,24 @@ template <bool RAGGED, class R, class A>
 __host__ __device__ __forceinline__ const auto& rg_pick(const R& rec, const A& arg) {
     if constexpr (RAGGED) return rec;
     else return arg;
+}
+// The last argument of k_stft_ft16: the number of tiles, or (DYN) that number with the plan's claim counters -- the instantiations that
+// deal their tiles out up front keep their kernel arguments byte for byte.
+struct TileClaim {
+    int total_tiles, pad_;
+    int* counters;
+};
+template <bool DYN>
+using TilesArg = std::conditional_t<DYN, TileClaim, int>;
+template <bool DYN>
+__host__ __device__ __forceinline__ const int& tiles_total(const TilesArg<DYN>& a) {
+    if constexpr (DYN) return a.total_tiles;
+    else return a;
+}
+template <bool DYN>
+__host__ __device__ __forceinline__ int* tiles_claim(const TilesArg<DYN>& a) {
+    if constexpr (DYN) return a.counters;
+    else return nullptr;
 }
 #ifdef __HIPCC__
 // The record of tile `tl` (uniform): its clip from the per-tile part of the table, the record by scalar loads.
@@ -338,6 +362,25 @@ hipError_t ensure_dynamic_lds(const void* kernel, int device, size_t bytes);
         if (blockIdx.x == 7 && (int)threadIdx.x == prof_thread_) atomicAdd(&prof_[i], now_ - tprev_);   \
         tprev_ = now_;                                                                     \
     } while (0)
+// Finish times per workgroup (k_stft_ft16; tools/stft_tail.py): thread 0 of every workgroup leaves four words in the array `name` points
+// to -- XCD assumed from blockIdx.x (& 7) | tiles it ran << 8, then the chip-wide 100-MHz clock (wall_clock64) at its start, at its first
+// store and behind its last tile -- with ordinary stores.  A null pointer (the default) records nothing.
+#define ZAFX_PROF_TAIL_PTR(name) __device__ unsigned long long* name = nullptr;
+#define PROF_TAIL_INIT() \
+    const unsigned long long tail_t0_ = wall_clock64(); \
+    unsigned long long tail_first_ = 0, tail_n_ = 0
+#define PROF_TAIL_FIRST() do { if (tail_n_ == 0) tail_first_ = wall_clock64(); } while (0)
+#define PROF_TAIL_TILE() ++tail_n_
+#define PROF_TAIL_END(name)                                                     \
+    do {                                                                        \
+        unsigned long long* const tail_ = name;                                 \
+        if (tail_ && threadIdx.x == 0) {                                        \
+            tail_[4 * blockIdx.x + 0] = (blockIdx.x & 7) | tail_n_ << 8;        \
+            tail_[4 * blockIdx.x + 1] = tail_t0_;                               \
+            tail_[4 * blockIdx.x + 2] = tail_first_;                            \
+            tail_[4 * blockIdx.x + 3] = wall_clock64();                         \
+        }                                                                       \
+    } while (0)
 #define ZAFX_PROF_EXPORT(fn, name)                                                                  \
     extern "C" int fn##_thread(int t) { return hipMemcpyToSymbol(HIP_SYMBOL(zafx::name##_thread), &t, sizeof(t)) != hipSuccess; } \
     extern "C" int fn(unsigned long long* out) {                                                    \
@@ -349,5 +392,10 @@ hipError_t ensure_dynamic_lds(const void* kernel, int device, size_t bytes);
 #define ZAFX_PROF_ARRAY(name)
 #define PROF_INIT(name)
 #define PROF_MARK(i)
+#define ZAFX_PROF_TAIL_PTR(name)
+#define PROF_TAIL_INIT()
+#define PROF_TAIL_FIRST()
+#define PROF_TAIL_TILE()
+#define PROF_TAIL_END(name)
 #define ZAFX_PROF_EXPORT(fn, name)
 #endif

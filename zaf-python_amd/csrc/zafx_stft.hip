@@ -176,6 +176,7 @@ __global__ __launch_bounds__(FPB * fft_threads(LOG2N, LOG2E)) void k_stft(
 //   * pads the frame pitch to 2 (mod 32) complex slots: the transposed read of the store
 //     phase (16 frames x 2 bins per 32-lane group) is then LDS-bank-conflict free.
 ZAFX_PROF_ARRAY(g_prof_stft)
+ZAFX_PROF_TAIL_PTR(g_stft_tail)
 constexpr int kFatWaves = 8;
 constexpr int kFatFrames = 16;
 
@@ -226,12 +227,32 @@ struct PcmPoint {
 // RAGGED (zafx_execute_ragged): clips of different lengths.  `n_samples` carries the batch's table and `tiles` the number of clips
 // (SamplesArg, zafx_internal.hpp); a tile's clip, its samples, frames, row pitch and the bases of its input and output come from its
 // record, and everything else -- the fast / edge decision, the zero padding, the XCD order, the store phase -- is the same code.
-template <int LOG2N, int LOG2E, bool ALIGNED, int SPEC, int FPB_ = kFatFrames, int PCM = 0, bool RAGGED = false>
+//
+// DYN: the tiles are claimed while the kernel runs instead of dealt out up front (tlv += gridDim.x).  The static split is even only if
+// every CU is served by the memory system at the same rate for the whole launch; the launch ends with the slowest workgroup's last tile, and
+// from the first workgroup that runs dry fewer CUs keep the HBM write queues full (profiles/r07_notes.md has the finish times per XCD).
+//   * Eight queues, one per XCD, over the ranges xcd_order gives the XCDs (claim_first / claim_len, zafx_fft.hpp): the workgroups of an XCD
+//     draw consecutive tiles of its range, as they walk it side by side in the static form.  A workgroup whose queue is empty goes on to
+//     the next XCD's, round once (claim_finish); a queue found empty stays empty, so it never goes back.
+//   * The counters (`tiles_arg.counters`: one per 128-byte line, the ninth counts the workgroups that have left) belong to the plan.  The
+//     last workgroup to leave puts all nine back to zero: launches of a plan are ordered by its stream, so the next one starts from zeros
+//     without a memset in front of it.
+//   * Two tiles ahead: every wave requests tile n + 1's samples ahead of tile n's first barrier, so that index is in LDS (slot[(n + 1) & 1])
+//     from tile n - 1 on.  Thread 0 draws tile n + 2's ticket at the start of tile n's last transform -- once the prefetched samples are
+//     all there: vmcnt retires in issue order, a ticket drawn ahead of them is waited for with the samples -- and reads it when the
+//     transform is done, ahead of the next tile's loads: nothing else of the wave is in flight then, and the round trip (about 1 us)
+//     has passed under the butterflies (about 3 us).  slot[n & 1] is published by the barriers of tile n.
+//   * A claimed tile is stored whole; every wave leaves on the same LDS word (slot < 0).  The row-sweep rotation stays a function of
+//     blockIdx.x: it orders a workgroup's stores and touches no value, so the output does not depend on who ran which tile.
+// The last argument is the tile count, or (DYN) the count with the counters: the other instantiations keep their arguments byte for byte.
+template <int LOG2N, int LOG2E, bool ALIGNED, int SPEC, int FPB_ = kFatFrames, int PCM = 0, bool RAGGED = false, bool DYN = false>
 __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     const float* __restrict__ x, const float* __restrict__ win, const float2* __restrict__ twp,
     const float2* __restrict__ tws, float2* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop, int T, int TP, int tiles,
-    int total_tiles) {
+    TilesArg<DYN> tiles_arg) {
     static_assert(!RAGGED || (PCM == 0 && FPB_ == kFatFrames), "ragged batches: float32 samples, 16-frame tiles");
+    static_assert(!DYN || FPB_ == kFatFrames, "claimed tiles: 16-frame tiles");
+    const int& total_tiles = tiles_total<DYN>(tiles_arg);
     // samples, frames and row pitch of the tile's clip: the kernel's arguments, or (RAGGED) the fields of the tile's record rc -- read where
     // they are used, as the arguments always were (rg_pick)
 #define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
@@ -249,6 +270,22 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     float2* tws_l = win_s + (F::WIN_LDS ? N : 0);      // N/2 + 1 roots of W
     const float2* win_l = F::WIN_LDS ? win_s : reinterpret_cast<const float2*>(win);
     const int tid = threadIdx.x;
+    // DYN: thread 0's state -- the queue it draws from, the ticket on its way, whether any queue may still hold a tile -- and the two LDS
+    // words behind the tables (kClaimLdsBytes) that carry the claimed indices to every wave
+    [[maybe_unused]] int* const slot = reinterpret_cast<int*>(tws_l + N / 2 + 1);
+    [[maybe_unused]] const int home = (int)blockIdx.x & (kClaimQueues - 1);
+    [[maybe_unused]] int cq = home, ticket = 0;
+    [[maybe_unused]] bool live = false;
+    [[maybe_unused]] auto draw = [&](int q) { return atomicAdd(tiles_claim<DYN>(tiles_arg) + q * kClaimStride, 1); };
+    if constexpr (DYN) {
+        if (tid == 0) {   // the first two tiles; the round trips pass while the tables are staged
+            const int c0 = claim_finish(cq, home, total_tiles, draw(cq), draw);
+            const int c1 = c0 >= 0 ? claim_finish(cq, home, total_tiles, draw(cq), draw) : -1;
+            slot[2] = c0;   // (a word of its own: thread 0 writes slot[0] during the first tile, with no barrier behind this read)
+            slot[1] = c1;
+            live = c1 >= 0;
+        }
+    }
     for (int i = tid; i < C::TW; i += NT) tw_l[i] = twp[i];
     static_assert(PCM == 0 || F::WIN_LDS, "int16 input: the staged window carries the scale");
     using PP = PcmPoint<PCM>;
@@ -269,10 +306,10 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     // inside the clip issues 2 x 16 unconditional 8-byte loads with no control flow in between, so the
     // loads stay in flight across the store phase; only the first and last tiles of a clip take the
     // predicated path (zero padding of zaf.py:112-125).
-    const bool xcd = ZAFX_XCD_ORDER && gridDim.x % 8 == 0;   // (see xcd_order: units of a clip to the workgroups of one XCD)
-    auto prefetch = [&](int tlv) {
-        if (tlv >= total_tiles) return;
-        const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
+    [[maybe_unused]] const bool xcd = ZAFX_XCD_ORDER && gridDim.x % 8 == 0;   // (see xcd_order: units of a clip to the workgroups of one XCD)
+    auto prefetch = [&](int tlv) {   // (DYN: tlv is the claimed tile itself, < 0 for none)
+        if (DYN ? tlv < 0 : tlv >= total_tiles) return;
+        const int tl = DYN ? tlv : xcd ? xcd_order(tlv, total_tiles) : tlv;
         int p = p_lane;   // (opaque at 32 points per thread: the 64-bit sample offsets of the edge path are recomputed, not hoisted)
         if constexpr (E >= 32 || ZAFX_STFT_FAT_OPAQUE(LOG2N, SPEC)) asm volatile("" : "+v"(p));
         [[maybe_unused]] RgClip rc;
@@ -326,10 +363,13 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         }
     };
     int tlv = blockIdx.x;
+    if constexpr (DYN) tlv = __builtin_amdgcn_readfirstlane(slot[2]);
+    [[maybe_unused]] int par = 0;   // DYN: parity of the current tile in the workgroup's own sequence
     prefetch(tlv);
     PROF_INIT(g_prof_stft);
-    for (; tlv < total_tiles; tlv += gridDim.x) {
-        const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
+    PROF_TAIL_INIT();
+    while (DYN ? tlv >= 0 : tlv < total_tiles) {
+        const int tl = DYN ? tlv : xcd ? xcd_order(tlv, total_tiles) : tlv;
         [[maybe_unused]] RgClip rc;
         if constexpr (RAGGED) rc = rg_clip(n_samples, tiles, tl);
         const int clip = RAGGED ? 0 : tl / tiles, tile = RAGGED ? tl - rc.first_tile : tl % tiles;
@@ -340,6 +380,19 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
 #pragma unroll
         for (int f = 0; f < FPW; ++f) {
             float2 v[E];
+            if constexpr (DYN) {   // the ticket of the tile after next, once the last prefetched samples have arrived
+                if (f == FPW - 1) {
+                    // (the samples pinned ahead of the draw, the arithmetic behind it untouched: left alone, the compiler draws first, and
+                    // the wait for the last samples -- vmcnt(0), the stores of the previous tile being uncounted -- takes the ticket's
+                    // round trip with it)
+#pragma unroll
+                    for (int i = 0; i < E; ++i) {
+                        if constexpr (PCM == 1) asm volatile("" : "+v"(xr[f][i])::"memory");
+                        else asm volatile("" : "+v"(xr[f][i].x), "+v"(xr[f][i].y)::"memory");
+                    }
+                    if (tid == 0 && live) ticket = draw(cq);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < E; ++i) {
                 const float2 wv = win_l[po + i * P], xv = PP::get(xr[f][i]);
@@ -356,11 +409,23 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         // the CU's vector-memory queue for 5-11 k cycles before the wave's first store.
         // (The two frames of a wave are adjacent and overlap by W - hop samples: requested together, the shared half is served by
         // the vector cache; requested half a store phase apart it was fetched from HBM twice.)
-        if (ZAFX_STFT_EARLY) prefetch(tlv + gridDim.x);
+        if constexpr (DYN) {
+            // the tile after next into the word this tile's index came from (read during the previous tile; the end-of-tile barrier
+            // publishes it).  Here, ahead of the next tile's loads, the ticket is the only thing in flight: the wait is for it alone.
+            if (tid == 0) {
+                const int c = live ? claim_finish(cq, home, total_tiles, ticket, draw) : -1;
+                slot[par] = c;
+                live = c >= 0;
+            }
+        }
+        int nxt = tlv + gridDim.x;
+        if constexpr (DYN) nxt = __builtin_amdgcn_readfirstlane(slot[par ^ 1]);   // (every wave reads the same word: uniform, and the exit condition)
+        if (ZAFX_STFT_EARLY) prefetch(nxt);
         PROF_MARK(1);
         lds_barrier();
         PROF_MARK(2);
-        if (!ZAFX_STFT_EARLY) prefetch(tlv + gridDim.x);   // in flight while this tile is stored
+        if (!ZAFX_STFT_EARLY) prefetch(nxt);   // in flight while this tile is stored
+        PROF_TAIL_FIRST();
         PROF_MARK(3);
         if (t0 + tt < CLIP_T) {
             float2* o = spec_base<SPEC>(out, (RAGGED ? rc.out_off : (long long)clip * ROWS * TP) + (t0 + tt));
@@ -408,6 +473,19 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         }
         PROF_MARK(4);
         lds_barrier();   // LDS reads of the tile are done; its global stores are NOT waited for
+        tlv = nxt;
+        par ^= 1;
+        PROF_TAIL_TILE();
+    }
+    PROF_TAIL_END(g_stft_tail);
+    if constexpr (DYN) {
+        // leaving: thread 0's tickets have all come back (it read every one of them).  The last workgroup to leave zeroes the counters for the
+        // plan's next launch -- nobody draws any more -- with atomics, which take the same way to memory as the draws.
+        if (tid == 0) {
+            int* const cnt = tiles_claim<DYN>(tiles_arg);
+            if (atomicAdd(cnt + kClaimQueues * kClaimStride, 1) == (int)gridDim.x - 1)
+                for (int i = 0; i <= kClaimQueues; ++i) atomicExch(cnt + i * kClaimStride, 0);
+        }
     }
 }
 #undef CLIP_N
@@ -2416,6 +2494,19 @@ static hipError_t run_stft_fat(const zafx_plan& pl, const float* x, float2* out,
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
     const long long grid = std::min<long long>(total, (long long)pl.n_cus * std::max(per_cu, 1));
     pl.ran = "k_stft_ft16";
+    if constexpr (SPEC < 2 && FPB == kFatFrames) {
+        // every store of a tile a whole line (what the kernel calls lines_whole), float32 samples: the tiles are claimed at run time (DYN)
+        if (pl.stft_dynamic && pl.d_claim && kern == k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, FPB> && row_pitch(pl, T) % 16 == 0 &&
+            reinterpret_cast<uintptr_t>(out) % 128 == 0) {
+            static_assert(F::SMEM + kClaimLdsBytes <= (size_t)kMaxLdsBytes, "tile + tables + claim words exceed LDS");
+            auto dyn = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, FPB, 0, false, true>;
+            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(dyn), pl.device, F::SMEM + kClaimLdsBytes); e != hipSuccess) return e;
+            hipLaunchKernelGGL(dyn, dim3((unsigned)grid), dim3(F::NT), F::SMEM + kClaimLdsBytes, pl.stream, x, pl.d_window,
+                               LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass, pl.d_tw_aux, out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles,
+                               TileClaim{(int)total, 0, pl.d_claim});
+            return hipGetLastError();
+        }
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F::NT), F::SMEM, pl.stream, x, pl.d_window, LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass,
                        pl.d_tw_aux, out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, (int)total);
     return hipGetLastError();
@@ -3361,6 +3452,14 @@ static hipError_t run_stft_fat_ragged(const zafx_plan& pl, const float* x, float
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
     const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus * std::max(per_cu, 1));
     pl.ran = "k_stft_ft16_ragged";
+    if (pl.stft_dynamic && pl.d_claim) {   // tiles claimed at run time (DYN): the tile count is rarely a multiple of the grid here
+        static_assert(F::SMEM + kClaimLdsBytes <= (size_t)kMaxLdsBytes, "tile + tables + claim words exceed LDS");
+        auto dyn = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, kFatFrames, 0, true, true>;
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(dyn), pl.device, F::SMEM + kClaimLdsBytes); e != hipSuccess) return e;
+        hipLaunchKernelGGL(dyn, dim3((unsigned)grid), dim3(F::NT), F::SMEM + kClaimLdsBytes, pl.stream, x, pl.d_window,
+                           LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass, pl.d_tw_aux, out, tab, pl.H, 0, 0, (int)n_clips, TileClaim{(int)total_tiles, 0, pl.d_claim});
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F::NT), F::SMEM, pl.stream, x, pl.d_window, LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass,
                        pl.d_tw_aux, out, tab, pl.H, 0, 0, (int)n_clips, (int)total_tiles);
     return hipGetLastError();
@@ -3404,3 +3503,21 @@ hipError_t launch_istft(const zafx_plan& pl, const float2* spec, float* y, int64
 
 ZAFX_PROF_EXPORT(zafx_debug_prof_istft, g_prof)
 ZAFX_PROF_EXPORT(zafx_debug_prof_stft, g_prof_stft)
+#ifdef ZAFX_PROF
+// Finish times per workgroup of k_stft_ft16 (PROF_TAIL_*): bind (on != 0) points the kernels of this library at an array the plan owns
+// (four words for each of up to 2 n_cus workgroups, zeroed), read waits for the plan's stream and copies n_words of it out.
+extern "C" int zafx_debug_stft_tail_bind(zafx_plan* pl, int on) {
+    if (!pl || hipSetDevice(pl->device) != hipSuccess) return 1;
+    const size_t bytes = (size_t)pl->n_cus * 2 * 4 * sizeof(unsigned long long);
+    if (on && !pl->d_tail && hipMalloc(reinterpret_cast<void**>(&pl->d_tail), bytes) != hipSuccess) return 1;
+    if (hipStreamSynchronize(pl->stream) != hipSuccess) return 1;
+    if (on && hipMemset(pl->d_tail, 0, bytes) != hipSuccess) return 1;
+    unsigned long long* p = on ? pl->d_tail : nullptr;
+    return hipMemcpyToSymbol(HIP_SYMBOL(zafx::g_stft_tail), &p, sizeof(p)) != hipSuccess;
+}
+extern "C" int zafx_debug_stft_tail_read(zafx_plan* pl, unsigned long long* out, int n_words) {
+    if (!pl || !pl->d_tail || n_words > pl->n_cus * 2 * 4) return 1;
+    if (hipStreamSynchronize(pl->stream) != hipSuccess) return 1;
+    return hipMemcpy(out, pl->d_tail, (size_t)n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess;
+}
+#endif
