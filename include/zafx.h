@@ -26,6 +26,9 @@
  *   ZAFX_DCT                       dct / dst       zaf.py:703-839, :842-981 (np.fft.fft of the 2N-2 /
  *                                                  2N+2 / 4N / 8N point extension :771, :791, :816, :834,
  *                                                  :909, :926, :948, :974; orthonormal scalings)
+ *   ZAFX_CENTER / _CENTER_SIDES    the center / sides example of istft's docstring, zaf.py:155-198 (stft of both
+ *                                  channels :176-177, magnitudes :181-182, masks :185-186, masked spectra :190-191,
+ *                                  istft :194-195, sides :198) in one kernel
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -63,11 +66,22 @@ enum zafx_kind {
     ZAFX_CHROMA = 8, /* in (B, N) f32            -> out (B, octave_resolution, T) or transposed    */
     ZAFX_LINEAR = 9, /* in (B, window_length) f32 -> out (B, n_filters) f32: y = M x per clip (a caller's own dense
                         map; dct / dst lengths the FFT form below does not take)                          */
-    ZAFX_DCT = 10    /* in (B, N) f32 -> out (B, N) f32: the orthonormal dct / dst of zaf.py:703-839 / :842-981, type
+    ZAFX_DCT = 10,   /* in (B, N) f32 -> out (B, N) f32: the orthonormal dct / dst of zaf.py:703-839 / :842-981, type
                         params.transform_type = 1..4, params.transform_sine = 0 (dct) / 1 (dst), N = window_length;
                         one M-point complex FFT per vector where M = N/2 (N-1 / N+1 for type I) is a power of two 32..8192,
                         every other N from 2 to 8192 on Bluestein convolutions: types 2-4 of N = 4 j two transforms of
                         2^ceil(log2(N-1)) points around the N/2-point transform, the rest two of 2^ceil(log2(2N-1)) (chirp-z sum) */
+    ZAFX_CENTER = 11,       /* in (B, N, 2) f32, interleaved stereo as wavread returns it -> out (B, N, 2) f32: the center of zaf.py:155-198,
+                               center[:, c] = istft(concat(m_c, m_c[-2:0:-1]) * stft(x[:, c]))[0:N] with the masks m_0 = (b < a) ? b / a : 1,
+                               m_1 = (a < b) ? a / b : 1 of a = |stft(x[:, 0])|, b = |stft(x[:, 1])| on rows 0..W/2.  The masks equal the
+                               reference's min(a, b) / a wherever that is finite; where the reference divides 0 by 0 (an exactly silent bin,
+                               which it turns into a frame of NaNs) the masked bin is 0, the limit value -- the one deliberate departure.
+                               float32 only, window_length 256 / 512 / 1024 / 2048, step_length = window_length / 2 (zaf.stft pads W/2 in
+                               front and zaf.istft trims W - H: at any other hop the reference's example fails on a shape mismatch);
+                               n_in = N sample frames; zafx_plan_out_dims: dims[0] = sample frames written per clip, dims[1] = 2 */
+    ZAFX_CENTER_SIDES = 12  /* as ZAFX_CENTER -> out (B, 2, N, 2): block 0 of a clip the center, block 1 the sides = input - center (:198);
+                               the center is bit-identical to ZAFX_CENTER's.  Neither kind takes zafx_execute_ragged, zafx_execute_pcm or
+                               zafx_run_host_pcm */
 };
 
 enum zafx_layout {

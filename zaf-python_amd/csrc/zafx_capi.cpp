@@ -13,6 +13,7 @@
 #include <string>
 #include <utility>
 
+#include "zafx_center.hpp"
 #include "zafx_internal.hpp"
 
 #ifndef ZAFX_STFT_FAT8_TABLES
@@ -295,6 +296,18 @@ static void bluestein_tables(int count, long long den, int log2m, std::vector<cl
             }
 }
 
+static bool is_center_kind(int kind) { return kind == ZAFX_CENTER || kind == ZAFX_CENTER_SIDES; }
+// Geometry of the center / sides kinds, checked before the device is touched (so also where there is none).
+static int check_center_params(const zafx_params* p) {
+    if (p->precision != ZAFX_PRECISION_F32) return fail_msg("center / sides: precision must be ZAFX_PRECISION_F32 (ZAFX_PRECISION_F64 is not available for these kinds)");
+    const int lw = ilog2_exact(p->window_length);
+    if (lw < 0 || !zafx::center_supported(lw)) return fail_msg("center / sides: window_length must be a power of two in [256, 2048]");
+    if (p->step_length != p->window_length / 2)
+        return fail_msg("center / sides: step_length must be window_length / 2 (zaf.stft pads window_length / 2 and zaf.istft trims window_length - step_length: "
+                        "the two agree at no other hop)");
+    if (p->layout != ZAFX_LAYOUT_FT || p->row_align > 1) return fail_msg("center / sides: layout and row_align do not apply (no 2-D array crosses the boundary)");
+    return 0;
+}
 static bool is_stft_family(int kind) { return kind == ZAFX_STFT || kind == ZAFX_ISTFT || kind == ZAFX_MEL || kind == ZAFX_MFCC; }
 static bool is_mdct_family(int kind) { return kind == ZAFX_MDCT || kind == ZAFX_IMDCT; }
 static bool is_cqt_family(int kind) { return kind == ZAFX_CQT || kind == ZAFX_CHROMA; }
@@ -888,6 +901,8 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
         return fail_msg("row_align must be 0 or a power of two <= 1024");
     if (params->row_align > 1 && (params->layout != ZAFX_LAYOUT_FT || kind == ZAFX_LINEAR || kind == ZAFX_DCT))
         return fail_msg("row_align applies to the 2-D arrays of ZAFX_LAYOUT_FT plans only");
+    if (is_center_kind(kind))
+        if (int rc = check_center_params(params)) return rc;
     {
         int n_dev = 0;
         ZAFX_HIP(hipGetDeviceCount(&n_dev));
@@ -950,6 +965,12 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
         aux.resize((size_t)n / 2 + 1);
         for (int k = 0; k <= n / 2; ++k) aux[(size_t)k] = unit_root(k, pl->W);
         pl->kernel_name = kind == ZAFX_STFT ? stft_kernel_name(lw - 1, pl->layout) : kind == ZAFX_ISTFT ? istft_kernel_name(lw - 1, pl->layout) : params->n_filters > 256 ? mel_wide_kernel_name() : lw - 1 == 11 ? "k_mel_ft16b" : lw - 1 >= 12 ? mel_wide_kernel_name() : mel_kernel_name();
+    } else if (is_center_kind(kind)) {
+        pl->W = params->window_length;
+        pl->H = params->step_length;
+        pl->log2nf = ilog2_exact(pl->W);   // a stereo sample frame is one complex point: W-point transforms
+        aux.assign(1, cf32{1.f, 0.f});
+        pl->kernel_name = center_kernel_name();
     } else if (is_mdct_family(kind)) {
         pl->W = params->window_length;
         pl->H = pl->W / 2;   // zaf.py:1029
@@ -1068,7 +1089,7 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
     } else {
         return bail("unknown plan kind");
     }
-    pl->log2e = default_log2e(pl->log2nf);
+    pl->log2e = is_center_kind(kind) ? center_log2e(pl->log2nf) : default_log2e(pl->log2nf);
 
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&pl->n_cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -1380,6 +1401,8 @@ int zafx_plan_out_dims(const zafx_plan* pl, int64_t n_in, int64_t dims[2]) {
         case ZAFX_MEL: dims[0] = pl->prm.n_filters; dims[1] = stft_frames(n_in, pl->W, pl->H); return 0;
         case ZAFX_MFCC: dims[0] = pl->prm.n_coefs + (pl->prm.with_mel ? pl->prm.n_filters : 0); dims[1] = stft_frames(n_in, pl->W, pl->H); return 0;
         case ZAFX_ISTFT: dims[0] = std::max<int64_t>(0, n_in * h - (w - h)); dims[1] = 1; return 0;   // zaf.py:217, :236-238
+        case ZAFX_CENTER: dims[0] = n_in; dims[1] = 2; return 0;                                      // sample frames written per clip x channels
+        case ZAFX_CENTER_SIDES: dims[0] = 2 * n_in; dims[1] = 2; return 0;
         case ZAFX_MDCT: dims[0] = w / 2; dims[1] = (n_in + h - 1) / h + 1; return 0;                  // zaf.py:1033
         case ZAFX_IMDCT: dims[0] = std::max<int64_t>(0, h * (n_in - 1) - 1); dims[1] = 1; return 0;    // zaf.py:1132, :1182
         case ZAFX_CQT: dims[0] = pl->prm.n_bins; dims[1] = n_in / h; return 0;                         // zaf.py:606
@@ -1405,6 +1428,7 @@ int zafx_plan_row_pitch(const zafx_plan* pl, int64_t n_in, int64_t* pitch) {
             return 0;
         case ZAFX_IMDCT: *pitch = pl->layout == ZAFX_LAYOUT_FT ? row_pitch(*pl, n_in) : pl->W / 2; return 0;
         case ZAFX_LINEAR: case ZAFX_DCT: *pitch = dims[0]; return 0;
+        case ZAFX_CENTER: case ZAFX_CENTER_SIDES: *pitch = 2; return 0;   // a row is one sample frame: (L, R)
         default: *pitch = pl->layout == ZAFX_LAYOUT_FT ? row_pitch(*pl, dims[1]) : dims[0]; return 0;
     }
 }
@@ -1465,6 +1489,11 @@ int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, 
         case ZAFX_LINEAR:
             e = launch_linear(*pl, (const float*)d_in, (float*)d_out, n_clips);
             break;
+        case ZAFX_CENTER:
+        case ZAFX_CENTER_SIDES:
+            if (pl->cola_gain == 0.f) return fail_msg("center / sides: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+            e = launch_center(*pl, (const float*)d_in, (float*)d_out, n_clips, n_in);
+            break;
         case ZAFX_DCT:
             e = pl->bs_log2m > 0 && pl->dct_half == 0 ? launch_dct_bs32(*pl, (const float*)d_in, (float*)d_out, n_clips) : launch_dct(*pl, (const float*)d_in, (float*)d_out, n_clips);
             break;
@@ -1509,6 +1538,7 @@ static int ragged_block(const zafx_plan* pl, int64_t len, int64_t* elems, int64_
 int zafx_plan_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int64_t* out_offsets) {
     if (!pl || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
     if (n_clips < 0) return fail_msg("negative size");
+    if (is_center_kind(pl->kind)) return fail_msg("ragged batches: center / sides plans take clips of one length (ragged stereo batches are not implemented)");
     if (!ragged_kind(pl->kind)) return fail_msg("ragged batches: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
     out_offsets[0] = 0;
     for (int64_t i = 0; i < n_clips; ++i) {
@@ -1564,6 +1594,7 @@ static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& r
 int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
     if (!pl) return fail_msg("null plan");
     if (n_clips < 0) return fail_msg("negative size");
+    if (is_center_kind(pl->kind)) return fail_msg("zafx_execute_ragged: center / sides plans take clips of one length (ragged stereo batches are not implemented)");
     if (!ragged_kind(pl->kind)) return fail_msg("zafx_execute_ragged: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
     if (n_clips == 0) return 0;
     if (!in_offsets || !lengths) return fail_msg("null argument");
@@ -1652,6 +1683,10 @@ static int clip_bytes(const zafx_plan* pl, int64_t n_in, int64_t* in_b, int64_t*
             *in_b = (ft ? (int64_t)(pl->W / 2) * pitch : n_in * (pl->W / 2)) * real;
             *out_b = dims[0] * real;
             return 0;
+        case ZAFX_CENTER: case ZAFX_CENTER_SIDES:
+            *in_b = n_in * 2 * real;
+            *out_b = dims[0] * 2 * real;
+            return 0;
         case ZAFX_LINEAR: case ZAFX_DCT:
             *in_b = (int64_t)pl->W * 4;
             *out_b = dims[0] * 4;
@@ -1731,6 +1766,7 @@ int zafx_execute_pcm(zafx_plan* pl, const void* d_pcm, void* d_out, int64_t n_cl
     if (n_channels < 1 || n_channels > 64) return fail_msg("n_channels must be in [1, 64]");
     if (sample_bytes != 2 && sample_bytes != 4) return fail_msg("sample_bytes must be 2 (int16) or 4 (int32)");
     if (pl->prm.precision != ZAFX_PRECISION_F32) return fail_msg("PCM ingest feeds the float32 plans");
+    if (is_center_kind(pl->kind)) return fail_msg("PCM ingest: center / sides plans take float32 stereo (integer stereo ingest is not implemented)");
     switch (pl->kind) {
         case ZAFX_STFT: case ZAFX_MDCT: case ZAFX_MEL: case ZAFX_MFCC: case ZAFX_CQT: case ZAFX_CHROMA: case ZAFX_DCT: break;
         default: return fail_msg("PCM ingest feeds the plans that take samples (stft, mdct, mel, mfcc, cqt, chroma, dct)");
@@ -1852,6 +1888,7 @@ int zafx_run_host_pcm(zafx_plan* pl, const void* h_pcm, void* h_out, int64_t n_c
     if (n_channels < 1 || n_channels > 64) return fail_msg("n_channels must be in [1, 64]");
     if (sample_bytes != 2 && sample_bytes != 4) return fail_msg("sample_bytes must be 2 (int16) or 4 (int32)");
     if (pl->prm.precision != ZAFX_PRECISION_F32) return fail_msg("PCM ingest feeds float32 plans");
+    if (is_center_kind(pl->kind)) return fail_msg("PCM ingest: center / sides plans take float32 stereo (integer stereo ingest is not implemented)");
     switch (pl->kind) {
         case ZAFX_STFT: case ZAFX_MDCT: case ZAFX_MEL: case ZAFX_MFCC: case ZAFX_CQT: case ZAFX_CHROMA: case ZAFX_DCT: break;
         default: return fail_msg("PCM ingest feeds the plans that take samples (stft, mdct, mel, mfcc, cqt, chroma, dct)");

@@ -1,0 +1,186 @@
+// zafx_center.hip -- k_center: the center / sides extraction of zaf.istft's example (zaf.py:155-198) in one kernel.
+//
+// Stereo STFT, the two time-frequency masks, both ISTFTs and sides = input - center without a spectrum ever leaving the CU
+// (zafx_center.hpp has the arithmetic and the mask's one departure from the reference).  Structure:
+//
+//   * An interleaved stereo sample frame (L, R) IS one complex point of z = L + i R: a frame of W sample frames is loaded as W
+//     float2, multiplied by the window and transformed as ONE W-point complex FFT.  Up to W = 1024 64 lanes own a frame (W / 64
+//     points per lane) and every exchange of the transform is wave-local (frame_sync<64>: no workgroup barrier inside a transform);
+//     at W = 2048 two wavefronts share a frame (16 points per lane: with 32 the transform does not fit 256 registers) and
+//     frame_sync is the workgroup's barrier, so every wave runs every tile's transforms, on zeros where its frame is not needed.
+//   * Split, mask and re-pack run in place on the pairs (k, W-k) of the LDS frame; the inverse transform is the forward core on
+//     the swapped parts.  Its real part is the center's left channel, its imaginary part the right one.
+//   * A workgroup of center_tile_frames(log2 W) frames' threads walks the frames of one segment of a clip in order, a tile of that many frames at
+//     a time.  Only step_length = W/2 exists (zaf.stft pads W/2 in front, zaf.istft trims W - H: the two agree at no other hop), so an
+//     output block b (sample frames b H .. b H + H - 1) is the second half of frame b plus the first half of frame b + 1: the wave
+//     of frame b + 1 writes it, taking the other half from its neighbour's LDS frame or, for the first frame of a tile, from the
+//     carry the previous tile left in LDS.  A segment starts by transforming the frame in front of its first block (one halo frame
+//     per segment), so it produces the same bits wherever it starts; every sample is the sum of exactly two terms.
+//   * SIDES: the lanes that write block b hold its input samples already (the first half of frame b + 1, before the window).
+#include <algorithm>
+
+#include "zafx_center.hpp"
+#include "zafx_internal.hpp"
+
+namespace zafx {
+
+template <int LOG2W>
+struct CenterCfg {
+    static constexpr int LOG2E = center_log2e(LOG2W);
+    using C = FftCfg<LOG2W, LOG2E>;
+    static constexpr int W = 1 << LOG2W, H = W / 2, E = C::E, P = C::P, F = center_tile_frames(LOG2W), NT = P * F;
+    static_assert(P == 64 || P == 128, "k_center: one or two wavefronts per frame");
+    // LDS (float2 slots): F padded frames | the carry (second half of the tile's last frame, H points) | the pass tables
+    static constexpr int OFF_CARRY = F * C::PITCH, OFF_TW = OFF_CARRY + H, SLOTS = OFF_TW + C::TW;
+    static constexpr size_t SMEM = (size_t)SLOTS * 8;
+    static_assert(SMEM <= (size_t)kMaxLdsBytes, "k_center: frames + carry + tables exceed LDS");
+};
+
+// One segment = blocks [seg * seg_blocks, min(n_blocks, (seg + 1) * seg_blocks)) of one clip; unit u = clip * n_segs + seg.
+template <int LOG2W, bool SIDES>
+__global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* __restrict__ x, const float* __restrict__ window, const float2* __restrict__ tw_g,
+                                                                   float2* __restrict__ out, long long n_samples, int n_blocks, int seg_blocks, int n_segs,
+                                                                   long long n_units, float gain) {
+    using K = CenterCfg<LOG2W>;
+    using C = typename K::C;
+    constexpr int E = K::E, H = K::H, W = K::W, F = K::F, P = K::P, HE = E / 2;
+    extern __shared__ float2 smem[];
+    const int tid = threadIdx.x, lane = tid & (P - 1), f = __builtin_amdgcn_readfirstlane(tid / P);   // lane: the thread's place among its frame's P
+    float2* const buf = smem + f * C::PITCH;
+    float2* const carry = smem + K::OFF_CARRY;
+    float2* const tw = smem + K::OFF_TW;
+    for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
+    __syncthreads();
+    const unsigned clip_bytes = (unsigned)(n_samples * 8);   // (the launcher keeps n_samples below 2^28)
+
+    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const long long clip = u / n_segs;
+        const int seg = (int)(u - clip * n_segs);
+        const int b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);   // blocks [b0, b1) need frames b0 .. b1
+        const float2* const xc = x + clip * n_samples;
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
+        float2* const oc = out + clip * n_samples * (SIDES ? 2 : 1);
+        for (int j0 = b0; j0 <= b1; j0 += F) {
+            const int j = j0 + f;              // this wave's frame: sample frames (j - 1) H .. (j + 1) H - 1
+            const bool live = j <= b1;         // (wave-uniform)
+            float2 v[E], raw[HE];
+            {
+                // samples in front of the clip and at or behind its end read as zero: the descriptor's range check does both, and a
+                // frame that is not needed reads nothing but zeros (its threads still meet the others at every frame_sync)
+                const int s0 = (j - 1) * H + lane;
+#pragma unroll
+                for (int i = 0; i < E; ++i) v[i] = buf_load_f32x2(rs, live ? (s0 + P * i) * 8 : -8);
+                if constexpr (SIDES) {
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) raw[i] = v[i];   // the frame's first half is the input of block j - 1, which this wave writes
+                }
+#pragma unroll
+                for (int i = 0; i < E; ++i) v[i] = cscale(v[i], window[lane + P * i]);
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+                // pairs (k, W - k), k = lane + P m < H; k = 0 pairs with itself, and lane 0 takes k = H as well
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    const int k = lane + P * m, kn = (W - k) & (W - 1);
+                    const int pk = phys_t<C::PS>(k), pn = phys_t<C::PS>(kn);
+                    float2 ck, cn;
+                    center_pair(buf[pk], buf[pn], ck, cn);
+                    buf[pk] = center_swap(ck);
+                    buf[pn] = center_swap(cn);
+                }
+                if (lane == 0) {
+                    const int ph = phys_t<C::PS>(H);
+                    float2 ck, cn;
+                    center_pair(buf[ph], buf[ph], ck, cn);
+                    buf[ph] = center_swap(ck);
+                }
+                frame_sync<P>();
+                regs_read<LOG2W, K::LOG2E>(v, buf, lane);
+                frame_sync<P>();
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+            }
+            lds_barrier();   // A: every frame of the tile lies in LDS
+            // block j - 1 = second half of frame j - 1 + first half of frame j
+            const int b = j - 1;
+            const bool writes = live && b >= b0 && (f > 0 || j0 > b0);
+            const bool hands_on = f == F - 1 && live && j < b1;   // the tile's last frame: its second half is the next tile's carry
+            float2 y[HE], keep[HE];
+            if (writes) {
+                const float2* const prev = f > 0 ? buf - C::PITCH : nullptr;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    const int n = lane + P * i;
+                    const float2 a = f > 0 ? prev[phys_t<C::PS>(H + n)] : carry[n];
+                    y[i] = center_swap(cscale(cadd(a, buf[phys_t<C::PS>(n)]), gain));
+                }
+            }
+            if (hands_on) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) keep[i] = buf[phys_t<C::PS>(H + lane + P * i)];
+            }
+            lds_barrier();   // B: the frames and the carry have been read
+            if (hands_on) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) carry[lane + P * i] = keep[i];
+            }
+            if (writes) {
+                const long long s = (long long)b * H + lane;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    if (s + P * i < n_samples) {   // nothing is written at or beyond sample frame N
+                        oc[s + P * i] = y[i];
+                        if constexpr (SIDES) oc[n_samples + s + P * i] = csub(raw[i], y[i]);
+                    }
+                }
+            }
+        }
+        lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
+    }
+}
+
+static const char* const kCenterName = "k_center";
+const char* center_kernel_name() { return kCenterName; }
+
+template <int LOG2W, bool SIDES>
+static hipError_t run_center(const zafx_plan& pl, const float2* x, float2* out, int64_t n_clips, int64_t n_samples) {
+    using K = CenterCfg<LOG2W>;
+    auto kern = k_center<LOG2W, SIDES>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
+    const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
+    if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
+    // segments: whole clips when there are enough of them to load every workgroup; otherwise cut, but never below two tiles
+    // (2 F - 1 blocks) a segment -- each pays one halo frame
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / K::SMEM));
+    const long long slots = (long long)pl.n_cus * per_cu;
+    long long segs = std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
+    if (n_clips >= slots) segs = 1;
+    segs = std::min<long long>(segs, std::max<long long>(1, n_blocks / (2 * K::F - 1)));
+    const int64_t seg_blocks = (n_blocks + segs - 1) / segs;
+    segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    const long long units = segs * n_clips;
+    const long long grid = std::min<long long>(units, slots);
+    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // ifft's 1 / W, then zaf.py:241
+    pl.ran = kCenterName;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, out, (long long)n_samples, (int)n_blocks,
+                       (int)seg_blocks, (int)segs, units, gain);
+    return hipGetLastError();
+}
+
+hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples) {
+    if (n_samples >= (1LL << 28)) {
+        set_error("center / sides: clips of 2^28 sample frames and more are not supported");
+        return hipErrorInvalidValue;
+    }
+    const bool sides = pl.kind == ZAFX_CENTER_SIDES;
+    const float2* xi = reinterpret_cast<const float2*>(x);
+    float2* o = reinterpret_cast<float2*>(out);
+    switch (pl.log2nf) {   // log2 of the complex FFT length = log2(W): a sample frame is one complex point
+        case 8: return sides ? run_center<8, true>(pl, xi, o, n_clips, n_samples) : run_center<8, false>(pl, xi, o, n_clips, n_samples);
+        case 9: return sides ? run_center<9, true>(pl, xi, o, n_clips, n_samples) : run_center<9, false>(pl, xi, o, n_clips, n_samples);
+        case 10: return sides ? run_center<10, true>(pl, xi, o, n_clips, n_samples) : run_center<10, false>(pl, xi, o, n_clips, n_samples);
+        case 11: return sides ? run_center<11, true>(pl, xi, o, n_clips, n_samples) : run_center<11, false>(pl, xi, o, n_clips, n_samples);
+    }
+    set_error("center / sides: window_length must be 256, 512, 1024 or 2048");
+    return hipErrorInvalidValue;
+}
+
+}  // namespace zafx

@@ -308,6 +308,8 @@ hipError_t launch_dct(const zafx_plan& pl, const float* x, float* y, int64_t n_r
 bool dct_supported(int log2m);   // log2 of the complex FFT length M
 const char* dct_kernel_name();
 const char* linear_kernel_name();
+hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples);   // zafx_center.hip: ZAFX_CENTER / ZAFX_CENTER_SIDES
+const char* center_kernel_name();
 hipError_t launch_pcm_to_float(hipStream_t stream, const void* pcm, float* out, int64_t n_total, int n_channels, int sample_bytes);
 
 // names of the dominant kernels (what rocprofv3 --kernel-trace prints, prefix match)

@@ -6,6 +6,8 @@
 Drop-in functions (zaf.py signatures, float64 / complex128 results):
     stft, istft, melfilterbank, melspectrogram, mfcc, cqtkernel, cqtspectrogram,
     cqtchromagram, mdct, imdct, dct, dst
+The center / sides example of zaf.istft's docstring (stereo STFT, masks, ISTFT, subtraction) in one kernel:
+    centersides ((N, 2) -> (center, sides)), centersides_batch ((B, N, 2) float32), center_plan
 Batched extension ((clips, samples) in, float32 / complex64 out):
     stft_batch, istft_batch, mdct_batch, imdct_batch, melspectrogram_batch, mfcc_batch,
     cqtspectrogram_batch, cqtchromagram_batch, dct_batch, dst_batch, mel_mfcc_batch (melspectrogram + mfcc from one set of transforms);
@@ -18,10 +20,10 @@ launch where the library has the kernel):
 Device-resident API: Plan, DeviceBuffer, Comm, *_plan factories, shard helpers; one process per GPU: launch.Rendezvous,
 spawn_ranks (file rendezvous + self-launcher, no torch.distributed).
 """
-from ._lib import (CHROMA, CQT, DCT, IMDCT, ISTFT, LAYOUT_FT, LAYOUT_TF, LINEAR, MDCT, MEL, MFCC, STFT, ZafxError, device_count,
+from ._lib import (CENTER, CENTER_SIDES, CHROMA, CQT, DCT, IMDCT, ISTFT, LAYOUT_FT, LAYOUT_TF, LINEAR, MDCT, MEL, MFCC, STFT, ZafxError, center_tile_frames, device_count,
                    device_name, library_path)
 from .constants import cqtkernel, dct2_rows, dct_matrix, dst_matrix, hamming, kaiser_bessel_derived, melfilterbank, sine
-from .core import (Comm, DeviceBuffer, Plan, clear_plan_cache, cqt_plan, cqtchromagram, cqtchromagram_batch, dct, dct_batch, dst,
+from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersides_batch, clear_plan_cache, cqt_plan, cqtchromagram, cqtchromagram_batch, dct, dct_batch, dst,
                    dst_batch, linear_plan, dct_plan, dct_fft_length,
                    cqtspectrogram, cqtspectrogram_batch, imdct, imdct_batch, istft, istft_batch, istft_plan, mdct,
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,

@@ -10,6 +10,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # enum zafx_kind
 STFT, ISTFT, MDCT, IMDCT, MEL, MFCC, CQT, CHROMA, LINEAR, DCT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+CENTER, CENTER_SIDES = 11, 12   # stereo (B, N, 2) -> center (B, N, 2) / center and sides (B, 2, N, 2)
+
+
+def center_tile_frames(window_length):
+    """Frames of one tile of k_center (center_tile_frames in csrc/zafx_center.hpp): the tests place clip lengths around its multiples."""
+    return 4 if window_length >= 2048 else 8
 # enum zafx_layout
 LAYOUT_FT, LAYOUT_TF = 0, 1
 # enum zafx_spectrum

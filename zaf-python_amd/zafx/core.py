@@ -372,6 +372,10 @@ class Plan:
         rows, frames = self.out_dims(n_in)
         if self.kind in self._FORWARD:
             return (n_clips, rows, self.row_pitch(n_in)) if self.layout == _lib.LAYOUT_FT else (n_clips, frames, rows)
+        if self.kind == _lib.CENTER:
+            return (n_clips, rows, 2)
+        if self.kind == _lib.CENTER_SIDES:   # block 0 the center, block 1 the sides
+            return (n_clips, 2, rows // 2, 2)
         return (n_clips, rows)
 
     @property
@@ -898,6 +902,32 @@ def cqt_plan(sampling_frequency, time_resolution, cqt_kernel, octave_resolution=
     return _cached(key, make)
 
 
+def _center_window(window_function, step_length):
+    """Window and hop of the center / sides kinds, checked without the library: float32 kernels for the powers of two 256 ... 2048,
+    and only the hop window_length / 2 (zaf.stft pads W/2 in front, zaf.istft trims W - H: the example works at no other hop)."""
+    w = np.asarray(window_function, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError("window_function must be 1-D")
+    if not _pow2(len(w)) or not 256 <= len(w) <= 2048:
+        raise ValueError(f"center / sides kernels need a power-of-two window_length in [256, 2048], got {len(w)}")
+    if step_length is not None and _as_step(step_length) != len(w) // 2:
+        raise ValueError(f"step_length must be window_length / 2 = {len(w) // 2} for the center / sides extraction, got {step_length}")
+    return w
+
+
+def center_plan(window_function, device=0, sides=True):
+    """Plan of the center / sides extraction (zaf.py:155-198) at step_length = window_length / 2: stereo (B, N, 2) float32 in,
+    (B, 2, N, 2) out (block 0 the center, block 1 the sides), or (B, N, 2), the center alone, with sides=False."""
+    w = _center_window(window_function, None)
+    key = ("center", device, len(w), bool(sides), _digest(w))
+
+    def make():
+        p = Plan(_lib.CENTER_SIDES if sides else _lib.CENTER, device, window_length=len(w), step_length=len(w) // 2)
+        p.set_window(w)
+        return p
+    return _cached(key, make)
+
+
 def linear_plan(matrix, device=0):
     """y = matrix @ x for every clip (the carrier of the dct / dst transforms)."""
     m = np.ascontiguousarray(matrix, dtype=np.float64)
@@ -997,6 +1027,25 @@ def istft_batch(spectra, window_function, step_length, layout="FT", device=0, on
                       lambda a: istft_plan(w, step_length, layout, device, onesided, f64, row_align=a), frames=nt, row_align=row_align)
     out = _run_host_into(plan, s if plan.row_align > 1 else np.ascontiguousarray(s, dtype=plan.in_dtype), nt, out)
     return out if f64 else out.astype(np.float32, copy=False)   # (a very small hop is computed in float64 whatever f64 says)
+
+
+def centersides_batch(clips, window_function, step_length=None, sides=True, device=0, out=None):
+    """The center / sides example of zaf.istft's docstring (zaf.py:155-198) for a batch of stereo clips, in one kernel:
+    (B, N, 2) -> (center, sides), float32 (B, N, 2) each -- views of one (B, 2, N, 2) result (which `out`, if given, is) -- or the
+    center alone with sides=False.  step_length: None or window_length / 2, the only hop at which the example works.
+
+    The masks are (b < a) ? b / a : 1 and (a < b) ? a / b : 1 of the channels' magnitudes a, b: the reference's min(a, b) / a
+    wherever that is finite; where the reference divides 0 by 0 (an exactly silent bin: it returns a frame of NaNs) the
+    masked bin is 0, the limit value."""
+    w = _center_window(window_function, step_length)
+    a = np.asarray(clips)
+    if a.ndim != 3 or a.shape[2] != 2:
+        raise ValueError(f"clips must be stereo, (clips, sample frames, 2), got shape {a.shape}")
+    if np.iscomplexobj(a):
+        raise ValueError("clips must be real")
+    x = np.ascontiguousarray(a, dtype=np.float32)
+    res = center_plan(w, device, sides).run_host(x, x.shape[1], out=out)
+    return (res[:, 0], res[:, 1]) if sides else res
 
 
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
@@ -1380,6 +1429,16 @@ def istft(audio_stft, window_function, step_length):
     if s.ndim != 2:
         raise ValueError("audio_stft must be 2-D (window_length, number_times)")
     return istft_batch(s[None], window_function, step_length, f64=_PRECISION["value"] == "f64")[0].astype(np.float64)
+
+
+def centersides(audio_signal, window_function, step_length):
+    """The example of zaf.istft's docstring (zaf.py:155-198) in one call: (N, 2) stereo -> (center_signal, sides_signal), float64 (N, 2)
+    each; step_length must be window_length / 2 (see centersides_batch, also for the mask's one departure from the reference)."""
+    a = np.asarray(audio_signal)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"audio_signal must be stereo, (sample frames, 2), got shape {a.shape}")
+    center, sides = centersides_batch(a[None], window_function, step_length)
+    return center[0].astype(np.float64), sides[0].astype(np.float64)
 
 
 def melspectrogram(audio_signal, window_function, step_length, mel_filterbank):
