@@ -39,6 +39,12 @@
  * are thread-safe; calls on one plan must be serialised by the caller.
  * All device arrays are float32 / complex64 (interleaved re,im), C-contiguous -- float64 /
  * complex128 for plans created with ZAFX_PRECISION_F64.
+ * A device array may start anywhere on the grid of its real type -- 4 bytes for the float32 kinds (complex64
+ * included: 4, not 8), 8 for the float64 ones (complex128 included), 2 for int16 and 4 for int32 PCM --, e.g. a slice
+ * of a batch or a piece of an arena; the fast routes additionally want the base on a 128-byte line (what zafx_alloc
+ * returns), other bases run on slower forms of the same kernels or on the generic ones (zafx_plan_last_kernel_name).
+ * Nothing outside the arrays is read into a result or written: not the bytes in front of element 0, not those behind
+ * the last element, not the row padding of a row_align plan, and no clip's result depends on another clip's samples.
  */
 #ifndef ZAFX_H
 #define ZAFX_H
