@@ -87,7 +87,7 @@ enum zafx_kind {
                                n_in = N sample frames; zafx_plan_out_dims: dims[0] = sample frames written per clip, dims[1] = 2 */
     ZAFX_CENTER_SIDES = 12  /* as ZAFX_CENTER -> out (B, 2, N, 2): block 0 of a clip the center, block 1 the sides = input - center (:198);
                                the center is bit-identical to ZAFX_CENTER's.  Neither kind takes zafx_execute_ragged, zafx_execute_pcm or
-                               zafx_run_host_pcm */
+                               zafx_run_host_pcm; clips of different lengths go through zafx_execute_center_ragged */
 };
 
 enum zafx_layout {
@@ -212,7 +212,9 @@ int zafx_sync(zafx_plan* plan);
  * Output placement: clip i of lengths[i] samples gets its block of the output array at element out_offsets[i];
  * out_offsets[n_clips] = total elements.  FT layout: F rows at zafx_plan_row_pitch(plan, lengths[i]); TF: T_i x F compact.
  * T_i is zafx_plan_out_dims(plan, lengths[i])[1] (a length of 0 gives the reference's single all-zero frame).  The blocks lie
- * back to back, so every block starts on a 128-byte line when the plan's rows are whole lines and the array does. */
+ * back to back, so every block starts on a 128-byte line when the plan's rows are whole lines and the array does.
+ * ZAFX_CENTER / ZAFX_CENTER_SIDES plans are refused here and by zafx_execute_ragged: their ragged batches have an entry point
+ * of their own, zafx_execute_center_ragged below (the output has the input's shape, so there is no layout to ask for). */
 int zafx_plan_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64_t n_clips, int64_t* out_offsets);
 /* Enqueue the transform of n_clips clips of different lengths on the plan's stream (asynchronous): clip i is lengths[i]
  * samples at element in_offsets[i] of d_in; its result goes to the block zafx_plan_ragged_layout assigns.  The two host
@@ -223,6 +225,17 @@ int zafx_plan_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64
  * ("k_mel2_ragged").  Everything else runs one zafx_execute per clip on the plan's stream ("per-clip <kernel>"). */
 int zafx_execute_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
                         int64_t n_clips);
+/* The center / sides extraction of n_clips stereo clips of different lengths in ONE launch (ZAFX_CENTER and ZAFX_CENTER_SIDES
+ * plans only; last kernel "k_center_ragged"), enqueued on the plan's stream (asynchronous).  Offsets and lengths count sample
+ * frames (one sample frame = L, R = 8 bytes): clip i is lengths[i] sample frames at sample frame in_offsets[i] of d_in -- clips
+ * may lie back to back, each is padded with zeros of its own -- and its center goes to sample frame out_offsets[i] of d_out;
+ * under ZAFX_CENTER_SIDES its sides follow directly behind, at out_offsets[i] + lengths[i] (the (2, N_i, 2) block of the
+ * equal-length kind, one per clip).  Every clip's result is bit-identical to zafx_execute on that clip alone.  A clip of
+ * length 0 is skipped: nothing of it is written.  The three host arrays are copied before return.  Rejected with a message:
+ * n_clips < 0, negative lengths or offsets, a clip of 2^28 sample frames or more.  NOT checked: that the output blocks do not
+ * overlap -- placing them is the caller's business.  d_in and d_out need 8-byte alignment only. */
+int zafx_execute_center_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
+                               const int64_t* out_offsets, int64_t n_clips);
 /* Bytes of ONE clip on the input and on the output side of the plan for `n_in` (as zafx_plan_out_dims; rows at the
  * plan's pitch): what a host array of n_clips clips must hold for zafx_run_host. */
 int zafx_plan_clip_bytes(const zafx_plan* plan, int64_t n_in, int64_t* in_bytes, int64_t* out_bytes);

@@ -8,12 +8,14 @@
 #include <complex>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
 #include <utility>
 
 #include "zafx_center.hpp"
+#include "zafx_center_units.hpp"
 #include "zafx_internal.hpp"
 
 #ifndef ZAFX_STFT_FAT8_TABLES
@@ -1559,11 +1561,10 @@ static const char* per_clip_name(const char* kernel) {
     return it->second.c_str();
 }
 
-// The table of a native launch (zafx::RgClip records, then the clip of every 16-frame tile) through the plan's page-locked staging copy onto
-// its device copy, on the plan's stream.  The staging copy is written only once the upload of the previous call has left it (rg_ev); the
+// The table of a native launch -- `need` bytes that `fill` writes -- through the plan's page-locked staging copy onto its device copy
+// (pl->d_ragged), on the plan's stream.  The staging copy is written only once the upload of the previous call has left it (rg_ev); the
 // device copy is overwritten in stream order behind the kernels that read it, and a larger one replaces it only once the stream is idle.
-static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& recs, int64_t total_tiles) {
-    const size_t rec_b = recs.size() * sizeof(zafx::RgClip), need = rec_b + (size_t)total_tiles * sizeof(int);
+static int upload_plan_table(zafx_plan* pl, size_t need, const std::function<void(unsigned char*)>& fill) {
     if (!pl->rg_ev) ZAFX_HIP(hipEventCreateWithFlags(&pl->rg_ev, hipEventDisableTiming));
     else ZAFX_HIP(hipEventSynchronize(pl->rg_ev));
     if (pl->ragged_host_bytes < need) {
@@ -1579,16 +1580,23 @@ static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& r
         ZAFX_HIP(hipMalloc(&pl->d_ragged, need));
         pl->ragged_bytes = need;
     }
-    unsigned char* h = static_cast<unsigned char*>(pl->h_ragged);
-    std::memcpy(h, recs.data(), rec_b);
-    int* clip_of = reinterpret_cast<int*>(h + rec_b);
-    for (size_t c = 0; c < recs.size(); ++c) {
-        const int tiles = (recs[c].T + 15) / 16;
-        for (int j = 0; j < tiles; ++j) clip_of[recs[c].first_tile + j] = (int)c;
-    }
+    fill(static_cast<unsigned char*>(pl->h_ragged));
     ZAFX_HIP(hipMemcpyAsync(pl->d_ragged, pl->h_ragged, need, hipMemcpyHostToDevice, pl->stream));
     ZAFX_HIP(hipEventRecord(pl->rg_ev, pl->stream));
     return 0;
+}
+
+// zafx_execute_ragged's table: zafx::RgClip records, then the clip of every 16-frame tile
+static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& recs, int64_t total_tiles) {
+    const size_t rec_b = recs.size() * sizeof(zafx::RgClip);
+    return upload_plan_table(pl, rec_b + (size_t)total_tiles * sizeof(int), [&](unsigned char* h) {
+        std::memcpy(h, recs.data(), rec_b);
+        int* clip_of = reinterpret_cast<int*>(h + rec_b);
+        for (size_t c = 0; c < recs.size(); ++c) {
+            const int tiles = (recs[c].T + 15) / 16;
+            for (int j = 0; j < tiles; ++j) clip_of[recs[c].first_tile + j] = (int)c;
+        }
+    });
 }
 
 int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
@@ -1643,6 +1651,43 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
     }
     const char* last = pl->ran.load(std::memory_order_acquire);
     pl->ran.store(per_clip_name(last ? last : pl->kernel_name.c_str()), std::memory_order_release);
+    return 0;
+}
+
+// Ragged stereo batches of the center / sides kinds: the host cuts the clips into units (center_cut_units), k_center's RAGGED form walks them.
+int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, const int64_t* out_offsets,
+                               int64_t n_clips) {
+    if (!pl) return fail_msg("null plan");
+    if (n_clips < 0) return fail_msg("zafx_execute_center_ragged: negative number of clips");
+    if (!is_center_kind(pl->kind)) return fail_msg("zafx_execute_center_ragged: ZAFX_CENTER and ZAFX_CENTER_SIDES plans only (zafx_execute_ragged takes the forward kinds)");
+    if (n_clips == 0) return 0;
+    if (!in_offsets || !lengths || !out_offsets) return fail_msg("null argument");
+    if (!d_in || !d_out) return fail_msg("null device pointer");
+    for (int64_t i = 0; i < n_clips; ++i) {
+        if (lengths[i] < 0 || in_offsets[i] < 0 || out_offsets[i] < 0)
+            return fail_msg("zafx_execute_center_ragged: negative length or offset of clip " + std::to_string(i));
+        if (lengths[i] >= (1LL << 28))
+            return fail_msg("zafx_execute_center_ragged: clip " + std::to_string(i) + " has 2^28 sample frames or more (not supported)");
+    }
+    if (!pl->d_window) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg("center / sides: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    int tile_frames = 0;
+    long long slots = 0;
+    if (!zafx::center_launch_shape(*pl, &tile_frames, &slots)) return fail_msg("center / sides: window_length must be 256, 512, 1024 or 2048");
+    // ZAFX_CENTER_UNITS_PER_SLOT in the environment: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
+    int per_slot = zafx::kCenterUnitsPerSlot;
+    if (const char* v = std::getenv("ZAFX_CENTER_UNITS_PER_SLOT")) per_slot = std::min(64, std::max(1, std::atoi(v)));
+    const std::vector<zafx::CenterUnit> units = zafx::center_cut_units(lengths, in_offsets, out_offsets, n_clips, pl->W, tile_frames, slots, per_slot);
+    ZAFX_HIP(hipSetDevice(pl->device));
+    if (!units.empty()) {
+        const size_t bytes = units.size() * sizeof(zafx::CenterUnit);
+        if (int rc = upload_plan_table(pl, bytes, [&](unsigned char* h) { std::memcpy(h, units.data(), bytes); })) return rc;
+    }
+    const hipError_t e = zafx::launch_center_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::CenterUnit*>(pl->d_ragged), (long long)units.size());
+    if (e != hipSuccess) {
+        if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_center_ragged", e);
+        return (int)e;
+    }
     return 0;
 }
 

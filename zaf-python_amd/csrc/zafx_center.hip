@@ -17,9 +17,14 @@
 //     carry the previous tile left in LDS.  A segment starts by transforming the frame in front of its first block (one halo frame
 //     per segment), so it produces the same bits wherever it starts; every sample is the sum of exactly two terms.
 //   * SIDES: the lanes that write block b hold its input samples already (the first half of frame b + 1, before the window).
+//   * RAGGED (zafx_execute_center_ragged): clips of different lengths.  The walk is the same; a unit's clip -- the base and the length
+//     its descriptor is built from, the base of its output -- and its blocks come from the unit's record of a device table
+//     (CenterUnit, zafx_center_units.hpp: the host cuts the batch) instead of from clip * n_samples and seg * seg_blocks.  A descriptor
+//     per clip pads every clip with zeros even where the next clip's samples lie right behind it.
 #include <algorithm>
 
 #include "zafx_center.hpp"
+#include "zafx_center_units.hpp"
 #include "zafx_internal.hpp"
 
 namespace zafx {
@@ -37,10 +42,14 @@ struct CenterCfg {
 };
 
 // One segment = blocks [seg * seg_blocks, min(n_blocks, (seg + 1) * seg_blocks)) of one clip; unit u = clip * n_segs + seg.
-template <int LOG2W, bool SIDES>
+// RAGGED: `n_samples` carries the table of unit records (SamplesArg, zafx_internal.hpp: the equal-length instantiations keep their kernel
+// arguments byte for byte), unit u is record u, and n_blocks / seg_blocks / n_segs are not used.
+template <bool RAGGED>
+using CenterSamplesArg = std::conditional_t<RAGGED, const CenterUnit* __restrict__, long long>;   // (restrict: the table is read with scalar loads)
+template <int LOG2W, bool SIDES, bool RAGGED>
 __global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* __restrict__ x, const float* __restrict__ window, const float2* __restrict__ tw_g,
-                                                                   float2* __restrict__ out, long long n_samples, int n_blocks, int seg_blocks, int n_segs,
-                                                                   long long n_units, float gain) {
+                                                                   float2* __restrict__ out, CenterSamplesArg<RAGGED> n_samples, int n_blocks,
+                                                                   int seg_blocks, int n_segs, long long n_units, float gain) {
     using K = CenterCfg<LOG2W>;
     using C = typename K::C;
     constexpr int E = K::E, H = K::H, W = K::W, F = K::F, P = K::P, HE = E / 2;
@@ -51,15 +60,39 @@ __global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* _
     float2* const tw = smem + K::OFF_TW;
     for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
     __syncthreads();
-    const unsigned clip_bytes = (unsigned)(n_samples * 8);   // (the launcher keeps n_samples below 2^28)
+    // sample frames of the unit's clip: the kernel's argument, or (RAGGED) the field of the unit's record
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+    unsigned clip_bytes = 0;   // (the launcher keeps every clip below 2^28 sample frames)
+    if constexpr (!RAGGED) clip_bytes = (unsigned)(n_samples * 8);
 
-    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
-        const long long clip = u / n_segs;
-        const int seg = (int)(u - clip * n_segs);
-        const int b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);   // blocks [b0, b1) need frames b0 .. b1
-        const float2* const xc = x + clip * n_samples;
+    // RAGGED: the units come ordered by descending length, and the rounds of gridDim.x units are dealt forwards and backwards in turn --
+    // the workgroup that took the longest unit of one round takes the shortest of the next (still a fixed deal: nothing is claimed)
+    const long long n_deal = RAGGED ? (n_units + gridDim.x - 1) / gridDim.x * gridDim.x : n_units;
+    int round = 0;
+    for (long long v = blockIdx.x; v < n_deal; v += gridDim.x, ++round) {
+        long long u = v;
+        if constexpr (RAGGED) {
+            if (round & 1) u = (2LL * round + 1) * gridDim.x - 1 - v;
+            if (u >= n_units) continue;   // (the last round may be short; uniform)
+        }
+        CenterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
+        int b0, b1;        // blocks [b0, b1) need frames b0 .. b1
+        const float2* xc;
+        float2* oc;
+        if constexpr (RAGGED) {
+            rc = n_samples[__builtin_amdgcn_readfirstlane((int)u)];   // (the launcher keeps the units below 2^31)
+            b0 = rc.b0, b1 = rc.b1;
+            xc = x + rc.in_off;
+            oc = out + rc.out_off;
+            clip_bytes = (unsigned)(rc.n_samples * 8);
+        } else {
+            const long long clip = u / n_segs;
+            const int seg = (int)(u - clip * n_segs);
+            b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
+            xc = x + clip * n_samples;
+            oc = out + clip * n_samples * (SIDES ? 2 : 1);
+        }
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
-        float2* const oc = out + clip * n_samples * (SIDES ? 2 : 1);
         for (int j0 = b0; j0 <= b1; j0 += F) {
             const int j = j0 + f;              // this wave's frame: sample frames (j - 1) H .. (j + 1) H - 1
             const bool live = j <= b1;         // (wave-uniform)
@@ -126,31 +159,39 @@ __global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* _
                 const long long s = (long long)b * H + lane;
 #pragma unroll
                 for (int i = 0; i < HE; ++i) {
-                    if (s + P * i < n_samples) {   // nothing is written at or beyond sample frame N
+                    if (s + P * i < CLIP_N) {   // nothing is written at or beyond sample frame N
                         oc[s + P * i] = y[i];
-                        if constexpr (SIDES) oc[n_samples + s + P * i] = csub(raw[i], y[i]);
+                        if constexpr (SIDES) oc[CLIP_N + s + P * i] = csub(raw[i], y[i]);
                     }
                 }
             }
         }
         lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
     }
+#undef CLIP_N
 }
 
 static const char* const kCenterName = "k_center";
+static const char* const kCenterRaggedName = "k_center_ragged";
 const char* center_kernel_name() { return kCenterName; }
+
+// workgroups the device holds at once: what LDS admits per CU, at most 4
+template <int LOG2W>
+static long long center_slots(const zafx_plan& pl) {
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / CenterCfg<LOG2W>::SMEM));
+    return (long long)pl.n_cus * per_cu;
+}
 
 template <int LOG2W, bool SIDES>
 static hipError_t run_center(const zafx_plan& pl, const float2* x, float2* out, int64_t n_clips, int64_t n_samples) {
     using K = CenterCfg<LOG2W>;
-    auto kern = k_center<LOG2W, SIDES>;
+    auto kern = k_center<LOG2W, SIDES, false>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
     const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
     if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
     // segments: whole clips when there are enough of them to load every workgroup; otherwise cut, but never below two tiles
     // (2 F - 1 blocks) a segment -- each pays one halo frame
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / K::SMEM));
-    const long long slots = (long long)pl.n_cus * per_cu;
+    const long long slots = center_slots<LOG2W>(pl);
     long long segs = std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
     if (n_clips >= slots) segs = 1;
     segs = std::min<long long>(segs, std::max<long long>(1, n_blocks / (2 * K::F - 1)));
@@ -178,6 +219,52 @@ hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_
         case 9: return sides ? run_center<9, true>(pl, xi, o, n_clips, n_samples) : run_center<9, false>(pl, xi, o, n_clips, n_samples);
         case 10: return sides ? run_center<10, true>(pl, xi, o, n_clips, n_samples) : run_center<10, false>(pl, xi, o, n_clips, n_samples);
         case 11: return sides ? run_center<11, true>(pl, xi, o, n_clips, n_samples) : run_center<11, false>(pl, xi, o, n_clips, n_samples);
+    }
+    set_error("center / sides: window_length must be 256, 512, 1024 or 2048");
+    return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------
+// ragged batches (zafx_execute_center_ragged): the units come cut and ordered from the host (center_cut_units)
+// ---------------------------------------------------------------------------------
+template <int LOG2W, bool SIDES>
+static hipError_t run_center_ragged(const zafx_plan& pl, const float2* x, float2* out, const CenterUnit* d_units, long long n_units) {
+    using K = CenterCfg<LOG2W>;
+    auto kern = k_center<LOG2W, SIDES, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
+    pl.ran = kCenterRaggedName;
+    if (n_units <= 0) return hipSuccess;
+    const long long grid = std::min<long long>(n_units, center_slots<LOG2W>(pl));
+    const float gain = 1.f / ((float)K::W * pl.cola_gain);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, out, d_units, 0, 0, 0, n_units, gain);
+    return hipGetLastError();
+}
+
+bool center_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots) {
+    switch (pl.log2nf) {
+        case 8: *slots = center_slots<8>(pl); break;
+        case 9: *slots = center_slots<9>(pl); break;
+        case 10: *slots = center_slots<10>(pl); break;
+        case 11: *slots = center_slots<11>(pl); break;
+        default: return false;
+    }
+    *tile_frames = center_tile_frames(pl.log2nf);
+    return true;
+}
+
+hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out, const CenterUnit* d_units, long long n_units) {
+    if (n_units >= (1LL << 31)) {
+        set_error("center / sides: ragged batch too large for one launch (units >= 2^31)");
+        return hipErrorInvalidValue;
+    }
+    const bool sides = pl.kind == ZAFX_CENTER_SIDES;
+    const float2* xi = reinterpret_cast<const float2*>(x);
+    float2* o = reinterpret_cast<float2*>(out);
+    switch (pl.log2nf) {
+        case 8: return sides ? run_center_ragged<8, true>(pl, xi, o, d_units, n_units) : run_center_ragged<8, false>(pl, xi, o, d_units, n_units);
+        case 9: return sides ? run_center_ragged<9, true>(pl, xi, o, d_units, n_units) : run_center_ragged<9, false>(pl, xi, o, d_units, n_units);
+        case 10: return sides ? run_center_ragged<10, true>(pl, xi, o, d_units, n_units) : run_center_ragged<10, false>(pl, xi, o, d_units, n_units);
+        case 11: return sides ? run_center_ragged<11, true>(pl, xi, o, d_units, n_units) : run_center_ragged<11, false>(pl, xi, o, d_units, n_units);
     }
     set_error("center / sides: window_length must be 256, 512, 1024 or 2048");
     return hipErrorInvalidValue;

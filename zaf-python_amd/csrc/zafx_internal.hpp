@@ -172,8 +172,9 @@ struct zafx_plan {
     int bs_log2m = 0;              // > 0: window that is not a power of two -- Bluestein convolution length 2^bs_log2m (zafx_f64.hip, zafx_bs32.hip)
     void* d_pcm_float = nullptr;   // zafx_execute_pcm's float32 staging for the kinds that do not (grow-only)
     size_t pcm_float_bytes = 0;
-    // zafx_execute_ragged: the batch's table (zafx::RgClip records, then the clip of every tile) on the device and its page-locked staging
-    // copy, both grow-only; rg_ev marks the upload of the last call -- the host waits for it before it writes the staging copy again
+    // zafx_execute_ragged / zafx_execute_center_ragged: the batch's table (zafx::RgClip records, then the clip of every tile; zafx::CenterUnit
+    // records) on the device and its page-locked staging copy, both grow-only; rg_ev marks the upload of the last call -- the host waits for
+    // it before it writes the staging copy again
     void* d_ragged = nullptr;
     size_t ragged_bytes = 0;
     void* h_ragged = nullptr;
@@ -213,7 +214,8 @@ struct RgClip {
 };
 static_assert(sizeof(RgClip) == 40 && alignof(RgClip) == 8, "RgClip: the layout the host writes");
 // The kernels' RAGGED forms (k_stft_ft16, k_mel2) take the table in the 8-byte slot of n_samples and the clip count in `tiles`: the existing
-// instantiations keep their kernel arguments byte for byte.
+// instantiations keep their kernel arguments byte for byte.  (k_center's RAGGED form does the same with its own record: CenterSamplesArg,
+// zafx_center.hip.)
 template <bool RAGGED>
 using SamplesArg = std::conditional_t<RAGGED, const RgClip*, long long>;
 // RAGGED ? a field of the tile's record : the kernel's own argument.  A reference: the equal-length instantiations read their arguments
@@ -310,6 +312,11 @@ const char* dct_kernel_name();
 const char* linear_kernel_name();
 hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples);   // zafx_center.hip: ZAFX_CENTER / ZAFX_CENTER_SIDES
 const char* center_kernel_name();
+// zafx_execute_center_ragged: the tile frames F and the workgroup slots of the plan's k_center (what center_cut_units takes), and the launch of
+// its RAGGED form on `n_units` records of the device table
+struct CenterUnit;
+bool center_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
+hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out, const CenterUnit* d_units, long long n_units);
 hipError_t launch_pcm_to_float(hipStream_t stream, const void* pcm, float* out, int64_t n_total, int n_channels, int sample_bytes);
 
 // names of the dominant kernels (what rocprofv3 --kernel-trace prints, prefix match)

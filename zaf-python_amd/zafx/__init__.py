@@ -7,7 +7,8 @@ Drop-in functions (zaf.py signatures, float64 / complex128 results):
     stft, istft, melfilterbank, melspectrogram, mfcc, cqtkernel, cqtspectrogram,
     cqtchromagram, mdct, imdct, dct, dst
 The center / sides example of zaf.istft's docstring (stereo STFT, masks, ISTFT, subtraction) in one kernel:
-    centersides ((N, 2) -> (center, sides)), centersides_batch ((B, N, 2) float32), center_plan
+    centersides ((N, 2) -> (center, sides)), centersides_batch ((B, N, 2) float32), center_plan;
+    centersides_ragged (a sequence of (N_i, 2) clips of different lengths in one launch), pack_ragged_stereo, Plan.execute_center_ragged
 Batched extension ((clips, samples) in, float32 / complex64 out):
     stft_batch, istft_batch, mdct_batch, imdct_batch, melspectrogram_batch, mfcc_batch,
     cqtspectrogram_batch, cqtchromagram_batch, dct_batch, dst_batch, mel_mfcc_batch (melspectrogram + mfcc from one set of transforms);
@@ -29,7 +30,7 @@ from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersid
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,
                    get_precision, set_precision, stft, stft_batch, stft_pcm_batch, stft_plan, mdct_pcm_batch, melspectrogram_pcm_batch, mfcc_pcm_batch,
                    cqtspectrogram_pcm_batch, cqtchromagram_pcm_batch, mel_mfcc_batch, mel_mfcc_pcm_batch, mel_mfcc_supported, set_row_padding, get_row_padding,
-                   stft_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged)
+                   stft_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo)
 from .launch import Rendezvous, rank_env, spawn_ranks
 from .shard import clip_range, run_sharded, shard_sizes
 

@@ -425,6 +425,31 @@ class Plan:
         _lib.check(_lib.load().zafx_execute_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, len(lengths)),
                    "zafx_execute_ragged")
 
+    def execute_center_ragged(self, d_in, in_offsets, lengths, d_out, out_offsets):
+        """Enqueue the center / sides extraction of stereo clips of different lengths as one launch on the plan's stream (asynchronous;
+        zafx_execute_center_ragged, center plans only; last_kernel: k_center_ragged).  Offsets and lengths count sample frames (L, R): clip i
+        is lengths[i] sample frames at sample frame in_offsets[i] of d_in, its center goes to sample frame out_offsets[i] of d_out and, for a
+        plan with sides, its sides directly behind.  Output blocks that overlap are not detected."""
+        arrays = []
+        for name, values in (("in_offsets", in_offsets), ("lengths", lengths), ("out_offsets", out_offsets)):
+            a = np.asarray(values)
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise ValueError(f"{name} must be a 1-D sequence of integers")
+            arrays.append(np.ascontiguousarray(a, dtype=np.int64))
+        in_offsets, lengths, out_offsets = arrays
+        if not len(in_offsets) == len(lengths) == len(out_offsets):
+            raise ValueError("in_offsets, lengths and out_offsets must have one entry per clip")
+        if d_in.dtype != np.float32 or d_out.dtype != np.float32:
+            raise ValueError("execute_center_ragged takes float32 sample frames and a float32 output buffer")
+        blocks = 2 if self.kind == _lib.CENTER_SIDES else 1
+        if len(lengths) and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min())) >= 0:   # (negative values: the library says so)
+            if int((in_offsets + lengths).max()) * 8 > d_in.nbytes:
+                raise ValueError("a clip reaches past the end of d_in")
+            if int((out_offsets + blocks * lengths).max()) * 8 > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_center_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, _i64p(out_offsets),
+                                                          len(lengths)), "zafx_execute_center_ragged")
+
     def sync(self):
         _lib.check(_lib.load().zafx_sync(self.handle), "zafx_sync")
 
@@ -1246,6 +1271,71 @@ def mel_mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_
     both = _run_ragged(plan, clips)
     ft = plan.layout == _lib.LAYOUT_FT
     return ([b[:n_filters] if ft else b[:, :n_filters] for b in both], [b[n_filters:] if ft else b[:, n_filters:] for b in both])
+
+def _as_ragged_stereo(clips):
+    """A ragged stereo batch -- a sequence of (N_i, 2) real arrays -- validated ahead of any device call."""
+    if isinstance(clips, np.ndarray) and clips.dtype != object and clips.ndim < 3:
+        raise ValueError("a ragged stereo batch is a sequence of (N, 2) clips, not one array")
+    try:
+        items = list(clips)
+    except TypeError:
+        raise ValueError("a ragged stereo batch is a sequence of (N, 2) clips") from None
+    if not items:
+        raise ValueError("a ragged stereo batch needs at least one clip")
+    out = []
+    for i, c in enumerate(items):
+        a = np.asarray(c)
+        if a.ndim != 2:
+            raise ValueError(f"clip {i} of the ragged stereo batch must be 2-D, (sample frames, 2), got {a.ndim}-D")
+        if a.shape[1] != 2:
+            raise ValueError(f"clip {i} of the ragged stereo batch must be stereo, (sample frames, 2), got shape {a.shape}")
+        if np.iscomplexobj(a) or a.dtype.kind not in "biuf":
+            raise ValueError(f"clip {i} of the ragged stereo batch must be real")
+        out.append(a)
+    return out
+
+
+def pack_ragged_stereo(clips):
+    """One contiguous float32 array of a ragged stereo batch: a sequence of (N_i, 2) real arrays -> (packed (S, 2), in_offsets, lengths), in
+    sample frames.  The clips lie back to back without gaps (in_offsets are the running sums of the lengths): k_center pads every clip through
+    a buffer descriptor of its own, so a neighbour right behind a clip is never read as its tail."""
+    arrays = _as_ragged_stereo(clips)
+    lengths = np.array([len(a) for a in arrays], np.int64)
+    offsets = np.zeros(len(arrays), np.int64)
+    offsets[1:] = np.cumsum(lengths)[:-1]
+    packed = np.empty((int(lengths.sum()), 2), np.float32)
+    for a, o in zip(arrays, offsets.tolist()):
+        packed[o:o + len(a)] = a
+    return packed, offsets, lengths
+
+
+def centersides_ragged(clips, window_function, step_length=None, sides=True, device=0):
+    """centersides_batch of stereo clips of different lengths in one launch: a sequence of (N_i, 2) real arrays -> a list of (center_i, sides_i)
+    pairs, or of centers with sides=False, each float32 (N_i, 2) and a view of the one result buffer; every clip's result has the bits
+    centersides_batch gives for that clip alone.  One upload, one launch (k_center_ragged), one download.  Window and step_length as in
+    centersides_batch."""
+    w = _center_window(window_function, step_length)
+    x, in_offsets, lengths = pack_ragged_stereo(clips)
+    plan = center_plan(w, device, sides)
+    blocks = 2 if sides else 1
+    out_offsets = blocks * in_offsets
+    total = blocks * int(lengths.sum())
+    d_in = DeviceBuffer((max(len(x), 1), 2), np.float32, plan.device)
+    d_out = DeviceBuffer((max(total, 1), 2), np.float32, plan.device)
+    try:
+        if len(x):
+            d_in.upload(x)
+        with plan.lock:
+            plan.execute_center_ragged(d_in, in_offsets, lengths, d_out, out_offsets)
+            plan.sync()
+            res = d_out.download()
+    finally:
+        d_in.free()
+        d_out.free()
+    if not sides:
+        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+
 
 def cqtspectrogram_batch(clips, sampling_frequency, time_resolution, cqt_kernel, layout="FT", device=0, f64=False, out=None):
     """(B, N) -> (B, n_bins, T) float32 (float64 arrays and arithmetic with f64)."""
