@@ -222,7 +222,11 @@ int zafx_plan_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64
  * rejected.  Float32 plans in ZAFX_LAYOUT_FT whose every clip has rows of whole 128-byte lines (params.row_align = one line)
  * and a 128-byte aligned d_out run in ONE launch: the STFT at window 256 ... 2048 on k_stft_ft16 (last kernel
  * "k_stft_ft16_ragged"; |X| / |X|^2 at 2048 on k_mel2), mel / mfcc on k_mel2 where zafx_execute runs them there
- * ("k_mel2_ragged").  Everything else runs one zafx_execute per clip on the plan's stream ("per-clip <kernel>"). */
+ * ("k_mel2_ragged"), the MDCT at window 512, 1024 and 2048 on k_mdct_ft32 ("k_mdct_ft32_ragged": 16-byte loads when d_in is
+ * 16-byte aligned and every offset and length is a multiple of 4 samples, 4-byte loads for any other offsets and lengths; every
+ * clip below 2^28 samples).  ZAFX_RAGGED_MDCT_NATIVE=0 in the environment keeps MDCT batches off that launch: a switch for
+ * measurements only (tools/ragged_rates.py times the launch against one execute per clip in one process), read at every call,
+ * not part of the interface.  Everything else runs one zafx_execute per clip on the plan's stream ("per-clip <kernel>"). */
 int zafx_execute_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
                         int64_t n_clips);
 /* The center / sides extraction of n_clips stereo clips of different lengths in ONE launch (ZAFX_CENTER and ZAFX_CENTER_SIDES

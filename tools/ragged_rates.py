@@ -1,6 +1,6 @@
 """Rates of ragged batches (zafx_execute_ragged) against the padded batch and an equal-length batch, in one process.
 
-    python tools/ragged_rates.py [--reps 30] [--out FILE]
+    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any]
 
 Batch: 1024 clips, lengths uniform in 5-15 s at 44.1 kHz (even, so that the aligned loads apply as they do for the equal-length batch),
 window 2048, hop 1024.  For the STFT (two-sided, the headline's kind), mel (128 filters), mfcc (20 coefficients) and the one-pass mel + mfcc:
@@ -9,6 +9,11 @@ window 2048, hop 1024.  For the STFT (two-sided, the headline's kind), mel (128 
   equal    1024 clips of 10 s as one execute
 each timed with the plan's HIP-event stopwatch, one launch per reading, median (min, max) of --reps readings after warm-up.  All outputs are
 DeviceBuffers (zafx_alloc) with rows on the 128-byte line grid, so placement treats the three alike; Msamples/s counts the clips' own samples.
+
+The `mdct` row: the same 1024 clips with lengths rounded down to multiples of 4 (the 16-byte loads of k_mdct_ft32), Kaiser-Bessel-derived
+window of 2048 samples, rows padded to whole lines; `mdct_any`: those lengths plus 0 ... 3 samples each (the 4-byte loads).  Next to ragged and padded it times `per_clip`: the same execute_ragged with
+ZAFX_RAGGED_MDCT_NATIVE=0 in the environment, which keeps the batch on one zafx_execute per clip -- what every MDCT batch ran before the
+RAGGED form of the kernel existed.
 """
 import argparse
 import json
@@ -74,11 +79,60 @@ def measure(name, plan, lengths, in_offsets, bufs, reps):
     return res
 
 
+def measure_mdct(name, lengths, reps):
+    """ragged / padded / per-clip of the MDCT on one plan, with input arrays of its own: lengths that are multiples of 4 ("mdct": 16-byte
+    loads), or ("mdct_any") the same lengths plus 0 ... 3 samples each, seeded: 4-byte loads, the ordinary case of real audio."""
+    lengths = lengths - lengths % 4
+    if name == "mdct_any":
+        lengths = lengths + np.random.default_rng(2).integers(0, 4, len(lengths))
+        lengths[np.argmax(lengths)] |= 1   # (the padded batch off the 16-byte form as well)
+    plan = zafx.mdct_plan(zafx.kaiser_bessel_derived(W), row_align=32)
+    rng = np.random.default_rng(1)
+    slots = (lengths + 31) // 32 * 32
+    in_offsets = np.zeros(len(lengths), np.int64)
+    in_offsets[1:] = np.cumsum(slots)[:-1]
+    nmax = int(lengths.max())
+    packed = zafx.DeviceBuffer((int(slots.sum()),), np.float32)
+    packed.upload(rng.standard_normal(packed.shape, dtype=np.float32))
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    out = zafx.DeviceBuffer((int(offs[-1]),), plan.out_dtype)
+    res = {"samples": int(lengths.sum()), "longest": nmax}
+    res["ragged"] = timed(plan, lambda: plan.execute_ragged(packed, in_offsets, lengths, out), reps)
+    res["ragged_kernel"] = plan.last_kernel
+    os.environ["ZAFX_RAGGED_MDCT_NATIVE"] = "0"
+    try:
+        res["per_clip"] = timed(plan, lambda: plan.execute_ragged(packed, in_offsets, lengths, out), reps)
+        res["per_clip_kernel"] = plan.last_kernel
+    finally:
+        del os.environ["ZAFX_RAGGED_MDCT_NATIVE"]
+    out.free()
+    packed.free()
+    padded = zafx.DeviceBuffer((CLIPS, nmax), np.float32)
+    padded.upload(rng.standard_normal(padded.shape, dtype=np.float32))
+    o = zafx.DeviceBuffer(plan.out_shape(CLIPS, nmax), plan.out_dtype)
+    res["padded"] = timed(plan, lambda: plan.execute(padded, o, CLIPS, nmax), reps)
+    res["padded_kernel"] = plan.last_kernel
+    o.free()
+    padded.free()
+    for key in ("ragged", "padded", "per_clip"):
+        res[key]["msamples_per_s"] = res["samples"] / (res[key]["median_ms"] * 1e3)
+    res["ragged_over_padded"] = res["ragged"]["median_ms"] / res["padded"]["median_ms"]
+    res["per_clip_over_ragged"] = res["per_clip"]["median_ms"] / res["ragged"]["median_ms"]
+    r, p, c = res["ragged"], res["padded"], res["per_clip"]
+    print(f"{name:9s} ragged {r['median_ms']:7.3f} ms ({r['min_ms']:.3f}-{r['max_ms']:.3f}) {r['msamples_per_s']:8.0f} Ms/s [{res['ragged_kernel']}] | "
+          f"padded {p['median_ms']:7.3f} ms ({p['min_ms']:.3f}-{p['max_ms']:.3f}) [{res['padded_kernel']}] | per clip {c['median_ms']:7.3f} ms "
+          f"({c['min_ms']:.3f}-{c['max_ms']:.3f}) [{res['per_clip_kernel']}] | ragged / padded {res['ragged_over_padded']:.3f}, "
+          f"per clip / ragged {res['per_clip_over_ragged']:.1f}", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default="")
+    ap.add_argument("--kinds", default="stft,mel,mfcc,mel+mfcc,mdct,mdct_any")
     a = ap.parse_args()
+    kinds = a.kinds.split(",")
     rng = np.random.default_rng(0)
     lengths = rng.integers(5 * FS, 15 * FS + 1, CLIPS).astype(np.int64)
     lengths -= lengths % 2
@@ -92,9 +146,16 @@ def main():
     }
     result = {"device": zafx.device_name(0), "clips": CLIPS, "window": W, "hop": HOP, "samples": int(lengths.sum()),
               "longest": int(lengths.max()), "reps": a.reps}
-    in_offsets, bufs = inputs(lengths)
-    for name, plan in plans.items():
-        result[name] = measure(name, plan, lengths, in_offsets, bufs, a.reps)
+    if any(k in plans for k in kinds):
+        in_offsets, bufs = inputs(lengths)
+        for name, plan in plans.items():
+            if name in kinds:
+                result[name] = measure(name, plan, lengths, in_offsets, bufs, a.reps)
+        for b in bufs.values():
+            b.free()
+    for name in ("mdct", "mdct_any"):
+        if name in kinds:
+            result[name] = measure_mdct(name, lengths, a.reps)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)

@@ -1586,16 +1586,13 @@ static int upload_plan_table(zafx_plan* pl, size_t need, const std::function<voi
     return 0;
 }
 
-// zafx_execute_ragged's table: zafx::RgClip records, then the clip of every 16-frame tile
-static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& recs, int64_t total_tiles) {
+// zafx_execute_ragged's table: zafx::RgClip records, then the clip of every tile of `tile_frames` frames (16: k_stft_ft16 / k_mel2; 32:
+// k_mdct_ft32) -- the tiles the records' first_tile counts (zafx_ragged_table.hpp)
+static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& recs, int64_t total_tiles, int tile_frames = 16) {
     const size_t rec_b = recs.size() * sizeof(zafx::RgClip);
     return upload_plan_table(pl, rec_b + (size_t)total_tiles * sizeof(int), [&](unsigned char* h) {
         std::memcpy(h, recs.data(), rec_b);
-        int* clip_of = reinterpret_cast<int*>(h + rec_b);
-        for (size_t c = 0; c < recs.size(); ++c) {
-            const int tiles = (recs[c].T + 15) / 16;
-            for (int j = 0; j < tiles; ++j) clip_of[recs[c].first_tile + j] = (int)c;
-        }
+        zafx::rg_fill_clip_of(recs.data(), recs.size(), tile_frames, reinterpret_cast<int*>(h + rec_b));
     });
 }
 
@@ -1627,6 +1624,32 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
         if (tiles >= (1LL << 31)) return fail_msg("zafx_execute_ragged: batch too large for one launch (16-frame tiles >= 2^31)");
     }
     ZAFX_HIP(hipSetDevice(pl->device));
+    // native, MDCT: k_mdct_ft32 in its RAGGED form (float32, reference layout, W = 512 / 1024 / 2048, every clip's rows whole 128-byte lines).
+    // Its tiles are 32 frames: the records' first_tile and the batch's tile count are redone for them (the 16-frame count summed above
+    // still bounds the call, as it does for every kind: 2^31 sixteen-frame tiles are 2^35 frames, no batch that fits a device).  Every
+    // clip is read through a buffer descriptor of its own with 32-bit byte offsets: a batch with a clip of 2^28 samples (1 GiB) or more stays
+    // per clip.  16-byte loads when the array is on 16 bytes and every offset and length is a multiple of 4 samples (a piece is inside or
+    // outside its clip as a whole); 4-byte loads for any other batch.  ZAFX_RAGGED_MDCT_NATIVE=0 in the environment keeps the batch on the
+    // per-clip path (measurements only, include/zafx.h: tools/ragged_rates.py times both in one process).
+    if (pl->kind == ZAFX_MDCT && pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->bs_log2m == 0 && lines &&
+        zafx::mdct_ragged_native(*pl)) {
+        const char* sw = std::getenv("ZAFX_RAGGED_MDCT_NATIVE");
+        const long long tiles32 = zafx::rg_assign_tiles(recs.data(), recs.size(), zafx::kMdctRaggedTile);
+        bool aligned = reinterpret_cast<uintptr_t>(d_in) % 16 == 0, short_enough = reinterpret_cast<uintptr_t>(d_in) % 4 == 0;
+        for (const zafx::RgClip& r : recs) {
+            aligned = aligned && r.in_off % 4 == 0 && r.n_samples % 4 == 0;
+            short_enough = short_enough && r.n_samples < (1LL << 28);
+        }
+        if (tiles32 < (1LL << 31) && short_enough && !(sw && sw[0] == '0')) {
+            if (int rc = upload_ragged_table(pl, recs, tiles32, zafx::kMdctRaggedTile)) return rc;
+            const hipError_t e = zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged), n_clips, tiles32, aligned);
+            if (e != hipSuccess) {
+                if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_ragged", e);
+                return (int)e;
+            }
+            return 0;
+        }
+    }
     // native: k_stft_ft16 / k_mel2 in their RAGGED forms (float32, reference layout, every clip's rows whole 128-byte lines)
     const bool on_mel2 = zafx::mel_ragged_native(*pl);
     const bool native = pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->d_window && lines &&

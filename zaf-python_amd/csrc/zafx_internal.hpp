@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/zafx.h"
+#include "zafx_ragged_table.hpp"
 #include "zafx_twiddle.hpp"
 
 namespace zafx {
@@ -206,14 +207,8 @@ struct zafx_plan {
 
 namespace zafx {
 
-// One clip of a ragged batch (zafx_execute_ragged).  The plan's table on the device is n_clips of these, then one int per 16-frame tile
-// of the batch: the clip it belongs to.  Offsets and lengths in elements of the input / output arrays.
-struct RgClip {
-    long long in_off, n_samples, out_off;
-    int T, TP, first_tile, pad_;
-};
-static_assert(sizeof(RgClip) == 40 && alignof(RgClip) == 8, "RgClip: the layout the host writes");
-// The kernels' RAGGED forms (k_stft_ft16, k_mel2) take the table in the 8-byte slot of n_samples and the clip count in `tiles`: the existing
+// RgClip, one clip of a ragged batch (zafx_execute_ragged), and the table's tile geometry: zafx_ragged_table.hpp.
+// The kernels' RAGGED forms (k_stft_ft16, k_mel2, k_mdct_ft32) take the table in the 8-byte slot of n_samples and the clip count in `tiles`: the existing
 // instantiations keep their kernel arguments byte for byte.  (k_center's RAGGED form does the same with its own record: CenterSamplesArg,
 // zafx_center.hip.)
 template <bool RAGGED>
@@ -249,12 +244,31 @@ __device__ __forceinline__ RgClip rg_clip(const RgClip* tab, int n_clips, int tl
     const int c = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(tab + n_clips)[tl]);
     return tab[c];
 }
+// The same record in SGPRs whatever the compiler can prove about the kernel's stores: the table is read through the constant address space
+// -- nothing writes it while a kernel runs: the upload precedes the launch on the plan's stream -- so the uniform loads are scalar loads.
+// (k_mdct_ft32: read as global memory the records came by vector loads and stayed in VGPRs, 11 more of them at W = 512 and scratch at
+// W = 2048.  k_stft_ft16 and k_mel2 keep rg_clip: their code is as it was measured.)
+__device__ __forceinline__ RgClip rg_clip_const(const RgClip* tab, int n_clips, int tl) {
+    typedef const __attribute__((address_space(4))) RgClip* CRec;
+    typedef const __attribute__((address_space(4))) int* CInt;
+    const CRec recs = (CRec)tab;
+    const CRec r = recs + ((CInt)(recs + n_clips))[tl];
+    RgClip rc;
+    rc.in_off = r->in_off, rc.n_samples = r->n_samples, rc.out_off = r->out_off;
+    rc.T = r->T, rc.TP = r->TP, rc.first_tile = r->first_tile, rc.pad_ = 0;
+    return rc;
+}
 #endif
 hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 bool spec2_ragged(const zafx_plan& pl);   // |X| / |X|^2 at W = 2048 on k_mel2 (what launch_spec2 takes)
 bool stft_ragged_native(const zafx_plan& pl);   // the plans whose ragged batches have a kernel of their own (zafx_execute_ragged)
 bool mel_ragged_native(const zafx_plan& pl);
+// k_mdct_ft32's RAGGED form: the table counts 32-frame tiles (kMdctTile); `aligned`: 16-byte buffer loads (d_in on 16 bytes, every offset and
+// length a multiple of 4 samples), else 4-byte buffer loads (any offsets and lengths); every length below 2^28 in both
+constexpr int kMdctRaggedTile = 32;
+bool mdct_ragged_native(const zafx_plan& pl);
+hipError_t launch_mdct_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 
 // Every launcher enqueues on plan.stream and returns hipGetLastError().
 // Frames between the starts of consecutive rows of a plan's (F, T) array: T rounded up to prm.row_align elements

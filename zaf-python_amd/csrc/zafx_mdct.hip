@@ -156,12 +156,19 @@ struct MdctPCfg {
 // PCM (ALIGNED forms): `x` holds int16 -- 1: mono, n_samples 2-byte samples per clip, a 4-sample piece is 8 bytes; 2: stereo, n_samples 4-byte frames,
 // a piece is the float32 form's 16 bytes and both channels are added -- normalised (zaf.py:1202) and averaged (zaf.py:65) on the way into the fold:
 // the power of two rides in the window quadruples (zafx_execute_pcm).
-template <int LOG2NF, int LOG2E, bool ALIGNED, int NSLOT, bool TFOUT = false, bool CARRY = false, int PCM = 0>
+// RAGGED (zafx_execute_ragged): clips of different lengths.  `n_samples` carries the batch's table and `tiles` the number of clips (SamplesArg,
+// zafx_internal.hpp); the table counts tiles of kMdctTile frames.  A tile's clip comes from the per-tile array; the base of its input, its
+// samples, frames, row pitch and the base of its output come from the clip's record (uniform: scalar loads into SGPRs).  The prefetch runs one
+// tile ahead and that tile may belong to another clip, so two records are live: rc, the tile being transformed and stored, and rn, the next
+// one, looked up at the head of the tile -- its round trip passes under the first frame -- and handed to fetch().  The zero padding (the clip's
+// own buffer descriptor, in 16-byte or in 4-byte loads), fold, transform and store phase are the same code.  The launcher admits rows of whole 128-byte lines only.
+template <int LOG2NF, int LOG2E, bool ALIGNED, int NSLOT, bool TFOUT = false, bool CARRY = false, int PCM = 0, bool RAGGED = false>
 __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
     const float* __restrict__ x, const float4* __restrict__ wfold, const float2* __restrict__ twp,
-    const float2* __restrict__ tw8, float* __restrict__ out, long long n_samples, int T, int TP, int tiles, int total_tiles,
+    const float2* __restrict__ tw8, float* __restrict__ out, SamplesArg<RAGGED> n_samples, int T, int TP, int tiles, int total_tiles,
     int segs = 1, int seg_tiles = 0, int units = 0) {
     static_assert(!(CARRY && TFOUT), "the carry form is for the reference layout");
+    static_assert(!RAGGED || (!TFOUT && !CARRY && PCM == 0), "ragged batches: float32 samples, reference layout, rows of whole lines");
     using C = FftCfg<LOG2NF, LOG2E>;
     constexpr int NF = C::N, M = 2 * NF, P = C::P, E = C::E, FPB = kMdctTile, NT = NSLOT * P;
     constexpr int FPW = FPB / NSLOT;                    // frames per wave and tile
@@ -183,8 +190,8 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
     }
     lds_barrier();
     const int slot = tid / P, p = tid % P;
-    const bool pair_ok = (TFOUT || TP % 2 == 0) && (reinterpret_cast<uintptr_t>(out) % 8 == 0);   // TP = row pitch (>= T)
-    const bool lines_whole = TP % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 64 == 0;   // rows of whole 64-B half lines: stream them
+    const bool pair_ok = (TFOUT || RAGGED || TP % 2 == 0) && (reinterpret_cast<uintptr_t>(out) % 8 == 0);   // TP = row pitch (>= T)
+    const bool lines_whole = (RAGGED || TP % 16 == 0) && reinterpret_cast<uintptr_t>(out) % 64 == 0;   // rows of whole 64-B half lines: stream them (RAGGED: every pitch is a multiple of 32)
     const bool lane_loads = p < NU;
 
     // A frame's W = 4 NF samples are fetched as 16-byte pieces.  Group u takes four of them,
@@ -199,11 +206,12 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
     // wave's registers recovered part of it, 1.075 ms -- rounds need no such code and run 1.05 ms.)
     auto frame_of = [&](int f) { return f * NSLOT + slot; };
     float4 q[UPL][4];
-    auto fetch = [&](int tl, int f) {
+    // (fr: RAGGED, the record of tile tl's clip; samples and frames of the clip are the kernel's arguments otherwise -- rg_pick)
+    auto fetch = [&](int tl, int f, [[maybe_unused]] const RgClip& fr) {
         if (tl >= total_tiles || !lane_loads) return;
-        const int clip = tl / tiles, tile = tl % tiles;
+        const int clip = RAGGED ? 0 : tl / tiles, tile = RAGGED ? tl - fr.first_tile : tl % tiles;
         const int t = tile * FPB + frame_of(f);
-        const float* xc = x + (long long)clip * n_samples;
+        const float* xc = x + (RAGGED ? fr.in_off : (long long)clip * rg_pick<RAGGED>(fr.n_samples, n_samples));
         const long long s0 = (long long)t * M - M;   // left pad = M (zaf.py:1036-1041)
         if constexpr (ALIGNED) {
             // Buffer loads through a descriptor of the clip: a 16-byte piece that lies before the clip's first or after its last
@@ -211,7 +219,8 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             // path (n_samples and every piece's first sample are multiples of 4: a piece is inside or outside as a whole;
             // offsets are 32-bit and wrap, a negative one is a huge unsigned one).  Four address registers per frame.
             if constexpr (PCM == 1) {   // four int16 samples = 8 bytes per piece
-                const __amdgpu_buffer_rsrc_t rs = make_rsrc(reinterpret_cast<const short*>(x) + (long long)clip * n_samples, (unsigned)(n_samples * 2));
+                const __amdgpu_buffer_rsrc_t rs = make_rsrc(reinterpret_cast<const short*>(x) + (long long)clip * rg_pick<RAGGED>(fr.n_samples, n_samples),
+                                                            (unsigned)(rg_pick<RAGGED>(fr.n_samples, n_samples) * 2));
                 const int b = (int)s0 * 2 + 8 * p, rb = (int)s0 * 2 - 8 * p - 8 * (UPL - 1) * P;
                 auto piece = [&](int off) {
                     const float2 d = buf_load_f32x2(rs, off);
@@ -227,7 +236,7 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
                 }
                 return;
             }
-            const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, (unsigned)(n_samples * 4));
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, (unsigned)(rg_pick<RAGGED>(fr.n_samples, n_samples) * 4));
             const int b = (int)s0 * 4 + 16 * p;                  // + 16 u forward pieces
             const int rb = (int)s0 * 4 - 16 * p - 16 * (UPL - 1) * P;   // - 16 u reversed pieces, lowest address of the UPL
             auto piece = [&](int off) {
@@ -244,6 +253,32 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
                 q[r][1] = piece(rb + 12 * NF - 16 + 16 * (UPL - 1 - r) * P);
                 q[r][2] = piece(b + 4 * NF + 16 * r * P);
                 q[r][3] = piece(rb + 4 * NF - 16 + 16 * (UPL - 1 - r) * P);
+            }
+        } else if constexpr (RAGGED) {
+            // Any offsets and lengths: the same descriptor of the clip, read one sample per load.  A 4-byte load is inside or outside the
+            // clip as a whole, so the range check alone gives the zero padding in front of the clip, behind it and in the frames past T
+            // (they start at or behind the last sample) -- no 64-bit addresses and no bounds tests per sample: with at() this form had
+            // 48 bytes of scratch at W = 2048.  The four samples of a piece are addressed from four registers the compiler knows nothing about
+            // (opaque): merged into one 16-byte load, a piece that straddles an end of the clip would rest on the range check of a wider load.  32-bit byte offsets: the launcher
+            // sends a batch here only if every clip is below 2^28 samples, as for the 16-byte form.
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, (unsigned)(fr.n_samples * 4));
+            // (b, rb: the lane's forward and reversed pieces, as above; [j]: sample j of a piece, a register of its own per j)
+            int b[4], rb[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                b[j] = (int)s0 * 4 + 16 * p + 4 * j;
+                rb[j] = (int)s0 * 4 - 16 * p - 16 * (UPL - 1) * P + 4 * j;
+                asm volatile("" : "+v"(b[j]), "+v"(rb[j]));
+            }
+            auto piece = [&](const int (&o)[4], int c) {
+                return make_float4(buf_load_f32(rs, o[0] + c), buf_load_f32(rs, o[1] + c), buf_load_f32(rs, o[2] + c), buf_load_f32(rs, o[3] + c));
+            };
+#pragma unroll
+            for (int r = 0; r < UPL; ++r) {
+                q[r][0] = piece(b, 12 * NF + 16 * r * P);
+                q[r][1] = piece(rb, 12 * NF - 16 + 16 * (UPL - 1 - r) * P);
+                q[r][2] = piece(b, 4 * NF + 16 * r * P);
+                q[r][3] = piece(rb, 4 * NF - 16 + 16 * (UPL - 1 - r) * P);
             }
         } else {   // clip edges (zero padding), frames past T, unaligned clips
             auto at = [&](long long s) { return (t < T && s >= 0 && s < n_samples) ? xc[s] : 0.f; };
@@ -314,12 +349,19 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
 #pragma unroll
         for (int i = 0; i < ITER; ++i) cva[i] = cvb[i] = 0.f;
     }
-    fetch(tl, 0);
+    [[maybe_unused]] RgClip rc{}, rn{};   // RAGGED: the records of the current and of the next tile's clip
+    if constexpr (RAGGED) {
+        if (tl < total_tiles) rc = rg_clip_const(n_samples, tiles, tl);
+    }
+    fetch(tl, 0, rc);
     PROF_INIT(g_prof_mdct);
     for (; tl < total_tiles;) {
-        const int clip = tl / tiles, tile = tl % tiles;
+        const int clip = RAGGED ? 0 : tl / tiles, tile = RAGGED ? tl - rc.first_tile : tl % tiles;
         const int t0 = tile * FPB;
         int tl_next = tl + gridDim.x, nj = wj + 1, nj1 = wj1, nv = wv;
+        if constexpr (RAGGED) {
+            if (tl_next < total_tiles) rn = rg_clip_const(n_samples, tiles, tl_next);
+        }
         if constexpr (CARRY) {
             if (nj < wj1) tl_next = tl + 1;
             else {
@@ -333,8 +375,8 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             float2* buf = frames + frame_of(f) * C::PITCH;
             fold(buf);
             PROF_MARK(1);
-            if (f + 1 < FPW) fetch(tl, f + 1);
-            else fetch(tl_next, 0);
+            if (f + 1 < FPW) fetch(tl, f + 1, rc);
+            else fetch(tl_next, 0, rn);
             frame_sync<P>();
             int po = p;   // opaque copy: the pass-twiddle reads stay in the loop (hoisted, they spill at 128 VGPRs)
             asm volatile("" : "+v"(po));
@@ -424,7 +466,7 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             if (have_prev) sweep(std::true_type{});
             else sweep(std::false_type{});
         } else
-        if (ta < T) {
+        if (ta < rg_pick<RAGGED>(rc.T, T)) {
             // Row of lane group g = (tid / 16) % 4 within the wave's 4 rows: 0, 2, 1, 3.  ds_read_b64 serves 32 lanes
             // per cycle; rows f and f + 2 of a half-wave read bins k and k + 1 (bank offset 2 dwords: conflict free with
             // the 4-dword frame-pair stride), rows f and f + 1 read bins k and M/2 - 1 - k (same bank class: 2-way).
@@ -432,8 +474,8 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             asm volatile("" : "+v"(fqo));
             const float2* ba = frames + (2 * tp) * C::PITCH;
             const float2* bb = ba + C::PITCH;
-            float* o = out + (long long)clip * M * TP + ta;
-            const bool two = ta + 1 < T;
+            float* o = out + (RAGGED ? rc.out_off : (long long)clip * M * rg_pick<RAGGED>(rc.TP, TP)) + ta;
+            const bool two = ta + 1 < rg_pick<RAGGED>(rc.T, T);
             // coefficient f of a frame is Re y[f / 2] (f even) or -Im y[(M - 1 - f) / 2] (f odd): one float of the frame's
             // conj(y) image.  A thread's f advances by NT / 16 (even), so its parity, the component it reads and the stride
             // of its bin (+- NT / 32, i.e. +- (NT / 32 + NT / 512) padded slots) are fixed: two ds_read_b32, one 8-byte
@@ -444,8 +486,8 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             const float* pa = reinterpret_cast<const float*>(ba + phys(k)) + odd;
             const float* pb2 = reinterpret_cast<const float*>(bb + phys(k)) + odd;
             const int dslot = odd ? -2 * DPH : 2 * DPH;     // floats
-            float* dst = o + (long long)fqo * TP;
-            const long long dstep = (long long)(NT / 16) * TP;
+            float* dst = o + (long long)fqo * rg_pick<RAGGED>(rc.TP, TP);
+            const long long dstep = (long long)(NT / 16) * rg_pick<RAGGED>(rc.TP, TP);
             // (A sweep that starts somewhere else in every workgroup, as in k_stft_ft16, gains nothing here: 0.791 against 0.787 ms,
             // A/B on one box, round 3 -- the switch stays for the experiment.)
             constexpr int ITER = M / (NT / 16);
@@ -482,6 +524,7 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             have_prev = nv == wv;   // the walk continues inside the same segment
             wv = nv, wj = nj, wj1 = nj1;
         }
+        if constexpr (RAGGED) rc = rn;
         tl = tl_next;
     }
 }
@@ -1507,6 +1550,42 @@ static hipError_t run_mdct_p(const zafx_plan& pl, const float* x, float* out, in
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NSLOT * 64), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_pass, pl.d_tw_aux, out,
                        (long long)n_samples, T, (int)row_pitch(pl, T), tiles, (int)total, 1, 0, 0);
     return hipGetLastError();
+}
+
+// zafx_execute_ragged: clips of different lengths on k_mdct_ft32's RAGGED form -- W = 512, 1024, 2048 (what mdct_use_persistent covers) in the
+// reference layout, float32, every clip's rows whole 128-byte lines (the caller checked).  One form runs the whole batch: `aligned`, the
+// 16-byte buffer loads (a descriptor per clip; the caller vouches for d_in on 16 bytes and for offsets and lengths that are multiples of 4
+// samples), else the edge form: the same descriptor read in 4-byte loads, any offsets and lengths.  Both: every clip below 2^28 samples.  The table counts tiles of kMdctTile frames.
+static_assert(kMdctRaggedTile == kMdctTile, "zafx_execute_ragged builds the table for the kernel's tile");
+bool mdct_ragged_native(const zafx_plan& pl) {
+    return pl.kind == ZAFX_MDCT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.layout == ZAFX_LAYOUT_FT &&
+           mdct_use_persistent(pl.log2nf, pl.layout) && pl.d_wfold && pl.d_tw_pass && pl.d_tw_aux;
+}
+
+template <int LOG2NF, bool ALIGNED>
+static hipError_t run_mdct_p_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* tab, int64_t n_clips, long long total_tiles) {
+    constexpr int LOG2E = default_log2e(LOG2NF);
+    using G = MdctPCfg<LOG2NF, LOG2E>;
+    auto kern = k_mdct_ft32<LOG2NF, LOG2E, ALIGNED, G::NSLOT, false, false, 0, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM); e != hipSuccess) return e;
+    if (total_tiles <= 0) return hipSuccess;
+    const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / G::SMEM);   // (the grid of run_mdct_p)
+    const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus * std::max(per_cu, 1));
+    pl.ran = "k_mdct_ft32_ragged";
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NSLOT * 64), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_pass, pl.d_tw_aux, out, tab, 0, 0,
+                       (int)n_clips, (int)total_tiles, 1, 0, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_mdct_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
+    if (!mdct_ragged_native(pl) || n_clips >= (1LL << 31) || total_tiles >= (1LL << 31)) return hipErrorInvalidValue;
+    switch (pl.log2nf) {
+#define X(L) \
+    case L: return aligned ? run_mdct_p_ragged<L, true>(pl, x, out, tab, n_clips, total_tiles) : run_mdct_p_ragged<L, false>(pl, x, out, tab, n_clips, total_tiles);
+        X(7) X(8) X(9)
+#undef X
+    }
+    return hipErrorInvalidValue;
 }
 
 #ifndef ZAFX_MDCT_BAND

@@ -1240,6 +1240,24 @@ def stft_ragged(clips, window_function, step_length, layout="FT", device=0, ones
     return _as_f32_views(_run_ragged(plan, clips), plan, f64)
 
 
+def mdct_ragged(clips, window_function, layout="FT", device=0, f64=False):
+    """mdct_batch of clips of different lengths in one call: a sequence of 1-D arrays -> a list of (W/2, T_i) float32 arrays ["FT"] or
+    (T_i, W/2) ["TF"] (float64 arrays and arithmetic with f64), each clip's frames T_i = ceil(N_i / (W/2)) + 1 as zaf.mdct gives them for that
+    clip alone (a clip of length 0: one frame of zeros).  The arrays are views of one result buffer.  "FT" / float32 at window 512, 1024 and
+    2048 runs in one launch (k_mdct_ft32_ragged); an empty list gives an empty list."""
+    w = _as_window(window_function, any_length=True)
+    if len(w) % 2 or len(w) < 4:
+        raise ValueError("the MDCT needs an even window_length >= 4")
+    _check_f64_window(len(w), bool(f64) or not _f32_window(len(w)))
+    _as_row_align(0, layout)   # (an unknown layout fails here)
+    if isinstance(clips, (list, tuple)) and not len(clips):
+        return []
+    clips = _as_ragged(clips)
+    plan = mdct_plan(w, layout, device, f64=f64)
+    plan = _ragged_grid(plan, lambda a: mdct_plan(w, layout, device, row_align=a, f64=f64))
+    return _as_f32_views(_run_ragged(plan, clips), plan, f64)
+
+
 def melspectrogram_ragged(clips, window_function, step_length, mel_filterbank, layout="FT", device=0, f64=False):
     """melspectrogram_batch of clips of different lengths: -> a list of (n_filters, T_i) float32 arrays (float64 with f64)."""
     clips = _as_ragged(clips)
