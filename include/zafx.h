@@ -240,6 +240,23 @@ int zafx_execute_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_off
  * overlap -- placing them is the caller's business.  d_in and d_out need 8-byte alignment only. */
 int zafx_execute_center_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
                                const int64_t* out_offsets, int64_t n_clips);
+/* The IMDCT of n_clips coefficient blocks of different frame counts, enqueued on the plan's stream (asynchronous; ZAFX_IMDCT plans only --
+ * zafx_execute_ragged and zafx_plan_ragged_layout keep refusing the inverse kinds).  Block i is the (W/2, frames[i]) array of one clip at
+ * element in_offsets[i] of d_coefs: W/2 rows at the pitch zafx_plan_row_pitch(plan, frames[i]) in ZAFX_LAYOUT_FT -- the layout a forward
+ * ZAFX_MDCT plan's zafx_execute_ragged writes at the same row_align, so the output buffer of a ragged MDCT can be fed back as it lies --,
+ * frames[i] x W/2 compact in ZAFX_LAYOUT_TF.  The pad columns of a block are never used; they may hold anything.  Clip i's
+ * max((W/2) (frames[i] - 1) - 1, 0) samples (zaf.py:1182) go to element out_offsets[i] of d_out; a block of at most one frame writes nothing.
+ * Every clip's result is bit-identical to zafx_execute on that block alone.  The three host arrays are copied before return.
+ * Rejected with a message: another plan kind, n_clips < 0, a negative frame count or offset (with the clip's index).  NOT checked: that the
+ * output ranges do not overlap -- placing them is the caller's business.
+ * ONE launch (last kernel "k_imdct_ragged") for float32 plans in ZAFX_LAYOUT_FT at window 512, 1024 and 2048 when every block's pitch is a
+ * multiple of 4 floats, every block is below 2^32 bytes and the batch gives fewer than 2^31 units; d_out and the output offsets need 4-byte alignment
+ * only (a clip's bits do not depend on where it is put).  Everything else -- ZAFX_LAYOUT_TF, float64, window 4096 / 8192, windows up to
+ * 256, Bluestein windows, compact pitches off the 4-float grid -- runs one zafx_execute per clip on the plan's stream and reports that
+ * kernel's name.  ZAFX_RAGGED_IMDCT_NATIVE=0 in the environment keeps a batch off the one launch, as ZAFX_RAGGED_MDCT_NATIVE does for the
+ * forward transform: a switch for measurements only (tools/ragged_rates.py --kinds imdct), read at every call, not part of the interface. */
+int zafx_execute_imdct_ragged(zafx_plan* plan, const void* d_coefs, const int64_t* in_offsets, const int64_t* frames, void* d_out,
+                              const int64_t* out_offsets, int64_t n_clips);
 /* Bytes of ONE clip on the input and on the output side of the plan for `n_in` (as zafx_plan_out_dims; rows at the
  * plan's pitch): what a host array of n_clips clips must hold for zafx_run_host. */
 int zafx_plan_clip_bytes(const zafx_plan* plan, int64_t n_in, int64_t* in_bytes, int64_t* out_bytes);

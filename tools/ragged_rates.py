@@ -1,6 +1,6 @@
 """Rates of ragged batches (zafx_execute_ragged) against the padded batch and an equal-length batch, in one process.
 
-    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any]
+    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct] [--imdct-k 2,4,8,12,16,24]
 
 Batch: 1024 clips, lengths uniform in 5-15 s at 44.1 kHz (even, so that the aligned loads apply as they do for the equal-length batch),
 window 2048, hop 1024.  For the STFT (two-sided, the headline's kind), mel (128 filters), mfcc (20 coefficients) and the one-pass mel + mfcc:
@@ -14,6 +14,12 @@ The `mdct` row: the same 1024 clips with lengths rounded down to multiples of 4 
 window of 2048 samples, rows padded to whole lines; `mdct_any`: those lengths plus 0 ... 3 samples each (the 4-byte loads).  Next to ragged and padded it times `per_clip`: the same execute_ragged with
 ZAFX_RAGGED_MDCT_NATIVE=0 in the environment, which keeps the batch on one zafx_execute per clip -- what every MDCT batch ran before the
 RAGGED form of the kernel existed.
+
+The `imdct` row (not in the default kinds): the (1024, T_i) coefficient blocks of those clips, T_i = ceil(N_i / 1024) + 1, rows padded to
+whole lines, as the ragged MDCT leaves them.  `ragged`: one execute_imdct_ragged, cutting and table upload included (k_imdct_ragged);
+`padded`: every block padded to the longest as one execute (k_imdct); `per_clip`: the same execute_imdct_ragged with
+ZAFX_RAGGED_IMDCT_NATIVE=0, one zafx_execute per block -- the only way before the RAGGED form existed.  --imdct-k: the ragged reading again
+for these units per workgroup slot of the cutting rule (ZAFX_IMDCT_UNITS_PER_SLOT), the sweep the shipped constant was chosen from.
 """
 import argparse
 import json
@@ -126,11 +132,68 @@ def measure_mdct(name, lengths, reps):
     return res
 
 
+def measure_imdct(lengths, reps, sweep):
+    """ragged / padded / per-clip of the IMDCT on one plan: noise coefficients (the pad columns included -- they are never used)."""
+    m = W // 2
+    plan = zafx.mdct_plan(zafx.kaiser_bessel_derived(W), inverse=True, row_align=32)
+    frames = -(-lengths // m) + 1
+    pitch = (frames + 31) // 32 * 32
+    in_offsets = np.zeros(len(frames), np.int64)
+    in_offsets[1:] = np.cumsum(m * pitch)[:-1]
+    out_len = m * (frames - 1) - 1
+    out_offsets = np.zeros(len(frames), np.int64)
+    out_offsets[1:] = np.cumsum((out_len + 31) // 32 * 32)[:-1]
+    rng = np.random.default_rng(1)
+    tmax = int(frames.max())
+    coefs = zafx.DeviceBuffer((int((m * pitch).sum()),), np.float32)
+    coefs.upload(rng.standard_normal(coefs.shape, dtype=np.float32))
+    out = zafx.DeviceBuffer((int(out_offsets[-1] + out_len[-1]) + 32,), np.float32)
+    res = {"samples": int(out_len.sum()), "frames": int(frames.sum()), "longest_frames": tmax}
+    call = lambda: plan.execute_imdct_ragged(coefs, in_offsets, frames, out, out_offsets)   # noqa: E731
+    res["ragged"] = timed(plan, call, reps)
+    res["ragged_kernel"] = plan.last_kernel
+    res["units_per_slot_sweep"] = {}
+    for k in sweep:
+        os.environ["ZAFX_IMDCT_UNITS_PER_SLOT"] = str(k)
+        try:
+            res["units_per_slot_sweep"][str(k)] = timed(plan, call, reps)
+        finally:
+            del os.environ["ZAFX_IMDCT_UNITS_PER_SLOT"]
+    os.environ["ZAFX_RAGGED_IMDCT_NATIVE"] = "0"
+    try:
+        res["per_clip"] = timed(plan, call, reps)
+        res["per_clip_kernel"] = plan.last_kernel
+    finally:
+        del os.environ["ZAFX_RAGGED_IMDCT_NATIVE"]
+    out.free()
+    coefs.free()
+    padded = zafx.DeviceBuffer((CLIPS, m, plan.row_pitch(tmax)), np.float32)
+    padded.upload(rng.standard_normal(padded.shape, dtype=np.float32))
+    o = zafx.DeviceBuffer(plan.out_shape(CLIPS, tmax), plan.out_dtype)
+    res["padded"] = timed(plan, lambda: plan.execute(padded, o, CLIPS, tmax), reps)
+    res["padded_kernel"] = plan.last_kernel
+    o.free()
+    padded.free()
+    for key in ("ragged", "padded", "per_clip"):
+        res[key]["msamples_per_s"] = res["samples"] / (res[key]["median_ms"] * 1e3)
+    res["ragged_over_padded"] = res["ragged"]["median_ms"] / res["padded"]["median_ms"]
+    res["per_clip_over_ragged"] = res["per_clip"]["median_ms"] / res["ragged"]["median_ms"]
+    r, p, c = res["ragged"], res["padded"], res["per_clip"]
+    print(f"imdct     ragged {r['median_ms']:7.3f} ms ({r['min_ms']:.3f}-{r['max_ms']:.3f}) {r['msamples_per_s']:8.0f} Ms/s [{res['ragged_kernel']}] | "
+          f"padded {p['median_ms']:7.3f} ms ({p['min_ms']:.3f}-{p['max_ms']:.3f}) [{res['padded_kernel']}] | per clip {c['median_ms']:7.3f} ms "
+          f"({c['min_ms']:.3f}-{c['max_ms']:.3f}) [{res['per_clip_kernel']}] | ragged / padded {res['ragged_over_padded']:.3f}, "
+          f"per clip / ragged {res['per_clip_over_ragged']:.1f}", flush=True)
+    for k, t in res["units_per_slot_sweep"].items():
+        print(f"imdct     units per slot {k:>3s}: ragged {t['median_ms']:7.3f} ms ({t['min_ms']:.3f}-{t['max_ms']:.3f})", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default="")
     ap.add_argument("--kinds", default="stft,mel,mfcc,mel+mfcc,mdct,mdct_any")
+    ap.add_argument("--imdct-k", default="2,4,8,12,16,24")
     a = ap.parse_args()
     kinds = a.kinds.split(",")
     rng = np.random.default_rng(0)
@@ -156,6 +219,8 @@ def main():
     for name in ("mdct", "mdct_any"):
         if name in kinds:
             result[name] = measure_mdct(name, lengths, a.reps)
+    if "imdct" in kinds:
+        result["imdct"] = measure_imdct(lengths, a.reps, [int(k) for k in a.imdct_k.split(",") if k])
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)

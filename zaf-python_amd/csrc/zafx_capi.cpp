@@ -16,6 +16,7 @@
 
 #include "zafx_center.hpp"
 #include "zafx_center_units.hpp"
+#include "zafx_imdct_units.hpp"
 #include "zafx_internal.hpp"
 
 #ifndef ZAFX_STFT_FAT8_TABLES
@@ -1710,6 +1711,66 @@ int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
     if (e != hipSuccess) {
         if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_center_ragged", e);
         return (int)e;
+    }
+    return 0;
+}
+
+// Ragged batches of the IMDCT: coefficient blocks of different frame counts.  The host cuts the blocks into units (imdct_cut_units), k_imdct's
+// RAGGED form walks them in one launch: float32, reference layout, W = 512 / 1024 / 2048, no Bluestein part, every block's pitch a multiple of
+// 4 floats (the 16-byte gather), every block below 2^32 bytes (a buffer descriptor per clip), units below 2^31.  Everything else -- the
+// frame-major layout, float64, W = 4096 / 8192, W <= 256, compact pitches off the 4-float grid -- runs one zafx_execute per clip on the plan's
+// stream and reports that kernel.  ZAFX_RAGGED_IMDCT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only,
+// include/zafx.h); ZAFX_IMDCT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t* in_offsets, const int64_t* frames, void* d_out, const int64_t* out_offsets,
+                              int64_t n_clips) {
+    if (!pl) return fail_msg("null plan");
+    if (n_clips < 0) return fail_msg("zafx_execute_imdct_ragged: negative number of clips");
+    if (pl->kind != ZAFX_IMDCT) return fail_msg("zafx_execute_imdct_ragged: inverse MDCT plans (ZAFX_IMDCT) only (zafx_execute_ragged takes the forward kinds)");
+    if (n_clips == 0) return 0;
+    if (!in_offsets || !frames || !out_offsets) return fail_msg("null argument");
+    if (!d_coefs || !d_out) return fail_msg("null device pointer");
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (frames[i] < 0 || in_offsets[i] < 0 || out_offsets[i] < 0)
+            return fail_msg("zafx_execute_imdct_ragged: negative frame count or offset of clip " + std::to_string(i));
+    if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
+    const int M = pl->W / 2;
+    bool native = zafx::imdct_ragged_native(*pl) && reinterpret_cast<uintptr_t>(d_coefs) % 4 == 0;
+    if (const char* sw = std::getenv("ZAFX_RAGGED_IMDCT_NATIVE")) native = native && sw[0] != '0';
+    for (int64_t i = 0; native && i < n_clips; ++i) {
+        const int64_t pitch = row_pitch(*pl, frames[i]);
+        native = pitch % 4 == 0 && (long long)M * pitch * 4 < (1LL << 32);
+    }
+    ZAFX_HIP(hipSetDevice(pl->device));
+    int tile_frames = 0;
+    long long slots = 0;
+    if (native && zafx::imdct_launch_shape(*pl, &tile_frames, &slots)) {
+        int per_slot = zafx::kImdctUnitsPerSlot;
+        if (const char* v = std::getenv("ZAFX_IMDCT_UNITS_PER_SLOT")) per_slot = std::min(64, std::max(1, std::atoi(v)));
+        std::vector<zafx::ImdctUnit> units = zafx::imdct_cut_units(frames, n_clips, tile_frames, slots, per_slot);
+        if (units.size() + (size_t)slots < (size_t)1 << 31) {   // (the table in launch order is at most one round longer)
+            for (zafx::ImdctUnit& u : units) {   // (the cutter leaves the clip's index in in_off)
+                const int64_t i = u.in_off;
+                zafx::imdct_fill_clip(u, in_offsets[i], out_offsets[i], row_pitch(*pl, frames[i]), M);
+            }
+            // the launch's workgroups (launch_imdct_ragged: min(records, slots) -- the table is a whole number of rounds or shorter than one)
+            const std::vector<zafx::ImdctUnit> table = zafx::imdct_deal_table(units, std::min<long long>((long long)units.size(), slots));
+            if (!table.empty()) {
+                const size_t bytes = table.size() * sizeof(zafx::ImdctUnit);
+                if (int rc = upload_plan_table(pl, bytes, [&](unsigned char* h) { std::memcpy(h, table.data(), bytes); })) return rc;
+            }
+            const hipError_t e = zafx::launch_imdct_ragged(*pl, (const float*)d_coefs, (float*)d_out, static_cast<const zafx::ImdctUnit*>(pl->d_ragged), (long long)table.size());
+            if (e != hipSuccess) {
+                if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_imdct_ragged", e);
+                return (int)e;
+            }
+            return 0;
+        }
+    }
+    // everything else: one zafx_execute per clip on the plan's stream (a block of at most one frame has no samples)
+    const int64_t eb = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        if (frames[i] <= 1) continue;
+        if (int rc = zafx_execute(pl, (const char*)d_coefs + in_offsets[i] * eb, (char*)d_out + out_offsets[i] * eb, 1, frames[i])) return rc;
     }
     return 0;
 }

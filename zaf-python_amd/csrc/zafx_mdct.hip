@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "zafx_fft.hpp"
+#include "zafx_imdct_units.hpp"
 #include "zafx_internal.hpp"
 
 
@@ -1095,14 +1096,49 @@ __global__ __launch_bounds__(MdctBandCfg::NT) void k_mdct_ft32bc(
 // mode (its last frame alone).  Barriers order LDS only; the output stores are not waited for.
 // WINL: the window (4 NF floats) is staged in LDS; false (W = 4096): it is read from global memory -- the sweep form of the
 // overlap-add reads a thread's two window pairs once per tile -- which makes room for 16-frame tiles (64-byte gather runs) instead of 8.
-template <int LOG2NF, int LOG2E, int FPB, int NSLOT, int LAYOUT, bool WINL = true>
+// RAGGED (zafx_execute_imdct_ragged): blocks of different frame counts.  The walk is the same; `out_len` carries the table of unit records
+// (ImdctLenArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (ImdctUnit,
+// zafx_imdct_units.hpp: the host cuts the batch): the base of the clip's block -- its buffer descriptor is built from it --, its frames, pitch
+// and tiles, the base and the length of its output and the unit's tiles come from the record (uniform: scalar loads into SGPRs) instead of
+// from unit / segs, unit % segs and the kernel's arguments (rg_pick).  T, TP, tiles, segs and seg_tiles are not used.  The gather runs one
+// tile ahead and that tile may belong to the workgroup's next unit, so two records are live: rc, the unit being transformed and stored, and
+// rn, the workgroup's next one (unit + gridDim.x), both read at the head of the unit -- rc again, not handed over from rn: of rn only the
+// four fields the gather needs stay in SGPRs through the unit, with all of it the W = 1024 and 2048 forms spilled SGPRs.  The table comes in
+// launch order (imdct_deal_table: rounds of gridDim.x units dealt forwards and backwards in turn; a record without tiles where a short last
+// round leaves a workgroup idle), so the walk is the equal-length one.  Only the 16-byte gather with its prefetch exists in this form (the
+// launcher vouches for the pitches).
+// A sample pair as one 8-byte store at an address that is only 4-byte aligned (global memory takes multi-dword accesses on any dword): what
+// k_imdct's RAGGED form writes a clip on an odd output offset with.
+struct __attribute__((packed, aligned(4))) Float2OnDword {
+    float x, y;
+};
+__device__ __forceinline__ void store_pair_on_dword(float2* p, float2 v) {
+    Float2OnDword t;
+    t.x = v.x, t.y = v.y;
+    *reinterpret_cast<Float2OnDword*>(p) = t;
+}
+template <bool RAGGED>
+using ImdctLenArg = std::conditional_t<RAGGED, const ImdctUnit*, long long>;
+// The record of unit `u` (uniform) in SGPRs: read through the constant address space, as rg_clip_const -- nothing writes the table while a
+// kernel runs.
+__device__ __forceinline__ ImdctUnit imdct_unit_const(const ImdctUnit* tab, int u) {
+    typedef const __attribute__((address_space(4))) ImdctUnit* CRec;
+    const CRec r = (CRec)tab + u;
+    ImdctUnit rc;
+    rc.in_off = r->in_off, rc.out_off = r->out_off, rc.out_len = r->out_len;
+    rc.T = r->T, rc.TP = r->TP, rc.tiles = r->tiles, rc.tile_a = r->tile_a, rc.tile_b = r->tile_b, rc.pad_ = 0;
+    return rc;
+}
+template <int LOG2NF, int LOG2E, int FPB, int NSLOT, int LAYOUT, bool WINL = true, bool RAGGED = false>
 __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     const float* __restrict__ coefs, const float* __restrict__ win, const float2* __restrict__ twp,
-    const float2* __restrict__ tw8g, float* __restrict__ y, int T, int TP, long long out_len, int tiles, int segs, int seg_tiles,
+    const float2* __restrict__ tw8g, float* __restrict__ y, int T, int TP, ImdctLenArg<RAGGED> out_len, int tiles, int segs, int seg_tiles,
     int total_units) {
     using C = FftCfg<LOG2NF, LOG2E>;
     constexpr int NF = C::N, M = 2 * NF, P = C::P, E = C::E, NT = NSLOT * P;
     static_assert(NT % FPB == 0 || LAYOUT == ZAFX_LAYOUT_TF, "time-minor gather needs NT to be a multiple of FPB");
+    static_assert(!RAGGED || (LAYOUT == ZAFX_LAYOUT_FT && WINL && FPB % 4 == 0 && NT % (FPB / 4) == 0 && NF >= NT / (FPB / 4)),
+                  "ragged batches: reference layout, the 16-byte gather");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* frames = reinterpret_cast<float2*>(smem_raw);
     float2* tw_l = frames + FPB * C::PITCH;
@@ -1120,8 +1156,9 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     const float gain = 2.f / (float)M;
     // (buffer loads: 16 bytes per lane at ANY 4-byte alignment -- rows off the line grid, T % 4 != 0, took the 4-byte path before, four times
     // the load instructions and no prefetch: T = 433 1.31 ms against 0.76 at T = 432 -- and a piece that runs past the clip's last row reads 0)
-    const bool vec4 = LAYOUT == ZAFX_LAYOUT_FT && FPB % 4 == 0 && NT % (FPB / 4) == 0 && NF >= NT / (FPB / 4) && (long long)M * TP * 4 < (1LL << 32) &&
-                      reinterpret_cast<uintptr_t>(coefs) % 4 == 0;
+    // (RAGGED: the launcher admits batches of blocks below 2^32 bytes on a 4-byte aligned array only)
+    const bool vec4 = RAGGED || (LAYOUT == ZAFX_LAYOUT_FT && FPB % 4 == 0 && NT % (FPB / 4) == 0 && NF >= NT / (FPB / 4) && (long long)M * TP * 4 < (1LL << 32) &&
+                                 reinterpret_cast<uintptr_t>(coefs) % 4 == 0);
 
     // 16-byte gathers (vec4): a lane reads 4 adjacent frames of a row (8 lanes per 128-B run; the CU's vector-memory queue
     // holds ~64 wave-level loads whatever their width, 4-byte lanes leave it carrying 256 B per entry).  The rows of the
@@ -1137,25 +1174,30 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     constexpr int LPR = FPB >= 4 ? FPB / 4 : 1, MSTEP = NT / LPR;
     constexpr int KI = (NF % MSTEP == 0 && NF >= MSTEP) ? NF / MSTEP : 1;
     constexpr bool PRE = ZAFX_IMDCT_PREFETCH && LAYOUT == ZAFX_LAYOUT_FT && KI <= 4;
+    static_assert(!RAGGED || PRE, "ragged batches: the gather runs one tile ahead");
+    [[maybe_unused]] ImdctUnit rc{}, rn{};   // RAGGED: the records of the workgroup's current and of its next unit (of rn the gather's fields alone stay live: in_off, T, TP, tile_a)
     const int fs4 = (tid % LPR) * 4, mq4 = tid / LPR;
     float4 pre_re[KI], pre_im[KI];
     bool pre_ok = false;
     bool converted = false;   // pre_re / pre_im hold the pre-twiddled FFT inputs (convert_rows), not the raw rows
-    auto gather4 = [&](int unit_n, int tile_n, int part = 2) {   // rows of my 4 frames of tile_n of unit_n -> registers (part 0: the rows 2m, 1: the rows M-1-2m, 2: both)
+    // (ru: RAGGED, the record of unit_n; the clip's frames and pitch are the kernel's arguments otherwise -- rg_pick)
+    auto gather4 = [&](int unit_n, int tile_n, [[maybe_unused]] const ImdctUnit& ru, int part = 2) {   // rows of my 4 frames of tile_n of unit_n -> registers (part 0: the rows 2m, 1: the rows M-1-2m, 2: both)
         pre_ok = false;
         converted = false;
         if (!vec4 || unit_n >= total_units) return;
-        const int tile_a_n = (unit_n % segs) * seg_tiles;
+        const int tile_a_n = RAGGED ? ru.tile_a : (unit_n % segs) * seg_tiles;
         const int first_needed_n = tile_n < tile_a_n ? FPB - 1 : 0;
         const int t = tile_n * FPB + fs4;
-        if (t < T && fs4 + 3 >= first_needed_n) {   // pitch % 4 == 0: the four frames lie in the row (those past T are not used)
+        if (t < rg_pick<RAGGED>(ru.T, T) && fs4 + 3 >= first_needed_n) {   // pitch % 4 == 0: the four frames lie in the row (those past T are not used)
             pre_ok = true;
-            const __amdgpu_buffer_rsrc_t rs = make_rsrc(coefs + (long long)(unit_n / segs) * M * TP, (unsigned)((long long)M * TP * 4));
+            // (RAGGED: a descriptor per clip -- a piece that runs past the clip's last row reads 0, not the next block)
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(coefs + (RAGGED ? ru.in_off : (long long)(unit_n / segs) * M * rg_pick<RAGGED>(ru.TP, TP)),
+                                                        (unsigned)((long long)M * rg_pick<RAGGED>(ru.TP, TP) * 4));
 #pragma unroll
             for (int i = 0; i < KI; ++i) {
                 const int m = mq4 + i * MSTEP;
-                if (part != 1) pre_re[i] = buf_load_f32x4(rs, (int)(((unsigned)(2 * m) * (unsigned)TP + (unsigned)t) * 4u));
-                if (part != 0) pre_im[i] = buf_load_f32x4(rs, (int)(((unsigned)(M - 1 - 2 * m) * (unsigned)TP + (unsigned)t) * 4u));
+                if (part != 1) pre_re[i] = buf_load_f32x4(rs, (int)(((unsigned)(2 * m) * (unsigned)rg_pick<RAGGED>(ru.TP, TP) + (unsigned)t) * 4u));
+                if (part != 0) pre_im[i] = buf_load_f32x4(rs, (int)(((unsigned)(M - 1 - 2 * m) * (unsigned)rg_pick<RAGGED>(ru.TP, TP) + (unsigned)t) * 4u));
             }
         }
     };
@@ -1180,11 +1222,14 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
         }
         converted = true;
     };
-    auto first_tile = [&](int unit_n) {
-        const int ta = (unit_n % segs) * seg_tiles;
+    auto first_tile = [&](int unit_n, [[maybe_unused]] const ImdctUnit& ru) {
+        const int ta = RAGGED ? ru.tile_a : (unit_n % segs) * seg_tiles;
         return ta > 0 ? ta - 1 : 0;
     };
-    if constexpr (PRE) gather4(blockIdx.x, blockIdx.x < total_units ? first_tile(blockIdx.x) : 0);
+    if constexpr (RAGGED) {
+        if (blockIdx.x < total_units) rn = imdct_unit_const(out_len, blockIdx.x);
+    }
+    if constexpr (PRE) gather4(blockIdx.x, blockIdx.x < total_units ? first_tile(blockIdx.x, rn) : 0, rn);
     // Frame-major input: a frame's M coefficients are contiguous; lane p of the wave that owns a frame takes the pairs
     // (m, NF-1-m): the two 8-byte reads X[2m..2m+1] and X[M-2-2m..M-1-2m] hold both packed inputs
     // c[m] = X[2m] + i X[M-1-2m] and c[NF-1-m] = X[M-2-2m] + i X[2m+1] -- coalesced 512-B runs instead of 4-byte
@@ -1215,12 +1260,16 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
             }
         }
     };
-    if constexpr (PRE_TF) gather_tf(blockIdx.x, blockIdx.x < total_units ? first_tile(blockIdx.x) : 0);
+    if constexpr (PRE_TF) gather_tf(blockIdx.x, blockIdx.x < total_units ? first_tile(blockIdx.x, rc) : 0);
 
     PROF_INIT(g_prof_imdct);
     for (int unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
-    const int clip = unit / segs, seg = unit % segs;
-    const int tile_a = seg * seg_tiles, tile_b = min(tile_a + seg_tiles, tiles);
+    if constexpr (RAGGED) {   // (the unit's first tile is in flight: requested through the record that was rn then)
+        rc = imdct_unit_const(out_len, unit);
+        if (unit + gridDim.x < total_units) rn = imdct_unit_const(out_len, unit + gridDim.x);
+    }
+    const int clip = RAGGED ? 0 : unit / segs, seg = RAGGED ? 0 : unit % segs;
+    const int tile_a = RAGGED ? rc.tile_a : seg * seg_tiles, tile_b = RAGGED ? rc.tile_b : min(tile_a + seg_tiles, tiles);
     for (int c = tid; c < M; c += NT) carry[c] = 0.f;
     for (int tile = tile_a > 0 ? tile_a - 1 : 0; tile < tile_b; ++tile) {
     const bool carry_only = tile < tile_a;
@@ -1254,7 +1303,7 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
             for (int m = mq; m < NF; m += P) fb[phys(m)] = cmul(make_float2(cp[2 * m], cp[M - 1 - 2 * m]), tw8[m]);
         }
     } else if (vec4) {
-        if constexpr (!PRE) gather4(unit, tile);
+        if constexpr (!PRE) gather4(unit, tile, rc);
         if (pre_ok) {
             convert_rows();   // (already done at the start of the previous overlap-add, except for the first tile of the launch)
             float2* fb = frames + fs4 * C::PITCH;
@@ -1297,9 +1346,9 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
         int unit_n = unit, tile_n = tile + 1;
         if (tile_n >= tile_b) {
             unit_n = unit + gridDim.x;
-            tile_n = unit_n < total_units ? first_tile(unit_n) : 0;
+            tile_n = unit_n < total_units ? first_tile(unit_n, rn) : 0;
         }
-        gather4(unit_n, tile_n, part);
+        gather4(unit_n, tile_n, unit_n == unit ? rc : rn, part);
     };
     if constexpr (PRE) {
         if (gather_now) gather_next(STAGGER == 2 ? 0 : 2);
@@ -1309,7 +1358,7 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
         int unit_n = unit, tile_n = tile + 1;
         if (tile_n >= tile_b) {
             unit_n = unit + gridDim.x;
-            tile_n = unit_n < total_units ? first_tile(unit_n) : 0;
+            tile_n = unit_n < total_units ? first_tile(unit_n, rn) : 0;
         }
         gather_tf(unit_n, tile_n);
     }
@@ -1347,7 +1396,7 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     // ---- phase C: unfold + window + TDAC overlap-add of the 2 covering frames (older first, as the
     //      reference's loop), trim (zaf.py:1166-1182); then the carry for the next tile
     {
-        const int n_valid = min(FPB, T - t_first);
+        const int n_valid = min(FPB, rg_pick<RAGGED>(rc.T, T) - t_first);
         // Two samples (n1, n1 + 1) at a time: each of the four operands is one aligned 8-byte LDS read (the
         // reversed halves of the unfold come out swapped), the result one 8-byte store.
         const float2* frames2 = frames;
@@ -1371,8 +1420,15 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
             return make_float2(u.x * w.x, u.y * w.y);
         };
         if (!carry_only) {
-            const int c_end2 = (tile == tiles - 1 ? (n_valid + 1) * M : FPB * M) / 2;
-            float* yc = y + (long long)clip * out_len;
+            // (RAGGED: the clip's last tile is told from its frames and its samples are counted in 32 bits -- a block is below 2^32 bytes --: the
+            // record's `tiles` and the upper half of its `out_len` need no SGPRs through the tile)
+            bool last_tile;   // (partial: frames up to n_valid, one more span with the older term only, trimmed at out_len)
+            if constexpr (RAGGED) last_tile = t_first + FPB >= rc.T;
+            else last_tile = tile == tiles - 1;
+            const int c_end2 = (last_tile ? (n_valid + 1) * M : FPB * M) / 2;
+            [[maybe_unused]] const int clip_len32 = RAGGED ? (int)rc.out_len : 0;
+            const auto& clip_len = rg_pick<RAGGED>(clip_len32, out_len);   // samples of the unit's clip
+            float* yc = y + (RAGGED ? rc.out_off : (long long)clip * clip_len);
             const long long o_first = (long long)t_first * M - M;
             const bool y_aligned = (reinterpret_cast<uintptr_t>(yc) % 8) == 0;
             // A full tile inside the clip: thread tid owns the sample pair n1 = 2 tid mod M of the frames h, h + FR, ... (FR = 2 NT / M
@@ -1380,8 +1436,7 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
             // frame are fixed and a sweep is two 8-byte LDS reads, three packed operations and one 8-byte store at constant strides
             // (the general loop below re-derives all of that per pair and waits for each LDS read in turn: 13 k of the tile's
             // 38 k cycles at W = 2048).  Same operations in the same order: bit-identical to the general loop.
-            const bool last_tile = tile == tiles - 1;   // (partial: frames up to n_valid, one more span with the older term only, trimmed at out_len)
-            if (SWEEP && (last_tile || (n_valid == FPB && o_first + (long long)FPB * M <= out_len))) {
+            if (SWEEP && (last_tile || (n_valid == FPB && o_first + (long long)FPB * M <= clip_len))) {
                 int to = tid;   // opaque: the slots and window pairs are recomputed per tile (carried through the transforms they spill)
                 asm volatile("" : "+v"(to));
                 const int n1 = (2 * to) & (M - 1);
@@ -1417,12 +1472,13 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
                             // (the reference's output length (T-1) M - 1 is odd: every second clip of a batch starts on a 4-byte boundary)
                             const long long o = o_first + 2 * to + (long long)it * 2 * NT;
                             // (compiled per alignment: with the test at every store the compiler folded both forms into 4-byte stores)
-                            if (A8 && (!L || o + 1 < out_len)) {
-                                dst[(size_t)it * NT] = make_float2(a.x * gain, a.y * gain);
+                            if (A8 && (!L || o + 1 < clip_len)) {
+                                if constexpr (RAGGED) store_pair_on_dword(dst + (size_t)it * NT, make_float2(a.x * gain, a.y * gain));
+                                else dst[(size_t)it * NT] = make_float2(a.x * gain, a.y * gain);
                             } else {
                                 float* d1 = reinterpret_cast<float*>(dst + (size_t)it * NT);
-                                if (!L || o < out_len) d1[0] = a.x * gain;
-                                if (!L || o + 1 < out_len) d1[1] = a.y * gain;
+                                if (!L || o < clip_len) d1[0] = a.x * gain;
+                                if (!L || o + 1 < clip_len) d1[1] = a.y * gain;
                             }
                         }
                     }
@@ -1431,11 +1487,17 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
                     if (lo) sweep(std::true_type{}, LAST, ALIGNED8);
                     else sweep(std::false_type{}, LAST, ALIGNED8);
                 };
+                // RAGGED: the pair form at every output offset, as 8-byte stores that need their dword only (store_pair_on_dword).  The two
+                // store forms are two instantiations of the sweep, and the compiler contracts the multiply-adds of the partial (last-tile)
+                // one differently in each: through the 4-byte form a clip on an odd offset left with other last bits in its last tile than
+                // the same clip on an even one (about a sixth of that tile's samples, one rounding of a product each).  A clip's bits must
+                // not depend on where the caller puts it, so one arithmetic form serves both and only the store's alignment differs.
+                const bool pair_form = RAGGED || y_aligned;
                 if (last_tile) {
-                    if (y_aligned) sweep_lo(std::true_type{}, std::true_type{});
+                    if (pair_form) sweep_lo(std::true_type{}, std::true_type{});
                     else sweep_lo(std::true_type{}, std::false_type{});
                 } else {
-                    if (y_aligned) sweep_lo(std::false_type{}, std::true_type{});
+                    if (pair_form) sweep_lo(std::false_type{}, std::true_type{});
                     else sweep_lo(std::false_type{}, std::false_type{});
                 }
             } else {
@@ -1456,11 +1518,11 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
                 }
                 const long long o = o_first + c;
                 if (o >= 0) {
-                    if (y_aligned && o + 1 < out_len) {
+                    if (y_aligned && o + 1 < clip_len) {
                         *reinterpret_cast<float2*>(yc + o) = make_float2(acc.x * gain, acc.y * gain);
                     } else {
-                        if (o < out_len) yc[o] = acc.x * gain;
-                        if (o + 1 < out_len) yc[o + 1] = acc.y * gain;
+                        if (o < clip_len) yc[o] = acc.x * gain;
+                        if (o + 1 < clip_len) yc[o + 1] = acc.y * gain;
                     }
                 }
             }
@@ -1948,6 +2010,66 @@ static hipError_t run_imdct(const zafx_plan& pl, const float* coefs, float* y, i
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NSLOT * C::P), SMEM, pl.stream, coefs, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, y, T,
                        (int)row_pitch(pl, T), (long long)out_len, tiles, segs, seg_tiles, (int)units);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// ragged batches (zafx_execute_imdct_ragged): the units come cut and ordered from the host (imdct_cut_units)
+// ---------------------------------------------------------------------------------
+// k_imdct's RAGGED form: W = 512, 1024, 2048 in the reference layout, float32 -- where imdct_fpb gives 32-frame tiles and the 16-byte gather
+// with its prefetch applies.  The geometry is run_imdct's.
+template <int LOG2NF>
+struct ImdctRaggedCfg {
+    static constexpr int LOG2E = default_log2e(LOG2NF);
+    static constexpr int FPB = imdct_fpb(LOG2NF, ZAFX_LAYOUT_FT);
+    static constexpr int NSLOT = imdct_nslot(LOG2NF, FPB);
+    using C = FftCfg<LOG2NF, LOG2E>;
+    static constexpr bool WINL = imdct_win_lds(LOG2NF);
+    static constexpr size_t SMEM = (size_t)(FPB * C::PITCH + C::TW + C::N) * 8 + (WINL ? (size_t)C::N * 16 : 0) + (size_t)C::N * 8;
+    static_assert(FPB == kImdctRaggedTile, "zafx_execute_imdct_ragged cuts the batch for the kernel's tile");
+    static_assert(SMEM <= (size_t)kMaxLdsBytes, "IMDCT tile does not fit LDS");
+    static long long slots(const zafx_plan& pl) {   // resident workgroups: run_imdct's grid bound
+        const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / SMEM);
+        return (long long)pl.n_cus * std::max(per_cu, 1);
+    }
+};
+
+bool imdct_ragged_native(const zafx_plan& pl) {
+    return pl.kind == ZAFX_IMDCT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.layout == ZAFX_LAYOUT_FT && pl.log2nf >= 7 &&
+           pl.log2nf <= 9 && pl.d_window && pl.d_tw_pass && pl.d_tw_aux;
+}
+
+bool imdct_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots) {
+    switch (pl.log2nf) {
+        case 7: *slots = ImdctRaggedCfg<7>::slots(pl); break;
+        case 8: *slots = ImdctRaggedCfg<8>::slots(pl); break;
+        case 9: *slots = ImdctRaggedCfg<9>::slots(pl); break;
+        default: return false;
+    }
+    *tile_frames = kImdctRaggedTile;
+    return true;
+}
+
+template <int LOG2NF>
+static hipError_t run_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const ImdctUnit* d_units, long long n_units) {
+    using G = ImdctRaggedCfg<LOG2NF>;
+    auto kern = k_imdct<LOG2NF, G::LOG2E, G::FPB, G::NSLOT, ZAFX_LAYOUT_FT, G::WINL, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM); e != hipSuccess) return e;
+    pl.ran = "k_imdct_ragged";
+    if (n_units <= 0) return hipSuccess;
+    const long long grid = std::min<long long>(n_units, G::slots(pl));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NSLOT * G::C::P), G::SMEM, pl.stream, coefs, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, y, 0, 0, d_units,
+                       0, 0, 0, (int)n_units);
+    return hipGetLastError();
+}
+
+hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const ImdctUnit* d_units, long long n_units) {
+    if (!imdct_ragged_native(pl) || n_units >= (1LL << 31) || reinterpret_cast<uintptr_t>(coefs) % 4 != 0) return hipErrorInvalidValue;
+    switch (pl.log2nf) {
+        case 7: return run_imdct_ragged<7>(pl, coefs, y, d_units, n_units);
+        case 8: return run_imdct_ragged<8>(pl, coefs, y, d_units, n_units);
+        case 9: return run_imdct_ragged<9>(pl, coefs, y, d_units, n_units);
+    }
+    return hipErrorInvalidValue;
 }
 
 #define ZAFX_MDCT_SIZES(X) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11)

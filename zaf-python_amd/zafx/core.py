@@ -450,6 +450,38 @@ class Plan:
         _lib.check(_lib.load().zafx_execute_center_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, _i64p(out_offsets),
                                                           len(lengths)), "zafx_execute_center_ragged")
 
+    def execute_imdct_ragged(self, d_coefs, in_offsets, frames, d_out, out_offsets):
+        """Enqueue the IMDCT of coefficient blocks of different frame counts on the plan's stream (asynchronous; zafx_execute_imdct_ragged,
+        inverse MDCT plans only).  Block i starts at element in_offsets[i] of d_coefs: W/2 rows of frames[i] coefficients at the pitch
+        row_pitch(frames[i]) ("FT" -- the blocks a forward plan's execute_ragged writes at the same row_align), or frames[i] x W/2 compact
+        ("TF"); its max((W/2) (frames[i] - 1) - 1, 0) samples go to element out_offsets[i] of d_out.  Float32 "FT" plans of window 512, 1024
+        and 2048 whose pitches are multiples of 4 run as one launch (last_kernel: k_imdct_ragged), the others as one execute per clip.  Output
+        ranges that overlap are not detected."""
+        arrays = []
+        for name, values in (("in_offsets", in_offsets), ("frames", frames), ("out_offsets", out_offsets)):
+            a = np.asarray(values)
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise ValueError(f"{name} must be a 1-D sequence of integers")
+            arrays.append(np.ascontiguousarray(a, dtype=np.int64))
+        in_offsets, frames, out_offsets = arrays
+        if not len(in_offsets) == len(frames) == len(out_offsets):
+            raise ValueError("in_offsets, frames and out_offsets must have one entry per block")
+        if d_coefs.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
+            raise ValueError(f"execute_imdct_ragged takes {self.in_dtype} coefficients and a {self.out_dtype} output buffer")
+        m = int(self.params.window_length) // 2
+        if len(frames) and min(int(frames.min()), int(in_offsets.min()), int(out_offsets.min())) >= 0:   # (negative values: the library says so)
+            if self.layout == _lib.LAYOUT_FT:
+                a = max(self.row_align, 1)
+                ends = in_offsets + m * ((frames + a - 1) // a * a)   # (whole rows: the 16-byte gather may read a row's pad columns)
+            else:
+                ends = in_offsets + frames * m
+            if int(ends.max()) * d_coefs.dtype.itemsize > d_coefs.nbytes:
+                raise ValueError("a block reaches past the end of d_coefs")
+            if int((out_offsets + np.maximum(m * (frames - 1) - 1, 0)).max()) * d_out.dtype.itemsize > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_imdct_ragged(self.handle, d_coefs.ptr, _i64p(in_offsets), _i64p(frames), d_out.ptr, _i64p(out_offsets),
+                                                         len(frames)), "zafx_execute_imdct_ragged")
+
     def sync(self):
         _lib.check(_lib.load().zafx_sync(self.handle), "zafx_sync")
 
@@ -1256,6 +1288,85 @@ def mdct_ragged(clips, window_function, layout="FT", device=0, f64=False):
     plan = mdct_plan(w, layout, device, f64=f64)
     plan = _ragged_grid(plan, lambda a: mdct_plan(w, layout, device, row_align=a, f64=f64))
     return _as_f32_views(_run_ragged(plan, clips), plan, f64)
+
+
+def _as_ragged_blocks(coefficients, rows, layout):
+    """A ragged batch of MDCT coefficient blocks -- a sequence of 2-D real arrays, (rows, T_i) ["FT"] or (T_i, rows) ["TF"] -- validated ahead
+    of any device call."""
+    if isinstance(coefficients, np.ndarray) and coefficients.dtype != object and coefficients.ndim < 3:
+        raise ValueError("a ragged batch of coefficients is a sequence of 2-D blocks, not one array")
+    try:
+        items = list(coefficients)
+    except TypeError:
+        raise ValueError("a ragged batch of coefficients is a sequence of 2-D blocks") from None
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    out = []
+    for i, c in enumerate(items):
+        a = np.asarray(c)
+        if a.ndim != 2:
+            raise ValueError(f"block {i} of the ragged batch must be 2-D, got {a.ndim}-D")
+        if np.iscomplexobj(a) or a.dtype.kind not in "biuf":
+            raise ValueError(f"block {i} of the ragged batch must be real")
+        if a.shape[0 if ft else 1] != rows:
+            raise ValueError(f"block {i} of the ragged batch must have window_length/2 = {rows} coefficient rows, got shape {a.shape}")
+        out.append(a)
+    return out
+
+
+def imdct_ragged(coefficients, window_function, layout="FT", device=0, f64=False, lengths=None):
+    """imdct_batch of coefficient blocks of different frame counts in one call: a sequence of (W/2, T_i) real arrays ["FT"] or (T_i, W/2)
+    ["TF"] -> a list of 1-D float32 arrays (float64 arrays and arithmetic with f64) of max((W/2) (T_i - 1) - 1, 0) samples, as zaf.imdct gives
+    them for that block alone; with lengths=[N_i] each is cut to its first N_i samples (the clip mdct_ragged was given).  The arrays are views
+    of one result buffer.  One upload, one execute, one download; the views mdct_ragged returns are taken as they lie.  "FT" / float32 at
+    window 512, 1024 and 2048 runs in one launch (k_imdct_ragged); an empty list gives an empty list."""
+    w = _as_window(window_function, any_length=True)
+    if len(w) % 2 or len(w) < 4:
+        raise ValueError("the MDCT needs an even window_length >= 4")
+    _check_f64_window(len(w), bool(f64) or not _f32_window(len(w)))
+    _as_row_align(0, layout)   # (an unknown layout fails here)
+    m = len(w) // 2
+    blocks = _as_ragged_blocks(coefficients, m, layout)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    frames = np.array([b.shape[1 if ft else 0] for b in blocks], np.int64)
+    out_len = np.maximum(m * (frames - 1) - 1, 0)
+    if lengths is not None:
+        lengths = _as_lengths(lengths)
+        if len(lengths) != len(blocks):
+            raise ValueError("lengths must have one entry per block")
+        for i, (n, o) in enumerate(zip(lengths.tolist(), out_len.tolist())):
+            if n > o:
+                raise ValueError(f"lengths[{i}] = {n} exceeds the {o} samples block {i} gives")
+    if not blocks:
+        return []
+    plan = mdct_plan(w, layout, device, inverse=True, f64=f64)
+    plan = _ragged_grid(plan, lambda a: mdct_plan(w, layout, device, inverse=True, row_align=a, f64=f64))
+    # the blocks back to back at the plan's pitch (every block starts on a 128-byte line), the clips' samples on the same grid
+    a = max(plan.row_align, 1)
+    pitch = (frames + a - 1) // a * a if ft else np.full(len(blocks), m, np.int64)
+    elems = m * pitch if ft else frames * m
+    in_offsets = np.zeros(len(blocks), np.int64)
+    in_offsets[1:] = np.cumsum(elems)[:-1]
+    slots = (out_len + _RAGGED_ALIGN - 1) // _RAGGED_ALIGN * _RAGGED_ALIGN
+    out_offsets = np.zeros(len(blocks), np.int64)
+    out_offsets[1:] = np.cumsum(slots)[:-1]
+    packed = np.empty(max(int(elems.sum()), 1), plan.in_dtype)   # (the pad columns are never used: they stay as they come)
+    for b, o, t, p in zip(blocks, in_offsets.tolist(), frames.tolist(), pitch.tolist()):
+        if ft:
+            packed[o:o + m * p].reshape(m, p)[:, :t] = b   # (rows of a view at any pitch: copied row by row)
+        else:
+            packed[o:o + t * m].reshape(t, m)[...] = b
+    d_in = DeviceBuffer(packed.shape, packed.dtype, plan.device).upload(packed)
+    d_out = DeviceBuffer((max(int(slots.sum()), 1),), plan.out_dtype, plan.device)
+    try:
+        with plan.lock:
+            plan.execute_imdct_ragged(d_in, in_offsets, frames, d_out, out_offsets)
+            plan.sync()
+            res = d_out.download()
+    finally:
+        d_in.free()
+        d_out.free()
+    keep = out_len if lengths is None else lengths
+    return _as_f32_views([res[o:o + n] for o, n in zip(out_offsets.tolist(), keep.tolist())], plan, f64)
 
 
 def melspectrogram_ragged(clips, window_function, step_length, mel_filterbank, layout="FT", device=0, f64=False):
