@@ -237,7 +237,9 @@ int zafx_execute_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_off
  * equal-length kind, one per clip).  Every clip's result is bit-identical to zafx_execute on that clip alone.  A clip of
  * length 0 is skipped: nothing of it is written.  The three host arrays are copied before return.  Rejected with a message:
  * n_clips < 0, negative lengths or offsets, a clip of 2^28 sample frames or more.  NOT checked: that the output blocks do not
- * overlap -- placing them is the caller's business.  d_in and d_out need 8-byte alignment only. */
+ * overlap -- placing them is the caller's business.  d_in and d_out need 4-byte alignment only, as every float32 array (the opening
+ * contract): a sample frame is read and written as one 8-byte piece, at the clip's own base plus a multiple of 8 bytes, whatever that base is
+ * (k_center has no address test; tests/test_gpu_arena.py runs bases at 4 mod 8). */
 int zafx_execute_center_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
                                const int64_t* out_offsets, int64_t n_clips);
 /* The IMDCT of n_clips coefficient blocks of different frame counts, enqueued on the plan's stream (asynchronous; ZAFX_IMDCT plans only --

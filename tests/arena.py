@@ -18,6 +18,10 @@ the zafx module as an argument, so this file imports nothing from the GPU side a
     (c) the values are finite and within `tol` (normwise per clip, conftest.relerr) of the float64 oracle,
     and, in a second pass at the same addresses with the middle clip poisoned (NaN), every other clip is bit-identical.
 
+Entry points that put every clip's result where the caller says (zafx_execute_center_ragged, zafx_execute_imdct_ragged) leave room between the
+blocks: a GAP is a Block of `frames` = 0 (gap_block), every element of which must still carry the fill -- reported as (a), a write outside the
+clips.  Blocks and gaps together tile the array.
+
 NaN payloads do not survive `==`: everything is compared as integers."""
 import ctypes
 from collections import namedtuple
@@ -31,6 +35,15 @@ MIN_GUARD = 64 * 1024
 # One clip's part of the output array: `offset` elements into the array, `shape` (rows, pitch) or (samples,), the first `frames` elements of
 # the last axis are the clip's (the rest is row padding), `ref` the oracle's compact result (shape[:-1] + (frames,)).
 Block = namedtuple("Block", "offset shape frames ref")
+
+
+def gap_block(offset, elems):
+    """`elems` elements at `offset` that belong to no clip: nothing may be written there."""
+    return Block(int(offset), (int(elems),), 0, None)
+
+
+def is_gap(block):
+    return block.frames == 0 and block.ref is None
 
 
 def guard_bytes(*clip_bytes):
@@ -130,6 +143,11 @@ def check_arena(arena, span, dtype, blocks, tol, relerr, skip=()):
     got = extract(arena, span, dtype, blocks)
     words = dtype.itemsize // wdtype.itemsize   # (2 for complex)
     for c, (b, g) in enumerate(zip(blocks, got)):
+        if is_gap(b):
+            # (a) for the room between two clips: every WORD still the fill (complex: both parts)
+            hit = np.ascontiguousarray(g).view(wdtype) != value
+            assert not hit.any(), f"(a) written into the gap in front of block {c + 1}: {int(hit.sum())} words changed, the first at element {b.offset + _first(hit) // words} of the array"
+            continue
         carries = (np.ascontiguousarray(g).view(wdtype).reshape(g.shape + (words,)) == value).any(axis=-1)
         inside, padding = carries[..., :b.frames], carries[..., b.frames:]
         # (b) every element written, no padding element written
@@ -154,7 +172,7 @@ def check_neighbours(clean, poisoned, blocks, dtype, middle=1):
     """The poisoned-neighbour pass: every clip but `middle` bit-identical to the clean pass (the clips' elements; padding is (b)'s)."""
     wdtype = fill_word(dtype)[0]
     for c, (b, a, p) in enumerate(zip(blocks, clean, poisoned)):
-        if c == middle:
+        if c == middle or is_gap(b):
             continue
         a = np.ascontiguousarray(a[..., :b.frames]).view(wdtype)
         p = np.ascontiguousarray(p[..., :b.frames]).view(wdtype)
@@ -194,11 +212,12 @@ def poisoned_copy(x, middle=1):
     return y
 
 
-def run_case(zafx, x, out_dtype, blocks, guard, deltas, launch, tol, relerr, poisoned=None, exact=None, exact_tol=0.0):
+def run_case(zafx, x, out_dtype, blocks, guard, deltas, launch, tol, relerr, poisoned=None, exact=None, exact_tol=0.0, middle=1):
     """One array pair at one (delta_in, delta_out): the clean pass with (a), (b), (c), then the poisoned-neighbour pass with (a), (b) and the
     bit comparison of clips 0 and 2.  `poisoned`: the input of the second pass (default: clip 1 of `x` all NaN).  `exact` (integer PCM):
     the same call's result on a plain allocation -- the clean pass must equal it bit for bit (exact_tol 0: the same kernel form ran there) or
-    within exact_tol normwise (another form of the kernel: same frames, other rounding order)."""
+    within exact_tol normwise (another form of the kernel: same frames, other rounding order).  `middle`: the poisoned clip's index in `blocks`
+    (gaps count); None: no second pass (a case without a neighbour to poison)."""
     out_elems = sum(int(np.prod(b.shape, dtype=np.int64)) for b in blocks)
     arena, span = run_in_arena(zafx, x, out_dtype, out_elems, guard, deltas[0], deltas[1], launch)
     clean = check_arena(arena, span, out_dtype, blocks, tol, relerr)
@@ -211,7 +230,9 @@ def run_case(zafx, x, out_dtype, blocks, guard, deltas, launch, tol, relerr, poi
             assert err <= exact_tol, f"{err:.3e} off the same call on a plain allocation, bound {exact_tol:.1e}"
         else:
             assert np.array_equal(have, want), "differs bitwise from the same call on a plain allocation"
+    if middle is None:
+        return clean
     arena2, span2 = run_in_arena(zafx, poisoned_copy(x) if poisoned is None else poisoned, out_dtype, out_elems, guard, deltas[0], deltas[1], launch)
-    other = check_arena(arena2, span2, out_dtype, blocks, tol, relerr, skip=(1,))
-    check_neighbours(clean, other, blocks, out_dtype)
+    other = check_arena(arena2, span2, out_dtype, blocks, tol, relerr, skip=(middle,))
+    check_neighbours(clean, other, blocks, out_dtype, middle)
     return clean

@@ -51,3 +51,46 @@ def signal(name, n):
     else:
         raise KeyError(name)
     return x.astype(np.float32)
+
+
+# Stereo clips for the center / sides extraction (zaf.py:155-198), built from the mono recipes above -- which stay as they are: signals.npz
+# pins their sums.  Each name is a case of the mask arithmetic (zafx_center.hpp): 0 / 0 in every bin, one channel's peak over the other's
+# leakage, a mask of exactly 0.5, a == b in every bin, a loud passage in front of a quiet one, a reference that is identically zero.
+STEREO_NAMES = ("silence", "dc", "pan_tones", "gain", "anti", "tones_chirp", "impulse", "noise_m90", "clipped", "loud_quiet", "left_only")
+
+
+def stereo_signal(name, n):
+    """(n, 2) float32: left, right."""
+    if name == "silence":
+        l, r = signal("silence", n), signal("silence", n)
+    elif name == "dc":
+        l, r = signal("dc", n), np.full(n, 0.25, np.float32)
+    elif name == "pan_tones":         # hard-panned tones: each channel's peak sits over the other's leakage
+        l, r = signal("sine_bin", n), signal("sine_half", n)
+    elif name == "gain":              # m0 = 0.5 exactly, m1 = 1: the center is 0.5 s in both channels
+        l = signal("sine_half", n)
+        r = np.float32(0.5) * l
+    elif name == "anti":              # a == b in every bin: both masks 1
+        l = signal("chirp", n)
+        r = -l
+    elif name == "tones_chirp":
+        l, r = signal("two_tones", n), signal("chirp", n)
+    elif name == "impulse":
+        l = signal("impulse", n)
+        r = np.roll(l, 3)
+    elif name == "noise_m90":         # two independent noises at -90 dBFS
+        l = signal("noise_m90", n)
+        r = (np.random.default_rng([91, n]).standard_normal(n) * 10.0 ** (-90.0 / 20.0)).astype(np.float32)
+    elif name == "clipped":
+        l = signal("clipped_pcm", n)
+        r = (np.rint(0.7 * l.astype(np.float64) * 32768.0) / 32768.0).astype(np.float32)
+    elif name == "loud_quiet":        # unit noise, then noise at -90 dB / the same reversed in time
+        g = np.random.default_rng([92, n]).standard_normal(n)
+        g[n // 2:] *= 10.0 ** (-90.0 / 20.0)
+        l = g.astype(np.float32)
+        r = l[::-1]
+    elif name == "left_only":         # the center is exactly 0 in the reference arithmetic
+        l, r = signal("chirp", n), signal("silence", n)
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(np.stack([l, r], axis=1), dtype=np.float32)

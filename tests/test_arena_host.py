@@ -132,3 +132,53 @@ def test_fills_and_guards():
     assert np.isnan(arena.filled(arena.Span(8, arena.MIN_GUARD, 4), arena.poison_word(np.complex64))[arena.MIN_GUARD + 4:][:8].copy().view(np.float32)).all()
     with pytest.raises(ValueError):
         arena.Span(8, 1000, 0)
+
+
+# ------------------------------------------------------------------------------------------------ gap blocks
+def gapped(delta_out=4):
+    """Three 1-D clips of 50, 1 and 33 float32 samples at caller-chosen places -- gaps of 1 and 3 elements between them and a tail of 2 --, as
+    the ragged center and IMDCT entry points write them: the blocks, the span and a clean arena with the oracle's numbers in the clips."""
+    ref = [np.cumsum(synth_clip(5, c, n).astype(np.float64)) for c, n in enumerate((50, 1, 33))]
+    blocks = [arena.Block(0, (50,), 50, ref[0]), arena.gap_block(50, 1), arena.Block(51, (1,), 1, ref[1]), arena.gap_block(52, 3),
+              arena.Block(55, (33,), 33, ref[2]), arena.gap_block(88, 2)]
+    span = arena.Span(90 * 4, arena.guard_bytes(200, 200), delta_out)
+    out = arena.filled(span, arena.fill_word(np.float32))
+    for b in blocks:
+        if not arena.is_gap(b):
+            out[span.lo + 4 * b.offset:span.lo + 4 * (b.offset + b.frames)] = np.frombuffer(b.ref.astype(np.float32).tobytes(), dtype=np.uint8)
+    return blocks, span, out
+
+
+def test_gap_blocks_accept_a_clean_arena():
+    blocks, span, out = gapped()
+    got = arena.check_arena(out, span, np.float32, blocks, TOL, relerr)
+    assert [g.shape for g in got] == [(50,), (1,), (1,), (3,), (33,), (2,)]
+    other = arena.check_arena(out, span, np.float32, blocks, TOL, relerr, skip=(2,))
+    arena.check_neighbours(got, other, blocks, np.float32, middle=2)
+
+
+@pytest.mark.parametrize("at,message", [(50, r"\(a\) written into the gap in front of block 2: 1 words changed, the first at element 50 of the array"),
+                                        (54, r"\(a\) written into the gap in front of block 4: 1 words changed, the first at element 54"),
+                                        (89, r"\(a\) written into the gap in front of block 6: 1 words changed, the first at element 89"),
+                                        (-1, r"\(a\) written in front of the array: byte -4"),
+                                        (90, r"\(a\) written behind the array: byte 0 past the end")])
+def test_gap_blocks_report_a_write(at, message):
+    """One float32 zero written into a gap, in front of the array and behind it: each is reported where it is."""
+    blocks, span, out = gapped()
+    out[span.lo + 4 * at:span.lo + 4 * at + 4] = 0
+    with pytest.raises(AssertionError, match=message):
+        arena.check_arena(out, span, np.float32, blocks, TOL, relerr)
+
+
+def test_gap_blocks_still_find_an_unwritten_element_and_a_leak():
+    blocks, span, out = gapped()
+    clean = arena.check_arena(out, span, np.float32, blocks, TOL, relerr)
+    bad = out.copy()
+    bad[span.lo + 4 * 60:span.lo + 4 * 61] = np.frombuffer(np.array([arena.FILL32], np.uint32).tobytes(), dtype=np.uint8)
+    with pytest.raises(AssertionError, match=r"\(b\) clip 4: 1 elements never written, the first at index \[5\]"):
+        arena.check_arena(bad, span, np.float32, blocks, TOL, relerr)
+    leak = out.copy()
+    leak[span.lo + 4 * 70] ^= 1
+    other = arena.check_arena(leak, span, np.float32, blocks, TOL, relerr, skip=(2,))
+    with pytest.raises(AssertionError, match=r"clip 4 depends on clip 2: 1 words differ"):
+        arena.check_neighbours(clean, other, blocks, np.float32, middle=2)

@@ -46,7 +46,14 @@ Route table -- geometry: (delta_in, delta_out) -> kernel, as the launchers read 
   float64: STFT d_i % 16 == 0 and d_o % 16 == 0 -> k_stft_ft8_f64 else k_stft_f64; mel / mfcc, CQT: d_i % 16 == 0 -> k_mel_ft8_f64 / k_cqt_ft_f64 else
     k_mel_f64 / k_cqt_f64; ISTFT, MDCT, IMDCT W 2048 -> k_istft_ft8_f64, k_mdct_ft16_f64, k_imdct_ft16_f64 at every offset; W 256: the generic kernels
   center / sides -> k_center (no address test in zafx_center.hip)
-  ragged: d_o % 128 == 0 -> one launch (k_stft_ft16_ragged / k_mel2_ragged), d_o = 8 -> "per-clip ..."
+  ragged: d_o % 128 == 0 -> one launch (k_stft_ft16_ragged / k_mel2_ragged / k_mdct_ft32_ragged), d_o = 8 -> "per-clip ..."
+    k_mdct_ft32_ragged (zafx_capi.cpp zafx_execute_ragged): the 16-byte-load form at d_i % 16 == 0 with every offset and length a multiple of 4,
+    the 4-byte form otherwise -- aligned lengths on a base 4 or 8 bytes off included: one name
+    k_imdct_ragged (zafx_execute_imdct_ragged): every d_i, d_o on the 4-byte grid at pitches that are multiples of 4 (16-byte buffer loads at any
+    4-byte alignment, pair stores that need their dword only); k_center_ragged (zafx_execute_center_ragged): every d_i, d_o on the 4-byte grid
+    (no address test: 8-byte pieces at the clip's base plus multiples of 8)
+  The entry points that take free offsets (all three ragged ones on the input side; center and IMDCT on the output side too) run with gaps of
+  1, 3 and 5 elements between the clips: poison on the input side, arena.gap_block on the output side.
 
 Not reachable through the entry points: the `d_matrix` / `d_window` / `win` tests (zafx_linear.hip:168, zafx_mdct.hip:70, :1847 -- plan-owned
 allocations, always on the grid); `x % 4`, `out % 4`, `coefs % 4` (zafx_stft.hip:2603, :2670-:2688, zafx_mdct.hip:1081, :1573, :1585-:1586: a float32
@@ -96,8 +103,9 @@ def zafx():
 class Prep:
     """One case, ready to run: the input, the output's blocks (with the oracle's results), the launch and the kernel each pair must reach."""
 
-    def __init__(self, plan, x, n_in, blocks, tol, want, err=relerr, launch=None, poisoned=None, exact=None, exact_kernel=None, n_clips=None, out_dtype=None):
-        self.plan, self.x, self.n_in, self.blocks, self.tol, self.want, self.err = plan, x, n_in, blocks, tol, want, err
+    def __init__(self, plan, x, n_in, blocks, tol, want, err=relerr, launch=None, poisoned=None, exact=None, exact_kernel=None, n_clips=None, out_dtype=None,
+                 middle=1):
+        self.plan, self.x, self.n_in, self.blocks, self.tol, self.want, self.err, self.middle = plan, x, n_in, blocks, tol, want, err, middle
         self.poisoned, self.exact, self.exact_kernel, self.out_dtype = poisoned, exact, exact_kernel, np.dtype(out_dtype or plan.out_dtype)
         n_clips = len(x) if n_clips is None else n_clips
         self.launch = launch or (lambda d_in, d_out: (plan.execute(d_in, d_out, n_clips, n_in), plan.sync()))
@@ -113,7 +121,8 @@ def run(zafx, prep, which):
     for pair in which:
         try:
             arena.run_case(zafx, prep.x, prep.out_dtype, prep.blocks, prep.guard, pair, prep.launch, prep.tol, prep.err,
-                           poisoned=prep.poisoned, exact=prep.exact, exact_tol=0.0 if prep.want(*pair) == prep.exact_kernel else OTHER_FORM)
+                           poisoned=prep.poisoned, exact=prep.exact, exact_tol=0.0 if prep.want(*pair) == prep.exact_kernel else OTHER_FORM,
+                           middle=prep.middle)
         except AssertionError as exc:
             failures.append(f"{pair}: {exc}")
         except zafx.ZafxError as exc:
@@ -332,6 +341,20 @@ def mdct_prep(zafx, w, layout, grid, row_align=0, f64=False, tile=32):
 @pytest.mark.parametrize("w", MDCT_WINDOWS)
 def test_mdct(zafx, w, layout, row_align, grid):
     run(zafx, mdct_prep(zafx, w, layout, grid, row_align), pairs(DELTAS))
+
+
+@pytest.mark.parametrize("w", [2048, 4096, 512])
+def test_mdct_padded_rows_odd_frames(zafx, w):
+    """row_align = 32 with n a multiple of 4 and T = 39, odd: rows of 64 with 25 padding elements.  On an output base off the 64-byte grid the
+    launchers take the carry forms (inside k_mdct_ft32; k_mdct_ft32bc at W = 4096), whose pair store of frames (38, 39) used to reach the first
+    padding element: test_mdct's "on" grid has an even T and its "off" grid a length off the 4-sample grid, which takes other forms."""
+    m = w // 2
+    n = 37 * m + 4
+    x, ref = mdct_ref(w, n, False)
+    plan = zafx.mdct_plan(window(zafx, w, True), row_align=32)
+    T, pitch = plan.out_dims(n)[1], plan.row_pitch(n)
+    assert (T, pitch) == (39, 64) and ref.shape[2] == T and n % 4 == 0
+    run(zafx, Prep(plan, x, n, blocks_2d(plan, 3, n, list(ref)), TOL_FFT, mdct_want(w, "FT", n, T, pitch)), pairs(DELTAS))
 
 
 @functools.lru_cache(maxsize=32)
@@ -625,3 +648,160 @@ def test_ragged(zafx, route):
     prep = Prep(plan, flat, None, blocks, tol, lambda di, do: native if do % 128 == 0 else "per-clip*", launch=launch, poisoned=poisoned, n_clips=1)
     prep.guard = arena.guard_bytes(int(lengths.max()) * 4, max(rows * int(p) for p in pitch) * plan.out_dtype.itemsize)
     run(zafx, prep, RAGGED_PAIRS)
+
+
+# ------------------------------------------------------------------------------------------------ the ragged MDCT, IMDCT and center launches
+INPUT_GAPS = (1, 3, 5)     # elements of poison behind clips 0, 1 and 2 of the input (the entry points take free offsets)
+POISON32 = np.array([arena.poison_word(np.float32)[1]], np.uint32).view(np.float32)[0]
+
+
+def with_gaps(parts, gaps, unit=1):
+    """`parts` (1-D float32 arrays) laid out with gaps[i] * unit poison elements behind part i: -> (flat, offsets in elements)."""
+    offsets, pieces, at = [], [], 0
+    for i, a in enumerate(parts):
+        offsets.append(at)
+        g = np.full(gaps[i % len(gaps)] * unit, POISON32, np.float32)
+        pieces += [np.ascontiguousarray(a, np.float32).reshape(-1), g]
+        at += a.size + g.size
+    flat = np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
+    return flat, np.array(offsets, np.int64)
+
+
+def ragged_guard(in_elems, blocks):
+    """arena.guard_bytes(longest clip's input bytes, largest block's output bytes): the harness's condition (tests/arena.py)."""
+    return arena.guard_bytes(int(max(in_elems)) * 4, max(int(np.prod(b.shape, dtype=np.int64)) for b in blocks) * 4)
+
+
+@pytest.mark.parametrize("form", ["edge", "aligned"])
+@pytest.mark.parametrize("w", [2048, 512])
+def test_mdct_ragged(zafx, w, form):
+    """k_mdct_ft32_ragged: three lengths in one call at row_align = 32.  "edge": lengths off the 4-sample grid with 1, 3 and 5 poisoned samples
+    behind the clips -- a clip that reads past its end (a KBD window edge of 1e-5 hides that on noise) or in front of its start reads NaN;
+    "aligned": lengths that are multiples of 4 back to back -- the 16-byte-load form at delta_in = 128 and 16, the 4-byte form on a base 4
+    or 8 bytes off.  One launch at delta_out = 128, one execute per clip at 8."""
+    m = w // 2
+    lengths = [37 * m + 5, 3000 + 1, 33 * m]
+    if form == "aligned":
+        lengths = [n - n % 4 for n in lengths]
+    x = [np.random.default_rng([78, w, i]).standard_normal(n).astype(np.float32) for i, n in enumerate(lengths)]
+    flat, in_offsets = with_gaps(x, INPUT_GAPS if form == "edge" else (0,))
+    lengths = np.array(lengths, np.int64)
+    assert form == "edge" or not (in_offsets % 4).any() and not (lengths % 4).any()
+    win = orc.kbd_window(w)
+    ref = [orc.mdct(c.astype(np.float64), win) for c in x]
+    plan = zafx.mdct_plan(zafx.kaiser_bessel_derived(w), row_align=32)
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    blocks = [arena.Block(int(offs[i]), (m, int(pitch[i])), int(frames[i]), ref[i]) for i in range(3)]
+    assert int(offs[3]) == sum(m * int(p) for p in pitch) and [r.shape[1] for r in ref] == frames.tolist()
+    poisoned = flat.copy()
+    poisoned[in_offsets[1]:in_offsets[1] + lengths[1]] = np.nan
+    launch = lambda d_in, d_out: (plan.execute_ragged(d_in, in_offsets, lengths, d_out), plan.sync())
+    prep = Prep(plan, flat, None, blocks, TOL_FFT, lambda di, do: "k_mdct_ft32_ragged" if do % 128 == 0 else "per-clip*", launch=launch, poisoned=poisoned, n_clips=1)
+    prep.guard = ragged_guard(lengths, blocks)
+    run(zafx, prep, RAGGED_PAIRS + [(8, 128), (16, 128)])
+
+
+IMDCT_RAGGED_PAIRS = [(di, do) for di in (128, 4, 8) for do in (128, 4, 8)]
+
+
+def imdct_ragged_prep(zafx, w, frames, row_align, middle):
+    """Blocks of `frames` frames at the plan's pitch, pad columns NaN, 1, 3 and 5 poisoned floats behind them; the clips' samples at
+    caller-chosen places with 1 and 3 floats between them and 2 behind the last.  `middle`: the block the second pass poisons, or None."""
+    m = w // 2
+    win = orc.kbd_window(w)
+    plan = zafx.mdct_plan(zafx.kaiser_bessel_derived(w), inverse=True, row_align=row_align)
+    coefs, ref, packed = [], [], []
+    for i, t in enumerate(frames):
+        c = orc.mdct(np.random.default_rng([79, w, i]).standard_normal((t - 1) * m), win).astype(np.float32)
+        assert c.shape == (m, t)
+        p = plan.row_pitch(t)
+        assert p % 4 == 0   # (native by the header's contract)
+        rows = np.full((m, p), np.nan, np.float32)
+        rows[:, :t] = c
+        coefs.append(c), packed.append(rows)
+        ref.append(orc.imdct(c.astype(np.float64), win) if t > 1 else np.zeros(0))
+    flat, in_offsets = with_gaps(packed, INPUT_GAPS)
+    blocks, out_offsets, at = [], [], 0
+    for i, r in enumerate(ref):
+        out_offsets.append(at)
+        if len(r):
+            assert len(r) == m * (frames[i] - 1) - 1
+            blocks.append(arena.Block(at, (len(r),), len(r), r))
+            at += len(r)
+        gap = (1, 3, 2)[i]   # (a block of one frame writes nothing: its place is the gap that follows)
+        blocks.append(arena.gap_block(at, gap))
+        at += gap
+    poisoned = None
+    if middle is not None:
+        poisoned = flat.copy()
+        poisoned[in_offsets[middle]:in_offsets[middle] + packed[middle].size] = np.nan
+    frames_a, out_a = np.array(frames, np.int64), np.array(out_offsets, np.int64)
+    launch = lambda d_in, d_out: (plan.execute_imdct_ragged(d_in, in_offsets, frames_a, d_out, out_a), plan.sync())
+    prep = Prep(plan, flat, None, blocks, TOL_FFT, lambda di, do: "k_imdct_ragged", launch=launch, poisoned=poisoned, n_clips=1,
+                middle=None if middle is None else 2 * middle)   # (clip i is block 2 i: a gap follows every clip)
+    prep.guard = ragged_guard([r.size for r in packed], blocks)
+    return prep
+
+
+@pytest.mark.parametrize("rows", ["padded", "compact", "one_frame"])
+@pytest.mark.parametrize("w", [2048, 512])
+def test_imdct_ragged(zafx, w, rows):
+    """k_imdct_ragged on coefficient arrays and sample arrays 4 and 8 bytes off the grid (16-byte buffer loads "at any 4-byte alignment", pair
+    stores that need their dword only: include/zafx.h).  "padded": 37, 2 and 33 frames in rows of 64, 32 and 64 with NaN pad columns;
+    "compact": 36, 4 and 32 frames at a pitch of their own, every one a multiple of 4; "one_frame": the middle block is a single frame,
+    which writes nothing -- its place in the output is a gap (one pass: there is no neighbour's result to compare)."""
+    if rows == "padded":
+        prep = imdct_ragged_prep(zafx, w, [37, 2, 33], 32, 1)
+    elif rows == "compact":
+        prep = imdct_ragged_prep(zafx, w, [36, 4, 32], 0, 1)
+    else:
+        prep = imdct_ragged_prep(zafx, w, [37, 1, 33], 32, None)
+    run(zafx, prep, IMDCT_RAGGED_PAIRS)
+
+
+# (4, 4), (4, 128): a base at 4 mod 8 -- k_center reads and writes a sample frame as one 8-byte piece at the clip's base plus a multiple of 8,
+# and test_center runs the same loads and stores at delta = 4; include/zafx.h states the 4-byte rule for zafx_execute_center_ragged
+CENTER_RAGGED_PAIRS = [(8, 8), (16, 64), (64, 128), (128, 8), (4, 4), (4, 128)]
+
+
+@pytest.mark.parametrize("empty", [False, True], ids=["three", "with_empty"])
+@pytest.mark.parametrize("sides", [True, False], ids=["center_sides", "center"])
+@pytest.mark.parametrize("w", [256, 1024, 2048])
+def test_center_ragged(zafx, w, sides, empty):
+    """k_center_ragged: clips of 2 F H + 65, F H (a tile's end exactly) and 3 F H - 1 sample frames with 1, 3 and 5 poisoned sample frames
+    behind them, their results at caller-chosen places with 1 and 3 sample frames between the blocks; "with_empty": a fourth clip of length
+    0, of which nothing is written.  test_center's error function (center normwise, sides against the input's level)."""
+    from center_oracle import oracle_center
+    from test_gpu_center import stereo
+    f, h = zafx.center_tile_frames(w), w // 2
+    lengths = [2 * f * h + 65, f * h, 3 * f * h - 1] + ([0] if empty else [])
+    x = [stereo(3 * w + c, n) for c, n in enumerate(lengths)]
+    flat, in_floats = with_gaps(x, INPUT_GAPS, unit=2)
+    win = zafx.hamming(w)
+    center = [oracle_center(c, win) for c in x[:3]]
+    ref = [np.stack([c, xc.astype(np.float64) - c]) for c, xc in zip(center, x)] if sides else center
+    per = 2 if sides else 1
+    blocks, out_offsets, at = [], [], 0   # (in sample frames)
+    for i, n in enumerate(lengths):
+        out_offsets.append(at)
+        if n:
+            blocks.append(arena.Block(2 * at, ref[i].shape, 2, ref[i]))
+            at += per * n
+        gap = (1, 3, 2, 4)[i]   # (the empty clip's place is a gap)
+        blocks.append(arena.gap_block(2 * at, 2 * gap))
+        at += gap
+    plan = zafx.center_plan(win, sides=sides)
+    in_offsets, lens, outs = in_floats // 2, np.array(lengths, np.int64), np.array(out_offsets, np.int64)
+    poisoned = flat.copy()
+    poisoned[in_floats[1]:in_floats[1] + 2 * lengths[1]] = np.nan
+
+    def err(val, r):
+        if not sides:
+            return relerr(val, r)
+        level = float(np.abs(r[0] + r[1]).max())
+        return max(relerr(val[0], r[0]), float(np.abs(val[1] - r[1]).max()) / level)
+
+    launch = lambda d_in, d_out: (plan.execute_center_ragged(d_in, in_offsets, lens, d_out, outs), plan.sync())
+    prep = Prep(plan, flat, None, blocks, TOL_FFT, lambda di, do: "k_center_ragged", err=err, launch=launch, poisoned=poisoned, n_clips=1, middle=2)
+    prep.guard = ragged_guard([2 * n for n in lengths], blocks)
+    run(zafx, prep, CENTER_RAGGED_PAIRS)

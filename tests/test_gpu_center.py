@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+from center_oracle import oracle_center
 from conftest import GOLDEN, ROOT, relerr
 
 pytestmark = pytest.mark.gpu
@@ -25,19 +26,6 @@ def stereo(seed, n):
     g = np.random.default_rng([909, seed])
     c, n1, n2 = g.standard_normal(n), g.standard_normal(n), g.standard_normal(n)
     return np.stack([c + 0.5 * n1, 0.8 * c + 0.5 * n2], axis=1).astype(np.float32)
-
-
-def oracle_center(x, w):
-    """zaf.py:176-195 with the oracle's stft / istft, float64; the mask in the library's comparison form."""
-    from oracle import zaf_oracle as orc
-    x = np.asarray(x, np.float64)
-    wl, h = len(w), len(w) // 2
-    s = [orc.stft(x[:, c], w, h) for c in (0, 1)]
-    a, b = np.abs(s[0][:wl // 2 + 1]), np.abs(s[1][:wl // 2 + 1])
-    with np.errstate(divide="ignore", invalid="ignore"):
-        m = [np.where(b < a, b / a, 1.0), np.where(a < b, a / b, 1.0)]
-    y = [orc.istft(np.concatenate((m[c], m[c][-2:0:-1])) * s[c], w, h)[:len(x)] for c in (0, 1)]
-    return np.stack(y, axis=1)
 
 
 def check(center, sides, x, ref, what):

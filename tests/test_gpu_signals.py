@@ -37,6 +37,7 @@ import numpy as np
 import pytest
 
 import signals as sig
+from center_oracle import assert_center_contract, oracle_center
 from conftest import bin_noise, excess, mfcc_floor, relerr, row_bound
 from oracle import zaf_oracle as orc
 
@@ -567,3 +568,157 @@ def test_signals_in_one_ragged_batch_mel_mfcc(zafx_lib, consts):
                 assert np.all(np.isfinite(c)) and np.abs(c).max() <= ZERO_MFCC, tag
             assert check(f"{tag}.mel", m, ref_mel, TOL_FB, mel_floor) <= TOL_FB
             check_mfcc(f"{tag}.mfcc", c, ref_cep, half, fbd)
+
+
+# ------------------------------------------------------------------------------------------------ center / sides and the ragged MDCT / IMDCT launches
+TOL_ROUND_TRIP = 1e-5   # |imdct(mdct(x)) - x| on unit-variance noise, absolute (tests/test_gpu_mdct_ragged.py)
+CENTER_SHAPES = [(2048, sig.N_FRAMES), (2048, N_LONG), (256, 128 * 69 + 37)]   # (W, N): 4 frames; several 4-frame tiles, a carry and an edge tile; 8-frame tiles
+
+
+def center_last_kernel(zafx, w, sides):
+    return zafx.center_plan(w, sides=sides).last_kernel
+
+
+@pytest.mark.parametrize("name", sig.STEREO_NAMES)
+@pytest.mark.parametrize("wl,n", CENTER_SHAPES)
+def test_stereo_signal_through_k_center(zafx_lib, wl, n, name):
+    """The center mask -- the library's most non-linear arithmetic: squared magnitudes, one v_rcp_f32 and one v_sqrt_f32 per bin, a clamp at the
+    smallest normal number, a departure from the reference at 0 / 0 (zafx_center.hpp) -- on the eleven stereo signals of tests/signals.py, both
+    kinds (ZAFX_CENTER_SIDES and ZAFX_CENTER) of k_center, against center_oracle.oracle_center.  Bounds (center_oracle.assert_center_contract):
+    finite; silence exactly zero; center <= 1e-5 normwise (left_only, whose reference is identically zero: max|center| <= 1e-5 max|x|); sides
+    <= 1e-5 max|x|; per hop of H samples per channel |out - ref| <= 10 * 1e-5 max_hop|ref| + C eps32 max|x| with C = 16 -- the smallest
+    power of two that leaves the float32 host emulation at or below half the bound (tests/test_center_host.py: its worst hop is left_only at
+    W = 2048, 0.353 of the bound; the other half is the device's 1-ulp rcp and sqrt).
+    Measured on MI355X (66 results): worst normwise 9.88e-07 (pan_tones_2048_70956.center), worst hop 0.360 of its bound (left_only_2048_70956.center),
+    worst sides 9.88e-07 of max|x| (pan_tones_2048_70956.sides)."""
+    zafx = zafx_lib
+    w = zafx.hamming(wl)
+    x = sig.stereo_signal(name, n)
+    ref = oracle_center(x, w)
+    c, s = zafx.centersides_batch(x[None], w)
+    assert center_last_kernel(zafx, w, True) == "k_center"
+    assert_center_contract(f"k_center.{name}_{wl}_{n}.sides", c[0], s[0], x, ref, wl // 2, _report)
+    only = zafx.centersides_batch(x[None], w, sides=False)
+    assert center_last_kernel(zafx, w, False) == "k_center"
+    assert_center_contract(f"k_center.{name}_{wl}_{n}.center", only[0], None, x, ref, wl // 2, _report)
+    assert np.array_equal(only[0].view(np.uint32), c[0].view(np.uint32))
+
+
+@pytest.mark.parametrize("wl", [2048, 256])
+def test_center_below_the_smallest_normal(zafx_lib, wl):
+    """The clamp in center_ratio (zafx_center.hpp), which none of the eleven signals reaches -- it takes |X| < 1e-19 --: the `gain` signal at 1e-23,
+    whose squared magnitudes are all denormal.  v_rcp_f32 takes a denormal for zero, so without the clamp the mask is lo * inf.  With it the
+    mask is only too small (lo / FLT_MIN < 1 for lo < hi < FLT_MIN), the right channel's mask stays 1, and the result is finite and no larger
+    than the input's peak.  The normwise bound does not apply: below the smallest normal number the mask's value is not the reference's."""
+    zafx = zafx_lib
+    w = zafx.hamming(wl)
+    x = sig.stereo_signal("gain", 128 * 69 + 37) * np.float32(1e-23)
+    peak = float(np.abs(x).max())
+    assert peak > 1e-24 and (peak * wl) ** 2 < np.finfo(np.float32).tiny
+    c, s = zafx.centersides_batch(x[None], w)
+    assert center_last_kernel(zafx, w, True) == "k_center"
+    _report[f"k_center.gain_1e-23_{wl}"] = {"finite": bool(np.isfinite(c).all()), "max_over_peak": float(np.nanmax(np.abs(c))) / peak}
+    assert np.isfinite(c).all() and np.isfinite(s).all()
+    assert float(np.abs(c).max()) <= peak
+
+
+def stereo_ragged_lengths(h, f):
+    """One length per stereo signal, 1 sample frame ... 70 hops: a clip of 1, one that ends a tile exactly (2 f h), the others around hops."""
+    hopsof = {"silence": 3 * h + 7, "dc": 1, "pan_tones": 70 * h - 5, "gain": 2 * f * h, "anti": 9 * h + h // 2, "tones_chirp": 33 * h, "impulse": 5 * h - 1,
+              "noise_m90": 17 * h + 1, "clipped": 48 * h + 3, "loud_quiet": 64 * h + 300, "left_only": 25 * h + 11}
+    assert set(hopsof) == set(sig.STEREO_NAMES) and len(set(hopsof.values())) == 11 and max(hopsof.values()) <= 70 * h
+    return [hopsof[name] for name in sig.STEREO_NAMES]
+
+
+@pytest.mark.parametrize("sides", [True, False], ids=["center_sides", "center"])
+@pytest.mark.parametrize("wl", [2048, 256])
+def test_stereo_signals_in_one_ragged_batch(zafx_lib, wl, sides):
+    """k_center_ragged: the eleven stereo signals in ONE centersides_ragged call, each of its own length (1 sample frame ... 70 hops, one ending a
+    tile exactly), packed back to back -- silence beside DC, the -90 dBFS noise between the impulses and the clipped sine -- clip by clip under
+    test_stereo_signal_through_k_center's bounds.
+    Measured on MI355X (44 results): worst normwise 9.85e-07 (pan_tones_2048_71675.center), worst hop 0.361 of its bound (left_only_2048_25611.center),
+    worst sides 9.88e-07 of max|x| (pan_tones_2048_71675.sides)."""
+    zafx = zafx_lib
+    w, h = zafx.hamming(wl), wl // 2
+    lengths = stereo_ragged_lengths(h, zafx.center_tile_frames(wl))
+    clips = [sig.stereo_signal(name, n) for name, n in zip(sig.STEREO_NAMES, lengths)]
+    res = zafx.centersides_ragged(clips, w, sides=sides)
+    assert center_last_kernel(zafx, w, sides) == "k_center_ragged"
+    assert len(res) == len(clips)
+    for name, n, x, r in zip(sig.STEREO_NAMES, lengths, clips, res):
+        c, s = r if sides else (r, None)
+        assert_center_contract(f"k_center_ragged.{name}_{wl}_{n}.{'sides' if sides else 'center'}", c, s, x, oracle_center(x, w), h, _report)
+
+
+# one length per mono signal, every one a multiple of 4 (mdct_ragged packs the clips on 128-byte lines: the 16-byte-load form); `odd` adds 1, 2
+# or 3 samples (the 4-byte form).  T = ceil(n / M) + 1: one tile, tile edges (31 M, 33 M) and several tiles at M = 1024 and at M = 256.
+MDCT_RAGGED = (("silence", 4100), ("dc", 20), ("sine_bin", 1024 * 40), ("sine_half", 16 * 1024 + 4), ("two_tones", 2 * sig.W + 8), ("impulse", 3 * 1024 + 4),
+               ("chirp", 1024 * 31), ("noise_m90", sig.N_FRAMES), ("clipped_pcm", 1024 * 33 + 12))
+
+
+def mdct_ragged_clips(odd):
+    assert tuple(name for name, _ in MDCT_RAGGED) == sig.NAMES and not any(n % 4 for _, n in MDCT_RAGGED)
+    lengths = [n + (1, 2, 3)[i % 3] * odd for i, (_, n) in enumerate(MDCT_RAGGED)]
+    assert all(n % 4 for n in lengths) if odd else True
+    return lengths, [sig.signal(name, n) for (name, _), n in zip(MDCT_RAGGED, lengths)]
+
+
+@pytest.mark.parametrize("lengths_are", ["multiples_of_4", "odd"])
+@pytest.mark.parametrize("wl", [2048, 512])
+def test_signals_in_one_ragged_mdct_batch(zafx_lib, wl, lengths_are):
+    """k_mdct_ft32_ragged (both load forms) on the nine mono signals in one mdct_ragged call at KBD 2048 and KBD 512, every clip against orc.mdct
+    with the per-row bound and C_FLOOR, exactly as the equal-length run_all; a clip of zeros comes out exactly zero.  Both forms report the one
+    kernel name: which one runs follows from the launcher's rule (zafx_execute_ragged: 16-byte loads when d_in is on 16 bytes and every offset
+    and length is a multiple of 4) and from how mdct_ragged packs -- a fresh allocation, every clip on a 32-element slot (asserted on
+    pack_ragged below).  This is a test of VALUES: the packing pads with zeros, so a read past a clip's end is invisible here; that is
+    tests/test_gpu_arena.py::test_mdct_ragged's, where NaNs lie between the clips.
+    Measured on MI355X (36 results): worst normwise 2.05e-07 (multiples_of_4.chirp_31744_2048.mdct), worst row 0.238 of its bound
+    (multiples_of_4.clipped_pcm_33804_2048.mdct)."""
+    zafx = zafx_lib
+    kbd = zafx.kaiser_bessel_derived(wl)
+    lengths, clips = mdct_ragged_clips(lengths_are == "odd")
+    _, in_off, lens = zafx.pack_ragged(clips)
+    assert not (in_off % 4).any() and bool((lens % 4).any()) == (lengths_are == "odd")   # (the launcher's condition for the 16-byte form, or not)
+    got = zafx.mdct_ragged(clips, kbd)
+    assert zafx.mdct_plan(kbd, row_align=32).last_kernel == "k_mdct_ft32_ragged"
+    assert len(got) == len(clips)
+    for (name, _), n, x, g in zip(MDCT_RAGGED, lengths, clips, got):
+        ref = orc.mdct(x.astype(np.float64), kbd)
+        if not np.any(x):
+            assert g.shape == ref.shape and not np.any(g), name
+        assert check(f"k_mdct_ft32_ragged.{lengths_are}.{name}_{n}_{wl}.mdct", g, ref, TOL_FFT) <= TOL_FFT
+
+
+@pytest.mark.parametrize("wl", [2048, 512])
+def test_signals_in_one_ragged_imdct_batch(zafx_lib, wl):
+    """k_imdct_ragged: the oracle's MDCT blocks of the nine signals in one imdct_ragged call, against orc.imdct per hop of W / 2 samples with the
+    per-row bound (run_all's imdct check); then the round trip mdct_ragged -> imdct_ragged of each signal, the views fed as they lie, within
+    TOL_ROUND_TRIP absolute -- for noise_m90 scaled by that signal's level, 10^(-90/20): the bound is DESIGN 1's for unit-variance noise, the
+    other signals are at full scale.
+    Measured on MI355X (18 results): worst normwise 5.36e-07 (clipped_pcm_33807_512.imdct), worst hop 0.234 of its bound (impulse_3079_2048.imdct).  Round
+    trip: worst 2.91e-11 against 3.16e-10 (noise_m90_3074_2048.round_trip)."""
+    zafx = zafx_lib
+    kbd, m = zafx.kaiser_bessel_derived(wl), wl // 2
+    lengths, clips = mdct_ragged_clips(True)
+    blocks = [orc.mdct(x.astype(np.float64), kbd) for x in clips]
+    got = zafx.imdct_ragged(blocks, kbd)
+    inverse = zafx.mdct_plan(kbd, inverse=True, row_align=32)
+    assert inverse.last_kernel == "k_imdct_ragged"
+    for (name, _), n, b, y in zip(MDCT_RAGGED, lengths, blocks, got):
+        ref = orc.imdct(b, kbd)
+        assert len(y) == len(ref)
+        if not np.any(b):
+            assert not np.any(y), name
+        assert check(f"k_imdct_ragged.{name}_{n}_{wl}.imdct", hops(y, m), hops(ref, m), TOL_FFT) <= TOL_FFT
+    spectra = zafx.mdct_ragged(clips, kbd)
+    assert zafx.mdct_plan(kbd, row_align=32).last_kernel == "k_mdct_ft32_ragged"
+    keep = [min(n, max(m * (s.shape[1] - 1) - 1, 0)) for n, s in zip(lengths, spectra)]
+    assert keep == lengths   # (no length is a whole number of hops: every sample comes back)
+    back = zafx.imdct_ragged(spectra, kbd, lengths=keep)
+    assert inverse.last_kernel == "k_imdct_ragged"
+    for (name, _), n, x, y in zip(MDCT_RAGGED, lengths, clips, back):
+        assert y.shape == x.shape
+        err = float(np.max(np.abs(y.astype(np.float64) - x)))
+        bound = TOL_ROUND_TRIP * (10.0 ** (-90.0 / 20.0) if name == "noise_m90" else 1.0)   # (the one signal far below unit level: held to its own)
+        _report[f"k_imdct_ragged.{name}_{n}_{wl}.round_trip"] = {"max_abs": err, "bound": bound}
+        assert err <= bound, (name, n, err, bound)

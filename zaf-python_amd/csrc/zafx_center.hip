@@ -100,6 +100,9 @@ __global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* _
             {
                 // samples in front of the clip and at or behind its end read as zero: the descriptor's range check does both, and a
                 // frame that is not needed reads nothing but zeros (its threads still meet the others at every frame_sync)
+                // (8-byte loads here and 8-byte stores below at the clip's base plus a multiple of 8 bytes: a base at 4 mod 8 -- include/zafx.h
+                // allows any 4-byte boundary -- makes them misaligned for float2, which global and buffer accesses take on this hardware in its
+                // unaligned access mode; tests/test_gpu_arena.py runs such bases.  Not something to "fix" by rounding the base.)
                 const int s0 = (j - 1) * H + lane;
 #pragma unroll
                 for (int i = 0; i < E; ++i) v[i] = buf_load_f32x2(rs, live ? (s0 + P * i) * 8 : -8);

@@ -148,7 +148,7 @@ struct MdctPCfg {
 
 // TFOUT = frame-major output (ZAFX_LAYOUT_TF): a frame's M coefficients are contiguous, so the wave that transformed a
 // frame also stores it (512-B coalesced runs) and the workgroup never meets after the table staging.
-// CARRY (reference layout, even T): rows that are not whole lines or half lines (T % 16 != 0) are completed from a register carry
+// CARRY (reference layout): rows that are not whole lines or half lines (T % 16 != 0) are completed from a register carry
 // of the previous tile, as in k_stft_ft16c: the
 // workgroup walks the tiles of a clip segment in order, thread (frame pair tp, rows fq + 64 i) keeps its own 16 pairs of the
 // previous tile (32 VGPRs, instead of the resident window quadruples), and for a row whose run starts `a` floats into a line the
@@ -433,7 +433,9 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             const int dslot = odd ? -2 * DPH : 2 * DPH;
             // phase of a row's run in its line, in floats: (array + (clip M + f) TP) mod 32 -- even, since TP and the array's offset are
             const int b0 = (int)((reinterpret_cast<uintptr_t>(out) >> 2) & 31), c0 = (int)(((long long)clip * M) & 31), tpm = TP & 31;
-            const bool pairs = TP % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
+            // (T even as well: at a padded pitch TP > T with T odd, the pair of the clip's last frame would put its second float into the row's
+            // first padding element -- such rows take the float-by-float form below, which tests ta + 1 < T)
+            const bool pairs = TP % 2 == 0 && T % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
             auto sweep = [&](auto stream) {
                 constexpr bool ST = decltype(stream)::value;
 #pragma unroll
@@ -1042,7 +1044,8 @@ __global__ __launch_bounds__(MdctBandCfg::NT) void k_mdct_ft32bc(
             const bool cur_ok = ta < T, last = j + 1 >= j1;
             // phase of a row's run in its line, in floats: (array + (clip M + f) TP) mod 32
             const int b0 = (int)((reinterpret_cast<uintptr_t>(out) >> 2) & 31), c0 = (int)(((long long)clip * M) & 31), tpm = TP & 31;
-            const bool pairs = TP % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
+            // (T even as well, as in k_mdct_ft32's carry form: at a padded pitch with T odd the last frame's pair would reach the row's first padding element)
+            const bool pairs = TP % 2 == 0 && T % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
             // (the thread's rows are 128 apart: the phase of their runs, (b0 + (c0 + f) tpm) mod 32, is the same for all sixteen)
             const int a = (b0 + (c0 + f0) * tpm) & 31;
             const long long dstep = (long long)(e ? -128 : 128) * TP;
