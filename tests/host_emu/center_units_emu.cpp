@@ -1,4 +1,4 @@
-// The cutter of ragged stereo batches (center_cut_units, zafx_center_units.hpp) on the host: prints the units it makes of one batch.
+// The cutter of ragged stereo batches (center_cut_units, zafx_units.hpp) on the host: prints the units it makes of one batch.
 //     g++ -O2 -std=c++17 -I zaf-python_amd/csrc tests/host_emu/center_units_emu.cpp -o center_units_emu
 //     ./center_units_emu W F slots len0 len1 ...        (lengths may also come on standard input, one per token, after a lone "-")
 // Output: "S <segment length in blocks>", then one line "clip b0 b1 n_samples" per unit, in the order the kernel walks them.  The clip's index
@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "zafx_center_units.hpp"
+#include "zafx_units.hpp"
 
 int main(int argc, char** argv) {
     if (argc < 4) return 2;

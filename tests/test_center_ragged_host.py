@@ -1,6 +1,6 @@
 """Ragged stereo batches of the center / sides extraction on the host side (no GPU): the packing of (N_i, 2) clips of different lengths, the
 validation that runs before any device call, the binding of the new entry point, and the cutter that turns a batch into the units k_center's
-RAGGED form walks (center_cut_units, zafx_center_units.hpp, compiled by g++)."""
+RAGGED form walks (center_cut_units, zafx_units.hpp, compiled by g++)."""
 import os
 import subprocess
 

@@ -1,6 +1,6 @@
 """Ragged batches of the IMDCT on the host side (no GPU): the export and the binding of the new entry point, the validation that runs before
 any device call, the empty batch, and the cutter and the deal that turn a batch of coefficient blocks into the table k_imdct's RAGGED form walks
-(imdct_cut_units / imdct_deal_table, zafx_imdct_units.hpp, compiled by g++)."""
+(imdct_cut_units / deal_table, zafx_units.hpp, compiled by g++)."""
 import os
 import subprocess
 

@@ -9,14 +9,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
 #include <utility>
 
 #include "zafx_center.hpp"
-#include "zafx_center_units.hpp"
-#include "zafx_imdct_units.hpp"
+#include "zafx_units.hpp"
 #include "zafx_internal.hpp"
 
 #ifndef ZAFX_STFT_FAT8_TABLES
@@ -61,6 +61,13 @@ static int fail_msg(const std::string& msg, int code = -1) {
         hipError_t e__ = (call);                          \
         if (e__ != hipSuccess) return fail(#call, e__);   \
     } while (0)
+
+// What an entry point returns for its launch: a launcher that refused its arguments has said why (set_error) and keeps its words
+static int launch_rc(const char* where, hipError_t e) {
+    if (e == hipSuccess) return 0;
+    if (g_err.empty() || e != hipErrorInvalidValue) return fail(where, e);
+    return (int)e;
+}
 
 static int ilog2_exact(int v) {
     if (v <= 0 || (v & (v - 1))) return -1;
@@ -1508,11 +1515,7 @@ int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, 
         default:
             return fail_msg("unknown plan kind");
     }
-    if (e != hipSuccess) {
-        if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute", e);
-        return (int)e;
-    }
-    return 0;
+    return launch_rc("zafx_execute", e);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1597,16 +1600,49 @@ static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& r
     });
 }
 
-int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
+// The table of zafx_execute_center_ragged / zafx_execute_imdct_ragged: the records as they are (none: nothing to upload)
+extern "C++" {
+template <class T>
+static int upload_records(zafx_plan* pl, const std::vector<T>& recs) {
+    const size_t bytes = recs.size() * sizeof(T);
+    return bytes ? upload_plan_table(pl, bytes, [&](unsigned char* h) { std::memcpy(h, recs.data(), bytes); }) : 0;
+}
+}
+
+// The switches of the ragged launches in the environment (measurements only, include/zafx.h), read on every call: tools/ragged_rates.py
+// flips them in one process.  A route is off when its switch starts with 0; the units per workgroup slot are 1 ... 64.
+static bool env_on(const char* name) {
+    const char* v = std::getenv(name);
+    return !(v && v[0] == '0');
+}
+static int env_units_per_slot(const char* name, int preset) {
+    const char* v = std::getenv(name);
+    return v ? std::min(64, std::max(1, std::atoi(v))) : preset;
+}
+
+// The arguments of a ragged entry point `fn`, checked in this order: the plan, the number of clips, the plan's kind (wrong_kind: what is wrong
+// with it, or null), then -- unless the batch is *empty -- the per-clip arrays, the device pointers and the sign of every entry (`what` they count).
+static int ragged_args(const char* fn, const zafx_plan* pl, int64_t n_clips, const char* wrong_kind, const void* d_in, const void* d_out,
+                       std::initializer_list<const int64_t*> per_clip, const char* what, bool* empty) {
     if (!pl) return fail_msg("null plan");
-    if (n_clips < 0) return fail_msg("negative size");
-    if (is_center_kind(pl->kind)) return fail_msg("zafx_execute_ragged: center / sides plans take clips of one length (ragged stereo batches are not implemented)");
-    if (!ragged_kind(pl->kind)) return fail_msg("zafx_execute_ragged: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
-    if (n_clips == 0) return 0;
-    if (!in_offsets || !lengths) return fail_msg("null argument");
+    if (n_clips < 0) return fail_msg(std::string(fn) + ": negative number of clips");
+    if (wrong_kind) return fail_msg(std::string(fn) + ": " + wrong_kind);
+    if ((*empty = n_clips == 0)) return 0;
+    for (const int64_t* a : per_clip)
+        if (!a) return fail_msg("null argument");
     if (!d_in || !d_out) return fail_msg("null device pointer");
     for (int64_t i = 0; i < n_clips; ++i)
-        if (lengths[i] < 0 || in_offsets[i] < 0) return fail_msg("zafx_execute_ragged: negative length or offset of clip " + std::to_string(i));
+        for (const int64_t* a : per_clip)
+            if (a[i] < 0) return fail_msg(std::string(fn) + ": negative " + what + " or offset of clip " + std::to_string(i));
+    return 0;
+}
+
+int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
+    const char* wrong_kind = !pl || ragged_kind(pl->kind) ? nullptr : !is_center_kind(pl->kind) ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)"
+                             : "center / sides plans take clips of one length (ragged stereo batches are not implemented)";
+    bool empty = false;
+    if (int rc = ragged_args("zafx_execute_ragged", pl, n_clips, wrong_kind, d_in, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
     // every clip's place in the output, frames and pitch; the 16-frame tiles of the batch
     std::vector<zafx::RgClip> recs((size_t)n_clips);
     const int64_t eb = out_elem_bytes(pl);
@@ -1634,21 +1670,16 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
     // per-clip path (measurements only, include/zafx.h: tools/ragged_rates.py times both in one process).
     if (pl->kind == ZAFX_MDCT && pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->bs_log2m == 0 && lines &&
         zafx::mdct_ragged_native(*pl)) {
-        const char* sw = std::getenv("ZAFX_RAGGED_MDCT_NATIVE");
         const long long tiles32 = zafx::rg_assign_tiles(recs.data(), recs.size(), zafx::kMdctRaggedTile);
         bool aligned = reinterpret_cast<uintptr_t>(d_in) % 16 == 0, short_enough = reinterpret_cast<uintptr_t>(d_in) % 4 == 0;
         for (const zafx::RgClip& r : recs) {
             aligned = aligned && r.in_off % 4 == 0 && r.n_samples % 4 == 0;
             short_enough = short_enough && r.n_samples < (1LL << 28);
         }
-        if (tiles32 < (1LL << 31) && short_enough && !(sw && sw[0] == '0')) {
+        if (tiles32 < (1LL << 31) && short_enough && env_on("ZAFX_RAGGED_MDCT_NATIVE")) {
             if (int rc = upload_ragged_table(pl, recs, tiles32, zafx::kMdctRaggedTile)) return rc;
-            const hipError_t e = zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged), n_clips, tiles32, aligned);
-            if (e != hipSuccess) {
-                if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_ragged", e);
-                return (int)e;
-            }
-            return 0;
+            return launch_rc("zafx_execute_ragged", zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged),
+                                                                             n_clips, tiles32, aligned));
         }
     }
     // native: k_stft_ft16 / k_mel2 in their RAGGED forms (float32, reference layout, every clip's rows whole 128-byte lines)
@@ -1658,13 +1689,8 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
     if (native) {
         if (int rc = upload_ragged_table(pl, recs, tiles)) return rc;
         const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged);
-        const hipError_t e = pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
-                                                   : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even);
-        if (e != hipSuccess) {
-            if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_ragged", e);
-            return (int)e;
-        }
-        return 0;
+        return launch_rc("zafx_execute_ragged", pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
+                                                                      : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even));
     }
     // everything else: one zafx_execute per clip on the plan's stream, into the same blocks
     const int64_t ib = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
@@ -1681,38 +1707,25 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
 // Ragged stereo batches of the center / sides kinds: the host cuts the clips into units (center_cut_units), k_center's RAGGED form walks them.
 int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, const int64_t* out_offsets,
                                int64_t n_clips) {
-    if (!pl) return fail_msg("null plan");
-    if (n_clips < 0) return fail_msg("zafx_execute_center_ragged: negative number of clips");
-    if (!is_center_kind(pl->kind)) return fail_msg("zafx_execute_center_ragged: ZAFX_CENTER and ZAFX_CENTER_SIDES plans only (zafx_execute_ragged takes the forward kinds)");
-    if (n_clips == 0) return 0;
-    if (!in_offsets || !lengths || !out_offsets) return fail_msg("null argument");
-    if (!d_in || !d_out) return fail_msg("null device pointer");
-    for (int64_t i = 0; i < n_clips; ++i) {
-        if (lengths[i] < 0 || in_offsets[i] < 0 || out_offsets[i] < 0)
-            return fail_msg("zafx_execute_center_ragged: negative length or offset of clip " + std::to_string(i));
+    const char* wrong_kind = !pl || is_center_kind(pl->kind) ? nullptr : "ZAFX_CENTER and ZAFX_CENTER_SIDES plans only (zafx_execute_ragged takes the forward kinds)";
+    bool empty = false;
+    if (int rc = ragged_args("zafx_execute_center_ragged", pl, n_clips, wrong_kind, d_in, d_out, {lengths, in_offsets, out_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    for (int64_t i = 0; i < n_clips; ++i)
         if (lengths[i] >= (1LL << 28))
             return fail_msg("zafx_execute_center_ragged: clip " + std::to_string(i) + " has 2^28 sample frames or more (not supported)");
-    }
     if (!pl->d_window) return fail_msg("window constant not set");
     if (pl->cola_gain == 0.f) return fail_msg("center / sides: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
     int tile_frames = 0;
     long long slots = 0;
     if (!zafx::center_launch_shape(*pl, &tile_frames, &slots)) return fail_msg("center / sides: window_length must be 256, 512, 1024 or 2048");
     // ZAFX_CENTER_UNITS_PER_SLOT in the environment: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
-    int per_slot = zafx::kCenterUnitsPerSlot;
-    if (const char* v = std::getenv("ZAFX_CENTER_UNITS_PER_SLOT")) per_slot = std::min(64, std::max(1, std::atoi(v)));
+    const int per_slot = env_units_per_slot("ZAFX_CENTER_UNITS_PER_SLOT", zafx::kCenterUnitsPerSlot);
     const std::vector<zafx::CenterUnit> units = zafx::center_cut_units(lengths, in_offsets, out_offsets, n_clips, pl->W, tile_frames, slots, per_slot);
     ZAFX_HIP(hipSetDevice(pl->device));
-    if (!units.empty()) {
-        const size_t bytes = units.size() * sizeof(zafx::CenterUnit);
-        if (int rc = upload_plan_table(pl, bytes, [&](unsigned char* h) { std::memcpy(h, units.data(), bytes); })) return rc;
-    }
-    const hipError_t e = zafx::launch_center_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::CenterUnit*>(pl->d_ragged), (long long)units.size());
-    if (e != hipSuccess) {
-        if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_center_ragged", e);
-        return (int)e;
-    }
-    return 0;
+    if (int rc = upload_records(pl, units)) return rc;
+    return launch_rc("zafx_execute_center_ragged", zafx::launch_center_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::CenterUnit*>(pl->d_ragged),
+                                                                              (long long)units.size()));
 }
 
 // Ragged batches of the IMDCT: coefficient blocks of different frame counts.  The host cuts the blocks into units (imdct_cut_units), k_imdct's
@@ -1723,19 +1736,13 @@ int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
 // include/zafx.h); ZAFX_IMDCT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
 int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t* in_offsets, const int64_t* frames, void* d_out, const int64_t* out_offsets,
                               int64_t n_clips) {
-    if (!pl) return fail_msg("null plan");
-    if (n_clips < 0) return fail_msg("zafx_execute_imdct_ragged: negative number of clips");
-    if (pl->kind != ZAFX_IMDCT) return fail_msg("zafx_execute_imdct_ragged: inverse MDCT plans (ZAFX_IMDCT) only (zafx_execute_ragged takes the forward kinds)");
-    if (n_clips == 0) return 0;
-    if (!in_offsets || !frames || !out_offsets) return fail_msg("null argument");
-    if (!d_coefs || !d_out) return fail_msg("null device pointer");
-    for (int64_t i = 0; i < n_clips; ++i)
-        if (frames[i] < 0 || in_offsets[i] < 0 || out_offsets[i] < 0)
-            return fail_msg("zafx_execute_imdct_ragged: negative frame count or offset of clip " + std::to_string(i));
+    const char* wrong_kind = !pl || pl->kind == ZAFX_IMDCT ? nullptr : "inverse MDCT plans (ZAFX_IMDCT) only (zafx_execute_ragged takes the forward kinds)";
+    bool empty = false;
+    if (int rc = ragged_args("zafx_execute_imdct_ragged", pl, n_clips, wrong_kind, d_coefs, d_out, {frames, in_offsets, out_offsets}, "frame count", &empty)) return rc;
+    if (empty) return 0;
     if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
     const int M = pl->W / 2;
-    bool native = zafx::imdct_ragged_native(*pl) && reinterpret_cast<uintptr_t>(d_coefs) % 4 == 0;
-    if (const char* sw = std::getenv("ZAFX_RAGGED_IMDCT_NATIVE")) native = native && sw[0] != '0';
+    bool native = zafx::imdct_ragged_native(*pl) && reinterpret_cast<uintptr_t>(d_coefs) % 4 == 0 && env_on("ZAFX_RAGGED_IMDCT_NATIVE");
     for (int64_t i = 0; native && i < n_clips; ++i) {
         const int64_t pitch = row_pitch(*pl, frames[i]);
         native = pitch % 4 == 0 && (long long)M * pitch * 4 < (1LL << 32);
@@ -1744,8 +1751,7 @@ int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t*
     int tile_frames = 0;
     long long slots = 0;
     if (native && zafx::imdct_launch_shape(*pl, &tile_frames, &slots)) {
-        int per_slot = zafx::kImdctUnitsPerSlot;
-        if (const char* v = std::getenv("ZAFX_IMDCT_UNITS_PER_SLOT")) per_slot = std::min(64, std::max(1, std::atoi(v)));
+        const int per_slot = env_units_per_slot("ZAFX_IMDCT_UNITS_PER_SLOT", zafx::kImdctUnitsPerSlot);
         std::vector<zafx::ImdctUnit> units = zafx::imdct_cut_units(frames, n_clips, tile_frames, slots, per_slot);
         if (units.size() + (size_t)slots < (size_t)1 << 31) {   // (the table in launch order is at most one round longer)
             for (zafx::ImdctUnit& u : units) {   // (the cutter leaves the clip's index in in_off)
@@ -1753,17 +1759,10 @@ int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t*
                 zafx::imdct_fill_clip(u, in_offsets[i], out_offsets[i], row_pitch(*pl, frames[i]), M);
             }
             // the launch's workgroups (launch_imdct_ragged: min(records, slots) -- the table is a whole number of rounds or shorter than one)
-            const std::vector<zafx::ImdctUnit> table = zafx::imdct_deal_table(units, std::min<long long>((long long)units.size(), slots));
-            if (!table.empty()) {
-                const size_t bytes = table.size() * sizeof(zafx::ImdctUnit);
-                if (int rc = upload_plan_table(pl, bytes, [&](unsigned char* h) { std::memcpy(h, table.data(), bytes); })) return rc;
-            }
-            const hipError_t e = zafx::launch_imdct_ragged(*pl, (const float*)d_coefs, (float*)d_out, static_cast<const zafx::ImdctUnit*>(pl->d_ragged), (long long)table.size());
-            if (e != hipSuccess) {
-                if (g_err.empty() || e != hipErrorInvalidValue) return fail("zafx_execute_imdct_ragged", e);
-                return (int)e;
-            }
-            return 0;
+            const std::vector<zafx::ImdctUnit> table = zafx::deal_table(units, std::min<long long>((long long)units.size(), slots));
+            if (int rc = upload_records(pl, table)) return rc;
+            return launch_rc("zafx_execute_imdct_ragged", zafx::launch_imdct_ragged(*pl, (const float*)d_coefs, (float*)d_out, static_cast<const zafx::ImdctUnit*>(pl->d_ragged),
+                                                                                  (long long)table.size()));
         }
     }
     // everything else: one zafx_execute per clip on the plan's stream (a block of at most one frame has no samples)

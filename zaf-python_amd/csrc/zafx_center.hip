@@ -19,12 +19,12 @@
 //   * SIDES: the lanes that write block b hold its input samples already (the first half of frame b + 1, before the window).
 //   * RAGGED (zafx_execute_center_ragged): clips of different lengths.  The walk is the same; a unit's clip -- the base and the length
 //     its descriptor is built from, the base of its output -- and its blocks come from the unit's record of a device table
-//     (CenterUnit, zafx_center_units.hpp: the host cuts the batch) instead of from clip * n_samples and seg * seg_blocks.  A descriptor
+//     (CenterUnit, zafx_units.hpp: the host cuts the batch) instead of from clip * n_samples and seg * seg_blocks.  A descriptor
 //     per clip pads every clip with zeros even where the next clip's samples lie right behind it.
 #include <algorithm>
 
 #include "zafx_center.hpp"
-#include "zafx_center_units.hpp"
+#include "zafx_units.hpp"
 #include "zafx_internal.hpp"
 
 namespace zafx {

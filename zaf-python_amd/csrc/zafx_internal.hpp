@@ -333,7 +333,7 @@ bool center_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots
 hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out, const CenterUnit* d_units, long long n_units);
 // zafx_execute_imdct_ragged: k_imdct's RAGGED form (float32, reference layout, W = 512 / 1024 / 2048) -- the plans that have it, the tile
 // frames and the workgroup slots of its launch (what imdct_cut_units takes), and the launch on `n_units` records of the device table
-// (zafx_imdct_units.hpp; every block's pitch a multiple of 4 floats, every block below 2^32 bytes, coefs on 4 bytes, units below 2^31)
+// (zafx_units.hpp; every block's pitch a multiple of 4 floats, every block below 2^32 bytes, coefs on 4 bytes, units below 2^31)
 struct ImdctUnit;
 constexpr int kImdctRaggedTile = 32;
 bool imdct_ragged_native(const zafx_plan& pl);

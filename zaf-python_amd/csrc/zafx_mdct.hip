@@ -18,7 +18,7 @@
 #include <type_traits>
 
 #include "zafx_fft.hpp"
-#include "zafx_imdct_units.hpp"
+#include "zafx_units.hpp"
 #include "zafx_internal.hpp"
 
 
@@ -1101,13 +1101,13 @@ __global__ __launch_bounds__(MdctBandCfg::NT) void k_mdct_ft32bc(
 // overlap-add reads a thread's two window pairs once per tile -- which makes room for 16-frame tiles (64-byte gather runs) instead of 8.
 // RAGGED (zafx_execute_imdct_ragged): blocks of different frame counts.  The walk is the same; `out_len` carries the table of unit records
 // (ImdctLenArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (ImdctUnit,
-// zafx_imdct_units.hpp: the host cuts the batch): the base of the clip's block -- its buffer descriptor is built from it --, its frames, pitch
+// zafx_units.hpp: the host cuts the batch): the base of the clip's block -- its buffer descriptor is built from it --, its frames, pitch
 // and tiles, the base and the length of its output and the unit's tiles come from the record (uniform: scalar loads into SGPRs) instead of
 // from unit / segs, unit % segs and the kernel's arguments (rg_pick).  T, TP, tiles, segs and seg_tiles are not used.  The gather runs one
 // tile ahead and that tile may belong to the workgroup's next unit, so two records are live: rc, the unit being transformed and stored, and
 // rn, the workgroup's next one (unit + gridDim.x), both read at the head of the unit -- rc again, not handed over from rn: of rn only the
 // four fields the gather needs stay in SGPRs through the unit, with all of it the W = 1024 and 2048 forms spilled SGPRs.  The table comes in
-// launch order (imdct_deal_table: rounds of gridDim.x units dealt forwards and backwards in turn; a record without tiles where a short last
+// launch order (deal_table: rounds of gridDim.x units dealt forwards and backwards in turn; a record without tiles where a short last
 // round leaves a workgroup idle), so the walk is the equal-length one.  Only the 16-byte gather with its prefetch exists in this form (the
 // launcher vouches for the pitches).
 // A sample pair as one 8-byte store at an address that is only 4-byte aligned (global memory takes multi-dword accesses on any dword): what

@@ -1,0 +1,153 @@
+// zafx_units.hpp -- a ragged batch cut into the units a RAGGED kernel form walks: k_center's (zafx_center.hip, zafx_execute_center_ragged) and
+// k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged).
+//
+// A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, tiles of `tile_frames` frames for k_imdct.  One unit = pieces
+// [a, b) of one clip.  A unit that does not start its clip pays a fixed entry cost -- k_center a halo frame, k_imdct the tile in front of it
+// in carry-only mode -- and for that gives the same bits wherever it starts.
+//
+// The rule (cut_segments): one segment length S in pieces for the whole batch,
+//     S = max(floor, ceil(total pieces / (per_slot x workgroup slots)));
+// a clip of at most S pieces is one unit, a longer one of n pieces is cut into k = ceil(n / S) near-equal segments: with q = n / k and
+// r = n % k, r segments of q + 1 pieces, then k - r of q.  A clip without pieces gives no unit.  The units are ordered by descending size
+// (stable: ties keep clip order, then a) and dealt in rounds of `grid` neighbours in that order, forwards and backwards in turn, so the
+// workgroups' sums stay within about one unit of each other.  A fixed deal: nothing is claimed at run time.
+//
+// The floor.  Every segment of a cut clip is to keep at least m pieces -- what amortises the entry cost -- and none may exceed S.  The second
+// holds for any S: k >= n / S, so n / k <= S and ceil(n / k) <= S.  The first, q >= m, is n >= m k; with k <= (n + S - 1) / S it follows from
+// m (S - 1) <= n (S - m), and a cut clip has n >= S + 1, so from m (S - 1) <= (S + 1) (S - m), which is S >= 2 m - 1.  S = 2 m - 2 is too
+// small: a clip of 2 m - 1 pieces would be cut into m and m - 1.  So floor = 2 m - 1:
+//     k_center: m = 2 F - 1 blocks, the two tiles of F frames that are the floor of the equal-length launch: floor = 2 (2 F - 1) - 1 = 4 F - 3;
+//     k_imdct:  m = 2 tiles:                                                                               floor = 2 x 2 - 1 = 3.
+//
+// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,imdct}_units_emu.cpp and the host layer's sanitizer build.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace zafx {
+
+struct Segment { int64_t clip; long long a, b; };   // pieces [a, b) of a clip
+
+// The batch's segment length in pieces; counts[i]: the pieces of clip i.
+inline long long segment_length(const long long* counts, int64_t n, long long floor, long long slots, int per_slot) {
+    long long total = 0;
+    for (int64_t i = 0; i < n; ++i) total += counts[i];
+    const long long want = std::max<long long>(1, slots) * std::max(1, per_slot);
+    return std::max(floor, (total + want - 1) / want);
+}
+
+// The batch's segments, ordered for the deal.
+inline std::vector<Segment> cut_segments(const long long* counts, int64_t n, long long floor, long long slots, int per_slot) {
+    const long long S = segment_length(counts, n, floor, slots, per_slot);
+    std::vector<Segment> segs;
+    for (int64_t i = 0; i < n; ++i) {
+        if (counts[i] <= 0) continue;
+        const long long k = (counts[i] + S - 1) / S, q = counts[i] / k, r = counts[i] % k;
+        long long a = 0;
+        for (long long j = 0; j < k; ++j) {
+            const long long len = q + (j < r ? 1 : 0);
+            segs.push_back({i, a, a + len});
+            a += len;
+        }
+    }
+    std::stable_sort(segs.begin(), segs.end(), [](const Segment& x, const Segment& y) { return x.b - x.a > y.b - y.a; });
+    return segs;
+}
+
+// The deal: the table in launch order for `grid` workgroups -- workgroup wg walks positions wg, wg + grid, ... -- from the ordered units: rounds
+// of `grid` neighbours, even rounds forwards, odd rounds backwards: the workgroup that took the longest unit of one round takes the shortest
+// of the next.  Only the last round can be short; where a backward one leaves the first workgroups without a unit their positions hold a
+// value-initialised record (no pieces: the kernel passes over it), a forward one simply ends the table.
+template <class Unit>
+std::vector<Unit> deal_table(const std::vector<Unit>& units, long long grid) {
+    const long long n = (long long)units.size();
+    std::vector<Unit> table;
+    if (n <= 0 || grid <= 0) return table;
+    const long long rounds = (n + grid - 1) / grid;
+    table.reserve((size_t)(rounds * grid));
+    for (long long r = 0; r < rounds; ++r)
+        for (long long wg = 0; wg < grid; ++wg) {
+            const long long u = (r & 1) ? (r + 1) * grid - 1 - wg : r * grid + wg;
+            if (u < n) table.push_back(units[(size_t)u]);
+            else if (r & 1) table.push_back(Unit{});
+        }
+    return table;
+}
+
+template <class Count>
+std::vector<long long> piece_counts(const int64_t* sizes, int64_t n, Count count) {
+    std::vector<long long> counts((size_t)std::max<int64_t>(n, 0));
+    for (size_t i = 0; i < counts.size(); ++i) counts[i] = count((long long)sizes[i]);
+    return counts;
+}
+
+// ---- k_center: blocks.  One record of the device table.  Offsets and lengths in sample frames (one sample frame = 8 bytes: L, R).  The kernel deals the rounds itself.
+struct CenterUnit {
+    long long in_off, n_samples, out_off;   // the unit's CLIP: its first sample frame in the input, its length, its first sample frame in the output
+    int b0, b1;                             // the unit: blocks [b0, b1) of that clip
+};
+static_assert(sizeof(CenterUnit) == 32 && alignof(CenterUnit) == 8, "CenterUnit: the layout the host writes");
+
+constexpr int kCenterUnitsPerSlot = 12;   // units per workgroup slot the segment length aims at (where the batch has the blocks); measured: DESIGN.md 4.7
+
+inline long long center_blocks(long long n_samples, int W) { return (n_samples + W / 2 - 1) / (W / 2); }
+
+inline long long center_segment_blocks(const int64_t* lengths, int64_t n_clips, int W, int F, long long slots, int per_slot = kCenterUnitsPerSlot) {
+    const auto counts = piece_counts(lengths, n_clips, [W](long long n) { return center_blocks(n, W); });
+    return segment_length(counts.data(), n_clips, 4LL * F - 3, slots, per_slot);
+}
+
+// in_offsets / out_offsets: null = 0 for every clip.
+inline std::vector<CenterUnit> center_cut_units(const int64_t* lengths, const int64_t* in_offsets, const int64_t* out_offsets, int64_t n_clips, int W,
+                                                int F, long long slots, int per_slot = kCenterUnitsPerSlot) {
+    const auto counts = piece_counts(lengths, n_clips, [W](long long n) { return center_blocks(n, W); });
+    std::vector<CenterUnit> units;
+    for (const Segment& s : cut_segments(counts.data(), n_clips, 4LL * F - 3, slots, per_slot))
+        units.push_back({in_offsets ? (long long)in_offsets[s.clip] : 0LL, (long long)lengths[s.clip], out_offsets ? (long long)out_offsets[s.clip] : 0LL,
+                         (int)s.a, (int)s.b});
+    return units;
+}
+
+// ---- k_imdct: tiles.  One record of the device table.  Offsets and lengths in floats.  The host deals the rounds (deal_table).
+struct ImdctUnit {
+    long long in_off, out_off, out_len;   // the unit's CLIP: its block in the coefficient array, its first sample in the output, its samples M (T - 1) - 1
+    int T, TP, tiles;                     // ... its frames, the pitch of its M rows, its tiles
+    int tile_a, tile_b, pad_;             // the unit: tiles [tile_a, tile_b) of that clip
+};
+static_assert(sizeof(ImdctUnit) == 48 && alignof(ImdctUnit) == 8, "ImdctUnit: the layout the host writes");
+
+constexpr int kImdctUnitsPerSlot = 4;    // units per workgroup slot the segment length aims at (where the batch has the tiles); measured: DESIGN.md 4.6
+constexpr int kImdctMinSegment = 3;      // floor of S
+
+// A clip whose output is empty (T <= 1: the reference returns y[M : -M-1], max(M (T - 1) - 1, 0) samples) has no tiles.
+inline long long imdct_tiles(long long frames, int tile_frames) { return frames <= 1 ? 0 : (frames + tile_frames - 1) / tile_frames; }
+inline long long imdct_out_len(long long frames, int M) { return std::max<long long>((long long)M * (frames - 1) - 1, 0); }
+
+inline long long imdct_segment_tiles(const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot = kImdctUnitsPerSlot) {
+    const auto counts = piece_counts(frames, n_clips, [tile_frames](long long t) { return imdct_tiles(t, tile_frames); });
+    return segment_length(counts.data(), n_clips, kImdctMinSegment, slots, per_slot);
+}
+
+// The records carry the clip's index in `in_off` and nothing else of the clip: the caller, who knows the plan's pitches, fills the rest in.
+inline std::vector<ImdctUnit> imdct_cut_units(const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot = kImdctUnitsPerSlot) {
+    const auto counts = piece_counts(frames, n_clips, [tile_frames](long long t) { return imdct_tiles(t, tile_frames); });
+    std::vector<ImdctUnit> units;
+    for (const Segment& s : cut_segments(counts.data(), n_clips, kImdctMinSegment, slots, per_slot)) {
+        ImdctUnit u{};
+        u.in_off = (long long)s.clip;
+        u.T = (int)frames[s.clip], u.tiles = (int)counts[(size_t)s.clip];
+        u.tile_a = (int)s.a, u.tile_b = (int)s.b;
+        units.push_back(u);
+    }
+    return units;
+}
+
+// ... M rows of `pitch` floats at float `in_off`, the samples at float `out_off`.
+inline void imdct_fill_clip(ImdctUnit& u, long long in_off, long long out_off, long long pitch, int M) {
+    u.in_off = in_off, u.out_off = out_off, u.out_len = imdct_out_len(u.T, M), u.TP = (int)pitch;
+}
+
+inline std::vector<ImdctUnit> imdct_deal_table(const std::vector<ImdctUnit>& units, long long grid) { return deal_table(units, grid); }   // (the name before deal_table)
+
+}  // namespace zafx

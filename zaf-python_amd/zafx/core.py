@@ -24,11 +24,15 @@ def _i64p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 
 
-def _as_lengths(values, name="lengths"):
+def _as_int64(values, name):
     a = np.asarray(values)
     if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
         raise ValueError(f"{name} must be a 1-D sequence of integers")
-    a = np.ascontiguousarray(a, dtype=np.int64)
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _as_lengths(values, name="lengths"):
+    a = _as_int64(values, name)
     if a.size and int(a.min()) < 0:
         raise ValueError(f"{name} must not be negative")
     return a
@@ -400,11 +404,15 @@ class Plan:
         arrays.  Clip i's block of the output array starts at element out_offsets[i] (out_offsets[-1]: elements in all) and holds F rows of
         pitch[i] elements ("FT"; frames[i] of them are the clip's) or frames[i] x F compact ("TF")."""
         lengths = _as_lengths(lengths)
-        offs = np.zeros(len(lengths) + 1, np.int64)
-        _lib.check(_lib.load().zafx_plan_ragged_layout(self.handle, _i64p(lengths), len(lengths), _i64p(offs)), "zafx_plan_ragged_layout")
+        offs = self._ragged_offsets(lengths)
         frames = np.array([self.out_dims(n)[1] for n in lengths.tolist()], np.int64)
         pitch = np.array([self.row_pitch(n) for n in lengths.tolist()], np.int64)
         return offs, frames, pitch
+
+    def _ragged_offsets(self, lengths):
+        offs = np.zeros(len(lengths) + 1, np.int64)
+        _lib.check(_lib.load().zafx_plan_ragged_layout(self.handle, _i64p(lengths), len(lengths), _i64p(offs)), "zafx_plan_ragged_layout")
+        return offs
 
     def execute_ragged(self, d_in, in_offsets, lengths, d_out):
         """Enqueue one ragged batch on the plan's stream (asynchronous; zafx_execute_ragged): clip i is lengths[i] samples at element in_offsets[i]
@@ -418,9 +426,7 @@ class Plan:
             raise ValueError(f"execute_ragged takes {self.in_dtype} samples and a {self.out_dtype} output buffer")
         if len(lengths) and int((in_offsets + lengths).max()) > d_in.nbytes // d_in.dtype.itemsize:
             raise ValueError("a clip reaches past the end of d_in")
-        offs = np.zeros(len(lengths) + 1, np.int64)
-        _lib.check(_lib.load().zafx_plan_ragged_layout(self.handle, _i64p(lengths), len(lengths), _i64p(offs)), "zafx_plan_ragged_layout")
-        if int(offs[-1]) * self.out_dtype.itemsize > d_out.nbytes:
+        if int(self._ragged_offsets(lengths)[-1]) * self.out_dtype.itemsize > d_out.nbytes:
             raise ValueError("d_out is smaller than the ragged batch's output (ragged_layout)")
         _lib.check(_lib.load().zafx_execute_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, len(lengths)),
                    "zafx_execute_ragged")
@@ -430,13 +436,7 @@ class Plan:
         zafx_execute_center_ragged, center plans only; last_kernel: k_center_ragged).  Offsets and lengths count sample frames (L, R): clip i
         is lengths[i] sample frames at sample frame in_offsets[i] of d_in, its center goes to sample frame out_offsets[i] of d_out and, for a
         plan with sides, its sides directly behind.  Output blocks that overlap are not detected."""
-        arrays = []
-        for name, values in (("in_offsets", in_offsets), ("lengths", lengths), ("out_offsets", out_offsets)):
-            a = np.asarray(values)
-            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-                raise ValueError(f"{name} must be a 1-D sequence of integers")
-            arrays.append(np.ascontiguousarray(a, dtype=np.int64))
-        in_offsets, lengths, out_offsets = arrays
+        in_offsets, lengths, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths"), _as_int64(out_offsets, "out_offsets")
         if not len(in_offsets) == len(lengths) == len(out_offsets):
             raise ValueError("in_offsets, lengths and out_offsets must have one entry per clip")
         if d_in.dtype != np.float32 or d_out.dtype != np.float32:
@@ -457,13 +457,7 @@ class Plan:
         ("TF"); its max((W/2) (frames[i] - 1) - 1, 0) samples go to element out_offsets[i] of d_out.  Float32 "FT" plans of window 512, 1024
         and 2048 whose pitches are multiples of 4 run as one launch (last_kernel: k_imdct_ragged), the others as one execute per clip.  Output
         ranges that overlap are not detected."""
-        arrays = []
-        for name, values in (("in_offsets", in_offsets), ("frames", frames), ("out_offsets", out_offsets)):
-            a = np.asarray(values)
-            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
-                raise ValueError(f"{name} must be a 1-D sequence of integers")
-            arrays.append(np.ascontiguousarray(a, dtype=np.int64))
-        in_offsets, frames, out_offsets = arrays
+        in_offsets, frames, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(frames, "frames"), _as_int64(out_offsets, "out_offsets")
         if not len(in_offsets) == len(frames) == len(out_offsets):
             raise ValueError("in_offsets, frames and out_offsets must have one entry per block")
         if d_coefs.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
@@ -1192,25 +1186,58 @@ def mel_mfcc_pcm_batch(pcm, window_function, step_length, mel_filterbank, number
 _RAGGED_ALIGN = 32   # elements between clip starts in a packed batch: 128 bytes of float32
 
 
-def _as_ragged(clips):
-    """A ragged batch -- a sequence of 1-D real arrays -- validated ahead of any device call."""
-    if isinstance(clips, np.ndarray) and clips.dtype != object and clips.ndim < 2:
-        raise ValueError("a ragged batch is a sequence of 1-D clips, not one array")
+def _as_ragged_items(batch, ndim, name, items, noun, rule=None, empty_ok=False):
+    """A ragged batch -- a sequence of real arrays of rank `ndim` -- validated ahead of any device call: -> the list of arrays.  `name`, `items`
+    and `noun` are the words of the messages; rule(a): what is wrong with the shape of an item ("must ...") or None."""
+    if isinstance(batch, np.ndarray) and batch.dtype != object and batch.ndim <= ndim:
+        raise ValueError(f"a {name} is a sequence of {items}, not one array")
     try:
-        items = list(clips)
+        arrays = list(batch)
     except TypeError:
-        raise ValueError("a ragged batch is a sequence of 1-D clips") from None
-    if not items:
-        raise ValueError("a ragged batch needs at least one clip")
-    out = []
-    for i, c in enumerate(items):
-        a = np.asarray(c)
-        if a.ndim != 1:
-            raise ValueError(f"clip {i} of the ragged batch must be 1-D, got {a.ndim}-D")
-        if np.iscomplexobj(a) or a.dtype.kind not in "biuf":
-            raise ValueError(f"clip {i} of the ragged batch must be real")
-        out.append(a)
-    return out
+        raise ValueError(f"a {name} is a sequence of {items}") from None
+    if not arrays and not empty_ok:
+        raise ValueError(f"a {name} needs at least one {noun}")
+    for i, c in enumerate(arrays):
+        arrays[i] = a = np.asarray(c)
+        wrong = None
+        if a.ndim != ndim:
+            wrong = f"must be {ndim}-D, got {a.ndim}-D"
+        elif np.iscomplexobj(a) or a.dtype.kind not in "biuf":
+            wrong = "must be real"
+        elif rule:
+            wrong = rule(a)
+        if wrong:
+            raise ValueError(f"{noun} {i} of the {name} {wrong}")
+    return arrays
+
+
+def _as_ragged(clips):
+    return _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
+
+
+def _back_to_back(sizes, align=1):
+    """-> (offsets, total): slots of `sizes` elements, each rounded up to a multiple of `align`, laid back to back."""
+    slots = (sizes + align - 1) // align * align
+    offsets = np.zeros(len(sizes), np.int64)
+    offsets[1:] = np.cumsum(slots)[:-1]
+    return offsets, int(slots.sum())
+
+
+def _round_trip(plan, x, n_out, enqueue):
+    """x up (an empty one is not copied), enqueue(d_in, d_out) and the wait under the plan's lock, the `n_out` results -- items of x's trailing
+    shape; at least one is allocated -- down: -> the one downloaded array.  Both buffers are freed whatever happens."""
+    d_in = DeviceBuffer((max(len(x), 1),) + x.shape[1:], x.dtype, plan.device)
+    d_out = DeviceBuffer((max(n_out, 1),) + x.shape[1:], plan.out_dtype, plan.device)
+    try:
+        if len(x):
+            d_in.upload(x)
+        with plan.lock:
+            enqueue(d_in, d_out)
+            plan.sync()
+            return d_out.download()
+    finally:
+        d_in.free()
+        d_out.free()
 
 
 def pack_ragged(clips, dtype=np.float32):
@@ -1219,10 +1246,8 @@ def pack_ragged(clips, dtype=np.float32):
     even (zafx_execute_ragged)."""
     arrays = _as_ragged(clips)
     lengths = np.array([len(a) for a in arrays], np.int64)
-    slots = (lengths + _RAGGED_ALIGN - 1) // _RAGGED_ALIGN * _RAGGED_ALIGN
-    offsets = np.zeros(len(arrays), np.int64)
-    offsets[1:] = np.cumsum(slots)[:-1]
-    packed = np.zeros(max(int(slots.sum()), _RAGGED_ALIGN), dtype)
+    offsets, total = _back_to_back(lengths, _RAGGED_ALIGN)
+    packed = np.zeros(max(total, _RAGGED_ALIGN), dtype)
     for a, o in zip(arrays, offsets.tolist()):
         packed[o:o + len(a)] = a
     return packed, offsets, lengths
@@ -1234,16 +1259,7 @@ def _run_ragged(plan, clips):
     x, in_offsets, lengths = pack_ragged(clips, plan.in_dtype)
     offs, frames, pitch = plan.ragged_layout(lengths)
     rows = plan.out_dims(0)[0]
-    d_in = DeviceBuffer(x.shape, x.dtype, plan.device).upload(x)
-    d_out = DeviceBuffer((max(int(offs[-1]), 1),), plan.out_dtype, plan.device)
-    try:
-        with plan.lock:
-            plan.execute_ragged(d_in, in_offsets, lengths, d_out)
-            plan.sync()
-            res = d_out.download()
-    finally:
-        d_in.free()
-        d_out.free()
+    res = _round_trip(plan, x, int(offs[-1]), lambda d_in, d_out: plan.execute_ragged(d_in, in_offsets, lengths, d_out))
     if plan.layout == _lib.LAYOUT_FT:
         return [res[o:o + rows * p].reshape(rows, p)[:, :t] for o, t, p in zip(offs.tolist(), frames.tolist(), pitch.tolist())]
     return [res[o:o + t * rows].reshape(t, rows) for o, t in zip(offs.tolist(), frames.tolist())]
@@ -1291,26 +1307,10 @@ def mdct_ragged(clips, window_function, layout="FT", device=0, f64=False):
 
 
 def _as_ragged_blocks(coefficients, rows, layout):
-    """A ragged batch of MDCT coefficient blocks -- a sequence of 2-D real arrays, (rows, T_i) ["FT"] or (T_i, rows) ["TF"] -- validated ahead
-    of any device call."""
-    if isinstance(coefficients, np.ndarray) and coefficients.dtype != object and coefficients.ndim < 3:
-        raise ValueError("a ragged batch of coefficients is a sequence of 2-D blocks, not one array")
-    try:
-        items = list(coefficients)
-    except TypeError:
-        raise ValueError("a ragged batch of coefficients is a sequence of 2-D blocks") from None
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    out = []
-    for i, c in enumerate(items):
-        a = np.asarray(c)
-        if a.ndim != 2:
-            raise ValueError(f"block {i} of the ragged batch must be 2-D, got {a.ndim}-D")
-        if np.iscomplexobj(a) or a.dtype.kind not in "biuf":
-            raise ValueError(f"block {i} of the ragged batch must be real")
-        if a.shape[0 if ft else 1] != rows:
-            raise ValueError(f"block {i} of the ragged batch must have window_length/2 = {rows} coefficient rows, got shape {a.shape}")
-        out.append(a)
-    return out
+    """A ragged batch of MDCT coefficient blocks: (rows, T_i) ["FT"] or (T_i, rows) ["TF"]; it may be empty."""
+    axis = 0 if _LAYOUTS[layout] == _lib.LAYOUT_FT else 1
+    return _as_ragged_items(coefficients, 2, "ragged batch of coefficients", "2-D blocks", "block", empty_ok=True,
+                            rule=lambda a: None if a.shape[axis] == rows else f"must have window_length/2 = {rows} coefficient rows, got shape {a.shape}")
 
 
 def imdct_ragged(coefficients, window_function, layout="FT", device=0, f64=False, lengths=None):
@@ -1344,27 +1344,15 @@ def imdct_ragged(coefficients, window_function, layout="FT", device=0, f64=False
     a = max(plan.row_align, 1)
     pitch = (frames + a - 1) // a * a if ft else np.full(len(blocks), m, np.int64)
     elems = m * pitch if ft else frames * m
-    in_offsets = np.zeros(len(blocks), np.int64)
-    in_offsets[1:] = np.cumsum(elems)[:-1]
-    slots = (out_len + _RAGGED_ALIGN - 1) // _RAGGED_ALIGN * _RAGGED_ALIGN
-    out_offsets = np.zeros(len(blocks), np.int64)
-    out_offsets[1:] = np.cumsum(slots)[:-1]
-    packed = np.empty(max(int(elems.sum()), 1), plan.in_dtype)   # (the pad columns are never used: they stay as they come)
+    in_offsets, n_in = _back_to_back(elems)
+    out_offsets, n_out = _back_to_back(out_len, _RAGGED_ALIGN)
+    packed = np.empty(max(n_in, 1), plan.in_dtype)   # (the pad columns are never used: they stay as they come)
     for b, o, t, p in zip(blocks, in_offsets.tolist(), frames.tolist(), pitch.tolist()):
         if ft:
             packed[o:o + m * p].reshape(m, p)[:, :t] = b   # (rows of a view at any pitch: copied row by row)
         else:
             packed[o:o + t * m].reshape(t, m)[...] = b
-    d_in = DeviceBuffer(packed.shape, packed.dtype, plan.device).upload(packed)
-    d_out = DeviceBuffer((max(int(slots.sum()), 1),), plan.out_dtype, plan.device)
-    try:
-        with plan.lock:
-            plan.execute_imdct_ragged(d_in, in_offsets, frames, d_out, out_offsets)
-            plan.sync()
-            res = d_out.download()
-    finally:
-        d_in.free()
-        d_out.free()
+    res = _round_trip(plan, packed, n_out, lambda d_in, d_out: plan.execute_imdct_ragged(d_in, in_offsets, frames, d_out, out_offsets))
     keep = out_len if lengths is None else lengths
     return _as_f32_views([res[o:o + n] for o, n in zip(out_offsets.tolist(), keep.tolist())], plan, f64)
 
@@ -1401,27 +1389,10 @@ def mel_mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_
     ft = plan.layout == _lib.LAYOUT_FT
     return ([b[:n_filters] if ft else b[:, :n_filters] for b in both], [b[n_filters:] if ft else b[:, n_filters:] for b in both])
 
+
 def _as_ragged_stereo(clips):
-    """A ragged stereo batch -- a sequence of (N_i, 2) real arrays -- validated ahead of any device call."""
-    if isinstance(clips, np.ndarray) and clips.dtype != object and clips.ndim < 3:
-        raise ValueError("a ragged stereo batch is a sequence of (N, 2) clips, not one array")
-    try:
-        items = list(clips)
-    except TypeError:
-        raise ValueError("a ragged stereo batch is a sequence of (N, 2) clips") from None
-    if not items:
-        raise ValueError("a ragged stereo batch needs at least one clip")
-    out = []
-    for i, c in enumerate(items):
-        a = np.asarray(c)
-        if a.ndim != 2:
-            raise ValueError(f"clip {i} of the ragged stereo batch must be 2-D, (sample frames, 2), got {a.ndim}-D")
-        if a.shape[1] != 2:
-            raise ValueError(f"clip {i} of the ragged stereo batch must be stereo, (sample frames, 2), got shape {a.shape}")
-        if np.iscomplexobj(a) or a.dtype.kind not in "biuf":
-            raise ValueError(f"clip {i} of the ragged stereo batch must be real")
-        out.append(a)
-    return out
+    return _as_ragged_items(clips, 2, "ragged stereo batch", "(N, 2) clips", "clip",
+                            rule=lambda a: None if a.shape[1] == 2 else f"must be stereo, (sample frames, 2), got shape {a.shape}")
 
 
 def pack_ragged_stereo(clips):
@@ -1430,9 +1401,8 @@ def pack_ragged_stereo(clips):
     a buffer descriptor of its own, so a neighbour right behind a clip is never read as its tail."""
     arrays = _as_ragged_stereo(clips)
     lengths = np.array([len(a) for a in arrays], np.int64)
-    offsets = np.zeros(len(arrays), np.int64)
-    offsets[1:] = np.cumsum(lengths)[:-1]
-    packed = np.empty((int(lengths.sum()), 2), np.float32)
+    offsets, total = _back_to_back(lengths)
+    packed = np.empty((total, 2), np.float32)
     for a, o in zip(arrays, offsets.tolist()):
         packed[o:o + len(a)] = a
     return packed, offsets, lengths
@@ -1448,19 +1418,7 @@ def centersides_ragged(clips, window_function, step_length=None, sides=True, dev
     plan = center_plan(w, device, sides)
     blocks = 2 if sides else 1
     out_offsets = blocks * in_offsets
-    total = blocks * int(lengths.sum())
-    d_in = DeviceBuffer((max(len(x), 1), 2), np.float32, plan.device)
-    d_out = DeviceBuffer((max(total, 1), 2), np.float32, plan.device)
-    try:
-        if len(x):
-            d_in.upload(x)
-        with plan.lock:
-            plan.execute_center_ragged(d_in, in_offsets, lengths, d_out, out_offsets)
-            plan.sync()
-            res = d_out.download()
-    finally:
-        d_in.free()
-        d_out.free()
+    res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: plan.execute_center_ragged(d_in, in_offsets, lengths, d_out, out_offsets))
     if not sides:
         return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
