@@ -259,6 +259,27 @@ int zafx_execute_center_ragged(zafx_plan* plan, const void* d_in, const int64_t*
  * forward transform: a switch for measurements only (tools/ragged_rates.py --kinds imdct), read at every call, not part of the interface. */
 int zafx_execute_imdct_ragged(zafx_plan* plan, const void* d_coefs, const int64_t* in_offsets, const int64_t* frames, void* d_out,
                               const int64_t* out_offsets, int64_t n_clips);
+/* The inverse STFT of n_clips spectra of different frame counts, enqueued on the plan's stream (asynchronous; ZAFX_ISTFT plans only --
+ * zafx_execute_ragged and zafx_plan_ragged_layout keep refusing the inverse kinds).  Block i is the (W, frames[i]) complex array -- (W/2 + 1,
+ * frames[i]) for a one-sided plan -- of one clip at complex element in_offsets[i] of d_spec: rows at the pitch zafx_plan_row_pitch(plan,
+ * frames[i]) in ZAFX_LAYOUT_FT -- the layout a ZAFX_STFT plan's zafx_execute_ragged writes at the same row_align and spectrum, so the output
+ * buffer of a ragged STFT can be fed back as it lies --, frames[i] x rows compact in ZAFX_LAYOUT_TF.  The pad columns of a block are never
+ * used; they may hold anything.  Clip i's max(frames[i] H - (W - H), 0) samples (zaf.py istft) go to float out_offsets[i] of d_out; a block
+ * that gives no samples writes nothing.  Every clip's result is bit-identical to zafx_execute on that block alone; nothing outside the clips
+ * is written.  The three host arrays are copied before return.  Rejected with a message: another plan kind, n_clips < 0, a negative frame
+ * count or offset (with the clip's index), a window constant that is not set, a window whose COLA gain sum(window[0:W:H]) is zero.  NOT
+ * checked: that the output ranges do not overlap -- placing them is the caller's business.
+ * ONE launch (last kernel "k_istft_ragged") for float32 plans in ZAFX_LAYOUT_FT at a power-of-two window 256 ... 2048 (the k_istft_ft16
+ * route) with ceil(W / H) - 1 < 16, when d_spec is 4-byte aligned, the batch gives fewer than 2^31 units and every block is below 2^31 bytes
+ * counted as W rows -- W x pitch x 8 < 2^31: the kernel addresses a block through one buffer descriptor with signed 32-bit byte offsets, the
+ * bound of the equal-length route; 16-byte gathers when d_spec is 8-byte aligned, 8-byte ones otherwise; d_out and the output offsets need
+ * 4-byte alignment only (a clip's bits do not depend on where it is put).  Everything else -- ZAFX_LAYOUT_TF, float64, window 4096 / 8192,
+ * windows below 256, Bluestein windows, hops with ceil(W / H) - 1 >= 16 -- runs one zafx_execute per clip on the plan's stream and reports that
+ * kernel's name.  ZAFX_RAGGED_ISTFT_NATIVE=0 in the environment keeps a batch off the one launch and ZAFX_ISTFT_UNITS_PER_SLOT sets the units
+ * per workgroup slot its cutting rule aims at: switches for measurements only (tools/ragged_rates.py --kinds istft), read at every call, not
+ * part of the interface. */
+int zafx_execute_istft_ragged(zafx_plan* plan, const void* d_spec, const int64_t* in_offsets, const int64_t* frames, void* d_out,
+                              const int64_t* out_offsets, int64_t n_clips);
 /* Bytes of ONE clip on the input and on the output side of the plan for `n_in` (as zafx_plan_out_dims; rows at the
  * plan's pitch): what a host array of n_clips clips must hold for zafx_run_host. */
 int zafx_plan_clip_bytes(const zafx_plan* plan, int64_t n_in, int64_t* in_bytes, int64_t* out_bytes);

@@ -1,6 +1,7 @@
 """Rates of ragged batches (zafx_execute_ragged) against the padded batch and an equal-length batch, in one process.
 
-    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct] [--imdct-k 2,4,8,12,16,24]
+    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct,istft] [--imdct-k 2,4,8,12,16,24]
+                                 [--istft-k 2,4,8,12,16,24]
 
 Batch: 1024 clips, lengths uniform in 5-15 s at 44.1 kHz (even, so that the aligned loads apply as they do for the equal-length batch),
 window 2048, hop 1024.  For the STFT (two-sided, the headline's kind), mel (128 filters), mfcc (20 coefficients) and the one-pass mel + mfcc:
@@ -20,6 +21,14 @@ whole lines, as the ragged MDCT leaves them.  `ragged`: one execute_imdct_ragged
 `padded`: every block padded to the longest as one execute (k_imdct); `per_clip`: the same execute_imdct_ragged with
 ZAFX_RAGGED_IMDCT_NATIVE=0, one zafx_execute per block -- the only way before the RAGGED form existed.  --imdct-k: the ragged reading again
 for these units per workgroup slot of the cutting rule (ZAFX_IMDCT_UNITS_PER_SLOT), the sweep the shipped constant was chosen from.
+
+The `istft` rows (not in the default kinds; `istft`: two-sided, `istft_onesided`: rows 0 ... W/2): the spectra of those clips, Hamming 2048 / hop
+1024, rows padded to whole lines -- written on the device by the ragged STFT (and by the STFT of the padded batch), as a caller who edits spectra
+has them.  `ragged`: one execute_istft_ragged, cutting and table upload included (k_istft_ragged); `padded`: every spectrum padded to the
+longest as one execute (k_istft_ft16); `per_clip`: the same execute_istft_ragged with ZAFX_RAGGED_ISTFT_NATIVE=0, one zafx_execute per
+spectrum.  The three are read in turn, one launch of each per round, --reps rounds after three warm-up rounds (every shape and route warmed),
+median (min, max).  --istft-k: the ragged reading again for these units per workgroup slot (ZAFX_ISTFT_UNITS_PER_SLOT).  With `istft` among
+the kinds the tool exits with status 1 unless the one launch is faster than both alternatives for both spectrum kinds.
 """
 import argparse
 import json
@@ -188,12 +197,101 @@ def measure_imdct(lengths, reps, sweep):
     return res
 
 
+def timed_in_turn(plan, launches, reps, warm=3):
+    """The launches (name -> callable) read in turn, one of each per round: what shares the device disturbs them alike."""
+    ms = {k: [] for k in launches}
+    for r in range(warm + reps):
+        for k, launch in launches.items():
+            plan.timer_start()
+            launch()
+            t = plan.timer_stop()
+            if r >= warm:
+                ms[k].append(t)
+    return {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v))} for k, v in ms.items()}
+
+
+def with_env(name, value, call):
+    def run():
+        os.environ[name] = value
+        try:
+            call()
+        finally:
+            del os.environ[name]
+    return run
+
+
+def measure_istft(name, onesided, lengths, reps, sweep):
+    """ragged / padded / per-clip of the ISTFT on one plan.  The spectra are made on the device: the ragged STFT of noise clips writes the
+    blocks where the ragged ISTFT reads them, the STFT of the clips padded to the longest writes the padded batch."""
+    window = zafx.hamming(W)
+    fwd = zafx.stft_plan(window, HOP, onesided=onesided, row_align=16)
+    plan = zafx.istft_plan(window, HOP, onesided=onesided, row_align=16)
+    rows = W // 2 + 1 if onesided else W
+    rng = np.random.default_rng(1)
+    slots = (lengths + 31) // 32 * 32
+    clip_offsets = np.zeros(len(lengths), np.int64)
+    clip_offsets[1:] = np.cumsum(slots)[:-1]
+    clips = zafx.DeviceBuffer((int(slots.sum()),), np.float32)
+    clips.upload(rng.standard_normal(clips.shape, dtype=np.float32))
+    offs, frames, pitch = fwd.ragged_layout(lengths)
+    in_offsets = np.ascontiguousarray(offs[:-1], dtype=np.int64)
+    assert all(plan.row_pitch(int(t)) == int(p) for t, p in zip(frames[:8], pitch[:8]))
+    spec = zafx.DeviceBuffer((int(offs[-1]),), np.complex64)
+    fwd.execute_ragged(clips, clip_offsets, lengths, spec)
+    fwd.sync()
+    clips.free()
+    out_len = np.maximum(frames * HOP - (W - HOP), 0)
+    out_offsets = np.zeros(len(frames), np.int64)
+    out_offsets[1:] = np.cumsum((out_len + 31) // 32 * 32)[:-1]
+    out = zafx.DeviceBuffer((int(out_offsets[-1] + out_len[-1]) + 32,), np.float32)
+    nmax, tmax = int(lengths.max()), int(frames.max())
+    padded_clips = zafx.DeviceBuffer((CLIPS, nmax), np.float32)
+    padded_clips.upload(rng.standard_normal(padded_clips.shape, dtype=np.float32))
+    padded = zafx.DeviceBuffer((CLIPS, rows, plan.row_pitch(tmax)), np.complex64)
+    fwd.execute(padded_clips, padded, CLIPS, nmax)
+    fwd.sync()
+    padded_clips.free()
+    o = zafx.DeviceBuffer(plan.out_shape(CLIPS, tmax), plan.out_dtype)
+    res = {"samples": int(out_len.sum()), "frames": int(frames.sum()), "longest_frames": tmax, "spectrum_rows": rows}
+    call = lambda: plan.execute_istft_ragged(spec, in_offsets, frames, out, out_offsets)   # noqa: E731
+    kernels = {}
+
+    def noting(key, launch):
+        def run():
+            launch()
+            kernels[key] = plan.last_kernel
+        return run
+    launches = {"ragged": noting("ragged", call), "padded": noting("padded", lambda: plan.execute(padded, o, CLIPS, tmax)),
+                "per_clip": noting("per_clip", with_env("ZAFX_RAGGED_ISTFT_NATIVE", "0", call))}
+    res.update(timed_in_turn(plan, launches, reps))
+    for key in launches:
+        res[key + "_kernel"] = kernels[key]
+    if sweep:
+        res["units_per_slot_sweep"] = timed_in_turn(plan, {str(k): with_env("ZAFX_ISTFT_UNITS_PER_SLOT", str(k), call) for k in sweep}, reps)
+    for b in (spec, out, padded, o):
+        b.free()
+    for key in ("ragged", "padded", "per_clip"):
+        res[key]["msamples_per_s"] = res["samples"] / (res[key]["median_ms"] * 1e3)
+    res["ragged_over_padded"] = res["ragged"]["median_ms"] / res["padded"]["median_ms"]
+    res["per_clip_over_ragged"] = res["per_clip"]["median_ms"] / res["ragged"]["median_ms"]
+    res["ragged_is_fastest"] = bool(res["ragged"]["median_ms"] < min(res["padded"]["median_ms"], res["per_clip"]["median_ms"]))
+    r, p, c = res["ragged"], res["padded"], res["per_clip"]
+    print(f"{name:9s} ragged {r['median_ms']:7.3f} ms ({r['min_ms']:.3f}-{r['max_ms']:.3f}) {r['msamples_per_s']:8.0f} Ms/s [{res['ragged_kernel']}] | "
+          f"padded {p['median_ms']:7.3f} ms ({p['min_ms']:.3f}-{p['max_ms']:.3f}) [{res['padded_kernel']}] | per clip {c['median_ms']:7.3f} ms "
+          f"({c['min_ms']:.3f}-{c['max_ms']:.3f}) [{res['per_clip_kernel']}] | ragged / padded {res['ragged_over_padded']:.3f}, "
+          f"per clip / ragged {res['per_clip_over_ragged']:.1f}", flush=True)
+    for k, t in res.get("units_per_slot_sweep", {}).items():
+        print(f"{name:9s} units per slot {k:>3s}: ragged {t['median_ms']:7.3f} ms ({t['min_ms']:.3f}-{t['max_ms']:.3f})", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default="")
     ap.add_argument("--kinds", default="stft,mel,mfcc,mel+mfcc,mdct,mdct_any")
     ap.add_argument("--imdct-k", default="2,4,8,12,16,24")
+    ap.add_argument("--istft-k", default="2,4,8,12,16,24")
     a = ap.parse_args()
     kinds = a.kinds.split(",")
     rng = np.random.default_rng(0)
@@ -221,9 +319,18 @@ def main():
             result[name] = measure_mdct(name, lengths, a.reps)
     if "imdct" in kinds:
         result["imdct"] = measure_imdct(lengths, a.reps, [int(k) for k in a.imdct_k.split(",") if k])
+    fastest = True
+    if "istft" in kinds:
+        sweep = [int(k) for k in a.istft_k.split(",") if k]
+        for name, onesided in (("istft", False), ("istft_onesided", True)):
+            result[name] = measure_istft(name, onesided, lengths, a.reps, sweep)
+            fastest = fastest and result[name]["ragged_is_fastest"]
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
+    if not fastest:
+        print("the one launch of the ragged ISTFT is not faster than both alternatives")
+        sys.exit(1)
 
 
 if __name__ == "__main__":

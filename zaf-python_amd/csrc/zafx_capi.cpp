@@ -1774,6 +1774,49 @@ int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t*
     return 0;
 }
 
+// Ragged batches of the inverse STFT: spectra of different frame counts.  The host cuts the blocks into units (istft_cut_units), k_istft_ft16's
+// RAGGED form walks them in one launch: float32, reference layout, W = 256 ... 2048, no Bluestein part, halo < 16, every block below 2^31
+// bytes counted as W rows (a buffer descriptor per clip, signed 32-bit byte offsets: run_istft's bound), units below 2^31.  Everything else
+// -- the frame-major layout, float64, W = 4096 / 8192, W < 256, Bluestein windows, smaller hops -- runs one zafx_execute per clip on the plan's
+// stream and reports that kernel.  ZAFX_RAGGED_ISTFT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only,
+// include/zafx.h); ZAFX_ISTFT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+int zafx_execute_istft_ragged(zafx_plan* pl, const void* d_spec, const int64_t* in_offsets, const int64_t* frames, void* d_out, const int64_t* out_offsets,
+                              int64_t n_clips) {
+    const char* wrong_kind = !pl || pl->kind == ZAFX_ISTFT ? nullptr : "inverse STFT plans (ZAFX_ISTFT) only (zafx_execute_ragged takes the forward kinds)";
+    bool empty = false;
+    if (int rc = ragged_args("zafx_execute_istft_ragged", pl, n_clips, wrong_kind, d_spec, d_out, {frames, in_offsets, out_offsets}, "frame count", &empty)) return rc;
+    if (empty) return 0;
+    if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg("istft: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    bool native = zafx::istft_ragged_native(*pl) && reinterpret_cast<uintptr_t>(d_spec) % 4 == 0 && env_on("ZAFX_RAGGED_ISTFT_NATIVE");
+    for (int64_t i = 0; native && i < n_clips; ++i) native = frames[i] < (1LL << 28) && (long long)pl->W * row_pitch(*pl, frames[i]) * 8 < (1LL << 31);
+    ZAFX_HIP(hipSetDevice(pl->device));
+    int tile_frames = 0;
+    long long slots = 0;
+    if (native && zafx::istft_launch_shape(*pl, &tile_frames, &slots)) {
+        const int per_slot = env_units_per_slot("ZAFX_ISTFT_UNITS_PER_SLOT", zafx::kIstftUnitsPerSlot);
+        std::vector<zafx::IstftUnit> units = zafx::istft_cut_units(frames, n_clips, pl->W, pl->H, tile_frames, slots, per_slot);
+        if (units.size() + (size_t)slots < (size_t)1 << 31) {   // (the table in launch order is at most one round longer)
+            for (zafx::IstftUnit& u : units) {   // (the cutter leaves the clip's index in in_off)
+                const int64_t i = u.in_off;
+                zafx::istft_fill_clip(u, in_offsets[i], out_offsets[i], row_pitch(*pl, frames[i]), pl->W, pl->H);
+            }
+            // the launch's workgroups (launch_istft_ragged: min(records, slots) -- the table is a whole number of rounds or shorter than one)
+            const std::vector<zafx::IstftUnit> table = zafx::deal_table(units, std::min<long long>((long long)units.size(), slots));
+            if (int rc = upload_records(pl, table)) return rc;
+            return launch_rc("zafx_execute_istft_ragged", zafx::launch_istft_ragged(*pl, (const float2*)d_spec, (float*)d_out, static_cast<const zafx::IstftUnit*>(pl->d_ragged),
+                                                                                  (long long)table.size()));
+        }
+    }
+    // everything else: one zafx_execute per clip on the plan's stream (a block that gives no samples is passed over)
+    const int64_t eb = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        if (zafx::istft_out_len(frames[i], pl->W, pl->H) <= 0) continue;
+        if (int rc = zafx_execute(pl, (const char*)d_spec + in_offsets[i] * 2 * eb, (char*)d_out + out_offsets[i] * eb, 1, frames[i])) return rc;
+    }
+    return 0;
+}
+
 int zafx_sync(zafx_plan* pl) {
     if (!pl) return fail_msg("null plan");
     ZAFX_HIP(hipSetDevice(pl->device));

@@ -339,6 +339,14 @@ constexpr int kImdctRaggedTile = 32;
 bool imdct_ragged_native(const zafx_plan& pl);
 bool imdct_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
 hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const ImdctUnit* d_units, long long n_units);
+// zafx_execute_istft_ragged: k_istft_ft16's RAGGED form (float32, reference layout, W = 256 ... 2048, halo < 16) -- the plans that have it, the
+// tile frames and the workgroup slots of its launch (what istft_cut_units takes), and the launch on `n_units` records of the device table
+// (zafx_units.hpp; every block below 2^31 bytes, spec on 4 bytes, units below 2^31)
+struct IstftUnit;
+constexpr int kIstftRaggedTile = 16;
+bool istft_ragged_native(const zafx_plan& pl);
+bool istft_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
+hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const IstftUnit* d_units, long long n_units);
 hipError_t launch_pcm_to_float(hipStream_t stream, const void* pcm, float* out, int64_t n_total, int n_channels, int sample_bytes);
 
 // names of the dominant kernels (what rocprofv3 --kernel-trace prints, prefix match)

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "zafx_fft.hpp"
+#include "zafx_units.hpp"
 #include "zafx_internal.hpp"
 
 namespace zafx {
@@ -1930,11 +1931,36 @@ ZAFX_PROF_ARRAY(g_prof)
 // transforms and the overlap-add, 1.945 -> 1.92 ms; two sweeps spill, 1.99 ms; a second sweep requested
 // when the transforms are done spills as well, 1.82 -> 1.91 ms).  Barriers order LDS only (lds_barrier): the output stores of a tile are not
 // waited for.
-template <int LOG2N, int LOG2E, int DEPTH, bool ONE, int FV, bool TF = false>
+// RAGGED (zafx_execute_istft_ragged): spectra of different frame counts.  The walk is the same; `out_len` carries the table of unit records
+// (IstftLenArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (IstftUnit, zafx_units.hpp:
+// the host cuts the batch and deals the table in launch order, deal_table).  The base of the clip's block -- its buffer descriptor is built
+// from it and sized to the block, so a piece that runs past the block reads 0 --, its frames, pitch and tiles, the base and the length of
+// its output and the unit's tiles come from the record (uniform: scalar loads into SGPRs) instead of from unit / segs, unit % segs and the
+// kernel's arguments (rg_pick); T, TP, tiles, segs and seg_tiles are not used.  Two records are live: rc, the unit of the tile being
+// transformed and stored, and rn, the unit of the tile after it (the prefetch goes through rn's descriptor); rn is rc inside a unit and is
+// looked up at the head of a unit's last tile, so the scalar loads hide under the fold.  A record without tiles (what deal_table fills a short
+// backward round with: only ever a workgroup's last) ends the walk.
+// Unit change: the carry belongs to one unit.  A unit's last tile has make_carry == false, which keeps it off the sweep form and makes both
+// other forms write 0 to every carry slot; a carry-only tile (write_out == false) never reads the carry and overwrites every slot; so a unit
+// starts on the zeros its predecessor left (or the ones written before the first tile) whatever clip that predecessor belonged to.
+template <bool RAGGED>
+using IstftLenArg = std::conditional_t<RAGGED, const IstftUnit*, long long>;
+// The record of unit `u` (uniform) in SGPRs: read through the constant address space, as rg_clip_const -- nothing writes the table while a
+// kernel runs.
+__device__ __forceinline__ IstftUnit istft_unit_const(const IstftUnit* tab, int u) {
+    typedef const __attribute__((address_space(4))) IstftUnit* CRec;
+    const CRec r = (CRec)tab + u;
+    IstftUnit rc;
+    rc.in_off = r->in_off, rc.out_off = r->out_off, rc.out_len = r->out_len;
+    rc.T = r->T, rc.TP = r->TP, rc.tiles = r->tiles, rc.tile_a = r->tile_a, rc.tile_b = r->tile_b, rc.pad_ = 0;
+    return rc;
+}
+template <int LOG2N, int LOG2E, int DEPTH, bool ONE, int FV, bool TF = false, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void k_istft_ft16(
     const float2* __restrict__ spec, const float2* __restrict__ twp, const float2* __restrict__ tws,
-    float* __restrict__ y, int T, int TP, int hop, long long out_len, float scale, int tiles, int segs, int seg_tiles,
+    float* __restrict__ y, int T, int TP, int hop, IstftLenArg<RAGGED> out_len, float scale, int tiles, int segs, int seg_tiles,
     int total_units, int halo) {
+    static_assert(!RAGGED || !TF, "ragged batches: the reference layout");
     using C = FftCfg<LOG2N, LOG2E>;
     using F = FatCfg<LOG2N, LOG2E>;
     constexpr int N = C::N, P = C::P, E = C::E, W = 2 * N, NT = 1024, FPB = kFatFrames, PITCH = F::PITCH;
@@ -1966,14 +1992,20 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
     struct Tile {
         int unit, tile, tile_a, tile_b;
     };
-    auto enter = [&](Tile& it) {   // first tile of it.unit (one before the segment when it needs a carry)
-        const int seg = it.unit % segs;
-        it.tile_a = seg * seg_tiles;
-        it.tile_b = min(it.tile_a + seg_tiles, tiles);
+    // (ru: RAGGED, the record of it.unit; the clip's frames, pitch and tiles are the kernel's arguments otherwise -- rg_pick)
+    auto enter = [&](Tile& it, [[maybe_unused]] const IstftUnit& ru) {   // first tile of it.unit (one before the segment when it needs a carry)
+        if constexpr (RAGGED) {
+            it.tile_a = ru.tile_a;
+            it.tile_b = ru.tile_b;
+        } else {
+            const int seg = it.unit % segs;
+            it.tile_a = seg * seg_tiles;
+            it.tile_b = min(it.tile_a + seg_tiles, tiles);
+        }
         it.tile = it.tile_a > 0 ? it.tile_a - 1 : 0;
     };
-    auto my_frame_needed = [&](const Tile& it) {   // (FV = 2: the pitch is even, so a pair's second frame is in the row; past T it is unused)
-        return it.tile * FPB + fs < T && fs + FV - 1 >= (it.tile < it.tile_a ? FPB - halo : 0);
+    auto my_frame_needed = [&](const Tile& it, [[maybe_unused]] const IstftUnit& ru) {   // (FV = 2: the pitch is even, so a pair's second frame is in the row; past T it is unused)
+        return it.tile * FPB + fs < rg_pick<RAGGED>(ru.T, T) && fs + FV - 1 >= (it.tile < it.tile_a ? FPB - halo : 0);
     };
     // Rows k, W-k, N-k, N+k of sweep s (k = 0: rows 0, N/2, N, 3N/2) for my frame(s).  Buffer loads: the
     // clip's descriptor and the sweep's row offsets are wave-uniform (SGPRs), the per-lane part is two
@@ -1983,11 +2015,19 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
     struct Src {
         __amdgpu_buffer_rsrc_t rsrc;
         int t_bytes;   // byte offset of the tile's first frame within a row
+        int row_bytes, v_up, v_down;   // RAGGED: the clip's own (the launcher admits blocks below 2^31 bytes)
     };
-    auto source = [&](const Tile& it) {
+    auto source = [&](const Tile& it, [[maybe_unused]] const IstftUnit& ru) {
         Src src;
-        src.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(spec) + (long long)(it.unit / segs) * ROWS * TP, 0,
-                                                     ROWS * row_bytes, 0x00020000);
+        if constexpr (RAGGED) {   // a descriptor per clip, sized to its block
+            src.row_bytes = ru.TP * 8;
+            src.v_up = kq * src.row_bytes + fs * 8, src.v_down = (KSTEP - kq) * src.row_bytes + fs * 8;
+            src.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(spec) + ru.in_off, 0, ROWS * src.row_bytes, 0x00020000);
+        } else {
+            src.row_bytes = src.v_up = src.v_down = 0;
+            src.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(spec) + (long long)(it.unit / segs) * ROWS * TP, 0,
+                                                         ROWS * row_bytes, 0x00020000);
+        }
         src.t_bytes = it.tile * FPB * 8;
         return src;
     };
@@ -2005,6 +2045,12 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
     // (one-sided input: only rows k and N-k are loaded -- plus row N/2 for the lane that holds k = 0 --
     // and fold4 completes the other two as conjugates)
     auto load4 = [&](const Src& src, int s, RV (&r)[4]) {
+        const int& row_bytes_k = row_bytes;   // (the kernel's own; the three names below are the clip's in the RAGGED form)
+        const int& v_up_k = v_up;
+        const int& v_down_k = v_down;
+        const int& row_bytes = rg_pick<RAGGED>(src.row_bytes, row_bytes_k);
+        const int& v_up = rg_pick<RAGGED>(src.v_up, v_up_k);
+        const int& v_down = rg_pick<RAGGED>(src.v_down, v_down_k);
         if (s == 0) {   // the sweep that holds k = 0: per-lane row select
             const int k = kq;
             r[0] = ld(src, v_up, 0);
@@ -2060,10 +2106,15 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
     constexpr int PF = (!TF && FV == 2 && KI >= ZAFX_ISTFT_PF) ? ZAFX_ISTFT_PF : 0;   // sweeps of the next tile requested ahead
     RV pre[PF > 0 ? PF : 1][4];
     bool pre_ok = false;
+    [[maybe_unused]] IstftUnit rc{}, rn{};   // RAGGED: the records of cur's and of nxt's unit
     Tile cur;
     cur.unit = blockIdx.x;
     if (cur.unit >= total_units) return;
-    enter(cur);
+    if constexpr (RAGGED) {
+        rc = istft_unit_const(out_len, cur.unit);
+        if (rc.tile_b <= rc.tile_a) return;
+    }
+    enter(cur, rc);
     for (int c = tid; c < ncarry; c += NT) carry[c] = 0.f;
     lds_barrier();   // tables staged
     PROF_INIT(g_prof);
@@ -2073,9 +2124,16 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
         const bool carry_only = cur.tile < cur.tile_a;
         const int t_first = cur.tile * FPB;
         Tile nxt = cur;
+        if constexpr (RAGGED) rn = rc;
         if (++nxt.tile >= nxt.tile_b) {
             nxt.unit += gridDim.x;
-            if (nxt.unit < total_units) enter(nxt);
+            if constexpr (RAGGED) {
+                if (nxt.unit < total_units) {
+                    rn = istft_unit_const(out_len, nxt.unit);
+                    if (rn.tile_b <= rn.tile_a) nxt.unit = total_units;   // (no tiles: the filler of the table's last round)
+                }
+            }
+            if (nxt.unit < total_units) enter(nxt, rn);
         }
         const bool has_next = nxt.unit < total_units;
         if constexpr (TF) {
@@ -2114,8 +2172,8 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
         //      were requested when the PREVIOUS tile had been folded and rode in registers across its transforms and its
         //      overlap-add (round 2: the kernel is at 96 VGPRs, the transforms no longer need 116): the gather, half of the tile
         //      time and the only phase with loads in flight, starts half done.
-        if (my_frame_needed(cur)) {
-            const Src sp = source(cur);
+        if (my_frame_needed(cur, rc)) {
+            const Src sp = source(cur, rc);
             if constexpr (PF > 0) {
                 if (pre_ok) {
                     RV r[4];
@@ -2146,9 +2204,9 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
             }
         }
         if constexpr (PF > 0) {
-            pre_ok = has_next && my_frame_needed(nxt);
+            pre_ok = has_next && my_frame_needed(nxt, rn);
             if (pre_ok) {
-                const Src spn = source(nxt);
+                const Src spn = source(nxt, rn);
 #pragma unroll
                 for (int s = 0; s < PF; ++s) load4(spn, s, pre[s]);
             }
@@ -2176,16 +2234,23 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
             a.pitch2 = 2 * PITCH;
             a.ncarry = ncarry;
             a.hop = hop;
-            a.n_valid = min(FPB, T - t_first);
-            a.c_end = cur.tile == tiles - 1 ? a.n_valid * hop + ncarry : FPB * hop;
+            a.n_valid = min(FPB, rg_pick<RAGGED>(rc.T, T) - t_first);
+            a.c_end = cur.tile == rg_pick<RAGGED>(rc.tiles, tiles) - 1 ? a.n_valid * hop + ncarry : FPB * hop;
             a.write_out = !carry_only;
             a.make_carry = cur.tile + 1 < cur.tile_b;
-            const long long clip = cur.unit / segs;
-            a.yc = y + clip * out_len;
+            // (RAGGED: the clip's samples lie at float rc.out_off of the output, any float; clip x out_len otherwise)
+            long long clip = 0, y_off;
+            if constexpr (RAGGED) {
+                y_off = rc.out_off;
+            } else {
+                clip = cur.unit / segs;
+                y_off = clip * out_len;
+            }
+            a.yc = y + y_off;
             a.o_first = (long long)t_first * hop - ncarry;
-            a.out_len = out_len;
+            a.out_len = rg_pick<RAGGED>(rc.out_len, out_len);
             a.scale = scale;
-            const bool ya = y_base_aligned && (clip * out_len) % 2 == 0;
+            const bool ya = y_base_aligned && y_off % 2 == 0;
             if (pairs) {
                 if (!ola_phase_sweep<W, NT, FPB>(a, tid, ya)) ola_phase_pairs<W, NT, FPB>(a, tid, ya);
             } else {
@@ -2197,6 +2262,7 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
         PROF_MARK(6);
         if (!has_next) break;
         cur = nxt;
+        if constexpr (RAGGED) rc = rn;
     }
 }
 
@@ -3485,6 +3551,69 @@ hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, 
         case 8: return dispatch_stft_ragged<8>(pl, x, out, tab, n_clips, total_tiles, aligned);
         case 9: return dispatch_stft_ragged<9>(pl, x, out, tab, n_clips, total_tiles, aligned);
         case 10: return dispatch_stft_ragged<10>(pl, x, out, tab, n_clips, total_tiles, aligned);
+    }
+    return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------
+// ragged batches (zafx_execute_istft_ragged): the units come cut and dealt from the host (istft_cut_units, deal_table)
+// ---------------------------------------------------------------------------------
+// k_istft_ft16's RAGGED form: W = 256 ... 2048 in the reference layout, float32, any hop with halo < 16 -- what run_istft_fat runs.  The
+// geometry (LDS, workgroups per CU, the 16-byte gather when the array is on 8 bytes: block offsets count complex64 elements, so every block
+// shares the array's alignment) is run_istft_fat's.
+bool istft_ragged_native(const zafx_plan& pl) {
+    return pl.kind == ZAFX_ISTFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && stft_use_fat(pl.log2nf, pl.layout) && pl.d_tw_pass &&
+           pl.d_tw_aux && pl.H >= 1 && (pl.W + pl.H - 1) / pl.H - 1 < kFatFrames;
+}
+
+template <int LOG2N>
+static long long istft_fat_slots(const zafx_plan& pl) {   // resident workgroups: run_istft_fat's grid bound
+    using F = FatCfg<LOG2N, default_log2e(LOG2N)>;
+    const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
+    return (long long)pl.n_cus * std::max(per_cu, 1);
+}
+
+bool istft_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots) {
+    switch (pl.log2nf) {
+        case 7: *slots = istft_fat_slots<7>(pl); break;
+        case 8: *slots = istft_fat_slots<8>(pl); break;
+        case 9: *slots = istft_fat_slots<9>(pl); break;
+        case 10: *slots = istft_fat_slots<10>(pl); break;
+        default: return false;
+    }
+    *tile_frames = kIstftRaggedTile;
+    return true;
+}
+
+template <int LOG2N, bool ONE>
+static hipError_t run_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const IstftUnit* d_units, long long n_units) {
+    static_assert(kFatFrames == kIstftRaggedTile, "zafx_execute_istft_ragged cuts the batch for the kernel's tile");
+    constexpr int LOG2E = default_log2e(LOG2N);
+    using F = FatCfg<LOG2N, LOG2E>;
+    constexpr bool can_vec = LOG2N >= 8;   // (as run_istft_fat)
+    const bool vec = can_vec && reinterpret_cast<uintptr_t>(spec) % 8 == 0;
+    constexpr int D1 = ONE ? 4 : 2, D2 = ONE ? 4 : 1;
+    auto kern = vec ? k_istft_ft16<LOG2N, LOG2E, can_vec ? D2 : D1, ONE, can_vec ? 2 : 1, false, true> : k_istft_ft16<LOG2N, LOG2E, D1, ONE, 1, false, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, F::SMEM); e != hipSuccess) return e;
+    pl.ran = "k_istft_ragged";
+    if (n_units <= 0) return hipSuccess;
+    const int W = 2 << LOG2N;
+    const int halo = (W + pl.H - 1) / pl.H - 1;
+    const float scale = 1.f / (4.f * (float)(1 << LOG2N) * pl.cola_gain);
+    const long long grid = std::min<long long>(n_units, istft_fat_slots<LOG2N>(pl));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(1024), F::SMEM, pl.stream, spec, pl.d_tw_pass, pl.d_tw_aux, y, 0, 0, pl.H, d_units, scale, 0, 0, 0,
+                       (int)n_units, halo);
+    return hipGetLastError();
+}
+
+hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const IstftUnit* d_units, long long n_units) {
+    if (!istft_ragged_native(pl) || n_units >= (1LL << 31) || reinterpret_cast<uintptr_t>(spec) % 4 != 0) return hipErrorInvalidValue;
+    const bool one = pl.prm.spectrum == ZAFX_SPECTRUM_ONE_SIDED;
+    switch (pl.log2nf) {
+#define X(L) \
+    case L: return one ? run_istft_ragged<L, true>(pl, spec, y, d_units, n_units) : run_istft_ragged<L, false>(pl, spec, y, d_units, n_units);
+        X(7) X(8) X(9) X(10)
+#undef X
     }
     return hipErrorInvalidValue;
 }

@@ -1,9 +1,9 @@
-// zafx_units.hpp -- a ragged batch cut into the units a RAGGED kernel form walks: k_center's (zafx_center.hip, zafx_execute_center_ragged) and
-// k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged).
+// zafx_units.hpp -- a ragged batch cut into the units a RAGGED kernel form walks: k_center's (zafx_center.hip, zafx_execute_center_ragged),
+// k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged) and k_istft_ft16's (zafx_stft.hip, zafx_execute_istft_ragged).
 //
-// A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, tiles of `tile_frames` frames for k_imdct.  One unit = pieces
-// [a, b) of one clip.  A unit that does not start its clip pays a fixed entry cost -- k_center a halo frame, k_imdct the tile in front of it
-// in carry-only mode -- and for that gives the same bits wherever it starts.
+// A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, tiles of `tile_frames` frames for k_imdct and k_istft_ft16.  One
+// unit = pieces [a, b) of one clip.  A unit that does not start its clip pays a fixed entry cost -- k_center a halo frame, k_imdct and
+// k_istft_ft16 the tile in front of it in carry-only mode -- and for that gives the same bits wherever it starts.
 //
 // The rule (cut_segments): one segment length S in pieces for the whole batch,
 //     S = max(floor, ceil(total pieces / (per_slot x workgroup slots)));
@@ -17,9 +17,10 @@
 // m (S - 1) <= n (S - m), and a cut clip has n >= S + 1, so from m (S - 1) <= (S + 1) (S - m), which is S >= 2 m - 1.  S = 2 m - 2 is too
 // small: a clip of 2 m - 1 pieces would be cut into m and m - 1.  So floor = 2 m - 1:
 //     k_center: m = 2 F - 1 blocks, the two tiles of F frames that are the floor of the equal-length launch: floor = 2 (2 F - 1) - 1 = 4 F - 3;
-//     k_imdct:  m = 2 tiles:                                                                               floor = 2 x 2 - 1 = 3.
+//     k_imdct:  m = 2 tiles:                                                                               floor = 2 x 2 - 1 = 3;
+//     k_istft_ft16: the carry-only tile transforms at most `halo` < 16 of its 16 frames, m = 2 tiles:      floor = 2 x 2 - 1 = 3.
 //
-// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,imdct}_units_emu.cpp and the host layer's sanitizer build.
+// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,imdct,istft}_units_emu.cpp and the host layer's sanitizer build.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -149,5 +150,46 @@ inline void imdct_fill_clip(ImdctUnit& u, long long in_off, long long out_off, l
 }
 
 inline std::vector<ImdctUnit> imdct_deal_table(const std::vector<ImdctUnit>& units, long long grid) { return deal_table(units, grid); }   // (the name before deal_table)
+
+// ---- k_istft_ft16: tiles.  One record of the device table.  The host deals the rounds (deal_table).
+struct IstftUnit {
+    long long in_off, out_off, out_len;   // the unit's CLIP: its block in the spectrum array (complex64 elements), its first sample in the output and its samples (floats)
+    int T, TP, tiles;                     // ... its frames, the pitch of its rows in frames, its tiles
+    int tile_a, tile_b, pad_;             // the unit: tiles [tile_a, tile_b) of that clip
+};
+static_assert(sizeof(IstftUnit) == 48 && alignof(IstftUnit) == 8, "IstftUnit: the layout the host writes");
+
+constexpr int kIstftUnitsPerSlot = 4;    // units per workgroup slot the segment length aims at (where the batch has the tiles): k_imdct's measured value, whose units pay the same entry cost; the ISTFT's own sweep (tools/ragged_rates.py --istft-k) has not been run yet: DESIGN.md 4.6
+constexpr int kIstftMinSegment = 3;      // floor of S
+
+// zaf.py istft: T frames at hop H overlap-add to (T - 1) H + W samples, W - H are trimmed at either end.  A spectrum whose output is empty has
+// no tiles and gives no unit.
+inline long long istft_out_len(long long frames, int W, int H) { return std::max<long long>(frames * H - (W - H), 0); }
+inline long long istft_tiles(long long frames, int tile_frames) { return frames <= 0 ? 0 : (frames + tile_frames - 1) / tile_frames; }
+
+inline long long istft_segment_tiles(const int64_t* frames, int64_t n_clips, int W, int H, int tile_frames, long long slots, int per_slot = kIstftUnitsPerSlot) {
+    const auto counts = piece_counts(frames, n_clips, [=](long long t) { return istft_out_len(t, W, H) > 0 ? istft_tiles(t, tile_frames) : 0LL; });
+    return segment_length(counts.data(), n_clips, kIstftMinSegment, slots, per_slot);
+}
+
+// The records carry the clip's index in `in_off` and nothing else of the clip: the caller, who knows the plan's pitches, fills the rest in.
+inline std::vector<IstftUnit> istft_cut_units(const int64_t* frames, int64_t n_clips, int W, int H, int tile_frames, long long slots,
+                                              int per_slot = kIstftUnitsPerSlot) {
+    const auto counts = piece_counts(frames, n_clips, [=](long long t) { return istft_out_len(t, W, H) > 0 ? istft_tiles(t, tile_frames) : 0LL; });
+    std::vector<IstftUnit> units;
+    for (const Segment& s : cut_segments(counts.data(), n_clips, kIstftMinSegment, slots, per_slot)) {
+        IstftUnit u{};
+        u.in_off = (long long)s.clip;
+        u.T = (int)frames[s.clip], u.tiles = (int)counts[(size_t)s.clip];
+        u.tile_a = (int)s.a, u.tile_b = (int)s.b;
+        units.push_back(u);
+    }
+    return units;
+}
+
+// ... rows of `pitch` complex64 elements at element `in_off`, the samples at float `out_off`.
+inline void istft_fill_clip(IstftUnit& u, long long in_off, long long out_off, long long pitch, int W, int H) {
+    u.in_off = in_off, u.out_off = out_off, u.out_len = istft_out_len(u.T, W, H), u.TP = (int)pitch;
+}
 
 }  // namespace zafx

@@ -82,6 +82,7 @@ SYMBOLS = {
     "zafx_execute_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _i64]),
     "zafx_execute_center_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
     "zafx_execute_imdct_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
+    "zafx_execute_istft_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
     "zafx_plan_clip_bytes": (_i, [_vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "zafx_run_host": (_i, [_vp, _vp, _vp, _i64, _i64, _i64]),
     "zafx_run_host_pcm": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i64]),

@@ -476,6 +476,33 @@ class Plan:
         _lib.check(_lib.load().zafx_execute_imdct_ragged(self.handle, d_coefs.ptr, _i64p(in_offsets), _i64p(frames), d_out.ptr, _i64p(out_offsets),
                                                          len(frames)), "zafx_execute_imdct_ragged")
 
+    def execute_istft_ragged(self, d_spec, in_offsets, frames, d_out, out_offsets):
+        """Enqueue the inverse STFT of spectra of different frame counts on the plan's stream (asynchronous; zafx_execute_istft_ragged,
+        inverse STFT plans only).  Block i starts at complex element in_offsets[i] of d_spec: W rows (W/2 + 1 for a one-sided plan) of
+        frames[i] bins at the pitch row_pitch(frames[i]) ("FT" -- the blocks an STFT plan's execute_ragged writes at the same row_align and
+        spectrum), or frames[i] x rows compact ("TF"); its max(frames[i] H - (W - H), 0) samples go to element out_offsets[i] of d_out.
+        Float32 "FT" plans of window 256 ... 2048 run as one launch (last_kernel: k_istft_ragged), the others as one execute per clip.
+        Output ranges that overlap are not detected."""
+        in_offsets, frames, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(frames, "frames"), _as_int64(out_offsets, "out_offsets")
+        if not len(in_offsets) == len(frames) == len(out_offsets):
+            raise ValueError("in_offsets, frames and out_offsets must have one entry per block")
+        if d_spec.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
+            raise ValueError(f"execute_istft_ragged takes {self.in_dtype} spectra and a {self.out_dtype} output buffer")
+        w, h = int(self.params.window_length), int(self.params.step_length)
+        rows = w // 2 + 1 if self.params.spectrum else w
+        if len(frames) and min(int(frames.min()), int(in_offsets.min()), int(out_offsets.min())) >= 0:   # (negative values: the library says so)
+            if self.layout == _lib.LAYOUT_FT:
+                a = max(self.row_align, 1)
+                ends = in_offsets + rows * ((frames + a - 1) // a * a)   # (whole rows: the 16-byte gather may read a row's pad columns)
+            else:
+                ends = in_offsets + frames * rows
+            if int(ends.max()) * d_spec.dtype.itemsize > d_spec.nbytes:
+                raise ValueError("a block reaches past the end of d_spec")
+            if int((out_offsets + np.maximum(frames * h - (w - h), 0)).max()) * d_out.dtype.itemsize > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_istft_ragged(self.handle, d_spec.ptr, _i64p(in_offsets), _i64p(frames), d_out.ptr, _i64p(out_offsets),
+                                                         len(frames)), "zafx_execute_istft_ragged")
+
     def sync(self):
         _lib.check(_lib.load().zafx_sync(self.handle), "zafx_sync")
 
@@ -1186,9 +1213,10 @@ def mel_mfcc_pcm_batch(pcm, window_function, step_length, mel_filterbank, number
 _RAGGED_ALIGN = 32   # elements between clip starts in a packed batch: 128 bytes of float32
 
 
-def _as_ragged_items(batch, ndim, name, items, noun, rule=None, empty_ok=False):
-    """A ragged batch -- a sequence of real arrays of rank `ndim` -- validated ahead of any device call: -> the list of arrays.  `name`, `items`
-    and `noun` are the words of the messages; rule(a): what is wrong with the shape of an item ("must ...") or None."""
+def _as_ragged_items(batch, ndim, name, items, noun, rule=None, empty_ok=False, complex_ok=False):
+    """A ragged batch -- a sequence of real arrays of rank `ndim` (complex_ok: real or complex ones) -- validated ahead of any device call: ->
+    the list of arrays.  `name`, `items` and `noun` are the words of the messages; rule(a): what is wrong with the shape of an item
+    ("must ...") or None."""
     if isinstance(batch, np.ndarray) and batch.dtype != object and batch.ndim <= ndim:
         raise ValueError(f"a {name} is a sequence of {items}, not one array")
     try:
@@ -1202,8 +1230,8 @@ def _as_ragged_items(batch, ndim, name, items, noun, rule=None, empty_ok=False):
         wrong = None
         if a.ndim != ndim:
             wrong = f"must be {ndim}-D, got {a.ndim}-D"
-        elif np.iscomplexobj(a) or a.dtype.kind not in "biuf":
-            wrong = "must be real"
+        elif a.dtype.kind not in ("biufc" if complex_ok else "biuf"):
+            wrong = "must be numeric" if complex_ok else "must be real"
         elif rule:
             wrong = rule(a)
         if wrong:
@@ -1265,9 +1293,10 @@ def _run_ragged(plan, clips):
     return [res[o:o + t * rows].reshape(t, rows) for o, t in zip(offs.tolist(), frames.tolist())]
 
 
-def _ragged_grid(plan, padded_plan):
-    """The plan of a ragged call in the reference layout: rows padded to whole 128-byte lines (as _line_grid), where the native ragged kernels run."""
-    return padded_plan(_line_elements(plan.out_dtype)) if plan.layout == _lib.LAYOUT_FT else plan
+def _ragged_grid(plan, padded_plan, inverse=False):
+    """The plan of a ragged call in the reference layout: rows padded to whole 128-byte lines (as _line_grid), where the native ragged kernels run.
+    inverse: the 2-D side is the plan's input."""
+    return padded_plan(_line_elements(plan.in_dtype if inverse else plan.out_dtype)) if plan.layout == _lib.LAYOUT_FT else plan
 
 
 def _as_f32_views(views, plan, f64):
@@ -1353,6 +1382,55 @@ def imdct_ragged(coefficients, window_function, layout="FT", device=0, f64=False
         else:
             packed[o:o + t * m].reshape(t, m)[...] = b
     res = _round_trip(plan, packed, n_out, lambda d_in, d_out: plan.execute_imdct_ragged(d_in, in_offsets, frames, d_out, out_offsets))
+    keep = out_len if lengths is None else lengths
+    return _as_f32_views([res[o:o + n] for o, n in zip(out_offsets.tolist(), keep.tolist())], plan, f64)
+
+
+def istft_ragged(spectra, window_function, step_length, layout="FT", device=0, onesided=False, f64=False, lengths=None):
+    """istft_batch of spectra of different frame counts in one call: a sequence of (W, T_i) complex arrays ["FT"] -- (W/2 + 1, T_i) with
+    onesided -- or their transposes ["TF"] -> a list of 1-D float32 arrays (float64 with f64) of max(T_i H - (W - H), 0) samples, as zaf.istft
+    gives them for that spectrum alone; with lengths=[N_i] each is cut to its first N_i samples (the clip stft_ragged was given).  The arrays
+    are views of one result buffer.  One upload, one execute, one download; the views stft_ragged returns are taken as they lie.  "FT" /
+    float32 at window 256 ... 2048 runs in one launch (k_istft_ragged); an empty list gives an empty list."""
+    w, h = _as_window(window_function, any_length=True), _as_step(step_length)
+    if h > len(w):
+        raise ValueError("step_length must not exceed window_length")
+    if onesided not in (False, True):
+        raise ValueError("istft takes a complex spectrum: onesided must be False or True")
+    _check_f64_window(len(w), bool(f64) or not _f32_window(len(w)))
+    _as_row_align(0, layout)   # (an unknown layout fails here)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    rows = len(w) // 2 + 1 if onesided else len(w)
+    axis = 0 if ft else 1
+    blocks = _as_ragged_items(spectra, 2, "ragged batch of spectra", "2-D blocks", "block", empty_ok=True, complex_ok=True,
+                              rule=lambda a: None if a.shape[axis] == rows else
+                              f"must have {'window_length/2 + 1' if onesided else 'window_length'} = {rows} spectrum rows, got shape {a.shape}")
+    frames = np.array([b.shape[1 - axis] for b in blocks], np.int64)
+    out_len = np.maximum(frames * h - (len(w) - h), 0)
+    if lengths is not None:
+        lengths = _as_lengths(lengths)
+        if len(lengths) != len(blocks):
+            raise ValueError("lengths must have one entry per block")
+        for i, (n, o) in enumerate(zip(lengths.tolist(), out_len.tolist())):
+            if n > o:
+                raise ValueError(f"lengths[{i}] = {n} exceeds the {o} samples block {i} gives")
+    if not blocks:
+        return []
+    plan = istft_plan(w, h, layout, device, onesided, f64)
+    plan = _ragged_grid(plan, lambda a: istft_plan(w, h, layout, device, onesided, f64, row_align=a), inverse=True)
+    # the blocks back to back at the plan's pitch (every block starts on a 128-byte line), the clips' samples on a grid of lines
+    a = max(plan.row_align, 1)
+    pitch = (frames + a - 1) // a * a if ft else np.full(len(blocks), rows, np.int64)
+    elems = rows * pitch if ft else frames * rows
+    in_offsets, n_in = _back_to_back(elems)
+    out_offsets, n_out = _back_to_back(out_len, _RAGGED_ALIGN)
+    packed = np.empty(max(n_in, 1), plan.in_dtype)   # (the pad columns are never used: they stay as they come)
+    for b, o, t, p in zip(blocks, in_offsets.tolist(), frames.tolist(), pitch.tolist()):
+        if ft:
+            packed[o:o + rows * p].reshape(rows, p)[:, :t] = b   # (rows of a view at any pitch: copied row by row)
+        else:
+            packed[o:o + t * rows].reshape(t, rows)[...] = b
+    res = _round_trip(plan, packed, n_out, lambda d_in, d_out: plan.execute_istft_ragged(d_in, in_offsets, frames, d_out, out_offsets))
     keep = out_len if lengths is None else lengths
     return _as_f32_views([res[o:o + n] for o, n in zip(out_offsets.tolist(), keep.tolist())], plan, f64)
 
