@@ -1,6 +1,6 @@
 """Ragged batches of the IMDCT on the host side (no GPU): the export and the binding of the new entry point, the validation that runs before
 any device call, the empty batch, and the cutter and the deal that turn a batch of coefficient blocks into the table k_imdct's RAGGED form walks
-(imdct_cut_units / deal_table, zafx_units.hpp, compiled by g++)."""
+(imdct_cut_units / deal_table, zafx_units.hpp; tests/host_emu/tile_units_emu.cpp compiled by g++)."""
 import os
 import subprocess
 
@@ -92,12 +92,12 @@ def test_imdct_ragged_of_no_blocks_is_no_arrays(no_device):
 # ------------------------------------------------------------------------------------------------------------------ the cutter and the deal
 @pytest.fixture(scope="module")
 def cutter(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("imdct_units") / "imdct_units_emu"
+    exe = tmp_path_factory.mktemp("imdct_units") / "tile_units_emu"
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "zaf-python_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_emu", "imdct_units_emu.cpp"), "-o", str(exe)], check=True)
+                    os.path.join(ROOT, "tests", "host_emu", "tile_units_emu.cpp"), "-o", str(exe)], check=True)
 
     def run(frames, slots, grid=None):
-        res = subprocess.run([str(exe), str(TILE), str(slots), str(slots if grid is None else grid), "-"], input=" ".join(str(t) for t in frames),
+        res = subprocess.run([str(exe), "imdct", str(TILE), str(slots), str(slots if grid is None else grid), "-"], input=" ".join(str(t) for t in frames),
                              capture_output=True, text=True)
         assert res.returncode == 0, res.stdout[-500:] + res.stderr[-500:]
         seg, grid_used, units, table = None, None, [], []

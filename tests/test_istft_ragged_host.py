@@ -1,6 +1,6 @@
 """Ragged batches of the inverse STFT on the host side (no GPU): the export and the binding of the new entry point, the validation that runs
 before any device call, the empty batch, and the cutter and the deal that turn a batch of spectra into the table k_istft_ft16's RAGGED form
-walks (istft_cut_units / deal_table, zafx_units.hpp, compiled by g++ -- once more under AddressSanitizer and UBSan as a plain program)."""
+walks (istft_cut_units / deal_table, zafx_units.hpp; tests/host_emu/tile_units_emu.cpp compiled by g++ -- once more under AddressSanitizer and UBSan as a plain program)."""
 import os
 import subprocess
 
@@ -108,7 +108,7 @@ def test_imdct_ragged_still_rejects_complex_blocks(no_device):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the cutter and the deal
-EMU = os.path.join(ROOT, "tests", "host_emu", "istft_units_emu.cpp")
+EMU = os.path.join(ROOT, "tests", "host_emu", "tile_units_emu.cpp")
 INC = os.path.join(ROOT, "zaf-python_amd", "csrc")
 
 
@@ -130,11 +130,11 @@ def parse(stdout):
 
 @pytest.fixture(scope="module")
 def cutter(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("istft_units") / "istft_units_emu"
+    exe = tmp_path_factory.mktemp("istft_units") / "tile_units_emu"
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", INC, EMU, "-o", str(exe)], check=True)
 
     def run(frames, slots, w=2048, h=1024, grid=None):
-        res = subprocess.run([str(exe), str(w), str(h), str(TILE), str(slots), str(slots if grid is None else grid), "-"],
+        res = subprocess.run([str(exe), "istft", str(w), str(h), str(TILE), str(slots), str(slots if grid is None else grid), "-"],
                              input=" ".join(str(t) for t in frames), capture_output=True, text=True)
         assert res.returncode == 0, res.stdout[-500:] + res.stderr[-500:]
         return parse(res.stdout)
@@ -232,14 +232,14 @@ def test_the_measured_batch_gives_every_slot_its_units(cutter):
 
 def test_cutter_under_the_sanitizers(tmp_path):
     """The same program built with AddressSanitizer and UBSan, run as it is (a plain host program)."""
-    exe = tmp_path / "istft_units_emu_san"
+    exe = tmp_path / "tile_units_emu_san"
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", INC, EMU, "-o", str(exe)],
                    check=True)
     for k, (what, frames, slots) in enumerate(random_batches()):
         if k % 4 and k > 4:
             continue
         w, h = [(2048, 1024), (512, 128), (1024, 768), (256, 129)][k % 4]
-        res = subprocess.run([str(exe), str(w), str(h), str(TILE), str(slots), str(slots), "-"], input=" ".join(str(t) for t in frames),
+        res = subprocess.run([str(exe), "istft", str(w), str(h), str(TILE), str(slots), str(slots), "-"], input=" ".join(str(t) for t in frames),
                              capture_output=True, text=True, timeout=120)
         assert res.returncode == 0 and "ERROR" not in res.stderr and "runtime error" not in res.stderr, (what, res.stderr[-800:])
         check_batch(what, frames, slots, w, h, parse(res.stdout))

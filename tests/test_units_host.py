@@ -1,11 +1,12 @@
 """The exact tables of the ragged launches (no GPU): the cutter's rule and the deal (zafx_units.hpp), restated here in a few lines of Python, held
-record for record against what the two host programs print -- center_units_emu for k_center's units, imdct_units_emu for k_imdct's units and its
-table in launch order.  test_center_ragged_host.py and test_imdct_ragged_host.py hold the invariants of a cut; this pins the cut itself, so a
-change to the shared cutter cannot re-balance one kernel's launch unnoticed."""
+record for record against what the two host programs print -- center_units_emu for k_center's units, tile_units_emu for k_imdct's and
+k_istft_ft16's units and their tables in launch order.  test_center_ragged_host.py, test_imdct_ragged_host.py and test_istft_ragged_host.py hold
+the invariants of a cut; this pins the cut itself, so a change to the shared cutter cannot re-balance one kernel's launch unnoticed."""
 import numpy as np
 
 from test_center_ragged_host import cutter as center_cutter, length_lists   # noqa: F401  (center_cutter: a fixture)
 from test_imdct_ragged_host import PER_SLOT, TILE, cutter as imdct_cutter, random_batches   # noqa: F401  (imdct_cutter: a fixture)
+from test_istft_ragged_host import PER_SLOT as ISTFT_PER_SLOT, TILE as ISTFT_TILE, cutter as istft_cutter, random_batches as istft_random_batches   # noqa: F401  (istft_cutter: a fixture)
 
 CENTER_PER_SLOT = 12   # kCenterUnitsPerSlot
 
@@ -79,6 +80,36 @@ def test_imdct_units_and_table_are_exactly_the_rule(imdct_cutter):
         assert (got_seg, got_grid) == (seg, grid), what
         assert got_units == units, what
         assert got_table == deal(units, grid, (-1, 0, 0, 0, 0)), what
+
+
+def istft_batches():
+    """(what, frames, slots, W, H); the random batches with the windows and hops test_istft_ragged_host.py gives them."""
+    for k, (what, frames, slots) in enumerate(istft_random_batches()):
+        yield (what, frames, slots) + [(2048, 1024), (512, 128), (1024, 768), (256, 129)][k % 4]
+    yield "only empty clips", [0, 1, 0, 1, 1], 8, 2048, 1024
+    yield "one clip of exactly S tiles, at the floor", [3 * ISTFT_TILE], 1, 2048, 1024
+    yield "one clip of S tiles + 1 frame, at the floor", [3 * ISTFT_TILE + 1], 1, 2048, 1024
+    yield "a backward last round with a single unit", [2] * 5, 4, 512, 256     # (hop W / 2: a spectrum of 2 frames still has output)
+    yield "a forward last round with a single unit", [2] * 9, 4, 512, 256
+    yield "frames but no output: no unit", [3] * 6, 4, 512, 128               # 3 H - (W - H) = 0
+
+
+def test_istft_units_and_table_are_exactly_the_rule(istft_cutter):
+    for what, frames, slots, w, h in istft_batches():
+        out = [max(t * h - (w - h), 0) for t in frames]
+        counts = [0 if t * h - (w - h) <= 0 else -(-t // ISTFT_TILE) for t in frames]
+        seg, segs = cut(counts, 3, slots, ISTFT_PER_SLOT)
+        units = [(clip, a, b, counts[clip], frames[clip], out[clip], -(-frames[clip] // 16) * 16) for clip, a, b in segs]
+        grid = min(slots, len(units))
+        got_seg, got_grid, got_lens, got_units, got_table = istft_cutter(frames, slots, w, h)
+        assert (got_seg, got_grid) == (seg, grid), what
+        assert got_lens == out, what
+        assert got_units == units, what
+        assert got_table == deal(units, grid, (-1, 0, 0, 0, 0, 0, 0)), what
+        if what.startswith("frames but no output"):
+            assert frames and min(frames) > 0 and got_units == [] and got_table == [], what
+        if "last round" in what:
+            assert len(units) % grid == 1 and (len(units) // grid) % 2 == ("backward" in what), what
 
 
 def test_the_added_batches_reach_the_edges_they_are_named_for():

@@ -1600,7 +1600,7 @@ static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& r
     });
 }
 
-// The table of zafx_execute_center_ragged / zafx_execute_imdct_ragged: the records as they are (none: nothing to upload)
+// The table of zafx_execute_center_ragged / zafx_execute_imdct_ragged / zafx_execute_istft_ragged: the records as they are (none: nothing to upload)
 extern "C++" {
 template <class T>
 static int upload_records(zafx_plan* pl, const std::vector<T>& recs) {
@@ -1728,50 +1728,81 @@ int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
                                                                               (long long)units.size()));
 }
 
+// What zafx_execute_imdct_ragged and zafx_execute_istft_ragged differ in: both cut their blocks into units of tiles (zafx_units.hpp) that the
+// RAGGED form of their kernel walks in one launch, and run one zafx_execute per block where that form does not apply.
+struct TileRagged {
+    const char* fn;                          // the entry point, as the messages name it
+    int kind;                                // the plans it takes ...
+    const char* wrong_kind;                  // ... and what it says of any other
+    const char* zero_gain;                   // what it says of a COLA gain of zero (null: the kind divides by none)
+    const char *env_native, *env_per_slot;   // the measurement switches (include/zafx.h) ...
+    int per_slot;                            // ... and what the second is preset to
+    bool (*plan_native)(const zafx_plan&);                    // the plan has the RAGGED form
+    bool (*block_native)(const zafx_plan&, int64_t frames);   // ... and a block of `frames` frames can go into its launch
+    bool (*launch_shape)(const zafx_plan&, int* tile_frames, long long* slots);
+    std::vector<zafx::TileUnit> (*cut)(const zafx_plan&, const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot);
+    long long (*out_len)(const zafx_plan&, long long frames);   // samples a block gives (none: the per-clip path passes over it)
+    int in_per_out;                          // bytes of an input element over those of an output element (a complex spectrum: 2)
+    hipError_t (*launch)(const zafx_plan&, const void* d_in, void* d_out, const zafx::TileUnit* d_units, long long n_units);
+};
+
+static int execute_tile_ragged(const TileRagged& k, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* frames, void* d_out,
+                               const int64_t* out_offsets, int64_t n_clips) {
+    const char* wrong_kind = !pl || pl->kind == k.kind ? nullptr : k.wrong_kind;
+    bool empty = false;
+    if (int rc = ragged_args(k.fn, pl, n_clips, wrong_kind, d_in, d_out, {frames, in_offsets, out_offsets}, "frame count", &empty)) return rc;
+    if (empty) return 0;
+    if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
+    if (k.zero_gain && pl->cola_gain == 0.f) return fail_msg(k.zero_gain);
+    bool native = k.plan_native(*pl) && reinterpret_cast<uintptr_t>(d_in) % 4 == 0 && env_on(k.env_native);
+    for (int64_t i = 0; native && i < n_clips; ++i) native = k.block_native(*pl, frames[i]);
+    ZAFX_HIP(hipSetDevice(pl->device));
+    int tile_frames = 0;
+    long long slots = 0;
+    if (native && k.launch_shape(*pl, &tile_frames, &slots)) {
+        std::vector<zafx::TileUnit> units = k.cut(*pl, frames, n_clips, tile_frames, slots, env_units_per_slot(k.env_per_slot, k.per_slot));
+        if (units.size() + (size_t)slots < (size_t)1 << 31) {   // (the table in launch order is at most one round longer)
+            for (zafx::TileUnit& u : units) {   // (the cutter leaves the clip's index in in_off)
+                const int64_t i = u.in_off;
+                zafx::tile_fill_clip(u, in_offsets[i], out_offsets[i], row_pitch(*pl, frames[i]), k.out_len(*pl, frames[i]));
+            }
+            // the launch's workgroups (the launchers: min(records, slots) -- the table is a whole number of rounds or shorter than one)
+            const std::vector<zafx::TileUnit> table = zafx::deal_table(units, std::min<long long>((long long)units.size(), slots));
+            if (int rc = upload_records(pl, table)) return rc;
+            return launch_rc(k.fn, k.launch(*pl, d_in, d_out, static_cast<const zafx::TileUnit*>(pl->d_ragged), (long long)table.size()));
+        }
+    }
+    // everything else: one zafx_execute per clip on the plan's stream (a block that gives no samples is passed over)
+    const int64_t eb = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        if (k.out_len(*pl, frames[i]) <= 0) continue;
+        if (int rc = zafx_execute(pl, (const char*)d_in + in_offsets[i] * k.in_per_out * eb, (char*)d_out + out_offsets[i] * eb, 1, frames[i])) return rc;
+    }
+    return 0;
+}
+
 // Ragged batches of the IMDCT: coefficient blocks of different frame counts.  The host cuts the blocks into units (imdct_cut_units), k_imdct's
 // RAGGED form walks them in one launch: float32, reference layout, W = 512 / 1024 / 2048, no Bluestein part, every block's pitch a multiple of
 // 4 floats (the 16-byte gather), every block below 2^32 bytes (a buffer descriptor per clip), units below 2^31.  Everything else -- the
 // frame-major layout, float64, W = 4096 / 8192, W <= 256, compact pitches off the 4-float grid -- runs one zafx_execute per clip on the plan's
-// stream and reports that kernel.  ZAFX_RAGGED_IMDCT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only,
-// include/zafx.h); ZAFX_IMDCT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+// stream and reports that kernel; the blocks it passes over are those of at most one frame (an MDCT window has W >= 4, so M (T - 1) - 1 > 0
+// from T = 2 on).  ZAFX_RAGGED_IMDCT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only, include/zafx.h);
+// ZAFX_IMDCT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+static const TileRagged kImdctRagged = {
+    "zafx_execute_imdct_ragged", ZAFX_IMDCT, "inverse MDCT plans (ZAFX_IMDCT) only (zafx_execute_ragged takes the forward kinds)", nullptr,
+    "ZAFX_RAGGED_IMDCT_NATIVE", "ZAFX_IMDCT_UNITS_PER_SLOT", zafx::kImdctUnitsPerSlot,
+    zafx::imdct_ragged_native,
+    [](const zafx_plan& pl, int64_t frames) { return row_pitch(pl, frames) % 4 == 0 && (long long)(pl.W / 2) * row_pitch(pl, frames) * 4 < (1LL << 32); },
+    zafx::imdct_launch_shape,
+    [](const zafx_plan&, const int64_t* frames, int64_t n, int tile_frames, long long slots, int per_slot) { return zafx::imdct_cut_units(frames, n, tile_frames, slots, per_slot); },
+    [](const zafx_plan& pl, long long frames) { return zafx::imdct_out_len(frames, pl.W / 2); },
+    1,
+    [](const zafx_plan& pl, const void* d_in, void* d_out, const zafx::TileUnit* tab, long long n) { return zafx::launch_imdct_ragged(pl, (const float*)d_in, (float*)d_out, tab, n); },
+};
+
 int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t* in_offsets, const int64_t* frames, void* d_out, const int64_t* out_offsets,
                               int64_t n_clips) {
-    const char* wrong_kind = !pl || pl->kind == ZAFX_IMDCT ? nullptr : "inverse MDCT plans (ZAFX_IMDCT) only (zafx_execute_ragged takes the forward kinds)";
-    bool empty = false;
-    if (int rc = ragged_args("zafx_execute_imdct_ragged", pl, n_clips, wrong_kind, d_coefs, d_out, {frames, in_offsets, out_offsets}, "frame count", &empty)) return rc;
-    if (empty) return 0;
-    if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
-    const int M = pl->W / 2;
-    bool native = zafx::imdct_ragged_native(*pl) && reinterpret_cast<uintptr_t>(d_coefs) % 4 == 0 && env_on("ZAFX_RAGGED_IMDCT_NATIVE");
-    for (int64_t i = 0; native && i < n_clips; ++i) {
-        const int64_t pitch = row_pitch(*pl, frames[i]);
-        native = pitch % 4 == 0 && (long long)M * pitch * 4 < (1LL << 32);
-    }
-    ZAFX_HIP(hipSetDevice(pl->device));
-    int tile_frames = 0;
-    long long slots = 0;
-    if (native && zafx::imdct_launch_shape(*pl, &tile_frames, &slots)) {
-        const int per_slot = env_units_per_slot("ZAFX_IMDCT_UNITS_PER_SLOT", zafx::kImdctUnitsPerSlot);
-        std::vector<zafx::ImdctUnit> units = zafx::imdct_cut_units(frames, n_clips, tile_frames, slots, per_slot);
-        if (units.size() + (size_t)slots < (size_t)1 << 31) {   // (the table in launch order is at most one round longer)
-            for (zafx::ImdctUnit& u : units) {   // (the cutter leaves the clip's index in in_off)
-                const int64_t i = u.in_off;
-                zafx::imdct_fill_clip(u, in_offsets[i], out_offsets[i], row_pitch(*pl, frames[i]), M);
-            }
-            // the launch's workgroups (launch_imdct_ragged: min(records, slots) -- the table is a whole number of rounds or shorter than one)
-            const std::vector<zafx::ImdctUnit> table = zafx::deal_table(units, std::min<long long>((long long)units.size(), slots));
-            if (int rc = upload_records(pl, table)) return rc;
-            return launch_rc("zafx_execute_imdct_ragged", zafx::launch_imdct_ragged(*pl, (const float*)d_coefs, (float*)d_out, static_cast<const zafx::ImdctUnit*>(pl->d_ragged),
-                                                                                  (long long)table.size()));
-        }
-    }
-    // everything else: one zafx_execute per clip on the plan's stream (a block of at most one frame has no samples)
-    const int64_t eb = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        if (frames[i] <= 1) continue;
-        if (int rc = zafx_execute(pl, (const char*)d_coefs + in_offsets[i] * eb, (char*)d_out + out_offsets[i] * eb, 1, frames[i])) return rc;
-    }
-    return 0;
+    return execute_tile_ragged(kImdctRagged, pl, d_coefs, in_offsets, frames, d_out, out_offsets, n_clips);
 }
 
 // Ragged batches of the inverse STFT: spectra of different frame counts.  The host cuts the blocks into units (istft_cut_units), k_istft_ft16's
@@ -1780,41 +1811,22 @@ int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t*
 // -- the frame-major layout, float64, W = 4096 / 8192, W < 256, Bluestein windows, smaller hops -- runs one zafx_execute per clip on the plan's
 // stream and reports that kernel.  ZAFX_RAGGED_ISTFT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only,
 // include/zafx.h); ZAFX_ISTFT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+static const TileRagged kIstftRagged = {
+    "zafx_execute_istft_ragged", ZAFX_ISTFT, "inverse STFT plans (ZAFX_ISTFT) only (zafx_execute_ragged takes the forward kinds)",
+    "istft: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)",
+    "ZAFX_RAGGED_ISTFT_NATIVE", "ZAFX_ISTFT_UNITS_PER_SLOT", zafx::kIstftUnitsPerSlot,
+    zafx::istft_ragged_native,
+    [](const zafx_plan& pl, int64_t frames) { return frames < (1LL << 28) && (long long)pl.W * row_pitch(pl, frames) * 8 < (1LL << 31); },
+    zafx::istft_launch_shape,
+    [](const zafx_plan& pl, const int64_t* frames, int64_t n, int tile_frames, long long slots, int per_slot) { return zafx::istft_cut_units(frames, n, pl.W, pl.H, tile_frames, slots, per_slot); },
+    [](const zafx_plan& pl, long long frames) { return zafx::istft_out_len(frames, pl.W, pl.H); },
+    2,
+    [](const zafx_plan& pl, const void* d_in, void* d_out, const zafx::TileUnit* tab, long long n) { return zafx::launch_istft_ragged(pl, (const float2*)d_in, (float*)d_out, tab, n); },
+};
+
 int zafx_execute_istft_ragged(zafx_plan* pl, const void* d_spec, const int64_t* in_offsets, const int64_t* frames, void* d_out, const int64_t* out_offsets,
                               int64_t n_clips) {
-    const char* wrong_kind = !pl || pl->kind == ZAFX_ISTFT ? nullptr : "inverse STFT plans (ZAFX_ISTFT) only (zafx_execute_ragged takes the forward kinds)";
-    bool empty = false;
-    if (int rc = ragged_args("zafx_execute_istft_ragged", pl, n_clips, wrong_kind, d_spec, d_out, {frames, in_offsets, out_offsets}, "frame count", &empty)) return rc;
-    if (empty) return 0;
-    if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
-    if (pl->cola_gain == 0.f) return fail_msg("istft: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
-    bool native = zafx::istft_ragged_native(*pl) && reinterpret_cast<uintptr_t>(d_spec) % 4 == 0 && env_on("ZAFX_RAGGED_ISTFT_NATIVE");
-    for (int64_t i = 0; native && i < n_clips; ++i) native = frames[i] < (1LL << 28) && (long long)pl->W * row_pitch(*pl, frames[i]) * 8 < (1LL << 31);
-    ZAFX_HIP(hipSetDevice(pl->device));
-    int tile_frames = 0;
-    long long slots = 0;
-    if (native && zafx::istft_launch_shape(*pl, &tile_frames, &slots)) {
-        const int per_slot = env_units_per_slot("ZAFX_ISTFT_UNITS_PER_SLOT", zafx::kIstftUnitsPerSlot);
-        std::vector<zafx::IstftUnit> units = zafx::istft_cut_units(frames, n_clips, pl->W, pl->H, tile_frames, slots, per_slot);
-        if (units.size() + (size_t)slots < (size_t)1 << 31) {   // (the table in launch order is at most one round longer)
-            for (zafx::IstftUnit& u : units) {   // (the cutter leaves the clip's index in in_off)
-                const int64_t i = u.in_off;
-                zafx::istft_fill_clip(u, in_offsets[i], out_offsets[i], row_pitch(*pl, frames[i]), pl->W, pl->H);
-            }
-            // the launch's workgroups (launch_istft_ragged: min(records, slots) -- the table is a whole number of rounds or shorter than one)
-            const std::vector<zafx::IstftUnit> table = zafx::deal_table(units, std::min<long long>((long long)units.size(), slots));
-            if (int rc = upload_records(pl, table)) return rc;
-            return launch_rc("zafx_execute_istft_ragged", zafx::launch_istft_ragged(*pl, (const float2*)d_spec, (float*)d_out, static_cast<const zafx::IstftUnit*>(pl->d_ragged),
-                                                                                  (long long)table.size()));
-        }
-    }
-    // everything else: one zafx_execute per clip on the plan's stream (a block that gives no samples is passed over)
-    const int64_t eb = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        if (zafx::istft_out_len(frames[i], pl->W, pl->H) <= 0) continue;
-        if (int rc = zafx_execute(pl, (const char*)d_spec + in_offsets[i] * 2 * eb, (char*)d_out + out_offsets[i] * eb, 1, frames[i])) return rc;
-    }
-    return 0;
+    return execute_tile_ragged(kIstftRagged, pl, d_spec, in_offsets, frames, d_out, out_offsets, n_clips);
 }
 
 int zafx_sync(zafx_plan* pl) {

@@ -11,6 +11,7 @@
 
 #include "../../include/zafx.h"
 #include "zafx_ragged_table.hpp"
+#include "zafx_units.hpp"
 #include "zafx_twiddle.hpp"
 
 namespace zafx {
@@ -258,7 +259,20 @@ __device__ __forceinline__ RgClip rg_clip_const(const RgClip* tab, int n_clips, 
     rc.T = r->T, rc.TP = r->TP, rc.first_tile = r->first_tile, rc.pad_ = 0;
     return rc;
 }
+// The record of unit `u` (uniform) of k_imdct's and k_istft_ft16's RAGGED forms in SGPRs: read through the constant address space, as
+// rg_clip_const -- nothing writes the table while a kernel runs.
+__device__ __forceinline__ TileUnit tile_unit_const(const TileUnit* tab, int u) {
+    typedef const __attribute__((address_space(4))) TileUnit* CRec;
+    const CRec r = (CRec)tab + u;
+    TileUnit rc;
+    rc.in_off = r->in_off, rc.out_off = r->out_off, rc.out_len = r->out_len;
+    rc.T = r->T, rc.TP = r->TP, rc.tiles = r->tiles, rc.tile_a = r->tile_a, rc.tile_b = r->tile_b, rc.pad_ = 0;
+    return rc;
+}
 #endif
+// The `out_len` argument of k_imdct and k_istft_ft16: the clips' output length, or (RAGGED) the table of unit records in the same 8-byte slot.
+template <bool RAGGED>
+using UnitTableArg = std::conditional_t<RAGGED, const TileUnit*, long long>;
 hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 bool spec2_ragged(const zafx_plan& pl);   // |X| / |X|^2 at W = 2048 on k_mel2 (what launch_spec2 takes)
@@ -334,19 +348,17 @@ hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out,
 // zafx_execute_imdct_ragged: k_imdct's RAGGED form (float32, reference layout, W = 512 / 1024 / 2048) -- the plans that have it, the tile
 // frames and the workgroup slots of its launch (what imdct_cut_units takes), and the launch on `n_units` records of the device table
 // (zafx_units.hpp; every block's pitch a multiple of 4 floats, every block below 2^32 bytes, coefs on 4 bytes, units below 2^31)
-struct ImdctUnit;
 constexpr int kImdctRaggedTile = 32;
 bool imdct_ragged_native(const zafx_plan& pl);
 bool imdct_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
-hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const ImdctUnit* d_units, long long n_units);
+hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const TileUnit* d_units, long long n_units);
 // zafx_execute_istft_ragged: k_istft_ft16's RAGGED form (float32, reference layout, W = 256 ... 2048, halo < 16) -- the plans that have it, the
 // tile frames and the workgroup slots of its launch (what istft_cut_units takes), and the launch on `n_units` records of the device table
 // (zafx_units.hpp; every block below 2^31 bytes, spec on 4 bytes, units below 2^31)
-struct IstftUnit;
 constexpr int kIstftRaggedTile = 16;
 bool istft_ragged_native(const zafx_plan& pl);
 bool istft_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
-hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const IstftUnit* d_units, long long n_units);
+hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const TileUnit* d_units, long long n_units);
 hipError_t launch_pcm_to_float(hipStream_t stream, const void* pcm, float* out, int64_t n_total, int n_channels, int sample_bytes);
 
 // names of the dominant kernels (what rocprofv3 --kernel-trace prints, prefix match)

@@ -1100,7 +1100,7 @@ __global__ __launch_bounds__(MdctBandCfg::NT) void k_mdct_ft32bc(
 // WINL: the window (4 NF floats) is staged in LDS; false (W = 4096): it is read from global memory -- the sweep form of the
 // overlap-add reads a thread's two window pairs once per tile -- which makes room for 16-frame tiles (64-byte gather runs) instead of 8.
 // RAGGED (zafx_execute_imdct_ragged): blocks of different frame counts.  The walk is the same; `out_len` carries the table of unit records
-// (ImdctLenArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (ImdctUnit,
+// (UnitTableArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (TileUnit,
 // zafx_units.hpp: the host cuts the batch): the base of the clip's block -- its buffer descriptor is built from it --, its frames, pitch
 // and tiles, the base and the length of its output and the unit's tiles come from the record (uniform: scalar loads into SGPRs) instead of
 // from unit / segs, unit % segs and the kernel's arguments (rg_pick).  T, TP, tiles, segs and seg_tiles are not used.  The gather runs one
@@ -1120,22 +1120,10 @@ __device__ __forceinline__ void store_pair_on_dword(float2* p, float2 v) {
     t.x = v.x, t.y = v.y;
     *reinterpret_cast<Float2OnDword*>(p) = t;
 }
-template <bool RAGGED>
-using ImdctLenArg = std::conditional_t<RAGGED, const ImdctUnit*, long long>;
-// The record of unit `u` (uniform) in SGPRs: read through the constant address space, as rg_clip_const -- nothing writes the table while a
-// kernel runs.
-__device__ __forceinline__ ImdctUnit imdct_unit_const(const ImdctUnit* tab, int u) {
-    typedef const __attribute__((address_space(4))) ImdctUnit* CRec;
-    const CRec r = (CRec)tab + u;
-    ImdctUnit rc;
-    rc.in_off = r->in_off, rc.out_off = r->out_off, rc.out_len = r->out_len;
-    rc.T = r->T, rc.TP = r->TP, rc.tiles = r->tiles, rc.tile_a = r->tile_a, rc.tile_b = r->tile_b, rc.pad_ = 0;
-    return rc;
-}
 template <int LOG2NF, int LOG2E, int FPB, int NSLOT, int LAYOUT, bool WINL = true, bool RAGGED = false>
 __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     const float* __restrict__ coefs, const float* __restrict__ win, const float2* __restrict__ twp,
-    const float2* __restrict__ tw8g, float* __restrict__ y, int T, int TP, ImdctLenArg<RAGGED> out_len, int tiles, int segs, int seg_tiles,
+    const float2* __restrict__ tw8g, float* __restrict__ y, int T, int TP, UnitTableArg<RAGGED> out_len, int tiles, int segs, int seg_tiles,
     int total_units) {
     using C = FftCfg<LOG2NF, LOG2E>;
     constexpr int NF = C::N, M = 2 * NF, P = C::P, E = C::E, NT = NSLOT * P;
@@ -1178,13 +1166,13 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     constexpr int KI = (NF % MSTEP == 0 && NF >= MSTEP) ? NF / MSTEP : 1;
     constexpr bool PRE = ZAFX_IMDCT_PREFETCH && LAYOUT == ZAFX_LAYOUT_FT && KI <= 4;
     static_assert(!RAGGED || PRE, "ragged batches: the gather runs one tile ahead");
-    [[maybe_unused]] ImdctUnit rc{}, rn{};   // RAGGED: the records of the workgroup's current and of its next unit (of rn the gather's fields alone stay live: in_off, T, TP, tile_a)
+    [[maybe_unused]] TileUnit rc{}, rn{};   // RAGGED: the records of the workgroup's current and of its next unit (of rn the gather's fields alone stay live: in_off, T, TP, tile_a)
     const int fs4 = (tid % LPR) * 4, mq4 = tid / LPR;
     float4 pre_re[KI], pre_im[KI];
     bool pre_ok = false;
     bool converted = false;   // pre_re / pre_im hold the pre-twiddled FFT inputs (convert_rows), not the raw rows
     // (ru: RAGGED, the record of unit_n; the clip's frames and pitch are the kernel's arguments otherwise -- rg_pick)
-    auto gather4 = [&](int unit_n, int tile_n, [[maybe_unused]] const ImdctUnit& ru, int part = 2) {   // rows of my 4 frames of tile_n of unit_n -> registers (part 0: the rows 2m, 1: the rows M-1-2m, 2: both)
+    auto gather4 = [&](int unit_n, int tile_n, [[maybe_unused]] const TileUnit& ru, int part = 2) {   // rows of my 4 frames of tile_n of unit_n -> registers (part 0: the rows 2m, 1: the rows M-1-2m, 2: both)
         pre_ok = false;
         converted = false;
         if (!vec4 || unit_n >= total_units) return;
@@ -1225,12 +1213,12 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
         }
         converted = true;
     };
-    auto first_tile = [&](int unit_n, [[maybe_unused]] const ImdctUnit& ru) {
+    auto first_tile = [&](int unit_n, [[maybe_unused]] const TileUnit& ru) {
         const int ta = RAGGED ? ru.tile_a : (unit_n % segs) * seg_tiles;
         return ta > 0 ? ta - 1 : 0;
     };
     if constexpr (RAGGED) {
-        if (blockIdx.x < total_units) rn = imdct_unit_const(out_len, blockIdx.x);
+        if (blockIdx.x < total_units) rn = tile_unit_const(out_len, blockIdx.x);
     }
     if constexpr (PRE) gather4(blockIdx.x, blockIdx.x < total_units ? first_tile(blockIdx.x, rn) : 0, rn);
     // Frame-major input: a frame's M coefficients are contiguous; lane p of the wave that owns a frame takes the pairs
@@ -1268,8 +1256,8 @@ __global__ __launch_bounds__(NSLOT * fft_threads(LOG2NF, LOG2E)) void k_imdct(
     PROF_INIT(g_prof_imdct);
     for (int unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
     if constexpr (RAGGED) {   // (the unit's first tile is in flight: requested through the record that was rn then)
-        rc = imdct_unit_const(out_len, unit);
-        if (unit + gridDim.x < total_units) rn = imdct_unit_const(out_len, unit + gridDim.x);
+        rc = tile_unit_const(out_len, unit);
+        if (unit + gridDim.x < total_units) rn = tile_unit_const(out_len, unit + gridDim.x);
     }
     const int clip = RAGGED ? 0 : unit / segs, seg = RAGGED ? 0 : unit % segs;
     const int tile_a = RAGGED ? rc.tile_a : seg * seg_tiles, tile_b = RAGGED ? rc.tile_b : min(tile_a + seg_tiles, tiles);
@@ -2053,7 +2041,7 @@ bool imdct_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots)
 }
 
 template <int LOG2NF>
-static hipError_t run_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const ImdctUnit* d_units, long long n_units) {
+static hipError_t run_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const TileUnit* d_units, long long n_units) {
     using G = ImdctRaggedCfg<LOG2NF>;
     auto kern = k_imdct<LOG2NF, G::LOG2E, G::FPB, G::NSLOT, ZAFX_LAYOUT_FT, G::WINL, true>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM); e != hipSuccess) return e;
@@ -2065,7 +2053,7 @@ static hipError_t run_imdct_ragged(const zafx_plan& pl, const float* coefs, floa
     return hipGetLastError();
 }
 
-hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const ImdctUnit* d_units, long long n_units) {
+hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const TileUnit* d_units, long long n_units) {
     if (!imdct_ragged_native(pl) || n_units >= (1LL << 31) || reinterpret_cast<uintptr_t>(coefs) % 4 != 0) return hipErrorInvalidValue;
     switch (pl.log2nf) {
         case 7: return run_imdct_ragged<7>(pl, coefs, y, d_units, n_units);

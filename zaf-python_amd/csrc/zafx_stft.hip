@@ -1932,7 +1932,7 @@ ZAFX_PROF_ARRAY(g_prof)
 // when the transforms are done spills as well, 1.82 -> 1.91 ms).  Barriers order LDS only (lds_barrier): the output stores of a tile are not
 // waited for.
 // RAGGED (zafx_execute_istft_ragged): spectra of different frame counts.  The walk is the same; `out_len` carries the table of unit records
-// (IstftLenArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (IstftUnit, zafx_units.hpp:
+// (UnitTableArg: the equal-length instantiations keep their kernel arguments byte for byte) and unit u is record u (TileUnit, zafx_units.hpp:
 // the host cuts the batch and deals the table in launch order, deal_table).  The base of the clip's block -- its buffer descriptor is built
 // from it and sized to the block, so a piece that runs past the block reads 0 --, its frames, pitch and tiles, the base and the length of
 // its output and the unit's tiles come from the record (uniform: scalar loads into SGPRs) instead of from unit / segs, unit % segs and the
@@ -1943,22 +1943,10 @@ ZAFX_PROF_ARRAY(g_prof)
 // Unit change: the carry belongs to one unit.  A unit's last tile has make_carry == false, which keeps it off the sweep form and makes both
 // other forms write 0 to every carry slot; a carry-only tile (write_out == false) never reads the carry and overwrites every slot; so a unit
 // starts on the zeros its predecessor left (or the ones written before the first tile) whatever clip that predecessor belonged to.
-template <bool RAGGED>
-using IstftLenArg = std::conditional_t<RAGGED, const IstftUnit*, long long>;
-// The record of unit `u` (uniform) in SGPRs: read through the constant address space, as rg_clip_const -- nothing writes the table while a
-// kernel runs.
-__device__ __forceinline__ IstftUnit istft_unit_const(const IstftUnit* tab, int u) {
-    typedef const __attribute__((address_space(4))) IstftUnit* CRec;
-    const CRec r = (CRec)tab + u;
-    IstftUnit rc;
-    rc.in_off = r->in_off, rc.out_off = r->out_off, rc.out_len = r->out_len;
-    rc.T = r->T, rc.TP = r->TP, rc.tiles = r->tiles, rc.tile_a = r->tile_a, rc.tile_b = r->tile_b, rc.pad_ = 0;
-    return rc;
-}
 template <int LOG2N, int LOG2E, int DEPTH, bool ONE, int FV, bool TF = false, bool RAGGED = false>
 __global__ __launch_bounds__(1024) void k_istft_ft16(
     const float2* __restrict__ spec, const float2* __restrict__ twp, const float2* __restrict__ tws,
-    float* __restrict__ y, int T, int TP, int hop, IstftLenArg<RAGGED> out_len, float scale, int tiles, int segs, int seg_tiles,
+    float* __restrict__ y, int T, int TP, int hop, UnitTableArg<RAGGED> out_len, float scale, int tiles, int segs, int seg_tiles,
     int total_units, int halo) {
     static_assert(!RAGGED || !TF, "ragged batches: the reference layout");
     using C = FftCfg<LOG2N, LOG2E>;
@@ -1993,7 +1981,7 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
         int unit, tile, tile_a, tile_b;
     };
     // (ru: RAGGED, the record of it.unit; the clip's frames, pitch and tiles are the kernel's arguments otherwise -- rg_pick)
-    auto enter = [&](Tile& it, [[maybe_unused]] const IstftUnit& ru) {   // first tile of it.unit (one before the segment when it needs a carry)
+    auto enter = [&](Tile& it, [[maybe_unused]] const TileUnit& ru) {   // first tile of it.unit (one before the segment when it needs a carry)
         if constexpr (RAGGED) {
             it.tile_a = ru.tile_a;
             it.tile_b = ru.tile_b;
@@ -2004,7 +1992,7 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
         }
         it.tile = it.tile_a > 0 ? it.tile_a - 1 : 0;
     };
-    auto my_frame_needed = [&](const Tile& it, [[maybe_unused]] const IstftUnit& ru) {   // (FV = 2: the pitch is even, so a pair's second frame is in the row; past T it is unused)
+    auto my_frame_needed = [&](const Tile& it, [[maybe_unused]] const TileUnit& ru) {   // (FV = 2: the pitch is even, so a pair's second frame is in the row; past T it is unused)
         return it.tile * FPB + fs < rg_pick<RAGGED>(ru.T, T) && fs + FV - 1 >= (it.tile < it.tile_a ? FPB - halo : 0);
     };
     // Rows k, W-k, N-k, N+k of sweep s (k = 0: rows 0, N/2, N, 3N/2) for my frame(s).  Buffer loads: the
@@ -2017,7 +2005,7 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
         int t_bytes;   // byte offset of the tile's first frame within a row
         int row_bytes, v_up, v_down;   // RAGGED: the clip's own (the launcher admits blocks below 2^31 bytes)
     };
-    auto source = [&](const Tile& it, [[maybe_unused]] const IstftUnit& ru) {
+    auto source = [&](const Tile& it, [[maybe_unused]] const TileUnit& ru) {
         Src src;
         if constexpr (RAGGED) {   // a descriptor per clip, sized to its block
             src.row_bytes = ru.TP * 8;
@@ -2106,12 +2094,12 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
     constexpr int PF = (!TF && FV == 2 && KI >= ZAFX_ISTFT_PF) ? ZAFX_ISTFT_PF : 0;   // sweeps of the next tile requested ahead
     RV pre[PF > 0 ? PF : 1][4];
     bool pre_ok = false;
-    [[maybe_unused]] IstftUnit rc{}, rn{};   // RAGGED: the records of cur's and of nxt's unit
+    [[maybe_unused]] TileUnit rc{}, rn{};   // RAGGED: the records of cur's and of nxt's unit
     Tile cur;
     cur.unit = blockIdx.x;
     if (cur.unit >= total_units) return;
     if constexpr (RAGGED) {
-        rc = istft_unit_const(out_len, cur.unit);
+        rc = tile_unit_const(out_len, cur.unit);
         if (rc.tile_b <= rc.tile_a) return;
     }
     enter(cur, rc);
@@ -2129,7 +2117,7 @@ __global__ __launch_bounds__(1024) void k_istft_ft16(
             nxt.unit += gridDim.x;
             if constexpr (RAGGED) {
                 if (nxt.unit < total_units) {
-                    rn = istft_unit_const(out_len, nxt.unit);
+                    rn = tile_unit_const(out_len, nxt.unit);
                     if (rn.tile_b <= rn.tile_a) nxt.unit = total_units;   // (no tiles: the filler of the table's last round)
                 }
             }
@@ -3586,7 +3574,7 @@ bool istft_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots)
 }
 
 template <int LOG2N, bool ONE>
-static hipError_t run_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const IstftUnit* d_units, long long n_units) {
+static hipError_t run_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const TileUnit* d_units, long long n_units) {
     static_assert(kFatFrames == kIstftRaggedTile, "zafx_execute_istft_ragged cuts the batch for the kernel's tile");
     constexpr int LOG2E = default_log2e(LOG2N);
     using F = FatCfg<LOG2N, LOG2E>;
@@ -3606,7 +3594,7 @@ static hipError_t run_istft_ragged(const zafx_plan& pl, const float2* spec, floa
     return hipGetLastError();
 }
 
-hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const IstftUnit* d_units, long long n_units) {
+hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const TileUnit* d_units, long long n_units) {
     if (!istft_ragged_native(pl) || n_units >= (1LL << 31) || reinterpret_cast<uintptr_t>(spec) % 4 != 0) return hipErrorInvalidValue;
     const bool one = pl.prm.spectrum == ZAFX_SPECTRUM_ONE_SIDED;
     switch (pl.log2nf) {

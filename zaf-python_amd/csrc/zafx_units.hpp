@@ -20,7 +20,7 @@
 //     k_imdct:  m = 2 tiles:                                                                               floor = 2 x 2 - 1 = 3;
 //     k_istft_ft16: the carry-only tile transforms at most `halo` < 16 of its 16 frames, m = 2 tiles:      floor = 2 x 2 - 1 = 3.
 //
-// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,imdct,istft}_units_emu.cpp and the host layer's sanitizer build.
+// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,tile}_units_emu.cpp and the host layer's sanitizer build.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -110,14 +110,35 @@ inline std::vector<CenterUnit> center_cut_units(const int64_t* lengths, const in
     return units;
 }
 
-// ---- k_imdct: tiles.  One record of the device table.  Offsets and lengths in floats.  The host deals the rounds (deal_table).
-struct ImdctUnit {
-    long long in_off, out_off, out_len;   // the unit's CLIP: its block in the coefficient array, its first sample in the output, its samples M (T - 1) - 1
-    int T, TP, tiles;                     // ... its frames, the pitch of its M rows, its tiles
+// ---- k_imdct and k_istft_ft16: tiles.  One record of the device table, the same for both kernels.  The host deals the rounds (deal_table).
+struct TileUnit {
+    long long in_off, out_off, out_len;   // the unit's CLIP: its block in the input array (k_imdct: floats; k_istft_ft16: complex64 elements), its first sample in the output and its samples (floats)
+    int T, TP, tiles;                     // ... its frames, the pitch of its rows in frames, its tiles
     int tile_a, tile_b, pad_;             // the unit: tiles [tile_a, tile_b) of that clip
 };
-static_assert(sizeof(ImdctUnit) == 48 && alignof(ImdctUnit) == 8, "ImdctUnit: the layout the host writes");
+static_assert(sizeof(TileUnit) == 48 && alignof(TileUnit) == 8, "TileUnit: the layout the host writes");
 
+// counts[i]: the tiles of clip i.  The records carry the clip's index in `in_off` and nothing else of the clip: the caller, who knows the plan's
+// pitches, fills the rest in (tile_fill_clip).
+inline std::vector<TileUnit> tile_cut_units(const std::vector<long long>& counts, const int64_t* frames, int64_t n_clips, long long floor, long long slots,
+                                            int per_slot) {
+    std::vector<TileUnit> units;
+    for (const Segment& s : cut_segments(counts.data(), n_clips, floor, slots, per_slot)) {
+        TileUnit u{};
+        u.in_off = (long long)s.clip;
+        u.T = (int)frames[s.clip], u.tiles = (int)counts[(size_t)s.clip];
+        u.tile_a = (int)s.a, u.tile_b = (int)s.b;
+        units.push_back(u);
+    }
+    return units;
+}
+
+// ... rows of `pitch` elements at element `in_off`, the `out_len` samples at float `out_off`.
+inline void tile_fill_clip(TileUnit& u, long long in_off, long long out_off, long long pitch, long long out_len) {
+    u.in_off = in_off, u.out_off = out_off, u.out_len = out_len, u.TP = (int)pitch;
+}
+
+// ---- k_imdct: tiles of 32 frames at W = 512, 1024, 2048.
 constexpr int kImdctUnitsPerSlot = 4;    // units per workgroup slot the segment length aims at (where the batch has the tiles); measured: DESIGN.md 4.6
 constexpr int kImdctMinSegment = 3;      // floor of S
 
@@ -125,41 +146,18 @@ constexpr int kImdctMinSegment = 3;      // floor of S
 inline long long imdct_tiles(long long frames, int tile_frames) { return frames <= 1 ? 0 : (frames + tile_frames - 1) / tile_frames; }
 inline long long imdct_out_len(long long frames, int M) { return std::max<long long>((long long)M * (frames - 1) - 1, 0); }
 
+inline std::vector<long long> imdct_tile_counts(const int64_t* frames, int64_t n_clips, int tile_frames) {
+    return piece_counts(frames, n_clips, [tile_frames](long long t) { return imdct_tiles(t, tile_frames); });
+}
 inline long long imdct_segment_tiles(const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot = kImdctUnitsPerSlot) {
-    const auto counts = piece_counts(frames, n_clips, [tile_frames](long long t) { return imdct_tiles(t, tile_frames); });
-    return segment_length(counts.data(), n_clips, kImdctMinSegment, slots, per_slot);
+    return segment_length(imdct_tile_counts(frames, n_clips, tile_frames).data(), n_clips, kImdctMinSegment, slots, per_slot);
+}
+inline std::vector<TileUnit> imdct_cut_units(const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot = kImdctUnitsPerSlot) {
+    return tile_cut_units(imdct_tile_counts(frames, n_clips, tile_frames), frames, n_clips, kImdctMinSegment, slots, per_slot);
 }
 
-// The records carry the clip's index in `in_off` and nothing else of the clip: the caller, who knows the plan's pitches, fills the rest in.
-inline std::vector<ImdctUnit> imdct_cut_units(const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot = kImdctUnitsPerSlot) {
-    const auto counts = piece_counts(frames, n_clips, [tile_frames](long long t) { return imdct_tiles(t, tile_frames); });
-    std::vector<ImdctUnit> units;
-    for (const Segment& s : cut_segments(counts.data(), n_clips, kImdctMinSegment, slots, per_slot)) {
-        ImdctUnit u{};
-        u.in_off = (long long)s.clip;
-        u.T = (int)frames[s.clip], u.tiles = (int)counts[(size_t)s.clip];
-        u.tile_a = (int)s.a, u.tile_b = (int)s.b;
-        units.push_back(u);
-    }
-    return units;
-}
-
-// ... M rows of `pitch` floats at float `in_off`, the samples at float `out_off`.
-inline void imdct_fill_clip(ImdctUnit& u, long long in_off, long long out_off, long long pitch, int M) {
-    u.in_off = in_off, u.out_off = out_off, u.out_len = imdct_out_len(u.T, M), u.TP = (int)pitch;
-}
-
-inline std::vector<ImdctUnit> imdct_deal_table(const std::vector<ImdctUnit>& units, long long grid) { return deal_table(units, grid); }   // (the name before deal_table)
-
-// ---- k_istft_ft16: tiles.  One record of the device table.  The host deals the rounds (deal_table).
-struct IstftUnit {
-    long long in_off, out_off, out_len;   // the unit's CLIP: its block in the spectrum array (complex64 elements), its first sample in the output and its samples (floats)
-    int T, TP, tiles;                     // ... its frames, the pitch of its rows in frames, its tiles
-    int tile_a, tile_b, pad_;             // the unit: tiles [tile_a, tile_b) of that clip
-};
-static_assert(sizeof(IstftUnit) == 48 && alignof(IstftUnit) == 8, "IstftUnit: the layout the host writes");
-
-constexpr int kIstftUnitsPerSlot = 4;    // units per workgroup slot the segment length aims at (where the batch has the tiles): k_imdct's measured value, whose units pay the same entry cost; the ISTFT's own sweep (tools/ragged_rates.py --istft-k) has not been run yet: DESIGN.md 4.6
+// ---- k_istft_ft16: tiles of 16 frames.
+constexpr int kIstftUnitsPerSlot = 4;    // units per workgroup slot the segment length aims at (where the batch has the tiles): k_imdct's measured value, whose units pay the same entry cost; the ISTFT's own sweep (tools/ragged_rates.py --istft-k) has not chosen it: DESIGN.md 4.6
 constexpr int kIstftMinSegment = 3;      // floor of S
 
 // zaf.py istft: T frames at hop H overlap-add to (T - 1) H + W samples, W - H are trimmed at either end.  A spectrum whose output is empty has
@@ -167,29 +165,15 @@ constexpr int kIstftMinSegment = 3;      // floor of S
 inline long long istft_out_len(long long frames, int W, int H) { return std::max<long long>(frames * H - (W - H), 0); }
 inline long long istft_tiles(long long frames, int tile_frames) { return frames <= 0 ? 0 : (frames + tile_frames - 1) / tile_frames; }
 
+inline std::vector<long long> istft_tile_counts(const int64_t* frames, int64_t n_clips, int W, int H, int tile_frames) {
+    return piece_counts(frames, n_clips, [=](long long t) { return istft_out_len(t, W, H) > 0 ? istft_tiles(t, tile_frames) : 0LL; });
+}
 inline long long istft_segment_tiles(const int64_t* frames, int64_t n_clips, int W, int H, int tile_frames, long long slots, int per_slot = kIstftUnitsPerSlot) {
-    const auto counts = piece_counts(frames, n_clips, [=](long long t) { return istft_out_len(t, W, H) > 0 ? istft_tiles(t, tile_frames) : 0LL; });
-    return segment_length(counts.data(), n_clips, kIstftMinSegment, slots, per_slot);
+    return segment_length(istft_tile_counts(frames, n_clips, W, H, tile_frames).data(), n_clips, kIstftMinSegment, slots, per_slot);
 }
-
-// The records carry the clip's index in `in_off` and nothing else of the clip: the caller, who knows the plan's pitches, fills the rest in.
-inline std::vector<IstftUnit> istft_cut_units(const int64_t* frames, int64_t n_clips, int W, int H, int tile_frames, long long slots,
-                                              int per_slot = kIstftUnitsPerSlot) {
-    const auto counts = piece_counts(frames, n_clips, [=](long long t) { return istft_out_len(t, W, H) > 0 ? istft_tiles(t, tile_frames) : 0LL; });
-    std::vector<IstftUnit> units;
-    for (const Segment& s : cut_segments(counts.data(), n_clips, kIstftMinSegment, slots, per_slot)) {
-        IstftUnit u{};
-        u.in_off = (long long)s.clip;
-        u.T = (int)frames[s.clip], u.tiles = (int)counts[(size_t)s.clip];
-        u.tile_a = (int)s.a, u.tile_b = (int)s.b;
-        units.push_back(u);
-    }
-    return units;
-}
-
-// ... rows of `pitch` complex64 elements at element `in_off`, the samples at float `out_off`.
-inline void istft_fill_clip(IstftUnit& u, long long in_off, long long out_off, long long pitch, int W, int H) {
-    u.in_off = in_off, u.out_off = out_off, u.out_len = istft_out_len(u.T, W, H), u.TP = (int)pitch;
+inline std::vector<TileUnit> istft_cut_units(const int64_t* frames, int64_t n_clips, int W, int H, int tile_frames, long long slots,
+                                             int per_slot = kIstftUnitsPerSlot) {
+    return tile_cut_units(istft_tile_counts(frames, n_clips, W, H, tile_frames), frames, n_clips, kIstftMinSegment, slots, per_slot);
 }
 
 }  // namespace zafx

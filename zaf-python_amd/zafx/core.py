@@ -457,24 +457,9 @@ class Plan:
         ("TF"); its max((W/2) (frames[i] - 1) - 1, 0) samples go to element out_offsets[i] of d_out.  Float32 "FT" plans of window 512, 1024
         and 2048 whose pitches are multiples of 4 run as one launch (last_kernel: k_imdct_ragged), the others as one execute per clip.  Output
         ranges that overlap are not detected."""
-        in_offsets, frames, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(frames, "frames"), _as_int64(out_offsets, "out_offsets")
-        if not len(in_offsets) == len(frames) == len(out_offsets):
-            raise ValueError("in_offsets, frames and out_offsets must have one entry per block")
-        if d_coefs.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
-            raise ValueError(f"execute_imdct_ragged takes {self.in_dtype} coefficients and a {self.out_dtype} output buffer")
         m = int(self.params.window_length) // 2
-        if len(frames) and min(int(frames.min()), int(in_offsets.min()), int(out_offsets.min())) >= 0:   # (negative values: the library says so)
-            if self.layout == _lib.LAYOUT_FT:
-                a = max(self.row_align, 1)
-                ends = in_offsets + m * ((frames + a - 1) // a * a)   # (whole rows: the 16-byte gather may read a row's pad columns)
-            else:
-                ends = in_offsets + frames * m
-            if int(ends.max()) * d_coefs.dtype.itemsize > d_coefs.nbytes:
-                raise ValueError("a block reaches past the end of d_coefs")
-            if int((out_offsets + np.maximum(m * (frames - 1) - 1, 0)).max()) * d_out.dtype.itemsize > d_out.nbytes:
-                raise ValueError("a clip's result reaches past the end of d_out")
-        _lib.check(_lib.load().zafx_execute_imdct_ragged(self.handle, d_coefs.ptr, _i64p(in_offsets), _i64p(frames), d_out.ptr, _i64p(out_offsets),
-                                                         len(frames)), "zafx_execute_imdct_ragged")
+        self._execute_blocks_ragged("zafx_execute_imdct_ragged", "coefficients", "d_coefs", m, lambda t: np.maximum(m * (t - 1) - 1, 0),
+                                    d_coefs, in_offsets, frames, d_out, out_offsets)
 
     def execute_istft_ragged(self, d_spec, in_offsets, frames, d_out, out_offsets):
         """Enqueue the inverse STFT of spectra of different frame counts on the plan's stream (asynchronous; zafx_execute_istft_ragged,
@@ -483,25 +468,29 @@ class Plan:
         spectrum), or frames[i] x rows compact ("TF"); its max(frames[i] H - (W - H), 0) samples go to element out_offsets[i] of d_out.
         Float32 "FT" plans of window 256 ... 2048 run as one launch (last_kernel: k_istft_ragged), the others as one execute per clip.
         Output ranges that overlap are not detected."""
+        w, h = int(self.params.window_length), int(self.params.step_length)
+        self._execute_blocks_ragged("zafx_execute_istft_ragged", "spectra", "d_spec", w // 2 + 1 if self.params.spectrum else w,
+                                    lambda t: np.maximum(t * h - (w - h), 0), d_spec, in_offsets, frames, d_out, out_offsets)
+
+    def _execute_blocks_ragged(self, entry, what, name, rows, out_len, d_in, in_offsets, frames, d_out, out_offsets):
+        """execute_imdct_ragged / execute_istft_ragged: the checks of the per-block arrays and of both buffers, then the library's `entry`.  A
+        block is `rows` rows; `out_len`: the samples blocks of these frame counts give; `what` and `name`: d_in in the messages."""
         in_offsets, frames, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(frames, "frames"), _as_int64(out_offsets, "out_offsets")
         if not len(in_offsets) == len(frames) == len(out_offsets):
             raise ValueError("in_offsets, frames and out_offsets must have one entry per block")
-        if d_spec.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
-            raise ValueError(f"execute_istft_ragged takes {self.in_dtype} spectra and a {self.out_dtype} output buffer")
-        w, h = int(self.params.window_length), int(self.params.step_length)
-        rows = w // 2 + 1 if self.params.spectrum else w
+        if d_in.dtype != self.in_dtype or d_out.dtype != self.out_dtype:
+            raise ValueError(f"{entry[5:]} takes {self.in_dtype} {what} and a {self.out_dtype} output buffer")
         if len(frames) and min(int(frames.min()), int(in_offsets.min()), int(out_offsets.min())) >= 0:   # (negative values: the library says so)
             if self.layout == _lib.LAYOUT_FT:
                 a = max(self.row_align, 1)
                 ends = in_offsets + rows * ((frames + a - 1) // a * a)   # (whole rows: the 16-byte gather may read a row's pad columns)
             else:
                 ends = in_offsets + frames * rows
-            if int(ends.max()) * d_spec.dtype.itemsize > d_spec.nbytes:
-                raise ValueError("a block reaches past the end of d_spec")
-            if int((out_offsets + np.maximum(frames * h - (w - h), 0)).max()) * d_out.dtype.itemsize > d_out.nbytes:
+            if int(ends.max()) * d_in.dtype.itemsize > d_in.nbytes:
+                raise ValueError(f"a block reaches past the end of {name}")
+            if int((out_offsets + out_len(frames)).max()) * d_out.dtype.itemsize > d_out.nbytes:
                 raise ValueError("a clip's result reaches past the end of d_out")
-        _lib.check(_lib.load().zafx_execute_istft_ragged(self.handle, d_spec.ptr, _i64p(in_offsets), _i64p(frames), d_out.ptr, _i64p(out_offsets),
-                                                         len(frames)), "zafx_execute_istft_ragged")
+        _lib.check(getattr(_lib.load(), entry)(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(frames), d_out.ptr, _i64p(out_offsets), len(frames)), entry)
 
     def sync(self):
         _lib.check(_lib.load().zafx_sync(self.handle), "zafx_sync")
@@ -1357,7 +1346,13 @@ def imdct_ragged(coefficients, window_function, layout="FT", device=0, f64=False
     blocks = _as_ragged_blocks(coefficients, m, layout)
     ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
     frames = np.array([b.shape[1 if ft else 0] for b in blocks], np.int64)
-    out_len = np.maximum(m * (frames - 1) - 1, 0)
+    return _blocks_ragged(blocks, m, frames, np.maximum(m * (frames - 1) - 1, 0), lengths, ft, f64, "execute_imdct_ragged",
+                          lambda a=0: mdct_plan(w, layout, device, inverse=True, row_align=a, f64=f64))
+
+
+def _blocks_ragged(blocks, rows, frames, out_len, lengths, ft, f64, execute, make_plan):
+    """imdct_ragged / istft_ragged behind their own checks: blocks of `rows` rows and frames[i] frames that give out_len[i] samples, through the
+    plan make_plan() (make_plan(row_align): the same on a grid of lines) and its method `execute`."""
     if lengths is not None:
         lengths = _as_lengths(lengths)
         if len(lengths) != len(blocks):
@@ -1367,21 +1362,20 @@ def imdct_ragged(coefficients, window_function, layout="FT", device=0, f64=False
                 raise ValueError(f"lengths[{i}] = {n} exceeds the {o} samples block {i} gives")
     if not blocks:
         return []
-    plan = mdct_plan(w, layout, device, inverse=True, f64=f64)
-    plan = _ragged_grid(plan, lambda a: mdct_plan(w, layout, device, inverse=True, row_align=a, f64=f64))
-    # the blocks back to back at the plan's pitch (every block starts on a 128-byte line), the clips' samples on the same grid
+    plan = _ragged_grid(make_plan(), make_plan, inverse=True)
+    # the blocks back to back at the plan's pitch (every block starts on a 128-byte line), the clips' samples on a grid of lines
     a = max(plan.row_align, 1)
-    pitch = (frames + a - 1) // a * a if ft else np.full(len(blocks), m, np.int64)
-    elems = m * pitch if ft else frames * m
+    pitch = (frames + a - 1) // a * a if ft else np.full(len(blocks), rows, np.int64)
+    elems = rows * pitch if ft else frames * rows
     in_offsets, n_in = _back_to_back(elems)
     out_offsets, n_out = _back_to_back(out_len, _RAGGED_ALIGN)
     packed = np.empty(max(n_in, 1), plan.in_dtype)   # (the pad columns are never used: they stay as they come)
     for b, o, t, p in zip(blocks, in_offsets.tolist(), frames.tolist(), pitch.tolist()):
         if ft:
-            packed[o:o + m * p].reshape(m, p)[:, :t] = b   # (rows of a view at any pitch: copied row by row)
+            packed[o:o + rows * p].reshape(rows, p)[:, :t] = b   # (rows of a view at any pitch: copied row by row)
         else:
-            packed[o:o + t * m].reshape(t, m)[...] = b
-    res = _round_trip(plan, packed, n_out, lambda d_in, d_out: plan.execute_imdct_ragged(d_in, in_offsets, frames, d_out, out_offsets))
+            packed[o:o + t * rows].reshape(t, rows)[...] = b
+    res = _round_trip(plan, packed, n_out, lambda d_in, d_out: getattr(plan, execute)(d_in, in_offsets, frames, d_out, out_offsets))
     keep = out_len if lengths is None else lengths
     return _as_f32_views([res[o:o + n] for o, n in zip(out_offsets.tolist(), keep.tolist())], plan, f64)
 
@@ -1406,33 +1400,8 @@ def istft_ragged(spectra, window_function, step_length, layout="FT", device=0, o
                               rule=lambda a: None if a.shape[axis] == rows else
                               f"must have {'window_length/2 + 1' if onesided else 'window_length'} = {rows} spectrum rows, got shape {a.shape}")
     frames = np.array([b.shape[1 - axis] for b in blocks], np.int64)
-    out_len = np.maximum(frames * h - (len(w) - h), 0)
-    if lengths is not None:
-        lengths = _as_lengths(lengths)
-        if len(lengths) != len(blocks):
-            raise ValueError("lengths must have one entry per block")
-        for i, (n, o) in enumerate(zip(lengths.tolist(), out_len.tolist())):
-            if n > o:
-                raise ValueError(f"lengths[{i}] = {n} exceeds the {o} samples block {i} gives")
-    if not blocks:
-        return []
-    plan = istft_plan(w, h, layout, device, onesided, f64)
-    plan = _ragged_grid(plan, lambda a: istft_plan(w, h, layout, device, onesided, f64, row_align=a), inverse=True)
-    # the blocks back to back at the plan's pitch (every block starts on a 128-byte line), the clips' samples on a grid of lines
-    a = max(plan.row_align, 1)
-    pitch = (frames + a - 1) // a * a if ft else np.full(len(blocks), rows, np.int64)
-    elems = rows * pitch if ft else frames * rows
-    in_offsets, n_in = _back_to_back(elems)
-    out_offsets, n_out = _back_to_back(out_len, _RAGGED_ALIGN)
-    packed = np.empty(max(n_in, 1), plan.in_dtype)   # (the pad columns are never used: they stay as they come)
-    for b, o, t, p in zip(blocks, in_offsets.tolist(), frames.tolist(), pitch.tolist()):
-        if ft:
-            packed[o:o + rows * p].reshape(rows, p)[:, :t] = b   # (rows of a view at any pitch: copied row by row)
-        else:
-            packed[o:o + t * rows].reshape(t, rows)[...] = b
-    res = _round_trip(plan, packed, n_out, lambda d_in, d_out: plan.execute_istft_ragged(d_in, in_offsets, frames, d_out, out_offsets))
-    keep = out_len if lengths is None else lengths
-    return _as_f32_views([res[o:o + n] for o, n in zip(out_offsets.tolist(), keep.tolist())], plan, f64)
+    return _blocks_ragged(blocks, rows, frames, np.maximum(frames * h - (len(w) - h), 0), lengths, ft, f64, "execute_istft_ragged",
+                          lambda a=0: istft_plan(w, h, layout, device, onesided, f64, row_align=a))
 
 
 def melspectrogram_ragged(clips, window_function, step_length, mel_filterbank, layout="FT", device=0, f64=False):
