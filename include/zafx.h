@@ -321,6 +321,29 @@ int zafx_pcm_to_float(zafx_plan* plan, const void* d_pcm, void* d_out, int64_t n
  * (every spectrum kind) and ZAFX_MDCT at window_length 2048 in the reference layout -- read 2 bytes per sample and channel of HBM instead of 6 + 4; every other
  * plan converts into a float32 staging array it owns (zafx_pcm_to_float) and runs zafx_execute on that.  Kinds as zafx_run_host_pcm. */
 int zafx_execute_pcm(zafx_plan* plan, const void* d_pcm, void* d_out, int64_t n_clips, int64_t n_frames, int n_channels, int sample_bytes);
+/* zafx_execute_ragged for integer PCM that is already on the device (asynchronous, on the plan's stream): clip i is lengths[i] SAMPLE FRAMES
+ * -- one int16 / int32 per channel: 2 bytes for int16 mono, the 4 bytes of one (left, right) pair for int16 stereo -- at sample frame
+ * in_offsets[i] of the interleaved array d_pcm; its result -- what zafx_execute_ragged writes for the normalised mono clip (zaf.py:1202, :65)
+ * -- goes to the block zafx_plan_ragged_layout(plan, lengths, ...) assigns, unchanged.  The two host arrays are copied before return.  Kinds:
+ * those of zafx_execute_ragged (float32 plans; ZAFX_DCT, center / sides and the inverse kinds are refused with a message).  Checked in this
+ * order: the plan, n_clips < 0, the kind, null arrays and pointers, negative lengths or offsets (with the clip's index), n_channels in [1, 64],
+ * sample_bytes 2 or 4, the plan's precision.
+ * ONE launch, the integers in the kernel's own loads (2 or 4 bytes per sample frame of HBM instead of 6 + 4; last kernel as the float
+ * launches: "k_mel2_ragged", "k_stft_ft16_ragged", "k_mdct_ft32_ragged"): int16, one or two channels, a float32 plan in ZAFX_LAYOUT_FT at
+ * window_length 2048 whose every clip has rows of whole 128-byte lines, d_out 128-byte aligned (as zafx_execute_ragged), and
+ *   - ZAFX_MEL / ZAFX_MFCC (with_mel included) where zafx_execute_ragged runs them on k_mel2, ZAFX_STFT of every spectrum kind: an even hop,
+ *     d_pcm 8-byte aligned, every in_offsets[i] even, every clip below 2^29 sample frames; lengths of either parity (every load of more than
+ *     one sample lies inside its clip, the tail goes sample by sample);
+ *   - ZAFX_MDCT: d_pcm 16-byte aligned, every offset and length a multiple of 4 sample frames, every clip below 2^28 sample frames.
+ * Everything else -- int32, other channel counts, other windows, odd hops or offsets, ZAFX_CQT / ZAFX_CHROMA, d_out off the line grid --
+ * converts first: the clip list is cut, in the order given, into groups of consecutive clips whose covered span of d_pcm (lowest offset
+ * to highest end) fits the plan's float32 staging array under the scratch budget (1 GiB; ZAFX_SCRATCH_BUDGET_MB) -- a group has at
+ * least one clip, and clips whose offsets are not increasing give smaller groups --, and every group is one zafx_pcm_to_float over its span and
+ * one zafx_execute_ragged: the bits of zafx_execute_ragged on the normalised samples.  ZAFX_RAGGED_PCM_NATIVE=0 in the environment keeps
+ * every batch on the convert-first route: a switch for measurements only (tools/ragged_rates.py --kinds mel_pcm,...), read at every call,
+ * not part of the interface. */
+int zafx_execute_ragged_pcm(zafx_plan* plan, const void* d_pcm, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
+                            int64_t n_clips, int n_channels, int sample_bytes);
 
 /* zafx_run_host for integer PCM: h_pcm = (n_clips, n_frames, n_channels) interleaved int16 / int32 as wavread's source
  * holds them (zaf.py:1187-1204); every chunk crosses PCIe as integers (2 or 4 bytes per sample and channel instead of 4 per

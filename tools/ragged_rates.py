@@ -1,6 +1,6 @@
 """Rates of ragged batches (zafx_execute_ragged) against the padded batch and an equal-length batch, in one process.
 
-    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct,istft] [--imdct-k 2,4,8,12,16,24]
+    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct,istft,mel_pcm,mfcc_pcm,stft_pcm,mdct_pcm] [--imdct-k 2,4,8,12,16,24]
                                  [--istft-k 2,4,8,12,16,24]
 
 Batch: 1024 clips, lengths uniform in 5-15 s at 44.1 kHz (even, so that the aligned loads apply as they do for the equal-length batch),
@@ -29,6 +29,15 @@ longest as one execute (k_istft_ft16); `per_clip`: the same execute_istft_ragged
 spectrum.  The three are read in turn, one launch of each per round, --reps rounds after three warm-up rounds (every shape and route warmed),
 median (min, max).  --istft-k: the ragged reading again for these units per workgroup slot (ZAFX_ISTFT_UNITS_PER_SLOT).  With `istft` among
 the kinds the tool exits with status 1 unless the one launch is faster than both alternatives for both spectrum kinds.
+
+The `mel_pcm`, `mfcc_pcm`, `stft_pcm` (two-sided) and `mdct_pcm` rows (not in the default kinds): the same 1024 clips as int16 mono that is
+already on the device, clip starts on multiples of 64 sample frames (`mdct_pcm`: lengths rounded down to multiples of 4).  `native`: one
+execute_ragged_pcm, the integers in the kernel's own loads; `convert_first`: the same call with ZAFX_RAGGED_PCM_NATIVE=0 in the environment --
+k_pcm_to_float over the packed array into the plan's staging (in groups under the scratch budget: two at this size), then execute_ragged, what
+the library's primitives amounted to before the RAGGED x PCM forms; `padded`: execute_pcm on the clips padded to the longest.  Whole-call
+times, the three read in turn, one launch of each per round, --reps rounds after three warm-up rounds, median (min, max).  With one of these
+among the kinds the tool exits with status 1 unless `native`'s median is below both alternatives' for every such kind (margin zero: the native
+launch moves strictly fewer bytes and is one launch fewer).
 """
 import argparse
 import json
@@ -285,6 +294,54 @@ def measure_istft(name, onesided, lengths, reps, sweep):
     return res
 
 
+PCM_KINDS = ("mel_pcm", "mfcc_pcm", "stft_pcm", "mdct_pcm")
+
+
+def measure_pcm(name, plan, lengths, reps):
+    """native / convert-first / padded of one kind on int16 mono that is already on the device (zafx_execute_ragged_pcm).  The gaps of the packed
+    array and the padding of the padded batch hold noise too: the kernels never read the former, and the latter costs what zeros cost."""
+    if name == "mdct_pcm":
+        lengths = lengths - lengths % 4
+    rng = np.random.default_rng(1)
+    slots = (lengths + 63) // 64 * 64
+    in_offsets = np.zeros(len(lengths), np.int64)
+    in_offsets[1:] = np.cumsum(slots)[:-1]
+    nmax = int(lengths.max())
+    packed = zafx.DeviceBuffer((int(slots.sum()),), np.int16)
+    packed.upload(rng.integers(-32768, 32767, packed.shape, dtype=np.int16, endpoint=True))
+    padded = zafx.DeviceBuffer((CLIPS, nmax), np.int16)
+    padded.upload(rng.integers(-32768, 32767, padded.shape, dtype=np.int16, endpoint=True))
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    out = zafx.DeviceBuffer((int(offs[-1]),), plan.out_dtype)
+    o = zafx.DeviceBuffer(plan.out_shape(CLIPS, nmax), plan.out_dtype)
+    call = lambda: plan.execute_ragged_pcm(packed, in_offsets, lengths, out, 1)   # noqa: E731
+    kernels = {}
+
+    def noting(key, launch):
+        def run():
+            launch()
+            kernels[key] = plan.last_kernel
+        return run
+    launches = {"native": noting("native", call), "convert_first": noting("convert_first", with_env("ZAFX_RAGGED_PCM_NATIVE", "0", call)),
+                "padded": noting("padded", lambda: plan.execute_pcm(padded, o, CLIPS, nmax, 1))}
+    res = {"samples": int(lengths.sum()), "longest": nmax}
+    res.update(timed_in_turn(plan, launches, reps))
+    for b in (packed, padded, out, o):
+        b.free()
+    for key in launches:
+        res[key + "_kernel"] = kernels[key]
+        res[key]["msamples_per_s"] = res["samples"] / (res[key]["median_ms"] * 1e3)
+    res["convert_first_over_native"] = res["convert_first"]["median_ms"] / res["native"]["median_ms"]
+    res["padded_over_native"] = res["padded"]["median_ms"] / res["native"]["median_ms"]
+    res["native_is_fastest"] = bool(res["native"]["median_ms"] < min(res["convert_first"]["median_ms"], res["padded"]["median_ms"]))
+    n, c, p = res["native"], res["convert_first"], res["padded"]
+    print(f"{name:9s} native {n['median_ms']:7.3f} ms ({n['min_ms']:.3f}-{n['max_ms']:.3f}) {n['msamples_per_s']:8.0f} Ms/s [{res['native_kernel']}] | "
+          f"convert first {c['median_ms']:7.3f} ms ({c['min_ms']:.3f}-{c['max_ms']:.3f}) [{res['convert_first_kernel']}] | padded {p['median_ms']:7.3f} ms "
+          f"({p['min_ms']:.3f}-{p['max_ms']:.3f}) [{res['padded_kernel']}] | convert first / native {res['convert_first_over_native']:.3f}, "
+          f"padded / native {res['padded_over_native']:.3f}", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -325,11 +382,21 @@ def main():
         for name, onesided in (("istft", False), ("istft_onesided", True)):
             result[name] = measure_istft(name, onesided, lengths, a.reps, sweep)
             fastest = fastest and result[name]["ragged_is_fastest"]
+    pcm_plans = {"mel_pcm": plans["mel"], "mfcc_pcm": plans["mfcc"], "stft_pcm": plans["stft"]}
+    pcm_fastest = True
+    for name in PCM_KINDS:
+        if name in kinds:
+            plan = pcm_plans[name] if name in pcm_plans else zafx.mdct_plan(zafx.kaiser_bessel_derived(W), row_align=32)
+            result[name] = measure_pcm(name, plan, lengths, a.reps)
+            pcm_fastest = pcm_fastest and result[name]["native_is_fastest"]
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
     if not fastest:
         print("the one launch of the ragged ISTFT is not faster than both alternatives")
+    if not pcm_fastest:
+        print("a ragged PCM kind's native launch is not faster than both alternatives (convert first, padded)")
+    if not (fastest and pcm_fastest):
         sys.exit(1)
 
 

@@ -1637,12 +1637,16 @@ static int ragged_args(const char* fn, const zafx_plan* pl, int64_t n_clips, con
     return 0;
 }
 
-int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
-    const char* wrong_kind = !pl || ragged_kind(pl->kind) ? nullptr : !is_center_kind(pl->kind) ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)"
-                             : "center / sides plans take clips of one length (ragged stereo batches are not implemented)";
-    bool empty = false;
-    if (int rc = ragged_args("zafx_execute_ragged", pl, n_clips, wrong_kind, d_in, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
-    if (empty) return 0;
+static const char* ragged_wrong_kind(const zafx_plan* pl) {
+    return !pl || ragged_kind(pl->kind) ? nullptr : !is_center_kind(pl->kind) ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)"
+                                        : "center / sides plans take clips of one length (ragged stereo batches are not implemented)";
+}
+
+// zafx_execute_ragged (pcm 0) and the one launch of zafx_execute_ragged_pcm (pcm 1 / 2: d_in holds int16 mono / stereo, offsets and lengths
+// count sample frames) behind their argument checks.  pcm != 0 runs a native launch or nothing: *launched tells which (there is no
+// per-clip path for integers; the caller converts first then).
+static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips,
+                                  int pcm, bool* launched) {
     // every clip's place in the output, frames and pitch; the 16-frame tiles of the batch
     std::vector<zafx::RgClip> recs((size_t)n_clips);
     const int64_t eb = out_elem_bytes(pl);
@@ -1655,12 +1659,25 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
         r = {in_offsets[i], lengths[i], out_off, (int)std::min<int64_t>(frames, INT32_MAX), (int)std::min<int64_t>(pitch, INT32_MAX), (int)std::min<int64_t>(tiles, INT32_MAX), 0};
         lines = lines && pl->layout == ZAFX_LAYOUT_FT && (pitch * eb) % 128 == 0 && pitch < INT32_MAX;
         short_clips = short_clips && lengths[i] < (1LL << 29);
-        even = even && in_offsets[i] % 2 == 0 && lengths[i] % 2 == 0;
+        // (int16: the fast paths of k_mel2 and k_stft_ft16 test s0 + W <= n per frame / last <= n per tile, so every multi-sample load lies
+        // inside the clip whatever its length's parity, and the tail goes sample by sample: the offsets alone must be even.  The float
+        // route keeps the condition on the lengths it was measured with.)
+        even = even && in_offsets[i] % 2 == 0 && (pcm != 0 || lengths[i] % 2 == 0);
         out_off += elems;
         tiles += (frames + 15) / 16;
-        if (tiles >= (1LL << 31)) return fail_msg("zafx_execute_ragged: batch too large for one launch (16-frame tiles >= 2^31)");
+        if (tiles >= (1LL << 31)) return fail_msg(std::string(fn) + ": batch too large for one launch (16-frame tiles >= 2^31)");
     }
     ZAFX_HIP(hipSetDevice(pl->device));
+    // (int16 in the loads: the launcher takes the calling thread's mode, as under zafx_execute_pcm; a launcher that did not read integers fails hard)
+    auto launch_pcm = [&](auto&& launch) {
+        zafx::set_pcm_mode(pcm);
+        const int rc = launch_rc(fn, launch());
+        const bool taken = zafx::pcm_mode_taken();
+        zafx::set_pcm_mode(0);
+        *launched = true;
+        if (rc == 0 && pcm != 0 && !taken) return fail_msg(std::string("internal: the ragged launch did not take the int16 input it was promised to (") + fn + ")");
+        return rc;
+    };
     // native, MDCT: k_mdct_ft32 in its RAGGED form (float32, reference layout, W = 512 / 1024 / 2048, every clip's rows whole 128-byte lines).
     // Its tiles are 32 frames: the records' first_tile and the batch's tile count are redone for them (the 16-frame count summed above
     // still bounds the call, as it does for every kind: 2^31 sixteen-frame tiles are 2^35 frames, no batch that fits a device).  Every
@@ -1676,21 +1693,30 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
             aligned = aligned && r.in_off % 4 == 0 && r.n_samples % 4 == 0;
             short_enough = short_enough && r.n_samples < (1LL << 28);
         }
-        if (tiles32 < (1LL << 31) && short_enough && env_on("ZAFX_RAGGED_MDCT_NATIVE")) {
+        // int16 (W = 2048 only): the 16-byte-piece form alone -- whole pieces inside or outside a clip, here 8 bytes mono and 16 stereo; the
+        // range check of a partial piece is not relied on.  Its switch is ZAFX_RAGGED_PCM_NATIVE, read by the caller.
+        const bool route = pcm != 0 ? aligned && pl->log2nf == 9 : env_on("ZAFX_RAGGED_MDCT_NATIVE");
+        if (tiles32 < (1LL << 31) && short_enough && route) {
             if (int rc = upload_ragged_table(pl, recs, tiles32, zafx::kMdctRaggedTile)) return rc;
-            return launch_rc("zafx_execute_ragged", zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged),
-                                                                             n_clips, tiles32, aligned));
+            return launch_pcm([&] {
+                return zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged), n_clips, tiles32, aligned);
+            });
         }
     }
+    if (pcm != 0 && pl->kind == ZAFX_MDCT) return 0;
     // native: k_stft_ft16 / k_mel2 in their RAGGED forms (float32, reference layout, every clip's rows whole 128-byte lines)
     const bool on_mel2 = zafx::mel_ragged_native(*pl);
     const bool native = pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->d_window && lines &&
                         (pl->kind == ZAFX_STFT ? zafx::stft_ragged_native(*pl) && (!on_mel2 || short_clips) : on_mel2 && short_clips);
+    // (int16: W = 2048 -- k_mel2's geometry, the complex kinds of k_stft_ft16 --, even hop and offsets, d_in on 8 bytes, clips below 2^29 frames)
+    if (pcm != 0 && !(native && pl->log2nf == 10 && even && short_clips)) return 0;
     if (native) {
         if (int rc = upload_ragged_table(pl, recs, tiles)) return rc;
         const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged);
-        return launch_rc("zafx_execute_ragged", pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
-                                                                      : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even));
+        return launch_pcm([&] {
+            return pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
+                                         : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even);
+        });
     }
     // everything else: one zafx_execute per clip on the plan's stream, into the same blocks
     const int64_t ib = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
@@ -1702,6 +1728,13 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
     const char* last = pl->ran.load(std::memory_order_acquire);
     pl->ran.store(per_clip_name(last ? last : pl->kernel_name.c_str()), std::memory_order_release);
     return 0;
+}
+
+int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
+    bool empty = false, launched = false;
+    if (int rc = ragged_args("zafx_execute_ragged", pl, n_clips, ragged_wrong_kind(pl), d_in, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    return execute_ragged_checked("zafx_execute_ragged", pl, d_in, in_offsets, lengths, d_out, n_clips, 0, &launched);
 }
 
 // Ragged stereo batches of the center / sides kinds: the host cuts the clips into units (center_cut_units), k_center's RAGGED form walks them.
@@ -1958,6 +1991,58 @@ int zafx_execute_pcm(zafx_plan* pl, const void* d_pcm, void* d_out, int64_t n_cl
     if (!d_pcm || !d_out) return fail_msg("null device pointer");
     ZAFX_HIP(hipSetDevice(pl->device));
     return execute_pcm(pl, d_pcm, d_out, n_clips, n_frames, n_channels, sample_bytes, nullptr);
+}
+
+// Ragged batches of integer PCM that is already on the device: clip i is lengths[i] sample frames at sample frame in_offsets[i] of d_pcm.
+// Route A, one launch: int16 mono / stereo into the RAGGED x PCM forms of k_mel2, k_stft_ft16 and k_mdct_ft32 at W = 2048 (the conditions are
+// execute_ragged_checked's; ZAFX_RAGGED_PCM_NATIVE=0 in the environment keeps a batch off it: measurements only).  Route B, everything else:
+// the clip list is cut into groups whose covered span of d_pcm converts into the plan's float32 staging array within the scratch budget
+// (rg_pcm_groups), and every group is one k_pcm_to_float over its span and one zafx_execute_ragged with the offsets rebased, into the blocks the
+// whole batch's layout gives its clips -- the bits of zafx_execute_ragged on the normalised samples by construction.
+int zafx_execute_ragged_pcm(zafx_plan* pl, const void* d_pcm, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips, int n_channels,
+                            int sample_bytes) {
+    const char* fn = "zafx_execute_ragged_pcm";
+    const char* wrong_kind = !pl ? nullptr : pl->kind == ZAFX_DCT ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma): a DCT plan takes zafx_execute_pcm"
+                                                                  : ragged_wrong_kind(pl);
+    bool empty = false;
+    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_pcm, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
+    if (n_channels < 1 || n_channels > 64) return fail_msg("n_channels must be in [1, 64]");
+    if (sample_bytes != 2 && sample_bytes != 4) return fail_msg("sample_bytes must be 2 (int16) or 4 (int32)");
+    if (pl->prm.precision != ZAFX_PRECISION_F32) return fail_msg("PCM ingest feeds the float32 plans");
+    if (empty) return 0;
+    if (sample_bytes == 2 && n_channels <= 2 && env_on("ZAFX_RAGGED_PCM_NATIVE")) {
+        bool launched = false;
+        const int rc = execute_ragged_checked(fn, pl, d_pcm, in_offsets, lengths, d_out, n_clips, n_channels, &launched);
+        if (rc || launched) return rc;
+    }
+    ZAFX_HIP(hipSetDevice(pl->device));
+    const int64_t budget_frames = zafx::scratch_clips_per_chunk(INT64_MAX, 1, 1, sizeof(float));   // (the budget in float32 samples)
+    const std::vector<zafx::RgPcmGroup> groups = zafx::rg_pcm_groups(in_offsets, lengths, n_clips, budget_frames);
+    long long span = 1;
+    for (const zafx::RgPcmGroup& g : groups) span = std::max(span, g.hi - g.lo);
+    if (span > INT64_MAX / 4) return fail_msg(std::string(fn) + ": a clip reaches past 2^61 sample frames");
+    if (pl->pcm_float_bytes < (size_t)span * 4) {   // (grow-only, once per call: the largest group's span)
+        ZAFX_HIP(hipStreamSynchronize(pl->stream));
+        if (pl->d_pcm_float) ZAFX_HIP(hipFree(pl->d_pcm_float));
+        pl->d_pcm_float = nullptr, pl->pcm_float_bytes = 0;
+        ZAFX_HIP(hipMalloc(&pl->d_pcm_float, (size_t)span * 4));
+        pl->pcm_float_bytes = (size_t)span * 4;
+    }
+    const int64_t eb = out_elem_bytes(pl), frame_b = (int64_t)n_channels * sample_bytes;
+    std::vector<int64_t> rebased;
+    int64_t out_off = 0;   // the group's first block in the whole batch's layout (the blocks lie back to back)
+    for (const zafx::RgPcmGroup& g : groups) {   // (one stream: a group's conversion waits for the transform of the group before it)
+        if (g.hi > g.lo) ZAFX_HIP(launch_pcm_to_float(pl->stream, (const char*)d_pcm + g.lo * frame_b, (float*)pl->d_pcm_float, g.hi - g.lo, n_channels, sample_bytes));
+        rebased.assign((size_t)g.count, 0);
+        for (long long i = 0; i < g.count; ++i) rebased[(size_t)i] = in_offsets[g.first + i] - g.lo;
+        if (int rc = zafx_execute_ragged(pl, pl->d_pcm_float, rebased.data(), lengths + g.first, (char*)d_out + out_off * eb, g.count)) return rc;
+        for (long long i = 0; i < g.count; ++i) {
+            int64_t elems = 0, frames = 0, pitch = 0;
+            if (int rc = ragged_block(pl, lengths[g.first + i], &elems, &frames, &pitch)) return rc;
+            out_off += elems;
+        }
+    }
+    return 0;
 }
 
 static int run_host_impl(zafx_plan* pl, const void* h_in, void* h_out, int64_t n_clips, int64_t n_in, int64_t chunk_clips, int pcm_channels, int pcm_bytes) {

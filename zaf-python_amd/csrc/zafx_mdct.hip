@@ -163,13 +163,15 @@ struct MdctPCfg {
 // tile ahead and that tile may belong to another clip, so two records are live: rc, the tile being transformed and stored, and rn, the next
 // one, looked up at the head of the tile -- its round trip passes under the first frame -- and handed to fetch().  The zero padding (the clip's
 // own buffer descriptor, in 16-byte or in 4-byte loads), fold, transform and store phase are the same code.  The launcher admits rows of whole 128-byte lines only.
+// RAGGED x PCM (zafx_execute_ragged_pcm; W = 2048, ALIGNED): the record's in_off and n_samples count sample frames -- 2 bytes mono, 4 stereo --, so
+// PCM 2 indexes as the float form does and PCM 1 takes its short* base and the descriptor's range (2 n_samples bytes) from the record fetch() is handed.
 template <int LOG2NF, int LOG2E, bool ALIGNED, int NSLOT, bool TFOUT = false, bool CARRY = false, int PCM = 0, bool RAGGED = false>
 __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
     const float* __restrict__ x, const float4* __restrict__ wfold, const float2* __restrict__ twp,
     const float2* __restrict__ tw8, float* __restrict__ out, SamplesArg<RAGGED> n_samples, int T, int TP, int tiles, int total_tiles,
     int segs = 1, int seg_tiles = 0, int units = 0) {
     static_assert(!(CARRY && TFOUT), "the carry form is for the reference layout");
-    static_assert(!RAGGED || (!TFOUT && !CARRY && PCM == 0), "ragged batches: float32 samples, reference layout, rows of whole lines");
+    static_assert(!RAGGED || (!TFOUT && !CARRY && (PCM == 0 || (LOG2NF == 9 && ALIGNED))), "ragged batches: reference layout, rows of whole lines; int16 samples at W = 2048 in the 16-byte-piece form");
     using C = FftCfg<LOG2NF, LOG2E>;
     constexpr int NF = C::N, M = 2 * NF, P = C::P, E = C::E, FPB = kMdctTile, NT = NSLOT * P;
     constexpr int FPW = FPB / NSLOT;                    // frames per wave and tile
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(NSLOT * 64) void k_mdct_ft32(
             // path (n_samples and every piece's first sample are multiples of 4: a piece is inside or outside as a whole;
             // offsets are 32-bit and wrap, a negative one is a huge unsigned one).  Four address registers per frame.
             if constexpr (PCM == 1) {   // four int16 samples = 8 bytes per piece
-                const __amdgpu_buffer_rsrc_t rs = make_rsrc(reinterpret_cast<const short*>(x) + (long long)clip * rg_pick<RAGGED>(fr.n_samples, n_samples),
+                const __amdgpu_buffer_rsrc_t rs = make_rsrc(reinterpret_cast<const short*>(x) + (RAGGED ? fr.in_off : (long long)clip * rg_pick<RAGGED>(fr.n_samples, n_samples)),
                                                             (unsigned)(rg_pick<RAGGED>(fr.n_samples, n_samples) * 2));
                 const int b = (int)s0 * 2 + 8 * p, rb = (int)s0 * 2 - 8 * p - 8 * (UPL - 1) * P;
                 auto piece = [&](int off) {
@@ -1620,6 +1622,12 @@ static hipError_t run_mdct_p_ragged(const zafx_plan& pl, const float* x, float* 
     constexpr int LOG2E = default_log2e(LOG2NF);
     using G = MdctPCfg<LOG2NF, LOG2E>;
     auto kern = k_mdct_ft32<LOG2NF, LOG2E, ALIGNED, G::NSLOT, false, false, 0, true>;
+    // (zafx_execute_ragged_pcm: int16 in the loads, the records count sample frames; it vouches for W = 2048 and `aligned`, here in frames)
+    if constexpr (LOG2NF == 9 && ALIGNED) {
+        const int pcm = take_pcm_mode();
+        if (pcm == 1) kern = k_mdct_ft32<LOG2NF, LOG2E, true, G::NSLOT, false, false, 1, true>;
+        if (pcm == 2) kern = k_mdct_ft32<LOG2NF, LOG2E, true, G::NSLOT, false, false, 2, true>;
+    }
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM); e != hipSuccess) return e;
     if (total_tiles <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / G::SMEM);   // (the grid of run_mdct_p)

@@ -594,12 +594,12 @@ constexpr int kMel2DualPitch = 1057;   // float2 slots per frame buffer of the o
 // 2^-15 (2^-16: the mean of two channels) is a power of two and rides in the window.
 // RAGGED (zafx_execute_ragged): clips of different lengths, as k_stft_ft16's RAGGED form -- `n_samples` carries the batch's table, `tiles` the
 // number of clips; a tile's clip gives its samples (and the base of the aligned form's buffer descriptor), frames, row pitch and output base.
+// RAGGED x PCM (zafx_execute_ragged_pcm): the record's in_off and n_samples count sample frames -- 2 bytes mono, the 4 bytes of a pair stereo.
 template <bool ALIGNED, int MODE, int PCM = 0, bool RAGGED = false>
 __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, const float* __restrict__ win, const float2* __restrict__ twp,
                                                    const float2* __restrict__ tws, const float* __restrict__ fb_pack, const int4* __restrict__ fb_whole,
                                                    const float* __restrict__ dct2, const int* __restrict__ owner2, float* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop,
                                                    int T, int TP, int tiles, int total_tiles, int n_filters, int n_coefs, int layout) {
-    static_assert(!RAGGED || PCM == 0, "ragged batches: float32 samples");
     // samples, frames and row pitch of the tile's clip: the kernel's arguments, or (RAGGED) the fields of the tile's record rc -- read where
     // they are used, as the arguments always were (rg_pick)
 #define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(1024, 1) void k_mel2(const float* __restrict__ x, c
         const long long s0 = (long long)t * hop - N;
         if constexpr (PCM == 1) {
             // int16 mono: a point (two samples) is one dword; xr[2 i] = the dwords of the points n, n + 1 of load i (xr[2 i + 1] is not used)
-            const short* xc = reinterpret_cast<const short*>(x) + (long long)clip * CLIP_N;
+            const short* xc = reinterpret_cast<const short*>(x) + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);   // (RAGGED: offsets and lengths count sample frames)
             if (ALIGNED && t < CLIP_T && s0 >= 0 && s0 + W <= CLIP_N) {   // interior frame (uniform)
                 frx = make_rsrc(xc, (unsigned)std::min<long long>(CLIP_N * 2, 0xfffffffcLL));
                 const int fvoff = ((int)s0 + 2 * (p & ~1)) * 2 + (p & 1) * (E / 2 * P * 4);
@@ -1227,14 +1227,16 @@ bool mel_ragged_native(const zafx_plan& pl) {
     return pl.fb.whole_ok && pl.fb.n_waves == 16 && (pl.kind == ZAFX_MEL || pl.dct.dct2_ok);
 }
 
-template <bool ALIGNED>
+// PCM 1 / 2 (zafx_execute_ragged_pcm, int16 mono / stereo): the records' in_off and n_samples count sample frames -- 2 bytes mono, the 4 bytes of
+// one (left, right) pair stereo, which is why PCM 2 indexes exactly as the float form does.
+template <bool ALIGNED, int PCM = 0>
 static auto mel2_ragged_kernel(int mode) {
     switch (mode) {
-        case 1: return k_mel2<ALIGNED, 1, 0, true>;
-        case 2: return k_mel2<ALIGNED, 2, 0, true>;
-        case 3: return k_mel2<ALIGNED, 3, 0, true>;
-        case 4: return k_mel2<false, 4, 0, true>;   // (the aligned one-pass form spills to scratch -- as its equal-length twin does --, this one does not)
-        default: return k_mel2<ALIGNED, 0, 0, true>;
+        case 1: return k_mel2<ALIGNED, 1, PCM, true>;
+        case 2: return k_mel2<ALIGNED, 2, PCM, true>;
+        case 3: return k_mel2<ALIGNED, 3, PCM, true>;
+        case 4: return k_mel2<false, 4, PCM, true>;   // (the aligned one-pass form spills to scratch -- as its equal-length twin does --, this one does not)
+        default: return k_mel2<ALIGNED, 0, PCM, true>;
     }
 }
 
@@ -1243,6 +1245,10 @@ hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, co
     const bool spec = pl.kind == ZAFX_STFT, mfcc = pl.kind == ZAFX_MFCC, dual = mfcc && pl.prm.with_mel;
     const int mode = spec ? (pl.prm.spectrum == ZAFX_SPECTRUM_POWER ? 3 : 2) : dual ? 4 : mfcc ? 1 : 0;
     auto k2 = aligned ? mel2_ragged_kernel<true>(mode) : mel2_ragged_kernel<false>(mode);
+    const int pcm = take_pcm_mode();   // (zafx_execute_ragged_pcm: int16 in the loads; it vouches for `aligned` -- even hop and offsets, d_pcm on 8 bytes)
+    if (pcm != 0 && !aligned) return hipErrorInvalidValue;
+    if (pcm == 1) k2 = mel2_ragged_kernel<true, 1>(mode);
+    if (pcm == 2) k2 = mel2_ragged_kernel<true, 2>(mode);
     const size_t smem = (size_t)(16 * (dual ? kMel2DualPitch : C::PITCH) + C::TW + C::N + C::N / 2 + 1) * 8 + (dual ? 2 : 1) * kMel2Slots * 1024;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k2), pl.device, smem); e != hipSuccess) return e;
     if (total_tiles <= 0) return hipSuccess;

@@ -11,6 +11,7 @@
 #include <climits>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace zafx {
 
@@ -41,6 +42,31 @@ inline void rg_fill_clip_of(const RgClip* recs, size_t n_clips, int tile_frames,
         const long long tiles = rg_tiles(recs[c].T, tile_frames);
         for (long long j = 0; j < tiles; ++j) clip_of[recs[c].first_tile + j] = (int)c;
     }
+}
+
+// zafx_execute_ragged_pcm, the batches no kernel reads as integers: the clip list cut, in the order given, into groups of consecutive clips
+// whose covered span of the integer array -- sample frames [lo, hi): lowest offset to highest end -- converts into a float32 staging array of
+// `budget_frames` samples.  A group has at least one clip, so a clip longer than the budget is a group of its own; clips whose offsets go
+// back and forth cover more than the sum of their lengths and are cut into smaller groups, one clip each in the worst case.  Clip i of a
+// group lies at offsets[i] - lo of the group's staging copy.  (An end past INT64_MAX saturates: such a clip is a group of its own.)
+struct RgPcmGroup {
+    long long first, count, lo, hi;
+};
+
+inline std::vector<RgPcmGroup> rg_pcm_groups(const int64_t* offsets, const int64_t* lengths, long long n_clips, long long budget_frames) {
+    std::vector<RgPcmGroup> groups;
+    auto end_of = [&](long long i) { return lengths[i] > INT64_MAX - offsets[i] ? (long long)INT64_MAX : (long long)(offsets[i] + lengths[i]); };
+    for (long long i = 0; i < n_clips;) {
+        RgPcmGroup g = {i, 1, (long long)offsets[i], end_of(i)};
+        for (long long j = i + 1; j < n_clips; ++j) {
+            const long long lo = std::min<long long>(g.lo, offsets[j]), hi = std::max(g.hi, end_of(j));
+            if (hi - lo > budget_frames) break;
+            g.lo = lo, g.hi = hi, ++g.count;
+        }
+        groups.push_back(g);
+        i += g.count;
+    }
+    return groups;
 }
 
 }  // namespace zafx

@@ -228,6 +228,7 @@ struct PcmPoint {
 // RAGGED (zafx_execute_ragged): clips of different lengths.  `n_samples` carries the batch's table and `tiles` the number of clips
 // (SamplesArg, zafx_internal.hpp); a tile's clip, its samples, frames, row pitch and the bases of its input and output come from its
 // record, and everything else -- the fast / edge decision, the zero padding, the XCD order, the store phase -- is the same code.
+// With PCM (zafx_execute_ragged_pcm; W = 2048) the record's in_off and n_samples count sample frames: 2 bytes mono, the 4 bytes of a pair stereo.
 //
 // DYN: the tiles are claimed while the kernel runs instead of dealt out up front (tlv += gridDim.x).  The static split is even only if
 // every CU is served by the memory system at the same rate for the whole launch; the launch ends with the slowest workgroup's last tile, and
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
     const float* __restrict__ x, const float* __restrict__ win, const float2* __restrict__ twp,
     const float2* __restrict__ tws, float2* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop, int T, int TP, int tiles,
     TilesArg<DYN> tiles_arg) {
-    static_assert(!RAGGED || (PCM == 0 && FPB_ == kFatFrames), "ragged batches: float32 samples, 16-frame tiles");
+    static_assert(!RAGGED || (FPB_ == kFatFrames && (PCM == 0 || LOG2N == 10)), "ragged batches: 16-frame tiles; int16 samples at W = 2048");
     static_assert(!DYN || FPB_ == kFatFrames, "claimed tiles: 16-frame tiles");
     const int& total_tiles = tiles_total<DYN>(tiles_arg);
     // samples, frames and row pitch of the tile's clip: the kernel's arguments, or (RAGGED) the fields of the tile's record rc -- read where
@@ -320,7 +321,7 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_stft_ft16(
         const long long first = (long long)tile * FPB * hop - N;               // first sample of the tile
         const long long last = first + (long long)(FPB - 1) * hop + W;          // one past its last sample
         if constexpr (PCM == 1) {   // int16 mono: a point is 4 bytes
-            const short* xs = reinterpret_cast<const short*>(x) + (long long)clip * CLIP_N;
+            const short* xs = reinterpret_cast<const short*>(x) + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);   // (RAGGED: offsets and lengths count sample frames)
             if (ALIGNED && first >= 0 && last <= CLIP_N && tile * FPB + FPB <= CLIP_T) {
                 const short* src = xs + first + (long long)(wave * FPW) * hop + 2 * p;
 #pragma unroll
@@ -3501,6 +3502,13 @@ static hipError_t run_stft_fat_ragged(const zafx_plan& pl, const float* x, float
     constexpr int LOG2E = (ZAFX_STFT_R32 && LOG2N == 10) ? 5 : default_log2e(LOG2N);   // (as run_stft_fat)
     using F = FatCfg<LOG2N, LOG2E>;
     auto kern = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, kFatFrames, 0, true>;
+    [[maybe_unused]] auto dyn = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, kFatFrames, 0, true, true>;
+    // (zafx_execute_ragged_pcm: int16 in the loads, the records count sample frames; it vouches for W = 2048, the complex kinds and `aligned`)
+    if constexpr (LOG2N == 10 && SPEC < 2 && ALIGNED) {
+        const int pcm = take_pcm_mode();
+        if (pcm == 1) kern = k_stft_ft16<LOG2N, LOG2E, true, SPEC, kFatFrames, 1, true>, dyn = k_stft_ft16<LOG2N, LOG2E, true, SPEC, kFatFrames, 1, true, true>;
+        if (pcm == 2) kern = k_stft_ft16<LOG2N, LOG2E, true, SPEC, kFatFrames, 2, true>, dyn = k_stft_ft16<LOG2N, LOG2E, true, SPEC, kFatFrames, 2, true, true>;
+    }
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, F::SMEM); e != hipSuccess) return e;
     if (total_tiles <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
@@ -3508,7 +3516,6 @@ static hipError_t run_stft_fat_ragged(const zafx_plan& pl, const float* x, float
     pl.ran = "k_stft_ft16_ragged";
     if (pl.stft_dynamic && pl.d_claim) {   // tiles claimed at run time (DYN): the tile count is rarely a multiple of the grid here
         static_assert(F::SMEM + kClaimLdsBytes <= (size_t)kMaxLdsBytes, "tile + tables + claim words exceed LDS");
-        auto dyn = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, kFatFrames, 0, true, true>;
         if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(dyn), pl.device, F::SMEM + kClaimLdsBytes); e != hipSuccess) return e;
         hipLaunchKernelGGL(dyn, dim3((unsigned)grid), dim3(F::NT), F::SMEM + kClaimLdsBytes, pl.stream, x, pl.d_window,
                            LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass, pl.d_tw_aux, out, tab, pl.H, 0, 0, (int)n_clips, TileClaim{(int)total_tiles, 0, pl.d_claim});

@@ -19,7 +19,9 @@ launch where the library has the kernel):
     stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged; pack_ragged (the packed array they upload);
     Plan.ragged_layout / Plan.execute_ragged on device buffers (every forward kind that takes samples);
     imdct_ragged (a sequence of (W/2, T_i) coefficient blocks -- mdct_ragged's views as they lie -- back to clips), Plan.execute_imdct_ragged;
-    istft_ragged (a sequence of (W, T_i) spectra -- stft_ragged's views as they lie -- back to clips), Plan.execute_istft_ragged
+    istft_ragged (a sequence of (W, T_i) spectra -- stft_ragged's views as they lie -- back to clips), Plan.execute_istft_ragged;
+    the forward ones from int16 / int32 PCM clips, (N_i,) or (N_i, C): stft_pcm_ragged, mdct_pcm_ragged, melspectrogram_pcm_ragged,
+    mfcc_pcm_ragged, mel_mfcc_pcm_ragged; pack_ragged_pcm; Plan.execute_ragged_pcm on device buffers
 Device-resident API: Plan, DeviceBuffer, Comm, *_plan factories, shard helpers; one process per GPU: launch.Rendezvous,
 spawn_ranks (file rendezvous + self-launcher, no torch.distributed).
 """
@@ -32,7 +34,8 @@ from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersid
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,
                    get_precision, set_precision, stft, stft_batch, stft_pcm_batch, stft_plan, mdct_pcm_batch, melspectrogram_pcm_batch, mfcc_pcm_batch,
                    cqtspectrogram_pcm_batch, cqtchromagram_pcm_batch, mel_mfcc_batch, mel_mfcc_pcm_batch, mel_mfcc_supported, set_row_padding, get_row_padding,
-                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, imdct_ragged, istft_ragged)
+                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, imdct_ragged, istft_ragged,
+                   stft_pcm_ragged, mdct_pcm_ragged, melspectrogram_pcm_ragged, mfcc_pcm_ragged, mel_mfcc_pcm_ragged, pack_ragged_pcm)
 from .launch import Rendezvous, rank_env, spawn_ranks
 from .shard import clip_range, run_sharded, shard_sizes
 

@@ -516,6 +516,30 @@ class Plan:
             _lib.check(_lib.load().zafx_execute_pcm(self.handle, d_pcm.ptr, d_out.ptr, n_clips, n_frames, n_channels,
                                                    d_pcm.dtype.itemsize), "zafx_execute_pcm")
 
+    def execute_ragged_pcm(self, d_pcm, in_offsets, lengths, d_out, n_channels=1):
+        """execute_ragged() on integer PCM that is already on the device (asynchronous; zafx_execute_ragged_pcm): d_pcm holds interleaved int16 /
+        int32 sample frames of n_channels channels, clip i is lengths[i] sample frames at sample frame in_offsets[i], and its result -- that of
+        execute_ragged on the normalised mono clip -- goes to the block ragged_layout(lengths) assigns in d_out.  int16 mono / stereo at window
+        2048 on a grid of lines is read by the ragged kernels themselves (last_kernel as execute_ragged's; even hop and offsets, d_pcm on 8
+        bytes -- the MDCT: offsets and lengths multiples of 4, d_pcm on 16 bytes); every other batch converts, in groups of clips, into a
+        bounded staging array the plan owns and runs execute_ragged on that (include/zafx.h)."""
+        lengths, in_offsets = _as_lengths(lengths), _as_lengths(in_offsets, "in_offsets")
+        n_channels = int(n_channels)
+        if len(in_offsets) != len(lengths):
+            raise ValueError("in_offsets and lengths must have one entry per clip")
+        if n_channels < 1:
+            raise ValueError("n_channels must be at least 1")
+        if d_pcm.dtype not in (np.dtype(np.int16), np.dtype(np.int32)) or d_out.dtype != self.out_dtype:
+            raise ValueError(f"execute_ragged_pcm takes int16 or int32 sample frames and a {self.out_dtype} output buffer")
+        if len(lengths) and int((in_offsets + lengths).max()) > d_pcm.nbytes // (d_pcm.dtype.itemsize * n_channels):
+            raise ValueError("a clip reaches past the end of d_pcm")
+        if int(self._ragged_offsets(lengths)[-1]) * self.out_dtype.itemsize > d_out.nbytes:
+            raise ValueError("d_out is smaller than the ragged batch's output (ragged_layout)")
+        # (the plan's staging array of the convert-first route is shared state: serialise calls on one plan, as the *_pcm_ragged functions do
+        # under the plan's lock)
+        _lib.check(_lib.load().zafx_execute_ragged_pcm(self.handle, d_pcm.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, len(lengths),
+                                                      n_channels, d_pcm.dtype.itemsize), "zafx_execute_ragged_pcm")
+
     def timer_start(self):
         _lib.check(_lib.load().zafx_timer_start(self.handle), "zafx_timer_start")
 
@@ -1277,6 +1301,11 @@ def _run_ragged(plan, clips):
     offs, frames, pitch = plan.ragged_layout(lengths)
     rows = plan.out_dims(0)[0]
     res = _round_trip(plan, x, int(offs[-1]), lambda d_in, d_out: plan.execute_ragged(d_in, in_offsets, lengths, d_out))
+    return _ragged_views(plan, res, rows, offs, frames, pitch)
+
+
+def _ragged_views(plan, res, rows, offs, frames, pitch):
+    """The per-clip views of a ragged batch's downloaded result (Plan.ragged_layout)."""
     if plan.layout == _lib.LAYOUT_FT:
         return [res[o:o + rows * p].reshape(rows, p)[:, :t] for o, t, p in zip(offs.tolist(), frames.tolist(), pitch.tolist())]
     return [res[o:o + t * rows].reshape(t, rows) for o, t in zip(offs.tolist(), frames.tolist())]
@@ -1434,6 +1463,132 @@ def mel_mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_
     plan = _ragged_grid(plan, lambda a: mel_plan(w, step_length, mel_filterbank, number_coefficients, layout, device, row_align=a, also_mel=True))
     both = _run_ragged(plan, clips)
     ft = plan.layout == _lib.LAYOUT_FT
+    return ([b[:n_filters] if ft else b[:, :n_filters] for b in both], [b[n_filters:] if ft else b[:, n_filters:] for b in both])
+
+
+# ---- ragged batches of integer PCM (zafx_execute_ragged_pcm) ----------------------------------
+_RAGGED_PCM_ALIGN = 64   # sample frames between clip starts in a packed PCM batch: 128 bytes of int16 mono
+
+
+def _as_ragged_pcm(clips, empty_ok=False):
+    """A ragged batch of integer PCM -- a sequence of (N_i,) or (N_i, C) arrays of ONE integer dtype (int16 or int32) and one channel count --
+    validated ahead of any device call: -> (list of (N_i, C) arrays, C, dtype, whether every clip came 1-D)."""
+    name, items, noun = "ragged PCM batch", "(N,) or (N, C) integer clips", "clip"
+    if isinstance(clips, np.ndarray) and clips.dtype != object and clips.ndim <= 1:
+        raise ValueError(f"a {name} is a sequence of {items}, not one array")
+    try:
+        arrays = list(clips)
+    except TypeError:
+        raise ValueError(f"a {name} is a sequence of {items}") from None
+    if not arrays and not empty_ok:
+        raise ValueError(f"a {name} needs at least one {noun}")
+    flat = True
+    for i, c in enumerate(arrays):
+        a = np.asarray(c)
+        wrong = None
+        if a.ndim not in (1, 2):
+            wrong = f"must be 1-D or (N, C), got {a.ndim}-D"
+        elif a.dtype not in (np.dtype(np.int16), np.dtype(np.int32)):
+            wrong = f"must be int16 or int32 (wavread's other dtypes: convert on the host), got {a.dtype}"
+        elif a.ndim == 2 and a.shape[1] < 1:
+            wrong = f"must have at least one channel, got shape {a.shape}"
+        if wrong:
+            raise ValueError(f"{noun} {i} of the {name} {wrong}")
+        flat = flat and a.ndim == 1
+        arrays[i] = a = a[:, None] if a.ndim == 1 else a
+        if a.dtype != arrays[0].dtype:
+            raise ValueError(f"{noun} {i} of the {name} must be {arrays[0].dtype} as clip 0 (one dtype per batch), got {a.dtype}")
+        if a.shape[1] != arrays[0].shape[1]:
+            raise ValueError(f"{noun} {i} of the {name} must have {arrays[0].shape[1]} channel(s) as clip 0 (one channel count per batch), got {a.shape[1]}")
+    ch, dtype = (arrays[0].shape[1], arrays[0].dtype) if arrays else (1, np.dtype(np.int16))
+    return arrays, ch, dtype, flat
+
+
+def _pack_ragged_pcm(arrays, ch, dtype):
+    lengths = np.array([len(a) for a in arrays], np.int64)
+    offsets, total = _back_to_back(lengths, _RAGGED_PCM_ALIGN)
+    packed = np.zeros((max(total, _RAGGED_PCM_ALIGN), ch), dtype)
+    for a, o in zip(arrays, offsets.tolist()):
+        packed[o:o + len(a)] = a
+    return packed, offsets, lengths
+
+
+def pack_ragged_pcm(clips):
+    """One contiguous array of a ragged batch of integer PCM: a sequence of (N_i,) or (N_i, C) int16 / int32 arrays of one dtype and one channel
+    count -> (packed, in_offsets, lengths), offsets and lengths in sample frames; packed is (S,) for 1-D clips, (S, C) interleaved otherwise.
+    Clip i starts at sample frame in_offsets[i], a multiple of 64 (128 bytes of int16 mono), and the gaps between the clips are zeros -- so that
+    the kernels that read int16 themselves apply whenever the hop is even (zafx_execute_ragged_pcm).  The array is never empty."""
+    arrays, ch, dtype, flat = _as_ragged_pcm(clips)
+    packed, offsets, lengths = _pack_ragged_pcm(arrays, ch, dtype)
+    return (packed[:, 0] if flat else packed), offsets, lengths
+
+
+def _run_ragged_pcm(make_plan, float_fn, batch):
+    """One ragged PCM batch (_as_ragged_pcm's result) through the plan make_plan() -- make_plan(row_align): the same on a grid of lines --: one
+    upload of the integers, one execute_ragged_pcm, one download.  -> list of per-clip views of the one result buffer, as _run_ragged.  A plan
+    the library runs in float64 (windows outside the float32 kernels) normalises on the device and takes float_fn(clips), as _pcm_batch."""
+    arrays, ch, dtype, _ = batch
+    plan = make_plan()
+    x, in_offsets, lengths = _pack_ragged_pcm(arrays, ch, dtype)
+    if plan.f64:
+        mono = pcm_to_mono(x[None], plan.device)[0]
+        return float_fn([mono[o:o + n] for o, n in zip(in_offsets.tolist(), lengths.tolist())])
+    plan = _ragged_grid(plan, make_plan)
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    res = _round_trip(plan, x.reshape(-1), int(offs[-1]), lambda d_in, d_out: plan.execute_ragged_pcm(d_in, in_offsets, lengths, d_out, ch))
+    return _ragged_views(plan, res, plan.out_dims(0)[0], offs, frames, pitch)
+
+
+def stft_pcm_ragged(clips, window_function, step_length, layout="FT", device=0, onesided=False):
+    """stft_ragged of integer PCM clips of different lengths: a sequence of (N_i,) or (N_i, C) int16 / int32 arrays -> the list stft_ragged gives
+    for the normalised mono clips (zaf.py:1202 x / 2^(bits-1), zaf.py:65 mean over the channels).  One upload of the integers (2-4 bytes per
+    sample and channel), one execute, one download; int16 mono / stereo at window 2048 with an even hop is read by the kernel itself."""
+    batch = _as_ragged_pcm(clips)
+    _spectrum_of(onesided)
+    return _run_ragged_pcm(lambda a=0: stft_plan(window_function, step_length, layout, device, onesided, row_align=a),
+                           lambda x: stft_ragged(x, window_function, step_length, layout, device, onesided), batch)
+
+
+def mdct_pcm_ragged(clips, window_function, layout="FT", device=0):
+    """mdct_ragged of integer PCM clips of different lengths (see stft_pcm_ragged); int16 mono / stereo at window 2048 is read by the kernel
+    itself when every clip's length is a multiple of 4 sample frames.  An empty list gives an empty list."""
+    w = _as_window(window_function, any_length=True)
+    if len(w) % 2 or len(w) < 4:
+        raise ValueError("the MDCT needs an even window_length >= 4")
+    _as_row_align(0, layout)   # (an unknown layout fails here)
+    if isinstance(clips, (list, tuple)) and not len(clips):
+        return []
+    batch = _as_ragged_pcm(clips)
+    return _run_ragged_pcm(lambda a=0: mdct_plan(w, layout, device, row_align=a), lambda x: mdct_ragged(x, w, layout, device), batch)
+
+
+def melspectrogram_pcm_ragged(clips, window_function, step_length, mel_filterbank, layout="FT", device=0):
+    """melspectrogram_ragged of integer PCM clips of different lengths (see stft_pcm_ragged)."""
+    batch = _as_ragged_pcm(clips)
+    return _run_ragged_pcm(lambda a=0: mel_plan(window_function, step_length, mel_filterbank, None, layout, device, row_align=a),
+                           lambda x: melspectrogram_ragged(x, window_function, step_length, mel_filterbank, layout, device), batch)
+
+
+def mfcc_pcm_ragged(clips, window_function, step_length, mel_filterbank, number_coefficients, layout="FT", device=0):
+    """mfcc_ragged of integer PCM clips of different lengths (see stft_pcm_ragged)."""
+    batch = _as_ragged_pcm(clips)
+    return _run_ragged_pcm(lambda a=0: mel_plan(window_function, step_length, mel_filterbank, number_coefficients, layout, device, row_align=a),
+                           lambda x: mfcc_ragged(x, window_function, step_length, mel_filterbank, number_coefficients, layout, device), batch)
+
+
+def mel_mfcc_pcm_ragged(clips, window_function, step_length, mel_filterbank, number_coefficients, layout="FT", device=0):
+    """mel_mfcc_ragged of integer PCM clips of different lengths (see stft_pcm_ragged): -> (list of (n_filters, T_i), list of
+    (number_coefficients, T_i)), from one set of transforms where the one-pass kernel takes the geometry (mel_mfcc_supported), else from the
+    two plans."""
+    batch = _as_ragged_pcm(clips)
+    w = _as_window(window_function, any_length=True)
+    n_filters = mel_filterbank.shape[0] if hasattr(mel_filterbank, "shape") else 0
+    if not mel_mfcc_supported(len(w), n_filters, int(number_coefficients), False):
+        return (melspectrogram_pcm_ragged(batch[0], w, step_length, mel_filterbank, layout, device),
+                mfcc_pcm_ragged(batch[0], w, step_length, mel_filterbank, number_coefficients, layout, device))
+    both = _run_ragged_pcm(lambda a=0: mel_plan(w, step_length, mel_filterbank, number_coefficients, layout, device, row_align=a, also_mel=True),
+                           None, batch)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
     return ([b[:n_filters] if ft else b[:, :n_filters] for b in both], [b[n_filters:] if ft else b[:, n_filters:] for b in both])
 
 
