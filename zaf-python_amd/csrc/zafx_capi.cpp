@@ -17,6 +17,7 @@
 
 #include "zafx_center.hpp"
 #include "zafx_units.hpp"
+#include "zafx_wfold.hpp"
 #include "zafx_internal.hpp"
 
 #ifndef ZAFX_STFT_FAT8_TABLES
@@ -361,20 +362,8 @@ static int finalize_constant(zafx_plan* pl, int which) {
             pl->cola_gain = (float)g;
             if (is_mdct_family(pl->kind)) {
                 // sign-folded window for the fold + pack step of k_mdct_ft32: packed input m reads taps
-                // (a, b | c, d); re = x[a] w0 + x[b] w1, im = x[c] w2 + x[d] w3
-                const int nf = pl->W / 4;
-                std::vector<float> wf((size_t)nf * 4);
-                const float* w = pl->h_window.data();
-                for (int m = 0; m < nf; ++m) {
-                    float* o = &wf[(size_t)m * 4];
-                    if (2 * m < nf) {
-                        o[0] = -w[3 * nf - 1 - 2 * m]; o[1] = -w[3 * nf + 2 * m];
-                        o[2] = w[nf - 1 - 2 * m];      o[3] = -w[nf + 2 * m];
-                    } else {
-                        o[0] = w[2 * m - nf];          o[1] = -w[3 * nf - 1 - 2 * m];
-                        o[2] = -w[nf + 2 * m];         o[3] = -w[5 * nf - 1 - 2 * m];
-                    }
-                }
+                // (a, b | c, d); re = x[a] w0 + x[b] w1, im = x[c] w2 + x[d] w3 (zafx_wfold.hpp)
+                const std::vector<float> wf = zafx::mdct_fold_window(pl->h_window.data(), pl->W);
                 ZAFX_HIP(upload(&pl->d_wfold, wf.data(), wf.size() * sizeof(float)));
             }
             return 0;
