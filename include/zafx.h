@@ -226,7 +226,19 @@ int zafx_plan_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64
  * 16-byte aligned and every offset and length is a multiple of 4 samples, 4-byte loads for any other offsets and lengths; every
  * clip below 2^28 samples).  ZAFX_RAGGED_MDCT_NATIVE=0 in the environment keeps MDCT batches off that launch: a switch for
  * measurements only (tools/ragged_rates.py times the launch against one execute per clip in one process), read at every call,
- * not part of the interface.  Everything else runs one zafx_execute per clip on the plan's stream ("per-clip <kernel>"). */
+ * not part of the interface.
+ * Float64 plans (params.precision = ZAFX_PRECISION_F64) in ZAFX_LAYOUT_FT at window_length 2048 (a power of two: no Bluestein
+ * part) run in ONE launch under the same conditions on the output -- every clip's rows whole 128-byte lines (row_align 8 for
+ * complex128, 16 for float64), d_out 128-byte aligned -- with d_in 16-byte aligned and fewer than 2^31 tiles: ZAFX_STFT with
+ * spectrum ZAFX_SPECTRUM_TWO_SIDED or _ONE_SIDED on k_stft_ft8_f64 ("k_stft_ft8_f64_ragged", 8-frame tiles), ZAFX_MDCT on
+ * k_mdct_ft16_f64 ("k_mdct_ft16_f64_ragged"), ZAFX_MEL / ZAFX_MFCC on k_mel_ft8_f64 where zafx_execute runs them there (up to
+ * 128 filters; "k_mel_ft8_f64_ragged").  Offsets and lengths are free: a frame that lies inside its clip and starts an even
+ * number of samples into d_in is read by 16-byte loads, every other frame sample by sample -- a clip at an odd offset throughout.
+ * The bits are those of zafx_execute on each clip.  ZAFX_RAGGED_F64_NATIVE=0 in the environment keeps float64 batches off these
+ * launches: for measurements only, read at every call, not part of the interface, as ZAFX_RAGGED_MDCT_NATIVE above and
+ * ZAFX_RAGGED_IMDCT_NATIVE, ZAFX_RAGGED_ISTFT_NATIVE and ZAFX_RAGGED_PCM_NATIVE below.
+ * Everything else -- ZAFX_LAYOUT_TF, |X| / |X|^2 and every other window in float64, compact rows, a d_out off the line grid, a
+ * d_in off 16 bytes in float64, CQT kinds -- runs one zafx_execute per clip on the plan's stream ("per-clip <kernel>"). */
 int zafx_execute_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out,
                         int64_t n_clips);
 /* The center / sides extraction of n_clips stereo clips of different lengths in ONE launch (ZAFX_CENTER and ZAFX_CENTER_SIDES

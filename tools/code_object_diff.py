@@ -1,5 +1,6 @@
 """Kernels of two builds of one translation unit, side by side: for every instantiation of a kernel in the OLD object, its twin in the NEW
-one -- matched by demangled name and template arguments, with the trailing `false` of a template parameter added since (RAGGED) dropped --
+one -- matched by demangled name and template arguments, with the trailing `false` of a template parameter added since (RAGGED) dropped (a kernel
+that was no template before is matched to its <false>) --
 compared by the metadata notes (VGPRs, SGPRs, spills, LDS, scratch; llvm-readelf --notes) and by the disassembled instruction stream.
 Also lists the NEW object's instantiations whose last template argument is `true`, with their notes.  Needs no GPU.
 
@@ -27,16 +28,19 @@ def code_object(obj, tmp):
 
 
 def notes(co):
+    """The FIELDS of every kernel's metadata entry.  An entry starts at `- .agpr_count:` and names its kernel in `.symbol: NAME.kd`; its
+    arguments carry `.name` fields of their own, so the entry is not keyed by that."""
     txt = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    res, cur = {}, None
+    res, cur = {}, {}
     for line in txt.splitlines():
-        m = re.match(r"\s+\.name:\s+(\S+)", line)
-        if m and not m.group(1).endswith(".kd"):
-            cur = m.group(1)
-            res[cur] = {}
-        m = re.match(r"\s+\.(\w+):\s+(\d+)\s*$", line)
-        if m and cur and m.group(1) in FIELDS:
-            res[cur][m.group(1)] = int(m.group(2))
+        if re.match(r"\s*- \.agpr_count:", line):
+            cur = {}
+        m = re.match(r"\s+(?:- )?\.(\w+):\s+(\d+)\s*$", line)
+        if m and m.group(1) in FIELDS:
+            cur[m.group(1)] = int(m.group(2))
+        m = re.match(r"\s+\.symbol:\s+(\S+)\.kd\s*$", line)
+        if m:
+            res[m.group(1)] = cur
     return res
 
 
@@ -49,7 +53,7 @@ def disasm(co):
         if m:
             cur = m.group(1)
             res[cur] = []
-        elif cur and line.strip():
+        elif cur and line.strip() and line.strip() != "...":   # ("...": zero padding behind a kernel, by its place in the object)
             res[cur].append(re.sub(r"\s*//.*$", "", line.strip()))   # (the comment holds the address and the encoding)
     return res
 
@@ -60,8 +64,11 @@ def demangle(names):
 
 
 def key(dem):
-    m = re.match(r"void (zafx::\w+)<(.*?)>\(", dem)
-    return f"{m.group(1)}<{', '.join(a.strip() for a in m.group(2).split(','))}>" if m else dem
+    """name<template arguments> of a kernel of namespace zafx (or its anonymous namespace); a kernel that is no template (demangled without its return type): name<>."""
+    m = re.match(r"(?:void )?(zafx::(?:\(anonymous namespace\)::)?\w+)(?:<(.*?)>)?\(", dem)
+    if not m:
+        return dem
+    return f"{m.group(1)}<{', '.join(a.strip() for a in m.group(2).split(',')) if m.group(2) else ''}>"
 
 
 def main(old_obj, new_obj, pattern):
@@ -73,7 +80,7 @@ def main(old_obj, new_obj, pattern):
     new = {key(dm[s]): s for s in nn if pattern in dm[s]}
     same_notes = same_code = 0
     for k, so in sorted(old.items()):
-        sn = new.get(k[:-1] + ", false>") or new.get(k)
+        sn = new.get(k[:-1] + ("false>" if k.endswith("<>") else ", false>")) or new.get(k)   # (k_mdct_ft16_f64 was no template before its RAGGED form)
         if sn is None:
             print(f"MISSING  {k}")
             continue
@@ -84,7 +91,7 @@ def main(old_obj, new_obj, pattern):
         print(f"{'notes same' if nt else 'NOTES DIFFER'}  {'code same' if code else 'code differs'}  {k}  {no[so]}"
               + ("" if nt else f" -> {nn[sn]}") + diff)
     print(f"{len(old)} instantiations: notes identical {same_notes}, instruction streams identical {same_code}")
-    added = {k: s for k, s in new.items() if k.endswith(", true>")}
+    added = {k: s for k, s in new.items() if re.search(r"[<, ]true>$", k)}
     if added:
         print("new instantiations (last template argument true):")
         for k, s in sorted(added.items()):

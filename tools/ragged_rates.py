@@ -1,6 +1,7 @@
 """Rates of ragged batches (zafx_execute_ragged) against the padded batch and an equal-length batch, in one process.
 
-    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct,istft,mel_pcm,mfcc_pcm,stft_pcm,mdct_pcm] [--imdct-k 2,4,8,12,16,24]
+    python tools/ragged_rates.py [--reps 30] [--out FILE] [--kinds stft,mel,mfcc,mel+mfcc,mdct,mdct_any,imdct,istft,mel_pcm,mfcc_pcm,stft_pcm,mdct_pcm,stft64,mdct64,mel64,mfcc64]
+                                 [--imdct-k 2,4,8,12,16,24]
                                  [--istft-k 2,4,8,12,16,24]
 
 Batch: 1024 clips, lengths uniform in 5-15 s at 44.1 kHz (even, so that the aligned loads apply as they do for the equal-length batch),
@@ -38,6 +39,16 @@ the library's primitives amounted to before the RAGGED x PCM forms; `padded`: ex
 times, the three read in turn, one launch of each per round, --reps rounds after three warm-up rounds, median (min, max).  With one of these
 among the kinds the tool exits with status 1 unless `native`'s median is below both alternatives' for every such kind (margin zero: the native
 launch moves strictly fewer bytes and is one launch fewer).
+
+The `stft64` (two-sided), `mdct64`, `mel64` and `mfcc64` rows (not in the default kinds): the same 1024 clips as float64, float64 plans on
+whole-line rows (Hamming 2048 / hop 1024, KBD 2048 for the MDCT, 128 filters, 20 coefficients).  `ragged`: one execute_ragged, table
+upload included (k_stft_ft8_f64_ragged, k_mdct_ft16_f64_ragged, k_mel_ft8_f64_ragged); `padded`: the clips padded to the longest as one
+execute of the equal-length tiled kernel; `per_clip`: the same execute_ragged with ZAFX_RAGGED_F64_NATIVE=0, one zafx_execute per clip --
+what every float64 batch ran before the RAGGED forms existed.  The three are read in turn, one launch of each per round, --reps rounds
+after three warm-up rounds, median (min, max); a kind's outputs are freed before the next kind's are allocated (the padded two-sided
+complex128 STFT alone is about 22 GB).  With one of these among the kinds the tool exits with status 1 unless `ragged`'s median is below
+both alternatives' for every such kind (margin zero: the one launch moves strictly fewer bytes than the padded one and is about 1000
+launches fewer than the per-clip route).
 """
 import argparse
 import json
@@ -342,6 +353,58 @@ def measure_pcm(name, plan, lengths, reps):
     return res
 
 
+F64_KINDS = ("stft64", "mdct64", "mel64", "mfcc64")
+
+
+def inputs_f64(lengths):
+    """The two float64 input arrays the four float64 kinds share: the packed ragged batch and the batch padded to the longest clip.  Noise
+    throughout (the gaps and the padding too: the kernels never read the former, the latter costs what zeros cost), drawn as float32."""
+    rng = np.random.default_rng(1)
+    slots = (lengths + 31) // 32 * 32
+    in_offsets = np.zeros(len(lengths), np.int64)
+    in_offsets[1:] = np.cumsum(slots)[:-1]
+    bufs = {}
+    for key, shape in (("ragged", (int(slots.sum()),)), ("padded", (CLIPS, int(lengths.max())))):
+        bufs[key] = zafx.DeviceBuffer(shape, np.float64)
+        bufs[key].upload(rng.standard_normal(shape, dtype=np.float32).astype(np.float64))
+    return in_offsets, bufs
+
+
+def measure_f64(name, plan, lengths, in_offsets, bufs, reps):
+    """ragged / padded / per-clip of one float64 kind on one plan (zafx_execute_ragged on the tiled float64 kernels' RAGGED forms)."""
+    nmax = int(lengths.max())
+    offs, frames, pitch = plan.ragged_layout(lengths)
+    out = zafx.DeviceBuffer((int(offs[-1]),), plan.out_dtype)
+    o = zafx.DeviceBuffer(plan.out_shape(CLIPS, nmax), plan.out_dtype)
+    call = lambda: plan.execute_ragged(bufs["ragged"], in_offsets, lengths, out)   # noqa: E731
+    kernels = {}
+
+    def noting(key, launch):
+        def run():
+            launch()
+            kernels[key] = plan.last_kernel
+        return run
+    launches = {"ragged": noting("ragged", call), "padded": noting("padded", lambda: plan.execute(bufs["padded"], o, CLIPS, nmax)),
+                "per_clip": noting("per_clip", with_env("ZAFX_RAGGED_F64_NATIVE", "0", call))}
+    res = {"samples": int(lengths.sum()), "longest": nmax, "ragged_output_bytes": int(offs[-1]) * plan.out_dtype.itemsize,
+           "padded_output_bytes": int(np.prod(plan.out_shape(CLIPS, nmax), dtype=np.int64)) * plan.out_dtype.itemsize}
+    res.update(timed_in_turn(plan, launches, reps))
+    out.free()
+    o.free()
+    for key in launches:
+        res[key + "_kernel"] = kernels[key]
+        res[key]["msamples_per_s"] = res["samples"] / (res[key]["median_ms"] * 1e3)
+    res["padded_over_ragged"] = res["padded"]["median_ms"] / res["ragged"]["median_ms"]
+    res["per_clip_over_ragged"] = res["per_clip"]["median_ms"] / res["ragged"]["median_ms"]
+    res["ragged_is_fastest"] = bool(res["ragged"]["median_ms"] < min(res["padded"]["median_ms"], res["per_clip"]["median_ms"]))
+    r, p, c = res["ragged"], res["padded"], res["per_clip"]
+    print(f"{name:9s} ragged {r['median_ms']:7.3f} ms ({r['min_ms']:.3f}-{r['max_ms']:.3f}) {r['msamples_per_s']:8.0f} Ms/s [{res['ragged_kernel']}] | "
+          f"padded {p['median_ms']:7.3f} ms ({p['min_ms']:.3f}-{p['max_ms']:.3f}) [{res['padded_kernel']}] | per clip {c['median_ms']:7.3f} ms "
+          f"({c['min_ms']:.3f}-{c['max_ms']:.3f}) [{res['per_clip_kernel']}] | padded / ragged {res['padded_over_ragged']:.3f}, "
+          f"per clip / ragged {res['per_clip_over_ragged']:.1f}", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -389,6 +452,18 @@ def main():
             plan = pcm_plans[name] if name in pcm_plans else zafx.mdct_plan(zafx.kaiser_bessel_derived(W), row_align=32)
             result[name] = measure_pcm(name, plan, lengths, a.reps)
             pcm_fastest = pcm_fastest and result[name]["native_is_fastest"]
+    f64_fastest = True
+    if any(k in F64_KINDS for k in kinds):
+        kbd = zafx.kaiser_bessel_derived(W)
+        f64_plans = {"stft64": lambda: zafx.stft_plan(window, HOP, f64=True, row_align=8), "mdct64": lambda: zafx.mdct_plan(kbd, row_align=16, f64=True),
+                     "mel64": lambda: zafx.mel_plan(window, HOP, fb, row_align=16, f64=True), "mfcc64": lambda: zafx.mel_plan(window, HOP, fb, 20, row_align=16, f64=True)}
+        in_offsets, bufs = inputs_f64(lengths)
+        for name in F64_KINDS:
+            if name in kinds:
+                result[name] = measure_f64(name, f64_plans[name](), lengths, in_offsets, bufs, a.reps)
+                f64_fastest = f64_fastest and result[name]["ragged_is_fastest"]
+        for b in bufs.values():
+            b.free()
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
@@ -396,7 +471,9 @@ def main():
         print("the one launch of the ragged ISTFT is not faster than both alternatives")
     if not pcm_fastest:
         print("a ragged PCM kind's native launch is not faster than both alternatives (convert first, padded)")
-    if not (fastest and pcm_fastest):
+    if not f64_fastest:
+        print("a float64 kind's one ragged launch is not faster than both alternatives (padded, per clip)")
+    if not (fastest and pcm_fastest and f64_fastest):
         sys.exit(1)
 
 

@@ -1580,7 +1580,8 @@ static int upload_plan_table(zafx_plan* pl, size_t need, const std::function<voi
 }
 
 // zafx_execute_ragged's table: zafx::RgClip records, then the clip of every tile of `tile_frames` frames (16: k_stft_ft16 / k_mel2; 32:
-// k_mdct_ft32) -- the tiles the records' first_tile counts (zafx_ragged_table.hpp)
+// k_mdct_ft32; float64: 8 for k_stft_ft8_f64, 16 for k_mdct_ft16_f64 / k_mel_ft8_f64) -- the tiles the records' first_tile counts
+// (zafx_ragged_table.hpp)
 static int upload_ragged_table(zafx_plan* pl, const std::vector<zafx::RgClip>& recs, int64_t total_tiles, int tile_frames = 16) {
     const size_t rec_b = recs.size() * sizeof(zafx::RgClip);
     return upload_plan_table(pl, rec_b + (size_t)total_tiles * sizeof(int), [&](unsigned char* h) {
@@ -1690,6 +1691,28 @@ static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_i
             return launch_pcm([&] {
                 return zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged), n_clips, tiles32, aligned);
             });
+        }
+    }
+    // native, float64: the tiled kernels of W = 2048 in their RAGGED forms -- k_stft_ft8_f64 (the complex kinds; 8-frame tiles), k_mdct_ft16_f64,
+    // k_mel_ft8_f64 (mel and mfcc; 16-frame tiles) -- for the plans their equal-length launchers send there (one predicate each, zafx_f64.hip),
+    // on the reference layout with every clip's rows whole 128-byte lines, d_out on 128 bytes and d_in on 16.  Offsets and lengths are free:
+    // a frame that starts an even number of samples into d_in and lies inside its clip comes by 16-byte loads, every other one sample by
+    // sample.  The STFT's tiles are 8 frames: first_tile and the tile count are redone for them, and that count is the one bounded.
+    // ZAFX_RAGGED_F64_NATIVE=0 in the environment keeps the batch on the per-clip path (measurements only, include/zafx.h).
+    if (pcm == 0 && pl->prm.precision == ZAFX_PRECISION_F64 && pl->d_window64 && lines && reinterpret_cast<uintptr_t>(d_in) % 16 == 0 &&
+        (pl->kind == ZAFX_STFT   ? zafx::stft_f64_tiled(*pl)
+         : pl->kind == ZAFX_MDCT ? zafx::mdct_f64_tiled(*pl)
+                                 : (pl->kind == ZAFX_MEL || pl->kind == ZAFX_MFCC) && zafx::mel_f64_tiled(*pl)) &&
+        env_on("ZAFX_RAGGED_F64_NATIVE")) {
+        const int tile_frames = pl->kind == ZAFX_STFT ? zafx::kStft64RaggedTile : zafx::kMd64RaggedTile;
+        const long long tiles64 = zafx::rg_assign_tiles(recs.data(), recs.size(), tile_frames);
+        if (tiles64 < (1LL << 31)) {
+            if (int rc = upload_ragged_table(pl, recs, tiles64, tile_frames)) return rc;
+            const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged);
+            *launched = true;
+            return launch_rc(fn, pl->kind == ZAFX_STFT   ? zafx::launch_stft_f64_ragged(*pl, (const double*)d_in, (double2*)d_out, tab, n_clips, tiles64)
+                                 : pl->kind == ZAFX_MDCT ? zafx::launch_mdct_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles64)
+                                                         : zafx::launch_mel_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles64));
         }
     }
     if (pcm != 0 && pl->kind == ZAFX_MDCT) return 0;

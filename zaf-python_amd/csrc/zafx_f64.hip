@@ -220,9 +220,20 @@ __device__ __forceinline__ void fft1024_f64(double2* v, double2* buf, int lane, 
     frame_sync<64>();
 }
 
-template <bool ONE>
+// The three tiled forward kernels (k_stft_ft8_f64, k_mdct_ft16_f64, k_mel_ft8_f64) read samples, frames and row pitch of a tile's clip through
+// these: the kernel's arguments, or (RAGGED) the fields of the tile's record rc (rg_pick: the equal-length forms read what they always did).
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+#define CLIP_T rg_pick<RAGGED>(rc.T, T)
+#define CLIP_TP rg_pick<RAGGED>(rc.TP, TP)
+// 16-byte loads: the frame at s0 starts an even number of samples into x (equal lengths: clip * n_samples + s0 is even for every clip).
+// Written in place in the frame's condition: hoisted into a bool in front of it, the equal-length forms compiled to other code.
+#define FRAME_EVEN (RAGGED ? ((rc.in_off + s0) & 1) == 0 : ((s0 | CLIP_N) & 1) == 0)
+// RAGGED (zafx_execute_ragged): clips of different lengths, as the float32 kernels' RAGGED forms -- `n_samples` carries the batch's table of
+// 8-frame tiles, `tiles` the number of clips; T and TP are not used.  A tile's clip, and with it samples, frames, pitch and the places of its
+// input and its output block, come from the table, once for the samples requested one tile ahead and once for the tile at hand.
+template <bool ONE, bool RAGGED = false>
 __global__ __launch_bounds__(kF64Frames * 64) void k_stft_ft8_f64(const double* __restrict__ x, const double* __restrict__ win, const double2* __restrict__ tw,
-                                                                   const double2* __restrict__ tws, double2* __restrict__ out, long long n_samples, int hop, int T,
+                                                                   const double2* __restrict__ tws, double2* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop, int T,
                                                                    int TP, int tiles, int total_tiles) {
     constexpr int N = kF64N, W = 2 * N, FPB = kF64Frames, PITCH = kF64Pitch, ROWS = ONE ? N + 1 : W;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -237,10 +248,12 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_stft_ft8_f64(const double* 
     auto request = [&](int tlv) {
         if (tlv >= total_tiles) return;
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t = (tl % tiles) * FPB + wave;
-        const double* xc = x + (long long)clip * n_samples;
+        RgClip rc = {};
+        if constexpr (RAGGED) rc = rg_clip_const(n_samples, tiles, tl);   // (the tile ahead is in general another clip's)
+        const int clip = RAGGED ? 0 : tl / tiles, t = (RAGGED ? tl - rc.first_tile : tl % tiles) * FPB + wave;
+        const double* xc = x + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);
         const long long s0 = (long long)t * hop - N;   // floor(W / 2) samples of left padding (zaf.py:99, :112)
-        if (t < T && s0 >= 0 && s0 + W <= n_samples && ((s0 | n_samples) & 1) == 0) {   // (uniform) interior frame, 16-byte loads
+        if (t < CLIP_T && s0 >= 0 && s0 + W <= CLIP_N && FRAME_EVEN) {   // (uniform) interior frame, 16-byte loads
             const double2* xp = reinterpret_cast<const double2*>(xc + s0);
 #pragma unroll
             for (int i = 0; i < 16; ++i) v[i] = xp[lane + 64 * i];
@@ -248,15 +261,17 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_stft_ft8_f64(const double* 
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const long long s = s0 + 2 * (lane + 64 * i);
-                v[i].x = (t < T && s >= 0 && s < n_samples) ? xc[s] : 0.0;
-                v[i].y = (t < T && s + 1 >= 0 && s + 1 < n_samples) ? xc[s + 1] : 0.0;
+                v[i].x = (t < CLIP_T && s >= 0 && s < CLIP_N) ? xc[s] : 0.0;
+                v[i].y = (t < CLIP_T && s + 1 >= 0 && s + 1 < CLIP_N) ? xc[s + 1] : 0.0;
             }
         }
     };
     request(blockIdx.x);
     for (int tlv = blockIdx.x; tlv < total_tiles; tlv += gridDim.x) {
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t0 = (tl % tiles) * FPB;
+        RgClip rc = {};
+        if constexpr (RAGGED) rc = rg_clip_const(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, t0 = (RAGGED ? tl - rc.first_tile : tl % tiles) * FPB;
         int lane_o = lane;
         asm volatile("" : "+v"(lane_o));   // (opaque per tile: window and twiddle values are re-read from L1, not hoisted out of the loop and spilled)
         double2 w2[16];
@@ -295,8 +310,8 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_stft_ft8_f64(const double* 
         {
             const int f = tid & (FPB - 1), g = tid / FPB;
             const double2* fb = frames + f * PITCH;
-            double2* o = out + (long long)clip * ROWS * TP + t0 + f;
-            if (t0 + f < T) {
+            double2* o = out + (RAGGED ? rc.out_off : (long long)clip * ROWS * CLIP_TP) + t0 + f;
+            if (t0 + f < CLIP_T) {
 #pragma unroll 4
                 for (int r = g; r < ROWS; r += 64) {   // (64 = threads / frames: rows per instruction of the workgroup)
                     double2 val;
@@ -307,7 +322,7 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_stft_ft8_f64(const double* 
                     f64x2 q;
                     q.x = val.x;
                     q.y = val.y;
-                    __builtin_nontemporal_store(q, reinterpret_cast<f64x2*>(o + (long long)r * TP));   // one 16-byte streaming store
+                    __builtin_nontemporal_store(q, reinterpret_cast<f64x2*>(o + (long long)r * CLIP_TP));   // one 16-byte streaming store
                 }
             }
         }
@@ -342,8 +357,10 @@ __device__ __forceinline__ double2 root512(const double2* __restrict__ tw, int m
     return m & 256 ? make_double2(-w.x, -w.y) : w;
 }
 
+// RAGGED (zafx_execute_ragged): as k_stft_ft8_f64's -- the table (of 16-frame tiles) in `n_samples`, the number of clips in `tiles`.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(kMd64Frames * 64) void k_mdct_ft16_f64(const double* __restrict__ x, const double* __restrict__ win, const double2* __restrict__ tw,
-                                                                     const double2* __restrict__ g, double* __restrict__ out, long long n_samples, int T, int TP,
+                                                                     const double2* __restrict__ g, double* __restrict__ out, SamplesArg<RAGGED> n_samples, int T, int TP,
                                                                      int tiles, int total_tiles) {
     constexpr int NF = kMd64NF, M = 2 * NF, FPB = kMd64Frames, PITCH = kMd64Pitch;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -355,10 +372,12 @@ __global__ __launch_bounds__(kMd64Frames * 64) void k_mdct_ft16_f64(const double
         int lane = tid & 63;
         asm volatile("" : "+v"(lane));   // (opaque per tile: the lane's window, twiddle and table values are re-read, not hoisted out of the loop and spilled)
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t0 = (tl % tiles) * FPB, t = t0 + wave;
-        const double* xc = x + (long long)clip * n_samples;
+        RgClip rc = {};
+        if constexpr (RAGGED) rc = rg_clip_const(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, t0 = (RAGGED ? tl - rc.first_tile : tl % tiles) * FPB, t = t0 + wave;
+        const double* xc = x + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);
         const long long s0 = (long long)t * M - M;   // left pad = M (zaf.py:1036-1041)
-        const bool inside = t < T && s0 >= 0 && s0 + 2 * M <= n_samples && ((s0 | n_samples) & 1) == 0;   // (uniform) 16-byte loads
+        const bool inside = t < CLIP_T && s0 >= 0 && s0 + 2 * M <= CLIP_N && FRAME_EVEN;   // (uniform) 16-byte loads
         // The frame's two halves go through the wave's buffer one after the other, windowed, as coalesced 16-byte pieces; the fold reads its
         // partners (a sample and its mirror image) from there.  (Folded straight out of global memory -- 32 + 32 strided 8-byte loads per lane in
         // flight -- the kernel needed more than its 128 registers: 676 bytes of scratch, 1.63 ms for 256 clips.)
@@ -379,7 +398,7 @@ __global__ __launch_bounds__(kMd64Frames * 64) void k_mdct_ft16_f64(const double
                     const int q = lane + 64 * j;
                     const long long sa = s0 + M * half + 2 * q;
                     const double2 w = wp[q];
-                    const double a = (t < T && sa >= 0 && sa < n_samples) ? xc[sa] : 0.0, b = (t < T && sa + 1 >= 0 && sa + 1 < n_samples) ? xc[sa + 1] : 0.0;
+                    const double a = (t < CLIP_T && sa >= 0 && sa < CLIP_N) ? xc[sa] : 0.0, b = (t < CLIP_T && sa + 1 >= 0 && sa + 1 < CLIP_N) ? xc[sa + 1] : 0.0;
                     reinterpret_cast<double2*>(ub)[q] = make_double2(a * w.x, b * w.y);
                 }
             }
@@ -446,10 +465,10 @@ __global__ __launch_bounds__(kMd64Frames * 64) void k_mdct_ft16_f64(const double
         {
             const int f = tid & 15, gq = tid >> 4;
             const double* fb = reinterpret_cast<const double*>(frames + f * PITCH);
-            double* o = out + (long long)clip * M * TP + t0 + f;
-            if (t0 + f < T) {
+            double* o = out + (RAGGED ? rc.out_off : (long long)clip * M * CLIP_TP) + t0 + f;
+            if (t0 + f < CLIP_T) {
 #pragma unroll 4
-                for (int r = gq; r < M; r += 64) __builtin_nontemporal_store(fb[2 * phys8(r >> 1) + (r & 1)], o + (long long)r * TP);
+                for (int r = gq; r < M; r += 64) __builtin_nontemporal_store(fb[2 * phys8(r >> 1) + (r & 1)], o + (long long)r * CLIP_TP);
             }
         }
         lds_barrier();
@@ -919,10 +938,12 @@ constexpr int kMel64OutPitch = 17;                   // doubles per staged row o
 constexpr int kMel64Spare = 2 * kF64Pitch - kF64N;   // doubles of a wave's frame buffer behind S: partial sums, then the log-mel column
 
 ZAFX_PROF_ARRAY(g_prof_mel64)
-template <bool MFCC>
+// RAGGED (zafx_execute_ragged): as k_stft_ft8_f64's -- the table (of 16-frame tiles) in `n_samples`, the number of clips in `tiles`; the
+// record is read for every frame requested (the second round's request is the next tile's, in general another clip's) and for the tile's stores.
+template <bool MFCC, bool RAGGED = false>
 __global__ __launch_bounds__(kF64Frames * 64) void k_mel_ft8_f64(const double* __restrict__ x, const double* __restrict__ win, const double2* __restrict__ tw,
                                                                   const double2* __restrict__ tws, const int4* __restrict__ stream, const int2* __restrict__ fin,
-                                                                  const double* __restrict__ dctT, double* __restrict__ out, long long n_samples, int hop, int T, int TP,
+                                                                  const double* __restrict__ dctT, double* __restrict__ out, SamplesArg<RAGGED> n_samples, int hop, int T, int TP,
                                                                   int tiles, int total_tiles, int n_filters, int n_coefs, int n_steps, int n_slots, int max_parts,
                                                                   int cpitch, int dct_half) {
     constexpr int N = kF64N, W = 2 * N, FPB = kF64Frames, PITCH = kF64Pitch, OP = kMel64OutPitch;
@@ -942,10 +963,12 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_mel_ft8_f64(const double* _
     auto load_frame = [&](double2 (&d)[16], int tlv, int round) {   // raw samples of this wave's frame of round `round` of tile `tlv`
         if (tlv >= total_tiles) return;
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t = (tl % tiles) * 16 + round * FPB + wave;
-        const double* xc = x + (long long)clip * n_samples;
+        RgClip rc = {};
+        if constexpr (RAGGED) rc = rg_clip_const(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, t = (RAGGED ? tl - rc.first_tile : tl % tiles) * 16 + round * FPB + wave;
+        const double* xc = x + (RAGGED ? rc.in_off : (long long)clip * CLIP_N);
         const long long s0 = (long long)t * hop - N;   // floor(W / 2) samples of left padding (zaf.py:99, :112)
-        if (t < T && s0 >= 0 && s0 + W <= n_samples && ((s0 | n_samples) & 1) == 0) {   // (uniform) interior frame, 16-byte loads
+        if (t < CLIP_T && s0 >= 0 && s0 + W <= CLIP_N && FRAME_EVEN) {   // (uniform) interior frame, 16-byte loads
             const double2* xp = reinterpret_cast<const double2*>(xc + s0);
 #pragma unroll
             for (int i = 0; i < 16; ++i) d[i] = xp[lane + 64 * i];
@@ -953,8 +976,8 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_mel_ft8_f64(const double* _
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const long long s = s0 + 2 * (lane + 64 * i);
-                d[i].x = (t < T && s >= 0 && s < n_samples) ? xc[s] : 0.0;
-                d[i].y = (t < T && s + 1 >= 0 && s + 1 < n_samples) ? xc[s + 1] : 0.0;
+                d[i].x = (t < CLIP_T && s >= 0 && s < CLIP_N) ? xc[s] : 0.0;
+                d[i].y = (t < CLIP_T && s + 1 >= 0 && s + 1 < CLIP_N) ? xc[s + 1] : 0.0;
             }
         }
     };
@@ -963,7 +986,9 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_mel_ft8_f64(const double* _
     PROF_INIT(g_prof_mel64);
     for (int tlv = blockIdx.x; tlv < total_tiles; tlv += gridDim.x) {
         const int tl = xcd ? xcd_order(tlv, total_tiles) : tlv;
-        const int clip = tl / tiles, t0 = (tl % tiles) * 16;
+        RgClip rc = {};
+        if constexpr (RAGGED) rc = rg_clip_const(n_samples, tiles, tl);
+        const int clip = RAGGED ? 0 : tl / tiles, t0 = (RAGGED ? tl - rc.first_tile : tl % tiles) * 16;
 #pragma unroll 1
         for (int round = 0; round < 2; ++round) {
             int lane_o = lane;
@@ -1111,15 +1136,19 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_mel_ft8_f64(const double* _
         PROF_MARK(6);
         {   // the tile's rows: sixteen lanes (frames) to a 128-byte line, 32 rows per instruction of the workgroup
             const int f = tid & 15;
-            double* o = out + (long long)clip * rows * TP + t0 + f;
-            if (t0 + f < T)
-                for (int r = tid >> 4; r < rows; r += 32) o[(long long)r * TP] = stage[r * OP + f];
+            double* o = out + (RAGGED ? rc.out_off : (long long)clip * rows * CLIP_TP) + t0 + f;
+            if (t0 + f < CLIP_T)
+                for (int r = tid >> 4; r < rows; r += 32) o[(long long)r * CLIP_TP] = stage[r * OP + f];
         }
         PROF_MARK(7);
         lds_barrier();
         PROF_MARK(8);
     }
 }
+#undef CLIP_N
+#undef CLIP_T
+#undef CLIP_TP
+#undef FRAME_EVEN
 
 // ---- windows that are not a power of two (the reference's np.fft takes any length): Bluestein ---------------------------
 // W-point DFT as a convolution of length M = 2^ceil(log2(2W-1)):  n k = (n^2 + k^2 - (k-n)^2) / 2, so with
@@ -1816,18 +1845,67 @@ static hipError_t launch_bs_f64(const zafx_plan& pl, const double* x, void* out,
     return hipGetLastError();
 }
 
+// The plans of the tiled kernels (W = 2048, reference layout): what the equal-length launchers below test before the tiled launch and what
+// zafx_execute_ragged tests before the RAGGED one -- one predicate per kernel, so that the two routes cannot drift.
+bool stft_f64_tiled(const zafx_plan& pl) {   // k_stft_ft8_f64: the complex kinds
+    return ZAFX_F64_TILED && pl.bs_log2m == 0 && pl.W == 2048 && pl.layout == ZAFX_LAYOUT_FT && pl.prm.spectrum <= ZAFX_SPECTRUM_ONE_SIDED;
+}
+bool mdct_f64_tiled(const zafx_plan& pl) {   // k_mdct_ft16_f64
+    return ZAFX_F64_TILED && pl.bs_log2m == 0 && pl.W == 2048 && pl.layout == ZAFX_LAYOUT_FT;
+}
+bool mel_f64_tiled(const zafx_plan& pl) {   // k_mel_ft8_f64: a filterbank its tables take (mel64_ok: W = 2048, up to 128 filters), mfcc: a DCT table whose terms fit the wave's spare LDS
+    const bool mfcc = pl.kind == ZAFX_MFCC;
+    return ZAFX_F64_TILED && pl.bs_log2m == 0 && pl.mel64_ok && (!mfcc || (pl.mel64_cpitch > 0 && pl.mel64_slots + 2 * pl.mel64_dct_half <= kMel64Spare)) &&
+           pl.layout == ZAFX_LAYOUT_FT;
+}
+
+static_assert(kF64Frames == kStft64RaggedTile && kMd64Frames == kMd64RaggedTile, "the tiles the host's table counts are the kernels' (k_mel_ft8_f64: two rounds of 8)");
+// zafx_execute_ragged on the tiled kernels' RAGGED forms: d_tab is the batch's table of `tile_frames`-frame tiles (8 for the STFT, 16 for
+// the MDCT, mel and mfcc), total_tiles < 2^31 its tiles; x on 16 bytes, every clip's output block on 128 (the caller's conditions).
+hipError_t launch_stft_f64_ragged(const zafx_plan& pl, const double* x, double2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles) {
+    if (total_tiles <= 0) return hipSuccess;
+    const size_t smem8 = (size_t)kF64Frames * kF64Pitch * sizeof(double2) + kF64Frames * sizeof(double);
+    auto k8 = pl.prm.spectrum == ZAFX_SPECTRUM_ONE_SIDED ? k_stft_ft8_f64<true, true> : k_stft_ft8_f64<false, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k8), pl.device, smem8); e != hipSuccess) return e;
+    pl.ran = "k_stft_ft8_f64_ragged";
+    hipLaunchKernelGGL(k8, dim3((unsigned)std::min<long long>(total_tiles, (long long)pl.n_cus * (kF64Frames <= 4 ? 2 : 1))), dim3(kF64Frames * 64), smem8, pl.stream, x, pl.d_window64,
+                       pl.d_tw64, pl.d_tws64, out, d_tab, pl.H, 0, 0, (int)n_clips, (int)total_tiles);
+    return hipGetLastError();
+}
+hipError_t launch_mdct_f64_ragged(const zafx_plan& pl, const double* x, double* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles) {
+    if (total_tiles <= 0) return hipSuccess;
+    const size_t smem16 = (size_t)kMd64Frames * kMd64Pitch * sizeof(double2);
+    auto k16 = k_mdct_ft16_f64<true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k16), pl.device, smem16); e != hipSuccess) return e;
+    pl.ran = "k_mdct_ft16_f64_ragged";
+    hipLaunchKernelGGL(k16, dim3((unsigned)std::min<long long>(total_tiles, pl.n_cus)), dim3(kMd64Frames * 64), smem16, pl.stream, x, pl.d_window64, pl.d_tw64, pl.d_tws64, out,
+                       d_tab, 0, 0, (int)n_clips, (int)total_tiles);
+    return hipGetLastError();
+}
+hipError_t launch_mel_f64_ragged(const zafx_plan& pl, const double* x, double* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles) {
+    if (total_tiles <= 0) return hipSuccess;
+    const bool mfcc = pl.kind == ZAFX_MFCC;
+    const size_t smem8 = (size_t)kF64Frames * kF64Pitch * sizeof(double2) + (size_t)kMel64Rows * kMel64OutPitch * sizeof(double);
+    auto k8 = mfcc ? k_mel_ft8_f64<true, true> : k_mel_ft8_f64<false, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k8), pl.device, smem8); e != hipSuccess) return e;
+    pl.ran = "k_mel_ft8_f64_ragged";
+    hipLaunchKernelGGL(k8, dim3((unsigned)std::min<long long>(total_tiles, pl.n_cus)), dim3(kF64Frames * 64), smem8, pl.stream, x, pl.d_window64, pl.d_tw64, pl.d_tws64,
+                       pl.d_mel64_stream, pl.d_mel64_fin, pl.d_mel64_dctT, out, d_tab, pl.H, 0, 0, (int)n_clips, (int)total_tiles, pl.prm.n_filters,
+                       mfcc ? pl.prm.n_coefs : 0, pl.mel64_steps, pl.mel64_slots, pl.mel64_max_parts, pl.mel64_cpitch, pl.mel64_dct_half);
+    return hipGetLastError();
+}
+
 hipError_t launch_stft_f64(const zafx_plan& pl, const double* x, double2* out, int64_t n_clips, int64_t n_samples, int T) {
     if (pl.bs_log2m > 0) return launch_bs_f64(pl, x, out, n_clips, n_samples, T, false);
     const long long blocks = (long long)n_clips * T;
     if (blocks <= 0) return hipSuccess;
-    if (ZAFX_F64_TILED && pl.W == 2048 && pl.layout == ZAFX_LAYOUT_FT && pl.prm.spectrum <= ZAFX_SPECTRUM_ONE_SIDED && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(out) % 16 == 0) {
+    if (stft_f64_tiled(pl) && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
         const int tiles = (T + kF64Frames - 1) / kF64Frames;
         const long long total = (long long)tiles * n_clips;
         if (total < (1LL << 31)) {
             const size_t smem8 = (size_t)kF64Frames * kF64Pitch * sizeof(double2) + kF64Frames * sizeof(double);
             const bool one = pl.prm.spectrum == ZAFX_SPECTRUM_ONE_SIDED;
-            auto k8 = one ? k_stft_ft8_f64<true> : k_stft_ft8_f64<false>;
+            auto k8 = one ? k_stft_ft8_f64<true, false> : k_stft_ft8_f64<false, false>;
             if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k8), pl.device, smem8); e != hipSuccess) return e;
             pl.ran = "k_stft_ft8_f64";
             hipLaunchKernelGGL(k8, dim3((unsigned)std::min<long long>(total, (long long)pl.n_cus * (kF64Frames <= 4 ? 2 : 1))), dim3(kF64Frames * 64), smem8, pl.stream, x, pl.d_window64, pl.d_tw64,
@@ -1970,12 +2048,12 @@ hipError_t launch_mel_f64(const zafx_plan& pl, const double* x, double* out, int
     const long long blocks = (long long)n_clips * T;
     if (blocks <= 0) return hipSuccess;
     const bool mfcc = pl.kind == ZAFX_MFCC;
-    if (ZAFX_F64_TILED && pl.mel64_ok && (!mfcc || (pl.mel64_cpitch > 0 && pl.mel64_slots + 2 * pl.mel64_dct_half <= kMel64Spare)) && pl.layout == ZAFX_LAYOUT_FT && reinterpret_cast<uintptr_t>(x) % 16 == 0) {
+    if (mel_f64_tiled(pl) && reinterpret_cast<uintptr_t>(x) % 16 == 0) {
         const int tiles = (T + 15) / 16;
         const long long total = (long long)tiles * n_clips;
         if (total < (1LL << 31)) {
             const size_t smem8 = (size_t)kF64Frames * kF64Pitch * sizeof(double2) + (size_t)kMel64Rows * kMel64OutPitch * sizeof(double);
-            auto k8 = mfcc ? k_mel_ft8_f64<true> : k_mel_ft8_f64<false>;
+            auto k8 = mfcc ? k_mel_ft8_f64<true, false> : k_mel_ft8_f64<false, false>;
             if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k8), pl.device, smem8); e != hipSuccess) return e;
             pl.ran = "k_mel_ft8_f64";
             hipLaunchKernelGGL(k8, dim3((unsigned)std::min<long long>(total, pl.n_cus)), dim3(kF64Frames * 64), smem8, pl.stream, x, pl.d_window64, pl.d_tw64, pl.d_tws64,
@@ -2007,12 +2085,12 @@ hipError_t launch_mdct_f64(const zafx_plan& pl, const double* x, double* out, in
                            out, (long long)n_samples, T, (int)row_pitch(pl, T), pl.W, pl.bs_log2m, pl.layout);
         return hipGetLastError();
     }
-    if (ZAFX_F64_TILED && pl.W == 2048 && pl.layout == ZAFX_LAYOUT_FT) {
+    if (mdct_f64_tiled(pl)) {
         const int tiles = (T + kMd64Frames - 1) / kMd64Frames;
         const long long total = (long long)tiles * n_clips;
         if (total < (1LL << 31)) {
             const size_t smem16 = (size_t)kMd64Frames * kMd64Pitch * sizeof(double2);
-            auto k16 = k_mdct_ft16_f64;
+            auto k16 = k_mdct_ft16_f64<false>;
             if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k16), pl.device, smem16); e != hipSuccess) return e;
             pl.ran = "k_mdct_ft16_f64";
             hipLaunchKernelGGL(k16, dim3((unsigned)std::min<long long>(total, pl.n_cus)), dim3(kMd64Frames * 64), smem16, pl.stream, x, pl.d_window64, pl.d_tw64,

@@ -299,6 +299,16 @@ hipError_t launch_istft_f64(zafx_plan& pl, const double2* spec, double* y, int64
 hipError_t launch_cqt_f64(zafx_plan& pl, const double* x, double* out, int64_t n_clips, int64_t n_samples, int T);
 hipError_t launch_mel_f64(const zafx_plan& pl, const double* x, double* out, int64_t n_clips, int64_t n_samples, int T);
 hipError_t launch_mdct_f64(const zafx_plan& pl, const double* x, double* out, int64_t n_clips, int64_t n_samples, int T);
+// The tiled float64 kernels (W = 2048, reference layout): the plans each takes -- one predicate per kernel, shared by the equal-length launcher
+// and the ragged route -- and zafx_execute_ragged's launches of their RAGGED forms.  The table counts tiles of kStft64RaggedTile frames for
+// the STFT and of kMd64RaggedTile frames for the MDCT, mel and mfcc; x on 16 bytes, every clip's output block on 128, total_tiles < 2^31.
+constexpr int kStft64RaggedTile = 8, kMd64RaggedTile = 16;
+bool stft_f64_tiled(const zafx_plan& pl);
+bool mdct_f64_tiled(const zafx_plan& pl);
+bool mel_f64_tiled(const zafx_plan& pl);
+hipError_t launch_stft_f64_ragged(const zafx_plan& pl, const double* x, double2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles);
+hipError_t launch_mdct_f64_ragged(const zafx_plan& pl, const double* x, double* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles);
+hipError_t launch_mel_f64_ragged(const zafx_plan& pl, const double* x, double* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles);
 hipError_t build_mel64_fb(zafx_plan& pl);    // host tables of k_mel_ft8_f64 (zafx_f64.hip), rebuilt whenever the filterbank / DCT constant is set
 hipError_t build_mel64_dct(zafx_plan& pl);
 hipError_t launch_imdct_f64(zafx_plan& pl, const double* coefs, double* y, int64_t n_clips, int T, int64_t out_len);

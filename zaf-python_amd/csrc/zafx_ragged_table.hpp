@@ -1,6 +1,7 @@
 // zafx_ragged_table.hpp -- the table of a ragged batch (zafx_execute_ragged): one record per clip, then the clip of every tile.
 //
-// A tile is `tile_frames` consecutive frames of ONE clip: 16 for k_stft_ft16 / k_mel2, 32 for k_mdct_ft32.  A clip of T frames owns
+// A tile is `tile_frames` consecutive frames of ONE clip: 16 for k_stft_ft16 / k_mel2, 32 for k_mdct_ft32; float64: 8 for k_stft_ft8_f64,
+// 16 for k_mdct_ft16_f64 / k_mel_ft8_f64.  A clip of T frames owns
 // ceil(T / tile_frames) consecutive tiles from its first_tile on -- a clip of length 0 still has T >= 1 frame (zafx_plan_out_dims), so it
 // owns one tile -- and the batch's tiles are numbered in clip order.  The kernels' RAGGED forms find a tile's clip in the per-tile array
 // and everything else in the clip's record.

@@ -418,7 +418,8 @@ class Plan:
         """Enqueue one ragged batch on the plan's stream (asynchronous; zafx_execute_ragged): clip i is lengths[i] samples at element in_offsets[i]
         of d_in, its result goes to the block ragged_layout(lengths) assigns in d_out.  Float32 plans in the "FT" layout whose rows are whole
         128-byte lines run as one launch where the library has the kernel (last_kernel: k_stft_ft16_ragged / k_mel2_ragged); the others as one
-        execute per clip ("per-clip <kernel>")."""
+        execute per clip ("per-clip <kernel>").  Float64 plans at window 2048 ("FT", rows of whole lines, d_in on 16 bytes): one launch of
+        k_stft_ft8_f64_ragged (complex kinds), k_mdct_ft16_f64_ragged or k_mel_ft8_f64_ragged, at any offsets and lengths."""
         lengths, in_offsets = _as_lengths(lengths), _as_lengths(in_offsets, "in_offsets")
         if len(in_offsets) != len(lengths):
             raise ValueError("in_offsets and lengths must have one entry per clip")
@@ -1327,7 +1328,9 @@ def _as_f32_views(views, plan, f64):
 def stft_ragged(clips, window_function, step_length, layout="FT", device=0, onesided=False, f64=False):
     """stft_batch of clips of different lengths in one call: a sequence of 1-D arrays -> a list of (W, T_i) complex64 arrays ["FT"] or (T_i, W)
     ["TF"] (rows 0..W/2, or |X| / |X|^2 as float32, with `onesided` as in stft_batch; complex128 / float64 with f64), each clip's frames
-    T_i as zaf.stft gives them for that clip alone.  The arrays are views of one result buffer."""
+    T_i as zaf.stft gives them for that clip alone.  The arrays are views of one result buffer.  "FT" with f64 at window 2048, two-sided or
+    rows 0..W/2, runs in one launch as the float32 plans do (k_stft_ft8_f64_ragged); |X| / |X|^2 and other windows in float64 run one
+    execute per clip."""
     clips = _as_ragged(clips)
     _spectrum_of(onesided)
     plan = stft_plan(window_function, step_length, layout, device, onesided, f64)
@@ -1339,7 +1342,8 @@ def mdct_ragged(clips, window_function, layout="FT", device=0, f64=False):
     """mdct_batch of clips of different lengths in one call: a sequence of 1-D arrays -> a list of (W/2, T_i) float32 arrays ["FT"] or
     (T_i, W/2) ["TF"] (float64 arrays and arithmetic with f64), each clip's frames T_i = ceil(N_i / (W/2)) + 1 as zaf.mdct gives them for that
     clip alone (a clip of length 0: one frame of zeros).  The arrays are views of one result buffer.  "FT" / float32 at window 512, 1024 and
-    2048 runs in one launch (k_mdct_ft32_ragged); an empty list gives an empty list."""
+    2048 runs in one launch (k_mdct_ft32_ragged), and so does "FT" with f64 at window 2048 (k_mdct_ft16_f64_ragged); an empty list gives an
+    empty list."""
     w = _as_window(window_function, any_length=True)
     if len(w) % 2 or len(w) < 4:
         raise ValueError("the MDCT needs an even window_length >= 4")
@@ -1434,7 +1438,8 @@ def istft_ragged(spectra, window_function, step_length, layout="FT", device=0, o
 
 
 def melspectrogram_ragged(clips, window_function, step_length, mel_filterbank, layout="FT", device=0, f64=False):
-    """melspectrogram_batch of clips of different lengths: -> a list of (n_filters, T_i) float32 arrays (float64 with f64)."""
+    """melspectrogram_batch of clips of different lengths: -> a list of (n_filters, T_i) float32 arrays (float64 with f64).  With f64, "FT" at
+    window 2048 and up to 128 filters runs in one launch (k_mel_ft8_f64_ragged), everything else in float64 one execute per clip."""
     clips = _as_ragged(clips)
     plan = mel_plan(window_function, step_length, mel_filterbank, None, layout, device, f64=f64)
     plan = _ragged_grid(plan, lambda a: mel_plan(window_function, step_length, mel_filterbank, None, layout, device, row_align=a, f64=f64))
@@ -1442,7 +1447,9 @@ def melspectrogram_ragged(clips, window_function, step_length, mel_filterbank, l
 
 
 def mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_coefficients, layout="FT", device=0, f64=False):
-    """mfcc_batch of clips of different lengths: -> a list of (number_coefficients, T_i) float32 arrays (float64 with f64)."""
+    """mfcc_batch of clips of different lengths: -> a list of (number_coefficients, T_i) float32 arrays (float64 with f64).  With f64 -- the
+    arithmetic in which the MFCCs of tonal material hold 1e-10 --, "FT" at window 2048 and up to 128 filters runs in one launch
+    (k_mel_ft8_f64_ragged), everything else in float64 one execute per clip."""
     clips = _as_ragged(clips)
     plan = mel_plan(window_function, step_length, mel_filterbank, number_coefficients, layout, device, f64=f64)
     plan = _ragged_grid(plan, lambda a: mel_plan(window_function, step_length, mel_filterbank, number_coefficients, layout, device, row_align=a,
@@ -1452,7 +1459,8 @@ def mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_coef
 
 def mel_mfcc_ragged(clips, window_function, step_length, mel_filterbank, number_coefficients, layout="FT", device=0, f64=False):
     """mel_mfcc_batch of clips of different lengths: -> (list of (n_filters, T_i), list of (number_coefficients, T_i)), from one set of
-    transforms where the one-pass kernel takes the geometry (mel_mfcc_supported), else from the two plans."""
+    transforms where the one-pass kernel takes the geometry (mel_mfcc_supported), else from the two plans -- with f64 always the two: one
+    launch each at window 2048 (k_mel_ft8_f64_ragged, as melspectrogram_ragged and mfcc_ragged)."""
     clips = _as_ragged(clips)
     w = _as_window(window_function, any_length=True)
     n_filters = mel_filterbank.shape[0] if hasattr(mel_filterbank, "shape") else 0
