@@ -193,6 +193,12 @@ int zafx_host_alloc(void** hptr, size_t bytes);
 int zafx_host_free(void* hptr);
 
 /* ---- plans -------------------------------------------------------------------------- */
+/* Environment read when a plan is created:
+ *   ZAFX_COMPUTE_UNITS=n   (n >= 1) the plan sizes every persistent grid, every cut of clips into carry segments and every slot count of a
+ *                          ragged launch for min(n, the device's count) compute units instead of the device's count: to leave compute units
+ *                          to other work on the same device, and to test the kernels on the grids a smaller device would give them.  Unset,
+ *                          empty, 0 or not a whole number: the device's count.  The results do not depend on it, bit for bit.
+ *   ZAFX_STFT_DYNAMIC=0    k_stft_ft16 deals its tiles out up front instead of claiming them at run time. */
 int zafx_plan_create(zafx_plan** plan, int device, int kind, const zafx_params* params);
 int zafx_plan_destroy(zafx_plan* plan);
 /* Upload one constant (copied; the host buffer may be released on return). */
@@ -313,6 +319,9 @@ int zafx_plan_kernel_name(const zafx_plan* plan, char* buf, size_t buflen);
  * rows; the carry / band / generic forms are chosen per call from T, hop and the buffers' alignment); "" before the
  * first execute. */
 int zafx_plan_last_kernel_name(const zafx_plan* plan, char* buf, size_t buflen);
+/* The compute units the plan sizes its launches for (*in_use: the device's count, or fewer under ZAFX_COMPUTE_UNITS at zafx_plan_create) and
+ * those of its device (*on_device). */
+int zafx_plan_compute_units(const zafx_plan* plan, int* in_use, int* on_device);
 
 /* Largest number of rows (n_bins) of a CQT kernel matrix that a float32 ZAFX_CQT / ZAFX_CHROMA plan of this fft_length
  * holds (k_cqt keeps the frame and the rows' bookkeeping in the 160 KB of LDS); 0 when fft_length itself is outside the

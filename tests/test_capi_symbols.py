@@ -32,6 +32,23 @@ def test_library_exports_every_declared_symbol(built_library):
     assert lib.zafx_version() == 101
 
 
+def test_compute_units_entry_point_is_declared_bound_and_checks_its_arguments(built_library):
+    """zafx_plan_compute_units(plan, in_use, on_device): in the header, in the binding with its three pointers, behind two read-only properties of
+    Plan; a null plan is an error with a message, not a crash (no device is needed to say so)."""
+    import zafx
+    from zafx import _lib
+    assert "zafx_plan_compute_units" in declared_symbols()
+    res, args = _lib.SYMBOLS["zafx_plan_compute_units"]
+    assert res is ctypes.c_int and len(args) == 3
+    for name in ("compute_units", "device_compute_units"):
+        prop = getattr(zafx.Plan, name)
+        assert isinstance(prop, property) and prop.fset is None
+    lib = _lib.load()
+    a, b = ctypes.c_int(-1), ctypes.c_int(-1)
+    assert lib.zafx_plan_compute_units(None, ctypes.byref(a), ctypes.byref(b)) != 0
+    assert b"null" in lib.zafx_last_error() and (a.value, b.value) == (-1, -1)
+
+
 def test_params_struct_layout(built_library):
     from zafx import _lib
     assert ctypes.sizeof(_lib.ZafxParams) == 16 * 4   # 12 fields + 4 reserved int32

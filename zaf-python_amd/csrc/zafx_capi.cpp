@@ -1091,7 +1091,18 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
     pl->log2e = is_center_kind(kind) ? center_log2e(pl->log2nf) : default_log2e(pl->log2nf);
 
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&pl->n_cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&pl->n_cus_device, hipDeviceAttributeMultiprocessorCount, device);
+    if (e == hipSuccess) {
+        // ZAFX_COMPUTE_UNITS=n (n >= 1) at plan creation: the plan sizes its grids, carry cuts and slot counts for min(n, the device's count)
+        // compute units -- to leave the others to other work, and to test the kernels on grids a smaller device would give them.  Unset, empty,
+        // 0 or anything that is not a whole number: the device's count.
+        pl->n_cus = pl->n_cus_device;
+        if (const char* sw = std::getenv("ZAFX_COMPUTE_UNITS"); sw && *sw) {
+            char* end = nullptr;
+            const long long n = std::strtoll(sw, &end, 10);
+            if (end != sw && *end == 0 && n >= 1) pl->n_cus = (int)std::min<long long>(n, pl->n_cus_device);
+        }
+    }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&pl->ev0);
     if (e == hipSuccess) e = hipEventCreate(&pl->ev1);
@@ -2262,6 +2273,12 @@ int zafx_plan_last_kernel_name(const zafx_plan* pl, char* buf, size_t buflen) {
     if (!pl || !buf || !buflen) return fail_msg("null argument");
     const char* ran = pl->ran.load(std::memory_order_acquire);
     std::snprintf(buf, buflen, "%s", ran ? ran : "");
+    return 0;
+}
+
+int zafx_plan_compute_units(const zafx_plan* pl, int* in_use, int* on_device) {
+    if (!pl || !in_use || !on_device) return fail_msg("null argument");
+    *in_use = pl->n_cus, *on_device = pl->n_cus_device;
     return 0;
 }
 

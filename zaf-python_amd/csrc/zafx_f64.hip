@@ -654,33 +654,30 @@ __global__ __launch_bounds__(kF64Frames * 64) void k_istft_ft8_f64(const double2
         const double2* sp = spec + (long long)clip * ROWS * TP;
         double* yc = y + (long long)clip * out_len;
         int rot = 0;
-        if (tile_a > 0) {   // the segment's left neighbour: frame 8 tile_a - 1, by the last wave alone
-            if (wave == FPB - 1) {
-                int lane = tid & 63;
-                asm volatile("" : "+v"(lane));
-                double2* buf = frames + ((rot + FPB) % NS) * PITCH;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) fold(sp, tile_a * FPB - 1, lane + 64 * i, buf);
-                frame_sync<64>();
-                transform(buf, lane);
-            }
-            lds_barrier();
-        }
-        for (int tile = tile_a; tile < tile_b; ++tile) {
+        // A segment that does not start its clip walks the tile in front of it first, for that tile's last frame alone (the segment's left
+        // neighbour) and without a store: the frame comes out of the very instructions that form it when a segment walks that tile in full, so
+        // a clip's samples are the same bits wherever it is cut (tests/test_gpu_compute_units.py; a copy of the fold and the transform for the
+        // last wave alone, as this was before, is contracted into other fused multiply-adds and moved one sample in three by an ulp).
+        for (int tile = tile_a > 0 ? tile_a - 1 : tile_a; tile < tile_b; ++tile) {
+            const bool pre = tile < tile_a;
             const int t0 = tile * FPB;
             int to = tid;
             asm volatile("" : "+v"(to));   // (opaque per tile: table values are re-read, not hoisted and spilled)
             {
                 const int f = to & 7, kq = to >> 3, t = t0 + f;
                 double2* buf = frames + ((rot + f) % NS) * PITCH;
-                if (t < T) {
+                if (t < T && (!pre || f == FPB - 1)) {
 #pragma unroll 2   // (4 or 8 pairs in flight: the same 0.65 ms)
                     for (int i = 0; i < 8; ++i) fold(sp, t, kq + 64 * i, buf);
                 }
             }
             lds_barrier();
-            if (t0 + wave < T) transform(frames + ((rot + wave) % NS) * PITCH, to & 63);
+            if (t0 + wave < T && (!pre || wave == FPB - 1)) transform(frames + ((rot + wave) % NS) * PITCH, to & 63);
             lds_barrier();
+            if (pre) {   // (the frame lies in slot FPB - 1; the next tile looks for its left neighbour in slot (rot + FPB) % NS)
+                rot = (rot + FPB) % NS;
+                continue;
+            }
             // samples s of the padded signal that no later frame reaches: [t0 hop, (t0 + 8) hop), and everything up to the end behind the clip's last frame
             const long long s_lo = (long long)t0 * hop;
             const long long s_hi = tile + 1 >= tiles ? (long long)(T - 1) * hop + W : (long long)(t0 + FPB) * hop;

@@ -85,7 +85,9 @@ constexpr int kMelResidentDct = 4;
 
 struct zafx_plan {
     int device = 0;
-    int n_cus = 256;   // compute units of the device (persistent-kernel grid size)
+    int n_cus = 256;   // compute units the plan uses: every persistent grid, carry cut and slot count is sized from it -- the device's count, or fewer
+                       // under ZAFX_COMPUTE_UNITS at plan creation (zafx_plan_compute_units)
+    int n_cus_device = 256;   // compute units of the device: what sizes an ALLOCATION made per workgroup (never the capped count)
     int kind = 0;
     zafx_params prm{};
     hipStream_t stream = nullptr;
@@ -399,7 +401,7 @@ void set_pcm_mode(int mode);   // (execute_pcm only) also clears the taken mark
 bool pcm_mode_taken();
 
 // Carry kernels (k_istft_ft16, k_imdct): number of segments to cut every clip's tile sequence into so that
-// `grid` persistent workgroups are evenly loaded (1 = whole clips; each extra segment pays one carry-only tile).
+// `grid` persistent workgroups are evenly loaded (1 = whole clips; each extra segment pays one carry-only tile).  Defined in zafx_units.hpp.
 int carry_segments(long long n_clips, int tiles, long long grid);
 
 // Raise a kernel's dynamic-LDS limit to `bytes` on `device` (once per (kernel, device); thread safe).

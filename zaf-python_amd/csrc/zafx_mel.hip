@@ -1367,7 +1367,7 @@ static hipError_t run_mel_wide(zafx_plan& pl, const float* x, float* out, int64_
     // the spectrum kernels see an STFT plan of this window: one-sided |X| (mel, zaf.py:370) or |X|^2 (mfcc, zaf.py:437-439),
     // reference layout, rows padded to 32 floats
     zafx_plan st;
-    st.device = pl.device; st.n_cus = pl.n_cus; st.kind = ZAFX_STFT; st.prm = pl.prm; st.stream = pl.stream;
+    st.device = pl.device; st.n_cus = pl.n_cus; st.n_cus_device = pl.n_cus_device; st.kind = ZAFX_STFT; st.prm = pl.prm; st.stream = pl.stream;
     st.prm.spectrum = mfcc ? ZAFX_SPECTRUM_POWER : ZAFX_SPECTRUM_MAGNITUDE;
     st.prm.row_align = 32;
     st.W = pl.W; st.H = pl.H; st.layout = ZAFX_LAYOUT_FT; st.log2nf = pl.log2nf; st.log2e = pl.log2e;

@@ -2777,20 +2777,7 @@ static hipError_t run_stft(const zafx_plan& pl, const float* x, float2* out, int
     }
 }
 
-// Cut every clip's tiles into `segs` segments so that the persistent grid is evenly loaded: whole
-// clips when there are enough of them, otherwise shorter segments (each pays one carry-only tile).
-int carry_segments(long long n_clips, int tiles, long long grid) {
-    int best = 1;
-    double best_cost = 1e300;
-    for (int segs = 1; segs <= tiles; ++segs) {
-        const int seg_tiles = (tiles + segs - 1) / segs;
-        if (segs > 1 && (segs - 1) * seg_tiles >= tiles) continue;   // would leave an empty segment
-        const long long rounds = (n_clips * segs + grid - 1) / grid;
-        const double cost = (double)rounds * (seg_tiles + (segs > 1 ? 0.5 : 0.0));
-        if (cost < best_cost - 1e-9) best_cost = cost, best = segs;
-    }
-    return best;
-}
+// (carry_segments, the cut of every clip's tiles into segments for the persistent grid: zafx_units.hpp)
 
 #ifndef ZAFX_ISTFT_TF_DEPTH
 #define ZAFX_ISTFT_TF_DEPTH 2
@@ -3629,10 +3616,10 @@ ZAFX_PROF_EXPORT(zafx_debug_prof_istft, g_prof)
 ZAFX_PROF_EXPORT(zafx_debug_prof_stft, g_prof_stft)
 #ifdef ZAFX_PROF
 // Finish times per workgroup of k_stft_ft16 (PROF_TAIL_*): bind (on != 0) points the kernels of this library at an array the plan owns
-// (four words for each of up to 2 n_cus workgroups, zeroed), read waits for the plan's stream and copies n_words of it out.
+// (four words for each of up to 2 n_cus_device workgroups -- the device's count, not a plan's capped one --, zeroed), read waits for the plan's stream and copies n_words of it out.
 extern "C" int zafx_debug_stft_tail_bind(zafx_plan* pl, int on) {
     if (!pl || hipSetDevice(pl->device) != hipSuccess) return 1;
-    const size_t bytes = (size_t)pl->n_cus * 2 * 4 * sizeof(unsigned long long);
+    const size_t bytes = (size_t)pl->n_cus_device * 2 * 4 * sizeof(unsigned long long);
     if (on && !pl->d_tail && hipMalloc(reinterpret_cast<void**>(&pl->d_tail), bytes) != hipSuccess) return 1;
     if (hipStreamSynchronize(pl->stream) != hipSuccess) return 1;
     if (on && hipMemset(pl->d_tail, 0, bytes) != hipSuccess) return 1;
@@ -3640,7 +3627,7 @@ extern "C" int zafx_debug_stft_tail_bind(zafx_plan* pl, int on) {
     return hipMemcpyToSymbol(HIP_SYMBOL(zafx::g_stft_tail), &p, sizeof(p)) != hipSuccess;
 }
 extern "C" int zafx_debug_stft_tail_read(zafx_plan* pl, unsigned long long* out, int n_words) {
-    if (!pl || !pl->d_tail || n_words > pl->n_cus * 2 * 4) return 1;
+    if (!pl || !pl->d_tail || n_words > pl->n_cus_device * 2 * 4) return 1;
     if (hipStreamSynchronize(pl->stream) != hipSuccess) return 1;
     return hipMemcpy(out, pl->d_tail, (size_t)n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess;
 }

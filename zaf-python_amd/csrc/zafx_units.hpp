@@ -176,4 +176,21 @@ inline std::vector<TileUnit> istft_cut_units(const int64_t* frames, int64_t n_cl
     return tile_cut_units(istft_tile_counts(frames, n_clips, W, H, tile_frames), frames, n_clips, kIstftMinSegment, slots, per_slot);
 }
 
+// ---- the carry kernels of equal-length batches (k_stft_ft16c, k_istft_ft16 and its band forms, k_imdct, k_mdct_ft32's carry forms, the float64
+// inverses): every clip has the same `tiles`.  Cut every clip's tiles into `segs` segments so that a persistent grid of `grid` workgroups is
+// evenly loaded: whole clips when there are enough of them, otherwise shorter segments (each pays one carry-only tile, counted as half a
+// tile).  The cost is rounds x (tiles of a segment + 0.5 for segs > 1); of the cuts without an empty segment the first of the cheapest wins.
+inline int carry_segments(long long n_clips, int tiles, long long grid) {
+    int best = 1;
+    double best_cost = 1e300;
+    for (int segs = 1; segs <= tiles; ++segs) {
+        const int seg_tiles = (tiles + segs - 1) / segs;
+        if (segs > 1 && (segs - 1) * seg_tiles >= tiles) continue;   // would leave an empty segment
+        const long long rounds = (n_clips * segs + grid - 1) / grid;
+        const double cost = (double)rounds * (seg_tiles + (segs > 1 ? 0.5 : 0.0));
+        if (cost < best_cost - 1e-9) best_cost = cost, best = segs;
+    }
+    return best;
+}
+
 }  // namespace zafx

@@ -564,6 +564,21 @@ class Plan:
         _lib.check(_lib.load().zafx_plan_last_kernel_name(self.handle, buf, 128), "zafx_plan_last_kernel_name")
         return buf.value.decode() or self.kernel_name
 
+    def _compute_units(self):
+        used, device = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.load().zafx_plan_compute_units(self.handle, ctypes.byref(used), ctypes.byref(device)), "zafx_plan_compute_units")
+        return used.value, device.value
+
+    @property
+    def compute_units(self):
+        """The compute units the plan sizes its launches for: the device's, or fewer under ZAFX_COMPUTE_UNITS at the plan's creation."""
+        return self._compute_units()[0]
+
+    @property
+    def device_compute_units(self):
+        """The compute units of the plan's device."""
+        return self._compute_units()[1]
+
     def clip_bytes(self, n_in):
         """(input bytes, output bytes) of ONE clip for `n_in` (zafx_plan_clip_bytes; rows at the plan's pitch)."""
         a, b = ctypes.c_int64(), ctypes.c_int64()
