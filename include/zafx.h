@@ -201,7 +201,15 @@ int zafx_host_free(void* hptr);
  *   ZAFX_STFT_DYNAMIC=0    k_stft_ft16 deals its tiles out up front instead of claiming them at run time. */
 int zafx_plan_create(zafx_plan** plan, int device, int kind, const zafx_params* params);
 int zafx_plan_destroy(zafx_plan* plan);
-/* Upload one constant (copied; the host buffer may be released on return). */
+/* Upload one constant (copied; the host buffer may be released on return).
+ * The call may be repeated between calls on the plan, at any time: it waits for the plan's stream (work already enqueued finishes with the
+ * constants it was enqueued under), replaces the constant and rebuilds everything derived from it.  Every later execute -- the ragged and the
+ * PCM entry points included -- gives, bit for bit, what a plan created with the constants now in place gives, on the kernel that plan runs (zafx_plan_kernel_name follows the
+ * last upload, zafx_plan_last_kernel_name the next execute).  An upload the call refuses (a wrong size, an id the kind does not take, a CQT column
+ * outside 0 .. fft_length - 1) leaves the plan unchanged.  The three arrays of a CQT kernel arrive one by one, so the lengths of
+ * ZAFX_CONST_CQT_INDICES and _VALUES are checked against each other where they are used: zafx_execute refuses a plan whose CSR arrays
+ * disagree and writes nothing (tests/test_gpu_constants.py).  An upload that was accepted and then fails on the device (no memory for a
+ * derived table, say: the HIP error is returned) leaves that constant unset or half rebuilt: upload it again before the next execute. */
 int zafx_plan_set_constant(zafx_plan* plan, int which, const void* host, size_t bytes);
 /* Output geometry for `n_in` (samples per clip for forward kinds, frames T for inverse
  * kinds): dims[0] = rows F (or samples L), dims[1] = frames T (or 1). */
@@ -322,6 +330,10 @@ int zafx_plan_last_kernel_name(const zafx_plan* plan, char* buf, size_t buflen);
 /* The compute units the plan sizes its launches for (*in_use: the device's count, or fewer under ZAFX_COMPUTE_UNITS at zafx_plan_create) and
  * those of its device (*on_device). */
 int zafx_plan_compute_units(const zafx_plan* plan, int* in_use, int* on_device);
+/* The form of k_cqt the LAST zafx_execute of a float32 CQT / chroma plan launched (both carry the name k_cqt): 1 = the matrix-core contraction
+ * (a numerically real kernel matrix whose columns lie in the lower half and whose segments fit the registers), 2 = the lane reduction
+ * (every other matrix); 0 before the first launch and for every other plan.  Chosen anew after each upload of a CQT constant. */
+int zafx_plan_cqt_form(const zafx_plan* plan, int* form);
 
 /* Largest number of rows (n_bins) of a CQT kernel matrix that a float32 ZAFX_CQT / ZAFX_CHROMA plan of this fft_length
  * holds (k_cqt keeps the frame and the rows' bookkeeping in the 160 KB of LDS); 0 when fft_length itself is outside the

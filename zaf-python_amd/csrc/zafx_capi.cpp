@@ -473,6 +473,7 @@ static int finalize_constant(zafx_plan* pl, int which) {
                 return 0;
             }
             ZAFX_HIP(upload(&pl->d_values, pl->h_values.data(), pl->h_values.size() * sizeof(cf32)));
+            pl->cqt_dirty = true;   // (k_cqt reads the tables build_cqt_chunks packs from h_values, and cqt_real is decided there)
             return 0;
     }
     return fail_msg("unknown constant id");
@@ -1369,9 +1370,10 @@ static int store_shadow(zafx_plan* pl, int which, const void* host, size_t bytes
             pl->h_indptr.assign((const int32_t*)host, (const int32_t*)host + bytes / sizeof(int32_t));
             break;
         case ZAFX_CONST_CQT_INDICES: {
-            pl->h_indices.assign((const int32_t*)host, (const int32_t*)host + bytes / sizeof(int32_t));
-            for (int32_t c : pl->h_indices)
-                if (c < 0 || c >= pl->W) return fail_msg("CQT kernel column index out of range");
+            const int32_t* cols = (const int32_t*)host;   // (checked in the caller's buffer: a refused upload leaves the plan as it was)
+            for (size_t i = 0; i < bytes / sizeof(int32_t); ++i)
+                if (cols[i] < 0 || cols[i] >= pl->W) return fail_msg("CQT kernel column index out of range");
+            pl->h_indices.assign(cols, cols + bytes / sizeof(int32_t));
             break;
         }
         case ZAFX_CONST_CQT_VALUES:
@@ -2273,6 +2275,12 @@ int zafx_plan_last_kernel_name(const zafx_plan* pl, char* buf, size_t buflen) {
     if (!pl || !buf || !buflen) return fail_msg("null argument");
     const char* ran = pl->ran.load(std::memory_order_acquire);
     std::snprintf(buf, buflen, "%s", ran ? ran : "");
+    return 0;
+}
+
+int zafx_plan_cqt_form(const zafx_plan* pl, int* form) {
+    if (!pl || !form) return fail_msg("null argument");
+    *form = pl->cqt_form_ran.load(std::memory_order_acquire);
     return 0;
 }
 

@@ -666,6 +666,7 @@ static hipError_t run_cqt(const zafx_plan& pl, const float* x, float* out, int64
     if (ZAFX_CQT_PRUNE && cqt_split(LOG2N) && !pl.cqt_k_special && pl.cqt_k_hi >= pl.cqt_k_lo && (pos_hi >> 6) <= 2)
         prune3 = pos_hi >> 6;
     pl.ran = "k_cqt";
+    pl.cqt_form_ran = mm ? 1 : 2;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::P), smem, pl.stream, x, pl.d_tw_pass, pl.d_tw_aux, pl.d_cqt_waves,
                        mm ? pl.d_cqt_mm_addr : pl.d_cqt_addrs, mm ? pl.d_cqt_mm_vals : pl.d_cqt_vals, pl.d_cqt_mm_fin, mm ? pl.cqt_mm_steps : 0, pl.cqt_mm_segs, out, (long long)n_samples, pl.H, left, T, (int)row_pitch(pl, T), (int)n_clips, n_groups,
                        pl.prm.n_bins, pl.kind == ZAFX_CHROMA ? pl.prm.octave_resolution : 0, pl.layout, pl.cqt_k_lo, pl.cqt_k_hi,

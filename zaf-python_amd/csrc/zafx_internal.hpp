@@ -205,6 +205,7 @@ struct zafx_plan {
     bool stft_dynamic = false;
     unsigned long long* d_tail = nullptr;   // ZAFX_PROF builds: per-workgroup finish times of k_stft_ft16 (zafx_debug_stft_tail_bind)
     std::string kernel_name;            // the kernel this plan is expected to run (set at creation)
+    mutable std::atomic<int> cqt_form_ran{0};       // the form k_cqt's last launch took: 1 matrix-core, 2 lane reduction (both are "k_cqt"); zafx_plan_cqt_form
     mutable std::atomic<const char*> ran{nullptr};  // the kernel the last execute really launched (routes depend on T, alignment and hop); zafx_plan_last_kernel_name
 };
 

@@ -91,6 +91,7 @@ SYMBOLS = {
     "zafx_plan_kernel_name": (_i, [_vp, ctypes.c_char_p, _sz]),
     "zafx_plan_last_kernel_name": (_i, [_vp, ctypes.c_char_p, _sz]),
     "zafx_plan_compute_units": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "zafx_plan_cqt_form": (_i, [_vp, ctypes.POINTER(_i)]),
     "zafx_cqt_max_bins": (_i, [_i, ctypes.POINTER(_i)]),
     "zafx_pcm_to_float": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i]),
     "zafx_execute_pcm": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i]),

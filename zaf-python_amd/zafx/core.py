@@ -579,6 +579,14 @@ class Plan:
         """The compute units of the plan's device."""
         return self._compute_units()[1]
 
+    @property
+    def cqt_form(self):
+        """The form of k_cqt the last execute of a float32 CQT / chroma plan launched (zafx_plan_cqt_form): "matrix-core" or "lane-reduction";
+        None before the first launch and for every other plan."""
+        form = ctypes.c_int()
+        _lib.check(_lib.load().zafx_plan_cqt_form(self.handle, ctypes.byref(form)), "zafx_plan_cqt_form")
+        return {1: "matrix-core", 2: "lane-reduction"}.get(form.value)
+
     def clip_bytes(self, n_in):
         """(input bytes, output bytes) of ONE clip for `n_in` (zafx_plan_clip_bytes; rows at the plan's pitch)."""
         a, b = ctypes.c_int64(), ctypes.c_int64()
