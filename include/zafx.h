@@ -182,6 +182,8 @@ int zafx_free(int device, void* dptr);
  * layer's DeviceBuffer.placed. */
 int zafx_alloc_placed(zafx_plan* plan, void** dptr, size_t bytes, const void* d_in, int64_t n_clips, int64_t n_in, int n_candidates, int reps,
                       float* probe_ms);
+/* Plain fills and copies.  All four return when the bytes are in place -- zafx_memset and zafx_d2d wait for the device, which hipMemset and a
+ * device-to-device hipMemcpy alone do not --, so a plan's stream, which does not wait for the null stream, sees them whatever is enqueued next. */
 int zafx_memset(int device, void* dptr, int value, size_t bytes);
 int zafx_h2d(int device, void* dst, const void* src, size_t bytes);
 int zafx_d2h(int device, void* dst, const void* src, size_t bytes);
@@ -218,7 +220,29 @@ int zafx_plan_out_dims(const zafx_plan* plan, int64_t n_in, int64_t dims[2]);
  * plans, T rounded up to params.row_align otherwise; the array then holds clips x F x pitch elements.  For
  * ZAFX_LAYOUT_TF and ZAFX_LINEAR plans this is the (contiguous) row length itself. */
 int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
-/* Enqueue the transform of n_clips clips on the plan's stream (asynchronous). */
+/* Enqueue the transform of n_clips clips on the plan's stream (asynchronous).
+ *
+ * The length of ONE clip.  Several kernels address a clip through one buffer descriptor with 32-bit byte offsets; the launchers take them
+ * only below the lengths listed here and run another kernel -- same result, same bounds, lower rate -- from there on, so no length
+ * changes what is computed (float32, ZAFX_LAYOUT_FT; tests/test_gpu_long_clips.py runs one clip on either side of each):
+ *   ZAFX_STFT, |X| and |X|^2 at window 2048   k_mel2 for n_in < 2^29 samples, k_stft_ft16 from there on
+ *   ZAFX_STFT, complex, rows off the line grid   the buffer-load form of k_stft_ft16c / k_stft_ft16bc while T x hop < 2^29, its pointer form /
+ *                                             the one-workgroup-per-tile kernel above; window 4096 and 8192: (T + 16) x hop < 2^29 / 2^28
+ *   ZAFX_ISTFT                                the tiled kernels while window x row pitch x 8 < 2^31 bytes -- window rows counted for a one-sided
+ *                                             spectrum too: 131072 frames at window 2048, 65536 at 4096, 32768 at 8192 --, k_istft above
+ *   ZAFX_MDCT                                 16-byte loads for n_in < 2^28 (window 512 ... 2048: k_mdct_ft32's 4-byte form above; window 4096: the two-band
+ *                                             kernels k_mdct_ft32b / k_mdct_ft32bc below, k_mdct above); window 8192: k_mdct_ft32q while (T + 33) x 4096 < 2^28,
+ *                                             k_mdct above
+ *   ZAFX_IMDCT                                16-byte gathers while window / 2 x row pitch x 4 < 2^32 bytes; window 8192: k_imdct_q while
+ *                                             4096 x row pitch x 4 < 2^31, k_imdct above
+ *   ZAFX_MEL / ZAFX_MFCC                      buffer loads for n_in < 2^29; window 4096: k_mel_ft16b while (T + 16) x hop < 2^29, the
+ *                                             spectrum kernel + k_melfb above
+ * Two kinds REFUSE long clips: the call returns an error (zafx_last_error names the limit), enqueues nothing and writes nothing.
+ *   ZAFX_CQT / ZAFX_CHROMA (float32)          n_in >= 2^29 samples (3.4 h at 44.1 kHz): cut the signal
+ *   ZAFX_CENTER / ZAFX_CENTER_SIDES           n_in >= 2^28 sample frames (1.7 h at 44.1 kHz)
+ * zafx_execute_pcm reads int16 in the kernels' own loads below the same lengths (n_frames < 2^29; the MDCT: < 2^28) and converts first above them.
+ * Not run at its bound by any test yet: the two-sided complex STFT at window 8192 (k_stft_ft16q takes whole-line rows only; its |X| kind is run).
+ * The ragged and PCM entry points state their own per-clip limits below. */
 int zafx_execute(zafx_plan* plan, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC

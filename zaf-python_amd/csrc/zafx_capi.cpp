@@ -855,6 +855,7 @@ int zafx_free(int device, void* dptr) {
 int zafx_memset(int device, void* dptr, int value, size_t bytes) {
     ZAFX_HIP(hipSetDevice(device));
     ZAFX_HIP(hipMemset(dptr, value, bytes));
+    ZAFX_HIP(hipStreamSynchronize(nullptr));   // (as zafx_d2d: done when the call returns)
     return 0;
 }
 int zafx_h2d(int device, void* dst, const void* src, size_t bytes) {
@@ -870,6 +871,9 @@ int zafx_d2h(int device, void* dst, const void* src, size_t bytes) {
 int zafx_d2d(int device, void* dst, const void* src, size_t bytes) {
     ZAFX_HIP(hipSetDevice(device));
     ZAFX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
+    // (a device-to-device hipMemcpy returns before the copy is done, and the plans' streams do not wait for the null stream: a kernel launched
+    // next read a half-copied input, or had its result overwritten by the copy.  The call returns when the bytes are there, as h2d and d2h do.)
+    ZAFX_HIP(hipStreamSynchronize(nullptr));
     return 0;
 }
 

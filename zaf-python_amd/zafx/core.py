@@ -192,6 +192,8 @@ class DeviceBuffer:
         return self
 
     def copy_from(self, other, nbytes=None, dst_offset=0, src_offset=0):
+        """Device-to-device copy of `nbytes` (default: all of `other`); returns when the copy is done (zafx_d2d), so a plan launched next
+        sees the bytes and cannot have its result overwritten by them."""
         nbytes = other.nbytes if nbytes is None else nbytes
         dst = ctypes.c_void_p(self.ptr.value + dst_offset)
         src = ctypes.c_void_p(other.ptr.value + src_offset)
