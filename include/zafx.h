@@ -203,6 +203,11 @@ int zafx_host_free(void* hptr);
  *   ZAFX_STFT_DYNAMIC=0    k_stft_ft16 deals its tiles out up front instead of claiming them at run time. */
 int zafx_plan_create(zafx_plan** plan, int device, int kind, const zafx_params* params);
 int zafx_plan_destroy(zafx_plan* plan);
+/* The number of device and page-locked allocations that plans of this process own right now (*count): tables, constants and the grow-only
+ * staging buffers of the execute calls -- every one is released by zafx_plan_destroy, so the count is back at its earlier value once a plan
+ * is gone, and a zafx_plan_create that fails leaves it as it was.  The arrays of zafx_alloc / zafx_host_alloc are the caller's and are not
+ * counted.  Needs no device. */
+int zafx_plan_live_allocations(int64_t* count);
 /* Upload one constant (copied; the host buffer may be released on return).
  * The call may be repeated between calls on the plan, at any time: it waits for the plan's stream (work already enqueued finishes with the
  * constants it was enqueued under), replaces the constant and rebuilds everything derived from it.  Every later execute -- the ragged and the

@@ -49,6 +49,19 @@ def test_compute_units_entry_point_is_declared_bound_and_checks_its_arguments(bu
     assert b"null" in lib.zafx_last_error() and (a.value, b.value) == (-1, -1)
 
 
+def test_live_allocations_entry_point_is_declared_bound_and_needs_no_device(built_library):
+    """zafx_plan_live_allocations(count): in the header, in the binding with its one pointer; the count is readable where there is no GPU, and a
+    null pointer is an error with a message."""
+    from zafx import _lib
+    assert "zafx_plan_live_allocations" in declared_symbols()
+    res, args = _lib.SYMBOLS["zafx_plan_live_allocations"]
+    assert res is ctypes.c_int and len(args) == 1
+    lib = _lib.load()
+    n = ctypes.c_int64(-1)
+    assert lib.zafx_plan_live_allocations(ctypes.byref(n)) == 0 and n.value >= 0
+    assert lib.zafx_plan_live_allocations(None) != 0 and b"null" in lib.zafx_last_error()
+
+
 def test_params_struct_layout(built_library):
     from zafx import _lib
     assert ctypes.sizeof(_lib.ZafxParams) == 16 * 4   # 12 fields + 4 reserved int32

@@ -255,7 +255,7 @@ hipError_t by_log2m(int log2m, F&& f) {
 hipError_t launch_ola(zafx_plan& pl, float* y, int64_t n_clips, int T, int hop, int64_t out_len, float scale) {
     const long long total = (long long)n_clips * out_len;
     const long long grid = std::min<long long>((total + 255) / 256, (long long)pl.n_cus * 32);
-    hipLaunchKernelGGL(k_ola_f32, dim3((unsigned)grid), dim3(256), 0, pl.stream, reinterpret_cast<const float*>(pl.d_scratch64), y, T, pl.W, hop,
+    hipLaunchKernelGGL(k_ola_f32, dim3((unsigned)grid), dim3(256), 0, pl.stream, reinterpret_cast<const float*>(pl.d_scratch64.get()), y, T, pl.W, hop,
                        (long long)out_len, total, scale);
     return hipGetLastError();
 }
@@ -297,7 +297,7 @@ hipError_t launch_istft_bs32(zafx_plan& pl, const float2* spec_all, float* y_all
             if (hipError_t e2 = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, BsCfg<L>::SMEM); e2 != hipSuccess) return e2;
             pl.ran = "k_ifft_frames_bs32";
             hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(BsCfg<L>::P), BsCfg<L>::SMEM, pl.stream, spec, pl.d_tw_pass, pl.d_bs_chirp, pl.d_bs_bhat,
-                               reinterpret_cast<float*>(pl.d_scratch64), T, (int)row_pitch(pl, T), pl.W, pl.layout, one, total);
+                               reinterpret_cast<float*>(pl.d_scratch64.get()), T, (int)row_pitch(pl, T), pl.W, pl.layout, one, total);
             return hipGetLastError();
         });
         if (e != hipSuccess) return e;
@@ -353,7 +353,7 @@ hipError_t launch_imdct_bs32(zafx_plan& pl, const float* coefs_all, float* y_all
             if (hipError_t e2 = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, BsCfg<L>::SMEM); e2 != hipSuccess) return e2;
             pl.ran = "k_imdct_frames_bs32";
             hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(BsCfg<L>::P), BsCfg<L>::SMEM, pl.stream, coefs, pl.d_window, pl.d_tw_pass, pl.d_bs_chirp,
-                               pl.d_bs_bhat, pl.d_tw_aux, reinterpret_cast<float*>(pl.d_scratch64), T, (int)row_pitch(pl, T), pl.W, pl.layout, total);
+                               pl.d_bs_bhat, pl.d_tw_aux, reinterpret_cast<float*>(pl.d_scratch64.get()), T, (int)row_pitch(pl, T), pl.W, pl.layout, total);
             return hipGetLastError();
         });
         if (e != hipSuccess) return e;

@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <complex>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <functional>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -19,10 +21,6 @@
 #include "zafx_units.hpp"
 #include "zafx_wfold.hpp"
 #include "zafx_internal.hpp"
-
-#ifndef ZAFX_STFT_FAT8_TABLES
-#define ZAFX_STFT_FAT8_TABLES 0   // pass tables of the W = 4096 persistent STFT experiment (zafx_stft.hip, ZAFX_STFT_FAT8)
-#endif
 
 namespace zafx {
 
@@ -77,18 +75,18 @@ static int ilog2_exact(int v) {
     return l;
 }
 
-template <class T>
-static hipError_t upload(T** dptr, const void* host, size_t bytes) {
-    if (*dptr) {
-        hipError_t e = hipFree(*dptr);
-        *dptr = nullptr;
-        if (e != hipSuccess) return e;
-    }
-    if (bytes == 0) return hipSuccess;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dptr), bytes);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dptr, host, bytes, hipMemcpyHostToDevice);
+// The allocator under DevBuf / PinnedBuf (zafx_devbuf.hpp), with the count of live plan-owned allocations (zafx_plan_live_allocations).
+static std::atomic<long long> g_live_allocations{0};
+static hipError_t counted(hipError_t e, void** p) {
+    if (e == hipSuccess) ++g_live_allocations;
+    else *p = nullptr;
+    return e;
 }
+hipError_t dev_alloc(void** p, size_t bytes) { return counted(hipMalloc(p, bytes), p); }
+hipError_t dev_free(void* p) { return --g_live_allocations, hipFree(p); }
+hipError_t dev_copy_h2d(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+hipError_t pinned_alloc(void** p, size_t bytes) { return counted(hipHostMalloc(p, bytes, hipHostMallocDefault), p); }
+hipError_t pinned_free(void* p) { return --g_live_allocations, hipHostFree(p); }
 
 // ---------------------------------------------------------------------------------
 // MFMA-fragment packing of a banded (rows x cols) matrix: per 16-row block keep only
@@ -209,7 +207,7 @@ static hipError_t pack_band(PackedBand& pb, const float* dense, int n_rows, int 
                     m[2] = q.off;
                     m[3] = q.blk | q.role << 8 | q.slot << 10 | (q.role == 1 ? addmask[(size_t)q.blk] : 0) << 12;
                 }
-            if (hipError_t e = upload(&pb.d_whole, whole.data(), whole.size() * sizeof(int)); e != hipSuccess) return e;
+            if (hipError_t e = pb.d_whole.upload(whole.data(), whole.size() * sizeof(int)); e != hipSuccess) return e;
             pb.h_owner.assign((size_t)pb.n_blocks, 0);
             for (int w = 0; w < 16; ++w)
                 for (int place = 0; place < 2; ++place) {
@@ -242,25 +240,12 @@ static hipError_t pack_band(PackedBand& pb, const float* dense, int n_rows, int 
     if (pack.empty()) pack.push_back(0.f);
     pack.resize(pack.size() + 64 * 2 * (size_t)std::max(kMelResidentFb, kMelResidentDct), 0.f);   // spare steps: k_mel reads a fixed number of fragments per wave
     if (flat.empty()) flat.assign(4, 0);
-    hipError_t e = upload(&pb.d_pack, pack.data(), pack.size() * sizeof(float));
-    if (e == hipSuccess) e = upload(&pb.d_items, flat.data(), flat.size() * sizeof(int));
-    if (e == hipSuccess) e = upload(&pb.d_wave_ptr, wave_ptr.data(), wave_ptr.size() * sizeof(int));
-    if (e == hipSuccess) e = upload(&pb.d_blk_ptr, blk_ptr.data(), blk_ptr.size() * sizeof(int));
-    if (e == hipSuccess) e = upload(&pb.d_desc, desc.data(), desc.size() * sizeof(unsigned short));
+    hipError_t e = pb.d_pack.upload(pack.data(), pack.size() * sizeof(float));
+    if (e == hipSuccess) e = pb.d_items.upload(flat.data(), flat.size() * sizeof(int));
+    if (e == hipSuccess) e = pb.d_wave_ptr.upload(wave_ptr.data(), wave_ptr.size() * sizeof(int));
+    if (e == hipSuccess) e = pb.d_blk_ptr.upload(blk_ptr.data(), blk_ptr.size() * sizeof(int));
+    if (e == hipSuccess) e = pb.d_desc.upload(desc.data(), desc.size() * sizeof(unsigned short));
     return e;
-}
-
-static void free_band(PackedBand& pb) {
-    if (pb.d_pack) (void)hipFree(pb.d_pack);
-    if (pb.d_items) (void)hipFree(pb.d_items);
-    if (pb.d_wave_ptr) (void)hipFree(pb.d_wave_ptr);
-    if (pb.d_blk_ptr) (void)hipFree(pb.d_blk_ptr);
-    if (pb.d_desc) (void)hipFree(pb.d_desc);
-    if (pb.d_direct) (void)hipFree(pb.d_direct);
-    if (pb.d_whole) (void)hipFree(pb.d_whole);
-    if (pb.d_dct2) (void)hipFree(pb.d_dct2);
-    if (pb.d_owner2) (void)hipFree(pb.d_owner2);
-    pb = PackedBand{};
 }
 
 // k_cqt's view of the CQT kernel matrix: rows sorted by length, four per step, steps dealt to the wavefronts.
@@ -338,24 +323,45 @@ static hipError_t build_mel2_dct(zafx_plan* pl) {
                     const int row = 16 * c + (l & 15), col = 16 * b + 4 * st + (l >> 4);
                     if (row < nc && col < nf) frag[(((size_t)b * 2 + c) * 4 + st) * 64 + l] = pl->h_dct[(size_t)row * nf + col];
                 }
-    if (hipError_t e = upload(&d.d_dct2, frag.data(), frag.size() * sizeof(float)); e != hipSuccess) return e;
-    if (hipError_t e = upload(&d.d_owner2, pl->fb.h_owner.data(), pl->fb.h_owner.size() * sizeof(int)); e != hipSuccess) return e;
+    if (hipError_t e = d.d_dct2.upload(frag.data(), frag.size() * sizeof(float)); e != hipSuccess) return e;
+    if (hipError_t e = d.d_owner2.upload(pl->fb.h_owner.data(), pl->fb.h_owner.size() * sizeof(int)); e != hipSuccess) return e;
     d.dct2_ok = true;
     return hipSuccess;
+}
+
+// A filterbank's rows as bands: the values of [first non-zero, last non-zero] of every row back to back, and meta [rows][3] = first column,
+// count, offset into the values.
+template <class T>
+static hipError_t band_rows(const std::vector<T>& dense, int rows, int cols, DevBuf<T>& d_vals, DevBuf<int>& d_meta) {
+    std::vector<int> meta((size_t)rows * 3, 0);
+    std::vector<T> vals;
+    for (int r = 0; r < rows; ++r) {
+        const T* row = &dense[(size_t)r * cols];
+        int lo = 0, hi = cols;
+        while (lo < cols && row[lo] == T(0)) ++lo;
+        while (hi > lo && row[hi - 1] == T(0)) --hi;
+        meta[(size_t)r * 3] = lo;
+        meta[(size_t)r * 3 + 1] = hi - lo;
+        meta[(size_t)r * 3 + 2] = (int)vals.size();
+        vals.insert(vals.end(), row + lo, row + hi);
+    }
+    if (vals.empty()) vals.push_back(T(0));
+    if (hipError_t e = d_vals.upload(vals.data(), vals.size() * sizeof(T)); e != hipSuccess) return e;
+    return d_meta.upload(meta.data(), meta.size() * sizeof(int));
 }
 
 static int finalize_constant(zafx_plan* pl, int which) {
     switch (which) {
         case ZAFX_CONST_WINDOW: {
             if (pl->prm.precision == ZAFX_PRECISION_F64) {
-                ZAFX_HIP(upload(&pl->d_window64, pl->h_window64.data(), pl->h_window64.size() * sizeof(double)));
+                ZAFX_HIP(pl->d_window64.upload(pl->h_window64.data(), pl->h_window64.size() * sizeof(double)));
                 long double g = 0;   // zaf.py:241  sum(window_function[0:W:H])
                 for (int i = 0; i < pl->W; i += pl->H) g += (long double)pl->h_window64[(size_t)i];
                 pl->cola_gain64 = (double)g;
                 pl->cola_gain = (float)g;
                 return 0;
             }
-            ZAFX_HIP(upload(&pl->d_window, pl->h_window.data(), pl->h_window.size() * sizeof(float)));
+            ZAFX_HIP(pl->d_window.upload(pl->h_window.data(), pl->h_window.size() * sizeof(float)));
             double g = 0;   // zaf.py:241  sum(window_function[0:W:H])
             if (pl->H > 0)
                 for (int i = 0; i < pl->W; i += pl->H) g += (double)pl->h_window[(size_t)i];
@@ -364,48 +370,18 @@ static int finalize_constant(zafx_plan* pl, int which) {
                 // sign-folded window for the fold + pack step of k_mdct_ft32: packed input m reads taps
                 // (a, b | c, d); re = x[a] w0 + x[b] w1, im = x[c] w2 + x[d] w3 (zafx_wfold.hpp)
                 const std::vector<float> wf = zafx::mdct_fold_window(pl->h_window.data(), pl->W);
-                ZAFX_HIP(upload(&pl->d_wfold, wf.data(), wf.size() * sizeof(float)));
+                ZAFX_HIP(pl->d_wfold.upload(wf.data(), wf.size() * sizeof(float)));
             }
             return 0;
         }
         case ZAFX_CONST_MEL_FB:
-            if (pl->prm.precision == ZAFX_PRECISION_F64) {   // rows as bands [first non-zero, last non-zero]
-                const int rows = pl->prm.n_filters, cols = pl->W / 2;
-                std::vector<int> meta((size_t)rows * 3, 0);
-                std::vector<double> vals;
-                for (int r = 0; r < rows; ++r) {
-                    const double* row = &pl->h_fb64[(size_t)r * cols];
-                    int lo = 0, hi = cols;
-                    while (lo < cols && row[lo] == 0.0) ++lo;
-                    while (hi > lo && row[hi - 1] == 0.0) --hi;
-                    meta[(size_t)r * 3] = lo;
-                    meta[(size_t)r * 3 + 1] = hi - lo;
-                    meta[(size_t)r * 3 + 2] = (int)vals.size();
-                    vals.insert(vals.end(), row + lo, row + hi);
-                }
-                if (vals.empty()) vals.push_back(0.0);
-                ZAFX_HIP(upload(&pl->d_fb64, vals.data(), vals.size() * sizeof(double)));
-                ZAFX_HIP(upload(&pl->d_fb64_meta, meta.data(), meta.size() * sizeof(int)));
+            if (pl->prm.precision == ZAFX_PRECISION_F64) {
+                ZAFX_HIP(band_rows(pl->h_fb64, pl->prm.n_filters, pl->W / 2, pl->d_fb64, pl->d_fb64_meta));
                 ZAFX_HIP(zafx::build_mel64_fb(*pl));
                 return 0;
             }
-            if (zafx::mel_takes_wide_route(*pl)) {   // W = 4096 / 8192, windows that are not a power of two, more than 256 filters (k_melfb): rows as float32 bands
-                const int rows = pl->prm.n_filters, cols = pl->W / 2;
-                std::vector<int> meta((size_t)rows * 3, 0);
-                std::vector<float> vals;
-                for (int r = 0; r < rows; ++r) {
-                    const float* row = &pl->h_fb[(size_t)r * cols];
-                    int lo = 0, hi = cols;
-                    while (lo < cols && row[lo] == 0.f) ++lo;
-                    while (hi > lo && row[hi - 1] == 0.f) --hi;
-                    meta[(size_t)r * 3] = lo;
-                    meta[(size_t)r * 3 + 1] = hi - lo;
-                    meta[(size_t)r * 3 + 2] = (int)vals.size();
-                    vals.insert(vals.end(), row + lo, row + hi);
-                }
-                if (vals.empty()) vals.push_back(0.f);
-                ZAFX_HIP(upload(&pl->d_fbw, vals.data(), vals.size() * sizeof(float)));
-                ZAFX_HIP(upload(&pl->d_fbw_meta, meta.data(), meta.size() * sizeof(int)));
+            if (zafx::mel_takes_wide_route(*pl)) {   // W = 4096 / 8192, windows that are not a power of two, more than 256 filters (k_melfb)
+                ZAFX_HIP(band_rows(pl->h_fb, pl->prm.n_filters, pl->W / 2, pl->d_fbw, pl->d_fbw_meta));
                 return 0;
             }
             {
@@ -420,12 +396,12 @@ static int finalize_constant(zafx_plan* pl, int which) {
             return 0;
         case ZAFX_CONST_DCT:
             if (pl->prm.precision == ZAFX_PRECISION_F64) {
-                ZAFX_HIP(upload(&pl->d_dct64, pl->h_dct64.data(), pl->h_dct64.size() * sizeof(double)));
+                ZAFX_HIP(pl->d_dct64.upload(pl->h_dct64.data(), pl->h_dct64.size() * sizeof(double)));
                 ZAFX_HIP(zafx::build_mel64_dct(*pl));
                 return 0;
             }
             if (zafx::mel_takes_wide_route(*pl)) {   // (k_melfb): dense rows
-                ZAFX_HIP(upload(&pl->d_dctw, pl->h_dct.data(), pl->h_dct.size() * sizeof(float)));
+                ZAFX_HIP(pl->d_dctw.upload(pl->h_dct.data(), pl->h_dct.size() * sizeof(float)));
                 return 0;
             }
             ZAFX_HIP(pack_band(pl->dct, pl->h_dct.data(), pl->prm.n_coefs, pl->prm.n_filters, mel_waves(pl->log2nf)));
@@ -446,33 +422,33 @@ static int finalize_constant(zafx_plan* pl, int which) {
                                     const int row = 16 * b + (l & 15), col = 4 * (w + nw * j) + (l >> 4);
                                     if (row < nc && col < nf) frag[(((size_t)w * 2 + j) * 2 + b) * 64 + l] = pl->h_dct[(size_t)row * nf + col];
                                 }
-                    ZAFX_HIP(upload(&d.d_direct, frag.data(), frag.size() * sizeof(float)));
+                    ZAFX_HIP(d.d_direct.upload(frag.data(), frag.size() * sizeof(float)));
                     d.direct_j = 2;
                 }
             }
             ZAFX_HIP(build_mel2_dct(pl));
             return 0;
         case ZAFX_CONST_MATRIX:
-            ZAFX_HIP(upload(&pl->d_matrix, pl->h_matrix.data(), pl->h_matrix.size() * sizeof(float)));
+            ZAFX_HIP(pl->d_matrix.upload(pl->h_matrix.data(), pl->h_matrix.size() * sizeof(float)));
             return 0;
         case ZAFX_CONST_CQT_INDPTR:
-            ZAFX_HIP(upload(&pl->d_indptr, pl->h_indptr.data(), pl->h_indptr.size() * sizeof(int32_t)));
+            ZAFX_HIP(pl->d_indptr.upload(pl->h_indptr.data(), pl->h_indptr.size() * sizeof(int32_t)));
             pl->cqt_dirty = true;
             pl->cqt64_dirty = true;
             return 0;
         case ZAFX_CONST_CQT_INDICES:
-            ZAFX_HIP(upload(&pl->d_indices, pl->h_indices.data(), pl->h_indices.size() * sizeof(int32_t)));
+            ZAFX_HIP(pl->d_indices.upload(pl->h_indices.data(), pl->h_indices.size() * sizeof(int32_t)));
             pl->nnz = (int)pl->h_indices.size();
             pl->cqt_dirty = true;
             pl->cqt64_dirty = true;
             return 0;
         case ZAFX_CONST_CQT_VALUES:
             if (pl->prm.precision == ZAFX_PRECISION_F64) {
-                ZAFX_HIP(upload(&pl->d_values64, pl->h_values64.data(), pl->h_values64.size() * sizeof(double2)));
+                ZAFX_HIP(pl->d_values64.upload(pl->h_values64.data(), pl->h_values64.size() * sizeof(double2)));
                 pl->cqt64_dirty = true;
                 return 0;
             }
-            ZAFX_HIP(upload(&pl->d_values, pl->h_values.data(), pl->h_values.size() * sizeof(cf32)));
+            ZAFX_HIP(pl->d_values.upload(pl->h_values.data(), pl->h_values.size() * sizeof(cf32)));
             pl->cqt_dirty = true;   // (k_cqt reads the tables build_cqt_chunks packs from h_values, and cqt_real is decided there)
             return 0;
     }
@@ -580,9 +556,9 @@ static int build_cqt_chunks(zafx_plan* pl) {
     pl->cqt_k_hi = k_hi;
     pl->cqt_k_special = special;
     if (addrs.empty()) addrs.assign(64, 0), vals.assign(pl->cqt_real ? 64 : 128, 0.f);
-    ZAFX_HIP(upload(&pl->d_cqt_addrs, addrs.data(), addrs.size() * sizeof(int32_t)));
-    ZAFX_HIP(upload(&pl->d_cqt_vals, vals.data(), vals.size() * sizeof(float)));
-    ZAFX_HIP(upload(&pl->d_cqt_waves, wave_tab.data(), wave_tab.size() * sizeof(int)));
+    ZAFX_HIP(pl->d_cqt_addrs.upload(addrs.data(), addrs.size() * sizeof(int32_t)));
+    ZAFX_HIP(pl->d_cqt_vals.upload(vals.data(), vals.size() * sizeof(float)));
+    ZAFX_HIP(pl->d_cqt_waves.upload(wave_tab.data(), wave_tab.size() * sizeof(int)));
     if (int rc = build_cqt_mm(pl, n_waves)) return rc;
     pl->cqt_dirty = false;
     return 0;
@@ -714,9 +690,9 @@ static int build_cqt_mm(zafx_plan* pl, int n_waves) {
             }
         }
     }
-    ZAFX_HIP(upload(&pl->d_cqt_mm_vals, vals.data(), vals.size() * sizeof(float)));
-    ZAFX_HIP(upload(&pl->d_cqt_mm_addr, addr.data(), addr.size() * sizeof(int32_t)));
-    ZAFX_HIP(upload(&pl->d_cqt_mm_fin, fin.data(), fin.size() * sizeof(int32_t)));
+    ZAFX_HIP(pl->d_cqt_mm_vals.upload(vals.data(), vals.size() * sizeof(float)));
+    ZAFX_HIP(pl->d_cqt_mm_addr.upload(addr.data(), addr.size() * sizeof(int32_t)));
+    ZAFX_HIP(pl->d_cqt_mm_fin.upload(fin.data(), fin.size() * sizeof(int32_t)));
     pl->cqt_mm_steps = S;
     return 0;
 }
@@ -889,8 +865,18 @@ int zafx_host_free(void* hptr) {
     return 0;
 }
 
-int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* params) {
-    if (!out || !params) return fail_msg("null argument");
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// Plan creation in steps (zafx_plan_create): check_params, the family's geometry, planned_kernel_name, then the tables --
+// build_tables_f32 for every plan, build_tables_bs32 / build_tables_f64 on top for the plans that have them.
+// ---------------------------------------------------------------------------------
+namespace {
+
+#define ZAFX_TRY(call) do { if (hipError_t e__ = (call); e__ != hipSuccess) return e__; } while (0)
+
+// Every check that needs neither a plan nor a device.
+int check_params(int kind, const zafx_params* params) {
     if (params->struct_size != (int32_t)sizeof(zafx_params)) return fail_msg("zafx_params.struct_size mismatch");
     if (params->layout != ZAFX_LAYOUT_FT && params->layout != ZAFX_LAYOUT_TF) return fail_msg("bad layout");
     if (params->spectrum < ZAFX_SPECTRUM_TWO_SIDED || params->spectrum > ZAFX_SPECTRUM_POWER) return fail_msg("bad spectrum");
@@ -905,411 +891,421 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
         return fail_msg("row_align must be 0 or a power of two <= 1024");
     if (params->row_align > 1 && (params->layout != ZAFX_LAYOUT_FT || kind == ZAFX_LINEAR || kind == ZAFX_DCT))
         return fail_msg("row_align applies to the 2-D arrays of ZAFX_LAYOUT_FT plans only");
-    if (is_center_kind(kind))
-        if (int rc = check_center_params(params)) return rc;
-    {
-        int n_dev = 0;
-        ZAFX_HIP(hipGetDeviceCount(&n_dev));
-        if (device < 0 || device >= n_dev) return fail_msg("device index out of range");
+    if (is_center_kind(kind)) return check_center_params(params);
+    return 0;
+}
+
+// The geometry of a family: W, H, log2nf, bs_log2m, dct_half, dct_den2 and the table that goes to d_tw_aux.  -> what is wrong, or nullptr.
+void bluestein_length(zafx_plan& pl, int points) {   // convolution length 2^bs_log2m >= 2 points - 1
+    while ((1 << pl.bs_log2m) < 2 * points - 1) ++pl.bs_log2m;
+}
+// log2 of a family's window -- for the lengths that take a Bluestein form instead (bs_log2m set: in float64 any length from `least` to 2048
+// that is no power of two >= 64, in float32 the lengths of zafx_bs32.hip; `even`: the MDCT's) 6, which only sizes the unused tables of the
+// tiled kernels; -1: not a length of this family.  `sub`: log2(W) - log2nf.
+int window_log2(zafx_plan& pl, int least, bool even, bool (*supported)(int), int sub) {
+    const bool parity_ok = !even || pl.W % 2 == 0;
+    const int lw = ilog2_exact(pl.W);
+    if (pl.prm.precision == ZAFX_PRECISION_F64 ? lw < 6 && pl.W >= least && pl.W <= 2048 && parity_ok : lw < 0 && parity_ok && bs32_supported(pl.W)) {
+        bluestein_length(pl, pl.W);
+        return 6;
     }
-    zafx_plan* pl = new zafx_plan();
+    return lw >= 0 && supported(lw - sub) ? lw : -1;
+}
+
+const char* stft_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
+    const zafx_params& prm = pl.prm;
+    const int kind = pl.kind;
+    pl.W = prm.window_length;
+    pl.H = prm.step_length;
+    // (float32 Bluestein forms of MEL / MFCC: the Bluestein STFT's magnitude / power kind + k_melfb, run_mel_wide)
+    const int lw = window_log2(pl, 2, false, stft_supported, 1);
+    if (lw < 0)
+        return "window_length must be a power of two in [64, 8192] or any other length in [33, 8192] "
+               "(any length in [2, 2048] with ZAFX_PRECISION_F64)";
+    if (pl.H < 1) return "step_length must be >= 1";
+    if (kind == ZAFX_ISTFT && pl.H > pl.W) return "istft: step_length must not exceed window_length";
+    if (pl.H > (1 << 20)) return "step_length must not exceed 2^20";
+    if (kind == ZAFX_ISTFT && prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && bs32_supported(pl.W)) {
+        // A hop so small that more frames cover a sample than the tiled overlap-add keeps in LDS (16): the frames + gather
+        // overlap-add form of zafx_bs32.hip has no such limit and takes any length, powers of two included.
+        const int tile = pl.W <= 2048 ? 16 : pl.W == 4096 ? 8 : 4;   // frames of the tiled kernel's LDS tile
+        if ((pl.W + pl.H - 1) / pl.H > tile) bluestein_length(pl, pl.W);
+    }
+    pl.log2nf = lw - 1;
+    if (kind == ZAFX_MEL || kind == ZAFX_MFCC) {
+        // (float32: up to 256 rows on the fused kernels; above that the spectrum kernel + k_melfb route, whose mfcc form holds a
+        // [n_filters][64] log-mel tile in LDS: 576 rows)
+        if (prm.n_filters < 1 || (prm.precision != ZAFX_PRECISION_F64 && prm.n_filters > 576))
+            return "n_filters must be in [1, 576] (up to window_length / 2 with ZAFX_PRECISION_F64)";
+        if (prm.with_mel != 0 && (prm.with_mel != 1 || kind != ZAFX_MFCC || prm.precision != ZAFX_PRECISION_F32 || prm.window_length != 2048 ||
+                                  prm.n_filters > 128 || prm.n_coefs > 32))
+            return "with_mel (melspectrogram + mfcc in one pass) takes a float32 ZAFX_MFCC plan of window_length 2048, up to 128 filters and up to 32 coefficients";
+        if (kind == ZAFX_MFCC && (prm.n_coefs < 1 || prm.n_coefs > prm.n_filters)) return "n_coefs must be in [1, n_filters]";
+        if (prm.precision == ZAFX_PRECISION_F64) {
+            if (prm.n_filters > std::max(pl.W / 2, 1)) return "n_filters must not exceed window_length / 2";
+        } else if (lw - 1 < 5 || lw - 1 > 12) {
+            return "float32 mel/mfcc kernels are built for window_length 64 ... 8192 (any power of two with ZAFX_PRECISION_F64)";
+        }
+    }
+    const int n = pl.W / 2;
+    aux.resize((size_t)n / 2 + 1);
+    for (int k = 0; k <= n / 2; ++k) aux[(size_t)k] = unit_root(k, pl.W);
+    return nullptr;
+}
+
+const char* center_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
+    pl.W = pl.prm.window_length;
+    pl.H = pl.prm.step_length;
+    pl.log2nf = ilog2_exact(pl.W);   // a stereo sample frame is one complex point: W-point transforms
+    aux.assign(1, cf32{1.f, 0.f});
+    return nullptr;
+}
+
+const char* mdct_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
+    pl.W = pl.prm.window_length;
+    pl.H = pl.W / 2;   // zaf.py:1029
+    const int lw = window_log2(pl, 4, true, mdct_supported, 2);
+    if (lw < 0)
+        return "window_length must be a power of two in [64, 8192] or any even length in [34, 8192] "
+               "(any even length in [4, 2048] with ZAFX_PRECISION_F64)";
+    pl.log2nf = lw - 2;
+    const int nf = pl.W / 4, m = pl.W / 2;
+    aux.resize((size_t)nf);
+    for (int i = 0; i < nf; ++i) aux[(size_t)i] = unit_root(8LL * i + 1, 16LL * m);
+    return nullptr;
+}
+
+const char* cqt_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
+    const zafx_params& prm = pl.prm;
+    pl.W = prm.fft_length;
+    pl.H = prm.step_length;
+    const int lw = ilog2_exact(pl.W);
+    if (prm.precision == ZAFX_PRECISION_F64) {   // k_cqt_f64 decimates the frame: no LDS limit on its length
+        if (lw < 9 || lw > 17) return "fft_length must be a power of two in [512, 131072] (ZAFX_PRECISION_F64 plan)";
+    } else if (lw < 0 || !cqt_supported(lw - 1)) {
+        return "fft_length must be a power of two in [512, 65536] (up to 131072 with ZAFX_PRECISION_F64)";
+    }
+    if (pl.H < 1) return "step_length must be >= 1";
+    if (prm.n_bins < 1 || prm.n_bins > 1024) return "n_bins must be in [1, 1024]";
+    if (pl.kind == ZAFX_CHROMA && (prm.octave_resolution < 1 || prm.octave_resolution > prm.n_bins)) return "octave_resolution must be in [1, n_bins]";
+    pl.log2nf = lw - 1;
+    aux = build_split_two_level_twiddles(pl.log2nf);   // exp(-2 pi i k / W), k < W/4, as hi[k >> 7] * lo[k & 127]
+    return nullptr;
+}
+
+const char* linear_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
+    pl.W = pl.prm.window_length;
+    if (pl.W < 1 || pl.W > 16384 || pl.prm.n_filters < 1 || pl.prm.n_filters > 16384)
+        return "linear map: window_length (columns) and n_filters (rows) must be in [1, 16384]";
+    pl.log2nf = 4;   // only so that the (unused) FFT tables are small
+    aux.assign(1, cf32{1.f, 0.f});
+    return nullptr;
+}
+
+// zaf.dct / zaf.dst on the FFT core (zafx_dct.hip): M complex points per vector, tables A | B of M + 1 entries each
+const char* dct_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
+    const int N = pl.prm.window_length, type = pl.prm.transform_type;
+    const bool sine = pl.prm.transform_sine != 0;
+    if (type < 1 || type > 4) return "transform_type must be 1, 2, 3 or 4";
+    if (pl.prm.transform_sine != 0 && pl.prm.transform_sine != 1) return "transform_sine must be 0 (dct) or 1 (dst)";
+    if (N < 2) return "dct / dst: window_length must be at least 2";
+    const int M = type == 1 ? (sine ? N + 1 : N - 1) : (N % 2 == 0 ? N / 2 : -1);
+    const int lm = ilog2_exact(M);
+    pl.W = N;
+    auto tables_ab = [&](int m) {
+        aux.resize(2 * (size_t)(m + 1));
+        for (int k = 0; k <= m; ++k) {
+            aux[(size_t)k] = type == 4 ? unit_root(4LL * k + 1, 8LL * N) : unit_root(k, 2LL * m);
+            aux[(size_t)(m + 1 + k)] = type == 4 ? unit_root(k, 2LL * N) : unit_root(k, 4LL * N);
+        }
+    };
+    if (lm >= 0 && dct_supported(lm)) {
+        pl.log2nf = lm;
+        tables_ab(M);
+    } else if (type >= 2 && N % 4 == 0 && N <= 8192) {
+        // N / 2 points, not a power of two (round 6): k_dct's maps around a Bluestein convolution of 2^bs_log2m >= 2 (N / 2) - 1 points --
+        // half the transform length of the chirp-z sum below (zafx_dct.hip, BS = true); tables A | B as above, chirp and its transform: build_tables_bs32
+        const int Mh = N / 2;
+        pl.dct_half = Mh;
+        pl.dct_den2 = Mh;   // (the chirp of an Mh-point DFT: exp(-i pi m^2 / Mh))
+        pl.log2nf = 4;
+        pl.bs_log2m = 7;
+        bluestein_length(pl, Mh);
+        tables_ab(Mh);
+    } else if (N <= 8192) {
+        // Every other length (the reference's np.fft.fft takes any, zaf.py:760-839, :900-981): all eight transforms are
+        //     y[k] = s_out[k] sum_n s_in[n] x[n] cos | sin(pi (n + a)(k + b) / D),   a, b in {0, 1/2, 1},  D = N - 1 | N | N + 1,
+        // and with n k = (n^2 + k^2 - (k - n)^2) / 2 the sum is a convolution with a chirp of step pi / D (a chirp-z transform):
+        //     y[k] = Re(Q[k] sum_n (x[n] P[n]) conj(c)[k - n]),   c[j] = exp(-i pi j^2 / (2 D)),
+        //     P[n] = s_in[n] exp(-i pi n b / D) c[n],   Q[k] = s_out[k] exp(-i pi (a k + a b) / D) c[k]  (x i for the sines),
+        // on the Bluestein machinery of zafx_bs32.hip (k_dct_bs32: two transforms of 2^ceil(log2(2N - 1)) points per vector instead of
+        // the dense N x N product of round 4).  Angles in units of pi / (4 D), reduced in integers.
+        const int a2 = sine ? (type == 1 ? 2 : type == 3 ? 2 : 1) : (type == 2 || type == 4 ? 1 : 0);   // 2 a
+        const int b2 = sine ? (type == 1 ? 2 : type == 2 ? 2 : 1) : (type == 3 || type == 4 ? 1 : 0);   // 2 b
+        const long long D = type == 1 ? (sine ? N + 1 : N - 1) : N;
+        pl.dct_den2 = 2 * D;
+        pl.log2nf = 4;   // (the FFT tables are those of the convolution length: build_tables_bs32)
+        pl.bs_log2m = 7;
+        bluestein_length(pl, N);
+        const double L = (double)(1 << pl.bs_log2m), s = std::sqrt(2.0 / (double)D), r2 = std::sqrt(0.5);
+        aux.resize(2 * (size_t)N);
+        for (long long n = 0; n < N; ++n) {
+            double sin_ = 1.0, sout = s;
+            if (type == 1 && !sine && (n == 0 || n == N - 1)) sin_ = r2, sout = s * r2;
+            if (type == 2 && (sine ? n == N - 1 : n == 0)) sout = s * r2;
+            if (type == 3 && (sine ? n == N - 1 : n == 0)) sin_ = r2;
+            auto root = [&](long long m, double scale) {   // scale exp(-i pi m / (4 D)), in float64, exact on the axes
+                m %= 8 * D;
+                const double ang = M_PI * (double)m / (double)(4 * D);
+                double c = std::cos(ang), sn = -std::sin(ang);
+                if (m % (2 * D) == 0) {
+                    const int quarter = (int)(m / (2 * D));
+                    c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
+                    sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
+                }
+                return cf32{(float)(scale * c), (float)(scale * sn)};
+            };
+            aux[(size_t)n] = root(2 * n * b2 + 2 * n * n, sin_);
+            aux[(size_t)(N + n)] = root(2 * n * a2 + a2 * b2 + 2 * n * n + (sine ? 6 * D : 0), sout / L);   // (x i = exp(-i pi 6 D / (4 D)))
+        }
+    } else {
+        return "dct / dst: lengths above 8192 need N / 2 (types 2-4), N - 1 (dct type 1) or N + 1 (dst type 1) to be a power of two (at most 8192)";
+    }
+    return nullptr;
+}
+
+// The kernel a plan is expected to run: the one place that decides it.  The float64 forms first, then the float32 Bluestein forms,
+// then the family's tiled kernels.
+std::string planned_kernel_name(const zafx_plan& pl) {
+    const int kind = pl.kind;
+    const bool mel = kind == ZAFX_MEL || kind == ZAFX_MFCC, bluestein = pl.bs_log2m > 0;
+    if (pl.prm.precision == ZAFX_PRECISION_F64) {
+        if (bluestein)
+            return kind == ZAFX_ISTFT ? "k_ifft_frames_bs_f64" : kind == ZAFX_MDCT ? "k_mdct_bs_f64" : kind == ZAFX_IMDCT ? "k_imdct_frames_bs_f64" : "k_stft_bs_f64";
+        return kind == ZAFX_STFT ? stft_f64_kernel_name() : kind == ZAFX_ISTFT ? istft_f64_kernel_name() : kind == ZAFX_MDCT ? mdct_f64_kernel_name()
+               : kind == ZAFX_IMDCT ? imdct_f64_kernel_name() : is_cqt_family(kind) ? cqt_f64_kernel_name() : mel_f64_kernel_name();
+    }
+    if (bluestein)
+        return kind == ZAFX_DCT ? (pl.dct_half > 0 ? "k_dct_bsh" : "k_dct_bs32") : kind == ZAFX_STFT ? "k_stft_bs32" : kind == ZAFX_ISTFT ? "k_ifft_frames_bs32"
+               : kind == ZAFX_MDCT ? "k_mdct_bs32" : mel ? mel_wide_kernel_name() : "k_imdct_frames_bs32";
+    if (kind == ZAFX_STFT) return stft_kernel_name(pl.log2nf, pl.layout);
+    if (kind == ZAFX_ISTFT) return istft_kernel_name(pl.log2nf, pl.layout);
+    if (mel) return pl.prm.n_filters > 256 ? mel_wide_kernel_name() : pl.log2nf == 11 ? "k_mel_ft16b" : pl.log2nf >= 12 ? mel_wide_kernel_name() : mel_kernel_name();
+    if (is_center_kind(kind)) return center_kernel_name();
+    if (kind == ZAFX_MDCT) return mdct_kernel_name(pl.log2nf, pl.layout);
+    if (kind == ZAFX_IMDCT) return imdct_kernel_name();
+    if (is_cqt_family(kind)) return cqt_kernel_name();
+    if (kind == ZAFX_LINEAR) return linear_kernel_name();
+    return dct_kernel_name();
+}
+
+// The float32 plans of W = 4096 / 8192 run their transform as sub-transforms: pass twiddles build_pass_twiddles(sub_log2n, sub_log2e) in
+// d_tw_sub and, to join them, `quad_count` roots exp(-2 pi i n / quad_den) in d_tw_quad or the band table of k_mdct_ft32b in d_tw_band.
+constexpr unsigned kind_bit(int kind) { return 1u << kind; }
+constexpr unsigned kStftKinds = kind_bit(ZAFX_STFT) | kind_bit(ZAFX_ISTFT) | kind_bit(ZAFX_MEL) | kind_bit(ZAFX_MFCC);
+struct SubRule {
+    unsigned kinds;
+    int log2nf;
+    bool bluestein_too;   // also the plans that take the Bluestein form at this size
+    int sub_log2n, sub_log2e;
+    int quad_count, quad_den;
+    bool band;
+};
+constexpr SubRule kSubRules[] = {
+    {kStftKinds, 11, true, 10, 4, 0, 0, false},                 // k_stft_ft16b: the two 1024-point band transforms
+    {kStftKinds, 12, false, 10, 4, 4096, 8192, false},          // k_stft_ft16q: four 1024-point class transforms, and the roots that form their inputs
+    {kind_bit(ZAFX_MDCT), 11, false, 9, 3, 2048, 2048, false},  // k_mdct_ft32q: four 512-point band transforms
+    {kind_bit(ZAFX_IMDCT), 11, false, 10, 4, 2048, 2048, false},   // k_imdct_q: two 1024-point class transforms, and the roots that join them
+    {kind_bit(ZAFX_MDCT), 10, false, 9, 3, 0, 0, true},         // k_mdct_ft32b: two 512-point band transforms
+};
+
+hipError_t build_tables_f32(zafx_plan& pl, const std::vector<cf32>& aux) {
+    const int kind = pl.kind;
+    const bool f32 = pl.prm.precision == ZAFX_PRECISION_F32;
+    auto tw = is_cqt_family(kind) ? build_two_level_twiddles(pl.log2nf) : build_pass_twiddles(pl.log2nf, pl.log2e);
+    if (is_cqt_family(kind) && cqt_split(pl.log2nf)) {   // + the pass tables of the 1024-point sub-transforms
+        const auto sub = build_pass_twiddles(10, 4);
+        tw.insert(tw.end(), sub.begin(), sub.end());
+    }
+    if (tw.empty()) tw.push_back(cf32{1.f, 0.f});
+    ZAFX_TRY(pl.d_tw_pass.upload(tw.data(), tw.size() * sizeof(cf32)));
+    if ((kind == ZAFX_STFT || kind == ZAFX_MEL || kind == ZAFX_MFCC) && pl.log2nf == 10) {
+        const auto tw5 = build_pass_twiddles(pl.log2nf, 5);
+        ZAFX_TRY(pl.d_tw_r32.upload(tw5.data(), tw5.size() * sizeof(cf32)));
+    }
+    if (kind == ZAFX_STFT && f32) {
+        // k_stft_ft16 with its tiles claimed at run time: the plan's counters, zero from here on between launches
+        const std::vector<int> zeros((size_t)zafx::kClaimInts, 0);
+        ZAFX_TRY(pl.d_claim.upload(zeros.data(), zeros.size() * sizeof(int)));
+        const char* sw = std::getenv("ZAFX_STFT_DYNAMIC");   // 0: the static split (to time both forms in one process: tools/stft_dyn_ab.py)
+        pl.stft_dynamic = !(sw && sw[0] == '0' && sw[1] == 0);
+    }
+    for (const SubRule& r : kSubRules) {
+        if (!f32 || !(r.kinds & kind_bit(kind)) || r.log2nf != pl.log2nf || (pl.bs_log2m > 0 && !r.bluestein_too)) continue;
+        const auto sub = build_pass_twiddles(r.sub_log2n, r.sub_log2e);
+        ZAFX_TRY(pl.d_tw_sub.upload(sub.data(), sub.size() * sizeof(cf32)));
+        if (r.quad_count) {
+            std::vector<cf32> q((size_t)r.quad_count);
+            for (int n = 0; n < r.quad_count; ++n) q[(size_t)n] = unit_root(n, r.quad_den);
+            ZAFX_TRY(pl.d_tw_quad.upload(q.data(), q.size() * sizeof(cf32)));
+        }
+        if (r.band) {   // g in band-major order, gb[s][q] = g[2 q + s], then bt[n] = g[n] exp(-2 pi i n / 1024)
+            const int nf = pl.W / 4;
+            std::vector<cf32> bt((size_t)nf + nf / 2);
+            for (int s = 0; s < 2; ++s)
+                for (int q = 0; q < nf / 2; ++q) bt[(size_t)s * (nf / 2) + q] = unit_root(8LL * (2 * q + s) + 1, 8LL * pl.W);
+            for (int n = 0; n < nf / 2; ++n) bt[(size_t)nf + n] = unit_root(40LL * n + 1, 32LL * nf);
+            ZAFX_TRY(pl.d_tw_band.upload(bt.data(), bt.size() * sizeof(cf32)));
+        }
+    }
+    return pl.d_tw_aux.upload(aux.data(), aux.size() * sizeof(cf32));
+}
+
+// float32 Bluestein plan (zafx_bs32.hip): the pass twiddles of the convolution length replace the family's, the chirp and its transform,
+// and for the MDCT family the pre / post twiddles of the reference's own W-point formulation (zaf.py:1047-1056, :1138-1156) replace d_tw_aux.
+// (build_tables_f32 has uploaded both tables it replaces: a Bluestein plan makes the same allocations, in the same order, as it always did.)
+hipError_t build_tables_bs32(zafx_plan& pl) {
+    const int kind = pl.kind;
+    const int M = 1 << pl.bs_log2m, W = pl.dct_half > 0 ? pl.dct_half : pl.W, F = W / 2;   // (W: the points of the transform that is convolved)
+    auto twm = build_pass_twiddles(pl.bs_log2m, default_log2e(pl.bs_log2m));
+    if (twm.empty()) twm.push_back(cf32{1.f, 0.f});
+    ZAFX_TRY(pl.d_tw_pass.upload(twm.data(), twm.size() * sizeof(cf32)));
+    std::vector<cld> c, b;
+    bluestein_tables(W, kind == ZAFX_DCT ? pl.dct_den2 : (long long)W, pl.bs_log2m, c, b);
+    std::vector<cf32> cf((size_t)W), bf((size_t)M);
+    for (int i = 0; i < W; ++i) cf[(size_t)i] = cf32{(float)c[(size_t)i].real(), (float)c[(size_t)i].imag()};
+    for (int i = 0; i < M; ++i) bf[(size_t)i] = cf32{(float)b[(size_t)i].real(), (float)b[(size_t)i].imag()};
+    ZAFX_TRY(pl.d_bs_chirp.upload(cf.data(), cf.size() * sizeof(cf32)));
+    ZAFX_TRY(pl.d_bs_bhat.upload(bf.data(), bf.size() * sizeof(cf32)));
+    if (is_mdct_family(kind)) {
+        std::vector<cf32> pp;
+        if (kind == ZAFX_MDCT) {
+            for (int n = 0; n < W; ++n) pp.push_back(unit_root(n, 2LL * W));                                  // exp(-i pi n / W)
+            for (int k = 0; k < F; ++k) pp.push_back(unit_root((long long)(F + 1) * (2 * k + 1), 4LL * W));   // exp(-i pi (F+1)(2k+1) / (2W))
+        } else {
+            for (int k = 0; k < F; ++k) pp.push_back(unit_root((long long)(F + 1) * k, 2LL * W));             // exp(-i pi (F+1) k / W)
+            for (int n = 0; n < W; ++n) pp.push_back(unit_root(2LL * n + 1 + F, 4LL * W));                    // exp(-i pi (2n+1+F) / (2W))
+        }
+        ZAFX_TRY(pl.d_tw_aux.upload(pp.data(), pp.size() * sizeof(cf32)));
+    }
+    return hipSuccess;
+}
+
+// float64 tables, evaluated in long double
+hipError_t build_tables_f64(zafx_plan& pl) {
+    const bool mdct = is_mdct_family(pl.kind), cqt = is_cqt_family(pl.kind);
+    const int n = mdct ? pl.W / 4 : cqt ? std::min(pl.W, kCqt64Sub) : pl.W / 2;   // FFT length (CQT: of one decimated sub-sequence)
+    auto root = [](long long num, long long den) {
+        const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)(num % den) / (long double)den;
+        double2 r = make_double2((double)cosl(a), (double)sinl(a));
+        if (num % den == 0) r = make_double2(1.0, 0.0);
+        if (4 * (num % den) == den) r = make_double2(0.0, -1.0);
+        if (2 * (num % den) == den) r = make_double2(-1.0, 0.0);
+        return r;
+    };
+    std::vector<double2> tw((size_t)std::max(n / 2, 1)), tws((size_t)(mdct ? n : cqt ? pl.W : n / 2 + 1));
+    for (int m = 0; m < n / 2; ++m) tw[(size_t)m] = root(m, n);
+    if (pl.bs_log2m > 0) {   // Bluestein: roots of M, the chirp c[n] = exp(-i pi n^2 / W), and FFT_M of its wrapped conjugate
+        const int M = 1 << pl.bs_log2m, W = pl.W;
+        tw.assign((size_t)M / 2, make_double2(0, 0));
+        for (int m = 0; m < M / 2; ++m) tw[(size_t)m] = root(m, M);
+        tws.assign((size_t)W, make_double2(0, 0));
+        for (long long k = 0; k < W; ++k) tws[(size_t)k] = root((k * k) % (2LL * W), 2LL * W);
+        std::vector<cld> c, b;
+        bluestein_tables(W, (long long)W, pl.bs_log2m, c, b);
+        std::vector<double2> bhat((size_t)M);
+        for (int i = 0; i < M; ++i) bhat[(size_t)i] = make_double2((double)b[(size_t)i].real(), (double)b[(size_t)i].imag());
+        ZAFX_TRY(pl.d_bhat64.upload(bhat.data(), bhat.size() * sizeof(double2)));
+    } else if (mdct) {   // g_m = exp(-i pi (8m+1) / (8M)), M = W/2: pre- and post-twiddle of the DCT-IV
+        for (int m = 0; m < n; ++m) tws[(size_t)m] = root(8LL * m + 1, 8LL * pl.W);
+    } else if (cqt) {   // every root of W: the decimation-in-time recombination reads exp(-2 pi i (n1 k mod W) / W)
+        for (int k = 0; k < pl.W; ++k) tws[(size_t)k] = root(k, pl.W);
+    } else {
+        for (int k = 0; k <= n / 2; ++k) tws[(size_t)k] = root(k, pl.W);
+    }
+    ZAFX_TRY(pl.d_tw64.upload(tw.data(), tw.size() * sizeof(double2)));
+    return pl.d_tws64.upload(tws.data(), tws.size() * sizeof(double2));
+}
+
+// The device side of a new plan: its compute units, stream and events, then the tables.
+hipError_t build_plan(zafx_plan& pl, const std::vector<cf32>& aux) {
+    ZAFX_TRY(hipSetDevice(pl.device));
+    ZAFX_TRY(hipDeviceGetAttribute(&pl.n_cus_device, hipDeviceAttributeMultiprocessorCount, pl.device));
+    // ZAFX_COMPUTE_UNITS=n (n >= 1) at plan creation: the plan sizes its grids, carry cuts and slot counts for min(n, the device's count)
+    // compute units -- to leave the others to other work, and to test the kernels on grids a smaller device would give them.  Unset, empty,
+    // 0 or anything that is not a whole number: the device's count.
+    pl.n_cus = pl.n_cus_device;
+    if (const char* sw = std::getenv("ZAFX_COMPUTE_UNITS"); sw && *sw) {
+        char* end = nullptr;
+        const long long n = std::strtoll(sw, &end, 10);
+        if (end != sw && *end == 0 && n >= 1) pl.n_cus = (int)std::min<long long>(n, pl.n_cus_device);
+    }
+    ZAFX_TRY(hipStreamCreateWithFlags(&pl.stream, hipStreamNonBlocking));
+    ZAFX_TRY(hipEventCreate(&pl.ev0));
+    ZAFX_TRY(hipEventCreate(&pl.ev1));
+    ZAFX_TRY(build_tables_f32(pl, aux));
+    if (pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m > 0) ZAFX_TRY(build_tables_bs32(pl));
+    if (pl.prm.precision == ZAFX_PRECISION_F64) ZAFX_TRY(build_tables_f64(pl));
+    return hipSuccess;
+}
+#undef ZAFX_TRY
+
+}  // namespace
+
+// Release order of a plan: see zafx_internal.hpp.
+zafx_plan::~zafx_plan() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+}
+PlanLanes::~PlanLanes() {
+    for (hipStream_t st : {stream_up, stream_down})
+        if (st) (void)hipStreamSynchronize(st);
+}
+PlanStreams::~PlanStreams() {
+    if (rg_ev) (void)hipEventDestroy(rg_ev);
+    for (hipEvent_t ev : pipe_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipStream_t st : {stream_up, stream_down})
+        if (st) (void)hipStreamDestroy(st);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+extern "C" {
+
+int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* params) {
+    if (!out || !params) return fail_msg("null argument");
+    if (int rc = check_params(kind, params)) return rc;
+    int n_dev = 0;
+    ZAFX_HIP(hipGetDeviceCount(&n_dev));
+    if (device < 0 || device >= n_dev) return fail_msg("device index out of range");
+    std::unique_ptr<zafx_plan> pl(new zafx_plan());   // (every failure below is a plain return: the plan releases what it holds)
     pl->device = device;
     pl->kind = kind;
     pl->prm = *params;
     pl->layout = params->layout;
-    auto bail = [&](const std::string& m) {
-        delete pl;
-        return fail_msg(m);
-    };
     std::vector<cf32> aux;
-    if (is_stft_family(kind)) {
-        pl->W = params->window_length;
-        pl->H = params->step_length;
-        int lw = ilog2_exact(pl->W);
-        if ((lw < 0 || lw < 6) && params->precision == ZAFX_PRECISION_F64 && pl->W >= 2 && pl->W <= 2048) {
-            // any length up to 2048 in the float64 mode: Bluestein convolution of length 2^bs_log2m >= 2 W - 1
-            while ((1 << pl->bs_log2m) < 2 * pl->W - 1) ++pl->bs_log2m;
-            lw = 6;   // (only sizes the unused float32 tables below)
-        } else if (lw < 0 && params->precision == ZAFX_PRECISION_F32 && bs32_supported(pl->W)) {
-            // float32 Bluestein forms (zafx_bs32.hip); MEL / MFCC: the Bluestein STFT's magnitude / power kind + k_melfb (run_mel_wide)
-            while ((1 << pl->bs_log2m) < 2 * pl->W - 1) ++pl->bs_log2m;
-            lw = 6;
-        } else if (lw < 0 || !stft_supported(lw - 1)) {
-            return bail("window_length must be a power of two in [64, 8192] or any other length in [33, 8192] "
-                        "(any length in [2, 2048] with ZAFX_PRECISION_F64)");
-        }
-        if (pl->H < 1) return bail("step_length must be >= 1");
-        if (kind == ZAFX_ISTFT && pl->H > pl->W) return bail("istft: step_length must not exceed window_length");
-        if (pl->H > (1 << 20)) return bail("step_length must not exceed 2^20");
-        if (kind == ZAFX_ISTFT && params->precision == ZAFX_PRECISION_F32 && pl->bs_log2m == 0 && bs32_supported(pl->W)) {
-            // A hop so small that more frames cover a sample than the tiled overlap-add keeps in LDS (16): the frames + gather
-            // overlap-add form of zafx_bs32.hip has no such limit and takes any length, powers of two included.
-            const int tile = pl->W <= 2048 ? 16 : pl->W == 4096 ? 8 : 4;   // frames of the tiled kernel's LDS tile
-            if ((pl->W + pl->H - 1) / pl->H > tile)
-                while ((1 << pl->bs_log2m) < 2 * pl->W - 1) ++pl->bs_log2m;
-        }
-        pl->log2nf = lw - 1;
-        if (kind == ZAFX_MEL || kind == ZAFX_MFCC) {
-            // (float32: up to 256 rows on the fused kernels; above that the spectrum kernel + k_melfb route, whose mfcc form holds a
-            // [n_filters][64] log-mel tile in LDS: 576 rows)
-            if (params->n_filters < 1 || (params->precision != ZAFX_PRECISION_F64 && params->n_filters > 576))
-                return bail("n_filters must be in [1, 576] (up to window_length / 2 with ZAFX_PRECISION_F64)");
-            if (params->with_mel != 0 && (params->with_mel != 1 || kind != ZAFX_MFCC || params->precision != ZAFX_PRECISION_F32 || params->window_length != 2048 ||
-                                          params->n_filters > 128 || params->n_coefs > 32))
-                return bail("with_mel (melspectrogram + mfcc in one pass) takes a float32 ZAFX_MFCC plan of window_length 2048, up to 128 filters and up to 32 coefficients");
-            if (kind == ZAFX_MFCC && (params->n_coefs < 1 || params->n_coefs > params->n_filters))
-                return bail("n_coefs must be in [1, n_filters]");
-            if (params->precision == ZAFX_PRECISION_F64) {
-                if (params->n_filters > std::max(pl->W / 2, 1)) return bail("n_filters must not exceed window_length / 2");
-            } else if (lw - 1 < 5 || lw - 1 > 12) {
-                return bail("float32 mel/mfcc kernels are built for window_length 64 ... 8192 (any power of two with ZAFX_PRECISION_F64)");
-            }
-        }
-        const int n = pl->W / 2;
-        aux.resize((size_t)n / 2 + 1);
-        for (int k = 0; k <= n / 2; ++k) aux[(size_t)k] = unit_root(k, pl->W);
-        pl->kernel_name = kind == ZAFX_STFT ? stft_kernel_name(lw - 1, pl->layout) : kind == ZAFX_ISTFT ? istft_kernel_name(lw - 1, pl->layout) : params->n_filters > 256 ? mel_wide_kernel_name() : lw - 1 == 11 ? "k_mel_ft16b" : lw - 1 >= 12 ? mel_wide_kernel_name() : mel_kernel_name();
-    } else if (is_center_kind(kind)) {
-        pl->W = params->window_length;
-        pl->H = params->step_length;
-        pl->log2nf = ilog2_exact(pl->W);   // a stereo sample frame is one complex point: W-point transforms
-        aux.assign(1, cf32{1.f, 0.f});
-        pl->kernel_name = center_kernel_name();
-    } else if (is_mdct_family(kind)) {
-        pl->W = params->window_length;
-        pl->H = pl->W / 2;   // zaf.py:1029
-        int lw = ilog2_exact(pl->W);
-        if ((lw < 0 || lw < 6) && params->precision == ZAFX_PRECISION_F64 && pl->W >= 4 && pl->W <= 2048 && pl->W % 2 == 0) {
-            while ((1 << pl->bs_log2m) < 2 * pl->W - 1) ++pl->bs_log2m;   // any even length in the float64 mode (Bluestein)
-            lw = 6;
-        } else if (lw < 0 && params->precision == ZAFX_PRECISION_F32 && pl->W % 2 == 0 && bs32_supported(pl->W)) {
-            while ((1 << pl->bs_log2m) < 2 * pl->W - 1) ++pl->bs_log2m;   // float32 Bluestein forms (zafx_bs32.hip)
-            lw = 6;
-        } else if (lw < 0 || !mdct_supported(lw - 2)) {
-            return bail("window_length must be a power of two in [64, 8192] or any even length in [34, 8192] "
-                        "(any even length in [4, 2048] with ZAFX_PRECISION_F64)");
-        }
-        pl->log2nf = lw - 2;
-        const int nf = pl->W / 4, m = pl->W / 2;
-        aux.resize((size_t)nf);
-        for (int i = 0; i < nf; ++i) aux[(size_t)i] = unit_root(8LL * i + 1, 16LL * m);
-        pl->kernel_name = kind == ZAFX_MDCT ? mdct_kernel_name(lw - 2, pl->layout) : imdct_kernel_name();
-    } else if (is_cqt_family(kind)) {
-        pl->W = params->fft_length;
-        pl->H = params->step_length;
-        const int lw = ilog2_exact(pl->W);
-        if (params->precision == ZAFX_PRECISION_F64) {   // k_cqt_f64 decimates the frame: no LDS limit on its length
-            if (lw < 9 || lw > 17) return bail("fft_length must be a power of two in [512, 131072] (ZAFX_PRECISION_F64 plan)");
-        } else if (lw < 0 || !cqt_supported(lw - 1)) {
-            return bail("fft_length must be a power of two in [512, 65536] (up to 131072 with ZAFX_PRECISION_F64)");
-        }
-        if (pl->H < 1) return bail("step_length must be >= 1");
-        if (params->n_bins < 1 || params->n_bins > 1024) return bail("n_bins must be in [1, 1024]");
-        if (kind == ZAFX_CHROMA && (params->octave_resolution < 1 || params->octave_resolution > params->n_bins))
-            return bail("octave_resolution must be in [1, n_bins]");
-        pl->log2nf = lw - 1;
-        aux = build_split_two_level_twiddles(pl->log2nf);   // exp(-2 pi i k / W), k < W/4, as hi[k >> 7] * lo[k & 127]
-        pl->kernel_name = cqt_kernel_name();
-    } else if (kind == ZAFX_LINEAR) {
-        pl->W = params->window_length;
-        if (pl->W < 1 || pl->W > 16384 || params->n_filters < 1 || params->n_filters > 16384)
-            return bail("linear map: window_length (columns) and n_filters (rows) must be in [1, 16384]");
-        pl->log2nf = 4;   // only so that the (unused) FFT tables below are small
-        aux.assign(1, cf32{1.f, 0.f});
-        pl->kernel_name = linear_kernel_name();
-    } else if (kind == ZAFX_DCT) {
-        // zaf.dct / zaf.dst on the FFT core (zafx_dct.hip): M complex points per vector, tables A | B of M + 1 entries each
-        const int N = params->window_length, type = params->transform_type;
-        const bool sine = params->transform_sine != 0;
-        if (type < 1 || type > 4) return bail("transform_type must be 1, 2, 3 or 4");
-        if (params->transform_sine != 0 && params->transform_sine != 1) return bail("transform_sine must be 0 (dct) or 1 (dst)");
-        if (N < 2) return bail("dct / dst: window_length must be at least 2");
-        const int M = type == 1 ? (sine ? N + 1 : N - 1) : (N % 2 == 0 ? N / 2 : -1);
-        const int lm = ilog2_exact(M);
-        pl->W = N;
-        if (lm >= 0 && dct_supported(lm)) {
-            pl->log2nf = lm;
-            aux.resize(2 * (size_t)(M + 1));
-            for (int k = 0; k <= M; ++k) {
-                aux[(size_t)k] = type == 4 ? unit_root(4LL * k + 1, 8LL * N) : unit_root(k, 2LL * M);
-                aux[(size_t)(M + 1 + k)] = type == 4 ? unit_root(k, 2LL * N) : unit_root(k, 4LL * N);
-            }
-            pl->kernel_name = dct_kernel_name();
-        } else if (type >= 2 && N % 4 == 0 && N <= 8192) {
-            // N / 2 points, not a power of two (round 6): k_dct's maps around a Bluestein convolution of 2^bs_log2m >= 2 (N / 2) - 1 points --
-            // half the transform length of the chirp-z sum below (zafx_dct.hip, BS = true); tables A | B as above, chirp and its transform below
-            const int Mh = N / 2;
-            pl->dct_half = Mh;
-            pl->dct_den2 = Mh;   // (the chirp of an Mh-point DFT: exp(-i pi m^2 / Mh))
-            pl->log2nf = 4;
-            pl->bs_log2m = 7;
-            while ((1 << pl->bs_log2m) < 2 * Mh - 1) ++pl->bs_log2m;
-            aux.resize(2 * (size_t)(Mh + 1));
-            for (int k = 0; k <= Mh; ++k) {
-                aux[(size_t)k] = type == 4 ? unit_root(4LL * k + 1, 8LL * N) : unit_root(k, 2LL * Mh);
-                aux[(size_t)(Mh + 1 + k)] = type == 4 ? unit_root(k, 2LL * N) : unit_root(k, 4LL * N);
-            }
-            pl->kernel_name = "k_dct_bsh";
-        } else if (N <= 8192) {
-            // Every other length (the reference's np.fft.fft takes any, zaf.py:760-839, :900-981): all eight transforms are
-            //     y[k] = s_out[k] sum_n s_in[n] x[n] cos | sin(pi (n + a)(k + b) / D),   a, b in {0, 1/2, 1},  D = N - 1 | N | N + 1,
-            // and with n k = (n^2 + k^2 - (k - n)^2) / 2 the sum is a convolution with a chirp of step pi / D (a chirp-z transform):
-            //     y[k] = Re(Q[k] sum_n (x[n] P[n]) conj(c)[k - n]),   c[j] = exp(-i pi j^2 / (2 D)),
-            //     P[n] = s_in[n] exp(-i pi n b / D) c[n],   Q[k] = s_out[k] exp(-i pi (a k + a b) / D) c[k]  (x i for the sines),
-            // on the Bluestein machinery of zafx_bs32.hip (k_dct_bs32: two transforms of 2^ceil(log2(2N - 1)) points per vector instead of
-            // the dense N x N product of round 4).  Angles in units of pi / (4 D), reduced in integers.
-            const int a2 = sine ? (type == 1 ? 2 : type == 3 ? 2 : 1) : (type == 2 || type == 4 ? 1 : 0);   // 2 a
-            const int b2 = sine ? (type == 1 ? 2 : type == 2 ? 2 : 1) : (type == 3 || type == 4 ? 1 : 0);   // 2 b
-            const long long D = type == 1 ? (sine ? N + 1 : N - 1) : N;
-            pl->dct_den2 = 2 * D;
-            pl->log2nf = 4;   // (the FFT tables are those of the convolution length, below)
-            pl->bs_log2m = 7;
-            while ((1 << pl->bs_log2m) < 2 * N - 1) ++pl->bs_log2m;
-            const double L = (double)(1 << pl->bs_log2m), s = std::sqrt(2.0 / (double)D), r2 = std::sqrt(0.5);
-            aux.resize(2 * (size_t)N);
-            for (long long n = 0; n < N; ++n) {
-                double sin_ = 1.0, sout = s;
-                if (type == 1 && !sine && (n == 0 || n == N - 1)) sin_ = r2, sout = s * r2;
-                if (type == 2 && (sine ? n == N - 1 : n == 0)) sout = s * r2;
-                if (type == 3 && (sine ? n == N - 1 : n == 0)) sin_ = r2;
-                auto root = [&](long long m, double scale) {   // scale exp(-i pi m / (4 D)), in float64, exact on the axes
-                    m %= 8 * D;
-                    const double ang = M_PI * (double)m / (double)(4 * D);
-                    double c = std::cos(ang), sn = -std::sin(ang);
-                    if (m % (2 * D) == 0) {
-                        const int quarter = (int)(m / (2 * D));
-                        c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
-                        sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
-                    }
-                    return cf32{(float)(scale * c), (float)(scale * sn)};
-                };
-                aux[(size_t)n] = root(2 * n * b2 + 2 * n * n, sin_);
-                aux[(size_t)(N + n)] = root(2 * n * a2 + a2 * b2 + 2 * n * n + (sine ? 6 * D : 0), sout / L);   // (x i = exp(-i pi 6 D / (4 D)))
-            }
-            pl->kernel_name = "k_dct_bs32";
-        } else {
-            return bail("dct / dst: lengths above 8192 need N / 2 (types 2-4), N - 1 (dct type 1) or N + 1 (dst type 1) to be a power of two (at most 8192)");
-        }
-    } else {
-        return bail("unknown plan kind");
-    }
+    const char* wrong = is_stft_family(kind) ? stft_geometry(*pl, aux) : is_center_kind(kind) ? center_geometry(*pl, aux)
+                        : is_mdct_family(kind) ? mdct_geometry(*pl, aux) : is_cqt_family(kind) ? cqt_geometry(*pl, aux)
+                        : kind == ZAFX_LINEAR ? linear_geometry(*pl, aux) : kind == ZAFX_DCT ? dct_geometry(*pl, aux) : "unknown plan kind";
+    if (wrong) return fail_msg(wrong);
     pl->log2e = is_center_kind(kind) ? center_log2e(pl->log2nf) : default_log2e(pl->log2nf);
-
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&pl->n_cus_device, hipDeviceAttributeMultiprocessorCount, device);
-    if (e == hipSuccess) {
-        // ZAFX_COMPUTE_UNITS=n (n >= 1) at plan creation: the plan sizes its grids, carry cuts and slot counts for min(n, the device's count)
-        // compute units -- to leave the others to other work, and to test the kernels on grids a smaller device would give them.  Unset, empty,
-        // 0 or anything that is not a whole number: the device's count.
-        pl->n_cus = pl->n_cus_device;
-        if (const char* sw = std::getenv("ZAFX_COMPUTE_UNITS"); sw && *sw) {
-            char* end = nullptr;
-            const long long n = std::strtoll(sw, &end, 10);
-            if (end != sw && *end == 0 && n >= 1) pl->n_cus = (int)std::min<long long>(n, pl->n_cus_device);
-        }
-    }
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&pl->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&pl->ev1);
-    if (e == hipSuccess) {
-        auto tw = is_cqt_family(kind) ? build_two_level_twiddles(pl->log2nf) : build_pass_twiddles(pl->log2nf, pl->log2e);
-        if (is_cqt_family(kind) && cqt_split(pl->log2nf)) {   // + the pass tables of the 1024-point sub-transforms
-            const auto sub = build_pass_twiddles(10, 4);
-            tw.insert(tw.end(), sub.begin(), sub.end());
-        }
-        if (tw.empty()) tw.push_back(cf32{1.f, 0.f});
-        e = upload(&pl->d_tw_pass, tw.data(), tw.size() * sizeof(cf32));
-        if (e == hipSuccess && (kind == ZAFX_STFT || kind == ZAFX_MEL || kind == ZAFX_MFCC) && (pl->log2nf == 10 || (ZAFX_STFT_FAT8_TABLES && pl->log2nf == 11 && kind == ZAFX_STFT))) {
-            auto tw5 = build_pass_twiddles(pl->log2nf, 5);   // (W = 4096: 2048 points as 32 x 32 x 2 in the persistent 8-frame form)
-            e = upload(&pl->d_tw_r32, tw5.data(), tw5.size() * sizeof(cf32));
-        }
-    }
-    if (e == hipSuccess && kind == ZAFX_STFT && pl->prm.precision == ZAFX_PRECISION_F32) {
-        // k_stft_ft16 with its tiles claimed at run time: the plan's counters, zero from here on between launches
-        const std::vector<int> zeros((size_t)zafx::kClaimInts, 0);
-        e = upload(&pl->d_claim, zeros.data(), zeros.size() * sizeof(int));
-        const char* sw = std::getenv("ZAFX_STFT_DYNAMIC");   // 0: the static split (to time both forms in one process: tools/stft_dyn_ab.py)
-        pl->stft_dynamic = !(sw && sw[0] == '0' && sw[1] == 0);
-    }
-    if (e == hipSuccess && (kind == ZAFX_STFT || kind == ZAFX_ISTFT || kind == ZAFX_MEL || kind == ZAFX_MFCC) && pl->log2nf == 11 && pl->prm.precision == ZAFX_PRECISION_F32) {
-        const auto sub = build_pass_twiddles(10, 4);   // the two 1024-point band transforms of k_stft_ft16b
-        e = upload(&pl->d_tw_sub, sub.data(), sub.size() * sizeof(cf32));
-    }
-    if (e == hipSuccess && (kind == ZAFX_STFT || kind == ZAFX_ISTFT || kind == ZAFX_MEL || kind == ZAFX_MFCC) && pl->log2nf == 12 && pl->prm.precision == ZAFX_PRECISION_F32 && pl->bs_log2m == 0) {
-        const auto sub = build_pass_twiddles(10, 4);   // the four 1024-point class transforms of k_stft_ft16q, and the roots that form their inputs
-        e = upload(&pl->d_tw_sub, sub.data(), sub.size() * sizeof(cf32));
-        std::vector<cf32> q(4096);
-        for (int n = 0; n < 4096; ++n) q[(size_t)n] = unit_root(n, 8192);
-        if (e == hipSuccess) e = upload(&pl->d_tw_quad, q.data(), q.size() * sizeof(cf32));
-    }
-    if (e == hipSuccess && kind == ZAFX_MDCT && pl->log2nf == 11 && pl->prm.precision == ZAFX_PRECISION_F32 && pl->bs_log2m == 0) {
-        const auto sub = build_pass_twiddles(9, 3);   // k_mdct_ft32q: the four 512-point band transforms, and exp(-2 pi i n / 2048)
-        e = upload(&pl->d_tw_sub, sub.data(), sub.size() * sizeof(cf32));
-        std::vector<cf32> q(2048);
-        for (int n = 0; n < 2048; ++n) q[(size_t)n] = unit_root(n, 2048);
-        if (e == hipSuccess) e = upload(&pl->d_tw_quad, q.data(), q.size() * sizeof(cf32));
-    }
-    if (e == hipSuccess && kind == ZAFX_IMDCT && pl->log2nf == 11 && pl->prm.precision == ZAFX_PRECISION_F32 && pl->bs_log2m == 0) {
-        const auto sub = build_pass_twiddles(10, 4);   // k_imdct_q: the two 1024-point class transforms, and exp(-2 pi i n / 2048) that joins them
-        e = upload(&pl->d_tw_sub, sub.data(), sub.size() * sizeof(cf32));
-        std::vector<cf32> q(2048);
-        for (int n = 0; n < 2048; ++n) q[(size_t)n] = unit_root(n, 2048);
-        if (e == hipSuccess) e = upload(&pl->d_tw_quad, q.data(), q.size() * sizeof(cf32));
-    }
-    if (e == hipSuccess && kind == ZAFX_MDCT && pl->log2nf == 10 && pl->prm.precision == ZAFX_PRECISION_F32 && pl->bs_log2m == 0) {
-        // k_mdct_ft32b: pass tables of the two 512-point band transforms; g in band-major order, and g[n] exp(-2 pi i n / 1024)
-        const auto sub = build_pass_twiddles(9, 3);
-        e = upload(&pl->d_tw_sub, sub.data(), sub.size() * sizeof(cf32));
-        const int nf = pl->W / 4;
-        std::vector<cf32> bt((size_t)nf + nf / 2);
-        for (int s = 0; s < 2; ++s)
-            for (int q = 0; q < nf / 2; ++q) bt[(size_t)s * (nf / 2) + q] = unit_root(8LL * (2 * q + s) + 1, 8LL * pl->W);
-        for (int n = 0; n < nf / 2; ++n) bt[(size_t)nf + n] = unit_root(40LL * n + 1, 32LL * nf);
-        if (e == hipSuccess) e = upload(&pl->d_tw_band, bt.data(), bt.size() * sizeof(cf32));
-    }
-    if (e == hipSuccess) e = upload(&pl->d_tw_aux, aux.data(), aux.size() * sizeof(cf32));
-    if (e == hipSuccess && pl->prm.precision == ZAFX_PRECISION_F32 && pl->bs_log2m > 0) {   // float32 Bluestein plan (zafx_bs32.hip)
-        const int M = 1 << pl->bs_log2m, W = pl->dct_half > 0 ? pl->dct_half : pl->W, F = W / 2;   // (W: the points of the transform that is convolved)
-        auto twm = build_pass_twiddles(pl->bs_log2m, default_log2e(pl->bs_log2m));
-        if (twm.empty()) twm.push_back(cf32{1.f, 0.f});
-        e = upload(&pl->d_tw_pass, twm.data(), twm.size() * sizeof(cf32));
-        std::vector<cld> c, b;
-        bluestein_tables(W, kind == ZAFX_DCT ? pl->dct_den2 : (long long)W, pl->bs_log2m, c, b);
-        std::vector<cf32> cf((size_t)W), bf((size_t)M);
-        for (int i = 0; i < W; ++i) cf[(size_t)i] = cf32{(float)c[(size_t)i].real(), (float)c[(size_t)i].imag()};
-        for (int i = 0; i < M; ++i) bf[(size_t)i] = cf32{(float)b[(size_t)i].real(), (float)b[(size_t)i].imag()};
-        if (e == hipSuccess) e = upload(&pl->d_bs_chirp, cf.data(), cf.size() * sizeof(cf32));
-        if (e == hipSuccess) e = upload(&pl->d_bs_bhat, bf.data(), bf.size() * sizeof(cf32));
-        if (is_mdct_family(kind)) {   // pre / post twiddles of the reference's own W-point formulation (zaf.py:1047-1056, :1138-1156)
-            std::vector<cf32> pp;
-            if (kind == ZAFX_MDCT) {
-                for (int n = 0; n < W; ++n) pp.push_back(unit_root(n, 2LL * W));                                  // exp(-i pi n / W)
-                for (int k = 0; k < F; ++k) pp.push_back(unit_root((long long)(F + 1) * (2 * k + 1), 4LL * W));   // exp(-i pi (F+1)(2k+1) / (2W))
-            } else {
-                for (int k = 0; k < F; ++k) pp.push_back(unit_root((long long)(F + 1) * k, 2LL * W));             // exp(-i pi (F+1) k / W)
-                for (int n = 0; n < W; ++n) pp.push_back(unit_root(2LL * n + 1 + F, 4LL * W));                    // exp(-i pi (2n+1+F) / (2W))
-            }
-            if (e == hipSuccess) e = upload(&pl->d_tw_aux, pp.data(), pp.size() * sizeof(cf32));
-        }
-        pl->kernel_name = kind == ZAFX_DCT ? (pl->dct_half > 0 ? "k_dct_bsh" : "k_dct_bs32") : kind == ZAFX_STFT ? "k_stft_bs32" : kind == ZAFX_ISTFT ? "k_ifft_frames_bs32" : kind == ZAFX_MDCT ? "k_mdct_bs32"
-                          : (kind == ZAFX_MEL || kind == ZAFX_MFCC) ? mel_wide_kernel_name() : "k_imdct_frames_bs32";
-    }
-    if (e == hipSuccess && pl->prm.precision == ZAFX_PRECISION_F64) {   // float64 tables, evaluated in long double
-        const bool mdct = is_mdct_family(kind), cqt = is_cqt_family(kind);
-        const int n = mdct ? pl->W / 4 : cqt ? std::min(pl->W, kCqt64Sub) : pl->W / 2;   // FFT length (CQT: of one decimated sub-sequence)
-        auto root = [](long long num, long long den) {
-            const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)(num % den) / (long double)den;
-            double2 r = make_double2((double)cosl(a), (double)sinl(a));
-            if (num % den == 0) r = make_double2(1.0, 0.0);
-            if (4 * (num % den) == den) r = make_double2(0.0, -1.0);
-            if (2 * (num % den) == den) r = make_double2(-1.0, 0.0);
-            return r;
-        };
-        std::vector<double2> tw((size_t)std::max(n / 2, 1)), tws((size_t)(mdct ? n : cqt ? pl->W : n / 2 + 1));
-        for (int m = 0; m < n / 2; ++m) tw[(size_t)m] = root(m, n);
-        if (pl->bs_log2m > 0) {   // Bluestein: roots of M, the chirp c[n] = exp(-i pi n^2 / W), and FFT_M of its wrapped conjugate
-            const int M = 1 << pl->bs_log2m, W = pl->W;
-            tw.assign((size_t)M / 2, make_double2(0, 0));
-            for (int m = 0; m < M / 2; ++m) tw[(size_t)m] = root(m, M);
-            tws.assign((size_t)W, make_double2(0, 0));
-            for (long long k = 0; k < W; ++k) tws[(size_t)k] = root((k * k) % (2LL * W), 2LL * W);
-            std::vector<cld> c, b;
-            bluestein_tables(W, (long long)W, pl->bs_log2m, c, b);
-            std::vector<double2> bhat((size_t)M);
-            for (int i = 0; i < M; ++i) bhat[(size_t)i] = make_double2((double)b[(size_t)i].real(), (double)b[(size_t)i].imag());
-            e = upload(&pl->d_bhat64, bhat.data(), bhat.size() * sizeof(double2));
-        } else if (mdct) {   // g_m = exp(-i pi (8m+1) / (8M)), M = W/2: pre- and post-twiddle of the DCT-IV
-            for (int m = 0; m < n; ++m) tws[(size_t)m] = root(8LL * m + 1, 8LL * pl->W);
-        } else if (cqt) {   // every root of W: the decimation-in-time recombination reads exp(-2 pi i (n1 k mod W) / W)
-            for (int k = 0; k < pl->W; ++k) tws[(size_t)k] = root(k, pl->W);
-        } else {
-            for (int k = 0; k <= n / 2; ++k) tws[(size_t)k] = root(k, pl->W);
-        }
-        if (e == hipSuccess) e = upload(&pl->d_tw64, tw.data(), tw.size() * sizeof(double2));
-        if (e == hipSuccess) e = upload(&pl->d_tws64, tws.data(), tws.size() * sizeof(double2));
-        pl->kernel_name = kind == ZAFX_STFT ? stft_f64_kernel_name() : kind == ZAFX_ISTFT ? istft_f64_kernel_name()
-                          : kind == ZAFX_MDCT ? mdct_f64_kernel_name() : kind == ZAFX_IMDCT ? imdct_f64_kernel_name()
-                          : cqt ? cqt_f64_kernel_name() : mel_f64_kernel_name();
-        if (pl->bs_log2m > 0)
-            pl->kernel_name = kind == ZAFX_ISTFT ? "k_ifft_frames_bs_f64" : kind == ZAFX_MDCT ? "k_mdct_bs_f64"
-                              : kind == ZAFX_IMDCT ? "k_imdct_frames_bs_f64" : "k_stft_bs_f64";
-    }
-    if (e != hipSuccess) {
-        zafx_plan_destroy(pl);
-        return fail("zafx_plan_create", e);
-    }
-    *out = pl;
+    pl->kernel_name = planned_kernel_name(*pl);
+    if (hipError_t e = build_plan(*pl, aux); e != hipSuccess) return fail("zafx_plan_create", e);
+    *out = pl.release();
     return 0;
 }
 
 int zafx_plan_destroy(zafx_plan* pl) {
     if (!pl) return 0;
-    (void)hipSetDevice(pl->device);
-    if (pl->stream) (void)hipStreamSynchronize(pl->stream);
-    for (int l = 0; l < 2; ++l)
-        if (pl->lane_pcm[l]) (void)hipFree(pl->lane_pcm[l]);
-    if (pl->d_window) (void)hipFree(pl->d_window);
-    if (pl->d_matrix) (void)hipFree(pl->d_matrix);
-    if (pl->d_wfold) (void)hipFree(pl->d_wfold);
-    if (pl->d_tw_pass) (void)hipFree(pl->d_tw_pass);
-    if (pl->d_tw_r32) (void)hipFree(pl->d_tw_r32);
-    if (pl->d_claim) (void)hipFree(pl->d_claim);
-    if (pl->d_tail) (void)hipFree(pl->d_tail);
-    if (pl->d_tw_quad) (void)hipFree(pl->d_tw_quad);
-    if (pl->d_tw_sub) (void)hipFree(pl->d_tw_sub);
-    if (pl->d_tw_band) (void)hipFree(pl->d_tw_band);
-    if (pl->d_fbw) (void)hipFree(pl->d_fbw);
-    if (pl->d_fbw_meta) (void)hipFree(pl->d_fbw_meta);
-    if (pl->d_dctw) (void)hipFree(pl->d_dctw);
-    if (pl->d_tw_aux) (void)hipFree(pl->d_tw_aux);
-    if (pl->d_indptr) (void)hipFree(pl->d_indptr);
-    if (pl->d_indices) (void)hipFree(pl->d_indices);
-    if (pl->d_values) (void)hipFree(pl->d_values);
-    if (pl->d_cqt_waves) (void)hipFree(pl->d_cqt_waves);
-    if (pl->d_cqt_addrs) (void)hipFree(pl->d_cqt_addrs);
-    if (pl->d_cqt_vals) (void)hipFree(pl->d_cqt_vals);
-    if (pl->d_cqt_mm_vals) (void)hipFree(pl->d_cqt_mm_vals);
-    if (pl->d_cqt_mm_addr) (void)hipFree(pl->d_cqt_mm_addr);
-    if (pl->d_cqt_mm_fin) (void)hipFree(pl->d_cqt_mm_fin);
-    if (pl->d_window64) (void)hipFree(pl->d_window64);
-    if (pl->d_tw64) (void)hipFree(pl->d_tw64);
-    if (pl->d_tws64) (void)hipFree(pl->d_tws64);
-    if (pl->d_scratch64) (void)hipFree(pl->d_scratch64);
-    if (pl->d_fb64) (void)hipFree(pl->d_fb64);
-    if (pl->d_fb64_meta) (void)hipFree(pl->d_fb64_meta);
-    if (pl->d_dct64) (void)hipFree(pl->d_dct64);
-    if (pl->d_cqt64_tw1) (void)hipFree(pl->d_cqt64_tw1);
-    if (pl->d_cqt64_split) (void)hipFree(pl->d_cqt64_split);
-    if (pl->d_cqt64_vals) (void)hipFree(pl->d_cqt64_vals);
-    if (pl->d_cqt64_meta) (void)hipFree(pl->d_cqt64_meta);
-    if (pl->d_cqt64_fin) (void)hipFree(pl->d_cqt64_fin);
-    if (pl->d_mel64_stream) (void)hipFree(pl->d_mel64_stream);
-    if (pl->d_mel64_fin) (void)hipFree(pl->d_mel64_fin);
-    if (pl->d_mel64_dctT) (void)hipFree(pl->d_mel64_dctT);
-    if (pl->d_values64) (void)hipFree(pl->d_values64);
-    if (pl->d_bhat64) (void)hipFree(pl->d_bhat64);
-    if (pl->d_pcm_float) (void)hipFree(pl->d_pcm_float);
-    if (pl->d_ragged) (void)hipFree(pl->d_ragged);
-    if (pl->h_ragged) (void)hipHostFree(pl->h_ragged);
-    if (pl->rg_ev) (void)hipEventDestroy(pl->rg_ev);
-    if (pl->d_bs_chirp) (void)hipFree(pl->d_bs_chirp);
-    if (pl->d_bs_bhat) (void)hipFree(pl->d_bs_bhat);
-    free_band(pl->fb);
-    free_band(pl->dct);
-    for (hipStream_t st : {pl->stream_up, pl->stream_down})
-        if (st) (void)hipStreamSynchronize(st);
-    for (int l = 0; l < 2; ++l) {
-        if (pl->lane_in[l]) (void)hipFree(pl->lane_in[l]);
-        if (pl->lane_out[l]) (void)hipFree(pl->lane_out[l]);
-    }
-    for (hipEvent_t ev : pl->pipe_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipStream_t st : {pl->stream_up, pl->stream_down})
-        if (st) (void)hipStreamDestroy(st);
-    if (pl->ev0) (void)hipEventDestroy(pl->ev0);
-    if (pl->ev1) (void)hipEventDestroy(pl->ev1);
-    if (pl->stream) (void)hipStreamDestroy(pl->stream);
-    delete pl;
+    delete pl;   // ~zafx_plan and its bases release everything, in the order zafx_internal.hpp gives
+    return 0;
+}
+
+int zafx_plan_live_allocations(int64_t* count) {
+    if (!count) return fail_msg("null argument");
+    *count = (int64_t)g_live_allocations.load();
     return 0;
 }
 
@@ -1462,7 +1458,7 @@ int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, 
     if (pl->kind == ZAFX_MFCC && !pl->dct.d_pack && !pl->d_dct64 && !pl->d_dctw) return fail_msg("DCT constant not set");
     if (is_cqt_family(pl->kind)) {
         const bool f64 = pl->prm.precision == ZAFX_PRECISION_F64;
-        if (!pl->d_indptr || !pl->d_indices || !(f64 ? (void*)pl->d_values64 : (void*)pl->d_values)) return fail_msg("CQT kernel constants not set");
+        if (!pl->d_indptr || !pl->d_indices || !(f64 ? (void*)pl->d_values64.get() : (void*)pl->d_values.get())) return fail_msg("CQT kernel constants not set");
         if ((int)(f64 ? pl->h_values64.size() : pl->h_values.size()) != pl->nnz || pl->h_indptr.back() != pl->nnz)
             return fail_msg("CQT kernel CSR arrays are inconsistent");
         for (size_t r = 0; f64 && r + 1 < pl->h_indptr.size(); ++r)
@@ -1571,26 +1567,22 @@ static const char* per_clip_name(const char* kernel) {
     return it->second.c_str();
 }
 
+// A grow-only buffer that kernels on the plan's stream may still use: a larger one replaces it only once the stream is idle.
+static int reserve_idle(zafx_plan* pl, DevBuf<void>& buf, size_t need) {
+    if (buf.bytes() < need) ZAFX_HIP(hipStreamSynchronize(pl->stream));
+    ZAFX_HIP(buf.reserve(need));
+    return 0;
+}
+
 // The table of a native launch -- `need` bytes that `fill` writes -- through the plan's page-locked staging copy onto its device copy
 // (pl->d_ragged), on the plan's stream.  The staging copy is written only once the upload of the previous call has left it (rg_ev); the
 // device copy is overwritten in stream order behind the kernels that read it, and a larger one replaces it only once the stream is idle.
 static int upload_plan_table(zafx_plan* pl, size_t need, const std::function<void(unsigned char*)>& fill) {
     if (!pl->rg_ev) ZAFX_HIP(hipEventCreateWithFlags(&pl->rg_ev, hipEventDisableTiming));
     else ZAFX_HIP(hipEventSynchronize(pl->rg_ev));
-    if (pl->ragged_host_bytes < need) {
-        if (pl->h_ragged) ZAFX_HIP(hipHostFree(pl->h_ragged));
-        pl->h_ragged = nullptr, pl->ragged_host_bytes = 0;
-        ZAFX_HIP(hipHostMalloc(&pl->h_ragged, need, hipHostMallocDefault));
-        pl->ragged_host_bytes = need;
-    }
-    if (pl->ragged_bytes < need) {
-        ZAFX_HIP(hipStreamSynchronize(pl->stream));
-        if (pl->d_ragged) ZAFX_HIP(hipFree(pl->d_ragged));
-        pl->d_ragged = nullptr, pl->ragged_bytes = 0;
-        ZAFX_HIP(hipMalloc(&pl->d_ragged, need));
-        pl->ragged_bytes = need;
-    }
-    fill(static_cast<unsigned char*>(pl->h_ragged));
+    ZAFX_HIP(pl->h_ragged.reserve(need));
+    if (int rc = reserve_idle(pl, pl->d_ragged, need)) return rc;
+    fill(static_cast<unsigned char*>(pl->h_ragged.get()));
     ZAFX_HIP(hipMemcpyAsync(pl->d_ragged, pl->h_ragged, need, hipMemcpyHostToDevice, pl->stream));
     ZAFX_HIP(hipEventRecord(pl->rg_ev, pl->stream));
     return 0;
@@ -1706,7 +1698,7 @@ static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_i
         if (tiles32 < (1LL << 31) && short_enough && route) {
             if (int rc = upload_ragged_table(pl, recs, tiles32, zafx::kMdctRaggedTile)) return rc;
             return launch_pcm([&] {
-                return zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged), n_clips, tiles32, aligned);
+                return zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged.get()), n_clips, tiles32, aligned);
             });
         }
     }
@@ -1725,7 +1717,7 @@ static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_i
         const long long tiles64 = zafx::rg_assign_tiles(recs.data(), recs.size(), tile_frames);
         if (tiles64 < (1LL << 31)) {
             if (int rc = upload_ragged_table(pl, recs, tiles64, tile_frames)) return rc;
-            const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged);
+            const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged.get());
             *launched = true;
             return launch_rc(fn, pl->kind == ZAFX_STFT   ? zafx::launch_stft_f64_ragged(*pl, (const double*)d_in, (double2*)d_out, tab, n_clips, tiles64)
                                  : pl->kind == ZAFX_MDCT ? zafx::launch_mdct_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles64)
@@ -1741,7 +1733,7 @@ static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_i
     if (pcm != 0 && !(native && pl->log2nf == 10 && even && short_clips)) return 0;
     if (native) {
         if (int rc = upload_ragged_table(pl, recs, tiles)) return rc;
-        const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged);
+        const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged.get());
         return launch_pcm([&] {
             return pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
                                          : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even);
@@ -1786,7 +1778,7 @@ int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
     const std::vector<zafx::CenterUnit> units = zafx::center_cut_units(lengths, in_offsets, out_offsets, n_clips, pl->W, tile_frames, slots, per_slot);
     ZAFX_HIP(hipSetDevice(pl->device));
     if (int rc = upload_records(pl, units)) return rc;
-    return launch_rc("zafx_execute_center_ragged", zafx::launch_center_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::CenterUnit*>(pl->d_ragged),
+    return launch_rc("zafx_execute_center_ragged", zafx::launch_center_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::CenterUnit*>(pl->d_ragged.get()),
                                                                               (long long)units.size()));
 }
 
@@ -1831,7 +1823,7 @@ static int execute_tile_ragged(const TileRagged& k, zafx_plan* pl, const void* d
             // the launch's workgroups (the launchers: min(records, slots) -- the table is a whole number of rounds or shorter than one)
             const std::vector<zafx::TileUnit> table = zafx::deal_table(units, std::min<long long>((long long)units.size(), slots));
             if (int rc = upload_records(pl, table)) return rc;
-            return launch_rc(k.fn, k.launch(*pl, d_in, d_out, static_cast<const zafx::TileUnit*>(pl->d_ragged), (long long)table.size()));
+            return launch_rc(k.fn, k.launch(*pl, d_in, d_out, static_cast<const zafx::TileUnit*>(pl->d_ragged.get()), (long long)table.size()));
         }
     }
     // everything else: one zafx_execute per clip on the plan's stream (a block that gives no samples is passed over)
@@ -1988,18 +1980,12 @@ static int execute_pcm(zafx_plan* pl, const void* d_pcm, void* d_out, int64_t n_
     if (int rc = clip_bytes(pl, n_frames, &in_b, &out_b)) return rc;
     const int64_t chunk = zafx::scratch_clips_per_chunk(n_clips, 1, (int)std::min<int64_t>(n_frames, INT32_MAX), sizeof(float));
     const size_t need = (size_t)std::max<int64_t>(chunk * n_frames * 4, 1);
-    if (pl->pcm_float_bytes < need) {
-        ZAFX_HIP(hipStreamSynchronize(pl->stream));
-        if (pl->d_pcm_float) ZAFX_HIP(hipFree(pl->d_pcm_float));
-        pl->d_pcm_float = nullptr, pl->pcm_float_bytes = 0;
-        ZAFX_HIP(hipMalloc(&pl->d_pcm_float, need));
-        pl->pcm_float_bytes = need;
-    }
+    if (int rc = reserve_idle(pl, pl->d_pcm_float, need)) return rc;
     const int64_t pcm_clip_b = n_frames * n_channels * sample_bytes;
     for (int64_t c0 = 0; c0 < n_clips; c0 += chunk) {   // (one stream: a chunk's conversion waits for the transform of the chunk before it)
         const int64_t n = std::min(chunk, n_clips - c0);
         if (n * n_frames > 0)
-            ZAFX_HIP(launch_pcm_to_float(pl->stream, (const char*)d_pcm + c0 * pcm_clip_b, (float*)pl->d_pcm_float, n * n_frames, n_channels, sample_bytes));
+            ZAFX_HIP(launch_pcm_to_float(pl->stream, (const char*)d_pcm + c0 * pcm_clip_b, (float*)pl->d_pcm_float.get(), n * n_frames, n_channels, sample_bytes));
         if (int rc = zafx_execute(pl, pl->d_pcm_float, (char*)d_out + c0 * out_b, n, n_frames)) return rc;
     }
     return 0;
@@ -2050,18 +2036,12 @@ int zafx_execute_ragged_pcm(zafx_plan* pl, const void* d_pcm, const int64_t* in_
     long long span = 1;
     for (const zafx::RgPcmGroup& g : groups) span = std::max(span, g.hi - g.lo);
     if (span > INT64_MAX / 4) return fail_msg(std::string(fn) + ": a clip reaches past 2^61 sample frames");
-    if (pl->pcm_float_bytes < (size_t)span * 4) {   // (grow-only, once per call: the largest group's span)
-        ZAFX_HIP(hipStreamSynchronize(pl->stream));
-        if (pl->d_pcm_float) ZAFX_HIP(hipFree(pl->d_pcm_float));
-        pl->d_pcm_float = nullptr, pl->pcm_float_bytes = 0;
-        ZAFX_HIP(hipMalloc(&pl->d_pcm_float, (size_t)span * 4));
-        pl->pcm_float_bytes = (size_t)span * 4;
-    }
+    if (int rc = reserve_idle(pl, pl->d_pcm_float, (size_t)span * 4)) return rc;   // (once per call: the largest group's span)
     const int64_t eb = out_elem_bytes(pl), frame_b = (int64_t)n_channels * sample_bytes;
     std::vector<int64_t> rebased;
     int64_t out_off = 0;   // the group's first block in the whole batch's layout (the blocks lie back to back)
     for (const zafx::RgPcmGroup& g : groups) {   // (one stream: a group's conversion waits for the transform of the group before it)
-        if (g.hi > g.lo) ZAFX_HIP(launch_pcm_to_float(pl->stream, (const char*)d_pcm + g.lo * frame_b, (float*)pl->d_pcm_float, g.hi - g.lo, n_channels, sample_bytes));
+        if (g.hi > g.lo) ZAFX_HIP(launch_pcm_to_float(pl->stream, (const char*)d_pcm + g.lo * frame_b, (float*)pl->d_pcm_float.get(), g.hi - g.lo, n_channels, sample_bytes));
         rebased.assign((size_t)g.count, 0);
         for (long long i = 0; i < g.count; ++i) rebased[(size_t)i] = in_offsets[g.first + i] - g.lo;
         if (int rc = zafx_execute_ragged(pl, pl->d_pcm_float, rebased.data(), lengths + g.first, (char*)d_out + out_off * eb, g.count)) return rc;
@@ -2121,25 +2101,10 @@ static int run_host_impl(zafx_plan* pl, const void* h_in, void* h_out, int64_t n
     }
     for (int l = 0; l < sets; ++l) {   // grow-only staging buffers
         const size_t need_in = (size_t)std::max<int64_t>(chunk_clips * in_b, 1), need_out = (size_t)std::max<int64_t>(chunk_clips * out_b, 1);
-        if (pl->lane_in_bytes[l] < need_in && !pcm_direct) {   // (integer PCM read by the kernel itself: no float32 lane)
-            if (pl->lane_in[l]) ZAFX_HIP(hipFree(pl->lane_in[l]));
-            pl->lane_in[l] = nullptr, pl->lane_in_bytes[l] = 0;
-            ZAFX_HIP(hipMalloc(&pl->lane_in[l], need_in));
-            pl->lane_in_bytes[l] = need_in;
-        }
+        if (!pcm_direct) ZAFX_HIP(pl->lane_in[l].reserve(need_in));   // (integer PCM read by the kernel itself: no float32 lane)
         const size_t need_pcm = pcm_bytes > 0 ? (size_t)std::max<int64_t>(chunk_clips * host_in_b, 1) : 0;
-        if (pl->lane_pcm_bytes[l] < need_pcm) {
-            if (pl->lane_pcm[l]) ZAFX_HIP(hipFree(pl->lane_pcm[l]));
-            pl->lane_pcm[l] = nullptr, pl->lane_pcm_bytes[l] = 0;
-            ZAFX_HIP(hipMalloc(&pl->lane_pcm[l], need_pcm));
-            pl->lane_pcm_bytes[l] = need_pcm;
-        }
-        if (pl->lane_out_bytes[l] < need_out) {
-            if (pl->lane_out[l]) ZAFX_HIP(hipFree(pl->lane_out[l]));
-            pl->lane_out[l] = nullptr, pl->lane_out_bytes[l] = 0;
-            ZAFX_HIP(hipMalloc(&pl->lane_out[l], need_out));
-            pl->lane_out_bytes[l] = need_out;
-        }
+        ZAFX_HIP(pl->lane_pcm[l].reserve(need_pcm));
+        ZAFX_HIP(pl->lane_out[l].reserve(need_out));
     }
     hipStream_t const s_k = pl->stream;
     hipStream_t const s_up = sets == 2 ? pl->stream_up : s_k, s_down = sets == 2 ? pl->stream_down : s_k;
@@ -2154,11 +2119,11 @@ static int run_host_impl(zafx_plan* pl, const void* h_in, void* h_out, int64_t n
         // than ~70 chunks in flight made the runtime fall off a cliff (1024 clips in 147 chunks: 444 ms instead of 135).
         if (sets == 2 && c >= 2) e = hipEventSynchronize(ev_down[l]);
         if (e == hipSuccess && count * host_in_b > 0)
-            e = hipMemcpyAsync(pcm_bytes > 0 ? pl->lane_pcm[l] : pl->lane_in[l], (const char*)h_in + first * host_in_b, (size_t)(count * host_in_b), hipMemcpyHostToDevice, s_up);
+            e = hipMemcpyAsync(pcm_bytes > 0 ? pl->lane_pcm[l].get() : pl->lane_in[l].get(), (const char*)h_in + first * host_in_b, (size_t)(count * host_in_b), hipMemcpyHostToDevice, s_up);
         if (e == hipSuccess && sets == 2) e = hipEventRecord(ev_up[l], s_up);
         if (e == hipSuccess && sets == 2) e = hipStreamWaitEvent(s_k, ev_up[l], 0);
         if (e != hipSuccess) { ret = fail("zafx_run_host: upload", e); break; }
-        if (pcm_bytes > 0) ret = execute_pcm(pl, pl->lane_pcm[l], pl->lane_out[l], count, n_in, pcm_channels, pcm_bytes, pcm_direct ? nullptr : (float*)pl->lane_in[l]);
+        if (pcm_bytes > 0) ret = execute_pcm(pl, pl->lane_pcm[l], pl->lane_out[l], count, n_in, pcm_channels, pcm_bytes, pcm_direct ? nullptr : (float*)pl->lane_in[l].get());
         else ret = zafx_execute(pl, pl->lane_in[l], pl->lane_out[l], count, n_in);   // (on pl->stream = s_k)
         if (ret) break;
         if (sets == 2) e = hipEventRecord(ev_k[l], s_k);

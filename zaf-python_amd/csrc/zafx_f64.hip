@@ -1719,15 +1719,9 @@ hipError_t build_mel64_fb(zafx_plan& pl) {
     if (!ZAFX_F64_TILED || pl.W != 2 * kF64N || pl.bs_log2m > 0 || nf < 1 || nf > kMel64Rows || pl.h_fb64.size() != (size_t)nf * cols) return hipSuccess;
     const Mel64Tables t = mel64_tables(pl.h_fb64.data(), nf, cols, kMel64Spare);
     if (!t.ok) return hipSuccess;   // (the frame-per-workgroup kernel takes such a matrix)
-    auto up = [](auto** d, const void* h, size_t bytes) -> hipError_t {
-        if (*d) (void)hipFree(*d);
-        *d = nullptr;
-        if (hipError_t e = hipMalloc((void**)d, bytes); e != hipSuccess) return e;
-        return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
     static_assert(sizeof(Mel64Entry) == sizeof(int4), "an entry is one 16-byte load");
-    if (hipError_t e = up(&pl.d_mel64_stream, t.stream.data(), t.stream.size() * sizeof(Mel64Entry)); e != hipSuccess) return e;
-    if (hipError_t e = up(&pl.d_mel64_fin, t.fin.data(), t.fin.size() * sizeof(int)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_mel64_stream.upload(t.stream.data(), t.stream.size() * sizeof(Mel64Entry)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_mel64_fin.upload(t.fin.data(), t.fin.size() * sizeof(int)); e != hipSuccess) return e;
     pl.mel64_steps = t.steps;
     pl.mel64_slots = t.slots;
     pl.mel64_max_parts = t.max_parts;
@@ -1743,10 +1737,7 @@ hipError_t build_mel64_dct(zafx_plan& pl) {   // DCT-II rows transposed and padd
     std::vector<double> t((size_t)2 * half * cp, 0.0);
     for (int c = 0; c < nc; ++c)
         for (int n = 0; n < nf; ++n) t[(size_t)n * cp + c] = pl.h_dct64[(size_t)c * nf + n];
-    if (pl.d_mel64_dctT) (void)hipFree(pl.d_mel64_dctT);
-    pl.d_mel64_dctT = nullptr;
-    if (hipError_t e = hipMalloc((void**)&pl.d_mel64_dctT, t.size() * sizeof(double)); e != hipSuccess) return e;
-    if (hipError_t e = hipMemcpy(pl.d_mel64_dctT, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_mel64_dctT.upload(t.data(), t.size() * sizeof(double)); e != hipSuccess) return e;
     pl.mel64_cpitch = cp;
     pl.mel64_dct_half = half;
     return hipSuccess;
@@ -1774,12 +1765,6 @@ static hipError_t build_cqt64(zafx_plan& pl) {
         if (!pl.cqt64_real) vals.push_back(en.im);
         meta[i] = (en.index & 0x1fff) | (en.index < 0 ? 0x2000 : 0) | ((en.slot + 1) << 14);   // compact index | conjugate << 13 | (slot + 1) << 14
     }
-    auto up = [](auto** d, const void* h, size_t bytes) -> hipError_t {
-        if (*d) (void)hipFree(*d);
-        *d = nullptr;
-        if (hipError_t e = hipMalloc((void**)d, bytes); e != hipSuccess) return e;
-        return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
-    };
     std::vector<double2> tw1((size_t)4 * 1024);   // tw1[i][m] = exp(-2 pi i m 2^i / 16384), in long double
     for (int i = 0; i < 4; ++i)
         for (int m = 0; m < 1024; ++m) {
@@ -1788,11 +1773,11 @@ static hipError_t build_cqt64(zafx_plan& pl) {
             tw1[(size_t)i * 1024 + m] = num == 0 ? make_double2(1.0, 0.0) : num == 4096 ? make_double2(0.0, -1.0) : num == 8192 ? make_double2(-1.0, 0.0)
                                         : num == 12288 ? make_double2(0.0, 1.0) : make_double2((double)cosl(a), (double)sinl(a));
         }
-    if (hipError_t e = up(&pl.d_cqt64_tw1, tw1.data(), tw1.size() * sizeof(double2)); e != hipSuccess) return e;
-    if (hipError_t e = up(&pl.d_cqt64_split, t.split.data(), t.split.size() * sizeof(int)); e != hipSuccess) return e;
-    if (hipError_t e = up(&pl.d_cqt64_vals, vals.data(), vals.size() * sizeof(double)); e != hipSuccess) return e;
-    if (hipError_t e = up(&pl.d_cqt64_meta, meta.data(), meta.size() * sizeof(int)); e != hipSuccess) return e;
-    if (hipError_t e = up(&pl.d_cqt64_fin, t.fin.data(), t.fin.size() * sizeof(int)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_cqt64_tw1.upload(tw1.data(), tw1.size() * sizeof(double2)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_cqt64_split.upload(t.split.data(), t.split.size() * sizeof(int)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_cqt64_vals.upload(vals.data(), vals.size() * sizeof(double)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_cqt64_meta.upload(meta.data(), meta.size() * sizeof(int)); e != hipSuccess) return e;
+    if (hipError_t e = pl.d_cqt64_fin.upload(t.fin.data(), t.fin.size() * sizeof(int)); e != hipSuccess) return e;
     pl.cqt64_kc2 = t.kc2;
     pl.cqt64_cols = t.n_cols;
     pl.cqt64_steps = t.steps;
@@ -1818,14 +1803,9 @@ static int threads_for(size_t smem) { return smem > 80 * 1024 ? kThreadsBig : sm
 
 // grow-only scratch of time-domain frames, owned by the plan
 hipError_t grow_scratch(zafx_plan& pl, size_t need) {
-    if (need <= pl.scratch_bytes) return hipSuccess;
+    if (need <= pl.d_scratch64.bytes()) return hipSuccess;
     if (hipError_t e = hipStreamSynchronize(pl.stream); e != hipSuccess) return e;
-    if (pl.d_scratch64) (void)hipFree(pl.d_scratch64);
-    pl.d_scratch64 = nullptr;
-    pl.scratch_bytes = 0;
-    if (hipError_t e = hipMalloc((void**)&pl.d_scratch64, need); e != hipSuccess) return e;
-    pl.scratch_bytes = need;
-    return hipSuccess;
+    return pl.d_scratch64.reserve(need);
 }
 
 // STFT / mel / mfcc of a window that is not a power of two
@@ -2035,7 +2015,7 @@ hipError_t launch_cqt_f64(zafx_plan& pl, const double* x, double* out, int64_t n
     const int left = diff >= 0 ? (diff + 1) / 2 : -((-diff) / 2);   // ceil((fft_length - step) / 2), zaf.py:615
     pl.ran = "k_cqt_f64";
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads_for(smem)), smem, pl.stream, x, pl.d_tw64, pl.d_tws64, pl.d_indptr, pl.d_indices,
-                       pl.d_values64, reinterpret_cast<double2*>(pl.d_scratch64), out, (long long)n_samples, pl.H, left, T,
+                       pl.d_values64, reinterpret_cast<double2*>(pl.d_scratch64.get()), out, (long long)n_samples, pl.H, left, T,
                        (int)row_pitch(pl, T), total, log2w, pl.prm.n_bins, pl.kind == ZAFX_CHROMA ? pl.prm.octave_resolution : 0, pl.layout);
     return hipGetLastError();
 }

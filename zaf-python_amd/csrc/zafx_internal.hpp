@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/zafx.h"
+#include "zafx_devbuf.hpp"
 #include "zafx_ragged_table.hpp"
 #include "zafx_units.hpp"
 #include "zafx_twiddle.hpp"
@@ -55,26 +56,26 @@ struct PackedBand {
     int n_items = 0;       // work items (a block's band cut into parts of bounded length)
     int n_waves = 0;       // wavefronts the items were dealt to
     int total_steps = 0;
-    float* d_pack = nullptr;     // [total_steps][64] : lane l -> A[l & 15][4*step + (l >> 4)]
-    int4* d_items = nullptr;     // per wave, longest first: {slot id, first column, steps, offset into d_pack (steps)}
-    int* d_wave_ptr = nullptr;   // [n_waves + 1] ranges into d_items
-    int* d_blk_ptr = nullptr;    // [n_blocks + 1] ranges of slot ids belonging to a block
-    float* d_direct = nullptr;   // DCT rows as MFMA A fragments for the register-fed form of k_mel: [wave][j][row block][64 lanes], K-step w + 16 j
+    DevBuf<float> d_pack;     // [total_steps][64] : lane l -> A[l & 15][4*step + (l >> 4)]
+    DevBuf<int4> d_items;     // per wave, longest first: {slot id, first column, steps, offset into d_pack (steps)}
+    DevBuf<int> d_wave_ptr;   // [n_waves + 1] ranges into d_items
+    DevBuf<int> d_blk_ptr;    // [n_blocks + 1] ranges of slot ids belonging to a block
+    DevBuf<float> d_direct;   // DCT rows as MFMA A fragments for the register-fed form of k_mel: [wave][j][row block][64 lanes], K-step w + 16 j
     int direct_j = 0;            // K-steps per wave of that form (0: not available)
-    unsigned short* d_desc = nullptr;   // [total_steps] K-step descriptors of the resident form: first column / 4 | slot id << 8 | item ends << 15
+    DevBuf<unsigned short> d_desc;   // [total_steps] K-step descriptors of the resident form: first column / 4 | slot id << 8 | item ends << 15
     bool desc_ok = false;        // every step fits the 16-bit descriptor
     int n_empty = 0;             // blocks without non-zeros (their zero tiles are written by the streamed form only)
     // k_mel2: whole 16-row blocks (one longer than a SIMD's quarter of the steps is cut in K; at most kMel2Slots cuts) dealt to the four
     // SIMDs longest first, then to a SIMD's waves w, w + 4, w + 8, w + 12, at most two items per wave: d_whole [wave][2] = {first column,
     // steps (-1: no item), offset into d_pack (steps), block | role << 8 (1 owner: stores the tile, 2 helper: hands its partial tile
     // over through LDS) | helper's slot << 10 | owner's mask of slots to add << 12}
-    int4* d_whole = nullptr;
+    DevBuf<int4> d_whole;
     bool whole_ok = false;
     std::vector<int> h_owner;    // (filterbank) wave | place << 8 of the item that owns block b's tile
     // k_mel2, mfcc (on the DCT band): d_dct2 [filterbank block][2 coefficient blocks][4 steps][64] = the DCT rows as A fragments over the
     // block's sixteen filters (lane l -> D[16 c + (l & 15)][16 b + 4 s + (l >> 4)]); d_owner2 [filterbank blocks] = the owner waves
-    float* d_dct2 = nullptr;
-    int* d_owner2 = nullptr;
+    DevBuf<float> d_dct2;
+    DevBuf<int> d_owner2;
     bool dct2_ok = false;
     int max_wave_steps = 0;      // steps of the busiest wave: wave w owns steps [total w / n_waves, total (w + 1) / n_waves)
 };
@@ -83,24 +84,33 @@ constexpr int kMelResidentDct = 4;
 
 }  // namespace zafx
 
-struct zafx_plan {
+// What a plan owns is released by destructors, in this order (zafx_plan_destroy is `delete`): ~zafx_plan waits for the plan's stream, then its
+// members -- every table and staging buffer -- go; ~PlanLanes waits for the upload / download streams, then the lanes go; ~PlanStreams
+// destroys the events, then the streams.  So the streams and events are declared first (in the first base), the buffers after them.
+struct PlanStreams {
     int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // zafx_run_host: upload / download streams and the events between the pipeline's stages ([0..1] upload done, [2..3] kernel
+    // done, [4..5] download done, per buffer set)
+    hipStream_t stream_up = nullptr, stream_down = nullptr;
+    hipEvent_t pipe_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t rg_ev = nullptr;   // the upload of the last ragged table (see h_ragged)
+    ~PlanStreams();
+};
+struct PlanLanes : PlanStreams {
+    zafx::DevBuf<void> lane_in[2], lane_out[2];   // zafx_run_host: two sets of device staging buffers (grow-only, freed with the plan)
+    ~PlanLanes();
+};
+
+struct zafx_plan : PlanLanes {
     int n_cus = 256;   // compute units the plan uses: every persistent grid, carry cut and slot count is sized from it -- the device's count, or fewer
                        // under ZAFX_COMPUTE_UNITS at plan creation (zafx_plan_compute_units)
     int n_cus_device = 256;   // compute units of the device: what sizes an ALLOCATION made per workgroup (never the capped count)
     int kind = 0;
     zafx_params prm{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // zafx_run_host: upload / download streams, the events between the pipeline's stages ([0..1] upload done, [2..3] kernel
-    // done, [4..5] download done, per buffer set) and two sets of device staging buffers (grow-only, freed with the plan)
-    hipStream_t stream_up = nullptr, stream_down = nullptr;
-    hipEvent_t pipe_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void* lane_in[2] = {nullptr, nullptr};
-    void* lane_out[2] = {nullptr, nullptr};
-    size_t lane_in_bytes[2] = {0, 0}, lane_out_bytes[2] = {0, 0};
-    void* lane_pcm[2] = {nullptr, nullptr};   // zafx_run_host_pcm: the uploaded integer PCM of a chunk
-    size_t lane_pcm_bytes[2] = {0, 0};
+    zafx::DevBuf<void> lane_pcm[2];   // zafx_run_host_pcm: the uploaded integer PCM of a chunk
+    ~zafx_plan();
 
     int W = 0;        // window length (or CQT fft_length)
     int H = 0;        // hop / step
@@ -109,24 +119,24 @@ struct zafx_plan {
     int log2e = 0;
 
     // device constants
-    float* d_window = nullptr;
-    float* d_matrix = nullptr;     // ZAFX_LINEAR: dense transform matrix [n_filters][window_length]
-    float4* d_wfold = nullptr;     // MDCT: sign-folded window, 4 taps per packed input (zafx_mdct.hip)
-    float2* d_tw_pass = nullptr;   // per-pass twiddles for fft_frame<log2nf, log2e>
-    float2* d_tw_aux = nullptr;    // real-split roots (STFT family / CQT) or tw8 (MDCT family)
+    zafx::DevBuf<float> d_window;
+    zafx::DevBuf<float> d_matrix;     // ZAFX_LINEAR: dense transform matrix [n_filters][window_length]
+    zafx::DevBuf<float4> d_wfold;     // MDCT: sign-folded window, 4 taps per packed input (zafx_mdct.hip)
+    zafx::DevBuf<float2> d_tw_pass;   // per-pass twiddles for fft_frame<log2nf, log2e>
+    zafx::DevBuf<float2> d_tw_aux;    // real-split roots (STFT family / CQT) or tw8 (MDCT family)
     float cola_gain = 0.f;         // sum(w[0:W:H])  (zaf.py:241)
     zafx::PackedBand fb, dct;
-    int* d_indptr = nullptr;
-    int* d_indices = nullptr;
-    float2* d_values = nullptr;
+    zafx::DevBuf<int> d_indptr;
+    zafx::DevBuf<int> d_indices;
+    zafx::DevBuf<float2> d_values;
     int nnz = 0;
     // k_cqt's view of the kernel matrix (build_cqt_chunks in zafx_capi.cpp): rows sorted by length and dealt out in "steps"
     // (four rows of 16 lanes, two of 32 or one of 64), steps dealt to the wavefronts; entry (iteration, lane) = value + LDS
     // byte address of its spectrum bin
-    int4* d_cqt_waves = nullptr;   // [waves]: {first iteration, iterations, step-end mask (bit i: iteration i ends a step), 0}
-    int* d_cqt_addrs = nullptr;    // [iterations][64]: bits 0-17 byte address of the bin in the LDS spectrum image, 31 conjugate, 29-30 shape of
+    zafx::DevBuf<int4> d_cqt_waves;   // [waves]: {first iteration, iterations, step-end mask (bit i: iteration i ends a step), 0}
+    zafx::DevBuf<int> d_cqt_addrs;    // [iterations][64]: bits 0-17 byte address of the bin in the LDS spectrum image, 31 conjugate, 29-30 shape of
                                    // a step that ends here (0: none), 18-28 row this lane then writes (0x7ff: none)  (zafx_cqt.hip)
-    float* d_cqt_vals = nullptr;   // [iterations][64] float (real matrix) or float2
+    zafx::DevBuf<float> d_cqt_vals;   // [iterations][64] float (real matrix) or float2
     int cqt_n_entries = 0;
     bool cqt_real = false;
     int cqt_resident = 0;          // kCqtResident: the busiest wave's iterations fit the registers; 0: entries streamed from L2 every frame
@@ -134,61 +144,56 @@ struct zafx_plan {
     // consecutive entries, two segments per 4-lane block of v_mfma_f32_4x4x1_16b_f32; 0: not available for this matrix
     int cqt_mm_steps = 0;
     int cqt_mm_segs = 0;              // segments of the longest pair
-    float* d_cqt_mm_vals = nullptr;   // [waves][steps][64]: lane (blk, i): K[row 2 pair + (i & 1)][column of the step] of the block's stream i >> 1
-    int* d_cqt_mm_addr = nullptr;     // [waves][steps][64]: lane (blk, j): LDS byte address of the re (j even) / im (j odd) part of that column's bin, stream j >> 1
-    int* d_cqt_mm_fin = nullptr;      // [pairs]: first stream slot | segments << 16 of the pair (its segments are consecutive stream slots)
+    zafx::DevBuf<float> d_cqt_mm_vals;   // [waves][steps][64]: lane (blk, i): K[row 2 pair + (i & 1)][column of the step] of the block's stream i >> 1
+    zafx::DevBuf<int> d_cqt_mm_addr;     // [waves][steps][64]: lane (blk, j): LDS byte address of the re (j even) / im (j odd) part of that column's bin, stream j >> 1
+    zafx::DevBuf<int> d_cqt_mm_fin;      // [pairs]: first stream slot | segments << 16 of the pair (its segments are consecutive stream slots)
     // mel / mfcc plans of W = 4096 / 8192 (k_melfb): filterbank rows as bands of float32 (values of [first, first + count) of every
     // row back to back; meta [n_filters][3] = first column, count, offset) and the DCT rows dense [n_coefs][n_filters]
-    float* d_fbw = nullptr;
-    int* d_fbw_meta = nullptr;
-    float* d_dctw = nullptr;
-    float2* d_tw_band = nullptr;   // k_mdct_ft32b (MDCT plans of W = 4096): gb[s][q] = g[2 q + s] (1024 entries), then bt[n] = g[n] exp(-2 pi i n / 1024) (512)
-    float2* d_tw_sub = nullptr;    // pass twiddles of the band transforms: 1024 points (k_stft_ft16b; STFT / mel plans of W = 4096), 512 points (k_mdct_ft32b; MDCT plans of W = 4096)
-    float2* d_tw_quad = nullptr;   // exp(-2 pi i n / 8192), n < 4096 (k_stft_ft16q; STFT / mel plans of W = 8192)
-    float2* d_tw_r32 = nullptr;    // pass twiddles of the radix-32 schedule (1024 points as 32 x 32), STFT plans of W = 2048
+    zafx::DevBuf<float> d_fbw;
+    zafx::DevBuf<int> d_fbw_meta;
+    zafx::DevBuf<float> d_dctw;
+    zafx::DevBuf<float2> d_tw_band;   // k_mdct_ft32b (MDCT plans of W = 4096): gb[s][q] = g[2 q + s] (1024 entries), then bt[n] = g[n] exp(-2 pi i n / 1024) (512)
+    zafx::DevBuf<float2> d_tw_sub;    // pass twiddles of the band transforms: 1024 points (k_stft_ft16b; STFT / mel plans of W = 4096), 512 points (k_mdct_ft32b; MDCT plans of W = 4096)
+    zafx::DevBuf<float2> d_tw_quad;   // exp(-2 pi i n / 8192), n < 4096 (k_stft_ft16q; STFT / mel plans of W = 8192)
+    zafx::DevBuf<float2> d_tw_r32;    // pass twiddles of the radix-32 schedule (1024 points as 32 x 32), STFT plans of W = 2048
     // float64 mode (ZAFX_PRECISION_F64, zafx_f64.hip)
-    double* d_window64 = nullptr;
-    double2* d_tw64 = nullptr;     // exp(-2 pi i m / (W/2)), m < W/4
-    double2* d_tws64 = nullptr;    // exp(-2 pi i k / W), k <= W/4
-    double* d_scratch64 = nullptr; // ISTFT: time-domain frames of the current call (grow-only)
-    size_t scratch_bytes = 0;
+    zafx::DevBuf<double> d_window64;
+    zafx::DevBuf<double2> d_tw64;     // exp(-2 pi i m / (W/2)), m < W/4
+    zafx::DevBuf<double2> d_tws64;    // exp(-2 pi i k / W), k <= W/4
+    zafx::DevBuf<double> d_scratch64; // ISTFT: time-domain frames of the current call (grow-only)
     double cola_gain64 = 0.0;
     std::vector<double> h_window64, h_fb64, h_dct64;
-    double* d_fb64 = nullptr;      // mel filterbank rows as bands: values of [first, first + count) of every row, back to back
-    int* d_fb64_meta = nullptr;    // [n_filters][3]: first column, count, offset into d_fb64
-    double* d_dct64 = nullptr;     // [n_coefs][n_filters]
+    zafx::DevBuf<double> d_fb64;      // mel filterbank rows as bands: values of [first, first + count) of every row, back to back
+    zafx::DevBuf<int> d_fb64_meta;    // [n_filters][3]: first column, count, offset into d_fb64
+    zafx::DevBuf<double> d_dct64;     // [n_coefs][n_filters]
     // k_mel_ft8_f64 (W = 2048, reference layout; build_mel64_fb in zafx_f64.hip, zafx_mel64.hpp): the filterbank's non-zeros as one equally
     // long stream per lane
-    int4* d_mel64_stream = nullptr;   // [steps][64] entries {value (2 words), column, slot of the partial sum or -1}
-    int2* d_mel64_fin = nullptr;      // [n_filters]: {first slot, slots} of a filter's partial sums (consecutive, ascending columns)
-    double* d_mel64_dctT = nullptr;   // mfcc: DCT-II rows transposed, [2 mel64_dct_half filters][coefficient pitch (a multiple of 32)], zeros outside
+    zafx::DevBuf<int4> d_mel64_stream;   // [steps][64] entries {value (2 words), column, slot of the partial sum or -1}
+    zafx::DevBuf<int2> d_mel64_fin;      // [n_filters]: {first slot, slots} of a filter's partial sums (consecutive, ascending columns)
+    zafx::DevBuf<double> d_mel64_dctT;   // mfcc: DCT-II rows transposed, [2 mel64_dct_half filters][coefficient pitch (a multiple of 32)], zeros outside
     int mel64_steps = 0, mel64_slots = 0, mel64_max_parts = 0, mel64_cpitch = 0, mel64_dct_half = 0;
     bool mel64_ok = false;
-    double2* d_values64 = nullptr; // CQT kernel values of a float64 plan (complex128)
+    zafx::DevBuf<double2> d_values64; // CQT kernel values of a float64 plan (complex128)
     // k_cqt_ft_f64 (fft_length 32768; build_cqt64 in zafx_f64.hip, zafx_cqt64.hpp)
-    double2* d_cqt64_tw1 = nullptr;     // [4][1024]: exp(-2 pi i m 2^i / 16384), the first pass's twiddles (products of these)
-    int* d_cqt64_split = nullptr;       // [2 rounds][kc2][512]: the one-sided bins a thread splits (bin | compact index << 14, -1: none)
-    double* d_cqt64_vals = nullptr;     // [steps][512] float64 (cqt64_real) or complex128: the matrix's non-zeros as one stream per thread ...
-    int* d_cqt64_meta = nullptr;        // ... compact index | conjugate << 13 | (slot of the partial sum + 1) << 14
-    int2* d_cqt64_fin = nullptr;        // [rows]: {first slot, slots}
+    zafx::DevBuf<double2> d_cqt64_tw1;     // [4][1024]: exp(-2 pi i m 2^i / 16384), the first pass's twiddles (products of these)
+    zafx::DevBuf<int> d_cqt64_split;       // [2 rounds][kc2][512]: the one-sided bins a thread splits (bin | compact index << 14, -1: none)
+    zafx::DevBuf<double> d_cqt64_vals;     // [steps][512] float64 (cqt64_real) or complex128: the matrix's non-zeros as one stream per thread ...
+    zafx::DevBuf<int> d_cqt64_meta;        // ... compact index | conjugate << 13 | (slot of the partial sum + 1) << 14
+    zafx::DevBuf<int2> d_cqt64_fin;        // [rows]: {first slot, slots}
     int cqt64_kc2 = 0, cqt64_cols = 0, cqt64_steps = 0, cqt64_slots = 0, cqt64_max_parts = 0, cqt64_klo = 511;   // klo: (highest kernel column) >> 4, what the sub-transforms' last pass may skip (fft1024_cq)
     bool cqt64_ok = false, cqt64_dirty = true, cqt64_real = false;
     int bs_log2m = 0;              // > 0: window that is not a power of two -- Bluestein convolution length 2^bs_log2m (zafx_f64.hip, zafx_bs32.hip)
-    void* d_pcm_float = nullptr;   // zafx_execute_pcm's float32 staging for the kinds that do not (grow-only)
-    size_t pcm_float_bytes = 0;
+    zafx::DevBuf<void> d_pcm_float;   // zafx_execute_pcm's float32 staging for the kinds that do not (grow-only)
     // zafx_execute_ragged / zafx_execute_center_ragged: the batch's table (zafx::RgClip records, then the clip of every tile; zafx::CenterUnit
-    // records) on the device and its page-locked staging copy, both grow-only; rg_ev marks the upload of the last call -- the host waits for
+    // records) on the device and its page-locked staging copy, both grow-only; rg_ev (PlanStreams) marks the upload of the last call -- the host waits for
     // it before it writes the staging copy again
-    void* d_ragged = nullptr;
-    size_t ragged_bytes = 0;
-    void* h_ragged = nullptr;
-    size_t ragged_host_bytes = 0;
-    hipEvent_t rg_ev = nullptr;
+    zafx::DevBuf<void> d_ragged;
+    zafx::PinnedBuf h_ragged;
     int dct_half = 0;              // ZAFX_DCT, types II-IV, N = 4 j with N / 2 not a power of two: N / 2, the points of the transform inside k_dct<.., BS> (zafx_dct.hip)
     long long dct_den2 = 0;        // ZAFX_DCT on the chirp-z form: 2 D, the denominator of its chirp exp(-i pi j^2 / (2 D)) (k_dct_bs32)
-    float2* d_bs_chirp = nullptr;  // float32 Bluestein plans: c[n] = exp(-i pi n^2 / W), n < W
-    float2* d_bs_bhat = nullptr;   // ... and FFT_M of the wrapped conjugate chirp
-    double2* d_bhat64 = nullptr;   // FFT of the wrapped conjugate chirp, 2^bs_log2m entries
+    zafx::DevBuf<float2> d_bs_chirp;  // float32 Bluestein plans: c[n] = exp(-i pi n^2 / W), n < W
+    zafx::DevBuf<float2> d_bs_bhat;   // ... and FFT_M of the wrapped conjugate chirp
+    zafx::DevBuf<double2> d_bhat64;   // FFT of the wrapped conjugate chirp, 2^bs_log2m entries
     std::vector<double2> h_values64;
     int cqt_k_lo = 0, cqt_k_hi = -1, cqt_k_special = 0;   // real-split pairs the kernel's columns need
     bool cqt_dirty = true;
@@ -201,9 +206,9 @@ struct zafx_plan {
     // k_stft_ft16's DYN form (tiles claimed at run time): eight queue counters and the count of the workgroups that have left, each on a
     // 128-byte line of its own (zafx::kClaimInts ints, zero between launches: the last workgroup of a launch puts them back).
     // ZAFX_STFT_DYNAMIC=0 in the environment at plan creation keeps the plan on the static split.
-    int* d_claim = nullptr;
+    zafx::DevBuf<int> d_claim;
     bool stft_dynamic = false;
-    unsigned long long* d_tail = nullptr;   // ZAFX_PROF builds: per-workgroup finish times of k_stft_ft16 (zafx_debug_stft_tail_bind)
+    zafx::DevBuf<unsigned long long> d_tail;   // ZAFX_PROF builds: per-workgroup finish times of k_stft_ft16 (zafx_debug_stft_tail_bind)
     std::string kernel_name;            // the kernel this plan is expected to run (set at creation)
     mutable std::atomic<int> cqt_form_ran{0};       // the form k_cqt's last launch took: 1 matrix-core, 2 lane reduction (both are "k_cqt"); zafx_plan_cqt_form
     mutable std::atomic<const char*> ran{nullptr};  // the kernel the last execute really launched (routes depend on T, alignment and hop); zafx_plan_last_kernel_name

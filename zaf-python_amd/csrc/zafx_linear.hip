@@ -165,7 +165,7 @@ const char* linear_kernel_name() { return "k_linear"; }   // prefix of both kern
 hipError_t launch_linear(const zafx_plan& pl, const float* x, float* y, int64_t n_clips) {
     if (n_clips <= 0) return hipSuccess;
     const int n_rows = pl.prm.n_filters, n_cols = pl.W;
-    if (n_cols % kBigK == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(pl.d_matrix) % 16 == 0 &&
+    if (n_cols % kBigK == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(pl.d_matrix.get()) % 16 == 0 &&
         (long long)n_rows * n_clips >= 128LL * 128 * 64) {   // enough tiles to fill the chip; small problems keep the 64-tile kernel
         const dim3 big((unsigned)((n_rows + kBigTile - 1) / kBigTile), (unsigned)((n_clips + kBigTile - 1) / kBigTile));
         pl.ran = "k_linear128";

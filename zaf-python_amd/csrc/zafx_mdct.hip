@@ -1984,7 +1984,7 @@ static hipError_t run_imdct(const zafx_plan& pl, const float* coefs, float* y, i
     if constexpr (ZAFX_IMDCT_QUAD && LOG2NF == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
         // W = 8192: the two-class kernel (four frames per 16-byte piece: a row pitch that is a multiple of 4; 32-bit byte offsets inside a clip)
         const int64_t TP = row_pitch(pl, T);
-        if (pl.d_tw_sub && pl.d_tw_quad && TP % 4 == 0 && reinterpret_cast<uintptr_t>(coefs) % 16 == 0 && reinterpret_cast<uintptr_t>(pl.d_window) % 16 == 0 &&
+        if (pl.d_tw_sub && pl.d_tw_quad && TP % 4 == 0 && reinterpret_cast<uintptr_t>(coefs) % 16 == 0 && reinterpret_cast<uintptr_t>(pl.d_window.get()) % 16 == 0 &&
             (long long)4096 * TP * 4 < (1LL << 31) && n_clips * (((long long)T + 15) / 16 + 1) < (1LL << 30))
             return run_imdct_quad(pl, coefs, y, n_clips, T, out_len);
     }

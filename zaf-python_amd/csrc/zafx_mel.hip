@@ -1363,16 +1363,18 @@ static hipError_t run_mel_wide(zafx_plan& pl, const float* x, float* out, int64_
         if (chunk >= m) chunk = chunk / m * m;
     }
     if (hipError_t e = grow_scratch(pl, (size_t)chunk * per_clip); e != hipSuccess) return e;
-    float* spec = reinterpret_cast<float*>(pl.d_scratch64);
+    float* spec = reinterpret_cast<float*>(pl.d_scratch64.get());
     // the spectrum kernels see an STFT plan of this window: one-sided |X| (mel, zaf.py:370) or |X|^2 (mfcc, zaf.py:437-439),
-    // reference layout, rows padded to 32 floats
-    zafx_plan st;
+    // reference layout, rows padded to 32 floats -- a view of pl: its tables are borrowed, and its stream is pl's, handed back before the view dies
+    struct View : zafx_plan {
+        ~View() { stream = nullptr; }
+    } st;
     st.device = pl.device; st.n_cus = pl.n_cus; st.n_cus_device = pl.n_cus_device; st.kind = ZAFX_STFT; st.prm = pl.prm; st.stream = pl.stream;
     st.prm.spectrum = mfcc ? ZAFX_SPECTRUM_POWER : ZAFX_SPECTRUM_MAGNITUDE;
     st.prm.row_align = 32;
     st.W = pl.W; st.H = pl.H; st.layout = ZAFX_LAYOUT_FT; st.log2nf = pl.log2nf; st.log2e = pl.log2e;
-    st.d_window = pl.d_window; st.d_tw_pass = pl.d_tw_pass; st.d_tw_aux = pl.d_tw_aux; st.d_tw_sub = pl.d_tw_sub; st.d_tw_r32 = pl.d_tw_r32; st.d_tw_quad = pl.d_tw_quad;
-    st.bs_log2m = pl.bs_log2m; st.d_bs_chirp = pl.d_bs_chirp; st.d_bs_bhat = pl.d_bs_bhat;   // (a window that is not a power of two: the Bluestein STFT)
+    st.d_window.borrow(pl.d_window); st.d_tw_pass.borrow(pl.d_tw_pass); st.d_tw_aux.borrow(pl.d_tw_aux); st.d_tw_sub.borrow(pl.d_tw_sub); st.d_tw_r32.borrow(pl.d_tw_r32); st.d_tw_quad.borrow(pl.d_tw_quad);
+    st.bs_log2m = pl.bs_log2m; st.d_bs_chirp.borrow(pl.d_bs_chirp); st.d_bs_bhat.borrow(pl.d_bs_bhat);   // (a window that is not a power of two: the Bluestein STFT)
     const size_t smem = mfcc ? (size_t)pl.prm.n_filters * 64 * sizeof(float) : 0;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k_melfb), pl.device, std::max<size_t>(smem, 1)); e != hipSuccess) return e;
     const int64_t out_per_clip = pl.layout == ZAFX_LAYOUT_FT ? (int64_t)(mfcc ? pl.prm.n_coefs : pl.prm.n_filters) * row_pitch(pl, T)

@@ -2699,15 +2699,6 @@ static hipError_t run_stft_tf(const zafx_plan& pl, const float* x, float2* out, 
 template <int LOG2N, int LAYOUT, int SPEC>
 static hipError_t run_stft(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
     const bool aligned = (n_samples % 2 == 0) && (pl.H % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0);
-#ifndef ZAFX_STFT_FAT8
-#define ZAFX_STFT_FAT8 0   // (measured: 6.54 ms against 3.13 ms for the one-workgroup-per-tile kernel at W = 4096 -- eight waves, one 2048-point
-#endif                     //  frame each as 32 x 32 x 2 with the window from global memory, are latency bound; profiles/r03_notes.md)
-    if constexpr (ZAFX_STFT_FAT8 && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 4096, reference layout: the persistent kernel with 8-frame tiles (experiment, off)
-        if (pl.d_tw_r32)
-            return aligned ? run_stft_fat<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T)
-                           : run_stft_fat<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T);
-    }
 #ifndef ZAFX_STFT_BAND
 #define ZAFX_STFT_BAND 1
 #endif
@@ -3430,7 +3421,6 @@ bool stft_pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, i
 }
 
 const char* stft_kernel_name(int log2n, int layout) {
-    if (ZAFX_STFT_FAT8 && log2n == 11 && layout == ZAFX_LAYOUT_FT) return "k_stft_ft16";
     if (ZAFX_STFT_BAND && log2n == 11 && layout == ZAFX_LAYOUT_FT) return "k_stft_ft16b";
     if (ZAFX_STFT_QUAD && log2n == 12 && layout == ZAFX_LAYOUT_FT) return "k_stft_ft16q";   // (planned: the four-class family; what RAN is last_kernel)
     return stft_use_fat(log2n, layout) ? "k_stft_ft16" : stft_use_tf(log2n, layout) ? "k_stft_tf" : "k_stft";
@@ -3620,10 +3610,10 @@ ZAFX_PROF_EXPORT(zafx_debug_prof_stft, g_prof_stft)
 extern "C" int zafx_debug_stft_tail_bind(zafx_plan* pl, int on) {
     if (!pl || hipSetDevice(pl->device) != hipSuccess) return 1;
     const size_t bytes = (size_t)pl->n_cus_device * 2 * 4 * sizeof(unsigned long long);
-    if (on && !pl->d_tail && hipMalloc(reinterpret_cast<void**>(&pl->d_tail), bytes) != hipSuccess) return 1;
+    if (on && pl->d_tail.reserve(bytes) != hipSuccess) return 1;
     if (hipStreamSynchronize(pl->stream) != hipSuccess) return 1;
     if (on && hipMemset(pl->d_tail, 0, bytes) != hipSuccess) return 1;
-    unsigned long long* p = on ? pl->d_tail : nullptr;
+    unsigned long long* p = on ? pl->d_tail.get() : nullptr;
     return hipMemcpyToSymbol(HIP_SYMBOL(zafx::g_stft_tail), &p, sizeof(p)) != hipSuccess;
 }
 extern "C" int zafx_debug_stft_tail_read(zafx_plan* pl, unsigned long long* out, int n_words) {

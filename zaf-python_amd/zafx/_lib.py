@@ -73,6 +73,7 @@ SYMBOLS = {
     "zafx_host_free": (_i, [_vp]),
     "zafx_plan_create": (_i, [ctypes.POINTER(_vp), _i, _i, ctypes.POINTER(ZafxParams)]),
     "zafx_plan_destroy": (_i, [_vp]),
+    "zafx_plan_live_allocations": (_i, [ctypes.POINTER(_i64)]),
     "zafx_plan_set_constant": (_i, [_vp, _i, _vp, _sz]),
     "zafx_plan_out_dims": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
     "zafx_plan_row_pitch": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
