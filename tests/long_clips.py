@@ -2,7 +2,8 @@
 tests/test_long_clips_host.py).
 
 The launchers take their fast kernels only below fixed lengths of a single clip -- the kernels address a clip through one buffer descriptor
-with 32-bit byte offsets, or count samples in 32 bits (BOUNDS below, read off the dispatch code).  A clip that long has an output of 1 - 4 GiB,
+with 32-bit byte offsets, or count samples in 32 bits (BOUNDS below, read off zaf-python_amd/csrc/zafx_routes.hpp, which
+tests/test_routes_host.py holds to every record on the CPU).  A clip that long has an output of 1 - 4 GiB,
 and no oracle transforms it.  So the clip is PERIODIC:
 
     x[n] = p[n mod P],   P = Q hop,   Q = 7   (coprime to the 8-, 16- and 32-frame tiles: equal frames land on every position of a tile)
@@ -448,108 +449,108 @@ def _bound(name, kind, w, hop, options, cond, text, source, kernel_below, above,
 
 _LO, _HI = 1 << 20, 9 << 28
 BOUNDS = [
-    # |X| and |X|^2 at W = 2048 run on k_mel2 (launch_spec2) below 2^29 samples, on k_stft_ft16's magnitude / power forms above.  The hop is W,
-    # so the output stays at 1 GiB; launch_spec2 has no condition on T H, so nothing coincides.
-    _bound("stft_magnitude_2048", "magnitude", 2048, 2048, dict(row_align=0), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_mel.hip:launch_spec2",
+    # |X| and |X|^2 at W = 2048 run on k_mel2 (spec2_usable) below 2^29 samples, on k_stft_ft16's magnitude / power forms above.  The hop is W,
+    # so the output stays at 1 GiB; spec2_usable has no condition on T H, so nothing coincides.
+    _bound("stft_magnitude_2048", "magnitude", 2048, 2048, dict(row_align=0), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_routes.hpp:spec2_usable",
            "k_mel2", "k_stft_ft16", _LO, _HI),
-    _bound("stft_power_2048_padded", "power", 2048, 2048, dict(row_align=32), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_mel.hip:launch_spec2",
+    _bound("stft_power_2048_padded", "power", 2048, 2048, dict(row_align=32), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_routes.hpp:spec2_usable",
            "k_mel2", "k_stft_ft16", _LO, _HI),
     # Complex rows off the line grid (compact, T % 16 != 0) run on k_stft_ft16c: its buffer-load form below the bound, its pointer form above
     # (one kernel name, two instantiations).  T H >= n + H at every hop, so `n_samples < 2^29` never decides: it is implied by T H < 2^29.
     # The lengths between n_below and n_above give T = 2^18, rows of whole lines, which k_stft_ft16 takes: they are not on this route.
     _bound("stft_one_sided_2048_carry", "stft_one_sided", 2048, 2048, dict(row_align=0), lambda n: n < 1 << 29 and _t(n, 2048, 2048) * 2048 < 1 << 29,
-           "n_samples < 2^29 and T H < 2^29 (even n)", "zafx_stft.hip:run_stft", "k_stft_ft16c", "k_stft_ft16c", _LO, _HI,
+           "n_samples < 2^29 and T H < 2^29 (even n)", "zafx_routes.hpp:frames_addressable", "k_stft_ft16c", "k_stft_ft16c", _LO, _HI,
            on_route=lambda n: n % 2 == 0 and _t(n, 2048, 2048) % 16 != 0, route="n even, T no multiple of 16",
            note="n_samples < 2^29 is implied by T H < 2^29 (T H >= n + H); T = 2^18 lies between the two lengths and runs k_stft_ft16"),
     _bound("stft_two_sided_2048_carry", "stft", 2048, 2048, dict(row_align=0), lambda n: n < 1 << 29 and _t(n, 2048, 2048) * 2048 < 1 << 29,
-           "n_samples < 2^29 and T H < 2^29 (even n)", "zafx_stft.hip:run_stft", "k_stft_ft16c", "k_stft_ft16c", _LO, _HI,
+           "n_samples < 2^29 and T H < 2^29 (even n)", "zafx_routes.hpp:frames_addressable", "k_stft_ft16c", "k_stft_ft16c", _LO, _HI,
            on_route=lambda n: n % 2 == 0 and _t(n, 2048, 2048) % 16 != 0, route="n even, T no multiple of 16",
            note="as the one-sided record; 4 GiB of output"),
     # The forward STFT at W = 4096 and 8192: these conditions carry the 16-frame halo of the tile the kernels read ahead ((T + 16) H); the
     # generic one-workgroup-per-tile k_stft above.  T H >= n + H, so `n_samples < 2^29` never decides.  Hop W keeps the outputs at 0.5 - 2 GiB.
     _bound("stft_one_sided_4096_carry", "stft_one_sided", 4096, 4096, dict(row_align=0), lambda n: n < 1 << 29 and (_t(n, 4096, 4096) + 16) * 4096 < 1 << 29,
-           "n_samples < 2^29 and (T + 16) H < 2^29", "zafx_stft.hip:run_stft", "k_stft_ft16bc", "k_stft", _LO, _HI,
+           "n_samples < 2^29 and (T + 16) H < 2^29", "zafx_routes.hpp:band_addressable", "k_stft_ft16bc", "k_stft", _LO, _HI,
            on_route=lambda n: _t(n, 4096, 4096) % 16 != 0, route="T no multiple of 16", note="n_samples < 2^29 is implied by (T + 16) H < 2^29"),
     _bound("stft_magnitude_4096", "magnitude", 4096, 4096, dict(row_align=0), lambda n: n < 1 << 29 and (_t(n, 4096, 4096) + 16) * 4096 < 1 << 29,
-           "n_samples < 2^29 and (T + 16) H < 2^29", "zafx_stft.hip:run_stft", "k_stft_ft16b", "k_stft", _LO, _HI, note="n_samples < 2^29 is implied"),
+           "n_samples < 2^29 and (T + 16) H < 2^29", "zafx_routes.hpp:band_addressable", "k_stft_ft16b", "k_stft", _LO, _HI, note="n_samples < 2^29 is implied"),
     _bound("stft_magnitude_8192", "magnitude", 8192, 8192, dict(row_align=0), lambda n: n < 1 << 29 and (_t(n, 8192, 8192) + 16) * 8192 < 1 << 28,
-           "n_samples < 2^29 and (T + 16) H < 2^28", "zafx_stft.hip:run_stft", "k_stft_ft16q", "k_stft", _LO, _HI, note="n_samples < 2^29 is implied"),
+           "n_samples < 2^29 and (T + 16) H < 2^28", "zafx_routes.hpp:quad_addressable", "k_stft_ft16q", "k_stft", _LO, _HI, note="n_samples < 2^29 is implied"),
     # mel at W = 4096: the fused two-band kernel k_mel_ft16b with the same halo; the spectrum kernel + k_melfb above
     _bound("mel_4096", "mel", 4096, 2048, dict(), lambda n: n < 1 << 29 and (_t(n, 4096, 2048) + 16) * 2048 < 1 << 29,
-           "n_samples < 2^29 and (T + 16) H < 2^29", "zafx_stft.hip:mel_band_usable", "k_mel_ft16b", "k_melfb", _LO, _HI, note="n_samples < 2^29 is implied"),
+           "n_samples < 2^29 and (T + 16) H < 2^29", "zafx_routes.hpp:mel_band_usable", "k_mel_ft16b", "k_melfb", _LO, _HI, note="n_samples < 2^29 is implied"),
     # ISTFT at W = 2048: the carry kernel k_istft_ft16 addresses the clip's spectrum -- counted as W rows, one-sided too -- through one
     # descriptor with signed 32-bit byte offsets; the generic k_istft above.  The condition is on the row pitch: T here, T rounded up to 16
     # for a row_align plan.  Lengths are those of the clip whose STFT is inverted (hop 1024: T = n / 1024 + 1 for n a multiple of 1024).
     _bound("istft_2048", "istft", 2048, 1024, dict(row_align=0), lambda n: 2048 * _t(n, 2048, 1024) * 8 < 1 << 31, "W pitch 8 < 2^31",
-           "zafx_stft.hip:run_istft", "k_istft_ft16", "k_istft", _LO, _HI, on_route=lambda n: n % 1024 == 0, route="n a multiple of the hop"),
+           "zafx_routes.hpp:spectrum_addressable", "k_istft_ft16", "k_istft", _LO, _HI, on_route=lambda n: n % 1024 == 0, route="n a multiple of the hop"),
     _bound("istft_one_sided_2048_padded", "istft_one_sided", 2048, 1024, dict(row_align=16), lambda n: 2048 * _pitch(_t(n, 2048, 1024), 16) * 8 < 1 << 31,
-           "W pitch 8 < 2^31 (W rows counted for a one-sided spectrum too)", "zafx_stft.hip:run_istft", "k_istft_ft16", "k_istft", _LO, _HI,
+           "W pitch 8 < 2^31 (W rows counted for a one-sided spectrum too)", "zafx_routes.hpp:spectrum_addressable", "k_istft_ft16", "k_istft", _LO, _HI,
            on_route=lambda n: n % 1024 == 0, route="n a multiple of the hop"),
     # W = 4096 at hop W / 2 (the two-class kernel k_istft_ft16d; the band form k_istft_ft16b has the same condition) and W = 8192 at hop W / 2
     # (the four-class kernel k_istft_ft8q): 32-bit byte offsets inside a clip's spectrum, the generic k_istft above
     _bound("istft_4096", "istft", 4096, 2048, dict(row_align=0), lambda n: 4096 * _t(n, 4096, 2048) * 8 < 1 << 31, "4096 pitch 8 < 2^31",
-           "zafx_stft.hip:run_istft", "k_istft_ft16d", "k_istft", _LO, _HI, on_route=lambda n: n % 2048 == 0, route="n a multiple of the hop"),
+           "zafx_routes.hpp:spectrum_addressable", "k_istft_ft16d", "k_istft", _LO, _HI, on_route=lambda n: n % 2048 == 0, route="n a multiple of the hop"),
     _bound("istft_one_sided_4096", "istft_one_sided", 4096, 2048, dict(row_align=0), lambda n: 4096 * _t(n, 4096, 2048) * 8 < 1 << 31,
-           "4096 pitch 8 < 2^31 (W rows counted for a one-sided spectrum too)", "zafx_stft.hip:run_istft", "k_istft_ft16d", "k_istft", _LO, _HI,
+           "4096 pitch 8 < 2^31 (W rows counted for a one-sided spectrum too)", "zafx_routes.hpp:spectrum_addressable", "k_istft_ft16d", "k_istft", _LO, _HI,
            on_route=lambda n: n % 2048 == 0, route="n a multiple of the hop"),
     _bound("istft_8192", "istft", 8192, 4096, dict(row_align=0), lambda n: 8192 * _t(n, 8192, 4096) * 8 < 1 << 31, "8192 pitch 8 < 2^31",
-           "zafx_stft.hip:run_istft", "k_istft_ft8q", "k_istft", _LO, _HI, on_route=lambda n: n % 4096 == 0, route="n a multiple of the hop"),
+           "zafx_routes.hpp:spectrum_addressable", "k_istft_ft8q", "k_istft", _LO, _HI, on_route=lambda n: n % 4096 == 0, route="n a multiple of the hop"),
     _bound("istft_one_sided_8192", "istft_one_sided", 8192, 4096, dict(row_align=0), lambda n: 8192 * _t(n, 8192, 4096) * 8 < 1 << 31,
-           "8192 pitch 8 < 2^31 (W rows counted for a one-sided spectrum too)", "zafx_stft.hip:run_istft", "k_istft_ft8q", "k_istft", _LO, _HI,
+           "8192 pitch 8 < 2^31 (W rows counted for a one-sided spectrum too)", "zafx_routes.hpp:spectrum_addressable", "k_istft_ft8q", "k_istft", _LO, _HI,
            on_route=lambda n: n % 4096 == 0, route="n a multiple of the hop"),
     # W = 4096 at another hop (a multiple of 4, at least 512): the band form k_istft_ft16b, the same condition
     _bound("istft_4096_band", "istft", 4096, 1024, dict(row_align=0), lambda n: 4096 * _t(n, 4096, 1024) * 8 < 1 << 31, "4096 pitch 8 < 2^31",
-           "zafx_stft.hip:run_istft", "k_istft_ft16b", "k_istft", _LO, _HI, on_route=lambda n: n % 1024 == 0, route="n a multiple of the hop"),
+           "zafx_routes.hpp:spectrum_addressable", "k_istft_ft16b", "k_istft", _LO, _HI, on_route=lambda n: n % 1024 == 0, route="n a multiple of the hop"),
     # MDCT at W = 2048: k_mdct_ft32's 16-byte buffer loads below 2^28 samples, its 4-byte edge form above (one kernel name)
-    _bound("mdct_2048", "mdct", 2048, 1024, dict(row_align=32), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_mdct.hip:run_mdct_p",
+    _bound("mdct_2048", "mdct", 2048, 1024, dict(row_align=32), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_routes.hpp:mdct_aligned",
            "k_mdct_ft32", "k_mdct_ft32", _LO, _HI, on_route=lambda n: n % 4 == 0, route="n a multiple of 4"),
     # the same on compact rows off the 64-byte grid (T = 262145): the carry instantiation below the bound, the plain 4-byte form above
-    _bound("mdct_2048_carry", "mdct", 2048, 1024, dict(row_align=0), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_mdct.hip:run_mdct_p",
+    _bound("mdct_2048_carry", "mdct", 2048, 1024, dict(row_align=0), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_routes.hpp:mdct_aligned",
            "k_mdct_ft32", "k_mdct_ft32", _LO, _HI, on_route=lambda n: n % 4 == 0 and _tm(n, 2048) % 16 != 0, route="n a multiple of 4, T no multiple of 16"),
     # MDCT at W = 4096: the two-band kernels (16-byte buffer loads) below 2^28 samples -- whole half lines: k_mdct_ft32b, compact rows off them:
     # the carry form k_mdct_ft32bc --, the generic k_mdct above
-    _bound("mdct_4096", "mdct", 4096, 2048, dict(row_align=32), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_mdct.hip:run_mdct",
+    _bound("mdct_4096", "mdct", 4096, 2048, dict(row_align=32), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_routes.hpp:mdct_aligned",
            "k_mdct_ft32b", "k_mdct", _LO, _HI, on_route=lambda n: n % 4 == 0, route="n a multiple of 4"),
-    _bound("mdct_4096_carry", "mdct", 4096, 2048, dict(row_align=0), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_mdct.hip:run_mdct",
+    _bound("mdct_4096_carry", "mdct", 4096, 2048, dict(row_align=0), lambda n: n < 1 << 28, "n_samples < 2^28 (n a multiple of 4)", "zafx_routes.hpp:mdct_aligned",
            "k_mdct_ft32bc", "k_mdct", _LO, _HI, on_route=lambda n: n % 4 == 0 and _tm(n, 4096) % 16 != 0, route="n a multiple of 4, T no multiple of 16"),
     # MDCT at W = 8192: the four-class kernel k_mdct_ft32q reads 33 frames of halo through the clip's descriptor; the generic k_mdct above.
     # (T + 33) 4096 >= n + 34 * 4096, so `n_samples < 2^28` never decides: it is implied.
     _bound("mdct_8192", "mdct", 8192, 4096, dict(row_align=32), lambda n: n < 1 << 28 and (_tm(n, 8192) + 33) * 4096 < 1 << 28,
-           "n_samples < 2^28 and (T + 33) 4096 < 2^28", "zafx_mdct.hip:run_mdct", "k_mdct_ft32q", "k_mdct", _LO, _HI,
+           "n_samples < 2^28 and (T + 33) 4096 < 2^28", "zafx_routes.hpp:mdct_route", "k_mdct_ft32q", "k_mdct", _LO, _HI,
            note="n_samples < 2^28 is implied by (T + 33) 4096 < 2^28"),
     # IMDCT at W = 8192: k_imdct_q (four frames per 16-byte piece: a pitch that is a multiple of 4) with 32-bit byte offsets inside a clip's
     # coefficients, the generic k_imdct above
     _bound("imdct_8192", "imdct", 8192, 4096, dict(row_align=0), lambda n: 4096 * _tm(n, 8192) * 4 < 1 << 31, "4096 pitch 4 < 2^31 (pitch a multiple of 4)",
-           "zafx_mdct.hip:run_imdct", "k_imdct_q", "k_imdct", _LO, _HI, on_route=lambda n: n % 4096 == 0 and _tm(n, 8192) % 4 == 0,
+           "zafx_routes.hpp:imdct_route", "k_imdct_q", "k_imdct", _LO, _HI, on_route=lambda n: n % 4096 == 0 and _tm(n, 8192) % 4 == 0,
            route="n a multiple of the hop, T a multiple of 4"),
     # IMDCT at W = 2048: k_imdct's 16-byte gather while a clip's coefficients stay below 2^32 bytes, its 4-byte gather above (one kernel name).
     # The only 2^32 bound of the equal-length launchers: 4 GiB of coefficients and 4 GiB of samples.
     _bound("imdct_2048", "imdct", 2048, 1024, dict(row_align=32, split=True), lambda n: 1024 * _pitch(_tm(n, 2048), 32) * 4 < 1 << 32, "M pitch 4 < 2^32",
            "zafx_mdct.hip:k_imdct", "k_imdct", "k_imdct", _LO, _HI, on_route=lambda n: n % 1024 == 0, route="n a multiple of the hop"),
     # mel / MFCC at W = 2048: the aligned form of the fused kernel below 2^29 samples, the pointer form above (one kernel name)
-    _bound("mel_2048", "mel", 2048, 1024, dict(), lambda n: n < 1 << 29, "n_samples < 2^29 (even n)", "zafx_mel.hip:run_mel_any", "k_mel2", "k_mel2", _LO, _HI,
+    _bound("mel_2048", "mel", 2048, 1024, dict(), lambda n: n < 1 << 29, "n_samples < 2^29 (even n)", "zafx_routes.hpp:mel_aligned", "k_mel2", "k_mel2", _LO, _HI,
            on_route=lambda n: n % 2 == 0, route="n even"),
-    _bound("mfcc_2048", "mfcc", 2048, 1024, dict(), lambda n: n < 1 << 29, "n_samples < 2^29 (even n)", "zafx_mel.hip:run_mel_any", "k_mel2", "k_mel2", _LO, _HI,
+    _bound("mfcc_2048", "mfcc", 2048, 1024, dict(), lambda n: n < 1 << 29, "n_samples < 2^29 (even n)", "zafx_routes.hpp:mel_aligned", "k_mel2", "k_mel2", _LO, _HI,
            on_route=lambda n: n % 2 == 0, route="n even"),
-    _bound("mel_mfcc_2048", "mel_mfcc", 2048, 1024, dict(), lambda n: n < 1 << 29, "n_samples < 2^29 (even n)", "zafx_mel.hip:run_mel_any", "k_mel2", "k_mel2",
+    _bound("mel_mfcc_2048", "mel_mfcc", 2048, 1024, dict(), lambda n: n < 1 << 29, "n_samples < 2^29 (even n)", "zafx_routes.hpp:mel_aligned", "k_mel2", "k_mel2",
            _LO, _HI, on_route=lambda n: n % 2 == 0, route="n even"),
     # int16 PCM on the device (zafx_execute_pcm, mono): the integers are read in the kernels' own loads below the bound; above it the clip is
     # converted into the plan's float32 staging array first and takes the float route.  (The STFT's T H < 2^29 implies n_frames < 2^29.)
     _bound("stft_pcm16_one_sided_2048", "stft_one_sided", 2048, 2048, dict(row_align=16, pcm=True), lambda n: n < 1 << 29 and _t(n, 2048, 2048) * 2048 < 1 << 29,
-           "n_frames < 2^29 and T H < 2^29 (even n_frames)", "zafx_stft.hip:stft_pcm_direct_ok", "k_stft_ft16", "k_stft_ft16", _LO, _HI,
+           "n_frames < 2^29 and T H < 2^29 (even n_frames)", "zafx_routes.hpp:stft_pcm_direct_ok", "k_stft_ft16", "k_stft_ft16", _LO, _HI,
            on_route=lambda n: n % 2 == 0, route="n even", note="n_frames < 2^29 is implied by T H < 2^29"),
-    _bound("mel_pcm16_2048", "mel", 2048, 1024, dict(pcm=True), lambda n: n < 1 << 29, "n_frames < 2^29", "zafx_mel.hip:pcm_direct_ok", "k_mel2", "k_mel2", _LO, _HI),
-    _bound("stft_pcm16_magnitude_2048", "magnitude", 2048, 2048, dict(row_align=0, pcm=True), lambda n: n < 1 << 29, "n_frames < 2^29", "zafx_mel.hip:pcm_direct_ok",
+    _bound("mel_pcm16_2048", "mel", 2048, 1024, dict(pcm=True), lambda n: n < 1 << 29, "n_frames < 2^29", "zafx_routes.hpp:pcm_direct_ok", "k_mel2", "k_mel2", _LO, _HI),
+    _bound("stft_pcm16_magnitude_2048", "magnitude", 2048, 2048, dict(row_align=0, pcm=True), lambda n: n < 1 << 29, "n_frames < 2^29", "zafx_routes.hpp:pcm_direct_ok",
            "k_mel2", "k_stft_ft16", _LO, _HI),
     _bound("mdct_pcm16_2048", "mdct", 2048, 1024, dict(row_align=32, pcm=True), lambda n: n < 1 << 28, "n_frames < 2^28 (a multiple of 4)",
-           "zafx_mdct.hip:mdct_pcm_direct_ok", "k_mdct_ft32", "k_mdct_ft32", _LO, _HI, on_route=lambda n: n % 4 == 0, route="n a multiple of 4"),
+           "zafx_routes.hpp:mdct_pcm_direct_ok", "k_mdct_ft32", "k_mdct_ft32", _LO, _HI, on_route=lambda n: n % 4 == 0, route="n a multiple of 4"),
     # CQT / chromagram: refused from 2^29 samples on
-    _bound("cqt", "cqt", 0, 1764, dict(), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_cqt.hip:run_cqt", "k_cqt", "refused", _LO, _HI),
-    _bound("chroma", "chroma", 0, 1764, dict(), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_cqt.hip:run_cqt", "k_cqt", "refused", _LO, _HI),
+    _bound("cqt", "cqt", 0, 1764, dict(), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_routes.hpp:cqt_clip_refused", "k_cqt", "refused", _LO, _HI),
+    _bound("chroma", "chroma", 0, 1764, dict(), lambda n: n < 1 << 29, "n_samples < 2^29", "zafx_routes.hpp:cqt_clip_refused", "k_cqt", "refused", _LO, _HI),
     # center: refused from 2^28 sample frames on
-    _bound("center_2048", "center", 2048, 1024, dict(sides=False), lambda n: n < 1 << 28, "n_samples < 2^28 (sample frames)", "zafx_center.hip:launch_center",
+    _bound("center_2048", "center", 2048, 1024, dict(sides=False), lambda n: n < 1 << 28, "n_samples < 2^28 (sample frames)", "zafx_routes.hpp:center_clip_refused",
            "k_center", "refused", _LO, _HI),
-    _bound("center_sides_2048", "center", 2048, 1024, dict(sides=True), lambda n: n < 1 << 28, "n_samples < 2^28 (sample frames)", "zafx_center.hip:launch_center",
+    _bound("center_sides_2048", "center", 2048, 1024, dict(sides=True), lambda n: n < 1 << 28, "n_samples < 2^28 (sample frames)", "zafx_routes.hpp:center_clip_refused",
            "k_center", "refused", _LO, _HI),
 ]
 BOUND_NAMES = [b["name"] for b in BOUNDS]

@@ -1090,7 +1090,7 @@ std::string planned_kernel_name(const zafx_plan& pl) {
                : kind == ZAFX_MDCT ? "k_mdct_bs32" : mel ? mel_wide_kernel_name() : "k_imdct_frames_bs32";
     if (kind == ZAFX_STFT) return stft_kernel_name(pl.log2nf, pl.layout);
     if (kind == ZAFX_ISTFT) return istft_kernel_name(pl.log2nf, pl.layout);
-    if (mel) return pl.prm.n_filters > 256 ? mel_wide_kernel_name() : pl.log2nf == 11 ? "k_mel_ft16b" : pl.log2nf >= 12 ? mel_wide_kernel_name() : mel_kernel_name();
+    if (mel) return kernel_name(mel_planned_route(pl.log2nf, pl.prm.n_filters));
     if (is_center_kind(kind)) return center_kernel_name();
     if (kind == ZAFX_MDCT) return mdct_kernel_name(pl.log2nf, pl.layout);
     if (kind == ZAFX_IMDCT) return imdct_kernel_name();

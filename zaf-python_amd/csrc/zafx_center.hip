@@ -174,7 +174,7 @@ __global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* _
 #undef CLIP_N
 }
 
-static const char* const kCenterName = "k_center";
+static const char* const kCenterName = kCenterKernel;   // (zafx_routes.hpp)
 static const char* const kCenterRaggedName = "k_center_ragged";
 const char* center_kernel_name() { return kCenterName; }
 
@@ -210,7 +210,7 @@ static hipError_t run_center(const zafx_plan& pl, const float2* x, float2* out, 
 }
 
 hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples) {
-    if (n_samples >= (1LL << 28)) {
+    if (center_clip_refused(route_call(pl, x, out, n_clips, n_samples, 0))) {
         set_error("center / sides: clips of 2^28 sample frames and more are not supported");
         return hipErrorInvalidValue;
     }

@@ -644,7 +644,7 @@ static hipError_t run_cqt(const zafx_plan& pl, const float* x, float* out, int64
         set_error("cqt: kernel matrix has too many rows for LDS at this fft_length");
         return hipErrorInvalidValue;
     }
-    if (n_samples >= (1LL << 29)) {   // a clip is addressed through one buffer descriptor with 32-bit byte offsets
+    if (cqt_clip_refused(route_call(pl, x, out, n_clips, n_samples, T))) {   // a clip is addressed through one buffer descriptor with 32-bit byte offsets
         set_error("cqt: clips of 2^29 samples or more are not supported (3.4 h at 44.1 kHz); cut the signal");
         return hipErrorInvalidValue;
     }
@@ -665,7 +665,7 @@ static hipError_t run_cqt(const zafx_plan& pl, const float* x, float* out, int64
     const int pos_hi = (DOUBLE ? pl.cqt_k_hi >> 1 : pl.cqt_k_hi) >> 4;   // (double form: bin k of the spectrum is position k >> 1 of its transform)
     if (ZAFX_CQT_PRUNE && cqt_split(LOG2N) && !pl.cqt_k_special && pl.cqt_k_hi >= pl.cqt_k_lo && (pos_hi >> 6) <= 2)
         prune3 = pos_hi >> 6;
-    pl.ran = "k_cqt";
+    pl.ran = kCqtKernel;
     pl.cqt_form_ran = mm ? 1 : 2;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::P), smem, pl.stream, x, pl.d_tw_pass, pl.d_tw_aux, pl.d_cqt_waves,
                        mm ? pl.d_cqt_mm_addr : pl.d_cqt_addrs, mm ? pl.d_cqt_mm_vals : pl.d_cqt_vals, pl.d_cqt_mm_fin, mm ? pl.cqt_mm_steps : 0, pl.cqt_mm_segs, out, (long long)n_samples, pl.H, left, T, (int)row_pitch(pl, T), (int)n_clips, n_groups,
@@ -679,7 +679,7 @@ int cqt_waves(int log2n) {
     if (cqt_double(log2n)) log2n = 14;   // (the double form runs the 16384-point kernel)
     return fft_threads(log2n, default_log2e(log2n)) / 64;
 }
-const char* cqt_kernel_name() { return "k_cqt"; }
+const char* cqt_kernel_name() { return kCqtKernel; }
 
 // Largest number of rows a float32 plan of this fft_length can hold, capped by the 11-bit row field of the entry words
 int cqt_max_bins(int log2n) {

@@ -13,6 +13,7 @@
 #include "zafx_devbuf.hpp"
 #include "zafx_ragged_table.hpp"
 #include "zafx_units.hpp"
+#include "zafx_routes.hpp"
 #include "zafx_twiddle.hpp"
 
 namespace zafx {
@@ -293,11 +294,23 @@ bool mdct_ragged_native(const zafx_plan& pl);
 hipError_t launch_mdct_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 
 // Every launcher enqueues on plan.stream and returns hipGetLastError().
-// Frames between the starts of consecutive rows of a plan's (F, T) array: T rounded up to prm.row_align elements
-// (reference-layout plans only; 0 / 1 = compact, the reference's own memory order).
-inline int64_t row_pitch(const zafx_plan& pl, int64_t T) {
-    const int64_t a = pl.prm.row_align;
-    return (pl.layout == ZAFX_LAYOUT_FT && a > 1) ? (T + a - 1) / a * a : T;
+// Frames between the starts of consecutive rows of a plan's (F, T) array: the rule of zafx_routes.hpp.
+inline int64_t row_pitch(const zafx_plan& pl, int64_t T) { return row_pitch(pl.layout, pl.prm.row_align, T); }
+
+// What the route conditions (zafx_routes.hpp) read of one call on this plan.  `n`: samples of a clip (the inverses: unused), `T`: frames.
+inline RouteCall route_call(const zafx_plan& pl, const void* in, const void* out, int64_t n_clips, int64_t n, int T, int64_t out_len = 0) {
+    RouteCall c;
+    c.kind = pl.kind, c.precision = pl.prm.precision, c.bluestein = pl.bs_log2m > 0;
+    c.log2nf = pl.log2nf, c.log2e = pl.log2e, c.layout = pl.layout, c.spectrum = pl.prm.spectrum;
+    c.W = pl.W, c.H = pl.H, c.row_align = pl.prm.row_align, c.n_filters = pl.prm.n_filters;
+    c.tw_pass = pl.d_tw_pass.get() != nullptr, c.tw_aux = pl.d_tw_aux.get() != nullptr, c.tw_r32 = pl.d_tw_r32.get() != nullptr, c.tw_sub = pl.d_tw_sub.get() != nullptr;
+    c.tw_quad = pl.d_tw_quad.get() != nullptr, c.tw_band = pl.d_tw_band.get() != nullptr, c.fbw = pl.d_fbw.get() != nullptr;
+    c.window16 = reinterpret_cast<uintptr_t>(pl.d_window.get()) % 16 == 0;
+    c.claim = pl.stft_dynamic && pl.d_claim.get() != nullptr;
+    c.mel2 = pl.fb.whole_ok && pl.fb.n_waves == 16 && (pl.kind != ZAFX_MFCC || pl.dct.dct2_ok);
+    c.n_clips = n_clips, c.n = n, c.T = T, c.out_len = out_len;
+    c.in = reinterpret_cast<uintptr_t>(in), c.out = reinterpret_cast<uintptr_t>(out);
+    return c;
 }
 
 hipError_t launch_stft(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T);
@@ -343,14 +356,14 @@ hipError_t launch_imdct(const zafx_plan& pl, const float* coefs, float* y, int64
 hipError_t launch_mel(zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T);   // (windows above 2048 samples grow the plan's scratch)
 const char* mel_wide_kernel_name();
 // mel / mfcc plans that run as a spectrum kernel + k_melfb (or, W = 4096 with up to 256 filters, the fused two-band kernel) instead of k_mel
-inline bool mel_takes_wide_route(const zafx_plan& pl) { return pl.log2nf >= 11 || pl.bs_log2m > 0 || pl.prm.n_filters > 256; }
-bool mel_band_usable(const zafx_plan& pl, const float* x, int64_t n_clips, int64_t n_samples, int T);   // W = 4096: the fused two-band kernel k_mel_ft16b (zafx_stft.hip)
-hipError_t launch_mel_band(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T);
+inline bool mel_takes_wide_route(const zafx_plan& pl) { return mel_wide(pl.log2nf, pl.bs_log2m > 0, pl.prm.n_filters); }
+// W = 4096: the fused two-band kernel k_mel_ft16b (zafx_stft.hip; MelRoute::Band)
+hipError_t launch_mel_band(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, bool aligned);
 hipError_t launch_cqt(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T);
 bool pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sample_bytes);   // zafx_mel.hip
 bool stft_pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sample_bytes, const void* d_pcm, int T);   // zafx_stft.hip
 bool mdct_pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sample_bytes, const void* d_pcm);   // zafx_mdct.hip
-bool launch_spec2(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, hipError_t& err);   // zafx_mel.hip: |X| / |X|^2 rows of an STFT plan on k_mel2
+hipError_t launch_spec2(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, bool aligned);   // zafx_mel.hip: |X| / |X|^2 rows of an STFT plan on k_mel2 (StftRoute::Spec2)
 hipError_t launch_linear(const zafx_plan& pl, const float* x, float* y, int64_t n_clips);
 hipError_t launch_dct(const zafx_plan& pl, const float* x, float* y, int64_t n_rows);   // zafx_dct.hip: dct / dst I-IV on the FFT core
 bool dct_supported(int log2m);   // log2 of the complex FFT length M

@@ -1550,19 +1550,19 @@ constexpr int mdct_fpb(int log2nf, int layout) {
 
 // int16 PCM (one or two channels) straight into k_mdct_ft32: W = 2048, reference layout, clips of a multiple of four frames (zafx_execute_pcm)
 bool mdct_pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sample_bytes, const void* d_pcm) {
-    return sample_bytes == 2 && (n_channels == 1 || n_channels == 2) && pl.kind == ZAFX_MDCT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 &&
-           pl.log2nf == 9 && pl.layout == ZAFX_LAYOUT_FT && n_frames % 4 == 0 && n_frames < (1LL << 28) && reinterpret_cast<uintptr_t>(d_pcm) % 16 == 0;
+    RouteCall c = route_call(pl, d_pcm, nullptr, 1, n_frames, 0);
+    c.channels = n_channels, c.sample_bytes = sample_bytes;
+    return mdct_pcm_direct_ok(c);
 }
 
-constexpr bool mdct_use_persistent(int log2nf, int layout) {
-    return log2nf >= 7 && log2nf <= 9;   // either layout
-}
+// (mdct_use_persistent -- W = 512 ... 2048 in either layout --: zafx_routes.hpp)
 
+// k_mdct_ft32: r.aligned the 16-byte buffer loads (32-bit byte offsets inside a clip), r.carry the carry instantiation (mdct_route)
 template <int LOG2NF, bool TFOUT>
-static hipError_t run_mdct_p(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
+static hipError_t run_mdct_p(const zafx_plan& pl, const Route<MdctRoute>& r, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
     constexpr int LOG2E = default_log2e(LOG2NF);
     using G = MdctPCfg<LOG2NF, LOG2E>;
-    const bool aligned = n_samples % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && n_samples < (1LL << 28);   // (32-bit byte offsets inside a clip)
+    const bool aligned = r.aligned;
     auto kern = aligned ? k_mdct_ft32<LOG2NF, LOG2E, true, G::NSLOT, TFOUT> : k_mdct_ft32<LOG2NF, LOG2E, false, G::NSLOT, TFOUT>;
     const int pcm = take_pcm_mode();   // (zafx_execute_pcm: int16 in the loads; mdct_pcm_direct_ok vouches for `aligned`, W = 2048 and the reference layout)
     if constexpr (LOG2NF == 9 && !TFOUT) {
@@ -1575,16 +1575,10 @@ static hipError_t run_mdct_p(const zafx_plan& pl, const float* x, float* out, in
     if (total <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / G::SMEM);
     const long long max_grid = (long long)pl.n_cus * std::max(per_cu, 1);
-#ifndef ZAFX_MDCT_CARRY
-#define ZAFX_MDCT_CARRY 1
-#endif
     if constexpr (!TFOUT && ZAFX_MDCT_CARRY) {
-        // Rows that are not even whole 64-byte half lines (T % 16 != 0; odd T with 4-byte stores): the carry form -- 1024 clips: T = 434 / 436 / 440 run
-        // 0.84 ms (4.3 TB/s) with it against 1.37 / 1.29 / 1.09 ms without.  At T % 16 == 0 (the benchmark's 432: odd rows start 64 bytes
-        // into a line and leave as two streamed half lines) the plain form is faster, 0.771 against 0.826 ms: the carry takes the
-        // registers of the resident window quadruples, worth 10 % on this LDS-bound kernel.
+        // rows that are not even whole 64-byte half lines: the carry form (ZAFX_MDCT_CARRY, zafx_routes.hpp)
         const int TP = (int)row_pitch(pl, T);
-        if (aligned && (TP % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 64 != 0) && total < (1LL << 31)) {
+        if (r.carry) {
             auto kc = k_mdct_ft32<LOG2NF, LOG2E, true, G::NSLOT, false, true>;
             if constexpr (LOG2NF == 9) {
                 if (pcm == 1) kc = k_mdct_ft32<LOG2NF, LOG2E, true, G::NSLOT, false, true, 1>;
@@ -1594,14 +1588,14 @@ static hipError_t run_mdct_p(const zafx_plan& pl, const float* x, float* out, in
             const int segs = carry_segments(n_clips, tiles, max_grid);
             const int seg_tiles = (tiles + segs - 1) / segs;
             const long long units = (long long)n_clips * segs;
-            pl.ran = "k_mdct_ft32";
+            pl.ran = kernel_name(MdctRoute::Persistent);
             hipLaunchKernelGGL(kc, dim3((unsigned)std::min<long long>(units, max_grid)), dim3(G::NSLOT * 64), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_pass,
                                pl.d_tw_aux, out, (long long)n_samples, T, TP, tiles, (int)total, segs, seg_tiles, (int)units);
             return hipGetLastError();
         }
     }
     const long long grid = std::min<long long>(total, max_grid);
-    pl.ran = "k_mdct_ft32";
+    pl.ran = kernel_name(MdctRoute::Persistent);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NSLOT * 64), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_pass, pl.d_tw_aux, out,
                        (long long)n_samples, T, (int)row_pitch(pl, T), tiles, (int)total, 1, 0, 0);
     return hipGetLastError();
@@ -1649,9 +1643,6 @@ hipError_t launch_mdct_ragged(const zafx_plan& pl, const float* x, float* out, c
     return hipErrorInvalidValue;
 }
 
-#ifndef ZAFX_MDCT_BAND
-#define ZAFX_MDCT_BAND 1
-#endif
 static hipError_t run_mdct_band(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
     using G = MdctBandCfg;
     auto kern = k_mdct_ft32b;
@@ -1660,34 +1651,27 @@ static hipError_t run_mdct_band(const zafx_plan& pl, const float* x, float* out,
     const long long total = (long long)tiles * n_clips;
     if (total <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total, (long long)pl.n_cus);
-    pl.ran = "k_mdct_ft32b";
+    pl.ran = kernel_name(MdctRoute::Band);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_sub, pl.d_tw_band, out, (long long)n_samples, T,
                        (int)row_pitch(pl, T), tiles, (int)total);
     return hipGetLastError();
 }
 
 // k_mdct_ft32q: W = 8192 in the reference layout, four bands of bins per 32-frame tile (see the kernel)
-#ifndef ZAFX_MDCT_QUAD
-#define ZAFX_MDCT_QUAD 1
-#endif
-static hipError_t run_mdct_quad(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
-    using G = MdctQuadCfg;
-    const bool aligned = n_samples % 2 == 0 && reinterpret_cast<uintptr_t>(x) % 8 == 0;   // sample pairs as 8-byte loads
+static hipError_t run_mdct_quad(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, bool aligned) {
+    using G = MdctQuadCfg;   // (aligned -- mdct_route's sample_pairs --: sample pairs as 8-byte loads)
     auto kern = aligned ? k_mdct_ft32q<true> : k_mdct_ft32q<false>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM); e != hipSuccess) return e;
     const int tiles = (T + G::FPB - 1) / G::FPB;
     const long long total = (long long)tiles * n_clips;
     if (total <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total, (long long)pl.n_cus);
-    pl.ran = "k_mdct_ft32q";
+    pl.ran = kernel_name(MdctRoute::Quad);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), G::SMEM, pl.stream, x, pl.d_window, pl.d_tw_sub, pl.d_tw_aux, pl.d_tw_quad, out, (long long)n_samples, T,
                        (int)row_pitch(pl, T), tiles, (int)total);
     return hipGetLastError();
 }
 
-#ifndef ZAFX_MDCT_BAND_CARRY
-#define ZAFX_MDCT_BAND_CARRY 1
-#endif
 static hipError_t run_mdct_band_carry(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
     using G = MdctBandCfg;
     auto kern = k_mdct_ft32bc;
@@ -1698,7 +1682,7 @@ static hipError_t run_mdct_band_carry(const zafx_plan& pl, const float* x, float
     const int segs = carry_segments(2 * n_clips, tiles, max_grid);   // (two units -- one per band -- for every segment)
     const int seg_tiles = (tiles + segs - 1) / segs;
     const long long units = 2LL * n_clips * segs;
-    pl.ran = "k_mdct_ft32bc";
+    pl.ran = kernel_name(MdctRoute::BandCarry);
     hipLaunchKernelGGL(kern, dim3((unsigned)std::min<long long>(units, max_grid)), dim3(G::NT), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_sub, pl.d_tw_band, out,
                        (long long)n_samples, T, (int)row_pitch(pl, T), tiles, segs, seg_tiles, (int)units);
     return hipGetLastError();
@@ -1706,42 +1690,38 @@ static hipError_t run_mdct_band_carry(const zafx_plan& pl, const float* x, float
 
 template <int LOG2NF, int LAYOUT>
 static hipError_t run_mdct(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
-    if constexpr (ZAFX_MDCT_BAND && ZAFX_MDCT_BAND_CARRY && LOG2NF == 10 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // rows that are not whole 64-byte half lines: the carry form (one band per workgroup)
-        const int64_t TP = row_pitch(pl, T);
-        if (pl.d_tw_sub && pl.d_tw_band && n_samples % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && n_samples < (1LL << 28) &&
-            (TP % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 64 != 0) && reinterpret_cast<uintptr_t>(out) % 4 == 0 &&
-            2LL * n_clips * ((T + 31) / 32) < (1LL << 30) && (long long)n_clips * 2048 * TP < (1LL << 40))
-            return run_mdct_band_carry(pl, x, out, n_clips, n_samples, T);
+    const Route<MdctRoute> r = mdct_route(route_call(pl, x, out, n_clips, n_samples, T));
+    switch (r.k) {
+        case MdctRoute::BandCarry:   // W = 4096, rows that are not whole 64-byte half lines: one band per workgroup
+            if constexpr (ZAFX_MDCT_BAND && ZAFX_MDCT_BAND_CARRY && LOG2NF == 10 && LAYOUT == ZAFX_LAYOUT_FT) return run_mdct_band_carry(pl, x, out, n_clips, n_samples, T);
+            break;
+        case MdctRoute::Band:   // W = 4096, reference layout: 32-frame tiles in two bands of bins
+            if constexpr (ZAFX_MDCT_BAND && LOG2NF == 10 && LAYOUT == ZAFX_LAYOUT_FT) return run_mdct_band(pl, x, out, n_clips, n_samples, T);
+            break;
+        case MdctRoute::Quad:   // W = 8192, reference layout: 32-frame tiles in four bands of bins
+            if constexpr (ZAFX_MDCT_QUAD && LOG2NF == 11 && LAYOUT == ZAFX_LAYOUT_FT) return run_mdct_quad(pl, x, out, n_clips, n_samples, T, r.aligned);
+            break;
+        case MdctRoute::Persistent:
+            if constexpr (mdct_use_persistent(LOG2NF, LAYOUT)) return run_mdct_p<LOG2NF, LAYOUT == ZAFX_LAYOUT_TF>(pl, r, x, out, n_clips, n_samples, T);
+            break;
+        case MdctRoute::Generic:
+            if constexpr (!mdct_use_persistent(LOG2NF, LAYOUT)) {
+                constexpr int LOG2E = default_log2e(LOG2NF);
+                constexpr int FPB = mdct_fpb(LOG2NF, LAYOUT);
+                using G = MdctCfg<LOG2NF, LOG2E, FPB>;
+                auto kern = k_mdct<LOG2NF, LOG2E, FPB, LAYOUT>;
+                if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM_FWD); e != hipSuccess) return e;
+                const int tiles = (T + FPB - 1) / FPB;
+                const long long blocks = (long long)tiles * n_clips;
+                if (blocks <= 0) return hipSuccess;
+                pl.ran = kernel_name(MdctRoute::Generic);
+                hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(G::NT), G::SMEM_FWD, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, out,
+                                   (long long)n_samples, T, (int)row_pitch(pl, T), tiles);
+                return hipGetLastError();
+            }
+            break;
     }
-    if constexpr (ZAFX_MDCT_BAND && LOG2NF == 10 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 4096, reference layout: 32-frame tiles in two bands of bins (16-byte buffer loads: clips of a multiple of four samples)
-        if (pl.d_tw_sub && pl.d_tw_band && n_samples % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && n_samples < (1LL << 28) &&
-            (long long)n_clips * ((T + 31) / 32) < (1LL << 31))
-            return run_mdct_band(pl, x, out, n_clips, n_samples, T);
-    }
-    if constexpr (ZAFX_MDCT_QUAD && LOG2NF == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 8192, reference layout: 32-frame tiles in four bands of bins (4-byte buffer loads: 32-bit byte offsets inside a clip)
-        if (pl.d_tw_sub && pl.d_tw_quad && n_samples < (1LL << 28) && (long long)(T + 33) * 4096 < (1LL << 28) && reinterpret_cast<uintptr_t>(x) % 4 == 0 &&
-            reinterpret_cast<uintptr_t>(out) % 4 == 0 && (long long)n_clips * ((T + 31) / 32) < (1LL << 31))
-            return run_mdct_quad(pl, x, out, n_clips, n_samples, T);
-    }
-    if constexpr (mdct_use_persistent(LOG2NF, LAYOUT)) {
-        return run_mdct_p<LOG2NF, LAYOUT == ZAFX_LAYOUT_TF>(pl, x, out, n_clips, n_samples, T);
-    } else {
-        constexpr int LOG2E = default_log2e(LOG2NF);
-        constexpr int FPB = mdct_fpb(LOG2NF, LAYOUT);
-        using G = MdctCfg<LOG2NF, LOG2E, FPB>;
-        auto kern = k_mdct<LOG2NF, LOG2E, FPB, LAYOUT>;
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM_FWD); e != hipSuccess) return e;
-        const int tiles = (T + FPB - 1) / FPB;
-        const long long blocks = (long long)tiles * n_clips;
-        if (blocks <= 0) return hipSuccess;
-        pl.ran = "k_mdct";
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(G::NT), G::SMEM_FWD, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, out,
-                           (long long)n_samples, T, (int)row_pitch(pl, T), tiles);
-        return hipGetLastError();
-    }
+    return hipErrorInvalidValue;
 }
 
 // IMDCT tile geometry: FPB frames resident, NSLOT of them transformed at a time.
@@ -1783,9 +1763,7 @@ constexpr int imdct_nslot(int log2nf, int fpb) {
 // u[2k + 2048] = Re z_(k+1024), u[4095 - 2k] = -Im z_k, u[2047 - 2k] = -Im z_(k+1024).  The unfold + window + TDAC overlap-add
 // (zaf.py:1166-1182: older frame first) then runs on u in LDS, eight frames at a time (16 frames x 16 KB do not fit): a wave stores the
 // samples between its frame and the one before (the tile's first frame: the carry of the tile before) as 16-byte pieces.
-#ifndef ZAFX_IMDCT_QUAD
-#define ZAFX_IMDCT_QUAD 1
-#endif
+// (ZAFX_IMDCT_QUAD, the switch of this route: zafx_routes.hpp)
 #ifndef ZAFX_IMDCT_QUAD_DEPTH
 #define ZAFX_IMDCT_QUAD_DEPTH 1   // sweeps of a class's gather in flight per thread (two 16-byte loads each; measured 1 / 2 / 4: 1.46 / 1.51 / 1.67 ms;
                                   // sweeps requested ahead -- the next tile's first class through the exchange, the second class through the first
@@ -1973,7 +1951,7 @@ static hipError_t run_imdct_quad(const zafx_plan& pl, const float* coefs, float*
     const int segs = carry_segments(n_clips, tiles, pl.n_cus);
     const int seg_tiles = (tiles + segs - 1) / segs;
     const long long units = n_clips * segs;
-    pl.ran = "k_imdct_q";
+    pl.ran = kernel_name(ImdctRoute::Quad);
     hipLaunchKernelGGL(kern, dim3((unsigned)std::min<long long>(units, pl.n_cus)), dim3(Q::NT), Q::SMEM, pl.stream, coefs, pl.d_window, pl.d_tw_sub, pl.d_tw_aux,
                        pl.d_tw_quad, y, T, (int)row_pitch(pl, T), (long long)out_len, tiles, segs, seg_tiles, (int)units);
     return hipGetLastError();
@@ -1982,11 +1960,8 @@ static hipError_t run_imdct_quad(const zafx_plan& pl, const float* coefs, float*
 template <int LOG2NF, int LAYOUT>
 static hipError_t run_imdct(const zafx_plan& pl, const float* coefs, float* y, int64_t n_clips, int T, int64_t out_len) {
     if constexpr (ZAFX_IMDCT_QUAD && LOG2NF == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 8192: the two-class kernel (four frames per 16-byte piece: a row pitch that is a multiple of 4; 32-bit byte offsets inside a clip)
-        const int64_t TP = row_pitch(pl, T);
-        if (pl.d_tw_sub && pl.d_tw_quad && TP % 4 == 0 && reinterpret_cast<uintptr_t>(coefs) % 16 == 0 && reinterpret_cast<uintptr_t>(pl.d_window.get()) % 16 == 0 &&
-            (long long)4096 * TP * 4 < (1LL << 31) && n_clips * (((long long)T + 15) / 16 + 1) < (1LL << 30))
-            return run_imdct_quad(pl, coefs, y, n_clips, T, out_len);
+        // W = 8192: the two-class kernel
+        if (imdct_route(route_call(pl, coefs, y, n_clips, T, T, out_len)).k == ImdctRoute::Quad) return run_imdct_quad(pl, coefs, y, n_clips, T, out_len);
     }
     constexpr int LOG2E = default_log2e(LOG2NF);
     constexpr int FPB = imdct_fpb(LOG2NF, LAYOUT);
@@ -2005,7 +1980,7 @@ static hipError_t run_imdct(const zafx_plan& pl, const float* coefs, float* y, i
     const int seg_tiles = (tiles + segs - 1) / segs;
     const long long units = (long long)n_clips * segs;
     const long long grid = std::min<long long>(units, max_grid);
-    pl.ran = "k_imdct";
+    pl.ran = kernel_name(ImdctRoute::Generic);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NSLOT * C::P), SMEM, pl.stream, coefs, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, y, T,
                        (int)row_pitch(pl, T), (long long)out_len, tiles, segs, seg_tiles, (int)units);
     return hipGetLastError();
@@ -2075,12 +2050,8 @@ hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y
 
 bool mdct_supported(int log2nf) { return log2nf >= 4 && log2nf <= 11; }
 int mdct_frames_per_block(int log2nf, int layout) { return mdct_fpb(log2nf, layout); }
-const char* mdct_kernel_name(int log2nf, int layout) {
-    if (ZAFX_MDCT_BAND && log2nf == 10 && layout == ZAFX_LAYOUT_FT) return "k_mdct_ft32b";
-    if (ZAFX_MDCT_QUAD && log2nf == 11 && layout == ZAFX_LAYOUT_FT) return "k_mdct_ft32q";
-    return mdct_use_persistent(log2nf, layout) ? "k_mdct_ft32" : "k_mdct";
-}
-const char* imdct_kernel_name() { return "k_imdct"; }
+const char* mdct_kernel_name(int log2nf, int layout) { return kernel_name(mdct_planned_route(log2nf, layout)); }
+const char* imdct_kernel_name() { return kernel_name(imdct_planned_route()); }
 
 hipError_t launch_mdct(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
     switch (pl.log2nf) {

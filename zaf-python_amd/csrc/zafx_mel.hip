@@ -28,12 +28,7 @@ namespace zafx {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 ZAFX_PROF_ARRAY(g_prof_mel)
 
-#ifndef ZAFX_MEL_THREADS
-#define ZAFX_MEL_THREADS 1024
-#endif
-#ifndef ZAFX_MEL_FPB
-#define ZAFX_MEL_FPB 16
-#endif
+// (ZAFX_MEL_THREADS, ZAFX_MEL_FPB: zafx_routes.hpp -- k_mel2's routes ask for 1024 threads and 16-frame tiles)
 constexpr int kMelThreads = ZAFX_MEL_THREADS;
 // frames per tile.  8 (with ZAFX_MEL_THREADS = 512): two workgroups per CU, each with 8 wavefronts and 8-frame tiles -- their
 // phases (transforms | filterbank GEMM | reduction) drift apart, so one workgroup's butterflies fill the vector pipe while the
@@ -571,9 +566,7 @@ __global__ __launch_bounds__(mel_threads(LOG2N, LOG2E), kMelFpb == 8 ? 2 * mel_t
 // the block's tile -- no partial-tile slots, no reduction phase (a cut block's helper hands one partial tile over through 1 KB of LDS).
 // Per tile: [product of tile i (waves that own items) ; transform of the frame of tile i + 1] | barrier | S <- magnitudes, request of tile
 // i + 2 | barrier | stores of tile i.  Two barriers instead of four, matrix and vector pipes busy in the same phase.
-#ifndef ZAFX_MEL2
-#define ZAFX_MEL2 1
-#endif
+// (ZAFX_MEL2, the switch of this kernel's routes: zafx_routes.hpp)
 constexpr int kMel2DualPitch = 1057;   // float2 slots per frame buffer of the one-pass mel + mfcc form (MODE 4)
 // MFCC: the levels are |X|^2 (zaf.py:437-439); between the two barriers the owners take log(mel + eps) of their tiles, turn them into B
 // fragments (a 4 x 4 transpose of register index against 16-lane row: two v_permlane swaps) and multiply them with their block's
@@ -1124,7 +1117,7 @@ static hipError_t run_mel(const zafx_plan& pl, const float* x, float* out, int64
             const long long total2 = (long long)tiles2 * n_clips;
             if (total2 <= 0) return hipSuccess;
             const long long grid2 = std::min<long long>(total2, (long long)pl.n_cus);
-            pl.ran = "k_mel2";
+            pl.ran = kernel_name(MelRoute::Mel2);
             hipLaunchKernelGGL(k2, dim3((unsigned)grid2), dim3(1024), smem, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, pl.fb.d_pack, pl.fb.d_whole, pl.dct.d_dct2,
                                pl.dct.d_owner2, out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles2, (int)total2, pl.prm.n_filters, mfcc ? pl.prm.n_coefs : 0, pl.layout);
             return hipGetLastError();
@@ -1159,7 +1152,7 @@ static hipError_t run_mel(const zafx_plan& pl, const float* x, float* out, int64
     if (total <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / G::SMEM);
     const long long grid = std::min<long long>(total, (long long)pl.n_cus * std::max(per_cu, 1));
-    pl.ran = "k_mel";
+    pl.ran = kernel_name(MelRoute::Mel);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), G::SMEM, pl.stream, x, pl.d_window, LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass, pl.d_tw_aux, pl.fb.d_pack,
                        pl.fb.d_items, pl.fb.d_wave_ptr, pl.fb.d_blk_ptr, pl.fb.d_desc, pl.fb.n_blocks, pl.fb.n_items, pl.fb.total_steps, mfcc ? pl.dct.total_steps : 0, pl.dct.d_pack, pl.dct.d_items,
                        pl.dct.d_wave_ptr, pl.dct.d_blk_ptr, pl.dct.d_desc, pl.dct.d_direct, direct_j, pl.dct.n_blocks, out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, (int)total,
@@ -1167,45 +1160,33 @@ static hipError_t run_mel(const zafx_plan& pl, const float* x, float* out, int64
     return hipGetLastError();
 }
 
-// ZAFX_SPECTRUM_MAGNITUDE / _POWER of an STFT plan at W = 2048 in the reference layout on k_mel2 (MODE 2 / 3); false: not this geometry
-#ifndef ZAFX_SPEC2
-#define ZAFX_SPEC2 1
-#endif
-bool launch_spec2(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, hipError_t& err) {
+// ZAFX_SPECTRUM_MAGNITUDE / _POWER of an STFT plan at W = 2048 in the reference layout on k_mel2 (MODE 2 / 3): StftRoute::Spec2 (spec2_usable
+// of zafx_routes.hpp vouches for the geometry and for fewer than 2^31 tiles)
+hipError_t launch_spec2(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, bool aligned) {
     using C = FftCfg<10, 4>;
-    if (!ZAFX_SPEC2 || pl.log2nf != 10 || pl.log2e != 4 || pl.layout != ZAFX_LAYOUT_FT || kMelFpb != 16 || kMelThreads != 1024 || !pl.d_tw_pass || !pl.d_tw_aux) return false;
-    if (pl.prm.spectrum != ZAFX_SPECTRUM_MAGNITUDE && pl.prm.spectrum != ZAFX_SPECTRUM_POWER) return false;
-    if (n_samples >= (1LL << 29)) return false;
     const int pcm = take_pcm_mode();
-    const bool aligned = (n_samples % 2 == 0) && (pl.H % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0);
     const bool power = pl.prm.spectrum == ZAFX_SPECTRUM_POWER;
     auto k2 = aligned ? (power ? k_mel2<true, 3> : k_mel2<true, 2>) : (power ? k_mel2<false, 3> : k_mel2<false, 2>);
     if (pcm == 1) k2 = aligned ? (power ? k_mel2<true, 3, 1> : k_mel2<true, 2, 1>) : (power ? k_mel2<false, 3, 1> : k_mel2<false, 2, 1>);
     if (pcm == 2) k2 = aligned ? (power ? k_mel2<true, 3, 2> : k_mel2<true, 2, 2>) : (power ? k_mel2<false, 3, 2> : k_mel2<false, 2, 2>);
     const size_t smem = (size_t)(16 * C::PITCH + C::TW + C::N + C::N / 2 + 1) * 8 + kMel2Slots * 1024;
-    err = ensure_dynamic_lds(reinterpret_cast<const void*>(k2), pl.device, smem);
-    if (err != hipSuccess) return true;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k2), pl.device, smem); e != hipSuccess) return e;
     const int tiles = (T + 15) / 16;
     const long long total = (long long)tiles * n_clips;
-    if (total <= 0 || total >= (1LL << 31)) return total <= 0;
+    if (total <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total, (long long)pl.n_cus);
-    pl.ran = "k_mel2";
+    pl.ran = kernel_name(StftRoute::Spec2);
     hipLaunchKernelGGL(k2, dim3((unsigned)grid), dim3(1024), smem, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, (const float*)nullptr, (const int4*)nullptr,
                        (const float*)nullptr, (const int*)nullptr, out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, (int)total, 0, 0, pl.layout);
-    err = hipGetLastError();
-    return true;
+    return hipGetLastError();
 }
 
 // Does a call with int16 PCM (n_channels = 1 or 2) of this plan run on k_mel2, which takes the integers in its loads?  (Everything else converts
 // into a float32 staging array first: zafx_execute_pcm.)
 bool pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sample_bytes) {
-    if (sample_bytes != 2 || (n_channels != 1 && n_channels != 2) || pl.prm.precision != ZAFX_PRECISION_F32 || pl.bs_log2m > 0) return false;
-    if (pl.log2nf != 10 || pl.log2e != 4 || kMelFpb != 16 || kMelThreads != 1024 || n_frames >= (1LL << 29)) return false;
-    if (pl.kind == ZAFX_MEL || pl.kind == ZAFX_MFCC)
-        return ZAFX_MEL2 && !mel_takes_wide_route(pl) && pl.fb.whole_ok && pl.fb.n_waves == 16 && (pl.kind == ZAFX_MEL || pl.dct.dct2_ok);
-    if (pl.kind == ZAFX_STFT)
-        return ZAFX_SPEC2 && pl.layout == ZAFX_LAYOUT_FT && (pl.prm.spectrum == ZAFX_SPECTRUM_MAGNITUDE || pl.prm.spectrum == ZAFX_SPECTRUM_POWER);
-    return false;
+    RouteCall c = route_call(pl, nullptr, nullptr, 1, n_frames, 0);
+    c.channels = n_channels, c.sample_bytes = sample_bytes;
+    return pcm_direct_ok(c);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1260,13 +1241,12 @@ hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, co
     return hipGetLastError();
 }
 
-const char* mel_kernel_name() { return "k_mel"; }
+const char* mel_kernel_name() { return kernel_name(MelRoute::Mel); }
 int mel_waves(int log2n) { return mel_threads(log2n, mel_log2e(log2n)) / 64; }
 
 template <int LOG2N>
-static hipError_t run_mel_any(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
-    // (the aligned form addresses a clip through one buffer descriptor with 32-bit byte offsets: clips below 2^29 samples)
-    const bool aligned = (n_samples % 2 == 0) && (pl.H % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0) && n_samples < (1LL << 29);
+static hipError_t run_mel_any(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, bool aligned) {
+    // (aligned -- mel_route's mel_aligned --: the form that addresses a clip through one buffer descriptor with 32-bit byte offsets)
     return aligned ? run_mel<LOG2N, true>(pl, x, out, n_clips, n_samples, T) : run_mel<LOG2N, false>(pl, x, out, n_clips, n_samples, T);
 }
 
@@ -1343,12 +1323,8 @@ static size_t melw_chunk_bytes() {
     return bytes;
 }
 
-#ifndef ZAFX_MEL_BAND
-#define ZAFX_MEL_BAND 1
-#endif
+// (MelRoute::Wide; W = 4096 within 32-bit byte offsets runs fused on k_mel_ft16b instead: MelRoute::Band, launch_mel)
 static hipError_t run_mel_wide(zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
-    if ((long long)n_clips * T <= 0) return hipSuccess;
-    if (ZAFX_MEL_BAND && mel_band_usable(pl, x, n_clips, n_samples, T)) return launch_mel_band(pl, x, out, n_clips, n_samples, T);   // W = 4096: fused (k_mel_ft16b)
     const int mfcc = pl.kind == ZAFX_MFCC;
     const int rows = pl.W / 2 + 1;
     const int SP = (T + 31) / 32 * 32;   // spectrum rows as whole 128-byte lines
@@ -1385,7 +1361,7 @@ static hipError_t run_mel_wide(zafx_plan& pl, const float* x, float* out, int64_
                                            : launch_stft(st, x + c0 * n_samples, reinterpret_cast<float2*>(spec), n, n_samples, T);
             e != hipSuccess)
             return e;
-        pl.ran = "k_melfb";
+        pl.ran = kernel_name(MelRoute::Wide);
         hipLaunchKernelGGL(k_melfb, dim3((unsigned)((T + 63) / 64), (unsigned)n), dim3(1024), smem, pl.stream, spec, pl.d_fbw, pl.d_fbw_meta, pl.d_dctw,
                            out + c0 * out_per_clip, pl.prm.n_filters, mfcc ? pl.prm.n_coefs : 0, rows, SP, T, (int)row_pitch(pl, T), pl.layout);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -1393,17 +1369,25 @@ static hipError_t run_mel_wide(zafx_plan& pl, const float* x, float* out, int64_
     return hipSuccess;
 }
 
-const char* mel_wide_kernel_name() { return "k_melfb"; }
+const char* mel_wide_kernel_name() { return kernel_name(MelRoute::Wide); }
 
 hipError_t launch_mel(zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
-    if (mel_takes_wide_route(pl)) return run_mel_wide(pl, x, out, n_clips, n_samples, T);
+    const Route<MelRoute> r = mel_route(route_call(pl, x, out, n_clips, n_samples, T));
+    switch (r.k) {
+        case MelRoute::Band:
+        case MelRoute::Wide:
+            if ((long long)n_clips * T <= 0) return hipSuccess;
+            return r.k == MelRoute::Band ? launch_mel_band(pl, x, out, n_clips, n_samples, T, r.aligned) : run_mel_wide(pl, x, out, n_clips, n_samples, T);
+        case MelRoute::Mel2:
+        case MelRoute::Mel: break;   // (run_mel picks between the two)
+    }
     switch (pl.log2nf) {
-        case 5: return run_mel_any<5>(pl, x, out, n_clips, n_samples, T);
-        case 6: return run_mel_any<6>(pl, x, out, n_clips, n_samples, T);
-        case 7: return run_mel_any<7>(pl, x, out, n_clips, n_samples, T);
-        case 8: return run_mel_any<8>(pl, x, out, n_clips, n_samples, T);
-        case 9: return run_mel_any<9>(pl, x, out, n_clips, n_samples, T);
-        case 10: return run_mel_any<10>(pl, x, out, n_clips, n_samples, T);
+        case 5: return run_mel_any<5>(pl, x, out, n_clips, n_samples, T, r.aligned);
+        case 6: return run_mel_any<6>(pl, x, out, n_clips, n_samples, T, r.aligned);
+        case 7: return run_mel_any<7>(pl, x, out, n_clips, n_samples, T, r.aligned);
+        case 8: return run_mel_any<8>(pl, x, out, n_clips, n_samples, T, r.aligned);
+        case 9: return run_mel_any<9>(pl, x, out, n_clips, n_samples, T, r.aligned);
+        case 10: return run_mel_any<10>(pl, x, out, n_clips, n_samples, T, r.aligned);
     }
     set_error("mel/mfcc: unsupported window_length");
     return hipErrorInvalidValue;

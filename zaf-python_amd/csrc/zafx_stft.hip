@@ -2518,12 +2518,9 @@ constexpr int stft_fpb(int log2n, int layout) {
     return r;
 }
 
-constexpr bool stft_use_fat(int log2n, int layout) {
-    return layout == ZAFX_LAYOUT_FT && log2n >= 7 && log2n <= 10;   // one wavefront per frame
-}
-
+// (stft_use_fat, stft_use_tf -- the kernel family by window and layout --: zafx_routes.hpp)
 template <int LOG2N, bool ALIGNED, int SPEC>
-static hipError_t run_stft_fat(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
+static hipError_t run_stft_fat(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T, bool claimed) {
 #ifndef ZAFX_STFT_R32
 #define ZAFX_STFT_R32 1
 #endif
@@ -2548,11 +2545,10 @@ static hipError_t run_stft_fat(const zafx_plan& pl, const float* x, float2* out,
     if (total <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
     const long long grid = std::min<long long>(total, (long long)pl.n_cus * std::max(per_cu, 1));
-    pl.ran = "k_stft_ft16";
+    pl.ran = kernel_name(StftRoute::Fat);
     if constexpr (SPEC < 2 && FPB == kFatFrames) {
         // every store of a tile a whole line (what the kernel calls lines_whole), float32 samples: the tiles are claimed at run time (DYN)
-        if (pl.stft_dynamic && pl.d_claim && kern == k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, FPB> && row_pitch(pl, T) % 16 == 0 &&
-            reinterpret_cast<uintptr_t>(out) % 128 == 0) {
+        if (claimed && kern == k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, FPB>) {
             static_assert(F::SMEM + kClaimLdsBytes <= (size_t)kMaxLdsBytes, "tile + tables + claim words exceed LDS");
             auto dyn = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, FPB, 0, false, true>;
             if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(dyn), pl.device, F::SMEM + kClaimLdsBytes); e != hipSuccess) return e;
@@ -2587,7 +2583,7 @@ static hipError_t run_stft_fat_carry(const zafx_plan& pl, const float* x, float2
         const int seg_tiles = (tiles + segs - 1) / segs;
         const long long units = (long long)n_clips * segs;
         const long long grid = std::min<long long>(units, max_grid);
-        pl.ran = "k_stft_ft16c";
+        pl.ran = kernel_name(StftRoute::FatCarry);
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F::NT), F::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, out,
                            (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, segs, seg_tiles, (int)units);
         return hipGetLastError();
@@ -2606,7 +2602,7 @@ static hipError_t run_stft_band(const zafx_plan& pl, const float* x, float2* out
     const long long total = (long long)tiles * n_clips;
     if (total <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total, (long long)pl.n_cus);
-    pl.ran = "k_stft_ft16b";
+    pl.ran = kernel_name(StftRoute::Band);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(B::NT), B::SMEM, pl.stream, x, pl.d_window, pl.d_tw_sub, pl.d_tw_aux, out,
                        (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, (int)total);
     return hipGetLastError();
@@ -2622,7 +2618,7 @@ static hipError_t run_stft_quad(const zafx_plan& pl, const float* x, float2* out
     const long long total = (long long)tiles * n_clips;
     if (total <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total, (long long)pl.n_cus);
-    pl.ran = "k_stft_ft16q";
+    pl.ran = kernel_name(StftRoute::Quad);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(B::NT), B::SMEM, pl.stream, x, pl.d_window, pl.d_tw_sub, pl.d_tw_quad, out,
                        (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, (int)total);
     return hipGetLastError();
@@ -2642,7 +2638,7 @@ static hipError_t run_stft_band_carry(const zafx_plan& pl, const float* x, float
         const int seg_tiles = (tiles + segs - 1) / segs;
         const long long units = 2LL * n_clips * segs;
         const long long grid = std::min<long long>(units, max_grid);
-        pl.ran = "k_stft_ft16bc";
+        pl.ran = kernel_name(StftRoute::BandCarry);
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(B::NT), B::SMEM, pl.stream, x, pl.d_window, pl.d_tw_sub, pl.d_tw_aux, out,
                            (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, segs, seg_tiles, (int)units);
         return hipGetLastError();
@@ -2651,30 +2647,20 @@ static hipError_t run_stft_band_carry(const zafx_plan& pl, const float* x, float
     }
 }
 
-// k_mel_ft16b: mel / mfcc at W = 4096, fused on the two-band kernel.  false: the caller takes the spectrum-kernel + k_melfb route (clips too
-// long for 32-bit byte offsets, unaligned base)
-bool mel_band_usable(const zafx_plan& pl, const float* x, int64_t n_clips, int64_t n_samples, int T) {
-    return pl.log2nf == 11 && pl.d_tw_sub && pl.d_fbw && pl.prm.n_filters <= 256 && n_samples < (1LL << 29) && (long long)(T + 16) * pl.H < (1LL << 29) &&
-           (long long)n_clips * ((T + 15) / 16) < (1LL << 31) && reinterpret_cast<uintptr_t>(x) % 4 == 0;
-}
-hipError_t launch_mel_band(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T) {
+// k_mel_ft16b: mel / mfcc at W = 4096, fused on the two-band kernel (MelRoute::Band; mel_band_usable of zafx_routes.hpp)
+hipError_t launch_mel_band(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples, int T, bool aligned) {
     using B = BandCfg;
     const bool mfcc = pl.kind == ZAFX_MFCC;
-    const bool aligned = (n_samples % 2 == 0) && (pl.H % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0);
     auto kern = mfcc ? (aligned ? k_mel_ft16b<true, true> : k_mel_ft16b<false, true>) : (aligned ? k_mel_ft16b<true, false> : k_mel_ft16b<false, false>);
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, B::SMEM); e != hipSuccess) return e;
     const int tiles = (T + B::FPB - 1) / B::FPB;
     const long long total = (long long)tiles * n_clips;
     if (total <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total, (long long)pl.n_cus);
-    pl.ran = "k_mel_ft16b";
+    pl.ran = kernel_name(MelRoute::Band);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(B::NT), B::SMEM, pl.stream, x, pl.d_window, pl.d_tw_sub, pl.d_tw_aux, pl.d_fbw, pl.d_fbw_meta, pl.d_dctw, out,
                        (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles, (int)total, pl.prm.n_filters, mfcc ? pl.prm.n_coefs : 0, pl.layout);
     return hipGetLastError();
-}
-
-constexpr bool stft_use_tf(int log2n, int layout) {
-    return layout == ZAFX_LAYOUT_TF && log2n >= 7 && log2n <= 10;   // one wavefront (or half of one) per frame
 }
 
 template <int LOG2N, bool ALIGNED, int SPEC>
@@ -2690,82 +2676,61 @@ static hipError_t run_stft_tf(const zafx_plan& pl, const float* x, float2* out, 
     if (total <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / SMEM);
     const long long grid = std::min<long long>((total + SLOTS - 1) / SLOTS, (long long)pl.n_cus * std::max(per_cu, 1));
-    pl.ran = "k_stft_tf";
+    pl.ran = kernel_name(StftRoute::Tf);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), SMEM, pl.stream, x, pl.d_window, LOG2E == 5 ? pl.d_tw_r32 : pl.d_tw_pass,
                        pl.d_tw_aux, out, (long long)n_samples, pl.H, T, total);
     return hipGetLastError();
 }
 
+// One route of zafx_routes.hpp's stft_route per call (launch_stft asks); the `if constexpr` guards keep every size to the kernels it has.
 template <int LOG2N, int LAYOUT, int SPEC>
-static hipError_t run_stft(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
-    const bool aligned = (n_samples % 2 == 0) && (pl.H % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0);
-#ifndef ZAFX_STFT_BAND
-#define ZAFX_STFT_BAND 1
-#endif
-    if constexpr (ZAFX_STFT_BAND && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 4096, reference layout: 16-frame tiles in two bands of bins (buffer loads: 32-bit byte offsets inside a clip)
-        // Complex rows off the 128-byte grid: k_stft_ft16b writes every line in two parts far apart (1024 clips, two-sided, T = 217: 4.33 ms
-        // against 3.24 on the one-workgroup-per-tile kernel); the carry form k_stft_ft16bc (one band per workgroup) completes the lines:
-        // T = 217: 2.33 ms, T = 434 (hop 1024): 4.44 against 5.20.  One-sided output has half the stores to gain from and the form reads
-        // every sample twice: it wins at hop >= W / 2 only (T = 217: 1.89 against 1.96; hop 1024: 3.72 against 3.36 -> generic kernel).
-        // The float32 kinds write half lines either way and gain from k_stft_ft16b at every T (magnitude, T = 217: 1.33 against 1.67 ms).
-        const bool whole = row_pitch(pl, T) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 128 == 0;
-#ifndef ZAFX_STFT_BAND_CARRY
-#define ZAFX_STFT_BAND_CARRY 1
-#endif
-        const bool fits = pl.d_tw_sub && (long long)n_clips * ((T + 15) / 16) < (1LL << 30) && n_samples < (1LL << 29) && (long long)(T + 16) * pl.H < (1LL << 29) && reinterpret_cast<uintptr_t>(x) % 4 == 0;
-        if constexpr (SPEC < 2 && ZAFX_STFT_BAND_CARRY) {
-            if (!whole && fits && (SPEC == 0 || 2 * pl.H >= pl.W) && reinterpret_cast<uintptr_t>(out) % 8 == 0 && n_clips * (long long)T < (1LL << 31))
-                return aligned ? run_stft_band_carry<true, SPEC>(pl, x, out, n_clips, n_samples, T) : run_stft_band_carry<false, SPEC>(pl, x, out, n_clips, n_samples, T);
-        }
-        if ((SPEC >= 2 || whole) && pl.d_tw_sub && (long long)n_clips * ((T + 15) / 16) < (1LL << 31) && n_samples < (1LL << 29) && (long long)(T + 16) * pl.H < (1LL << 29) && reinterpret_cast<uintptr_t>(x) % 4 == 0)
-            return aligned ? run_stft_band<true, SPEC>(pl, x, out, n_clips, n_samples, T) : run_stft_band<false, SPEC>(pl, x, out, n_clips, n_samples, T);
+static hipError_t run_stft(const zafx_plan& pl, const Route<StftRoute>& r, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
+    switch (r.k) {
+        case StftRoute::BandCarry:
+            if constexpr (ZAFX_STFT_BAND && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT && SPEC < 2 && ZAFX_STFT_BAND_CARRY)
+                return r.aligned ? run_stft_band_carry<true, SPEC>(pl, x, out, n_clips, n_samples, T) : run_stft_band_carry<false, SPEC>(pl, x, out, n_clips, n_samples, T);
+            break;
+        case StftRoute::Band:
+            if constexpr (ZAFX_STFT_BAND && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT)
+                return r.aligned ? run_stft_band<true, SPEC>(pl, x, out, n_clips, n_samples, T) : run_stft_band<false, SPEC>(pl, x, out, n_clips, n_samples, T);
+            break;
+        case StftRoute::Quad:
+            if constexpr (ZAFX_STFT_QUAD && LOG2N == 12 && LAYOUT == ZAFX_LAYOUT_FT) return run_stft_quad<SPEC>(pl, x, out, n_clips, n_samples, T);
+            break;
+        case StftRoute::FatCarry:
+            if constexpr (stft_use_fat(LOG2N, LAYOUT) && SPEC < 2 && ZAFX_STFT_CARRY)
+                return r.aligned ? run_stft_fat_carry<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T)
+                                 : run_stft_fat_carry<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T);
+            break;
+        case StftRoute::Fat:
+            if constexpr (stft_use_fat(LOG2N, LAYOUT))
+                return r.aligned ? run_stft_fat<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T, r.claimed)
+                                 : run_stft_fat<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T, r.claimed);
+            break;
+        case StftRoute::Tf:
+            if constexpr (stft_use_tf(LOG2N, LAYOUT))
+                return r.aligned ? run_stft_tf<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T)
+                                 : run_stft_tf<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T);
+            break;
+        case StftRoute::Generic:
+            if constexpr (!stft_use_fat(LOG2N, LAYOUT) && !stft_use_tf(LOG2N, LAYOUT)) {
+                constexpr int LOG2E = default_log2e(LOG2N);
+                constexpr int FPB = stft_fpb(LOG2N, LAYOUT);
+                using S = StftCfg<LOG2N, LOG2E, FPB>;
+                auto kern = k_stft<LOG2N, LOG2E, FPB, LAYOUT, SPEC>;
+                if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, S::SMEM); e != hipSuccess) return e;
+                const int tiles = (T + FPB - 1) / FPB;
+                const long long blocks = (long long)tiles * n_clips;
+                if (blocks <= 0) return hipSuccess;
+                pl.ran = kernel_name(StftRoute::Generic);
+                hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(S::NT), S::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux,
+                                   out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles);
+                return hipGetLastError();
+            }
+            break;
+        case StftRoute::Spec2: break;   // (launch_stft sent it to launch_spec2)
     }
-#ifndef ZAFX_STFT_QUAD
-#define ZAFX_STFT_QUAD 1
-#endif
-    if constexpr (ZAFX_STFT_QUAD && LOG2N == 12 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 8192, reference layout: 16-frame tiles in four classes of bins (4-byte buffer loads: 32-bit byte offsets inside a clip)
-        // 1024 clips x 10 s, hop 4096, T = 112 (rows are whole lines): two-sided 2.19-2.29 ms against 2.77 on the one-workgroup-per-tile kernel, one-sided
-        // 1.68 against 1.99, |X| 1.60 against 1.84; T = 109: 3.3-4.3 against 3.04 two-sided (every line written in two parts by two workgroups: the
-        // generic kernel keeps those), 2.19 against 2.17 one-sided, 1.74 against 1.93 |X|
-        const bool whole = row_pitch(pl, T) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 128 == 0;
-        if ((SPEC != 0 || whole) && pl.d_tw_sub && pl.d_tw_quad && (long long)n_clips * ((T + 15) / 16) < (1LL << 31) && n_samples < (1LL << 29) &&
-            (long long)(T + 16) * pl.H < (1LL << 28) && reinterpret_cast<uintptr_t>(x) % 4 == 0)
-            return run_stft_quad<SPEC>(pl, x, out, n_clips, n_samples, T);
-    }
-    if constexpr (stft_use_fat(LOG2N, LAYOUT)) {
-#ifndef ZAFX_STFT_CARRY
-#define ZAFX_STFT_CARRY 1
-#endif
-#ifndef ZAFX_STFT_CARRY_ALWAYS
-#define ZAFX_STFT_CARRY_ALWAYS(log2n) ((log2n) == 9)   // W = 1024, two-sided: the carry form also on the line grid (863 / 864 frames: 1.90 ms against k_stft_ft16's 2.22; one-sided 1.31 against 1.21: not; W = 512, 256: 2.15 / 2.54 against 2.05 / 2.12: not)
-#endif
-        if constexpr (SPEC < 2 && ZAFX_STFT_CARRY) {
-            // rows off the 128-byte grid (the array itself only needs its 8-byte alignment): the carry form writes whole lines anyway
-            if (((SPEC == 0 && ZAFX_STFT_CARRY_ALWAYS(LOG2N)) || row_pitch(pl, T) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 128 != 0) && reinterpret_cast<uintptr_t>(out) % 8 == 0 && n_clips * (long long)T < (1LL << 31))
-                return aligned && n_samples < (1LL << 29) && (long long)T * pl.H < (1LL << 29) ? run_stft_fat_carry<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T)
-                               : run_stft_fat_carry<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T);
-        }
-        return aligned ? run_stft_fat<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T)
-                       : run_stft_fat<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T);
-    } else if constexpr (stft_use_tf(LOG2N, LAYOUT)) {
-        return aligned ? run_stft_tf<LOG2N, true, SPEC>(pl, x, out, n_clips, n_samples, T)
-                       : run_stft_tf<LOG2N, false, SPEC>(pl, x, out, n_clips, n_samples, T);
-    } else {
-        constexpr int LOG2E = default_log2e(LOG2N);
-        constexpr int FPB = stft_fpb(LOG2N, LAYOUT);
-        using S = StftCfg<LOG2N, LOG2E, FPB>;
-        auto kern = k_stft<LOG2N, LOG2E, FPB, LAYOUT, SPEC>;
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, S::SMEM); e != hipSuccess) return e;
-        const int tiles = (T + FPB - 1) / FPB;
-        const long long blocks = (long long)tiles * n_clips;
-        if (blocks <= 0) return hipSuccess;
-        pl.ran = "k_stft";
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(S::NT), S::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux,
-                           out, (long long)n_samples, pl.H, T, (int)row_pitch(pl, T), tiles);
-        return hipGetLastError();
-    }
+    return hipErrorInvalidValue;
 }
 
 // (carry_segments, the cut of every clip's tiles into segments for the persistent grid: zafx_units.hpp)
@@ -2774,7 +2739,7 @@ static hipError_t run_stft(const zafx_plan& pl, const float* x, float2* out, int
 #define ZAFX_ISTFT_TF_DEPTH 2
 #endif
 template <int LOG2N, bool ONE, bool TF = false>
-static hipError_t run_istft_fat(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len) {
+static hipError_t run_istft_fat(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len, bool pairs) {
     constexpr int LOG2E = default_log2e(LOG2N);
     using F = FatCfg<LOG2N, LOG2E>;
     // 16-byte gathers (two adjacent frames per lane) when the rows allow it; see the kernel
@@ -2782,7 +2747,7 @@ static hipError_t run_istft_fat(const zafx_plan& pl, const float2* spec, float* 
     const int TP = (int)row_pitch(pl, T);
     // (buffer loads take 16 bytes at any 8-byte offset: odd row pitches -- T = 433: 2.46 ms on the 8-byte form against 1.80 at T = 432 -- ride the
     // 16-byte form too; a pair whose second frame lies past T reads the next row's first element, or 0 past the clip, and that frame is never used)
-    const bool vec = can_vec && reinterpret_cast<uintptr_t>(spec) % 8 == 0;
+    const bool vec = can_vec && pairs;   // (istft_route's `vec`: spec on 8 bytes)
     // sweeps streamed together: 8 loads per wave in flight is the measured optimum (profiles/r01_notes.md);
     // a one-sided sweep has 2 loads instead of 4
     constexpr int D1 = TF ? ZAFX_ISTFT_TF_DEPTH : ONE ? 4 : 2, D2 = ONE ? 4 : 1;
@@ -2804,22 +2769,19 @@ static hipError_t run_istft_fat(const zafx_plan& pl, const float2* spec, float* 
     const long long units = (long long)n_clips * segs;
     const float scale = 1.f / (4.f * (float)(1 << LOG2N) * pl.cola_gain);
     const long long grid = std::min<long long>(units, max_grid);
-    pl.ran = "k_istft_ft16";
+    pl.ran = kernel_name(IstftRoute::Fat);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nt), F::SMEM, pl.stream, spec, pl.d_tw_pass, pl.d_tw_aux, y, T, TP, pl.H,
                        (long long)out_len, scale, tiles, segs, seg_tiles, (int)units, halo);
     return hipGetLastError();
 }
 
-#ifndef ZAFX_ISTFT_BAND
-#define ZAFX_ISTFT_BAND 1
-#endif
 // k_istft_ft16b: W = 4096 in the reference layout, one band of samples per workgroup (see the kernel)
 template <bool ONE>
-static hipError_t run_istft_band(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len) {
+static hipError_t run_istft_band(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len, bool vec) {
     using F = FatCfg<10, 4>;
     constexpr int M = 2048;
     const size_t smem = (size_t)(kFatFrames * F::PITCH + FftCfg<10, 4>::TW + M / 2 + 1) * 8 + (size_t)(2048 - pl.H / 2) * 4;
-    const bool vec = row_pitch(pl, T) % 2 == 0 && reinterpret_cast<uintptr_t>(spec) % 16 == 0;   // 16-byte row pieces of two adjacent frames
+    // (vec -- istft_route's spectrum_pairs --: 16-byte row pieces of two adjacent frames)
     auto kern = vec ? k_istft_ft16b<1, ONE, 2> : k_istft_ft16b<ONE ? 2 : 1, ONE, 1>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, smem); e != hipSuccess) return e;
     const int halo = (4096 + pl.H - 1) / pl.H - 1;
@@ -2831,7 +2793,7 @@ static hipError_t run_istft_band(const zafx_plan& pl, const float2* spec, float*
     const long long units = 2LL * n_clips * segs;
     const float scale = 1.f / (4.f * (float)M * pl.cola_gain);
     const long long grid = std::min<long long>(units, max_grid);
-    pl.ran = "k_istft_ft16b";
+    pl.ran = kernel_name(IstftRoute::Band);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(1024), smem, pl.stream, spec, pl.d_tw_sub, pl.d_tw_aux, y, T, (int)row_pitch(pl, T), pl.H / 2,
                        (long long)out_len, scale, tiles, segs, seg_tiles, (int)units, halo);
     return hipGetLastError();
@@ -2855,9 +2817,7 @@ static hipError_t run_istft_band(const zafx_plan& pl, const float2* spec, float*
 // registers.  Overlap-add in the reference's ascending frame order (zaf.py:226-233): a frame's second half goes through LDS to the wave of
 // the next frame (the tile's last one to the next tile), which adds its first half and stores 16-byte pieces; the trim of zaf.py:236-238
 // drops frame 0's first half and the last frame's second.
-#ifndef ZAFX_ISTFT_QUAD
-#define ZAFX_ISTFT_QUAD 1
-#endif
+// (ZAFX_ISTFT_QUAD, the switch of this route: zafx_routes.hpp)
 #ifndef ZAFX_ISTFT_QUAD_FV
 #define ZAFX_ISTFT_QUAD_FV 2   // frames per lane and load where the row pitch is even
 #endif
@@ -3119,18 +3079,18 @@ __global__ __launch_bounds__(IstftQCfg::NT) void k_istft_ft8q(const float2* __re
 }
 
 template <bool ONE>
-static hipError_t run_istft_quad(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len) {
+static hipError_t run_istft_quad(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len, bool vec) {
     using Q = IstftQCfg;
     const int tiles = (T + Q::FPB - 1) / Q::FPB;
     if ((long long)tiles * n_clips <= 0 || out_len <= 0) return hipSuccess;
-    const bool wide = ZAFX_ISTFT_QUAD_FV == 2 && row_pitch(pl, T) % 2 == 0 && reinterpret_cast<uintptr_t>(spec) % 16 == 0;   // 16-byte pieces of two frames
+    const bool wide = ZAFX_ISTFT_QUAD_FV == 2 && vec;   // 16-byte pieces of two frames (istft_route's spectrum_pairs)
     auto kern = wide ? k_istft_ft8q<ONE, 2> : k_istft_ft8q<ONE, 1>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, Q::SMEM); e != hipSuccess) return e;
     const int segs = carry_segments(n_clips, tiles, pl.n_cus);
     const int seg_tiles = (tiles + segs - 1) / segs;
     const long long units = n_clips * segs;
     const float scale = 1.f / (8192.f * pl.cola_gain);   // 1 / W of the inverse transform (the classes carry 2 Xh); zaf.py:241
-    pl.ran = "k_istft_ft8q";
+    pl.ran = kernel_name(IstftRoute::Quad);
     hipLaunchKernelGGL(kern, dim3((unsigned)std::min<long long>(units, pl.n_cus)), dim3(Q::NT), Q::SMEM, pl.stream, spec, pl.d_tw_sub, pl.d_tw_quad, y, T,
                        (int)row_pitch(pl, T), (long long)out_len, scale, tiles, segs, seg_tiles, (int)units);
     return hipGetLastError();
@@ -3147,9 +3107,7 @@ static hipError_t run_istft_quad(const zafx_plan& pl, const float2* spec, float*
 // k_istft_ft16b runs one band of SAMPLES per workgroup and each band needs every row: 1.79 x the algorithmic bytes -- as 128-byte pieces (16
 // frames), a wavefront transforms its frame in its own buffer, and the overlap-add (zaf.py:226-233, hop = W / 2: a frame's second half + the next
 // frame's first) goes through LDS to the wave of the next frame (the tile's last one: to the next tile) with 16-byte stores.
-#ifndef ZAFX_ISTFT_DUO
-#define ZAFX_ISTFT_DUO 1
-#endif
+// (ZAFX_ISTFT_DUO, the switch of this route: zafx_routes.hpp)
 #ifndef ZAFX_ISTFT_DUO_DEPTH
 #define ZAFX_ISTFT_DUO_DEPTH 1   // sweeps of a class's gather in flight per thread (1 / 2 / 4: 1.87 / 1.92 / 1.98 ms on padded rows, 2.95 / 3.06 / 3.53 compact at T = 217)
 #endif
@@ -3339,18 +3297,18 @@ __global__ __launch_bounds__(IstftDCfg::NT) void k_istft_ft16d(const float2* __r
 }
 
 template <bool ONE>
-static hipError_t run_istft_duo(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len) {
+static hipError_t run_istft_duo(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len, bool wide) {
     using Q = IstftDCfg;
     const int tiles = (T + Q::FPB - 1) / Q::FPB;
     if ((long long)tiles * n_clips <= 0 || out_len <= 0) return hipSuccess;
-    const bool wide = row_pitch(pl, T) % 2 == 0 && reinterpret_cast<uintptr_t>(spec) % 16 == 0;   // 16-byte pieces of two frames
+    // (wide -- istft_route's spectrum_pairs --: 16-byte pieces of two frames)
     auto kern = wide ? k_istft_ft16d<ONE, 2> : k_istft_ft16d<ONE, 1>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, Q::SMEM); e != hipSuccess) return e;
     const int segs = carry_segments(n_clips, tiles, pl.n_cus);
     const int seg_tiles = (tiles + segs - 1) / segs;
     const long long units = n_clips * segs;
     const float scale = 1.f / (4096.f * pl.cola_gain);   // 1 / W of the inverse transform (the classes carry 2 Xh); zaf.py:241
-    pl.ran = "k_istft_ft16d";
+    pl.ran = kernel_name(IstftRoute::Duo);
     hipLaunchKernelGGL(kern, dim3((unsigned)std::min<long long>(units, pl.n_cus)), dim3(Q::NT), Q::SMEM, pl.stream, spec, pl.d_tw_sub, pl.d_tw_aux, y, T,
                        (int)row_pitch(pl, T), (long long)out_len, scale, tiles, segs, seg_tiles, (int)units);
     return hipGetLastError();
@@ -3358,54 +3316,49 @@ static hipError_t run_istft_duo(const zafx_plan& pl, const float2* spec, float* 
 
 template <int LOG2N, int LAYOUT, bool ONE>
 static hipError_t run_istft(const zafx_plan& pl, const float2* spec, float* y, int64_t n_clips, int T, int64_t out_len) {
-    if constexpr (ZAFX_ISTFT_DUO && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 4096, hop = W / 2: the two-class kernel (32-bit byte offsets inside a clip's spectrum, 16-byte stores into the clip's samples)
-        const int64_t TP = row_pitch(pl, T);
-        if (pl.d_tw_sub && pl.d_tw_aux && pl.H == 2048 && reinterpret_cast<uintptr_t>(spec) % 8 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-            (long long)4096 * TP * 8 < (1LL << 31) && n_clips * (((long long)T + 15) / 16 + 1) < (1LL << 30))
-            return run_istft_duo<ONE>(pl, spec, y, n_clips, T, out_len);
+    const Route<IstftRoute> r = istft_route(route_call(pl, spec, y, n_clips, T, T, out_len));
+    switch (r.k) {
+        case IstftRoute::Duo:
+            if constexpr (ZAFX_ISTFT_DUO && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT) return run_istft_duo<ONE>(pl, spec, y, n_clips, T, out_len, r.vec);
+            break;
+        case IstftRoute::Band:
+            if constexpr (ZAFX_ISTFT_BAND && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT) return run_istft_band<ONE>(pl, spec, y, n_clips, T, out_len, r.vec);
+            break;
+        case IstftRoute::Quad:
+            if constexpr (ZAFX_ISTFT_QUAD && LOG2N == 12 && LAYOUT == ZAFX_LAYOUT_FT) return run_istft_quad<ONE>(pl, spec, y, n_clips, T, out_len, r.vec);
+            break;
+        case IstftRoute::Fat:
+            if constexpr (stft_use_fat(LOG2N, LAYOUT)) return run_istft_fat<LOG2N, ONE>(pl, spec, y, n_clips, T, out_len, r.vec);
+            break;
+        case IstftRoute::Tf:
+            if constexpr (stft_use_tf(LOG2N, LAYOUT)) return run_istft_fat<LOG2N, ONE, true>(pl, spec, y, n_clips, T, out_len, r.vec);
+            break;
+        case IstftRoute::Generic:
+            {   // (no guard: the frame-major sizes of k_istft_ft16 never get here, but their k_istft has always been built -- the set of kernels stays)
+                constexpr int LOG2E = default_log2e(LOG2N);
+                constexpr int FPB = stft_fpb(LOG2N, ZAFX_LAYOUT_FT);
+                using S = StftCfg<LOG2N, LOG2E, FPB>;
+                auto kern = k_istft<LOG2N, LOG2E, FPB, LAYOUT, ONE>;
+                if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, S::SMEM); e != hipSuccess) return e;
+                const int W = 2 << LOG2N;
+                const int halo = (W + pl.H - 1) / pl.H - 1;
+                const int owned = FPB - halo;
+                if (owned < 1) {
+                    set_error("istft: step_length too small for this window_length (ceil(W/H) exceeds frames per workgroup)");
+                    return hipErrorInvalidValue;
+                }
+                const int tiles = (T + owned - 1) / owned;
+                const long long blocks = (long long)tiles * n_clips;
+                if (blocks <= 0 || out_len <= 0) return hipSuccess;
+                const float scale = 1.f / (4.f * (float)(1 << LOG2N) * pl.cola_gain);
+                pl.ran = kernel_name(IstftRoute::Generic);
+                hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(S::NT), S::SMEM, pl.stream, spec, pl.d_tw_pass, pl.d_tw_aux, y, T,
+                                   (int)row_pitch(pl, T), pl.H, (long long)out_len, scale, tiles, owned, halo);
+                return hipGetLastError();
+            }
+            break;
     }
-    if constexpr (ZAFX_ISTFT_BAND && LOG2N == 11 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 4096: the band form wants a hop that is a multiple of 4 (a sample keeps its residue mod 4 from frame to frame), at least 512
-        // (ceil(W / H) - 1 <= 7 halo frames; the carry fits LDS), 32-bit byte offsets inside a clip's spectrum
-        const int64_t TP = row_pitch(pl, T);
-        if (pl.d_tw_sub && pl.H % 4 == 0 && pl.H >= 512 && pl.H <= 4096 && reinterpret_cast<uintptr_t>(spec) % 8 == 0 &&
-            (long long)4096 * TP * 8 < (1LL << 31) && 2LL * n_clips * ((T + 15) / 16) < (1LL << 30))
-            return run_istft_band<ONE>(pl, spec, y, n_clips, T, out_len);
-    }
-    if constexpr (ZAFX_ISTFT_QUAD && LOG2N == 12 && LAYOUT == ZAFX_LAYOUT_FT) {
-        // W = 8192, hop = W / 2: the four-class kernel (32-bit byte offsets inside a clip's spectrum, 16-byte stores into the clip's samples)
-        const int64_t TP = row_pitch(pl, T);
-        if (pl.d_tw_sub && pl.d_tw_quad && pl.H == 4096 && reinterpret_cast<uintptr_t>(spec) % 8 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-            (long long)8192 * TP * 8 < (1LL << 31) && n_clips * (((long long)T + 7) / 8 + 1) < (1LL << 30))
-            return run_istft_quad<ONE>(pl, spec, y, n_clips, T, out_len);
-    }
-    if constexpr (stft_use_fat(LOG2N, LAYOUT)) {
-        // the carry kernel addresses a clip through one buffer descriptor (32-bit byte offsets)
-        if ((long long)(2 << LOG2N) * row_pitch(pl, T) * 8 < (1LL << 31)) return run_istft_fat<LOG2N, ONE>(pl, spec, y, n_clips, T, out_len);
-    } else if constexpr (stft_use_tf(LOG2N, LAYOUT)) {
-        return run_istft_fat<LOG2N, ONE, true>(pl, spec, y, n_clips, T, out_len);
-    }
-    constexpr int LOG2E = default_log2e(LOG2N);
-    constexpr int FPB = stft_fpb(LOG2N, ZAFX_LAYOUT_FT);
-    using S = StftCfg<LOG2N, LOG2E, FPB>;
-    auto kern = k_istft<LOG2N, LOG2E, FPB, LAYOUT, ONE>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, S::SMEM); e != hipSuccess) return e;
-    const int W = 2 << LOG2N;
-    const int halo = (W + pl.H - 1) / pl.H - 1;
-    const int owned = FPB - halo;
-    if (owned < 1) {
-        set_error("istft: step_length too small for this window_length (ceil(W/H) exceeds frames per workgroup)");
-        return hipErrorInvalidValue;
-    }
-    const int tiles = (T + owned - 1) / owned;
-    const long long blocks = (long long)tiles * n_clips;
-    if (blocks <= 0 || out_len <= 0) return hipSuccess;
-    const float scale = 1.f / (4.f * (float)(1 << LOG2N) * pl.cola_gain);
-    pl.ran = "k_istft";
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(S::NT), S::SMEM, pl.stream, spec, pl.d_tw_pass, pl.d_tw_aux, y, T,
-                       (int)row_pitch(pl, T), pl.H, (long long)out_len, scale, tiles, owned, halo);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 #define ZAFX_STFT_SIZES(X) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
@@ -3415,35 +3368,28 @@ int stft_frames_per_block(int log2n, int layout) { return stft_fpb(log2n, layout
 // int16 PCM (one or two channels) straight into the complex STFT at W = 2048 in the reference layout (k_stft_ft16 / k_stft_ft16c): even clip length and
 // hop, everything inside the 32-bit offsets of one descriptor (zafx_execute_pcm)
 bool stft_pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sample_bytes, const void* d_pcm, int T) {
-    return sample_bytes == 2 && (n_channels == 1 || n_channels == 2) && pl.kind == ZAFX_STFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 &&
-           pl.log2nf == 10 && pl.layout == ZAFX_LAYOUT_FT && pl.prm.spectrum <= ZAFX_SPECTRUM_ONE_SIDED && n_frames % 2 == 0 && pl.H % 2 == 0 &&
-           reinterpret_cast<uintptr_t>(d_pcm) % 8 == 0 && n_frames < (1LL << 29) && (long long)T * pl.H < (1LL << 29);
+    RouteCall c = route_call(pl, d_pcm, nullptr, 1, n_frames, T);
+    c.channels = n_channels, c.sample_bytes = sample_bytes;
+    return stft_pcm_direct_ok(c);
 }
 
-const char* stft_kernel_name(int log2n, int layout) {
-    if (ZAFX_STFT_BAND && log2n == 11 && layout == ZAFX_LAYOUT_FT) return "k_stft_ft16b";
-    if (ZAFX_STFT_QUAD && log2n == 12 && layout == ZAFX_LAYOUT_FT) return "k_stft_ft16q";   // (planned: the four-class family; what RAN is last_kernel)
-    return stft_use_fat(log2n, layout) ? "k_stft_ft16" : stft_use_tf(log2n, layout) ? "k_stft_tf" : "k_stft";
-}
-const char* istft_kernel_name(int log2n, int layout) {
-    if (ZAFX_ISTFT_BAND && log2n == 11 && layout == ZAFX_LAYOUT_FT) return "k_istft_ft16b";
-    return stft_use_fat(log2n, layout) || stft_use_tf(log2n, layout) ? "k_istft_ft16" : "k_istft";
-}
+const char* stft_kernel_name(int log2n, int layout) { return kernel_name(stft_planned_route(log2n, layout)); }
+const char* istft_kernel_name(int log2n, int layout) { return kernel_name(istft_planned_route(log2n, layout)); }
 
 template <int L, int LAYOUT>
-static hipError_t dispatch_stft_spec(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
+static hipError_t dispatch_stft_spec(const zafx_plan& pl, const Route<StftRoute>& r, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
     switch (pl.prm.spectrum) {
-        case ZAFX_SPECTRUM_ONE_SIDED: return run_stft<L, LAYOUT, 1>(pl, x, out, n_clips, n_samples, T);
-        case ZAFX_SPECTRUM_MAGNITUDE: return run_stft<L, LAYOUT, 2>(pl, x, out, n_clips, n_samples, T);
-        case ZAFX_SPECTRUM_POWER: return run_stft<L, LAYOUT, 3>(pl, x, out, n_clips, n_samples, T);
-        default: return run_stft<L, LAYOUT, 0>(pl, x, out, n_clips, n_samples, T);
+        case ZAFX_SPECTRUM_ONE_SIDED: return run_stft<L, LAYOUT, 1>(pl, r, x, out, n_clips, n_samples, T);
+        case ZAFX_SPECTRUM_MAGNITUDE: return run_stft<L, LAYOUT, 2>(pl, r, x, out, n_clips, n_samples, T);
+        case ZAFX_SPECTRUM_POWER: return run_stft<L, LAYOUT, 3>(pl, r, x, out, n_clips, n_samples, T);
+        default: return run_stft<L, LAYOUT, 0>(pl, r, x, out, n_clips, n_samples, T);
     }
 }
 
 template <int L>
-static hipError_t dispatch_stft(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
-    return pl.layout == ZAFX_LAYOUT_FT ? dispatch_stft_spec<L, ZAFX_LAYOUT_FT>(pl, x, out, n_clips, n_samples, T)
-                                       : dispatch_stft_spec<L, ZAFX_LAYOUT_TF>(pl, x, out, n_clips, n_samples, T);
+static hipError_t dispatch_stft(const zafx_plan& pl, const Route<StftRoute>& r, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
+    return pl.layout == ZAFX_LAYOUT_FT ? dispatch_stft_spec<L, ZAFX_LAYOUT_FT>(pl, r, x, out, n_clips, n_samples, T)
+                                       : dispatch_stft_spec<L, ZAFX_LAYOUT_TF>(pl, r, x, out, n_clips, n_samples, T);
 }
 
 template <int L>
@@ -3455,10 +3401,11 @@ static hipError_t dispatch_istft(const zafx_plan& pl, const float2* spec, float*
 }
 
 hipError_t launch_stft(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T) {
-    if (hipError_t e = hipSuccess; launch_spec2(pl, x, reinterpret_cast<float*>(out), n_clips, n_samples, T, e)) return e;   // W = 2048, |X| / |X|^2, reference layout
+    const Route<StftRoute> r = stft_route(route_call(pl, x, out, n_clips, n_samples, T));
+    if (r.k == StftRoute::Spec2) return launch_spec2(pl, x, reinterpret_cast<float*>(out), n_clips, n_samples, T, r.aligned);   // W = 2048, |X| / |X|^2, reference layout
     switch (pl.log2nf) {
 #define X(L) \
-    case L: return dispatch_stft<L>(pl, x, out, n_clips, n_samples, T);
+    case L: return dispatch_stft<L>(pl, r, x, out, n_clips, n_samples, T);
         ZAFX_STFT_SIZES(X)
 #undef X
     }
