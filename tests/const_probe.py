@@ -120,10 +120,12 @@ def cqt_values_complex(ck):
 # ------------------------------------------------------------------------------------------------ the machinery
 class Case:
     """kind: name of the plan kind in zafx._lib; kw: Plan's keyword arguments; consts: constants A in upload order; ref(consts) -> the clips'
-    float64 results; bind(plan) -> x, out_shape, launch, split, keep (as tests/cu_probe.py); variants: name -> [(key, value), ...]."""
+    float64 results; bind(plan) -> x, out_shape, launch, split, keep (as tests/cu_probe.py); variants: name -> [(key, value), ...]; data: the
+    host input without a plan's row padding -- the clips, or the compact (B, rows, frames) blocks of an inverse case (tests/accuracy_cases.py)."""
 
-    def __init__(self, kind, kw, consts, ref, bind, tol, kernel, variants, err=relerr):
+    def __init__(self, kind, kw, consts, ref, bind, tol, kernel, variants, err=relerr, data=None):
         self.kind, self.kw, self.consts, self.ref, self.bind, self.tol, self.kernel, self.variants, self.err = kind, kw, consts, ref, bind, tol, kernel, variants, err
+        self.data = data
         self.oracle_rows = {}   # variant -> the leading rows of a result that are held to the oracle (mel_case); absent: all of them
         self._refs = {}
 
@@ -243,7 +245,8 @@ def stft_case(w, hop, kernel, row_align=0, layout="FT", onesided=False, f64=Fals
         half = full[:, :w // 2 + 1]
         return list(half if onesided is True else np.abs(half) if onesided == "magnitude" else np.abs(half) ** 2)
     kw = dict(window_length=w, step_length=hop, layout=layout, onesided=onesided, f64=f64, row_align=row_align)
-    return Case("STFT", kw, {"window": window_a(w)}, ref, forward_bind(x, n, frames, layout), TOL_F64 if f64 else TOL_FFT, kernel, window_variants(w))
+    return Case("STFT", kw, {"window": window_a(w)}, ref, forward_bind(x, n, frames, layout), TOL_F64 if f64 else TOL_FFT, kernel, window_variants(w),
+                data=x)
 
 
 def istft_case(w, hop, kernel, row_align=0, onesided=False, f64=False, frames=None, zero_gain=False):
@@ -265,7 +268,7 @@ def istft_case(w, hop, kernel, row_align=0, onesided=False, f64=False, frames=No
     if zero_gain:
         variants["zero_gain"] = [("window", window_zero_gain(w, hop))]
     kw = dict(window_length=w, step_length=hop, onesided=onesided, f64=f64, row_align=row_align)
-    return Case("ISTFT", kw, {"window": a}, ref, inverse_bind(spec, frames, dtype), TOL_F64 if f64 else TOL_FFT, kernel, variants)
+    return Case("ISTFT", kw, {"window": a}, ref, inverse_bind(spec, frames, dtype), TOL_F64 if f64 else TOL_FFT, kernel, variants, data=spec)
 
 
 def mdct_case(w, kernel, row_align=0, f64=False, frames=None):
@@ -276,7 +279,7 @@ def mdct_case(w, kernel, row_align=0, f64=False, frames=None):
     x = clips_of(w + 1, n, np.float64 if f64 else np.float32)
     ref = lambda c: list(orc.mdct_batch(x.astype(np.float64), c["window"]))
     return Case("MDCT", dict(window_length=w, row_align=row_align, f64=f64), {"window": window_a(w, True)}, ref, forward_bind(x, n, frames),
-                TOL_F64 if f64 else TOL_FFT, kernel, window_variants(w))
+                TOL_F64 if f64 else TOL_FFT, kernel, window_variants(w), data=x)
 
 
 def imdct_case(w, kernel, row_align=0, f64=False, frames=None):
@@ -288,7 +291,7 @@ def imdct_case(w, kernel, row_align=0, f64=False, frames=None):
     assert coefs.shape[2] == frames
     ref = lambda c: [orc.imdct(k.astype(np.float64), c["window"]) for k in coefs]
     return Case("IMDCT", dict(window_length=w, row_align=row_align, f64=f64), {"window": a}, ref, inverse_bind(coefs, frames, dtype),
-                TOL_F64 if f64 else TOL_FFT, kernel, window_variants(w))
+                TOL_F64 if f64 else TOL_FFT, kernel, window_variants(w), data=coefs)
 
 
 # ------------------------------------------------------------------------------------------------ mel / mfcc
@@ -331,7 +334,7 @@ def mel_case(w, hop, n_mel, n_coef, kernel, fs=FS, f64=False, also_mel=False, ro
     tol = (TOL_F64_MFCC if mfcc else TOL_F64) if f64 else TOL_FB
     # the one-pass plan's rows are the melspectrogram's, then the MFCCs': each part against its own level (the MFCCs are a tenth of the other's)
     err = (lambda val, r: max(relerr(val[:n_mel], r[:n_mel]), relerr(val[n_mel:], r[n_mel:]))) if also_mel else relerr
-    case = Case("MFCC" if mfcc else "MEL", kw, consts, mel_ref(x, hop, mfcc, also_mel), forward_bind(x, n, frames), tol, kernel, variants, err=err)
+    case = Case("MFCC" if mfcc else "MEL", kw, consts, mel_ref(x, hop, mfcc, also_mel), forward_bind(x, n, frames), tol, kernel, variants, err=err, data=x)
     if mfcc and not f64 and "dense" in extra_fb:
         # Under the dense filterbank every band holds the whole spectrum: the log-mel values are all about 14 and differ by a hundredth, the
         # DCT's rows 1 .. n cancel the common level, and the MFCCs come out at 0.05 -- float32's rounding of the logs alone is 1e-4 of that, and
@@ -402,7 +405,7 @@ def cqt_case(which, chroma, kernel, f64=False):
         assert ck3.shape == ck.shape and ck3.nnz != ck.nnz, (ck3.shape, ck.shape, ck3.nnz, ck.nnz)
         variants["kernel"] = [("cqt", ck3)]
     kw = dict(step_length=step, fft_length=ck.shape[1], n_bins=ck.shape[0], octave_resolution=res if chroma else 0, f64=f64)
-    return Case("CHROMA" if chroma else "CQT", kw, {"cqt": ck}, ref, forward_bind(x, n, 5), TOL_F64 if f64 else TOL_FB, kernel, variants)
+    return Case("CHROMA" if chroma else "CQT", kw, {"cqt": ck}, ref, forward_bind(x, n, 5), TOL_F64 if f64 else TOL_FB, kernel, variants, data=x)
 
 
 def linear_case():
@@ -415,7 +418,7 @@ def linear_case():
         return dict(x=x, out_shape=(N_CLIPS, rows), launch=lambda p, d_in, d_out: p.execute(d_in, d_out, N_CLIPS, cols),
                     split=lambda out: [out[c] for c in range(N_CLIPS)], keep=None)
     return Case("LINEAR", dict(window_length=cols, n_filters=rows), {"matrix": a}, lambda c: [c["matrix"] @ r.astype(np.float64) for r in x], bind,
-                TOL_FFT, "k_linear", {"matrix": [("matrix", b)]})
+                TOL_FFT, "k_linear", {"matrix": [("matrix", b)]}, data=x)
 
 
 # ------------------------------------------------------------------------------------------------ the routes

@@ -176,8 +176,9 @@ def _view(zafx, raw, delta, nbytes):
     return zafx.DeviceBuffer((nbytes,), np.uint8, _ptr_from_pool=ctypes.c_void_p(raw.ptr.value + delta))
 
 
-def run(c, plan, tag):
-    """One execute of N_CLIPS clips at the case's addresses -> the output array's bytes (row padding included)."""
+def run(c, plan, tag, keep=None):
+    """One execute of N_CLIPS clips at the case's addresses -> the output array's bytes (row padding included).  keep: a dict that receives
+    the host input ("x", as the plan's rows hold it, pad columns included) and its length or frame count ("n_in")."""
     import zafx
     n_in = c["frames"] if is_inverse(c) else samples(c)
     in_bytes, out_bytes = plan.clip_bytes(n_in)
@@ -185,6 +186,8 @@ def run(c, plan, tag):
         x = noise(tag, (N_CLIPS, n_in), np.int16)
     else:
         x = noise(tag, (N_CLIPS * in_bytes // plan.in_dtype.itemsize,), plan.in_dtype)
+    if keep is not None:
+        keep.update(x=x, n_in=n_in)
     host = np.zeros(c["in_delta"] + x.nbytes + SLACK, np.uint8)
     host[c["in_delta"]:c["in_delta"] + x.nbytes] = np.frombuffer(x.tobytes(), np.uint8)
     raw_in = zafx.DeviceBuffer.from_host(host)
@@ -205,15 +208,19 @@ def run(c, plan, tag):
         raw_out.free()
 
 
-def record(name):
-    """-> [last_kernel, SHA-256 of the output bytes], or ["refused", the library's message]."""
+def record(name, keep=None):
+    """-> [last_kernel, SHA-256 of the output bytes], or ["refused", the library's message].  keep: a dict that receives the case's plan geometry
+    ("out_shape", "out_dtype", "pitch"), run's "x" and "n_in", and the output bytes ("out")."""
     import zafx
     c = CASES[name]
     zafx.clear_plan_cache()
     try:
         try:
             plan = make_plan(c)
-            out = run(c, plan, zlib.crc32(name.encode()))
+            out = run(c, plan, zlib.crc32(name.encode()), keep)
+            if keep is not None:
+                n_in = keep["n_in"]
+                keep.update(out=out, out_shape=plan.out_shape(N_CLIPS, n_in), out_dtype=plan.out_dtype, pitch=plan.row_pitch(n_in))
         except (RuntimeError, ValueError) as e:
             return ["refused", str(e)]
         return [plan.last_kernel, hashlib.sha256(out).hexdigest()]
