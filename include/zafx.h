@@ -29,6 +29,9 @@
  *   ZAFX_CENTER / _CENTER_SIDES    the center / sides example of istft's docstring, zaf.py:155-198 (stft of both
  *                                  channels :176-177, magnitudes :181-182, masks :185-186, masked spectra :190-191,
  *                                  istft :194-195, sides :198) in one kernel
+ *   ZAFX_MASKFILTER / _REST with   the same example with a mask of the caller's: stft zaf.py:176-177, the mirrored real mask times the
+ *   zafx_execute_masked            spectrum :190-191 (np.concatenate((mask, mask[-2:0:-1])) * audio_stft), istft :194-195 and, _REST,
+ *                                  the subtraction :198, for a mono clip in one kernel; zafx_plan_mask_dims gives the mask's shape
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -85,9 +88,18 @@ enum zafx_kind {
                                float32 only, window_length 256 / 512 / 1024 / 2048, step_length = window_length / 2 (zaf.stft pads W/2 in
                                front and zaf.istft trims W - H: at any other hop the reference's example fails on a shape mismatch);
                                n_in = N sample frames; zafx_plan_out_dims: dims[0] = sample frames written per clip, dims[1] = 2 */
-    ZAFX_CENTER_SIDES = 12  /* as ZAFX_CENTER -> out (B, 2, N, 2): block 0 of a clip the center, block 1 the sides = input - center (:198);
+    ZAFX_CENTER_SIDES = 12, /* as ZAFX_CENTER -> out (B, 2, N, 2): block 0 of a clip the center, block 1 the sides = input - center (:198);
                                the center is bit-identical to ZAFX_CENTER's.  Neither kind takes zafx_execute_ragged, zafx_execute_pcm or
                                zafx_run_host_pcm; clips of different lengths go through zafx_execute_center_ragged */
+    ZAFX_MASKFILTER = 13,   /* in (B, N) f32 mono and a real mask (B, W/2+1, T) f32 [FT: rows at zafx_plan_row_pitch, the array a
+                               ZAFX_SPECTRUM_MAGNITUDE STFT plan of the same layout and row_align writes] or (B, T, W/2+1) [TF], T = ceil(N / H) + 1
+                               (zafx_plan_mask_dims) -> out (B, N) f32: y = istft(concat(m, m[-2:0:-1]) * stft(x))[0:N], zaf.py:185-195 with the
+                               caller's mask.  Through zafx_execute_masked only.  float32 only, window_length 256 / 512 / 1024 / 2048,
+                               step_length = window_length / 2 (as the center kinds).  Two neighbouring frames of one clip share a complex
+                               transform: rounding error and a non-finite value of frame 2j+1 reach frame 2j (H samples further than in the
+                               reference), never another clip.  n_in = N samples; zafx_plan_out_dims: dims[0] = samples written per clip, dims[1] = 1 */
+    ZAFX_MASKFILTER_REST = 14 /* as ZAFX_MASKFILTER -> out (B, 2, N): block 0 of a clip the filtered clip, bit-identical to ZAFX_MASKFILTER's,
+                               block 1 the rest = input - block 0 in float32 (the filter of mask 1 - m) */
 };
 
 enum zafx_layout {
@@ -245,10 +257,25 @@ int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
  * Two kinds REFUSE long clips: the call returns an error (zafx_last_error names the limit), enqueues nothing and writes nothing.
  *   ZAFX_CQT / ZAFX_CHROMA (float32)          n_in >= 2^29 samples (3.4 h at 44.1 kHz): cut the signal
  *   ZAFX_CENTER / ZAFX_CENTER_SIDES           n_in >= 2^28 sample frames (1.7 h at 44.1 kHz)
+ *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked)
  * zafx_execute_pcm reads int16 in the kernels' own loads below the same lengths (n_frames < 2^29; the MDCT: < 2^28) and converts first above them.
  * Not run at its bound by any test yet: the two-sided complex STFT at window 8192 (k_stft_ft16q takes whole-line rows only; its |X| kind is run).
  * The ragged and PCM entry points state their own per-clip limits below. */
 int zafx_execute(zafx_plan* plan, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in);
+/* The mask filter of n_clips mono clips of n_in samples, enqueued on the plan's stream (asynchronous; ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST
+ * plans only, which zafx_execute, zafx_execute_ragged, zafx_execute_pcm and zafx_run_host* refuse; every other kind is refused here; last
+ * kernel "k_maskfilter").  d_mask: one real float32 mask per clip, zafx_plan_mask_dims rows x frames: in ZAFX_LAYOUT_FT (B, rows, pitch) with
+ * pitch = zafx_plan_row_pitch(plan, n_in) -- frames for a compact plan, frames rounded up to params.row_align otherwise; the padding and
+ * anything from column `frames` on is never read --, in ZAFX_LAYOUT_TF (B, frames, rows) compact, which reads whole lines and is the
+ * faster of the two.  The three arrays need 4-byte alignment only.  Nothing is read in front of sample 0 or from sample
+ * n_in on, nothing is written at or beyond n_in; no clip's result depends on another clip's samples or mask, and a clip has the same
+ * bits alone, anywhere in a batch and under any ZAFX_COMPUTE_UNITS.  A mask of zeros gives exact zeros, and so does silence under any
+ * finite mask.  Rejected with a message, nothing enqueued or written: a null plan or pointer, negative sizes, another kind, a window
+ * that is not set or whose sum(window[0:W:H]) is zero, clips of 2^28 samples and more. */
+int zafx_execute_masked(zafx_plan* plan, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in);
+/* The mask of one clip of n_in samples under a ZAFX_MASKFILTER / _REST plan: dims[0] = rows W/2 + 1, dims[1] = frames T = ceil(n_in / H) + 1,
+ * the frame count of zaf.stft (zaf.py:99-109).  zafx_plan_row_pitch(plan, n_in) gives the elements between its rows. */
+int zafx_plan_mask_dims(const zafx_plan* plan, int64_t n_in, int64_t dims[2]);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
  * with_mel included, _CQT, _CHROMA; float32 and float64).

@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "zafx_center.hpp"
+#include "zafx_maskfilter.hpp"
 #include "zafx_units.hpp"
 #include "zafx_wfold.hpp"
 #include "zafx_internal.hpp"
@@ -304,6 +305,18 @@ static int check_center_params(const zafx_params* p) {
     if (p->layout != ZAFX_LAYOUT_FT || p->row_align > 1) return fail_msg("center / sides: layout and row_align do not apply (no 2-D array crosses the boundary)");
     return 0;
 }
+static bool is_maskfilter_kind(int kind) { return kind == ZAFX_MASKFILTER || kind == ZAFX_MASKFILTER_REST; }
+// Geometry of the mask filter kinds, checked before the device is touched.  Both layouts and row_align apply: to the mask.
+static int check_maskfilter_params(const zafx_params* p) {
+    if (p->precision != ZAFX_PRECISION_F32) return fail_msg("mask filter: precision must be ZAFX_PRECISION_F32 (ZAFX_PRECISION_F64 is not available for these kinds)");
+    const int lw = ilog2_exact(p->window_length);
+    if (lw < 0 || !zafx::maskfilter_supported(lw)) return fail_msg("mask filter: window_length must be a power of two in [256, 2048]");
+    if (p->step_length != p->window_length / 2)
+        return fail_msg("mask filter: step_length must be window_length / 2 (zaf.stft pads window_length / 2 and zaf.istft trims window_length - step_length: "
+                        "the two agree at no other hop)");
+    return 0;
+}
+static const char* const kMaskedOnly = "mask filter plans (ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST) take a mask: call zafx_execute_masked";
 static bool is_stft_family(int kind) { return kind == ZAFX_STFT || kind == ZAFX_ISTFT || kind == ZAFX_MEL || kind == ZAFX_MFCC; }
 static bool is_mdct_family(int kind) { return kind == ZAFX_MDCT || kind == ZAFX_IMDCT; }
 static bool is_cqt_family(int kind) { return kind == ZAFX_CQT || kind == ZAFX_CHROMA; }
@@ -892,6 +905,7 @@ int check_params(int kind, const zafx_params* params) {
     if (params->row_align > 1 && (params->layout != ZAFX_LAYOUT_FT || kind == ZAFX_LINEAR || kind == ZAFX_DCT))
         return fail_msg("row_align applies to the 2-D arrays of ZAFX_LAYOUT_FT plans only");
     if (is_center_kind(kind)) return check_center_params(params);
+    if (is_maskfilter_kind(kind)) return check_maskfilter_params(params);
     return 0;
 }
 
@@ -956,7 +970,7 @@ const char* stft_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
 const char* center_geometry(zafx_plan& pl, std::vector<cf32>& aux) {
     pl.W = pl.prm.window_length;
     pl.H = pl.prm.step_length;
-    pl.log2nf = ilog2_exact(pl.W);   // a stereo sample frame is one complex point: W-point transforms
+    pl.log2nf = ilog2_exact(pl.W);   // a stereo sample frame is one complex point: W-point transforms (mask filter: two frames of a clip)
     aux.assign(1, cf32{1.f, 0.f});
     return nullptr;
 }
@@ -1092,6 +1106,7 @@ std::string planned_kernel_name(const zafx_plan& pl) {
     if (kind == ZAFX_ISTFT) return istft_kernel_name(pl.log2nf, pl.layout);
     if (mel) return kernel_name(mel_planned_route(pl.log2nf, pl.prm.n_filters));
     if (is_center_kind(kind)) return center_kernel_name();
+    if (is_maskfilter_kind(kind)) return maskfilter_kernel_name();
     if (kind == ZAFX_MDCT) return mdct_kernel_name(pl.log2nf, pl.layout);
     if (kind == ZAFX_IMDCT) return imdct_kernel_name();
     if (is_cqt_family(kind)) return cqt_kernel_name();
@@ -1286,11 +1301,11 @@ int zafx_plan_create(zafx_plan** out, int device, int kind, const zafx_params* p
     pl->prm = *params;
     pl->layout = params->layout;
     std::vector<cf32> aux;
-    const char* wrong = is_stft_family(kind) ? stft_geometry(*pl, aux) : is_center_kind(kind) ? center_geometry(*pl, aux)
+    const char* wrong = is_stft_family(kind) ? stft_geometry(*pl, aux) : is_center_kind(kind) || is_maskfilter_kind(kind) ? center_geometry(*pl, aux)
                         : is_mdct_family(kind) ? mdct_geometry(*pl, aux) : is_cqt_family(kind) ? cqt_geometry(*pl, aux)
                         : kind == ZAFX_LINEAR ? linear_geometry(*pl, aux) : kind == ZAFX_DCT ? dct_geometry(*pl, aux) : "unknown plan kind";
     if (wrong) return fail_msg(wrong);
-    pl->log2e = is_center_kind(kind) ? center_log2e(pl->log2nf) : default_log2e(pl->log2nf);
+    pl->log2e = is_center_kind(kind) || is_maskfilter_kind(kind) ? center_log2e(pl->log2nf) : default_log2e(pl->log2nf);
     pl->kernel_name = planned_kernel_name(*pl);
     if (hipError_t e = build_plan(*pl, aux); e != hipSuccess) return fail("zafx_plan_create", e);
     *out = pl.release();
@@ -1415,6 +1430,8 @@ int zafx_plan_out_dims(const zafx_plan* pl, int64_t n_in, int64_t dims[2]) {
         case ZAFX_ISTFT: dims[0] = std::max<int64_t>(0, n_in * h - (w - h)); dims[1] = 1; return 0;   // zaf.py:217, :236-238
         case ZAFX_CENTER: dims[0] = n_in; dims[1] = 2; return 0;                                      // sample frames written per clip x channels
         case ZAFX_CENTER_SIDES: dims[0] = 2 * n_in; dims[1] = 2; return 0;
+        case ZAFX_MASKFILTER: dims[0] = n_in; dims[1] = 1; return 0;                                  // samples written per clip
+        case ZAFX_MASKFILTER_REST: dims[0] = 2 * n_in; dims[1] = 1; return 0;
         case ZAFX_MDCT: dims[0] = w / 2; dims[1] = (n_in + h - 1) / h + 1; return 0;                  // zaf.py:1033
         case ZAFX_IMDCT: dims[0] = std::max<int64_t>(0, h * (n_in - 1) - 1); dims[1] = 1; return 0;    // zaf.py:1132, :1182
         case ZAFX_CQT: dims[0] = pl->prm.n_bins; dims[1] = n_in / h; return 0;                         // zaf.py:606
@@ -1441,12 +1458,37 @@ int zafx_plan_row_pitch(const zafx_plan* pl, int64_t n_in, int64_t* pitch) {
         case ZAFX_IMDCT: *pitch = pl->layout == ZAFX_LAYOUT_FT ? row_pitch(*pl, n_in) : pl->W / 2; return 0;
         case ZAFX_LINEAR: case ZAFX_DCT: *pitch = dims[0]; return 0;
         case ZAFX_CENTER: case ZAFX_CENTER_SIDES: *pitch = 2; return 0;   // a row is one sample frame: (L, R)
+        case ZAFX_MASKFILTER: case ZAFX_MASKFILTER_REST:                    // the 2-D side is the mask: (W/2 + 1, T)
+            *pitch = pl->layout == ZAFX_LAYOUT_FT ? row_pitch(*pl, zafx::maskfilter_frames(n_in, pl->W)) : pl->W / 2 + 1;
+            return 0;
         default: *pitch = pl->layout == ZAFX_LAYOUT_FT ? row_pitch(*pl, dims[1]) : dims[0]; return 0;
     }
 }
 
+int zafx_plan_mask_dims(const zafx_plan* pl, int64_t n_in, int64_t dims[2]) {
+    if (!pl || !dims) return fail_msg("null argument");
+    if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_plan_mask_dims: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only");
+    if (n_in < 0) return fail_msg("negative size");
+    dims[0] = pl->W / 2 + 1;
+    dims[1] = zafx::maskfilter_frames(n_in, pl->W);
+    return 0;
+}
+
+int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
+    if (!pl) return fail_msg("null plan");
+    if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_execute_masked: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only (every other kind takes zafx_execute)");
+    if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
+    if (n_clips == 0) return 0;
+    if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
+    if (!pl->d_window) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    ZAFX_HIP(hipSetDevice(pl->device));
+    return launch_rc("zafx_execute_masked", zafx::launch_maskfilter(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in));
+}
+
 int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in) {
     if (!pl) return fail_msg("null plan");
+    if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("zafx_execute: ") + kMaskedOnly);
     if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
     if (n_clips == 0) return 0;
     if (!d_in || !d_out) return fail_msg("null device pointer");
@@ -1547,6 +1589,7 @@ int zafx_plan_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t
     if (!pl || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
     if (n_clips < 0) return fail_msg("negative size");
     if (is_center_kind(pl->kind)) return fail_msg("ragged batches: center / sides plans take clips of one length (ragged stereo batches are not implemented)");
+    if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("ragged batches: ") + kMaskedOnly);
     if (!ragged_kind(pl->kind)) return fail_msg("ragged batches: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
     out_offsets[0] = 0;
     for (int64_t i = 0; i < n_clips; ++i) {
@@ -1637,7 +1680,7 @@ static int ragged_args(const char* fn, const zafx_plan* pl, int64_t n_clips, con
 }
 
 static const char* ragged_wrong_kind(const zafx_plan* pl) {
-    return !pl || ragged_kind(pl->kind) ? nullptr : !is_center_kind(pl->kind) ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)"
+    return !pl || ragged_kind(pl->kind) ? nullptr : is_maskfilter_kind(pl->kind) ? kMaskedOnly : !is_center_kind(pl->kind) ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)"
                                         : "center / sides plans take clips of one length (ragged stereo batches are not implemented)";
 }
 
@@ -1924,6 +1967,10 @@ static int clip_bytes(const zafx_plan* pl, int64_t n_in, int64_t* in_b, int64_t*
             *in_b = n_in * 2 * real;
             *out_b = dims[0] * 2 * real;
             return 0;
+        case ZAFX_MASKFILTER: case ZAFX_MASKFILTER_REST:   // (the clip's samples; its mask: zafx_plan_mask_dims rows at zafx_plan_row_pitch)
+            *in_b = n_in * real;
+            *out_b = dims[0] * real;
+            return 0;
         case ZAFX_LINEAR: case ZAFX_DCT:
             *in_b = (int64_t)pl->W * 4;
             *out_b = dims[0] * 4;
@@ -1998,6 +2045,7 @@ int zafx_execute_pcm(zafx_plan* pl, const void* d_pcm, void* d_out, int64_t n_cl
     if (sample_bytes != 2 && sample_bytes != 4) return fail_msg("sample_bytes must be 2 (int16) or 4 (int32)");
     if (pl->prm.precision != ZAFX_PRECISION_F32) return fail_msg("PCM ingest feeds the float32 plans");
     if (is_center_kind(pl->kind)) return fail_msg("PCM ingest: center / sides plans take float32 stereo (integer stereo ingest is not implemented)");
+    if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("PCM ingest: ") + kMaskedOnly);
     switch (pl->kind) {
         case ZAFX_STFT: case ZAFX_MDCT: case ZAFX_MEL: case ZAFX_MFCC: case ZAFX_CQT: case ZAFX_CHROMA: case ZAFX_DCT: break;
         default: return fail_msg("PCM ingest feeds the plans that take samples (stft, mdct, mel, mfcc, cqt, chroma, dct)");
@@ -2059,6 +2107,7 @@ static int run_host_impl(zafx_plan* pl, const void* h_in, void* h_out, int64_t n
     if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
     if (n_clips == 0) return 0;
     if (!h_in || !h_out) return fail_msg("null host pointer");
+    if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("zafx_run_host: ") + kMaskedOnly);
     int64_t in_b = 0, out_b = 0;
     if (int rc = clip_bytes(pl, n_in, &in_b, &out_b)) return rc;
     const int64_t host_in_b = pcm_bytes > 0 ? n_in * pcm_channels * pcm_bytes : in_b;   // bytes of one clip in h_in
@@ -2151,6 +2200,7 @@ int zafx_run_host_pcm(zafx_plan* pl, const void* h_pcm, void* h_out, int64_t n_c
     if (sample_bytes != 2 && sample_bytes != 4) return fail_msg("sample_bytes must be 2 (int16) or 4 (int32)");
     if (pl->prm.precision != ZAFX_PRECISION_F32) return fail_msg("PCM ingest feeds float32 plans");
     if (is_center_kind(pl->kind)) return fail_msg("PCM ingest: center / sides plans take float32 stereo (integer stereo ingest is not implemented)");
+    if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("PCM ingest: ") + kMaskedOnly);
     switch (pl->kind) {
         case ZAFX_STFT: case ZAFX_MDCT: case ZAFX_MEL: case ZAFX_MFCC: case ZAFX_CQT: case ZAFX_CHROMA: case ZAFX_DCT: break;
         default: return fail_msg("PCM ingest feeds the plans that take samples (stft, mdct, mel, mfcc, cqt, chroma, dct)");

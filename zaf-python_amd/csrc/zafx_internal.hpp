@@ -371,6 +371,9 @@ const char* dct_kernel_name();
 const char* linear_kernel_name();
 hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples);   // zafx_center.hip: ZAFX_CENTER / ZAFX_CENTER_SIDES
 const char* center_kernel_name();
+// zafx_maskfilter.hip: ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST (zafx_execute_masked); mask: (B, W/2+1, row_pitch(T)) or, ZAFX_LAYOUT_TF, (B, T, W/2+1)
+hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples);
+const char* maskfilter_kernel_name();
 // zafx_execute_center_ragged: the tile frames F and the workgroup slots of the plan's k_center (what center_cut_units takes), and the launch of
 // its RAGGED form on `n_units` records of the device table
 struct CenterUnit;

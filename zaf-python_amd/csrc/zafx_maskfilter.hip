@@ -1,0 +1,274 @@
+// zafx_maskfilter.hip -- k_maskfilter: STFT, the caller's real time-frequency mask and ISTFT of mono clips in one kernel.
+//
+// y = istft(concat(m, m[-2:0:-1]) * stft(x, w, W/2), w, W/2)[0:N] (zaf.py:185-195 with a mask of the caller's) without a spectrum ever
+// leaving the CU; REST: rest = x - y behind it.  zafx_maskfilter.hpp has the arithmetic.  Structure, on k_center's plan
+// (zafx_center.hip) of segments, tiles and a carry in LDS:
+//
+//   * Two neighbouring frames of one clip are ONE W-point complex transform: transform q holds frame 2q (sample frames (2q - 1) H ..) in
+//     its real part and frame 2q + 1 (2q H ..) in its imaginary part.  The second half of frame 2q IS the first half of frame 2q + 1, so
+//     a lane loads 3 E / 2 samples for its E complex points.  No two clips ever share a transform.
+//   * Split, mask and re-pack run in place on the pairs (k, W-k) of the LDS frame (maskfilter_pair) with the mask values of a lane's
+//     pairs, m[k, 2q] and m[k, 2q + 1].  ZAFX_LAYOUT_TF: 64 lanes read 64 consecutive floats of a frame's row, behind the samples and in
+//     front of the forward transform, so the values arrive under it.  ZAFX_LAYOUT_FT: a lane's two values are 8 bytes of ITS row -- read that
+//     way a load instruction touches 64 lines and every line comes from HBM about five times --, so every second tile the
+//     whole workgroup fetches the next FS frames of every row, FS lanes to a row (64 or 128 contiguous bytes), into a stage in LDS, and
+//     the lanes take their pairs' values from there.  These loads are waited for where they are issued, not under the transform.
+//     A frame beyond the clip's last (an odd frame count pairs the last frame with zeros) reads no mask: its mask is 0.
+//   * The inverse is the forward core on the swapped parts.  Output block b (samples b H .. b H + H - 1) is the second half of frame b plus
+//     the first half of frame b + 1: block 2q comes from transform q alone, block 2q - 1 from the imaginary part of transform q - 1 -- the
+//     neighbour's LDS frame, or the carry the previous tile left -- and the real part of transform q.  The lanes of transform q write both.
+//   * A segment is an even number of blocks, so it starts on a transform of its own and needs nothing in front; one that ends on an even
+//     block runs one transform more for that block's second term (the halo).  Every transform's inputs are the clip's own samples and mask
+//     columns whatever the segment, so a clip has the same bits however it is cut.
+#include <algorithm>
+
+#include "zafx_maskfilter.hpp"
+#include "zafx_internal.hpp"
+
+namespace zafx {
+
+template <int LOG2W, bool TF>
+struct MaskfilterCfg {
+    static constexpr int LOG2E = maskfilter_log2e(LOG2W);
+    using C = FftCfg<LOG2W, LOG2E>;
+    static constexpr int W = 1 << LOG2W, H = W / 2, E = C::E, P = C::P, F = maskfilter_tile_transforms(LOG2W), NT = P * F;
+    static_assert(P == 64 || P == 128, "k_maskfilter: one or two wavefronts per transform");
+    // LDS (float2 slots): F padded frames | the carry (imaginary second half of the tile's last transform, H floats) | the pass tables
+    // ZAFX_LAYOUT_FT: | the mask stage: FS frames of every row, rows SP floats apart (FS = two tiles; 32 frames are one 128-byte line of a row)
+    static constexpr int FS = LOG2W >= 11 ? 16 : 32, SP = FS + 2;
+    static_assert(FS == 4 * F, "k_maskfilter: a mask stage is two tiles");
+    static constexpr int OFF_CARRY = F * C::PITCH, OFF_TW = OFF_CARRY + H / 2, OFF_STAGE = OFF_TW + C::TW;
+    static constexpr int SLOTS = OFF_STAGE + (TF ? 0 : ((H + 1) * SP + 1) / 2);
+    static constexpr size_t SMEM = (size_t)SLOTS * 8;
+    static_assert(SMEM <= (size_t)kMaxLdsBytes, "k_maskfilter: frames + carry + tables exceed LDS");
+};
+
+// One segment = blocks [seg * seg_blocks, min(n_blocks, (seg + 1) * seg_blocks)) of one clip, seg_blocks even; unit u = clip * n_segs + seg.
+// mask: element (bin k, frame t) of a clip at k * mask_pitch + t (FT) or t * (H + 1) + k (TF); clips mask_clip elements apart.
+template <int LOG2W, bool REST, bool TF>
+__global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(const float* __restrict__ x, const float* __restrict__ mask,
+                                                                           const float* __restrict__ window, const float2* __restrict__ tw_g,
+                                                                           float* __restrict__ out, long long n_samples, long long mask_clip, int mask_pitch,
+                                                                           int n_blocks, int seg_blocks, int n_segs, long long n_units, float gain) {
+    using K = MaskfilterCfg<LOG2W, TF>;
+    using C = typename K::C;
+    constexpr int E = K::E, H = K::H, W = K::W, F = K::F, P = K::P, HE = E / 2, FS = K::FS, SP = K::SP;
+    extern __shared__ float2 smem[];
+    const int tid = threadIdx.x, lane = tid & (P - 1), f = __builtin_amdgcn_readfirstlane(tid / P);   // lane: the thread's place among its transform's P
+    float2* const buf = smem + f * C::PITCH;
+    float* const carry = reinterpret_cast<float*>(smem + K::OFF_CARRY);
+    float2* const tw = smem + K::OFF_TW;
+    float* const stage = reinterpret_cast<float*>(smem + K::OFF_STAGE);   // (ZAFX_LAYOUT_FT only)
+    for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
+    __syncthreads();
+    const unsigned clip_bytes = (unsigned)(n_samples * 4);    // (the launcher keeps every clip below 2^28 samples ...
+    const unsigned mask_bytes = (unsigned)(mask_clip * 4);    //  ... which keeps its mask below 2^31 bytes)
+    const int sk = TF ? 4 : mask_pitch * 4, st = TF ? (H + 1) * 4 : 4;   // bytes from bin to bin and from frame to frame
+
+    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const long long clip = u / n_segs;
+        const int seg = (int)(u - clip * n_segs);
+        const int b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
+        const int q0 = b0 >> 1, q1 = b1 >> 1;   // transforms q0 .. q1 hold the frames b0 .. b1 that blocks [b0, b1) need
+        const float* const xc = x + clip * n_samples;
+        float* const oc = out + clip * n_samples * (REST ? 2 : 1);
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
+        const __amdgpu_buffer_rsrc_t rm = make_rsrc(mask + clip * mask_clip, mask_bytes);
+        for (int qt = q0; qt <= q1; qt += F) {
+            const int q = qt + f;            // this wave's transform: frames 2q and 2q + 1
+            const bool live = q <= q1;       // (wave-uniform)
+            float2 v[E];
+            float raw[E], ma[HE], mb[HE], mah = 0.f, mbh = 0.f;
+            const int qs = q0 + (qt - q0) / (2 * F) * (2 * F);   // first transform of the tile's mask stage (FT)
+            {
+                // samples in front of the clip and at or behind its end read as zero: the descriptor's range check does both, and a
+                // transform that is not needed reads nothing but zeros (its threads still meet the others at every frame_sync)
+                const int s0 = (2 * q - 1) * H + lane;
+                float xr[E + HE];
+#pragma unroll
+                for (int i = 0; i < E + HE; ++i) xr[i] = buf_load_f32(rs, live ? (s0 + P * i) * 4 : -4);
+                // the mask: TF this lane's pairs, in flight under the forward transform; FT the stage of this tile and the next.  Frames beyond
+                // the clip's last (n_blocks) have none: the offset -4 reads zero, as does everything outside the clip's mask.
+                if constexpr (TF) {
+                    const bool has_a = live && 2 * q <= n_blocks, has_b = live && 2 * q + 1 <= n_blocks;
+                    const int m0 = lane * sk + 2 * q * st;
+#pragma unroll
+                    for (int m = 0; m < HE; ++m) {
+                        ma[m] = buf_load_f32(rm, has_a ? m0 + P * m * sk : -4);
+                        mb[m] = buf_load_f32(rm, has_b ? m0 + P * m * sk + st : -4);
+                    }
+                    if (lane == 0) {   // bin H
+                        mah = buf_load_f32(rm, has_a ? H * sk + 2 * q * st : -4);
+                        mbh = buf_load_f32(rm, has_b ? H * sk + 2 * q * st + st : -4);
+                    }
+                } else if (qt == qs) {   // (uniform) FT: the whole workgroup fetches frames 2 qs .. 2 qs + FS - 1 of every row, FS lanes to a row
+                    constexpr int NL = ((H + 1) * FS + K::NT - 1) / K::NT;
+                    float sr[NL];
+#pragma unroll
+                    for (int i = 0; i < NL; ++i) {
+                        const int e = tid + K::NT * i, r = e / FS, c = e % FS;
+                        sr[i] = buf_load_f32(rm, r <= H && 2 * qs + c <= n_blocks ? r * sk + (2 * qs + c) * 4 : -4);
+                    }
+#pragma unroll
+                    for (int i = 0; i < NL; ++i) {
+                        const int e = tid + K::NT * i, r = e / FS, c = e % FS;
+                        if (r <= H) stage[r * SP + c] = sr[i];
+                    }
+                    lds_barrier();   // the stage lies in LDS (its last readers met at barrier A of the tile before)
+                }
+#pragma unroll
+                for (int i = 0; i < E; ++i) {
+                    const float wv = window[lane + P * i];
+                    v[i] = make_float2(xr[i] * wv, xr[i + HE] * wv);
+                }
+                if constexpr (REST) {
+#pragma unroll
+                    for (int i = 0; i < E; ++i) raw[i] = xr[i];   // the inputs of blocks 2q - 1 (i < HE) and 2q, which this wave writes
+                }
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+                if constexpr (!TF) {   // this transform's two columns of the stage (a frame beyond the clip's last was staged as 0)
+                    const float* const col = stage + 2 * (q - qs);
+#pragma unroll
+                    for (int m = 0; m < HE; ++m) {
+                        const float2 mm = *reinterpret_cast<const float2*>(col + (lane + P * m) * SP);
+                        ma[m] = mm.x, mb[m] = mm.y;
+                    }
+                    if (lane == 0) mah = col[H * SP], mbh = col[H * SP + 1];
+                }
+                // pairs (k, W - k), k = lane + P m < H; k = 0 pairs with itself, and lane 0 takes k = H as well
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    const int k = lane + P * m, kn = (W - k) & (W - 1);
+                    const int pk = phys_t<C::PS>(k), pn = phys_t<C::PS>(kn);
+                    float2 ck, cn;
+                    maskfilter_pair(buf[pk], buf[pn], ma[m], mb[m], ck, cn);
+                    buf[pk] = center_swap(ck);
+                    buf[pn] = center_swap(cn);
+                }
+                if (lane == 0) {
+                    const int ph = phys_t<C::PS>(H);
+                    float2 ck, cn;
+                    maskfilter_pair(buf[ph], buf[ph], mah, mbh, ck, cn);
+                    buf[ph] = center_swap(ck);
+                }
+                frame_sync<P>();
+                regs_read<LOG2W, K::LOG2E>(v, buf, lane);
+                frame_sync<P>();
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+            }
+            lds_barrier();   // A: every transform of the tile lies in LDS, swapped: .y = masked frame 2q, .x = masked frame 2q + 1
+            const bool writes_odd = live && q > q0;          // block 2q - 1 = second half of frame 2q - 1 + first half of frame 2q
+            const bool writes_even = live && 2 * q < b1;     // block 2q     = second half of frame 2q + first half of frame 2q + 1
+            const bool hands_on = f == F - 1 && live && q < q1;   // the tile's last transform: its imaginary second half is the next tile's carry
+            float yo[HE], ye[HE], keep[HE];
+            if (writes_odd) {
+                const float2* const prev = f > 0 ? buf - C::PITCH : nullptr;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    const int n = lane + P * i;
+                    const float a = f > 0 ? prev[phys_t<C::PS>(H + n)].x : carry[n];
+                    yo[i] = (a + buf[phys_t<C::PS>(n)].y) * gain;
+                }
+            }
+            if (writes_even) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    const int n = lane + P * i;
+                    ye[i] = (buf[phys_t<C::PS>(H + n)].y + buf[phys_t<C::PS>(n)].x) * gain;
+                }
+            }
+            if (hands_on) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) keep[i] = buf[phys_t<C::PS>(H + lane + P * i)].x;
+            }
+            lds_barrier();   // B: the frames and the carry have been read
+            if (hands_on) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) carry[lane + P * i] = keep[i];
+            }
+            if (writes_odd) {
+                const long long s = (long long)(2 * q - 1) * H + lane;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    if (s + P * i < n_samples) {   // nothing is written at or beyond sample N
+                        oc[s + P * i] = yo[i];
+                        if constexpr (REST) oc[n_samples + s + P * i] = raw[i] - yo[i];
+                    }
+                }
+            }
+            if (writes_even) {
+                const long long s = (long long)(2 * q) * H + lane;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    if (s + P * i < n_samples) {
+                        oc[s + P * i] = ye[i];
+                        if constexpr (REST) oc[n_samples + s + P * i] = raw[HE + i] - ye[i];
+                    }
+                }
+            }
+        }
+        lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
+    }
+}
+
+const char* maskfilter_kernel_name() { return kMaskfilterKernel; }   // (zafx_routes.hpp)
+
+// workgroups the device holds at once: what LDS admits per CU, at most 4
+template <int LOG2W, bool TF>
+static long long maskfilter_slots(const zafx_plan& pl) {
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / MaskfilterCfg<LOG2W, TF>::SMEM));
+    return (long long)pl.n_cus * per_cu;
+}
+
+template <int LOG2W, bool REST, bool TF>
+static hipError_t run_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
+    using K = MaskfilterCfg<LOG2W, TF>;
+    auto kern = k_maskfilter<LOG2W, REST, TF>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
+    pl.ran = kMaskfilterKernel;
+    const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
+    if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
+    const int64_t T = n_blocks + 1, pitch = TF ? K::H + 1 : row_pitch(pl, T);
+    const int64_t mask_clip = TF ? T * (K::H + 1) : (int64_t)(K::H + 1) * pitch;
+    // segments: whole clips when there are enough of them to load every workgroup; otherwise cut into runs of 2 F m - 2 blocks, m >= 2:
+    // such a run ends on an even block, and its F m transforms -- the halo included -- fill m tiles exactly
+    const long long slots = maskfilter_slots<LOG2W, TF>(pl);
+    long long want = n_clips >= slots ? 1 : std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
+    int64_t seg_blocks = (n_blocks + 1) & ~(int64_t)1;
+    if (want > 1) {
+        const int64_t ideal = (n_blocks + want - 1) / want;
+        const int64_t m = std::max<int64_t>(2, (ideal + 2 + 2 * K::F - 1) / (2 * K::F));
+        seg_blocks = std::min(seg_blocks, 2 * K::F * m - 2);
+    }
+    const long long segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    const long long units = segs * n_clips;
+    const long long grid = std::min<long long>(units, slots);
+    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // ifft's 1 / W, then zaf.py:241
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
+                       (long long)mask_clip, (int)pitch, (int)n_blocks, (int)seg_blocks, (int)segs, units, gain);
+    return hipGetLastError();
+}
+
+template <int LOG2W>
+static hipError_t run_maskfilter_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
+    const bool rest = pl.kind == ZAFX_MASKFILTER_REST, tf = pl.layout == ZAFX_LAYOUT_TF;
+    if (rest) return tf ? run_maskfilter<LOG2W, true, true>(pl, x, mask, out, n_clips, n_samples) : run_maskfilter<LOG2W, true, false>(pl, x, mask, out, n_clips, n_samples);
+    return tf ? run_maskfilter<LOG2W, false, true>(pl, x, mask, out, n_clips, n_samples) : run_maskfilter<LOG2W, false, false>(pl, x, mask, out, n_clips, n_samples);
+}
+
+hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
+    if (maskfilter_clip_refused(route_call(pl, x, out, n_clips, n_samples, 0))) {
+        set_error("mask filter: clips of 2^28 samples and more are not supported");
+        return hipErrorInvalidValue;
+    }
+    switch (pl.log2nf) {   // log2 of the complex FFT length = log2(W): two frames are one W-point transform
+        case 8: return run_maskfilter_kind<8>(pl, x, mask, out, n_clips, n_samples);
+        case 9: return run_maskfilter_kind<9>(pl, x, mask, out, n_clips, n_samples);
+        case 10: return run_maskfilter_kind<10>(pl, x, mask, out, n_clips, n_samples);
+        case 11: return run_maskfilter_kind<11>(pl, x, mask, out, n_clips, n_samples);
+    }
+    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return hipErrorInvalidValue;
+}
+
+}  // namespace zafx

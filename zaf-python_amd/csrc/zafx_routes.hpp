@@ -143,6 +143,7 @@ constexpr const char* kImdctKernels[] = {"k_imdct_q", "k_imdct"};
 constexpr const char* kMelKernels[] = {"k_mel2", "k_mel", "k_mel_ft16b", "k_melfb"};
 constexpr const char* kCqtKernel = "k_cqt";
 constexpr const char* kCenterKernel = "k_center";
+constexpr const char* kMaskfilterKernel = "k_maskfilter";
 constexpr const char* kernel_name(StftRoute r) { return kStftKernels[(int)r]; }
 constexpr const char* kernel_name(IstftRoute r) { return kIstftKernels[(int)r]; }
 constexpr const char* kernel_name(MdctRoute r) { return kMdctKernels[(int)r]; }
@@ -434,5 +435,6 @@ inline bool mdct_pcm_direct_ok(const RouteCall& c) {
 // refusals: a clip is addressed through one buffer descriptor with 32-bit byte offsets
 inline bool cqt_clip_refused(const RouteCall& c) { return c.n >= (1LL << 29); }
 inline bool center_clip_refused(const RouteCall& c) { return c.n >= (1LL << 28); }   // (sample frames)
+inline bool maskfilter_clip_refused(const RouteCall& c) { return c.n >= (1LL << 28); }   // (samples; the clip's mask then stays below 2^31 bytes)
 
 }  // namespace zafx

@@ -11,11 +11,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # enum zafx_kind
 STFT, ISTFT, MDCT, IMDCT, MEL, MFCC, CQT, CHROMA, LINEAR, DCT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 CENTER, CENTER_SIDES = 11, 12   # stereo (B, N, 2) -> center (B, N, 2) / center and sides (B, 2, N, 2)
+MASKFILTER, MASKFILTER_REST = 13, 14   # mono (B, N) and a real mask (B, W/2+1, T) -> filtered (B, N) / filtered and rest (B, 2, N)
 
 
 def center_tile_frames(window_length):
     """Frames of one tile of k_center (center_tile_frames in csrc/zafx_center.hpp): the tests place clip lengths around its multiples."""
     return 4 if window_length >= 2048 else 8
+
+
+def maskfilter_tile_transforms(window_length):
+    """Packed transforms of one tile of k_maskfilter (maskfilter_tile_transforms in csrc/zafx_maskfilter.hpp); a tile is twice as many frames."""
+    return center_tile_frames(window_length)
 # enum zafx_layout
 LAYOUT_FT, LAYOUT_TF = 0, 1
 # enum zafx_spectrum
@@ -78,6 +84,8 @@ SYMBOLS = {
     "zafx_plan_out_dims": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
     "zafx_plan_row_pitch": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
     "zafx_execute": (_i, [_vp, _vp, _vp, _i64, _i64]),
+    "zafx_execute_masked": (_i, [_vp, _vp, _vp, _vp, _i64, _i64]),
+    "zafx_plan_mask_dims": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
     "zafx_sync": (_i, [_vp]),
     "zafx_plan_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
     "zafx_execute_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _i64]),

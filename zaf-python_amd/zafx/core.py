@@ -382,7 +382,21 @@ class Plan:
             return (n_clips, rows, 2)
         if self.kind == _lib.CENTER_SIDES:   # block 0 the center, block 1 the sides
             return (n_clips, 2, rows // 2, 2)
+        if self.kind == _lib.MASKFILTER_REST:   # block 0 the filtered clip, block 1 the rest
+            return (n_clips, 2, rows // 2)
         return (n_clips, rows)
+
+    def mask_dims(self, n_in):
+        """(rows, frames) of one clip's mask under a mask filter plan (zafx_plan_mask_dims): W/2 + 1 and ceil(n_in / H) + 1."""
+        dims = (ctypes.c_int64 * 2)()
+        _lib.check(_lib.load().zafx_plan_mask_dims(self.handle, int(n_in), dims), "zafx_plan_mask_dims")
+        return int(dims[0]), int(dims[1])
+
+    def mask_shape(self, n_clips, n_in):
+        """Shape of the float32 device array execute_masked() reads its masks from: (clips, W/2 + 1, row_pitch(n_in)) in "FT" -- the last axis
+        is the pitch, the frame count rounded up to row_align -- or (clips, frames, W/2 + 1) in "TF"."""
+        rows, frames = self.mask_dims(n_in)
+        return (n_clips, rows, self.row_pitch(n_in)) if self.layout == _lib.LAYOUT_FT else (n_clips, frames, rows)
 
     @property
     def out_dtype(self):
@@ -400,6 +414,26 @@ class Plan:
     def execute(self, d_in, d_out, n_clips, n_in):
         """Enqueue on the plan's stream (asynchronous); d_in / d_out are DeviceBuffers."""
         _lib.check(_lib.load().zafx_execute(self.handle, d_in.ptr, d_out.ptr, int(n_clips), int(n_in)), "zafx_execute")
+
+    def execute_masked(self, d_in, d_mask, d_out, n_clips, n_in):
+        """Enqueue the mask filter on the plan's stream (asynchronous; zafx_execute_masked, mask filter plans only; last_kernel: k_maskfilter):
+        d_in (clips, n_in) float32 samples, d_mask float32 of mask_shape(n_clips, n_in), d_out of out_shape(n_clips, n_in).  Buffers of another
+        dtype or too small for these clips raise ValueError before anything is enqueued."""
+        n_clips, n_in = int(n_clips), int(n_in)
+        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
+            raise ValueError("execute_masked takes float32 samples, a float32 mask and a float32 output buffer")
+        if n_clips < 0 or n_in < 0:
+            raise ValueError("n_clips and n_in must not be negative")
+        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST):   # (another kind: the library says so)
+            need_mask = int(np.prod(self.mask_shape(n_clips, n_in), dtype=np.int64)) * 4
+            need_out = int(np.prod(self.out_shape(n_clips, n_in), dtype=np.int64)) * 4
+            if d_in.nbytes < n_clips * n_in * 4:
+                raise ValueError("d_in holds fewer than clips x n_in samples")
+            if d_mask.nbytes != need_mask:
+                raise ValueError(f"d_mask must hold mask_shape(n_clips, n_in) = {self.mask_shape(n_clips, n_in)} float32, got {d_mask.nbytes} bytes")
+            if d_out.nbytes < need_out:
+                raise ValueError("d_out is smaller than the plan's output for these clips")
+        _lib.check(_lib.load().zafx_execute_masked(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked")
 
     def ragged_layout(self, lengths):
         """Placement of a ragged batch's results (zafx_plan_ragged_layout) for clips of `lengths` samples: -> (out_offsets, frames, pitch), int64
@@ -1045,6 +1079,33 @@ def center_plan(window_function, device=0, sides=True):
     return _cached(key, make)
 
 
+def _maskfilter_window(window_function, step_length):
+    """Window and hop of the mask filter kinds, checked without the library: those of the center / sides kinds."""
+    w = np.asarray(window_function, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError("window_function must be 1-D")
+    if not _pow2(len(w)) or not 256 <= len(w) <= 2048:
+        raise ValueError(f"the mask filter needs a power-of-two window_length in [256, 2048], got {len(w)}")
+    if step_length is not None and _as_step(step_length) != len(w) // 2:
+        raise ValueError(f"step_length must be window_length / 2 = {len(w) // 2} for the mask filter, got {step_length}")
+    return w
+
+
+def maskfilter_plan(window_function, rest=False, layout="FT", device=0, row_align=0):
+    """Plan of the mask filter y = istft(concat(m, m[-2:0:-1]) * stft(x))[0:N] (zaf.py:185-195 with the caller's mask) at step_length =
+    window_length / 2: mono (B, N) float32 and a mask of Plan.mask_shape in, (B, N) out, or (B, 2, N) -- block 0 the filtered clip, block 1
+    the rest x - y -- with rest=True.  layout / row_align: of the mask; "TF", (B, T, W/2 + 1), is the faster one."""
+    w = _maskfilter_window(window_function, None)
+    a = _as_row_align(row_align, layout)
+    key = ("maskfilter", device, len(w), bool(rest), _LAYOUTS[layout], a, _digest(w))
+
+    def make():
+        p = Plan(_lib.MASKFILTER_REST if rest else _lib.MASKFILTER, device, window_length=len(w), step_length=len(w) // 2, layout=layout, row_align=a)
+        p.set_window(w)
+        return p
+    return _cached(key, make)
+
+
 def linear_plan(matrix, device=0):
     """y = matrix @ x for every clip (the carrier of the dct / dst transforms)."""
     m = np.ascontiguousarray(matrix, dtype=np.float64)
@@ -1163,6 +1224,44 @@ def centersides_batch(clips, window_function, step_length=None, sides=True, devi
     x = np.ascontiguousarray(a, dtype=np.float32)
     res = center_plan(w, device, sides).run_host(x, x.shape[1], out=out)
     return (res[:, 0], res[:, 1]) if sides else res
+
+
+def maskfilter_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
+    """The mask filter for a batch of mono clips in one kernel: clips (B, N) and real masks (B, W/2 + 1, T) -- (B, T, W/2 + 1) with layout "TF" --,
+    T = ceil(N / (W/2)) + 1 as zaf.stft gives -> y = istft(concat(m, m[-2:0:-1]) * stft(x))[0:N] (zaf.py:185-195), float32 (B, N); with rest=True
+    (y, rest = x - y), views of one (B, 2, N) result (which `out`, if given, is).  step_length: None or window_length / 2."""
+    w = _maskfilter_window(window_function, step_length)
+    a, m = np.asarray(clips), np.asarray(masks)
+    if a.ndim != 2:
+        raise ValueError(f"clips must be mono, (clips, samples), got shape {a.shape}")
+    if np.iscomplexobj(a) or np.iscomplexobj(m):
+        raise ValueError("clips and masks must be real")
+    n_clips, n = a.shape
+    h = len(w) // 2
+    frames, rows = (n + h - 1) // h + 1, h + 1
+    want = (n_clips, rows, frames) if _LAYOUTS[layout] == _lib.LAYOUT_FT else (n_clips, frames, rows)
+    if m.shape != want:
+        raise ValueError(f"masks must have shape {want} for clips of {n} samples (layout {layout!r}), got {m.shape}")
+    shape = (n_clips, 2, n) if rest else (n_clips, n)
+    if out is None:
+        out = np.empty(shape, np.float32)
+    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
+    if out.size:
+        plan = maskfilter_plan(w, rest, layout, device)
+        x = np.ascontiguousarray(a, dtype=np.float32)
+        d_in, d_mask, d_out = DeviceBuffer(x.shape, np.float32, device), DeviceBuffer(want, np.float32, device), DeviceBuffer(shape, np.float32, device)
+        try:
+            d_in.upload(x)
+            d_mask.upload(np.ascontiguousarray(m, dtype=np.float32))
+            with plan.lock:
+                plan.execute_masked(d_in, d_mask, d_out, n_clips, n)
+                plan.sync()
+                d_out.download(out=out)
+        finally:
+            for b in (d_in, d_mask, d_out):
+                b.free()
+    return (out[:, 0], out[:, 1]) if rest else out
 
 
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
@@ -1851,6 +1950,18 @@ def centersides(audio_signal, window_function, step_length):
         raise ValueError(f"audio_signal must be stereo, (sample frames, 2), got shape {a.shape}")
     center, sides = centersides_batch(a[None], window_function, step_length)
     return center[0].astype(np.float64), sides[0].astype(np.float64)
+
+
+def maskfilter(audio_signal, window_function, step_length, mask):
+    """zaf.istft(np.concatenate((mask, mask[-2:0:-1])) * zaf.stft(audio_signal, window_function, step_length), window_function,
+    step_length)[0:N] (zaf.py:185-195) in one call: a 1-D signal and a real (W/2 + 1, T) mask -> float64 (N,); step_length must be
+    window_length / 2 (see maskfilter_batch)."""
+    a, m = np.asarray(audio_signal), np.asarray(mask)
+    if a.ndim != 1:
+        raise ValueError(f"audio_signal must be 1-D, got shape {a.shape}")
+    if m.ndim != 2:
+        raise ValueError(f"mask must be 2-D (window_length / 2 + 1, number_times), got shape {m.shape}")
+    return maskfilter_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
 
 
 def melspectrogram(audio_signal, window_function, step_length, mel_filterbank):
