@@ -32,6 +32,7 @@
  *   ZAFX_MASKFILTER / _REST with   the same example with a mask of the caller's: stft zaf.py:176-177, the mirrored real mask times the
  *   zafx_execute_masked            spectrum :190-191 (np.concatenate((mask, mask[-2:0:-1])) * audio_stft), istft :194-195 and, _REST,
  *                                  the subtraction :198, for a mono clip in one kernel; zafx_plan_mask_dims gives the mask's shape
+ *                                  (clips of different lengths in one launch: zafx_execute_masked_ragged, zafx_plan_mask_ragged_layout)
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -257,7 +258,7 @@ int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
  * Two kinds REFUSE long clips: the call returns an error (zafx_last_error names the limit), enqueues nothing and writes nothing.
  *   ZAFX_CQT / ZAFX_CHROMA (float32)          n_in >= 2^29 samples (3.4 h at 44.1 kHz): cut the signal
  *   ZAFX_CENTER / ZAFX_CENTER_SIDES           n_in >= 2^28 sample frames (1.7 h at 44.1 kHz)
- *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked)
+ *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked; zafx_execute_masked_ragged: any clip of the batch)
  * zafx_execute_pcm reads int16 in the kernels' own loads below the same lengths (n_frames < 2^29; the MDCT: < 2^28) and converts first above them.
  * Not run at its bound by any test yet: the two-sided complex STFT at window 8192 (k_stft_ft16q takes whole-line rows only; its |X| kind is run).
  * The ragged and PCM entry points state their own per-clip limits below. */
@@ -276,6 +277,25 @@ int zafx_execute_masked(zafx_plan* plan, const void* d_in, const void* d_mask, v
 /* The mask of one clip of n_in samples under a ZAFX_MASKFILTER / _REST plan: dims[0] = rows W/2 + 1, dims[1] = frames T = ceil(n_in / H) + 1,
  * the frame count of zaf.stft (zaf.py:99-109).  zafx_plan_row_pitch(plan, n_in) gives the elements between its rows. */
 int zafx_plan_mask_dims(const zafx_plan* plan, int64_t n_in, int64_t dims[2]);
+/* Mask placement of a ragged mask-filter batch: the mask of clip i is zafx_plan_mask_dims(plan, lengths[i]) -- in ZAFX_LAYOUT_FT rows x
+ * zafx_plan_row_pitch(plan, lengths[i]), in ZAFX_LAYOUT_TF frames x rows compact -- at element mask_offsets[i] of the mask array; the masks
+ * lie back to back and mask_offsets[n_clips] = total elements.  A length of 0 has the one-frame mask zafx_plan_mask_dims gives; it is never
+ * read.  This is the layout zafx_plan_ragged_layout gives a one-sided ZAFX_SPECTRUM_MAGNITUDE ZAFX_STFT plan of the same window, layout and
+ * row_align, so the |X| a ragged STFT writes can be turned into masks where it lies. */
+int zafx_plan_mask_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64_t n_clips, int64_t* mask_offsets);
+/* The mask filter of n_clips mono clips of different lengths in ONE launch (ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only; last
+ * kernel "k_maskfilter_ragged"), enqueued on the plan's stream (asynchronous).  Offsets and lengths count float32 elements: clip i is
+ * lengths[i] samples at element in_offsets[i] of d_in -- clips may lie back to back, each is padded with zeros of its own --, its mask
+ * (shape and pitch as zafx_plan_mask_ragged_layout describes) starts at element mask_offsets[i] of d_mask -- any placement will do; the pad
+ * columns of a row and anything behind a mask's last frame are never read --, and its filtered samples go to element out_offsets[i] of
+ * d_out; under ZAFX_MASKFILTER_REST the rest follows directly behind, at out_offsets[i] + lengths[i] (the (2, N_i) block of the
+ * equal-length kind, one per clip).  Every clip's result is bit-identical to zafx_execute_masked on that clip and mask alone.  A clip of
+ * length 0 is skipped: nothing of it is read or written.  The four host arrays are copied before return.  The arrays need 4-byte alignment
+ * only.  Rejected with a message, nothing enqueued or written: a null plan, pointer or host array, n_clips < 0, another kind, negative
+ * lengths or offsets (with the clip's index), a clip of 2^28 samples or more, a window that is not set or whose sum(window[0:W:H]) is
+ * zero.  NOT checked: that the output blocks do not overlap -- placing them is the caller's business. */
+int zafx_execute_masked_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                               const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
  * with_mel included, _CQT, _CHROMA; float32 and float64).

@@ -1825,6 +1825,59 @@ int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
                                                                               (long long)units.size()));
 }
 
+// The mask of one clip of `len` samples under a mask-filter plan: the elements between its rows (FT; TF: W/2 + 1, compact) and its elements --
+// zafx_plan_mask_dims rows at zafx_plan_row_pitch in FT, frames x rows in TF.
+static void mask_block(const zafx_plan* pl, int64_t len, int64_t* elems, int64_t* pitch) {
+    const int64_t rows = pl->W / 2 + 1, frames = zafx::maskfilter_frames(len, pl->W);
+    *pitch = pl->layout == ZAFX_LAYOUT_FT ? row_pitch(*pl, frames) : rows;
+    *elems = pl->layout == ZAFX_LAYOUT_FT ? rows * *pitch : frames * rows;
+}
+
+int zafx_plan_mask_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int64_t* mask_offsets) {
+    if (!pl || !mask_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
+    if (n_clips < 0) return fail_msg("negative size");
+    if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_plan_mask_ragged_layout: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only");
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] < 0) return fail_msg("zafx_plan_mask_ragged_layout: negative length of clip " + std::to_string(i));
+    mask_offsets[0] = 0;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        int64_t elems = 0, pitch = 0;
+        mask_block(pl, lengths[i], &elems, &pitch);
+        mask_offsets[i + 1] = mask_offsets[i] + elems;
+    }
+    return 0;
+}
+
+// Ragged batches of the mask-filter kinds: the host cuts the clips into units of block pairs (maskfilter_cut_units), k_maskfilter's RAGGED form walks them.
+int zafx_execute_masked_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask, const int64_t* mask_offsets,
+                               void* d_out, const int64_t* out_offsets, int64_t n_clips) {
+    const char* const fn = "zafx_execute_masked_ragged";
+    const char* wrong_kind = !pl || is_maskfilter_kind(pl->kind) ? nullptr : "ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only (zafx_execute_ragged takes the forward kinds)";
+    bool empty = false;
+    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] >= (1LL << 28)) return fail_msg(std::string(fn) + ": clip " + std::to_string(i) + " has 2^28 samples or more (not supported)");
+    if (!pl->d_window) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    int tile_transforms = 0;
+    long long slots = 0;
+    if (!zafx::maskfilter_launch_shape(*pl, &tile_transforms, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
+    std::vector<int64_t> pitches((size_t)n_clips);
+    for (int64_t i = 0; i < n_clips; ++i) {
+        int64_t elems = 0;
+        mask_block(pl, lengths[i], &elems, &pitches[(size_t)i]);
+    }
+    // ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
+    const int per_slot = env_units_per_slot("ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot);
+    const std::vector<zafx::MaskfilterUnit> units =
+        zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, pitches.data(), n_clips, pl->W, tile_transforms, slots, per_slot);
+    ZAFX_HIP(hipSetDevice(pl->device));
+    if (int rc = upload_records(pl, units)) return rc;
+    return launch_rc(fn, zafx::launch_maskfilter_ragged(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out,
+                                                        static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size()));
+}
+
 // What zafx_execute_imdct_ragged and zafx_execute_istft_ragged differ in: both cut their blocks into units of tiles (zafx_units.hpp) that the
 // RAGGED form of their kernel walks in one launch, and run one zafx_execute per block where that form does not apply.
 struct TileRagged {

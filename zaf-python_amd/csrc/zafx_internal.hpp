@@ -374,6 +374,11 @@ const char* center_kernel_name();
 // zafx_maskfilter.hip: ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST (zafx_execute_masked); mask: (B, W/2+1, row_pitch(T)) or, ZAFX_LAYOUT_TF, (B, T, W/2+1)
 hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples);
 const char* maskfilter_kernel_name();
+// zafx_execute_masked_ragged: the tile transforms F and the workgroup slots of the plan's k_maskfilter (what maskfilter_cut_units takes), and
+// the launch of its RAGGED form over a device table of MaskfilterUnit records (zafx_units.hpp)
+struct MaskfilterUnit;
+bool maskfilter_launch_shape(const zafx_plan& pl, int* tile_transforms, long long* slots);
+hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units);
 // zafx_execute_center_ragged: the tile frames F and the workgroup slots of the plan's k_center (what center_cut_units takes), and the launch of
 // its RAGGED form on `n_units` records of the device table
 struct CenterUnit;

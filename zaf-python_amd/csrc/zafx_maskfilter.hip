@@ -20,9 +20,15 @@
 //   * A segment is an even number of blocks, so it starts on a transform of its own and needs nothing in front; one that ends on an even
 //     block runs one transform more for that block's second term (the halo).  Every transform's inputs are the clip's own samples and mask
 //     columns whatever the segment, so a clip has the same bits however it is cut.
+//   * RAGGED (zafx_execute_masked_ragged): clips of different lengths.  The walk is the same; a unit's clip -- the base and the length of its
+//     samples, the base, pitch and extent of its mask, the base of its output -- and its blocks come from the unit's record of a device
+//     table (MaskfilterUnit, zafx_units.hpp: the host cuts the batch into even-sized segments) instead of from clip * n_samples,
+//     clip * mask_clip and seg * seg_blocks.  A descriptor per clip and per mask pads every clip with zeros and ends every mask at its own
+//     last column, even where the next clip's samples or mask lie right behind.
 #include <algorithm>
 
 #include "zafx_maskfilter.hpp"
+#include "zafx_units.hpp"
 #include "zafx_internal.hpp"
 
 namespace zafx {
@@ -45,10 +51,14 @@ struct MaskfilterCfg {
 
 // One segment = blocks [seg * seg_blocks, min(n_blocks, (seg + 1) * seg_blocks)) of one clip, seg_blocks even; unit u = clip * n_segs + seg.
 // mask: element (bin k, frame t) of a clip at k * mask_pitch + t (FT) or t * (H + 1) + k (TF); clips mask_clip elements apart.
-template <int LOG2W, bool REST, bool TF>
+// RAGGED: `n_samples` carries the table of unit records (the equal-length instantiations keep their kernel arguments byte for byte, as
+// k_center's do: CenterSamplesArg), unit u is record u, and mask_clip / mask_pitch / n_blocks / seg_blocks / n_segs are not used.
+template <bool RAGGED>
+using MaskfilterSamplesArg = std::conditional_t<RAGGED, const MaskfilterUnit* __restrict__, long long>;   // (restrict: the table is read with scalar loads)
+template <int LOG2W, bool REST, bool TF, bool RAGGED>
 __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(const float* __restrict__ x, const float* __restrict__ mask,
                                                                            const float* __restrict__ window, const float2* __restrict__ tw_g,
-                                                                           float* __restrict__ out, long long n_samples, long long mask_clip, int mask_pitch,
+                                                                           float* __restrict__ out, MaskfilterSamplesArg<RAGGED> n_samples, long long mask_clip, int mask_pitch,
                                                                            int n_blocks, int seg_blocks, int n_segs, long long n_units, float gain) {
     using K = MaskfilterCfg<LOG2W, TF>;
     using C = typename K::C;
@@ -61,19 +71,57 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
     float* const stage = reinterpret_cast<float*>(smem + K::OFF_STAGE);   // (ZAFX_LAYOUT_FT only)
     for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
     __syncthreads();
-    const unsigned clip_bytes = (unsigned)(n_samples * 4);    // (the launcher keeps every clip below 2^28 samples ...
-    const unsigned mask_bytes = (unsigned)(mask_clip * 4);    //  ... which keeps its mask below 2^31 bytes)
-    const int sk = TF ? 4 : mask_pitch * 4, st = TF ? (H + 1) * 4 : 4;   // bytes from bin to bin and from frame to frame
+    // samples of the unit's clip: the kernel's argument, or (RAGGED) the field of the unit's record
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+    unsigned clip_bytes = 0, mask_bytes = 0;   // (the launcher keeps every clip below 2^28 samples, which keeps its mask below 2^31 bytes)
+    int sk = TF ? 4 : 0;                       // bytes from bin to bin ...
+    constexpr int st = TF ? (H + 1) * 4 : 4;   // ... and from frame to frame
+    if constexpr (!RAGGED) {
+        clip_bytes = (unsigned)(n_samples * 4);
+        mask_bytes = (unsigned)(mask_clip * 4);
+        sk = TF ? 4 : mask_pitch * 4;
+    }
 
-    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
-        const long long clip = u / n_segs;
-        const int seg = (int)(u - clip * n_segs);
-        const int b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
+    // RAGGED: the units come ordered by descending length, and the rounds of gridDim.x units are dealt forwards and backwards in turn, as
+    // k_center's are (still a fixed deal: nothing is claimed)
+    // (RAGGED counts its units in 32 bits -- the launcher keeps them below 2^31 --: the loop's tests are then scalar compares; 64-bit ones are
+    // vector compares that hold n_deal in a VGPR pair through the kernel, and W = 256 / TF has none to spare beside its twin's 64)
+    using Cnt = std::conditional_t<RAGGED, unsigned, long long>;
+    const Cnt n_all = (Cnt)n_units;
+    const Cnt n_deal = RAGGED ? (n_all + gridDim.x - 1) / gridDim.x * gridDim.x : n_all;
+    unsigned round = 0;
+    for (Cnt w = blockIdx.x; w < n_deal; w += gridDim.x, ++round) {
+        Cnt u = w;
+        if constexpr (RAGGED) {
+            if (round & 1) u = (round + 1) * gridDim.x - 1 - blockIdx.x;   // = (2 round + 1) gridDim.x - 1 - w
+            if (u >= n_all) continue;   // (the last round may be short; uniform)
+        }
+        MaskfilterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
+        int b0, b1;
+        const float* xc;
+        long long mo;   // the first element of the clip's mask
+        float* oc;
+        if constexpr (RAGGED) {
+            rc = n_samples[__builtin_amdgcn_readfirstlane((int)u)];   // (the launcher keeps the units below 2^31)
+            if (rc.b1 <= rc.b0) continue;                             // a value-initialised record: no blocks (uniform)
+            b0 = rc.b0, b1 = rc.b1;
+            n_blocks = (int)((rc.n_samples + H - 1) / H);
+            xc = x + rc.in_off, mo = rc.mask_off, oc = out + rc.out_off;
+            clip_bytes = (unsigned)(rc.n_samples * 4);
+            // the mask ends with its last frame's last bin: FT row H, column n_blocks; TF frame n_blocks, bin H
+            mask_bytes = TF ? (unsigned)(n_blocks + 1) * (unsigned)((H + 1) * 4) : ((unsigned)H * (unsigned)rc.mask_pitch + (unsigned)(n_blocks + 1)) * 4u;
+            if constexpr (!TF) sk = rc.mask_pitch * 4;
+        } else {
+            const long long clip = u / n_segs;
+            const int seg = (int)(u - clip * n_segs);
+            b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
+            xc = x + clip * n_samples;
+            oc = out + clip * n_samples * (REST ? 2 : 1);
+            mo = clip * mask_clip;
+        }
         const int q0 = b0 >> 1, q1 = b1 >> 1;   // transforms q0 .. q1 hold the frames b0 .. b1 that blocks [b0, b1) need
-        const float* const xc = x + clip * n_samples;
-        float* const oc = out + clip * n_samples * (REST ? 2 : 1);
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
-        const __amdgpu_buffer_rsrc_t rm = make_rsrc(mask + clip * mask_clip, mask_bytes);
+        const __amdgpu_buffer_rsrc_t rm = make_rsrc(mask + mo, mask_bytes);
         for (int qt = q0; qt <= q1; qt += F) {
             const int q = qt + f;            // this wave's transform: frames 2q and 2q + 1
             const bool live = q <= q1;       // (wave-uniform)
@@ -104,10 +152,14 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
                 } else if (qt == qs) {   // (uniform) FT: the whole workgroup fetches frames 2 qs .. 2 qs + FS - 1 of every row, FS lanes to a row
                     constexpr int NL = ((H + 1) * FS + K::NT - 1) / K::NT;
                     float sr[NL];
+                    // RAGGED: the row pitch is the unit's, and the NL products r * sk, computed once per unit, would stay in registers through
+                    // all of its tiles (30 VGPRs at W = 2048: spills).  The empty statement has them computed here, per stage.
+                    int sks = sk;
+                    if constexpr (RAGGED) asm volatile("" : "+s"(sks));
 #pragma unroll
                     for (int i = 0; i < NL; ++i) {
                         const int e = tid + K::NT * i, r = e / FS, c = e % FS;
-                        sr[i] = buf_load_f32(rm, r <= H && 2 * qs + c <= n_blocks ? r * sk + (2 * qs + c) * 4 : -4);
+                        sr[i] = buf_load_f32(rm, r <= H && 2 * qs + c <= n_blocks ? r * sks + (2 * qs + c) * 4 : -4);
                     }
 #pragma unroll
                     for (int i = 0; i < NL; ++i) {
@@ -190,9 +242,9 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
                 const long long s = (long long)(2 * q - 1) * H + lane;
 #pragma unroll
                 for (int i = 0; i < HE; ++i) {
-                    if (s + P * i < n_samples) {   // nothing is written at or beyond sample N
+                    if (s + P * i < CLIP_N) {   // nothing is written at or beyond sample N
                         oc[s + P * i] = yo[i];
-                        if constexpr (REST) oc[n_samples + s + P * i] = raw[i] - yo[i];
+                        if constexpr (REST) oc[CLIP_N + s + P * i] = raw[i] - yo[i];
                     }
                 }
             }
@@ -200,15 +252,16 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
                 const long long s = (long long)(2 * q) * H + lane;
 #pragma unroll
                 for (int i = 0; i < HE; ++i) {
-                    if (s + P * i < n_samples) {
+                    if (s + P * i < CLIP_N) {
                         oc[s + P * i] = ye[i];
-                        if constexpr (REST) oc[n_samples + s + P * i] = raw[HE + i] - ye[i];
+                        if constexpr (REST) oc[CLIP_N + s + P * i] = raw[HE + i] - ye[i];
                     }
                 }
             }
         }
         lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
     }
+#undef CLIP_N
 }
 
 const char* maskfilter_kernel_name() { return kMaskfilterKernel; }   // (zafx_routes.hpp)
@@ -223,7 +276,7 @@ static long long maskfilter_slots(const zafx_plan& pl) {
 template <int LOG2W, bool REST, bool TF>
 static hipError_t run_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
     using K = MaskfilterCfg<LOG2W, TF>;
-    auto kern = k_maskfilter<LOG2W, REST, TF>;
+    auto kern = k_maskfilter<LOG2W, REST, TF, false>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
     pl.ran = kMaskfilterKernel;
     const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
@@ -266,6 +319,59 @@ hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* m
         case 9: return run_maskfilter_kind<9>(pl, x, mask, out, n_clips, n_samples);
         case 10: return run_maskfilter_kind<10>(pl, x, mask, out, n_clips, n_samples);
         case 11: return run_maskfilter_kind<11>(pl, x, mask, out, n_clips, n_samples);
+    }
+    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------
+// ragged batches (zafx_execute_masked_ragged): the units come cut and ordered from the host (maskfilter_cut_units)
+// ---------------------------------------------------------------------------------
+static const char* const kMaskfilterRaggedName = "k_maskfilter_ragged";
+
+template <int LOG2W, bool REST, bool TF>
+static hipError_t run_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
+    using K = MaskfilterCfg<LOG2W, TF>;
+    auto kern = k_maskfilter<LOG2W, REST, TF, true>;
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
+    pl.ran = kMaskfilterRaggedName;
+    if (n_units <= 0) return hipSuccess;
+    const long long grid = std::min<long long>(n_units, maskfilter_slots<LOG2W, TF>(pl));
+    const float gain = 1.f / ((float)K::W * pl.cola_gain);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, 0, 0, 0, 0, n_units, gain);
+    return hipGetLastError();
+}
+
+template <int LOG2W>
+static hipError_t run_maskfilter_ragged_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
+    const bool rest = pl.kind == ZAFX_MASKFILTER_REST, tf = pl.layout == ZAFX_LAYOUT_TF;
+    if (rest) return tf ? run_maskfilter_ragged<LOG2W, true, true>(pl, x, mask, out, d_units, n_units) : run_maskfilter_ragged<LOG2W, true, false>(pl, x, mask, out, d_units, n_units);
+    return tf ? run_maskfilter_ragged<LOG2W, false, true>(pl, x, mask, out, d_units, n_units) : run_maskfilter_ragged<LOG2W, false, false>(pl, x, mask, out, d_units, n_units);
+}
+
+bool maskfilter_launch_shape(const zafx_plan& pl, int* tile_transforms, long long* slots) {
+    const bool tf = pl.layout == ZAFX_LAYOUT_TF;
+    switch (pl.log2nf) {
+        case 8: *slots = tf ? maskfilter_slots<8, true>(pl) : maskfilter_slots<8, false>(pl); break;
+        case 9: *slots = tf ? maskfilter_slots<9, true>(pl) : maskfilter_slots<9, false>(pl); break;
+        case 10: *slots = tf ? maskfilter_slots<10, true>(pl) : maskfilter_slots<10, false>(pl); break;
+        case 11: *slots = tf ? maskfilter_slots<11, true>(pl) : maskfilter_slots<11, false>(pl); break;
+        default: return false;
+    }
+    *tile_transforms = maskfilter_tile_transforms(pl.log2nf);
+    return true;
+}
+
+hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
+    if (n_units >= (1LL << 31)) {
+        set_error("mask filter: ragged batch too large for one launch (units >= 2^31)");
+        return hipErrorInvalidValue;
+    }
+    switch (pl.log2nf) {
+        case 8: return run_maskfilter_ragged_kind<8>(pl, x, mask, out, d_units, n_units);
+        case 9: return run_maskfilter_ragged_kind<9>(pl, x, mask, out, d_units, n_units);
+        case 10: return run_maskfilter_ragged_kind<10>(pl, x, mask, out, d_units, n_units);
+        case 11: return run_maskfilter_ragged_kind<11>(pl, x, mask, out, d_units, n_units);
     }
     set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
     return hipErrorInvalidValue;

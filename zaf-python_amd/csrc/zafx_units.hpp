@@ -1,9 +1,11 @@
 // zafx_units.hpp -- a ragged batch cut into the units a RAGGED kernel form walks: k_center's (zafx_center.hip, zafx_execute_center_ragged),
-// k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged) and k_istft_ft16's (zafx_stft.hip, zafx_execute_istft_ragged).
+// k_maskfilter's (zafx_maskfilter.hip, zafx_execute_masked_ragged), k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged) and k_istft_ft16's
+// (zafx_stft.hip, zafx_execute_istft_ragged).
 //
-// A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, tiles of `tile_frames` frames for k_imdct and k_istft_ft16.  One
-// unit = pieces [a, b) of one clip.  A unit that does not start its clip pays a fixed entry cost -- k_center a halo frame, k_imdct and
-// k_istft_ft16 the tile in front of it in carry-only mode -- and for that gives the same bits wherever it starts.
+// A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, pairs of such blocks (one packed transform) for k_maskfilter, tiles
+// of `tile_frames` frames for k_imdct and k_istft_ft16.  One unit = pieces [a, b) of one clip.  A unit that does not start its clip pays a fixed
+// entry cost -- k_center a halo frame, k_imdct and k_istft_ft16 the tile in front of it in carry-only mode; k_maskfilter's pays at its END, the
+// halo transform behind an even last block -- and for that gives the same bits wherever it starts.
 //
 // The rule (cut_segments): one segment length S in pieces for the whole batch,
 //     S = max(floor, ceil(total pieces / (per_slot x workgroup slots)));
@@ -17,10 +19,11 @@
 // m (S - 1) <= n (S - m), and a cut clip has n >= S + 1, so from m (S - 1) <= (S + 1) (S - m), which is S >= 2 m - 1.  S = 2 m - 2 is too
 // small: a clip of 2 m - 1 pieces would be cut into m and m - 1.  So floor = 2 m - 1:
 //     k_center: m = 2 F - 1 blocks, the two tiles of F frames that are the floor of the equal-length launch: floor = 2 (2 F - 1) - 1 = 4 F - 3;
+//     k_maskfilter: m = 2 F - 1 block pairs, with the halo transform two tiles of F transforms:             floor = 2 (2 F - 1) - 1 = 4 F - 3;
 //     k_imdct:  m = 2 tiles:                                                                               floor = 2 x 2 - 1 = 3;
 //     k_istft_ft16: the carry-only tile transforms at most `halo` < 16 of its 16 frames, m = 2 tiles:      floor = 2 x 2 - 1 = 3.
 //
-// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,tile}_units_emu.cpp and the host layer's sanitizer build.
+// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,maskfilter,tile}_units_emu.cpp and the host layer's sanitizer build.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -107,6 +110,37 @@ inline std::vector<CenterUnit> center_cut_units(const int64_t* lengths, const in
     for (const Segment& s : cut_segments(counts.data(), n_clips, 4LL * F - 3, slots, per_slot))
         units.push_back({in_offsets ? (long long)in_offsets[s.clip] : 0LL, (long long)lengths[s.clip], out_offsets ? (long long)out_offsets[s.clip] : 0LL,
                          (int)s.a, (int)s.b});
+    return units;
+}
+
+// ---- k_maskfilter: pairs of blocks.  One record of the device table.  Offsets and lengths in float32 elements.  The kernel deals the rounds itself.
+// The piece is one packed transform's two blocks: a clip of n_blocks = ceil(n / H) blocks has ceil(n_blocks / 2) pieces, and the segment of
+// pieces [a, b) is blocks [2 a, min(n_blocks, 2 b)) -- every segment starts on an even block, which the kernel requires, and all but a clip's
+// last end on one (those run one transform more, the halo).  m = 2 F - 1 pieces: with the halo two full tiles of F transforms, the floor of
+// the equal-length launch; floor of S = 2 m - 1 = 4 F - 3, as for k_center.
+struct MaskfilterUnit {
+    long long in_off, n_samples, out_off, mask_off;   // the unit's CLIP: its first sample in the input, its length, its first sample in the output, the first element of its mask
+    int b0, b1;                                       // the unit: blocks [b0, b1) of that clip, b0 even
+    int mask_pitch, pad_;                             // elements between the rows of the clip's mask (ZAFX_LAYOUT_FT; TF masks are compact: not used)
+};
+static_assert(sizeof(MaskfilterUnit) == 48 && alignof(MaskfilterUnit) == 8, "MaskfilterUnit: the layout the host writes");
+
+constexpr int kMaskfilterUnitsPerSlot = 8;   // units per workgroup slot the segment length aims at (where the batch has the pieces); measured: DESIGN.md 4.12 (k_center's 12 costs 2 %)
+
+inline long long maskfilter_pieces(long long n_samples, int W) { return (center_blocks(n_samples, W) + 1) / 2; }
+
+// in_offsets / out_offsets / mask_offsets / mask_pitches: null = 0 for every clip.
+inline std::vector<MaskfilterUnit> maskfilter_cut_units(const int64_t* lengths, const int64_t* in_offsets, const int64_t* out_offsets, const int64_t* mask_offsets,
+                                                        const int64_t* mask_pitches, int64_t n_clips, int W, int F, long long slots,
+                                                        int per_slot = kMaskfilterUnitsPerSlot) {
+    const auto counts = piece_counts(lengths, n_clips, [W](long long n) { return maskfilter_pieces(n, W); });
+    std::vector<MaskfilterUnit> units;
+    for (const Segment& s : cut_segments(counts.data(), n_clips, 4LL * F - 3, slots, per_slot)) {
+        const long long n_blocks = center_blocks((long long)lengths[s.clip], W);
+        units.push_back({in_offsets ? (long long)in_offsets[s.clip] : 0LL, (long long)lengths[s.clip], out_offsets ? (long long)out_offsets[s.clip] : 0LL,
+                         mask_offsets ? (long long)mask_offsets[s.clip] : 0LL, (int)(2 * s.a), (int)std::min(n_blocks, 2 * s.b),
+                         mask_pitches ? (int)mask_pitches[s.clip] : 0, 0});
+    }
     return units;
 }
 

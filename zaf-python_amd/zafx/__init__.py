@@ -11,6 +11,8 @@ The center / sides example of zaf.istft's docstring (stereo STFT, masks, ISTFT, 
     centersides_ragged (a sequence of (N_i, 2) clips of different lengths in one launch), pack_ragged_stereo, Plan.execute_center_ragged
 The same with a mask of the caller's (STFT, real mask, ISTFT of mono clips in one kernel; zaf.py:185-195):
     maskfilter ((N,), (W/2+1, T) -> (N,)), maskfilter_batch ((B, N), (B, W/2+1, T) float32), maskfilter_plan, Plan.execute_masked / Plan.mask_shape
+    maskfilter_ragged (sequences of (N_i,) clips and (W/2+1, T_i) masks of different lengths in one launch), pack_ragged_masks,
+    Plan.mask_ragged_layout / Plan.execute_masked_ragged
 Batched extension ((clips, samples) in, float32 / complex64 out):
     stft_batch, istft_batch, mdct_batch, imdct_batch, melspectrogram_batch, mfcc_batch,
     cqtspectrogram_batch, cqtchromagram_batch, dct_batch, dst_batch, mel_mfcc_batch (melspectrogram + mfcc from one set of transforms);
@@ -36,7 +38,7 @@ from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersid
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,
                    get_precision, set_precision, stft, stft_batch, stft_pcm_batch, stft_plan, mdct_pcm_batch, melspectrogram_pcm_batch, mfcc_pcm_batch,
                    cqtspectrogram_pcm_batch, cqtchromagram_pcm_batch, mel_mfcc_batch, mel_mfcc_pcm_batch, mel_mfcc_supported, set_row_padding, get_row_padding,
-                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, imdct_ragged, istft_ragged,
+                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, maskfilter_ragged, pack_ragged_masks, imdct_ragged, istft_ragged,
                    stft_pcm_ragged, mdct_pcm_ragged, melspectrogram_pcm_ragged, mfcc_pcm_ragged, mel_mfcc_pcm_ragged, pack_ragged_pcm)
 from .launch import Rendezvous, rank_env, spawn_ranks
 from .shard import clip_range, run_sharded, shard_sizes

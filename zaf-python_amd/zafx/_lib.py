@@ -86,6 +86,8 @@ SYMBOLS = {
     "zafx_execute": (_i, [_vp, _vp, _vp, _i64, _i64]),
     "zafx_execute_masked": (_i, [_vp, _vp, _vp, _vp, _i64, _i64]),
     "zafx_plan_mask_dims": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
+    "zafx_plan_mask_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
+    "zafx_execute_masked_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
     "zafx_sync": (_i, [_vp]),
     "zafx_plan_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
     "zafx_execute_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _i64]),

@@ -487,6 +487,50 @@ class Plan:
         _lib.check(_lib.load().zafx_execute_center_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_out.ptr, _i64p(out_offsets),
                                                           len(lengths)), "zafx_execute_center_ragged")
 
+    def mask_ragged_layout(self, lengths):
+        """Placement of a ragged mask-filter batch's masks (zafx_plan_mask_ragged_layout) for clips of `lengths` samples: -> mask_offsets, int64
+        of len(lengths) + 1.  Clip i's mask -- mask_dims(lengths[i]) rows at row_pitch(lengths[i]) in "FT", frames x rows compact in "TF" --
+        starts at element mask_offsets[i] of the mask array, the masks lie back to back and mask_offsets[-1] counts the elements in all: the
+        layout ragged_layout gives a one-sided magnitude STFT plan of the same window, layout and row_align."""
+        lengths = _as_lengths(lengths)
+        offs = np.zeros(len(lengths) + 1, np.int64)
+        _lib.check(_lib.load().zafx_plan_mask_ragged_layout(self.handle, _i64p(lengths), len(lengths), _i64p(offs)), "zafx_plan_mask_ragged_layout")
+        return offs
+
+    def execute_masked_ragged(self, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets):
+        """Enqueue the mask filter of mono clips of different lengths as one launch on the plan's stream (asynchronous;
+        zafx_execute_masked_ragged, mask filter plans only; last_kernel: k_maskfilter_ragged).  Offsets and lengths count float32 elements:
+        clip i is lengths[i] samples at element in_offsets[i] of d_in, its mask (shape and pitch as in mask_ragged_layout) starts at element
+        mask_offsets[i] of d_mask, its filtered samples go to element out_offsets[i] of d_out and, for a plan with rest, the rest directly
+        behind.  mask_offsets may carry the total mask_ragged_layout appends.  Output blocks that overlap are not detected."""
+        in_offsets, lengths, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths"), _as_int64(out_offsets, "out_offsets")
+        mask_offsets = _as_int64(mask_offsets, "mask_offsets")
+        if len(mask_offsets) == len(lengths) + 1:
+            mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
+        if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
+            raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
+        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
+            raise ValueError("execute_masked_ragged takes float32 samples, a float32 mask and a float32 output buffer")
+        blocks = 2 if self.kind == _lib.MASKFILTER_REST else 1
+        if (self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and len(lengths)   # (another kind, negative values: the library says so)
+                and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0):
+            h = int(self.params.window_length) // 2
+            frames = (lengths + h - 1) // h + 1
+            if self.layout == _lib.LAYOUT_FT:   # the last element the kernel may read: row H, the clip's last frame
+                a = max(self.row_align, 1)
+                mask_ends = mask_offsets + h * ((frames + a - 1) // a * a) + frames
+            else:
+                mask_ends = mask_offsets + frames * (h + 1)
+            live = lengths > 0   # (a clip of length 0 is skipped: its mask is never read)
+            if int((in_offsets + lengths).max()) * 4 > d_in.nbytes:
+                raise ValueError("a clip reaches past the end of d_in")
+            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
+                raise ValueError("a clip's mask reaches past the end of d_mask")
+            if int((out_offsets + blocks * lengths).max()) * 4 > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_masked_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
+                                                          d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_ragged")
+
     def execute_imdct_ragged(self, d_coefs, in_offsets, frames, d_out, out_offsets):
         """Enqueue the IMDCT of coefficient blocks of different frame counts on the plan's stream (asynchronous; zafx_execute_imdct_ragged,
         inverse MDCT plans only).  Block i starts at element in_offsets[i] of d_coefs: W/2 rows of frames[i] coefficients at the pitch
@@ -1754,6 +1798,62 @@ def centersides_ragged(clips, window_function, step_length=None, sides=True, dev
     out_offsets = blocks * in_offsets
     res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: plan.execute_center_ragged(d_in, in_offsets, lengths, d_out, out_offsets))
     if not sides:
+        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+
+
+def pack_ragged_masks(masks, lengths, window_length, layout="FT", row_align=0):
+    """One contiguous float32 array of a ragged batch's masks: a sequence of real (W/2 + 1, T_i) arrays -- (T_i, W/2 + 1) with layout "TF" --,
+    T_i = ceil(lengths[i] / (W/2)) + 1 -> (packed 1-D, mask_offsets of len(lengths) + 1), the layout of Plan.mask_ragged_layout for a plan of
+    that window_length, layout and row_align: the masks back to back, "FT" rows at the frame count rounded up to row_align (the pad columns
+    are zeros).  A mask of another shape raises ValueError with the clip's index."""
+    lengths = _as_lengths(lengths)
+    w, ft = int(window_length), _LAYOUTS[layout] == _lib.LAYOUT_FT
+    a = max(_as_row_align(row_align, layout), 1)
+    h = w // 2
+    arrays = _as_ragged_items(masks, 2, "ragged mask batch", "2-D masks", "mask", empty_ok=True)
+    if len(arrays) != len(lengths):
+        raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
+    frames = (lengths + h - 1) // h + 1
+    pitch = (frames + a - 1) // a * a if ft else np.full(len(lengths), h + 1, np.int64)
+    offsets = np.zeros(len(lengths) + 1, np.int64)
+    offsets[1:] = np.cumsum((h + 1) * pitch if ft else frames * (h + 1))
+    packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
+    for i, (m, o, t, p) in enumerate(zip(arrays, offsets.tolist(), frames.tolist(), pitch.tolist())):
+        want = (h + 1, t) if ft else (t, h + 1)
+        if m.shape != want:
+            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} samples (layout {layout!r}), got {m.shape}")
+        if ft:
+            packed[o:o + (h + 1) * p].reshape(h + 1, p)[:, :t] = m
+        else:
+            packed[o:o + t * (h + 1)] = np.ravel(m)
+    return packed, offsets
+
+
+def maskfilter_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
+    """maskfilter_batch of mono clips of different lengths in one launch: a sequence of 1-D real clips and one of real masks, (W/2 + 1, T_i) --
+    (T_i, W/2 + 1) with layout "TF" --, T_i = ceil(N_i / (W/2)) + 1 -> a list of float32 (N_i,) arrays, or of (y_i, rest_i) pairs with
+    rest=True, each a view of the one result buffer; every clip's result has the bits maskfilter_batch gives for that clip alone.  One upload
+    each of clips and masks, one launch (k_maskfilter_ragged), one download.  Window and step_length as in maskfilter_batch."""
+    w = _maskfilter_window(window_function, step_length)
+    arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
+    lengths = np.array([len(a) for a in arrays], np.int64)
+    m, mask_offsets = pack_ragged_masks(masks, lengths, len(w), layout)
+    in_offsets, total = _back_to_back(lengths)   # back to back: the kernel pads every clip through a descriptor of its own
+    x = np.empty(max(total, 1), np.float32)
+    for a, o in zip(arrays, in_offsets.tolist()):
+        x[o:o + len(a)] = a
+    plan = maskfilter_plan(w, rest, layout, device)
+    blocks = 2 if rest else 1
+    out_offsets = blocks * in_offsets
+    d_mask = DeviceBuffer(m.shape, np.float32, device)
+    try:
+        d_mask.upload(m)
+        res = _round_trip(plan, x, blocks * len(x),
+                          lambda d_in, d_out: plan.execute_masked_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets))
+    finally:
+        d_mask.free()
+    if not rest:
         return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
 
