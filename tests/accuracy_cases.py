@@ -1,11 +1,12 @@
-"""The cases of tests/test_gpu_accuracy.py and tests/test_accuracy_host.py: each catalogue case (tests/const_probe.py, tests/route_cases.py)
-and the ones added here as three pieces of host arithmetic -- the reference, the yardstick (tests/plain.py at the kernel's precision) and
+"""The cases of tests/test_gpu_accuracy.py and tests/test_accuracy_host.py: each catalogue case (tests/const_probe.py, tests/route_cases.py,
+tests/linear_cases.py) and the ones added here as three pieces of host arithmetic -- the reference, the yardstick (tests/plain.py at the kernel's precision) and
 the way a result is split for tests/accuracy.py.  Nothing here touches the GPU.
 
 Reference: the pinned float64 oracle for a float32 case; tests/plain.py at long double for a float64 one."""
 import numpy as np
 
 import const_probe as cp
+import linear_cases as lc
 import plain
 import route_cases as rc
 from oracle import zaf_oracle as orc
@@ -212,6 +213,29 @@ def dct_reference(x, t, sine):
 
 def dct_plain(x, t, sine, dtype):
     return list((plain.dst if sine else plain.dct)(x, t, dtype))
+
+
+# ------------------------------------------------------------------------------------------------ tests/linear_cases.py
+# The table's cases and the dense dct-II at N = 8224, judged against plain.linear_chain: ONE k-ordered float32 chain per output, which is what
+# both kernels of zafx_linear.hip compute (OWN_FACTORS above) -- at rows of thousands of columns np.matmul lies 4 ... 9 times BELOW any
+# single chain (blocked partial sums), past MAX_FACTOR, and is no yardstick for them.  Family factors, no entry in OWN_FACTORS; const/linear
+# keeps np.matmul and its own factor.
+DCT2_DENSE = "dct2_%d" % lc.DCT_N
+LINEAR_NAMES = [lc.name_of(c) for c in lc.CASES] + [DCT2_DENSE]
+
+
+def linear_case(name):
+    """-> (every clip of the launch, the float32 matrix, the judged clips' indices, their float64 reference, the kernel of the launch).
+    DCT2_DENSE: the launch is zafx.dct_batch(clips, 2); the matrix is the one core._transform_batch uploads, the reference the oracle's dct."""
+    if name == DCT2_DENSE:
+        from zafx import constants
+        x = lc.dct_clips()
+        pick = np.arange(lc.DCT_DISTINCT)
+        ref = np.stack([orc.dct(v.astype(np.float64), 2) for v in x[pick]])
+        return x, constants.dct_matrix(lc.DCT_N, 2).astype(np.float32), pick, ref, lc.kernel(lc.DCT_N, lc.DCT_N, lc.DCT_CLIPS)
+    rows, cols, count = lc.CASES[LINEAR_NAMES.index(name)]
+    x, m, pick = lc.clips(rows, cols, count), lc.matrix(rows, cols), lc.judged(count)
+    return x, m, pick, lc.reference(x[pick], m), lc.kernel(rows, cols, count)
 
 
 # Cases built like those of tests/const_probe.py.  float64 Bluestein at W = 1000: the library's only device-side trigonometry (sincospi in

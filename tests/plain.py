@@ -287,3 +287,22 @@ def linear(x, matrix, dtype):
     out = np.matmul(_clips(x, dtype), np.asarray(matrix).astype(dtype).T)
     assert out.dtype == dtype
     return out
+
+
+def linear_chain(x, matrix, dtype):
+    """(B, cols) -> (B, rows) as ONE accumulator per output, k ascending: acc = dtype(acc + dtype(a_k * b_k)).
+
+    What np.matmul computes depends on the shape (BLAS's vector form runs 8 interleaved partial sums, blocked forms more), and at rows of
+    thousands of columns its error is several times below any single chain's: no yardstick for kernels that ARE a single chain
+    (tests/accuracy_cases.py, OWN_FACTORS).  This one is: vectorised over clips and rows, a Python loop over k, the matrix transposed once
+    so that every step reads one contiguous row.  Unfused -- product and sum are rounded separately --, so slightly above a fused chain."""
+    dtype = real_of(dtype)
+    x = _clips(x, dtype)
+    mt = np.ascontiguousarray(np.asarray(matrix).astype(dtype).T)   # (cols, rows)
+    assert mt.shape[0] == x.shape[1], (mt.shape, x.shape)
+    acc = np.zeros((x.shape[0], mt.shape[1]), dtype)
+    term = np.empty_like(acc)
+    for k in range(mt.shape[0]):
+        np.multiply(x[:, k:k + 1], mt[k][None, :], out=term)
+        np.add(acc, term, out=acc)
+    return acc

@@ -9,7 +9,9 @@ per-case factor with its cause in tests/accuracy_cases.OWN_FACTORS.  The contrac
 
 The cases: constants A of every route of tests/const_probe.py but the center mask; the 92 calls of tests/route_cases.py on the very inputs
 its hashes were recorded with (kernel names held to tests/golden/call_routes.json); float64 Bluestein STFT and MDCT at W = 1000 (the only
-device-side trigonometry), k_mel's melspectrogram at W = 1024, and dct / dst of types 1-4 at 64, 1024 (k_dct), 100, 132 (k_dct_bsh) and 134 (k_dct_bs32), 8 rows each.
+device-side trigonometry), k_mel's melspectrogram at W = 1024, and dct / dst of types 1-4 at 64, 1024 (k_dct), 100, 132 (k_dct_bsh) and 134 (k_dct_bs32), 8 rows each; k_linear and k_linear128 at the shapes of tests/linear_cases.py and the dense dct-II at
+N = 8224, 16 clips each, whose yardstick is one k-ordered float32 chain per output (plain.linear_chain: what the matrix core computes; BLAS is
+4 ... 9 times below any single chain at thousands of columns).
 
 One line per case: kernel, the eight numbers, the four ratios.  ZAFX_ACCURACY_REPORT=path writes them as JSON (profiles/accuracy_ratios.json)."""
 import json
@@ -21,6 +23,7 @@ import pytest
 import accuracy as acc
 import accuracy_cases as ac
 import const_probe as cp
+import plain
 import route_cases as rc
 from conftest import GOLDEN, relerr
 
@@ -125,3 +128,21 @@ def test_dct_dst_are_as_accurate_as_a_plain_transform(zafx, name):
     ref = ac.dct_reference(x, t, sine)
     assert max(relerr(g.astype(np.float64), r) for g, r in zip(got, ref)) <= cp.TOL_FFT
     judge(f"dct/{name}", kernel, "DCT", list(got), ref, ac.dct_plain(x, t, sine, np.float32), None)
+
+
+@pytest.mark.parametrize("name", ac.LINEAR_NAMES)
+def test_linear_is_as_accurate_as_a_single_chain(zafx, name):
+    """Both kernels of zafx_linear.hip at the shapes of tests/linear_cases.py -- 1 to 128 K tiles -- and the dense dct-II at N = 8224 (257 K
+    tiles through zafx.dct_batch), the judged clips against plain.linear_chain at float32."""
+    from zafx import core
+    x, m, pick, ref, kernel = ac.linear_case(name)
+    if name == ac.DCT2_DENSE:
+        got = zafx.dct_batch(x, 2)
+        plan = core._cache[("dct_matrix", 2, x.shape[1], 0)]
+    else:
+        plan = zafx.linear_plan(m)
+        got = plan.run_host(x, x.shape[1])
+    assert plan.last_kernel == kernel and got.shape == (len(x), len(m)) and got.dtype == np.float32, (plan.last_kernel, kernel)
+    got = got[pick]
+    assert max(relerr(g.astype(np.float64), r) for g, r in zip(got, ref)) <= cp.TOL_FFT
+    judge(f"linear/{name}", kernel, "LINEAR", list(got), list(ref), list(plain.linear_chain(x[pick], m, np.float32)), None)

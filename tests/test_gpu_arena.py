@@ -41,7 +41,9 @@ Route table -- geometry: (delta_in, delta_out) -> kernel, as the launchers read 
     W 1024 / 64 filters -> k_mel; d_i % 8 (zafx_mel.hip:1263, zafx_stft.hip:2608) selects the ALIGNED template
   CQT / chromagram -> k_cqt (d_i % 8: ALIGNED template)
   DCT / DST: N 64, 1024 types 2-4 -> k_dct; N 100 types 2-4 -> k_dct_bsh; type 1 of these lengths and N 441 -> k_dct_bs32
-  LINEAR -> k_linear; 16384 x 32 on 64 clips: d_i % 16 == 0 -> k_linear128 (zafx_linear.hip:168), else k_linear
+  LINEAR -> k_linear; 16384 x 32 on 64 clips: d_i % 16 == 0 -> k_linear128 (zafx_linear.hip:168), else k_linear.  That case is ONE K tile, whole
+    row tiles and one clip tile: the tile edges of both kernels, k_linear128's double buffer and scalar stores (rows % 4 != 0, or d_o % 16 != 0)
+    run under the same harness in tests/test_gpu_linear.py (cases: tests/linear_cases.py), where the two kernels must also agree bit for bit
   int16 PCM: direct (the plan's own kernel reads int16) at d_i % 8 == 0 (MDCT: % 16), staged through k_pcm_to_float otherwise: same names
   float64: STFT d_i % 16 == 0 and d_o % 16 == 0 -> k_stft_ft8_f64 else k_stft_f64; mel / mfcc, CQT: d_i % 16 == 0 -> k_mel_ft8_f64 / k_cqt_ft_f64 else
     k_mel_f64 / k_cqt_f64; ISTFT, MDCT, IMDCT W 2048 -> k_istft_ft8_f64, k_mdct_ft16_f64, k_imdct_ft16_f64 at every offset; W 256: the generic kernels

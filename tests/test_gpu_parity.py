@@ -2197,20 +2197,26 @@ def test_host_layer_fixes_of_round_2(zafx):
     finally:
         core.DeviceBuffer._POOL_CAP = cap
         core.DeviceBuffer.drain_pool()
-    # dct: the second call finds the plan by (transform, type, N, device) without touching the matrix builder
+    # dct: the second call finds the plan by (transform, type, N, device) without touching the matrix builder.  Only the lengths without an
+    # FFT form still build a matrix (one sample; 8192 < N <= 16384 off the power-of-two grid): one sample is the cheap one.  From an empty
+    # cache the first call builds exactly once, the second not at all.
     v = synth_clip(3, 0, 300)
     first = zafx.dct(v, 2)
+    v1 = synth_clip(3, 1, 1)
     calls = []
-    orig = zafx.constants.dct_matrix if hasattr(zafx, "constants") else None
     import zafx.constants as zc
     orig = zc.dct_matrix
+    zafx.clear_plan_cache()
     try:
         def spy(n, t):
             calls.append((n, t))
             return orig(n, t)
         spy.__name__ = "dct_matrix"
         zc.dct_matrix = spy
-        assert np.array_equal(zafx.dct(v, 2), first) and not calls
+        one = zafx.dct(v1, 2)
+        assert calls == [(1, 2)] and one.shape == (1,) and abs(one[0] - float(v1[0])) <= TOL_FFT * abs(float(v1[0]))   # (the 1 x 1 dct-II is 1)
+        assert np.array_equal(zafx.dct(v1, 2), one) and calls == [(1, 2)]
+        assert np.array_equal(zafx.dct(v, 2), first) and calls == [(1, 2)]   # (length 300 has an FFT form: never a matrix)
     finally:
         zc.dct_matrix = orig
     with pytest.raises(ValueError):
