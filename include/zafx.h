@@ -32,7 +32,8 @@
  *   ZAFX_MASKFILTER / _REST with   the same example with a mask of the caller's: stft zaf.py:176-177, the mirrored real mask times the
  *   zafx_execute_masked            spectrum :190-191 (np.concatenate((mask, mask[-2:0:-1])) * audio_stft), istft :194-195 and, _REST,
  *                                  the subtraction :198, for a mono clip in one kernel; zafx_plan_mask_dims gives the mask's shape
- *                                  (clips of different lengths in one launch: zafx_execute_masked_ragged, zafx_plan_mask_ragged_layout)
+ *                                  (clips of different lengths in one launch: zafx_execute_masked_ragged, zafx_plan_mask_ragged_layout;
+ *                                  several masks per clip over one forward transform: zafx_execute_masked_stems)
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -296,6 +297,23 @@ int zafx_plan_mask_ragged_layout(const zafx_plan* plan, const int64_t* lengths, 
  * zero.  NOT checked: that the output blocks do not overlap -- placing them is the caller's business. */
 int zafx_execute_masked_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips);
+/* Stems: n_stems masks per clip over ONE forward transform, n_stems inverse transforms, in one launch (ZAFX_MASKFILTER and
+ * ZAFX_MASKFILTER_REST plans created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_stems", for n_stems == 1 too), enqueued on the
+ * plan's stream (asynchronous).  d_in (B, n_in) float32 samples; d_mask (B, n_stems, frames, rows) float32 compact, frames x rows =
+ * zafx_plan_mask_dims of ZAFX_LAYOUT_TF, the masks of a clip back to back; d_out (B, n_stems, n_in) float32: block s of a clip is that clip
+ * filtered with its mask s.  ZAFX_MASKFILTER_REST: d_out (B, n_stems + 1, n_in), and block n_stems of a clip holds the rest
+ * ((x - y_0) - y_1) - ... - y_{n_stems-1}, float32, subtracted in that order from the samples as read.  Stem s of every clip is
+ * bit-identical to zafx_execute_masked on that clip with mask s alone under a ZAFX_LAYOUT_TF plan -- whatever n_stems and the other stems'
+ * masks, wherever the clip lies in the batch, under any ZAFX_COMPUTE_UNITS --, so a mask of zeros gives exact zeros in its stem, silence
+ * gives exact zeros everywhere, and a non-finite value stays within its own clip.  The three arrays need 4-byte alignment only.  Nothing
+ * is read in front of a clip's sample 0 or from its sample n_in on, nothing behind a mask's last frame, and nothing is written at or
+ * beyond sample n_in of a block.  Rejected with a message, nothing enqueued or written: a null plan or pointer, negative sizes, another
+ * kind, a plan in ZAFX_LAYOUT_FT (the message names ZAFX_LAYOUT_TF), n_stems outside 1 .. ZAFX_MASKFILTER_MAX_STEMS, a window that is not
+ * set or whose sum(window[0:W:H]) is zero, clips of 2^28 samples and more.  zafx_execute_masked and zafx_execute_masked_ragged on the same
+ * plan are not affected. */
+#define ZAFX_MASKFILTER_MAX_STEMS 8
+int zafx_execute_masked_stems(zafx_plan* plan, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in,
+                              int32_t n_stems);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
  * with_mel included, _CQT, _CHROMA; float32 and float64).

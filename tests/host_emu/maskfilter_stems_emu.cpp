@@ -1,0 +1,122 @@
+// CPU emulation of k_maskfilter_stems (zafx_maskfilter.hip): ONE forward transform of two neighbouring frames of a mono clip, then per stem
+// the split / mask / re-pack from the kept spectrum (zafx_maskfilter.hpp), the inverse transform on the forward core, the two-term
+// overlap-add with the stem's own carry, and the rest's chain ((x - y_0) - y_1) - ... subtracted in place from the samples -- "threads" are
+// loops, arithmetic in float32 as on the device.  Per stem the values pass through the functions of tests/host_emu/maskfilter_emu.cpp in the
+// same order, so stem s has the bits that program gives with mask s alone.
+// Build: g++ -O2 -std=c++17 -DZAFX_HOST_EMU -I zaf-python_amd/csrc tests/host_emu/maskfilter_stems_emu.cpp -o maskfilter_stems_emu
+// stdin:  int32 W, int32 N, int32 S, int32 rest, float32 window[W], float32 x[N], float32 mask[S][W/2+1][T] (T = ceil(N / (W/2)) + 1)
+// stdout: float32 y[S][N], then (rest) float32 rest[N]
+#include <cstdio>
+#include <vector>
+
+#include "zafx_maskfilter.hpp"
+#include "zafx_twiddle.hpp"
+
+using namespace zafx;
+
+template <int LOG2N, int LOG2E, int LOG2NS>
+struct Runner {   // fft_frame<LOG2N, LOG2E> with the frame's threads as a loop (as tests/host_emu/fft_emu.cpp)
+    static void run(std::vector<float2>& regs, std::vector<float2>& buf, const float2* tw) {
+        using C = FftCfg<LOG2N, LOG2E>;
+        if constexpr (LOG2NS < LOG2N) {
+            constexpr int LR = pass_log2r(LOG2N - LOG2NS, LOG2E);
+            for (int p = 0; p < C::P; ++p)
+                pass_write<LOG2N, LOG2E, LOG2NS, LR>(&regs[(size_t)p * C::E], buf.data(), p, tw + twiddle_offset(LOG2N, LOG2E, LOG2NS));
+            if constexpr (LOG2NS + LR < LOG2N) {
+                for (int p = 0; p < C::P; ++p) regs_read<LOG2N, LOG2E>(&regs[(size_t)p * C::E], buf.data(), p);
+                Runner<LOG2N, LOG2E, LOG2NS + LR>::run(regs, buf, tw);
+            }
+        }
+    }
+};
+
+template <int LOG2W>
+static void run(const std::vector<float>& win, const std::vector<float>& x, const std::vector<float>& mask, long long n, int stems, bool rest,
+                std::vector<float>& out) {
+    constexpr int LOG2E = maskfilter_log2e(LOG2W);
+    using C = FftCfg<LOG2W, LOG2E>;
+    constexpr int W = C::N, H = W / 2;
+    const auto twv = build_pass_twiddles(LOG2W, LOG2E);
+    std::vector<float2> tw(twv.size() + 1);
+    for (size_t i = 0; i < twv.size(); ++i) tw[i] = make_float2(twv[i].re, twv[i].im);
+    double g = 0;
+    for (int i = 0; i < W; i += H) g += (double)win[(size_t)i];
+    const float gain = 1.f / ((float)W * (float)g);
+    const long long blocks = (n + H - 1) / H, T = maskfilter_frames(n, W);
+    auto sample = [&](long long s) { return s >= 0 && s < n ? x[(size_t)s] : 0.f; };
+    auto m = [&](int st, int k, long long t) {   // a frame beyond the last has mask 0
+        return t < T ? mask[((size_t)st * (size_t)(H + 1) + (size_t)k) * (size_t)T + (size_t)t] : 0.f;
+    };
+    std::vector<float2> regs((size_t)W), buf((size_t)C::PITCH), spec((size_t)C::PITCH);
+    std::vector<float> carry((size_t)stems * H), raw((size_t)W);
+    for (long long q = 0; 2 * q <= blocks; ++q) {   // transform q: frame 2q (from sample (2q - 1) H) + i frame 2q + 1 (from sample 2q H)
+        for (int p = 0; p < C::P; ++p)
+            for (int i = 0; i < C::E; ++i) {
+                const int k = p + i * C::P;
+                const long long s = (2 * q - 1) * H + k;
+                regs[(size_t)p * C::E + i] = make_float2(sample(s) * win[(size_t)k], sample(s + H) * win[(size_t)k]);
+                raw[(size_t)k] = sample(s);   // the inputs of blocks 2q - 1 (k < H) and 2q
+            }
+        Runner<LOG2W, LOG2E, 0>::run(regs, buf, tw.data());
+        spec = buf;   // the spectrum, kept through the stems
+        for (int st = 0; st < stems; ++st) {
+            float* const y = out.data() + (size_t)st * (size_t)n;
+            float* const cr = carry.data() + (size_t)st * H;
+            for (int k = 0; k <= H; ++k) {
+                const int pk = phys_t<C::PS>(k), pn = phys_t<C::PS>((W - k) & (W - 1));
+                float2 ck, cn;
+                maskfilter_pair(spec[(size_t)pk], spec[(size_t)pn], m(st, k, 2 * q), m(st, k, 2 * q + 1), ck, cn);
+                buf[(size_t)pk] = center_swap(ck);
+                buf[(size_t)pn] = center_swap(cn);
+            }
+            for (int p = 0; p < C::P; ++p) regs_read<LOG2W, LOG2E>(&regs[(size_t)p * C::E], buf.data(), p);
+            Runner<LOG2W, LOG2E, 0>::run(regs, buf, tw.data());
+            // swapped: .y = masked frame 2q, .x = masked frame 2q + 1
+            if (q > 0)   // block 2q - 1
+                for (int k = 0; k < H; ++k) {
+                    const long long s = (2 * q - 1) * H + k;
+                    if (s < n) {
+                        y[(size_t)s] = (cr[k] + buf[(size_t)phys_t<C::PS>(k)].y) * gain;
+                        raw[(size_t)k] = raw[(size_t)k] - y[(size_t)s];
+                    }
+                }
+            for (int k = 0; k < H; ++k) {   // block 2q
+                const long long s = 2 * q * H + k;
+                if (s < n) {
+                    y[(size_t)s] = (buf[(size_t)phys_t<C::PS>(H + k)].y + buf[(size_t)phys_t<C::PS>(k)].x) * gain;
+                    raw[(size_t)(H + k)] = raw[(size_t)(H + k)] - y[(size_t)s];
+                }
+            }
+            for (int k = 0; k < H; ++k) cr[k] = buf[(size_t)phys_t<C::PS>(H + k)].x;
+        }
+        if (rest) {
+            float* const r = out.data() + (size_t)stems * (size_t)n;
+            for (int k = 0; k < W; ++k) {
+                const long long s = (2 * q - 1) * H + k;
+                if (s >= 0 && s < n && (k >= H || q > 0)) r[(size_t)s] = raw[(size_t)k];
+            }
+        }
+    }
+}
+
+int main() {
+    int hdr[4];
+    if (fread(hdr, sizeof(int), 4, stdin) != 4) return 2;
+    const int w = hdr[0], stems = hdr[2];
+    const long long n = hdr[1];
+    const bool rest = hdr[3] != 0;
+    if (w < 2 || n < 0 || stems < 1 || stems > 8) return 3;
+    const long long frames = maskfilter_frames(n, w);
+    std::vector<float> win((size_t)w), x((size_t)n), mask((size_t)stems * (size_t)(w / 2 + 1) * (size_t)frames), out((size_t)(stems + (rest ? 1 : 0)) * (size_t)n, 0.f);
+    if (fread(win.data(), sizeof(float), win.size(), stdin) != win.size()) return 2;
+    if (fread(x.data(), sizeof(float), x.size(), stdin) != x.size()) return 2;
+    if (fread(mask.data(), sizeof(float), mask.size(), stdin) != mask.size()) return 2;
+    switch (w) {
+        case 256: run<8>(win, x, mask, n, stems, rest, out); break;
+        case 512: run<9>(win, x, mask, n, stems, rest, out); break;
+        case 1024: run<10>(win, x, mask, n, stems, rest, out); break;
+        case 2048: run<11>(win, x, mask, n, stems, rest, out); break;
+        default: return 3;
+    }
+    return fwrite(out.data(), sizeof(float), out.size(), stdout) == out.size() ? 0 : 4;
+}

@@ -1486,6 +1486,23 @@ int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, voi
     return launch_rc("zafx_execute_masked", zafx::launch_maskfilter(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in));
 }
 
+static_assert(ZAFX_MASKFILTER_MAX_STEMS == zafx::kMaskfilterMaxStems, "the header's stem bound is the launcher's");
+
+int zafx_execute_masked_stems(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t n_stems) {
+    if (!pl) return fail_msg("null plan");
+    if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_execute_masked_stems: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only");
+    if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
+    zafx::RouteCall c;   // the launcher's refusals, for an empty batch too
+    c.layout = pl->layout, c.n = n_in;
+    if (const char* why = zafx::maskfilter_stems_refusal(c, n_stems)) return fail_msg(std::string("zafx_execute_masked_stems: ") + why);
+    if (n_clips == 0) return 0;
+    if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
+    if (!pl->d_window) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    ZAFX_HIP(hipSetDevice(pl->device));
+    return launch_rc("zafx_execute_masked_stems", zafx::launch_maskfilter_stems(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in, n_stems));
+}
+
 int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in) {
     if (!pl) return fail_msg("null plan");
     if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("zafx_execute: ") + kMaskedOnly);

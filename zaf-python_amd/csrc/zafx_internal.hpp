@@ -374,6 +374,8 @@ const char* center_kernel_name();
 // zafx_maskfilter.hip: ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST (zafx_execute_masked); mask: (B, W/2+1, row_pitch(T)) or, ZAFX_LAYOUT_TF, (B, T, W/2+1)
 hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples);
 const char* maskfilter_kernel_name();
+// zafx_execute_masked_stems: mask (B, S, T, W/2+1), out (B, S, N) or, ZAFX_MASKFILTER_REST, (B, S + 1, N); refuses what maskfilter_stems_refusal names
+hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int64_t n_stems);
 // zafx_execute_masked_ragged: the tile transforms F and the workgroup slots of the plan's k_maskfilter (what maskfilter_cut_units takes), and
 // the launch of its RAGGED form over a device table of MaskfilterUnit records (zafx_units.hpp)
 struct MaskfilterUnit;

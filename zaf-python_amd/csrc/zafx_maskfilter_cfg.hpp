@@ -1,0 +1,25 @@
+// zafx_maskfilter_cfg.hpp -- the launch geometry and LDS layout of k_maskfilter (zafx_maskfilter.hip), shared with k_maskfilter_stems
+// (zafx_maskfilter_stems.hip), which runs on the same frames, carry and tables.
+#pragma once
+#include "zafx_maskfilter.hpp"
+#include "zafx_internal.hpp"
+
+namespace zafx {
+
+template <int LOG2W, bool TF>
+struct MaskfilterCfg {
+    static constexpr int LOG2E = maskfilter_log2e(LOG2W);
+    using C = FftCfg<LOG2W, LOG2E>;
+    static constexpr int W = 1 << LOG2W, H = W / 2, E = C::E, P = C::P, F = maskfilter_tile_transforms(LOG2W), NT = P * F;
+    static_assert(P == 64 || P == 128, "k_maskfilter: one or two wavefronts per transform");
+    // LDS (float2 slots): F padded frames | the carry (imaginary second half of the tile's last transform, H floats) | the pass tables
+    // ZAFX_LAYOUT_FT: | the mask stage: FS frames of every row, rows SP floats apart (FS = two tiles; 32 frames are one 128-byte line of a row)
+    static constexpr int FS = LOG2W >= 11 ? 16 : 32, SP = FS + 2;
+    static_assert(FS == 4 * F, "k_maskfilter: a mask stage is two tiles");
+    static constexpr int OFF_CARRY = F * C::PITCH, OFF_TW = OFF_CARRY + H / 2, OFF_STAGE = OFF_TW + C::TW;
+    static constexpr int SLOTS = OFF_STAGE + (TF ? 0 : ((H + 1) * SP + 1) / 2);
+    static constexpr size_t SMEM = (size_t)SLOTS * 8;
+    static_assert(SMEM <= (size_t)kMaxLdsBytes, "k_maskfilter: frames + carry + tables exceed LDS");
+};
+
+}  // namespace zafx

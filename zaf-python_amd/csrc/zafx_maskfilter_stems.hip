@@ -1,0 +1,254 @@
+// zafx_maskfilter_stems.hip -- k_maskfilter_stems: the mask filter with S masks per clip (the stems of a source separation): one STFT, S masks,
+// S ISTFTs of mono clips in one kernel (zafx_execute_masked_stems).  A translation unit of its own: k_maskfilter's instantiations
+// (zafx_maskfilter.hip) keep their registers to the last one.
+#include <algorithm>
+
+#include "zafx_maskfilter_cfg.hpp"
+
+namespace zafx {
+
+// ---------------------------------------------------------------------------------
+// stems (zafx_execute_masked_stems): S masks over one forward transform, S inverse transforms, in one kernel
+// ---------------------------------------------------------------------------------
+// k_maskfilter's plan -- segments, tiles, the samples' descriptor, the pair arithmetic, the inverse on the forward core, the two-term overlap-add,
+// the gain -- with a loop over the stems between the forward transform and the tile's end (DESIGN.md 4.12 "Stems"):
+//   * The inverse runs in place in the LDS frame and destroys the spectrum, so a lane takes the spectrum of its pairs (k, W - k) into registers
+//     behind the forward transform (2 E floats, lane 0 bin H as well) and forms every stem's masked pairs from there.  A lane is the only
+//     reader and writer of its pairs' slots, so no barrier stands between the forward transform and the first stem's pairs.
+//   * One carry per stem: carry 0 where k_maskfilter has its one, carries 1 .. S - 1 behind the pass tables (stems_smem).
+//   * Masks: (B, S, T, W/2 + 1), ZAFX_LAYOUT_TF, one descriptor per (clip, stem).  Stem 0's values are loaded in front of the forward transform as
+//     k_maskfilter's are; stem s + 1's are loaded into the same registers as soon as stem s's pairs are formed, under stem s's inverse.
+//   * Output (B, S, N); REST: (B, S + 1, N), block S = ((x - y_0) - y_1) - ... - y_{S-1}, subtracted in place from the samples as loaded.
+// Stem s of a clip has the bits k_maskfilter gives that clip with mask s alone: every value passes through the same inline functions in the same
+// order, and no stem's arithmetic reads another stem's values.
+template <int LOG2W>
+constexpr size_t maskfilter_stems_smem(int n_stems) {
+    return MaskfilterCfg<LOG2W, true>::SMEM + (size_t)(n_stems - 1) * MaskfilterCfg<LOG2W, true>::H * 4;
+}
+
+// unit u = clip * n_segs + seg as in k_maskfilter; stem s of a clip: mask at (clip * n_stems + s) * mask_clip, output at (clip * blocks_out + s) * n_samples,
+// blocks_out = n_stems + REST
+template <int LOG2W, bool REST>
+__global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter_stems(const float* __restrict__ x, const float* __restrict__ mask,
+                                                                                   const float* __restrict__ window, const float2* __restrict__ tw_g,
+                                                                                   float* __restrict__ out, long long n_samples, long long mask_clip, int n_stems,
+                                                                                   int n_blocks, int seg_blocks, int n_segs, long long n_units, float gain) {
+    using K = MaskfilterCfg<LOG2W, true>;
+    using C = typename K::C;
+    constexpr int E = K::E, H = K::H, W = K::W, F = K::F, P = K::P, HE = E / 2;
+    extern __shared__ float2 smem[];
+    const int tid = threadIdx.x, lane = tid & (P - 1), f = __builtin_amdgcn_readfirstlane(tid / P);
+    float2* const buf = smem + f * C::PITCH;
+    float* const carry0 = reinterpret_cast<float*>(smem + K::OFF_CARRY);
+    float* const carry1 = reinterpret_cast<float*>(smem + K::SLOTS) - H;   // carry s >= 1 at carry1 + s H
+    float2* const tw = smem + K::OFF_TW;
+    for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
+    __syncthreads();
+    const unsigned clip_bytes = (unsigned)(n_samples * 4), mask_bytes = (unsigned)(mask_clip * 4);   // (clips below 2^28 samples: the launcher)
+    constexpr int st = (H + 1) * 4;   // bytes from frame to frame of a mask
+    const int blocks_out = n_stems + (REST ? 1 : 0);
+
+    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const long long clip = u / n_segs;
+        const int seg = (int)(u - clip * n_segs);
+        const int b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
+        const float* const xc = x + clip * n_samples;
+        float* const oc = out + clip * blocks_out * n_samples;
+        const float* const mc = mask + clip * n_stems * mask_clip;
+        const int q0 = b0 >> 1, q1 = b1 >> 1;
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
+        for (int qt = q0; qt <= q1; qt += F) {
+            const int q = qt + f;
+            const bool live = q <= q1;   // (wave-uniform)
+            float2 v[E], zk[HE], zn[HE], zh = make_float2(0.f, 0.f);
+            float raw[E], ma[HE], mb[HE], mah = 0.f, mbh = 0.f;
+            // a frame beyond the clip's last (n_blocks) has no mask: the offset -4 reads zero, as does everything outside the stem's mask
+            const bool has_a = live && 2 * q <= n_blocks, has_b = live && 2 * q + 1 <= n_blocks;
+            const int m0 = lane * 4 + 2 * q * st;
+            auto load_mask = [&](int s) {   // stem s < n_stems (uniform)
+                const __amdgpu_buffer_rsrc_t rm = make_rsrc(mc + s * mask_clip, mask_bytes);
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    ma[m] = buf_load_f32(rm, has_a ? m0 + P * m * 4 : -4);
+                    mb[m] = buf_load_f32(rm, has_b ? m0 + P * m * 4 + st : -4);
+                }
+                if (lane == 0) {   // bin H
+                    mah = buf_load_f32(rm, has_a ? H * 4 + 2 * q * st : -4);
+                    mbh = buf_load_f32(rm, has_b ? H * 4 + 2 * q * st + st : -4);
+                }
+            };
+            {
+                const int s0 = (2 * q - 1) * H + lane;
+                float xr[E + HE];
+#pragma unroll
+                for (int i = 0; i < E + HE; ++i) xr[i] = buf_load_f32(rs, live ? (s0 + P * i) * 4 : -4);
+                load_mask(0);
+#pragma unroll
+                for (int i = 0; i < E; ++i) {
+                    const float wv = window[lane + P * i];
+                    v[i] = make_float2(xr[i] * wv, xr[i + HE] * wv);
+                }
+                if constexpr (REST) {
+#pragma unroll
+                    for (int i = 0; i < E; ++i) raw[i] = xr[i];   // the inputs of blocks 2q - 1 (i < HE) and 2q: the rest is subtracted from them in place
+                }
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+                // the spectrum of this lane's pairs (k, W - k), k = lane + P m < H, and lane 0's bin H: kept through the stems
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    const int k = lane + P * m, kn = (W - k) & (W - 1);
+                    zk[m] = buf[phys_t<C::PS>(k)];
+                    zn[m] = buf[phys_t<C::PS>(kn)];
+                }
+                if (lane == 0) zh = buf[phys_t<C::PS>(H)];
+            }
+            const bool writes_odd = live && q > q0;          // block 2q - 1
+            const bool writes_even = live && 2 * q < b1;     // block 2q
+            const bool hands_on = f == F - 1 && live && q < q1;   // the tile's last transform: its imaginary second half is the next tile's carry
+            for (int s = 0; s < n_stems; ++s) {
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    const int k = lane + P * m, kn = (W - k) & (W - 1);
+                    float2 ck, cn;
+                    maskfilter_pair(zk[m], zn[m], ma[m], mb[m], ck, cn);
+                    buf[phys_t<C::PS>(k)] = center_swap(ck);
+                    buf[phys_t<C::PS>(kn)] = center_swap(cn);
+                }
+                if (lane == 0) {
+                    float2 ck, cn;
+                    maskfilter_pair(zh, zh, mah, mbh, ck, cn);
+                    buf[phys_t<C::PS>(H)] = center_swap(ck);
+                }
+                if (s + 1 < n_stems) load_mask(s + 1);   // (uniform) the next stem's values arrive under this stem's inverse
+                frame_sync<P>();
+                regs_read<LOG2W, K::LOG2E>(v, buf, lane);
+                frame_sync<P>();
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+                lds_barrier();   // A: every transform of the tile lies in LDS, swapped: .y = masked frame 2q, .x = masked frame 2q + 1
+                float* const carry = s ? carry1 + s * H : carry0;
+                float yo[HE], ye[HE], keep[HE];
+                if (writes_odd) {
+                    const float2* const prev = f > 0 ? buf - C::PITCH : nullptr;
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) {
+                        const int n = lane + P * i;
+                        const float a = f > 0 ? prev[phys_t<C::PS>(H + n)].x : carry[n];
+                        yo[i] = (a + buf[phys_t<C::PS>(n)].y) * gain;
+                    }
+                }
+                if (writes_even) {
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) {
+                        const int n = lane + P * i;
+                        ye[i] = (buf[phys_t<C::PS>(H + n)].y + buf[phys_t<C::PS>(n)].x) * gain;
+                    }
+                }
+                if (hands_on) {
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) keep[i] = buf[phys_t<C::PS>(H + lane + P * i)].x;
+                }
+                lds_barrier();   // B: the frames and the stem's carry have been read; the next stem's pairs may overwrite the frames
+                if (hands_on) {
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) carry[lane + P * i] = keep[i];
+                }
+                float* const os = oc + (long long)s * n_samples;
+                if (writes_odd) {
+                    const long long sm = (long long)(2 * q - 1) * H + lane;
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) {
+                        if (sm + P * i < n_samples) {   // nothing is written at or beyond sample N
+                            os[sm + P * i] = yo[i];
+                            if constexpr (REST) raw[i] = raw[i] - yo[i];
+                        }
+                    }
+                }
+                if (writes_even) {
+                    const long long sm = (long long)(2 * q) * H + lane;
+#pragma unroll
+                    for (int i = 0; i < HE; ++i) {
+                        if (sm + P * i < n_samples) {
+                            os[sm + P * i] = ye[i];
+                            if constexpr (REST) raw[HE + i] = raw[HE + i] - ye[i];
+                        }
+                    }
+                }
+            }
+            if constexpr (REST) {   // block S: what the stems left of the samples
+                float* const orest = oc + (long long)n_stems * n_samples;
+                if (writes_odd) {
+                    const long long sm = (long long)(2 * q - 1) * H + lane;
+#pragma unroll
+                    for (int i = 0; i < HE; ++i)
+                        if (sm + P * i < n_samples) orest[sm + P * i] = raw[i];
+                }
+                if (writes_even) {
+                    const long long sm = (long long)(2 * q) * H + lane;
+#pragma unroll
+                    for (int i = 0; i < HE; ++i)
+                        if (sm + P * i < n_samples) orest[sm + P * i] = raw[HE + i];
+                }
+            }
+        }
+        lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
+    }
+}
+
+// workgroups the device holds at once under the stems' LDS size: what LDS admits per CU, at most 4
+template <int LOG2W>
+static long long maskfilter_stems_slots(const zafx_plan& pl, int n_stems) {
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / maskfilter_stems_smem<LOG2W>(n_stems)));
+    return (long long)pl.n_cus * per_cu;
+}
+
+template <int LOG2W, bool REST>
+static hipError_t run_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int n_stems) {
+    using K = MaskfilterCfg<LOG2W, true>;
+    static_assert(maskfilter_stems_smem<LOG2W>(kMaskfilterMaxStems) <= (size_t)kMaxLdsBytes, "k_maskfilter_stems: frames + carries + tables exceed LDS");
+    auto kern = k_maskfilter_stems<LOG2W, REST>;
+    const size_t smem = maskfilter_stems_smem<LOG2W>(n_stems);
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, smem); e != hipSuccess) return e;
+    pl.ran = kMaskfilterStemsKernel;
+    const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
+    if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
+    const int64_t mask_clip = (n_blocks + 1) * (K::H + 1);
+    // segments: run_maskfilter's rule, the slots from the stems' LDS size
+    const long long slots = maskfilter_stems_slots<LOG2W>(pl, n_stems);
+    long long want = n_clips >= slots ? 1 : std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
+    int64_t seg_blocks = (n_blocks + 1) & ~(int64_t)1;
+    if (want > 1) {
+        const int64_t ideal = (n_blocks + want - 1) / want;
+        const int64_t m = std::max<int64_t>(2, (ideal + 2 + 2 * K::F - 1) / (2 * K::F));
+        seg_blocks = std::min(seg_blocks, 2 * K::F * m - 2);
+    }
+    const long long segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    const long long units = segs * n_clips;
+    const long long grid = std::min<long long>(units, slots);
+    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // as run_maskfilter's
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), smem, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
+                       (long long)mask_clip, n_stems, (int)n_blocks, (int)seg_blocks, (int)segs, units, gain);
+    return hipGetLastError();
+}
+
+template <int LOG2W>
+static hipError_t run_maskfilter_stems_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int n_stems) {
+    return pl.kind == ZAFX_MASKFILTER_REST ? run_maskfilter_stems<LOG2W, true>(pl, x, mask, out, n_clips, n_samples, n_stems)
+                                           : run_maskfilter_stems<LOG2W, false>(pl, x, mask, out, n_clips, n_samples, n_stems);
+}
+
+hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int64_t n_stems) {
+    if (const char* why = maskfilter_stems_refusal(route_call(pl, x, out, n_clips, n_samples, 0), n_stems)) {
+        set_error(why);
+        return hipErrorInvalidValue;
+    }
+    switch (pl.log2nf) {
+        case 8: return run_maskfilter_stems_kind<8>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
+        case 9: return run_maskfilter_stems_kind<9>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
+        case 10: return run_maskfilter_stems_kind<10>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
+        case 11: return run_maskfilter_stems_kind<11>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
+    }
+    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return hipErrorInvalidValue;
+}
+
+}  // namespace zafx

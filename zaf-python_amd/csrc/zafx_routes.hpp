@@ -144,6 +144,8 @@ constexpr const char* kMelKernels[] = {"k_mel2", "k_mel", "k_mel_ft16b", "k_melf
 constexpr const char* kCqtKernel = "k_cqt";
 constexpr const char* kCenterKernel = "k_center";
 constexpr const char* kMaskfilterKernel = "k_maskfilter";
+constexpr const char* kMaskfilterStemsKernel = "k_maskfilter_stems";   // zafx_execute_masked_stems, whatever the stem count
+constexpr int kMaskfilterMaxStems = 8;                                 // (ZAFX_MASKFILTER_MAX_STEMS: a carry of W/2 floats per stem in LDS)
 constexpr const char* kernel_name(StftRoute r) { return kStftKernels[(int)r]; }
 constexpr const char* kernel_name(IstftRoute r) { return kIstftKernels[(int)r]; }
 constexpr const char* kernel_name(MdctRoute r) { return kMdctKernels[(int)r]; }
@@ -436,5 +438,13 @@ inline bool mdct_pcm_direct_ok(const RouteCall& c) {
 inline bool cqt_clip_refused(const RouteCall& c) { return c.n >= (1LL << 29); }
 inline bool center_clip_refused(const RouteCall& c) { return c.n >= (1LL << 28); }   // (sample frames)
 inline bool maskfilter_clip_refused(const RouteCall& c) { return c.n >= (1LL << 28); }   // (samples; the clip's mask then stays below 2^31 bytes)
+// zafx_execute_masked_stems: masks in ZAFX_LAYOUT_TF only (k_maskfilter's FT stage and eight carries do not fit LDS at W = 2048), 1 .. 8 stems,
+// and the clip bound of the one-mask kind -- a descriptor per (clip, stem) addresses one mask, as there.  nullptr: the call is taken.
+inline const char* maskfilter_stems_refusal(const RouteCall& c, int64_t n_stems) {
+    if (c.layout != ZAFX_LAYOUT_TF) return "mask filter stems: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)";
+    if (n_stems < 1 || n_stems > kMaskfilterMaxStems) return "mask filter stems: n_stems must be in 1 .. 8 (ZAFX_MASKFILTER_MAX_STEMS)";
+    if (maskfilter_clip_refused(c)) return "mask filter: clips of 2^28 samples and more are not supported";
+    return nullptr;
+}
 
 }  // namespace zafx

@@ -13,6 +13,8 @@ The same with a mask of the caller's (STFT, real mask, ISTFT of mono clips in on
     maskfilter ((N,), (W/2+1, T) -> (N,)), maskfilter_batch ((B, N), (B, W/2+1, T) float32), maskfilter_plan, Plan.execute_masked / Plan.mask_shape
     maskfilter_ragged (sequences of (N_i,) clips and (W/2+1, T_i) masks of different lengths in one launch), pack_ragged_masks,
     Plan.mask_ragged_layout / Plan.execute_masked_ragged
+    maskfilter_stems ((N,), (S, W/2+1, T) -> (S, N)), maskfilter_stems_batch ((B, N), (B, S, W/2+1, T) float32 -> (B, S, N)): S = 1 .. 8 masks per
+    clip over one forward transform in one launch; Plan.execute_masked_stems / Plan.stems_mask_shape / Plan.stems_out_shape
 Batched extension ((clips, samples) in, float32 / complex64 out):
     stft_batch, istft_batch, mdct_batch, imdct_batch, melspectrogram_batch, mfcc_batch,
     cqtspectrogram_batch, cqtchromagram_batch, dct_batch, dst_batch, mel_mfcc_batch (melspectrogram + mfcc from one set of transforms);
@@ -29,10 +31,10 @@ launch where the library has the kernel):
 Device-resident API: Plan, DeviceBuffer, Comm, *_plan factories, shard helpers; one process per GPU: launch.Rendezvous,
 spawn_ranks (file rendezvous + self-launcher, no torch.distributed).
 """
-from ._lib import (CENTER, CENTER_SIDES, CHROMA, CQT, DCT, IMDCT, ISTFT, LAYOUT_FT, LAYOUT_TF, LINEAR, MASKFILTER, MASKFILTER_REST, MDCT, MEL, MFCC, STFT, ZafxError,
+from ._lib import (CENTER, CENTER_SIDES, CHROMA, CQT, DCT, IMDCT, ISTFT, LAYOUT_FT, LAYOUT_TF, LINEAR, MASKFILTER, MASKFILTER_MAX_STEMS, MASKFILTER_REST, MDCT, MEL, MFCC, STFT, ZafxError,
                    center_tile_frames, device_count, device_name, library_path, maskfilter_tile_transforms)
 from .constants import cqtkernel, dct2_rows, dct_matrix, dst_matrix, hamming, kaiser_bessel_derived, melfilterbank, sine
-from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersides_batch, maskfilter, maskfilter_batch, maskfilter_plan, clear_plan_cache, cqt_plan, cqtchromagram, cqtchromagram_batch, dct, dct_batch, dst,
+from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersides_batch, maskfilter, maskfilter_batch, maskfilter_plan, maskfilter_stems, maskfilter_stems_batch, clear_plan_cache, cqt_plan, cqtchromagram, cqtchromagram_batch, dct, dct_batch, dst,
                    dst_batch, linear_plan, dct_plan, dct_fft_length,
                    cqtspectrogram, cqtspectrogram_batch, imdct, imdct_batch, istft, istft_batch, istft_plan, mdct,
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,

@@ -22,6 +22,10 @@ def center_tile_frames(window_length):
 def maskfilter_tile_transforms(window_length):
     """Packed transforms of one tile of k_maskfilter (maskfilter_tile_transforms in csrc/zafx_maskfilter.hpp); a tile is twice as many frames."""
     return center_tile_frames(window_length)
+
+
+# most masks per clip of zafx_execute_masked_stems (ZAFX_MASKFILTER_MAX_STEMS in include/zafx.h)
+MASKFILTER_MAX_STEMS = 8
 # enum zafx_layout
 LAYOUT_FT, LAYOUT_TF = 0, 1
 # enum zafx_spectrum
@@ -88,6 +92,7 @@ SYMBOLS = {
     "zafx_plan_mask_dims": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
     "zafx_plan_mask_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
     "zafx_execute_masked_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
+    "zafx_execute_masked_stems": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32]),
     "zafx_sync": (_i, [_vp]),
     "zafx_plan_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
     "zafx_execute_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _i64]),

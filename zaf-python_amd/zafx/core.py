@@ -435,6 +435,40 @@ class Plan:
                 raise ValueError("d_out is smaller than the plan's output for these clips")
         _lib.check(_lib.load().zafx_execute_masked(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked")
 
+    def stems_mask_shape(self, n_clips, n_in, n_stems):
+        """Shape of the float32 device array execute_masked_stems() reads its masks from: (clips, stems, frames, W/2 + 1) compact -- a clip's
+        masks back to back, each as a "TF" plan's mask_shape gives it."""
+        rows, frames = self.mask_dims(n_in)
+        return (int(n_clips), int(n_stems), frames, rows)
+
+    def stems_out_shape(self, n_clips, n_in, n_stems):
+        """Shape of execute_masked_stems()'s output: (clips, stems, n_in), or (clips, stems + 1, n_in) under a MASKFILTER_REST plan, whose last
+        block of a clip is the rest."""
+        return (int(n_clips), int(n_stems) + (1 if self.kind == _lib.MASKFILTER_REST else 0), int(n_in))
+
+    def execute_masked_stems(self, d_in, d_mask, d_out, n_clips, n_in, n_stems):
+        """Enqueue the mask filter with n_stems masks per clip on the plan's stream (asynchronous; zafx_execute_masked_stems, mask filter plans of
+        layout "TF" only; last_kernel: k_maskfilter_stems): one forward transform per clip, one inverse per stem.  d_in (clips, n_in) float32
+        samples, d_mask float32 of stems_mask_shape(n_clips, n_in, n_stems), d_out of stems_out_shape(n_clips, n_in, n_stems).  Stem s of a clip
+        has the bits execute_masked gives that clip with mask s alone.  Buffers of another dtype or of the wrong size raise ValueError before
+        anything is enqueued."""
+        n_clips, n_in, n_stems = int(n_clips), int(n_in), int(n_stems)
+        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
+            raise ValueError("execute_masked_stems takes float32 samples, float32 masks and a float32 output buffer")
+        if n_clips < 0 or n_in < 0:
+            raise ValueError("n_clips and n_in must not be negative")
+        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:   # (otherwise: the library says so)
+            shape = self.stems_mask_shape(n_clips, n_in, n_stems)
+            need_mask = int(np.prod(shape, dtype=np.int64)) * 4
+            need_out = int(np.prod(self.stems_out_shape(n_clips, n_in, n_stems), dtype=np.int64)) * 4
+            if d_in.nbytes < n_clips * n_in * 4:
+                raise ValueError("d_in holds fewer than clips x n_in samples")
+            if d_mask.nbytes != need_mask:
+                raise ValueError(f"d_mask must hold stems_mask_shape(n_clips, n_in, n_stems) = {shape} float32, got {d_mask.nbytes} bytes")
+            if d_out.nbytes < need_out:
+                raise ValueError("d_out is smaller than the plan's output for these clips and stems")
+        _lib.check(_lib.load().zafx_execute_masked_stems(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, n_stems), "zafx_execute_masked_stems")
+
     def ragged_layout(self, lengths):
         """Placement of a ragged batch's results (zafx_plan_ragged_layout) for clips of `lengths` samples: -> (out_offsets, frames, pitch), int64
         arrays.  Clip i's block of the output array starts at element out_offsets[i] (out_offsets[-1]: elements in all) and holds F rows of
@@ -1308,6 +1342,55 @@ def maskfilter_batch(clips, window_function, masks, step_length=None, rest=False
     return (out[:, 0], out[:, 1]) if rest else out
 
 
+def maskfilter_stems_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
+    """The mask filter with several masks per clip -- the stems of a source separation -- in one kernel: clips (B, N) and real masks
+    (B, S, W/2 + 1, T), the reference's order -- (B, S, T, W/2 + 1) with layout "TF" --, S in 1 .. 8, T = ceil(N / (W/2)) + 1 -> float32
+    (B, S, N), stem s of clip b being maskfilter_batch of that clip with masks[b, s], bit for bit; the forward transform of a clip runs once
+    for all its stems (k_maskfilter_stems).  With rest=True (stems, rest), rest = ((x - y_0) - y_1) - ... - y_{S-1} in float32, (B, N): views
+    of one (B, S + 1, N) result (which `out`, if given, is).  The device reads "TF" masks only: "FT" masks are transposed on the host before
+    the upload -- one more pass over the masks in host memory, B S T (W/2 + 1) floats copied with a strided read; hand over "TF" masks where
+    that matters.  step_length: None or window_length / 2."""
+    w = _maskfilter_window(window_function, step_length)
+    a, m = np.asarray(clips), np.asarray(masks)
+    if a.ndim != 2:
+        raise ValueError(f"clips must be mono, (clips, samples), got shape {a.shape}")
+    if np.iscomplexobj(a) or np.iscomplexobj(m):
+        raise ValueError("clips and masks must be real")
+    if m.ndim != 4:
+        raise ValueError(f"masks must be 4-D, (clips, stems, ...), got shape {m.shape}")
+    n_clips, n = a.shape
+    n_stems = m.shape[1]
+    if not 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:
+        raise ValueError(f"the number of stems, masks.shape[1], must be in 1 .. {_lib.MASKFILTER_MAX_STEMS}, got {n_stems}")
+    h = len(w) // 2
+    frames, rows = (n + h - 1) // h + 1, h + 1
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    want = (n_clips, n_stems, rows, frames) if ft else (n_clips, n_stems, frames, rows)
+    if m.shape != want:
+        raise ValueError(f"masks must have shape {want} for clips of {n} samples (layout {layout!r}), got {m.shape}")
+    shape = (n_clips, n_stems + 1, n) if rest else (n_clips, n_stems, n)
+    if out is None:
+        out = np.empty(shape, np.float32)
+    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
+    if out.size:
+        plan = maskfilter_plan(w, rest, "TF", device)
+        x = np.ascontiguousarray(a, dtype=np.float32)
+        mt = np.ascontiguousarray(m.transpose(0, 1, 3, 2) if ft else m, dtype=np.float32)
+        d_in, d_mask, d_out = DeviceBuffer(x.shape, np.float32, device), DeviceBuffer(mt.shape, np.float32, device), DeviceBuffer(shape, np.float32, device)
+        try:
+            d_in.upload(x)
+            d_mask.upload(mt)
+            with plan.lock:
+                plan.execute_masked_stems(d_in, d_mask, d_out, n_clips, n, n_stems)
+                plan.sync()
+                d_out.download(out=out)
+        finally:
+            for b in (d_in, d_mask, d_out):
+                b.free()
+    return (out[:, :n_stems], out[:, n_stems]) if rest else out
+
+
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
     """(B, N) -> (B, W/2, T) float32 ["FT"] or (B, T, W/2) ["TF"]; f64: float64 arrays and arithmetic."""
     x = _as_clips(clips, dtype=np.float64 if f64 else np.float32)
@@ -2062,6 +2145,17 @@ def maskfilter(audio_signal, window_function, step_length, mask):
     if m.ndim != 2:
         raise ValueError(f"mask must be 2-D (window_length / 2 + 1, number_times), got shape {m.shape}")
     return maskfilter_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
+
+
+def maskfilter_stems(audio_signal, window_function, step_length, masks):
+    """maskfilter for S masks of one signal in one call: a 1-D signal and real masks (S, W/2 + 1, T), S in 1 .. 8 -> float64 (S, N), row s
+    being maskfilter(audio_signal, window_function, step_length, masks[s]); the signal is transformed once (see maskfilter_stems_batch)."""
+    a, m = np.asarray(audio_signal), np.asarray(masks)
+    if a.ndim != 1:
+        raise ValueError(f"audio_signal must be 1-D, got shape {a.shape}")
+    if m.ndim != 3:
+        raise ValueError(f"masks must be 3-D (stems, window_length / 2 + 1, number_times), got shape {m.shape}")
+    return maskfilter_stems_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
 
 
 def melspectrogram(audio_signal, window_function, step_length, mel_filterbank):
