@@ -33,7 +33,8 @@
  *   zafx_execute_masked            spectrum :190-191 (np.concatenate((mask, mask[-2:0:-1])) * audio_stft), istft :194-195 and, _REST,
  *                                  the subtraction :198, for a mono clip in one kernel; zafx_plan_mask_dims gives the mask's shape
  *                                  (clips of different lengths in one launch: zafx_execute_masked_ragged, zafx_plan_mask_ragged_layout;
- *                                  several masks per clip over one forward transform: zafx_execute_masked_stems)
+ *                                  several masks per clip over one forward transform: zafx_execute_masked_stems;
+ *                                  both at once: zafx_execute_masked_stems_ragged, zafx_plan_stems_ragged_layout)
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -259,7 +260,7 @@ int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
  * Two kinds REFUSE long clips: the call returns an error (zafx_last_error names the limit), enqueues nothing and writes nothing.
  *   ZAFX_CQT / ZAFX_CHROMA (float32)          n_in >= 2^29 samples (3.4 h at 44.1 kHz): cut the signal
  *   ZAFX_CENTER / ZAFX_CENTER_SIDES           n_in >= 2^28 sample frames (1.7 h at 44.1 kHz)
- *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked; zafx_execute_masked_ragged: any clip of the batch)
+ *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked; zafx_execute_masked_ragged, zafx_execute_masked_stems_ragged: any clip of the batch)
  * zafx_execute_pcm reads int16 in the kernels' own loads below the same lengths (n_frames < 2^29; the MDCT: < 2^28) and converts first above them.
  * Not run at its bound by any test yet: the two-sided complex STFT at window 8192 (k_stft_ft16q takes whole-line rows only; its |X| kind is run).
  * The ragged and PCM entry points state their own per-clip limits below. */
@@ -314,6 +315,33 @@ int zafx_execute_masked_ragged(zafx_plan* plan, const void* d_in, const int64_t*
 #define ZAFX_MASKFILTER_MAX_STEMS 8
 int zafx_execute_masked_stems(zafx_plan* plan, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in,
                               int32_t n_stems);
+/* Placement of a ragged stems batch (ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans of ZAFX_LAYOUT_TF, n_stems in 1 ..
+ * ZAFX_MASKFILTER_MAX_STEMS), in float32 elements, both arrays of n_clips + 1 entries: the n_stems masks of clip i lie back to back as
+ * (n_stems, T_i, W/2 + 1), T_i = zafx_plan_mask_dims(plan, lengths[i])[1], at element mask_offsets[i] of the mask array, the clips back to
+ * back -- n_stems x what zafx_plan_mask_ragged_layout gives --; its output block is (n_stems, lengths[i]), under ZAFX_MASKFILTER_REST
+ * (n_stems + 1, lengths[i]), at element out_offsets[i], the blocks back to back.  Entry n_clips of either array is the total.  A clip of
+ * length 0 has T = 1 (its masks are never read) and an empty output block. */
+int zafx_plan_stems_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64_t n_clips, int32_t n_stems, int64_t* mask_offsets,
+                                  int64_t* out_offsets);
+/* Ragged stems: zafx_execute_masked_stems for n_clips mono clips of different lengths in ONE launch (ZAFX_MASKFILTER and
+ * ZAFX_MASKFILTER_REST plans created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_stems_ragged"), enqueued on the plan's stream
+ * (asynchronous).  n_stems is one value for the batch.  Offsets and lengths count float32 elements: clip i is lengths[i] samples at element
+ * in_offsets[i] of d_in; its n_stems masks, each (T_i, W/2 + 1) compact, lie back to back from element mask_offsets[i] of d_mask; its
+ * output block -- (n_stems, lengths[i]), under ZAFX_MASKFILTER_REST (n_stems + 1, lengths[i]) with the rest
+ * ((x - y_0) - y_1) - ... - y_{n_stems-1} in its last row -- starts at element out_offsets[i] of d_out.  Any placement of clips, masks and
+ * output blocks will do (zafx_plan_stems_ragged_layout gives the compact one): clips and masks may lie back to back -- every clip is
+ * padded with zeros of its own, and nothing behind a stem's last frame is read for that stem --, and nothing is written outside the output
+ * blocks.  The arrays need 4-byte alignment only.  CONTRACT: clip i's block is bit-identical to zafx_execute_masked_stems on that clip and
+ * its n_stems masks alone, so stem s is bit-identical to zafx_execute_masked with mask s alone -- whatever the batch, the clip's place in
+ * it, the cut into units and ZAFX_COMPUTE_UNITS.  A clip of length 0 is skipped: nothing of it is read or written; an empty batch is
+ * fine.  The four host arrays are copied before return.  Rejected with a message, nothing enqueued or written: a null plan, pointer or host
+ * array, n_clips < 0, another kind, a plan in ZAFX_LAYOUT_FT (the message names ZAFX_LAYOUT_TF), n_stems outside 1 ..
+ * ZAFX_MASKFILTER_MAX_STEMS, negative lengths or offsets (with the clip's index), a clip of 2^28 samples or more (with its index; decided
+ * on `lengths` before anything is read), a window that is not set or whose sum(window[0:W:H]) is zero.  NOT checked: that the output
+ * blocks do not overlap.  Every other entry point on the same plan is not affected.  ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment
+ * applies as it does to zafx_execute_masked_ragged (measurements only). */
+int zafx_execute_masked_stems_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                     const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
  * with_mel included, _CQT, _CHROMA; float32 and float64).

@@ -3,6 +3,7 @@ existed, in one process.
 
     python tools/maskfilter_stems_rates.py [--clips 1024] [--reps 30] [--stems 2,4] [--out FILE]
     python tools/maskfilter_stems_rates.py --only stems4 --reps 2      one case alone, no comparison: the command of a counter run
+    python tools/maskfilter_stems_rates.py --ragged [--reps 30] [--stems 2,4] [--per-slot 4,6,8,12] [--out FILE]
 
 Workload: --clips mono clips x 441 000 samples (10 s at 44.1 kHz; 432 frames), Hamming 2048 / hop 1024, "TF" masks uniform in [0, 1],
 everything device-resident (32 distinct noise clips and mask sets repeated over the batch).  Timed with the plan's HIP-event stopwatch, median
@@ -14,6 +15,18 @@ everything device-resident (32 distinct noise clips and mask sets repeated over 
 Algorithmic bytes per sample: stems 4 + 4 S (+ 4 with the rest) and the masks' 4 S * 1025 / 1024; singles S * (4 + 4 (8 with the rest)) and the same
 masks.  The stems call counts as faster when its median lies below the singles' median by more than the larger of the two (max - min) spreads;
 exit status 1 when it does not at S = 4.
+
+--ragged (the recipe of tools/maskfilter_rates.py --ragged: 1024 mono clips of 5-15 s at 44.1 kHz, Hamming 2048 / 1024, "TF" masks uniform in
+[0, 1], everything resident), per S and plan kind:
+  ragged    one execute_masked_stems_ragged of the clips, masks and output blocks packed back to back (k_maskfilter_stems_ragged; the cutting of
+            the units and the table's upload included)
+  padded    the same clips padded with zeros to the longest, with masks of the longest's shape, as one execute_masked_stems
+  singles   S execute_masked_ragged calls (k_maskfilter_ragged) over the same clips, call s with the clips' masks s where they lie, all S in
+            one reading
+median (min, max) of --reps readings after warm-up.  --per-slot: at the last S of --stems, also times the ragged call with the cutter aiming
+at these numbers of units per workgroup slot (ZAFX_MASKFILTER_UNITS_PER_SLOT) instead of the library's own.  The ragged call counts as faster
+than a baseline when its median lies below the baseline's by more than the larger of the two (max - min) spreads; the verdicts are printed and
+stored, the exit status is 0 either way.
 """
 import argparse
 import json
@@ -55,6 +68,96 @@ def show(name, r):
           f"{r['hbm_fraction']:.3f} of HBM peak on {r['algorithmic_bytes_per_sample']:.2f} B per sample  [{r['kernel']}]", flush=True)
 
 
+def ragged_main(a):
+    fs, clips = 44100, 1024
+    lengths = np.random.default_rng(0).integers(5 * fs, 15 * fs + 1, clips).astype(np.int64)
+    longest, total = int(lengths.max()), int(lengths.sum())
+    in_offsets = np.zeros(clips, np.int64)
+    in_offsets[1:] = np.cumsum(lengths)[:-1]
+    window = zafx.hamming(W)
+    plans = {rest: zafx.maskfilter_plan(window, rest=rest, layout="TF") for rest in (False, True)}
+    res = {"device": zafx.device_name(0), "clips": clips, "window": W, "hop": HOP, "samples": total, "longest": longest, "reps": a.reps,
+           "padded_over_ragged_samples": clips * longest / total, "compute_units": plans[False].compute_units}
+    print(f"{clips} clips, {total} samples in all, longest {longest}: the padded batch holds {clips * longest / total:.3f} x as many", flush=True)
+    # clip i = the first lengths[i] samples of noise clip i % DISTINCT, packed and padded
+    small = zafx.DeviceBuffer.from_host(np.random.default_rng(1).standard_normal((DISTINCT, longest), dtype=np.float32))
+    d_rag = zafx.DeviceBuffer((total,), np.float32)
+    d_pad = zafx.DeviceBuffer((clips, longest), np.float32)
+    d_pad.fill_zero()
+    for i in range(clips):
+        src, n = (i % DISTINCT) * longest * 4, int(lengths[i])
+        d_rag.copy_from(small, nbytes=n * 4, dst_offset=int(in_offsets[i]) * 4, src_offset=src)
+        d_pad.copy_from(small, nbytes=n * 4, dst_offset=i * longest * 4, src_offset=src)
+    small.free()
+    rows, frames_pad = plans[False].mask_dims(longest)
+    one_pad = rows * frames_pad
+    one_offsets = plans[False].mask_ragged_layout(lengths)   # one mask per clip: element counts
+    one = np.diff(one_offsets)
+
+    def verdict(r, base):
+        x, y = r["ragged"], r[base]
+        spread = max(x["max_ms"] - x["min_ms"], y["max_ms"] - y["min_ms"])
+        r[f"ragged_over_{base}"] = x["median_ms"] / y["median_ms"]
+        r[f"faster_than_{base}"] = bool(y["median_ms"] - x["median_ms"] > spread)
+        return f"ragged / {base} {r[f'ragged_over_{base}']:.3f} (larger spread {spread:.3f} ms: {'faster' if r[f'faster_than_{base}'] else 'NOT faster'})"
+
+    for s in a.stems:
+        # a mask is uniform noise whatever its shape: mask (i, j) = the first elements of noise mask (i % DISTINCT, j), in both arrays
+        noise = zafx.DeviceBuffer.from_host(np.random.default_rng([2, s]).random((DISTINCT, s, one_pad), dtype=np.float32))
+        mask_offsets, _ = plans[False].stems_ragged_layout(lengths, s)
+        m_rag = zafx.DeviceBuffer((int(mask_offsets[-1]),), np.float32)
+        m_pad = zafx.DeviceBuffer((clips, s, one_pad), np.float32)
+        for i in range(clips):
+            m_pad.copy_from(noise, nbytes=s * one_pad * 4, dst_offset=i * s * one_pad * 4, src_offset=(i % DISTINCT) * s * one_pad * 4)
+            for j in range(s):
+                m_rag.copy_from(noise, nbytes=int(one[i]) * 4, dst_offset=(int(mask_offsets[i]) + j * int(one[i])) * 4,
+                                src_offset=((i % DISTINCT) * s + j) * one_pad * 4)
+        noise.free()
+        for rest in (False, True):
+            plan, name = plans[rest], f"s{s}" + ("_rest" if rest else "")
+            blocks = s + (1 if rest else 0)
+            r = {}
+            out = zafx.DeviceBuffer((blocks * total,), np.float32)
+            out_offsets = blocks * in_offsets
+            variants = [("ragged", None)] + [(f"ragged_per_slot_{v}", v) for v in (a.per_slot if s == a.stems[-1] else [])]
+            for key, per_slot in variants:
+                if per_slot is None:
+                    os.environ.pop("ZAFX_MASKFILTER_UNITS_PER_SLOT", None)
+                else:
+                    os.environ["ZAFX_MASKFILTER_UNITS_PER_SLOT"] = str(per_slot)
+                r[key] = timed(plan, lambda: plan.execute_masked_stems_ragged(d_rag, in_offsets, lengths, m_rag, mask_offsets, out, out_offsets, s), a.reps)
+                r[key]["kernel"] = plan.last_kernel
+            os.environ.pop("ZAFX_MASKFILTER_UNITS_PER_SLOT", None)
+            out.free()
+            # (b) S calls of the ragged one-mask kind: call j reads the clips' masks j where they lie, and writes an output array of its own
+            one_blocks = 2 if rest else 1
+            outs = [zafx.DeviceBuffer((one_blocks * total,), np.float32) for _ in range(s)]
+            offs = [np.ascontiguousarray(mask_offsets[:-1] + j * one) for j in range(s)]
+
+            def singles():
+                for j in range(s):
+                    plan.execute_masked_ragged(d_rag, in_offsets, lengths, m_rag, offs[j], outs[j], one_blocks * in_offsets)
+            r["singles"] = timed(plan, singles, a.reps)
+            r["singles"]["kernel"] = plan.last_kernel
+            for o in outs:
+                o.free()
+            # (a) padded to the longest
+            out = zafx.DeviceBuffer(plan.stems_out_shape(clips, longest, s), np.float32)
+            r["padded"] = timed(plan, lambda: plan.execute_masked_stems(d_pad, m_pad, out, clips, longest, s), a.reps)
+            r["padded"]["kernel"] = plan.last_kernel
+            out.free()
+            for key, v in r.items():
+                v["msamples_per_s"] = total / (v["median_ms"] * 1e3)
+                print(f"{name:8s} {key:20s} {v['median_ms']:8.3f} ms ({v['min_ms']:.3f}-{v['max_ms']:.3f})  {v['msamples_per_s']:9.0f} Msamples/s  [{v['kernel']}]", flush=True)
+            print(f"{name:8s} {verdict(r, 'padded')}; {verdict(r, 'singles')}", flush=True)
+            res[name] = r
+        m_rag.free(), m_pad.free()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=1024)
@@ -62,7 +165,11 @@ def main():
     ap.add_argument("--stems", type=lambda v: [int(t) for t in v.split(",") if t], default=[2, 4])
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="", help="comma-separated case names (stems4, singles4_rest, ...); no comparison")
+    ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--per-slot", type=lambda v: [int(t) for t in v.split(",") if t], default=[])
     a = ap.parse_args()
+    if a.ragged:
+        return ragged_main(a)
     b = a.clips
     only = [t for t in a.only.split(",") if t]
     window = zafx.hamming(W)

@@ -1895,6 +1895,54 @@ int zafx_execute_masked_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
                                                         static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size()));
 }
 
+// Stems of a ragged batch: a clip's n_stems masks back to back, each as a TF plan's mask_block, and its n_stems (+ 1 with rest) output blocks
+int zafx_plan_stems_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t n_stems, int64_t* mask_offsets, int64_t* out_offsets) {
+    const char* const fn = "zafx_plan_stems_ragged_layout";
+    if (!pl || !mask_offsets || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
+    if (n_clips < 0) return fail_msg("negative size");
+    int64_t clip = -1;
+    if (const char* why = zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, nullptr, 0, &clip)) return fail_msg(std::string(fn) + ": " + why);
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] < 0) return fail_msg(std::string(fn) + ": negative length of clip " + std::to_string(i));
+    const int64_t blocks = n_stems + (pl->kind == ZAFX_MASKFILTER_REST ? 1 : 0);
+    mask_offsets[0] = out_offsets[0] = 0;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        int64_t elems = 0, pitch = 0;
+        mask_block(pl, lengths[i], &elems, &pitch);
+        mask_offsets[i + 1] = mask_offsets[i] + n_stems * elems;
+        out_offsets[i + 1] = out_offsets[i] + blocks * lengths[i];
+    }
+    return 0;
+}
+
+// Ragged batches with n_stems masks per clip: the units are k_maskfilter's (maskfilter_cut_units), cut for the slots the stems' LDS size
+// leaves; k_maskfilter_stems' RAGGED form walks them.
+int zafx_execute_masked_stems_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                     const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems) {
+    const char* const fn = "zafx_execute_masked_stems_ragged";
+    int64_t clip = -1;
+    // the kind, the layout and the stem count: refused for an empty batch too, as zafx_execute_masked_stems does
+    const char* wrong_kind = pl ? zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, nullptr, 0, &clip) : nullptr;
+    bool empty = false;
+    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    if (const char* why = zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, lengths, n_clips, &clip))
+        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
+    if (!pl->d_window) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    int tile_transforms = 0;
+    long long slots = 0;
+    if (!zafx::maskfilter_stems_launch_shape(*pl, n_stems, &tile_transforms, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
+    // ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment, as for zafx_execute_masked_ragged (measurements only)
+    const int per_slot = env_units_per_slot("ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot);
+    const std::vector<zafx::MaskfilterUnit> units =
+        zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, nullptr, n_clips, pl->W, tile_transforms, slots, per_slot);   // (TF masks: no pitch)
+    ZAFX_HIP(hipSetDevice(pl->device));
+    if (int rc = upload_records(pl, units)) return rc;
+    return launch_rc(fn, zafx::launch_maskfilter_stems_ragged(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out,
+                                                              static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size(), n_stems));
+}
+
 // What zafx_execute_imdct_ragged and zafx_execute_istft_ragged differ in: both cut their blocks into units of tiles (zafx_units.hpp) that the
 // RAGGED form of their kernel walks in one launch, and run one zafx_execute per block where that form does not apply.
 struct TileRagged {

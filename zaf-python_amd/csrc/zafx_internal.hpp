@@ -381,6 +381,12 @@ hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const fl
 struct MaskfilterUnit;
 bool maskfilter_launch_shape(const zafx_plan& pl, int* tile_transforms, long long* slots);
 hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units);
+// zafx_execute_masked_stems_ragged: the same for k_maskfilter_stems -- the slots follow the stems' LDS size (false as well for a stem count
+// outside 1 .. 8) -- and the launch on a device table of unit records: a clip's n_stems masks back to back at mask_off, its n_stems (+ 1 with
+// rest) output blocks back to back at out_off
+bool maskfilter_stems_launch_shape(const zafx_plan& pl, int n_stems, int* tile_transforms, long long* slots);
+hipError_t launch_maskfilter_stems_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
+                                          int64_t n_stems);
 // zafx_execute_center_ragged: the tile frames F and the workgroup slots of the plan's k_center (what center_cut_units takes), and the launch of
 // its RAGGED form on `n_units` records of the device table
 struct CenterUnit;

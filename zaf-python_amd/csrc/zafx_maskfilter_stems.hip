@@ -1,9 +1,10 @@
 // zafx_maskfilter_stems.hip -- k_maskfilter_stems: the mask filter with S masks per clip (the stems of a source separation): one STFT, S masks,
-// S ISTFTs of mono clips in one kernel (zafx_execute_masked_stems).  A translation unit of its own: k_maskfilter's instantiations
-// (zafx_maskfilter.hip) keep their registers to the last one.
+// S ISTFTs of mono clips in one kernel (zafx_execute_masked_stems; clips of different lengths: its RAGGED form, zafx_execute_masked_stems_ragged).
+// A translation unit of its own: k_maskfilter's instantiations (zafx_maskfilter.hip) keep their registers to the last one.
 #include <algorithm>
 
 #include "zafx_maskfilter_cfg.hpp"
+#include "zafx_units.hpp"
 
 namespace zafx {
 
@@ -28,10 +29,16 @@ constexpr size_t maskfilter_stems_smem(int n_stems) {
 
 // unit u = clip * n_segs + seg as in k_maskfilter; stem s of a clip: mask at (clip * n_stems + s) * mask_clip, output at (clip * blocks_out + s) * n_samples,
 // blocks_out = n_stems + REST
-template <int LOG2W, bool REST>
+// RAGGED (zafx_execute_masked_stems_ragged): clips of different lengths, as k_maskfilter's RAGGED form has them.  `n_samples` carries the table
+// of unit records (the equal-length instantiations keep their kernel arguments byte for byte), unit u is record u -- its clip's samples at
+// x + in_off, n_samples of them, its S masks back to back at mask + mask_off, each (n_blocks + 1) (H + 1) elements with a descriptor of its
+// own, its S (+ REST) output blocks of n_samples back to back at out + out_off --, and mask_clip / n_blocks / seg_blocks / n_segs are not used.
+template <bool RAGGED>
+using MaskfilterStemsSamplesArg = std::conditional_t<RAGGED, const MaskfilterUnit* __restrict__, long long>;   // (restrict: the table is read with scalar loads)
+template <int LOG2W, bool REST, bool RAGGED>
 __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter_stems(const float* __restrict__ x, const float* __restrict__ mask,
                                                                                    const float* __restrict__ window, const float2* __restrict__ tw_g,
-                                                                                   float* __restrict__ out, long long n_samples, long long mask_clip, int n_stems,
+                                                                                   float* __restrict__ out, MaskfilterStemsSamplesArg<RAGGED> n_samples, long long mask_clip, int n_stems,
                                                                                    int n_blocks, int seg_blocks, int n_segs, long long n_units, float gain) {
     using K = MaskfilterCfg<LOG2W, true>;
     using C = typename K::C;
@@ -44,17 +51,50 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
     float2* const tw = smem + K::OFF_TW;
     for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
     __syncthreads();
-    const unsigned clip_bytes = (unsigned)(n_samples * 4), mask_bytes = (unsigned)(mask_clip * 4);   // (clips below 2^28 samples: the launcher)
+    // samples of the unit's clip: the kernel's argument, or (RAGGED) the field of the unit's record
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+    unsigned clip_bytes = 0, mask_bytes = 0;   // (clips below 2^28 samples: the launcher)
+    if constexpr (!RAGGED) {
+        clip_bytes = (unsigned)(n_samples * 4);
+        mask_bytes = (unsigned)(mask_clip * 4);
+    }
     constexpr int st = (H + 1) * 4;   // bytes from frame to frame of a mask
     const int blocks_out = n_stems + (REST ? 1 : 0);
 
-    for (long long u = blockIdx.x; u < n_units; u += gridDim.x) {
-        const long long clip = u / n_segs;
-        const int seg = (int)(u - clip * n_segs);
-        const int b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
-        const float* const xc = x + clip * n_samples;
-        float* const oc = out + clip * blocks_out * n_samples;
-        const float* const mc = mask + clip * n_stems * mask_clip;
+    // RAGGED: the units come ordered by descending length, and the rounds of gridDim.x units are dealt forwards and backwards in turn, counted
+    // in 32 bits (the launcher keeps them below 2^31), as k_maskfilter's are and for its reasons
+    using Cnt = std::conditional_t<RAGGED, unsigned, long long>;
+    const Cnt n_all = (Cnt)n_units;
+    const Cnt n_deal = RAGGED ? (n_all + gridDim.x - 1) / gridDim.x * gridDim.x : n_all;
+    unsigned round = 0;
+    for (Cnt w = blockIdx.x; w < n_deal; w += gridDim.x, ++round) {
+        Cnt u = w;
+        if constexpr (RAGGED) {
+            if (round & 1) u = (round + 1) * gridDim.x - 1 - blockIdx.x;   // = (2 round + 1) gridDim.x - 1 - w
+            if (u >= n_all) continue;   // (the last round may be short; uniform)
+        }
+        MaskfilterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
+        int b0, b1;
+        const float* xc;
+        float* oc;
+        const float* mc;
+        if constexpr (RAGGED) {
+            rc = n_samples[__builtin_amdgcn_readfirstlane((int)u)];   // (the launcher keeps the units below 2^31)
+            if (rc.b1 <= rc.b0) continue;                             // a value-initialised record: no blocks (uniform)
+            b0 = rc.b0, b1 = rc.b1;
+            n_blocks = (int)((rc.n_samples + H - 1) / H);
+            mask_clip = (long long)(n_blocks + 1) * (H + 1);   // a stem's mask: frames 0 .. n_blocks, compact
+            xc = x + rc.in_off, mc = mask + rc.mask_off, oc = out + rc.out_off;
+            clip_bytes = (unsigned)(rc.n_samples * 4);
+            mask_bytes = (unsigned)(n_blocks + 1) * (unsigned)((H + 1) * 4);
+        } else {
+            const long long clip = u / n_segs;
+            const int seg = (int)(u - clip * n_segs);
+            b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
+            xc = x + clip * n_samples;
+            oc = out + clip * blocks_out * n_samples;
+            mc = mask + clip * n_stems * mask_clip;
+        }
         const int q0 = b0 >> 1, q1 = b1 >> 1;
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
         for (int qt = q0; qt <= q1; qt += F) {
@@ -152,12 +192,12 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
 #pragma unroll
                     for (int i = 0; i < HE; ++i) carry[lane + P * i] = keep[i];
                 }
-                float* const os = oc + (long long)s * n_samples;
+                float* const os = oc + (long long)s * CLIP_N;
                 if (writes_odd) {
                     const long long sm = (long long)(2 * q - 1) * H + lane;
 #pragma unroll
                     for (int i = 0; i < HE; ++i) {
-                        if (sm + P * i < n_samples) {   // nothing is written at or beyond sample N
+                        if (sm + P * i < CLIP_N) {   // nothing is written at or beyond sample N
                             os[sm + P * i] = yo[i];
                             if constexpr (REST) raw[i] = raw[i] - yo[i];
                         }
@@ -167,7 +207,7 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
                     const long long sm = (long long)(2 * q) * H + lane;
 #pragma unroll
                     for (int i = 0; i < HE; ++i) {
-                        if (sm + P * i < n_samples) {
+                        if (sm + P * i < CLIP_N) {
                             os[sm + P * i] = ye[i];
                             if constexpr (REST) raw[HE + i] = raw[HE + i] - ye[i];
                         }
@@ -175,23 +215,24 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
                 }
             }
             if constexpr (REST) {   // block S: what the stems left of the samples
-                float* const orest = oc + (long long)n_stems * n_samples;
+                float* const orest = oc + (long long)n_stems * CLIP_N;
                 if (writes_odd) {
                     const long long sm = (long long)(2 * q - 1) * H + lane;
 #pragma unroll
                     for (int i = 0; i < HE; ++i)
-                        if (sm + P * i < n_samples) orest[sm + P * i] = raw[i];
+                        if (sm + P * i < CLIP_N) orest[sm + P * i] = raw[i];
                 }
                 if (writes_even) {
                     const long long sm = (long long)(2 * q) * H + lane;
 #pragma unroll
                     for (int i = 0; i < HE; ++i)
-                        if (sm + P * i < n_samples) orest[sm + P * i] = raw[HE + i];
+                        if (sm + P * i < CLIP_N) orest[sm + P * i] = raw[HE + i];
                 }
             }
         }
         lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
     }
+#undef CLIP_N
 }
 
 // workgroups the device holds at once under the stems' LDS size: what LDS admits per CU, at most 4
@@ -205,7 +246,7 @@ template <int LOG2W, bool REST>
 static hipError_t run_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int n_stems) {
     using K = MaskfilterCfg<LOG2W, true>;
     static_assert(maskfilter_stems_smem<LOG2W>(kMaskfilterMaxStems) <= (size_t)kMaxLdsBytes, "k_maskfilter_stems: frames + carries + tables exceed LDS");
-    auto kern = k_maskfilter_stems<LOG2W, REST>;
+    auto kern = k_maskfilter_stems<LOG2W, REST, false>;
     const size_t smem = maskfilter_stems_smem<LOG2W>(n_stems);
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, smem); e != hipSuccess) return e;
     pl.ran = kMaskfilterStemsKernel;
@@ -246,6 +287,66 @@ hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const fl
         case 9: return run_maskfilter_stems_kind<9>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
         case 10: return run_maskfilter_stems_kind<10>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
         case 11: return run_maskfilter_stems_kind<11>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
+    }
+    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------
+// ragged batches (zafx_execute_masked_stems_ragged): the units come cut and ordered from the host (maskfilter_cut_units under the stems' slots)
+// ---------------------------------------------------------------------------------
+static const char* const kMaskfilterStemsRaggedName = "k_maskfilter_stems_ragged";
+
+template <int LOG2W, bool REST>
+static hipError_t run_maskfilter_stems_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
+                                              int n_stems) {
+    using K = MaskfilterCfg<LOG2W, true>;
+    auto kern = k_maskfilter_stems<LOG2W, REST, true>;
+    const size_t smem = maskfilter_stems_smem<LOG2W>(n_stems);
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, smem); e != hipSuccess) return e;
+    pl.ran = kMaskfilterStemsRaggedName;
+    if (n_units <= 0) return hipSuccess;
+    const long long grid = std::min<long long>(n_units, maskfilter_stems_slots<LOG2W>(pl, n_stems));
+    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // as run_maskfilter's
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), smem, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, n_stems, 0, 0, 0, n_units, gain);
+    return hipGetLastError();
+}
+
+template <int LOG2W>
+static hipError_t run_maskfilter_stems_ragged_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
+                                                   int n_stems) {
+    return pl.kind == ZAFX_MASKFILTER_REST ? run_maskfilter_stems_ragged<LOG2W, true>(pl, x, mask, out, d_units, n_units, n_stems)
+                                           : run_maskfilter_stems_ragged<LOG2W, false>(pl, x, mask, out, d_units, n_units, n_stems);
+}
+
+bool maskfilter_stems_launch_shape(const zafx_plan& pl, int n_stems, int* tile_transforms, long long* slots) {
+    if (n_stems < 1 || n_stems > kMaskfilterMaxStems) return false;
+    switch (pl.log2nf) {
+        case 8: *slots = maskfilter_stems_slots<8>(pl, n_stems); break;
+        case 9: *slots = maskfilter_stems_slots<9>(pl, n_stems); break;
+        case 10: *slots = maskfilter_stems_slots<10>(pl, n_stems); break;
+        case 11: *slots = maskfilter_stems_slots<11>(pl, n_stems); break;
+        default: return false;
+    }
+    *tile_transforms = maskfilter_tile_transforms(pl.log2nf);
+    return true;
+}
+
+hipError_t launch_maskfilter_stems_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
+                                          int64_t n_stems) {
+    if (pl.layout != ZAFX_LAYOUT_TF || n_stems < 1 || n_stems > kMaskfilterMaxStems) {   // (the entry point has said why: maskfilter_stems_ragged_refusal)
+        set_error("mask filter stems: ZAFX_LAYOUT_TF plans and 1 .. 8 stems only");
+        return hipErrorInvalidValue;
+    }
+    if (n_units >= (1LL << 31)) {
+        set_error("mask filter stems: ragged batch too large for one launch (units >= 2^31)");
+        return hipErrorInvalidValue;
+    }
+    switch (pl.log2nf) {
+        case 8: return run_maskfilter_stems_ragged_kind<8>(pl, x, mask, out, d_units, n_units, (int)n_stems);
+        case 9: return run_maskfilter_stems_ragged_kind<9>(pl, x, mask, out, d_units, n_units, (int)n_stems);
+        case 10: return run_maskfilter_stems_ragged_kind<10>(pl, x, mask, out, d_units, n_units, (int)n_stems);
+        case 11: return run_maskfilter_stems_ragged_kind<11>(pl, x, mask, out, d_units, n_units, (int)n_stems);
     }
     set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
     return hipErrorInvalidValue;

@@ -446,5 +446,22 @@ inline const char* maskfilter_stems_refusal(const RouteCall& c, int64_t n_stems)
     if (maskfilter_clip_refused(c)) return "mask filter: clips of 2^28 samples and more are not supported";
     return nullptr;
 }
+// zafx_execute_masked_stems_ragged: the kind, the layout and the stem count as above, then every clip's length against the clip bound.
+// nullptr: the call is taken; otherwise *clip is the index of the clip refused, or -1 where the refusal is none of a clip's.
+inline const char* maskfilter_stems_ragged_refusal(int kind, int layout, int64_t n_stems, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
+    *clip = -1;
+    if (kind != ZAFX_MASKFILTER && kind != ZAFX_MASKFILTER_REST) return "mask filter stems: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only";
+    RouteCall c;
+    c.kind = kind, c.layout = layout;
+    if (const char* why = maskfilter_stems_refusal(c, n_stems)) return why;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        c.n = lengths[i];
+        if (maskfilter_clip_refused(c)) {
+            *clip = i;
+            return "mask filter stems: a clip has 2^28 samples or more (not supported)";
+        }
+    }
+    return nullptr;
+}
 
 }  // namespace zafx

@@ -1,5 +1,6 @@
 // zafx_units.hpp -- a ragged batch cut into the units a RAGGED kernel form walks: k_center's (zafx_center.hip, zafx_execute_center_ragged),
-// k_maskfilter's (zafx_maskfilter.hip, zafx_execute_masked_ragged), k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged) and k_istft_ft16's
+// k_maskfilter's (zafx_maskfilter.hip, zafx_execute_masked_ragged) and k_maskfilter_stems' (zafx_maskfilter_stems.hip,
+// zafx_execute_masked_stems_ragged: the same records and cut, the slots of the stems' LDS size), k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged) and k_istft_ft16's
 // (zafx_stft.hip, zafx_execute_istft_ragged).
 //
 // A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, pairs of such blocks (one packed transform) for k_maskfilter, tiles
@@ -116,7 +117,8 @@ inline std::vector<CenterUnit> center_cut_units(const int64_t* lengths, const in
 // ---- k_maskfilter: pairs of blocks.  One record of the device table.  Offsets and lengths in float32 elements.  The kernel deals the rounds itself.
 // The piece is one packed transform's two blocks: a clip of n_blocks = ceil(n / H) blocks has ceil(n_blocks / 2) pieces, and the segment of
 // pieces [a, b) is blocks [2 a, min(n_blocks, 2 b)) -- every segment starts on an even block, which the kernel requires, and all but a clip's
-// last end on one (those run one transform more, the halo).  m = 2 F - 1 pieces: with the halo two full tiles of F transforms, the floor of
+// last end on one (those run one transform more, the halo).  k_maskfilter_stems reads the same record: mask_off is the first of the clip's S
+// compact TF masks, which lie back to back, out_off the first of its S (+ 1 with the rest) output blocks of n_samples, mask_pitch is not used.  m = 2 F - 1 pieces: with the halo two full tiles of F transforms, the floor of
 // the equal-length launch; floor of S = 2 m - 1 = 4 F - 3, as for k_center.
 struct MaskfilterUnit {
     long long in_off, n_samples, out_off, mask_off;   // the unit's CLIP: its first sample in the input, its length, its first sample in the output, the first element of its mask

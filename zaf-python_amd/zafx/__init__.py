@@ -15,6 +15,8 @@ The same with a mask of the caller's (STFT, real mask, ISTFT of mono clips in on
     Plan.mask_ragged_layout / Plan.execute_masked_ragged
     maskfilter_stems ((N,), (S, W/2+1, T) -> (S, N)), maskfilter_stems_batch ((B, N), (B, S, W/2+1, T) float32 -> (B, S, N)): S = 1 .. 8 masks per
     clip over one forward transform in one launch; Plan.execute_masked_stems / Plan.stems_mask_shape / Plan.stems_out_shape
+    maskfilter_stems_ragged (sequences of (N_i,) clips and (S, W/2+1, T_i) masks of different lengths -> a list of (S, N_i) in one launch),
+    pack_ragged_stems_masks, Plan.stems_ragged_layout / Plan.execute_masked_stems_ragged
 Batched extension ((clips, samples) in, float32 / complex64 out):
     stft_batch, istft_batch, mdct_batch, imdct_batch, melspectrogram_batch, mfcc_batch,
     cqtspectrogram_batch, cqtchromagram_batch, dct_batch, dst_batch, mel_mfcc_batch (melspectrogram + mfcc from one set of transforms);
@@ -40,7 +42,7 @@ from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersid
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,
                    get_precision, set_precision, stft, stft_batch, stft_pcm_batch, stft_plan, mdct_pcm_batch, melspectrogram_pcm_batch, mfcc_pcm_batch,
                    cqtspectrogram_pcm_batch, cqtchromagram_pcm_batch, mel_mfcc_batch, mel_mfcc_pcm_batch, mel_mfcc_supported, set_row_padding, get_row_padding,
-                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, maskfilter_ragged, pack_ragged_masks, imdct_ragged, istft_ragged,
+                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, maskfilter_ragged, pack_ragged_masks, maskfilter_stems_ragged, pack_ragged_stems_masks, imdct_ragged, istft_ragged,
                    stft_pcm_ragged, mdct_pcm_ragged, melspectrogram_pcm_ragged, mfcc_pcm_ragged, mel_mfcc_pcm_ragged, pack_ragged_pcm)
 from .launch import Rendezvous, rank_env, spawn_ranks
 from .shard import clip_range, run_sharded, shard_sizes

@@ -565,6 +565,52 @@ class Plan:
         _lib.check(_lib.load().zafx_execute_masked_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
                                                           d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_ragged")
 
+    def stems_ragged_layout(self, lengths, n_stems):
+        """Placement of a ragged stems batch (zafx_plan_stems_ragged_layout, mask filter plans of layout "TF") for clips of `lengths` samples
+        with n_stems masks each: -> (mask_offsets, out_offsets), int64 of len(lengths) + 1, in float32 elements.  Clip i's masks lie back to
+        back as (n_stems, T_i, W/2 + 1) from element mask_offsets[i] -- n_stems x what mask_ragged_layout gives --, its output block,
+        (n_stems, N_i) or with rest (n_stems + 1, N_i), starts at element out_offsets[i]; the last entries are the totals."""
+        lengths = _as_lengths(lengths)
+        mask_offs, out_offs = np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths) + 1, np.int64)
+        _lib.check(_lib.load().zafx_plan_stems_ragged_layout(self.handle, _i64p(lengths), len(lengths), int(n_stems), _i64p(mask_offs), _i64p(out_offs)),
+                   "zafx_plan_stems_ragged_layout")
+        return mask_offs, out_offs
+
+    def execute_masked_stems_ragged(self, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems):
+        """Enqueue the mask filter with n_stems masks per clip for mono clips of different lengths as one launch on the plan's stream
+        (asynchronous; zafx_execute_masked_stems_ragged, mask filter plans of layout "TF" only; last_kernel: k_maskfilter_stems_ragged).
+        Offsets and lengths count float32 elements: clip i is lengths[i] samples at element in_offsets[i] of d_in, its n_stems masks, each
+        (T_i, W/2 + 1) compact, lie back to back from element mask_offsets[i] of d_mask, and its block -- (n_stems, N_i), with rest
+        (n_stems + 1, N_i) -- starts at element out_offsets[i] of d_out; any placement will do (stems_ragged_layout: the compact one, whose
+        arrays with their totals are accepted as they are).  Clip i's block has the bits execute_masked_stems gives that clip and its masks
+        alone.  Output blocks that overlap are not detected."""
+        n_stems = int(n_stems)
+        in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
+        mask_offsets, out_offsets = _as_int64(mask_offsets, "mask_offsets"), _as_int64(out_offsets, "out_offsets")
+        if len(mask_offsets) == len(lengths) + 1:
+            mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
+        if len(out_offsets) == len(lengths) + 1:
+            out_offsets = np.ascontiguousarray(out_offsets[:-1])
+        if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
+            raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
+        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
+            raise ValueError("execute_masked_stems_ragged takes float32 samples, float32 masks and a float32 output buffer")
+        if (self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS and len(lengths)   # (otherwise: the library says so)
+                and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0
+                and int(lengths.max()) < 1 << 28):
+            h = int(self.params.window_length) // 2
+            blocks = n_stems + (1 if self.kind == _lib.MASKFILTER_REST else 0)
+            mask_ends = mask_offsets + n_stems * ((lengths + h - 1) // h + 1) * (h + 1)
+            live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
+            if int((in_offsets + lengths).max()) * 4 > d_in.nbytes:
+                raise ValueError("a clip reaches past the end of d_in")
+            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
+                raise ValueError("a clip's masks reach past the end of d_mask")
+            if int((out_offsets + blocks * lengths).max()) * 4 > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_masked_stems_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
+                                                                d_out.ptr, _i64p(out_offsets), len(lengths), n_stems), "zafx_execute_masked_stems_ragged")
+
     def execute_imdct_ragged(self, d_coefs, in_offsets, frames, d_out, out_offsets):
         """Enqueue the IMDCT of coefficient blocks of different frame counts on the plan's stream (asynchronous; zafx_execute_imdct_ragged,
         inverse MDCT plans only).  Block i starts at element in_offsets[i] of d_coefs: W/2 rows of frames[i] coefficients at the pitch
@@ -1939,6 +1985,65 @@ def maskfilter_ragged(clips, window_function, masks, step_length=None, rest=Fals
     if not rest:
         return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+
+
+def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
+    """One contiguous float32 array of a ragged stems batch's masks: a sequence of real (S, W/2 + 1, T_i) arrays -- (S, T_i, W/2 + 1) with
+    layout "TF" --, T_i = ceil(lengths[i] / (W/2)) + 1, S the same for every clip -> (packed 1-D, mask_offsets of len(lengths) + 1), the layout
+    of Plan.stems_ragged_layout: clip i's masks back to back as (S, T_i, W/2 + 1), the clips back to back.  The device reads "TF" masks only:
+    "FT" masks are transposed here, on the host, as maskfilter_stems_batch does.  A mask of another shape, or a stem count that differs from
+    the first clip's, raises ValueError with the clip's index."""
+    lengths = _as_lengths(lengths)
+    h, ft = int(window_length) // 2, _LAYOUTS[layout] == _lib.LAYOUT_FT
+    arrays = _as_ragged_items(masks, 3, "ragged stems mask batch", "3-D masks, (stems, ...)", "mask", empty_ok=True)
+    if len(arrays) != len(lengths):
+        raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
+    n_stems = arrays[0].shape[0] if arrays else 1
+    if not 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:
+        raise ValueError(f"the number of stems, masks[0].shape[0], must be in 1 .. {_lib.MASKFILTER_MAX_STEMS}, got {n_stems}")
+    frames = (lengths + h - 1) // h + 1
+    offsets = np.zeros(len(lengths) + 1, np.int64)
+    offsets[1:] = np.cumsum(n_stems * frames * (h + 1))
+    packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
+    for i, (m, o, t) in enumerate(zip(arrays, offsets.tolist(), frames.tolist())):
+        if m.shape[0] != n_stems:
+            raise ValueError(f"mask {i} has {m.shape[0]} stems, mask 0 has {n_stems}: the stem count is one for the batch")
+        want = (n_stems, h + 1, t) if ft else (n_stems, t, h + 1)
+        if m.shape != want:
+            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} samples (layout {layout!r}), got {m.shape}")
+        packed[o:o + n_stems * t * (h + 1)].reshape(n_stems, t, h + 1)[...] = m.transpose(0, 2, 1) if ft else m
+    return packed, offsets
+
+
+def maskfilter_stems_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
+    """maskfilter_stems_batch of mono clips of different lengths in one launch: a sequence of 1-D real clips and one of real masks,
+    (S, W/2 + 1, T_i) -- (S, T_i, W/2 + 1) with layout "TF" --, S in 1 .. 8 the same for every clip, T_i = ceil(N_i / (W/2)) + 1 -> a list of
+    float32 (S, N_i) arrays, or of (stems_i, rest_i) pairs with rest=True, rest_i = ((x - y_0) - y_1) - ... in float32, each a view of the
+    one result buffer; every clip's result has the bits maskfilter_stems_batch gives for that clip alone.  One upload each of clips and
+    masks, one launch (k_maskfilter_stems_ragged), one download.  "FT" masks are transposed on the host (pack_ragged_stems_masks).  Window and
+    step_length as in maskfilter_batch."""
+    w = _maskfilter_window(window_function, step_length)
+    arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
+    lengths = np.array([len(a) for a in arrays], np.int64)
+    m, mask_offsets = pack_ragged_stems_masks(masks, lengths, len(w), layout)
+    h = len(w) // 2
+    n_stems = int(mask_offsets[1]) // (((int(lengths[0]) + h - 1) // h + 1) * (h + 1))
+    in_offsets, total = _back_to_back(lengths)   # back to back: the kernel pads every clip through a descriptor of its own
+    x = np.empty(max(total, 1), np.float32)
+    for a, o in zip(arrays, in_offsets.tolist()):
+        x[o:o + len(a)] = a
+    plan = maskfilter_plan(w, rest, "TF", device)
+    blocks = n_stems + (1 if rest else 0)
+    out_offsets = blocks * in_offsets
+    d_mask = DeviceBuffer(m.shape, np.float32, device)
+    try:
+        d_mask.upload(m)
+        res = _round_trip(plan, x, blocks * len(x),
+                          lambda d_in, d_out: plan.execute_masked_stems_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems))
+    finally:
+        d_mask.free()
+    out = [res[o:o + blocks * n].reshape(blocks, n) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return [(b[:n_stems], b[n_stems]) for b in out] if rest else out
 
 
 def cqtspectrogram_batch(clips, sampling_frequency, time_resolution, cqt_kernel, layout="FT", device=0, f64=False, out=None):
