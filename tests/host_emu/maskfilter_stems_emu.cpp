@@ -11,24 +11,9 @@
 
 #include "zafx_maskfilter.hpp"
 #include "zafx_twiddle.hpp"
+#include "fft_runner.hpp"
 
 using namespace zafx;
-
-template <int LOG2N, int LOG2E, int LOG2NS>
-struct Runner {   // fft_frame<LOG2N, LOG2E> with the frame's threads as a loop (as tests/host_emu/fft_emu.cpp)
-    static void run(std::vector<float2>& regs, std::vector<float2>& buf, const float2* tw) {
-        using C = FftCfg<LOG2N, LOG2E>;
-        if constexpr (LOG2NS < LOG2N) {
-            constexpr int LR = pass_log2r(LOG2N - LOG2NS, LOG2E);
-            for (int p = 0; p < C::P; ++p)
-                pass_write<LOG2N, LOG2E, LOG2NS, LR>(&regs[(size_t)p * C::E], buf.data(), p, tw + twiddle_offset(LOG2N, LOG2E, LOG2NS));
-            if constexpr (LOG2NS + LR < LOG2N) {
-                for (int p = 0; p < C::P; ++p) regs_read<LOG2N, LOG2E>(&regs[(size_t)p * C::E], buf.data(), p);
-                Runner<LOG2N, LOG2E, LOG2NS + LR>::run(regs, buf, tw);
-            }
-        }
-    }
-};
 
 template <int LOG2W>
 static void run(const std::vector<float>& win, const std::vector<float>& x, const std::vector<float>& mask, long long n, int stems, bool rest,

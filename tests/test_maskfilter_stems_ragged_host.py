@@ -38,7 +38,7 @@ def tile(wl):
 
 
 def stems_slots(wl, n_stems, cus=CUS):
-    """Workgroups the device holds at once under the stems' LDS size: what LDS admits per compute unit, at most 4 (maskfilter_stems_slots)."""
+    """Workgroups the device holds at once under the stems' LDS size: what LDS admits per compute unit, at most 4 (lds_slots of maskfilter_stems_smem)."""
     return cus * max(1, min(4, LDS // (SMEM_ONE[wl] + (n_stems - 1) * (wl // 2) * 4)))
 
 

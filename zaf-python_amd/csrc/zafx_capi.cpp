@@ -1474,14 +1474,20 @@ int zafx_plan_mask_dims(const zafx_plan* pl, int64_t n_in, int64_t dims[2]) {
     return 0;
 }
 
+// What every launch that divides by the COLA gain asks of the plan's window; `what`: how the message names the transform.
+static int check_window_gain(const zafx_plan* pl, const char* what) {
+    if (!pl->d_window) return fail_msg("window constant not set");
+    if (pl->cola_gain == 0.f) return fail_msg(std::string(what) + ": sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    return 0;
+}
+
 int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
     if (!pl) return fail_msg("null plan");
     if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_execute_masked: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only (every other kind takes zafx_execute)");
     if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
     if (n_clips == 0) return 0;
     if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
-    if (!pl->d_window) return fail_msg("window constant not set");
-    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    if (int rc = check_window_gain(pl, "mask filter")) return rc;
     ZAFX_HIP(hipSetDevice(pl->device));
     return launch_rc("zafx_execute_masked", zafx::launch_maskfilter(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in));
 }
@@ -1497,8 +1503,7 @@ int zafx_execute_masked_stems(zafx_plan* pl, const void* d_in, const void* d_mas
     if (const char* why = zafx::maskfilter_stems_refusal(c, n_stems)) return fail_msg(std::string("zafx_execute_masked_stems: ") + why);
     if (n_clips == 0) return 0;
     if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
-    if (!pl->d_window) return fail_msg("window constant not set");
-    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    if (int rc = check_window_gain(pl, "mask filter")) return rc;
     ZAFX_HIP(hipSetDevice(pl->device));
     return launch_rc("zafx_execute_masked_stems", zafx::launch_maskfilter_stems(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in, n_stems));
 }
@@ -1562,7 +1567,7 @@ int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, 
             break;
         case ZAFX_CENTER:
         case ZAFX_CENTER_SIDES:
-            if (pl->cola_gain == 0.f) return fail_msg("center / sides: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+            if (int rc = check_window_gain(pl, "center / sides")) return rc;
             e = launch_center(*pl, (const float*)d_in, (float*)d_out, n_clips, n_in);
             break;
         case ZAFX_DCT:
@@ -1818,6 +1823,13 @@ int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offse
     return execute_ragged_checked("zafx_execute_ragged", pl, d_in, in_offsets, lengths, d_out, n_clips, 0, &launched);
 }
 
+// The walk kernels read a clip through a buffer descriptor with 32-bit byte offsets; `what`: what a clip's length counts.
+static int check_clips_below_2_28(const char* fn, const int64_t* lengths, int64_t n_clips, const char* what) {
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] >= (1LL << 28)) return fail_msg(std::string(fn) + ": clip " + std::to_string(i) + " has 2^28 " + what + " or more (not supported)");
+    return 0;
+}
+
 // Ragged stereo batches of the center / sides kinds: the host cuts the clips into units (center_cut_units), k_center's RAGGED form walks them.
 int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, const int64_t* out_offsets,
                                int64_t n_clips) {
@@ -1825,11 +1837,8 @@ int zafx_execute_center_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
     bool empty = false;
     if (int rc = ragged_args("zafx_execute_center_ragged", pl, n_clips, wrong_kind, d_in, d_out, {lengths, in_offsets, out_offsets}, "length", &empty)) return rc;
     if (empty) return 0;
-    for (int64_t i = 0; i < n_clips; ++i)
-        if (lengths[i] >= (1LL << 28))
-            return fail_msg("zafx_execute_center_ragged: clip " + std::to_string(i) + " has 2^28 sample frames or more (not supported)");
-    if (!pl->d_window) return fail_msg("window constant not set");
-    if (pl->cola_gain == 0.f) return fail_msg("center / sides: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
+    if (int rc = check_clips_below_2_28("zafx_execute_center_ragged", lengths, n_clips, "sample frames")) return rc;
+    if (int rc = check_window_gain(pl, "center / sides")) return rc;
     int tile_frames = 0;
     long long slots = 0;
     if (!zafx::center_launch_shape(*pl, &tile_frames, &slots)) return fail_msg("center / sides: window_length must be 256, 512, 1024 or 2048");
@@ -1865,6 +1874,33 @@ int zafx_plan_mask_ragged_layout(const zafx_plan* pl, const int64_t* lengths, in
     return 0;
 }
 
+// The tail of zafx_execute_masked_ragged (n_stems = 0: k_maskfilter, masks in the plan's layout) and zafx_execute_masked_stems_ragged
+// (k_maskfilter_stems, compact TF masks: no pitch), behind their argument checks: the window, the kernel's launch shape, the cut, the upload
+// of the units and the launch.
+static int cut_and_launch_masked(const char* fn, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                 const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems) {
+    if (int rc = check_window_gain(pl, "mask filter")) return rc;
+    int tile_transforms = 0;
+    long long slots = 0;
+    if (!(n_stems ? zafx::maskfilter_stems_launch_shape(*pl, n_stems, &tile_transforms, &slots) : zafx::maskfilter_launch_shape(*pl, &tile_transforms, &slots)))
+        return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
+    std::vector<int64_t> pitches(n_stems ? 0 : (size_t)n_clips);
+    for (size_t i = 0; i < pitches.size(); ++i) {
+        int64_t elems = 0;
+        mask_block(pl, lengths[i], &elems, &pitches[i]);
+    }
+    // ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
+    const int per_slot = env_units_per_slot("ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot);
+    const std::vector<zafx::MaskfilterUnit> units = zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, n_stems ? nullptr : pitches.data(), n_clips,
+                                                                               pl->W, tile_transforms, slots, per_slot);
+    ZAFX_HIP(hipSetDevice(pl->device));
+    if (int rc = upload_records(pl, units)) return rc;
+    const auto* d_units = static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get());
+    const float *x = (const float*)d_in, *m = (const float*)d_mask;
+    return launch_rc(fn, n_stems ? zafx::launch_maskfilter_stems_ragged(*pl, x, m, (float*)d_out, d_units, (long long)units.size(), n_stems)
+                                 : zafx::launch_maskfilter_ragged(*pl, x, m, (float*)d_out, d_units, (long long)units.size()));
+}
+
 // Ragged batches of the mask-filter kinds: the host cuts the clips into units of block pairs (maskfilter_cut_units), k_maskfilter's RAGGED form walks them.
 int zafx_execute_masked_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask, const int64_t* mask_offsets,
                                void* d_out, const int64_t* out_offsets, int64_t n_clips) {
@@ -1873,26 +1909,8 @@ int zafx_execute_masked_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
     bool empty = false;
     if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
     if (empty) return 0;
-    for (int64_t i = 0; i < n_clips; ++i)
-        if (lengths[i] >= (1LL << 28)) return fail_msg(std::string(fn) + ": clip " + std::to_string(i) + " has 2^28 samples or more (not supported)");
-    if (!pl->d_window) return fail_msg("window constant not set");
-    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
-    int tile_transforms = 0;
-    long long slots = 0;
-    if (!zafx::maskfilter_launch_shape(*pl, &tile_transforms, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
-    std::vector<int64_t> pitches((size_t)n_clips);
-    for (int64_t i = 0; i < n_clips; ++i) {
-        int64_t elems = 0;
-        mask_block(pl, lengths[i], &elems, &pitches[(size_t)i]);
-    }
-    // ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
-    const int per_slot = env_units_per_slot("ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot);
-    const std::vector<zafx::MaskfilterUnit> units =
-        zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, pitches.data(), n_clips, pl->W, tile_transforms, slots, per_slot);
-    ZAFX_HIP(hipSetDevice(pl->device));
-    if (int rc = upload_records(pl, units)) return rc;
-    return launch_rc(fn, zafx::launch_maskfilter_ragged(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out,
-                                                        static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size()));
+    if (int rc = check_clips_below_2_28(fn, lengths, n_clips, "samples")) return rc;
+    return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0);
 }
 
 // Stems of a ragged batch: a clip's n_stems masks back to back, each as a TF plan's mask_block, and its n_stems (+ 1 with rest) output blocks
@@ -1928,19 +1946,7 @@ int zafx_execute_masked_stems_ragged(zafx_plan* pl, const void* d_in, const int6
     if (empty) return 0;
     if (const char* why = zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, lengths, n_clips, &clip))
         return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
-    if (!pl->d_window) return fail_msg("window constant not set");
-    if (pl->cola_gain == 0.f) return fail_msg("mask filter: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)");
-    int tile_transforms = 0;
-    long long slots = 0;
-    if (!zafx::maskfilter_stems_launch_shape(*pl, n_stems, &tile_transforms, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
-    // ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment, as for zafx_execute_masked_ragged (measurements only)
-    const int per_slot = env_units_per_slot("ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot);
-    const std::vector<zafx::MaskfilterUnit> units =
-        zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, nullptr, n_clips, pl->W, tile_transforms, slots, per_slot);   // (TF masks: no pitch)
-    ZAFX_HIP(hipSetDevice(pl->device));
-    if (int rc = upload_records(pl, units)) return rc;
-    return launch_rc(fn, zafx::launch_maskfilter_stems_ragged(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out,
-                                                              static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size(), n_stems));
+    return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, n_stems);
 }
 
 // What zafx_execute_imdct_ragged and zafx_execute_istft_ragged differ in: both cut their blocks into units of tiles (zafx_units.hpp) that the

@@ -1,7 +1,8 @@
 // zafx_center.hip -- k_center: the center / sides extraction of zaf.istft's example (zaf.py:155-198) in one kernel.
 //
 // Stereo STFT, the two time-frequency masks, both ISTFTs and sides = input - center without a spectrum ever leaving the CU
-// (zafx_center.hpp has the arithmetic and the mask's one departure from the reference).  Structure:
+// (zafx_center.hpp has the arithmetic and the mask's one departure from the reference).  Structure (what it shares with
+// k_maskfilter and k_maskfilter_stems: zafx_overlap_walk.hpp):
 //
 //   * An interleaved stereo sample frame (L, R) IS one complex point of z = L + i R: a frame of W sample frames is loaded as W
 //     float2, multiplied by the window and transformed as ONE W-point complex FFT.  Up to W = 1024 64 lanes own a frame (W / 64
@@ -25,7 +26,7 @@
 
 #include "zafx_center.hpp"
 #include "zafx_units.hpp"
-#include "zafx_internal.hpp"
+#include "zafx_overlap_walk.hpp"
 
 namespace zafx {
 
@@ -65,32 +66,26 @@ __global__ __launch_bounds__(CenterCfg<LOG2W>::NT) void k_center(const float2* _
     unsigned clip_bytes = 0;   // (the launcher keeps every clip below 2^28 sample frames)
     if constexpr (!RAGGED) clip_bytes = (unsigned)(n_samples * 8);
 
-    // RAGGED: the units come ordered by descending length, and the rounds of gridDim.x units are dealt forwards and backwards in turn --
-    // the workgroup that took the longest unit of one round takes the shortest of the next (still a fixed deal: nothing is claimed)
-    const long long n_deal = RAGGED ? (n_units + gridDim.x - 1) / gridDim.x * gridDim.x : n_units;
+    const long long n_deal = deal_rounds<RAGGED>(n_units);   // (zafx_overlap_walk.hpp: the deal)
     int round = 0;
-    for (long long v = blockIdx.x; v < n_deal; v += gridDim.x, ++round) {
-        long long u = v;
-        if constexpr (RAGGED) {
-            if (round & 1) u = (2LL * round + 1) * gridDim.x - 1 - v;
-            if (u >= n_units) continue;   // (the last round may be short; uniform)
-        }
+    for (long long w = blockIdx.x; w < n_deal; w += gridDim.x, ++round) {
+        long long u;
+        if (!deal_unit<RAGGED>(w, round, n_units, u)) continue;   // (the last round may be short; uniform)
         CenterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
         int b0, b1;        // blocks [b0, b1) need frames b0 .. b1
         const float2* xc;
         float2* oc;
         if constexpr (RAGGED) {
-            rc = n_samples[__builtin_amdgcn_readfirstlane((int)u)];   // (the launcher keeps the units below 2^31)
+            rc = read_unit(n_samples, u);
             b0 = rc.b0, b1 = rc.b1;
             xc = x + rc.in_off;
             oc = out + rc.out_off;
             clip_bytes = (unsigned)(rc.n_samples * 8);
         } else {
-            const long long clip = u / n_segs;
-            const int seg = (int)(u - clip * n_segs);
-            b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
-            xc = x + clip * n_samples;
-            oc = out + clip * n_samples * (SIDES ? 2 : 1);
+            const EqualUnit eu = equal_unit(u, n_segs, seg_blocks, n_blocks);
+            b0 = eu.b0, b1 = eu.b1;
+            xc = x + eu.clip * n_samples;
+            oc = out + eu.clip * n_samples * (SIDES ? 2 : 1);
         }
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
         for (int j0 = b0; j0 <= b1; j0 += F) {
@@ -178,35 +173,36 @@ static const char* const kCenterName = kCenterKernel;   // (zafx_routes.hpp)
 static const char* const kCenterRaggedName = "k_center_ragged";
 const char* center_kernel_name() { return kCenterName; }
 
-// workgroups the device holds at once: what LDS admits per CU, at most 4
-template <int LOG2W>
-static long long center_slots(const zafx_plan& pl) {
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / CenterCfg<LOG2W>::SMEM));
-    return (long long)pl.n_cus * per_cu;
+// One launch of k_center<LOG2W, SIDES, RAGGED>.  Equal-length: n clips of n_samples sample frames each, cut here (center_equal_segments).
+// RAGGED (zafx_execute_center_ragged): the n units of d_units, which come cut and ordered from the host (center_cut_units).
+template <int LOG2W, bool SIDES, bool RAGGED>
+static hipError_t run_center(const zafx_plan& pl, const float2* x, float2* out, const CenterUnit* d_units, int64_t n, int64_t n_samples) {
+    using K = CenterCfg<LOG2W>;
+    auto kern = k_center<LOG2W, SIDES, RAGGED>;
+    const long long slots = lds_slots(pl.n_cus, K::SMEM);
+    if constexpr (RAGGED) {
+        return launch_walk<LOG2W>(pl, kern, kCenterRaggedName, K::NT, K::SMEM, n, slots, x, pl.d_window, pl.d_tw_pass, out, d_units, 0, 0, 0);
+    } else {
+        const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
+        if (n_blocks <= 0 || n <= 0) return hipSuccess;
+        const EqualSegments cut = center_equal_segments(n_blocks, n, K::F, slots);
+        return launch_walk<LOG2W>(pl, kern, kCenterName, K::NT, K::SMEM, cut.segs * n, slots, x, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
+                                  (int)n_blocks, (int)cut.seg_blocks, (int)cut.segs);
+    }
 }
 
-template <int LOG2W, bool SIDES>
-static hipError_t run_center(const zafx_plan& pl, const float2* x, float2* out, int64_t n_clips, int64_t n_samples) {
-    using K = CenterCfg<LOG2W>;
-    auto kern = k_center<LOG2W, SIDES, false>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
-    const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
-    if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
-    // segments: whole clips when there are enough of them to load every workgroup; otherwise cut, but never below two tiles
-    // (2 F - 1 blocks) a segment -- each pays one halo frame
-    const long long slots = center_slots<LOG2W>(pl);
-    long long segs = std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
-    if (n_clips >= slots) segs = 1;
-    segs = std::min<long long>(segs, std::max<long long>(1, n_blocks / (2 * K::F - 1)));
-    const int64_t seg_blocks = (n_blocks + segs - 1) / segs;
-    segs = (n_blocks + seg_blocks - 1) / seg_blocks;
-    const long long units = segs * n_clips;
-    const long long grid = std::min<long long>(units, slots);
-    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // ifft's 1 / W, then zaf.py:241
-    pl.ran = kCenterName;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, out, (long long)n_samples, (int)n_blocks,
-                       (int)seg_blocks, (int)segs, units, gain);
-    return hipGetLastError();
+// log2 of the complex FFT length = log2(W): a sample frame is one complex point
+template <bool RAGGED>
+static hipError_t dispatch_center(const zafx_plan& pl, const float* x, float* out, const CenterUnit* d_units, int64_t n, int64_t n_samples) {
+    const float2* xi = reinterpret_cast<const float2*>(x);
+    float2* o = reinterpret_cast<float2*>(out);
+    hipError_t e = hipErrorInvalidValue;
+    if (!dispatch_log2w(pl.log2nf, [&](auto lw) {
+            constexpr int L = decltype(lw)::value;
+            e = pl.kind == ZAFX_CENTER_SIDES ? run_center<L, true, RAGGED>(pl, xi, o, d_units, n, n_samples) : run_center<L, false, RAGGED>(pl, xi, o, d_units, n, n_samples);
+        }))
+        set_error("center / sides: window_length must be 256, 512, 1024 or 2048");
+    return e;
 }
 
 hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_t n_clips, int64_t n_samples) {
@@ -214,45 +210,12 @@ hipError_t launch_center(const zafx_plan& pl, const float* x, float* out, int64_
         set_error("center / sides: clips of 2^28 sample frames and more are not supported");
         return hipErrorInvalidValue;
     }
-    const bool sides = pl.kind == ZAFX_CENTER_SIDES;
-    const float2* xi = reinterpret_cast<const float2*>(x);
-    float2* o = reinterpret_cast<float2*>(out);
-    switch (pl.log2nf) {   // log2 of the complex FFT length = log2(W): a sample frame is one complex point
-        case 8: return sides ? run_center<8, true>(pl, xi, o, n_clips, n_samples) : run_center<8, false>(pl, xi, o, n_clips, n_samples);
-        case 9: return sides ? run_center<9, true>(pl, xi, o, n_clips, n_samples) : run_center<9, false>(pl, xi, o, n_clips, n_samples);
-        case 10: return sides ? run_center<10, true>(pl, xi, o, n_clips, n_samples) : run_center<10, false>(pl, xi, o, n_clips, n_samples);
-        case 11: return sides ? run_center<11, true>(pl, xi, o, n_clips, n_samples) : run_center<11, false>(pl, xi, o, n_clips, n_samples);
-    }
-    set_error("center / sides: window_length must be 256, 512, 1024 or 2048");
-    return hipErrorInvalidValue;
-}
-
-// ---------------------------------------------------------------------------------
-// ragged batches (zafx_execute_center_ragged): the units come cut and ordered from the host (center_cut_units)
-// ---------------------------------------------------------------------------------
-template <int LOG2W, bool SIDES>
-static hipError_t run_center_ragged(const zafx_plan& pl, const float2* x, float2* out, const CenterUnit* d_units, long long n_units) {
-    using K = CenterCfg<LOG2W>;
-    auto kern = k_center<LOG2W, SIDES, true>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
-    pl.ran = kCenterRaggedName;
-    if (n_units <= 0) return hipSuccess;
-    const long long grid = std::min<long long>(n_units, center_slots<LOG2W>(pl));
-    const float gain = 1.f / ((float)K::W * pl.cola_gain);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, pl.d_window, pl.d_tw_pass, out, d_units, 0, 0, 0, n_units, gain);
-    return hipGetLastError();
+    return dispatch_center<false>(pl, x, out, nullptr, n_clips, n_samples);
 }
 
 bool center_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots) {
-    switch (pl.log2nf) {
-        case 8: *slots = center_slots<8>(pl); break;
-        case 9: *slots = center_slots<9>(pl); break;
-        case 10: *slots = center_slots<10>(pl); break;
-        case 11: *slots = center_slots<11>(pl); break;
-        default: return false;
-    }
     *tile_frames = center_tile_frames(pl.log2nf);
-    return true;
+    return dispatch_log2w(pl.log2nf, [&](auto lw) { *slots = lds_slots(pl.n_cus, CenterCfg<decltype(lw)::value>::SMEM); });
 }
 
 hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out, const CenterUnit* d_units, long long n_units) {
@@ -260,17 +223,7 @@ hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out,
         set_error("center / sides: ragged batch too large for one launch (units >= 2^31)");
         return hipErrorInvalidValue;
     }
-    const bool sides = pl.kind == ZAFX_CENTER_SIDES;
-    const float2* xi = reinterpret_cast<const float2*>(x);
-    float2* o = reinterpret_cast<float2*>(out);
-    switch (pl.log2nf) {
-        case 8: return sides ? run_center_ragged<8, true>(pl, xi, o, d_units, n_units) : run_center_ragged<8, false>(pl, xi, o, d_units, n_units);
-        case 9: return sides ? run_center_ragged<9, true>(pl, xi, o, d_units, n_units) : run_center_ragged<9, false>(pl, xi, o, d_units, n_units);
-        case 10: return sides ? run_center_ragged<10, true>(pl, xi, o, d_units, n_units) : run_center_ragged<10, false>(pl, xi, o, d_units, n_units);
-        case 11: return sides ? run_center_ragged<11, true>(pl, xi, o, d_units, n_units) : run_center_ragged<11, false>(pl, xi, o, d_units, n_units);
-    }
-    set_error("center / sides: window_length must be 256, 512, 1024 or 2048");
-    return hipErrorInvalidValue;
+    return dispatch_center<true>(pl, x, out, d_units, n_units, 0);
 }
 
 }  // namespace zafx

@@ -29,7 +29,7 @@
 
 #include "zafx_maskfilter_cfg.hpp"
 #include "zafx_units.hpp"
-#include "zafx_internal.hpp"
+#include "zafx_overlap_walk.hpp"
 
 namespace zafx {
 
@@ -66,28 +66,23 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
         sk = TF ? 4 : mask_pitch * 4;
     }
 
-    // RAGGED: the units come ordered by descending length, and the rounds of gridDim.x units are dealt forwards and backwards in turn, as
-    // k_center's are (still a fixed deal: nothing is claimed)
+    // The deal (zafx_overlap_walk.hpp), as k_center's.
     // (RAGGED counts its units in 32 bits -- the launcher keeps them below 2^31 --: the loop's tests are then scalar compares; 64-bit ones are
     // vector compares that hold n_deal in a VGPR pair through the kernel, and W = 256 / TF has none to spare beside its twin's 64)
     using Cnt = std::conditional_t<RAGGED, unsigned, long long>;
-    const Cnt n_all = (Cnt)n_units;
-    const Cnt n_deal = RAGGED ? (n_all + gridDim.x - 1) / gridDim.x * gridDim.x : n_all;
+    const Cnt n_all = (Cnt)n_units, n_deal = deal_rounds<RAGGED>(n_all);
     unsigned round = 0;
     for (Cnt w = blockIdx.x; w < n_deal; w += gridDim.x, ++round) {
-        Cnt u = w;
-        if constexpr (RAGGED) {
-            if (round & 1) u = (round + 1) * gridDim.x - 1 - blockIdx.x;   // = (2 round + 1) gridDim.x - 1 - w
-            if (u >= n_all) continue;   // (the last round may be short; uniform)
-        }
+        Cnt u;
+        if (!deal_unit<RAGGED>(w, round, n_all, u)) continue;
         MaskfilterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
         int b0, b1;
         const float* xc;
         long long mo;   // the first element of the clip's mask
         float* oc;
         if constexpr (RAGGED) {
-            rc = n_samples[__builtin_amdgcn_readfirstlane((int)u)];   // (the launcher keeps the units below 2^31)
-            if (rc.b1 <= rc.b0) continue;                             // a value-initialised record: no blocks (uniform)
+            rc = read_unit(n_samples, u);
+            if (rc.b1 <= rc.b0) continue;   // a value-initialised record: no blocks (uniform)
             b0 = rc.b0, b1 = rc.b1;
             n_blocks = (int)((rc.n_samples + H - 1) / H);
             xc = x + rc.in_off, mo = rc.mask_off, oc = out + rc.out_off;
@@ -96,12 +91,11 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
             mask_bytes = TF ? (unsigned)(n_blocks + 1) * (unsigned)((H + 1) * 4) : ((unsigned)H * (unsigned)rc.mask_pitch + (unsigned)(n_blocks + 1)) * 4u;
             if constexpr (!TF) sk = rc.mask_pitch * 4;
         } else {
-            const long long clip = u / n_segs;
-            const int seg = (int)(u - clip * n_segs);
-            b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
-            xc = x + clip * n_samples;
-            oc = out + clip * n_samples * (REST ? 2 : 1);
-            mo = clip * mask_clip;
+            const EqualUnit eu = equal_unit(u, n_segs, seg_blocks, n_blocks);
+            b0 = eu.b0, b1 = eu.b1;
+            xc = x + eu.clip * n_samples;
+            oc = out + eu.clip * n_samples * (REST ? 2 : 1);
+            mo = eu.clip * mask_clip;
         }
         const int q0 = b0 >> 1, q1 = b1 >> 1;   // transforms q0 .. q1 hold the frames b0 .. b1 that blocks [b0, b1) need
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
@@ -250,47 +244,39 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, TF>::NT)) void k_maskfilter(c
 
 const char* maskfilter_kernel_name() { return kMaskfilterKernel; }   // (zafx_routes.hpp)
 
-// workgroups the device holds at once: what LDS admits per CU, at most 4
-template <int LOG2W, bool TF>
-static long long maskfilter_slots(const zafx_plan& pl) {
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / MaskfilterCfg<LOG2W, TF>::SMEM));
-    return (long long)pl.n_cus * per_cu;
-}
+static const char* const kMaskfilterRaggedName = "k_maskfilter_ragged";
 
-template <int LOG2W, bool REST, bool TF>
-static hipError_t run_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
+// One launch of k_maskfilter<LOG2W, REST, TF, RAGGED>.  Equal-length: n clips of n_samples samples each, cut here (maskfilter_equal_segments).
+// RAGGED (zafx_execute_masked_ragged): the n units of d_units, which come cut and ordered from the host (maskfilter_cut_units).
+template <int LOG2W, bool REST, bool TF, bool RAGGED>
+static hipError_t run_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, int64_t n, int64_t n_samples) {
     using K = MaskfilterCfg<LOG2W, TF>;
-    auto kern = k_maskfilter<LOG2W, REST, TF, false>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
-    pl.ran = kMaskfilterKernel;
-    const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
-    if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
-    const int64_t T = n_blocks + 1, pitch = TF ? K::H + 1 : row_pitch(pl, T);
-    const int64_t mask_clip = TF ? T * (K::H + 1) : (int64_t)(K::H + 1) * pitch;
-    // segments: whole clips when there are enough of them to load every workgroup; otherwise cut into runs of 2 F m - 2 blocks, m >= 2:
-    // such a run ends on an even block, and its F m transforms -- the halo included -- fill m tiles exactly
-    const long long slots = maskfilter_slots<LOG2W, TF>(pl);
-    long long want = n_clips >= slots ? 1 : std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
-    int64_t seg_blocks = (n_blocks + 1) & ~(int64_t)1;
-    if (want > 1) {
-        const int64_t ideal = (n_blocks + want - 1) / want;
-        const int64_t m = std::max<int64_t>(2, (ideal + 2 + 2 * K::F - 1) / (2 * K::F));
-        seg_blocks = std::min(seg_blocks, 2 * K::F * m - 2);
+    auto kern = k_maskfilter<LOG2W, REST, TF, RAGGED>;
+    const long long slots = lds_slots(pl.n_cus, K::SMEM);
+    if constexpr (RAGGED) {
+        return launch_walk<LOG2W>(pl, kern, kMaskfilterRaggedName, K::NT, K::SMEM, n, slots, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, 0, 0, 0, 0);
+    } else {
+        const int64_t n_blocks = n <= 0 ? 0 : (n_samples + K::H - 1) / K::H;
+        const int64_t T = n_blocks + 1, pitch = TF ? K::H + 1 : row_pitch(pl, T);
+        const int64_t mask_clip = TF ? T * (K::H + 1) : (int64_t)(K::H + 1) * pitch;
+        const EqualSegments cut = n_blocks <= 0 ? EqualSegments{0, 0} : maskfilter_equal_segments(n_blocks, n, K::F, slots);
+        return launch_walk<LOG2W>(pl, kern, kMaskfilterKernel, K::NT, K::SMEM, cut.segs * n, slots, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
+                                  (long long)mask_clip, (int)pitch, (int)n_blocks, (int)cut.seg_blocks, (int)cut.segs);
     }
-    const long long segs = (n_blocks + seg_blocks - 1) / seg_blocks;
-    const long long units = segs * n_clips;
-    const long long grid = std::min<long long>(units, slots);
-    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // ifft's 1 / W, then zaf.py:241
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
-                       (long long)mask_clip, (int)pitch, (int)n_blocks, (int)seg_blocks, (int)segs, units, gain);
-    return hipGetLastError();
 }
 
-template <int LOG2W>
-static hipError_t run_maskfilter_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
+// log2 of the complex FFT length = log2(W): two frames are one W-point transform
+template <bool RAGGED>
+static hipError_t dispatch_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, int64_t n, int64_t n_samples) {
     const bool rest = pl.kind == ZAFX_MASKFILTER_REST, tf = pl.layout == ZAFX_LAYOUT_TF;
-    if (rest) return tf ? run_maskfilter<LOG2W, true, true>(pl, x, mask, out, n_clips, n_samples) : run_maskfilter<LOG2W, true, false>(pl, x, mask, out, n_clips, n_samples);
-    return tf ? run_maskfilter<LOG2W, false, true>(pl, x, mask, out, n_clips, n_samples) : run_maskfilter<LOG2W, false, false>(pl, x, mask, out, n_clips, n_samples);
+    hipError_t e = hipErrorInvalidValue;
+    if (!dispatch_log2w(pl.log2nf, [&](auto lw) {
+            constexpr int L = decltype(lw)::value;
+            if (rest) e = tf ? run_maskfilter<L, true, true, RAGGED>(pl, x, mask, out, d_units, n, n_samples) : run_maskfilter<L, true, false, RAGGED>(pl, x, mask, out, d_units, n, n_samples);
+            else e = tf ? run_maskfilter<L, false, true, RAGGED>(pl, x, mask, out, d_units, n, n_samples) : run_maskfilter<L, false, false, RAGGED>(pl, x, mask, out, d_units, n, n_samples);
+        }))
+        set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return e;
 }
 
 hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples) {
@@ -298,52 +284,15 @@ hipError_t launch_maskfilter(const zafx_plan& pl, const float* x, const float* m
         set_error("mask filter: clips of 2^28 samples and more are not supported");
         return hipErrorInvalidValue;
     }
-    switch (pl.log2nf) {   // log2 of the complex FFT length = log2(W): two frames are one W-point transform
-        case 8: return run_maskfilter_kind<8>(pl, x, mask, out, n_clips, n_samples);
-        case 9: return run_maskfilter_kind<9>(pl, x, mask, out, n_clips, n_samples);
-        case 10: return run_maskfilter_kind<10>(pl, x, mask, out, n_clips, n_samples);
-        case 11: return run_maskfilter_kind<11>(pl, x, mask, out, n_clips, n_samples);
-    }
-    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
-    return hipErrorInvalidValue;
-}
-
-// ---------------------------------------------------------------------------------
-// ragged batches (zafx_execute_masked_ragged): the units come cut and ordered from the host (maskfilter_cut_units)
-// ---------------------------------------------------------------------------------
-static const char* const kMaskfilterRaggedName = "k_maskfilter_ragged";
-
-template <int LOG2W, bool REST, bool TF>
-static hipError_t run_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
-    using K = MaskfilterCfg<LOG2W, TF>;
-    auto kern = k_maskfilter<LOG2W, REST, TF, true>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, K::SMEM); e != hipSuccess) return e;
-    pl.ran = kMaskfilterRaggedName;
-    if (n_units <= 0) return hipSuccess;
-    const long long grid = std::min<long long>(n_units, maskfilter_slots<LOG2W, TF>(pl));
-    const float gain = 1.f / ((float)K::W * pl.cola_gain);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), K::SMEM, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, 0, 0, 0, 0, n_units, gain);
-    return hipGetLastError();
-}
-
-template <int LOG2W>
-static hipError_t run_maskfilter_ragged_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
-    const bool rest = pl.kind == ZAFX_MASKFILTER_REST, tf = pl.layout == ZAFX_LAYOUT_TF;
-    if (rest) return tf ? run_maskfilter_ragged<LOG2W, true, true>(pl, x, mask, out, d_units, n_units) : run_maskfilter_ragged<LOG2W, true, false>(pl, x, mask, out, d_units, n_units);
-    return tf ? run_maskfilter_ragged<LOG2W, false, true>(pl, x, mask, out, d_units, n_units) : run_maskfilter_ragged<LOG2W, false, false>(pl, x, mask, out, d_units, n_units);
+    return dispatch_maskfilter<false>(pl, x, mask, out, nullptr, n_clips, n_samples);
 }
 
 bool maskfilter_launch_shape(const zafx_plan& pl, int* tile_transforms, long long* slots) {
-    const bool tf = pl.layout == ZAFX_LAYOUT_TF;
-    switch (pl.log2nf) {
-        case 8: *slots = tf ? maskfilter_slots<8, true>(pl) : maskfilter_slots<8, false>(pl); break;
-        case 9: *slots = tf ? maskfilter_slots<9, true>(pl) : maskfilter_slots<9, false>(pl); break;
-        case 10: *slots = tf ? maskfilter_slots<10, true>(pl) : maskfilter_slots<10, false>(pl); break;
-        case 11: *slots = tf ? maskfilter_slots<11, true>(pl) : maskfilter_slots<11, false>(pl); break;
-        default: return false;
-    }
     *tile_transforms = maskfilter_tile_transforms(pl.log2nf);
-    return true;
+    return dispatch_log2w(pl.log2nf, [&](auto lw) {
+        constexpr int L = decltype(lw)::value;
+        *slots = lds_slots(pl.n_cus, pl.layout == ZAFX_LAYOUT_TF ? MaskfilterCfg<L, true>::SMEM : MaskfilterCfg<L, false>::SMEM);
+    });
 }
 
 hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
@@ -351,14 +300,7 @@ hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const f
         set_error("mask filter: ragged batch too large for one launch (units >= 2^31)");
         return hipErrorInvalidValue;
     }
-    switch (pl.log2nf) {
-        case 8: return run_maskfilter_ragged_kind<8>(pl, x, mask, out, d_units, n_units);
-        case 9: return run_maskfilter_ragged_kind<9>(pl, x, mask, out, d_units, n_units);
-        case 10: return run_maskfilter_ragged_kind<10>(pl, x, mask, out, d_units, n_units);
-        case 11: return run_maskfilter_ragged_kind<11>(pl, x, mask, out, d_units, n_units);
-    }
-    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
-    return hipErrorInvalidValue;
+    return dispatch_maskfilter<true>(pl, x, mask, out, d_units, n_units, 0);
 }
 
 }  // namespace zafx

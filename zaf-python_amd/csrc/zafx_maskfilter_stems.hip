@@ -5,6 +5,7 @@
 
 #include "zafx_maskfilter_cfg.hpp"
 #include "zafx_units.hpp"
+#include "zafx_overlap_walk.hpp"
 
 namespace zafx {
 
@@ -61,26 +62,21 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
     constexpr int st = (H + 1) * 4;   // bytes from frame to frame of a mask
     const int blocks_out = n_stems + (REST ? 1 : 0);
 
-    // RAGGED: the units come ordered by descending length, and the rounds of gridDim.x units are dealt forwards and backwards in turn, counted
-    // in 32 bits (the launcher keeps them below 2^31), as k_maskfilter's are and for its reasons
+    // The deal (zafx_overlap_walk.hpp); RAGGED counts in 32 bits (the launcher keeps the units below 2^31), as k_maskfilter does and for its reasons
     using Cnt = std::conditional_t<RAGGED, unsigned, long long>;
-    const Cnt n_all = (Cnt)n_units;
-    const Cnt n_deal = RAGGED ? (n_all + gridDim.x - 1) / gridDim.x * gridDim.x : n_all;
+    const Cnt n_all = (Cnt)n_units, n_deal = deal_rounds<RAGGED>(n_all);
     unsigned round = 0;
     for (Cnt w = blockIdx.x; w < n_deal; w += gridDim.x, ++round) {
-        Cnt u = w;
-        if constexpr (RAGGED) {
-            if (round & 1) u = (round + 1) * gridDim.x - 1 - blockIdx.x;   // = (2 round + 1) gridDim.x - 1 - w
-            if (u >= n_all) continue;   // (the last round may be short; uniform)
-        }
+        Cnt u;
+        if (!deal_unit<RAGGED>(w, round, n_all, u)) continue;
         MaskfilterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
         int b0, b1;
         const float* xc;
         float* oc;
         const float* mc;
         if constexpr (RAGGED) {
-            rc = n_samples[__builtin_amdgcn_readfirstlane((int)u)];   // (the launcher keeps the units below 2^31)
-            if (rc.b1 <= rc.b0) continue;                             // a value-initialised record: no blocks (uniform)
+            rc = read_unit(n_samples, u);
+            if (rc.b1 <= rc.b0) continue;   // a value-initialised record: no blocks (uniform)
             b0 = rc.b0, b1 = rc.b1;
             n_blocks = (int)((rc.n_samples + H - 1) / H);
             mask_clip = (long long)(n_blocks + 1) * (H + 1);   // a stem's mask: frames 0 .. n_blocks, compact
@@ -88,12 +84,11 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
             clip_bytes = (unsigned)(rc.n_samples * 4);
             mask_bytes = (unsigned)(n_blocks + 1) * (unsigned)((H + 1) * 4);
         } else {
-            const long long clip = u / n_segs;
-            const int seg = (int)(u - clip * n_segs);
-            b0 = seg * seg_blocks, b1 = min(n_blocks, b0 + seg_blocks);
-            xc = x + clip * n_samples;
-            oc = out + clip * blocks_out * n_samples;
-            mc = mask + clip * n_stems * mask_clip;
+            const EqualUnit eu = equal_unit(u, n_segs, seg_blocks, n_blocks);
+            b0 = eu.b0, b1 = eu.b1;
+            xc = x + eu.clip * n_samples;
+            oc = out + eu.clip * blocks_out * n_samples;
+            mc = mask + eu.clip * n_stems * mask_clip;
         }
         const int q0 = b0 >> 1, q1 = b1 >> 1;
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
@@ -235,46 +230,41 @@ __global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter
 #undef CLIP_N
 }
 
-// workgroups the device holds at once under the stems' LDS size: what LDS admits per CU, at most 4
-template <int LOG2W>
-static long long maskfilter_stems_slots(const zafx_plan& pl, int n_stems) {
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)kMaxLdsBytes / maskfilter_stems_smem<LOG2W>(n_stems)));
-    return (long long)pl.n_cus * per_cu;
-}
+static const char* const kMaskfilterStemsRaggedName = "k_maskfilter_stems_ragged";
 
-template <int LOG2W, bool REST>
-static hipError_t run_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int n_stems) {
+// One launch of k_maskfilter_stems<LOG2W, REST, RAGGED>; the slots follow the stems' LDS size.  Equal-length: n clips of n_samples samples each,
+// cut by k_maskfilter's rule (maskfilter_equal_segments).  RAGGED (zafx_execute_masked_stems_ragged): the n units of d_units, which come cut and
+// ordered from the host (maskfilter_cut_units under the stems' slots).
+template <int LOG2W, bool REST, bool RAGGED>
+static hipError_t run_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, int64_t n, int64_t n_samples,
+                                       int n_stems) {
     using K = MaskfilterCfg<LOG2W, true>;
     static_assert(maskfilter_stems_smem<LOG2W>(kMaskfilterMaxStems) <= (size_t)kMaxLdsBytes, "k_maskfilter_stems: frames + carries + tables exceed LDS");
-    auto kern = k_maskfilter_stems<LOG2W, REST, false>;
+    auto kern = k_maskfilter_stems<LOG2W, REST, RAGGED>;
     const size_t smem = maskfilter_stems_smem<LOG2W>(n_stems);
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, smem); e != hipSuccess) return e;
-    pl.ran = kMaskfilterStemsKernel;
-    const int64_t n_blocks = (n_samples + K::H - 1) / K::H;
-    if (n_blocks <= 0 || n_clips <= 0) return hipSuccess;
-    const int64_t mask_clip = (n_blocks + 1) * (K::H + 1);
-    // segments: run_maskfilter's rule, the slots from the stems' LDS size
-    const long long slots = maskfilter_stems_slots<LOG2W>(pl, n_stems);
-    long long want = n_clips >= slots ? 1 : std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
-    int64_t seg_blocks = (n_blocks + 1) & ~(int64_t)1;
-    if (want > 1) {
-        const int64_t ideal = (n_blocks + want - 1) / want;
-        const int64_t m = std::max<int64_t>(2, (ideal + 2 + 2 * K::F - 1) / (2 * K::F));
-        seg_blocks = std::min(seg_blocks, 2 * K::F * m - 2);
+    const long long slots = lds_slots(pl.n_cus, smem);
+    if constexpr (RAGGED) {
+        return launch_walk<LOG2W>(pl, kern, kMaskfilterStemsRaggedName, K::NT, smem, n, slots, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, n_stems, 0, 0, 0);
+    } else {
+        const int64_t n_blocks = n <= 0 ? 0 : (n_samples + K::H - 1) / K::H;
+        const int64_t mask_clip = (n_blocks + 1) * (K::H + 1);
+        const EqualSegments cut = n_blocks <= 0 ? EqualSegments{0, 0} : maskfilter_equal_segments(n_blocks, n, K::F, slots);
+        return launch_walk<LOG2W>(pl, kern, kMaskfilterStemsKernel, K::NT, smem, cut.segs * n, slots, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
+                                  (long long)mask_clip, n_stems, (int)n_blocks, (int)cut.seg_blocks, (int)cut.segs);
     }
-    const long long segs = (n_blocks + seg_blocks - 1) / seg_blocks;
-    const long long units = segs * n_clips;
-    const long long grid = std::min<long long>(units, slots);
-    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // as run_maskfilter's
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), smem, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
-                       (long long)mask_clip, n_stems, (int)n_blocks, (int)seg_blocks, (int)segs, units, gain);
-    return hipGetLastError();
 }
 
-template <int LOG2W>
-static hipError_t run_maskfilter_stems_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int n_stems) {
-    return pl.kind == ZAFX_MASKFILTER_REST ? run_maskfilter_stems<LOG2W, true>(pl, x, mask, out, n_clips, n_samples, n_stems)
-                                           : run_maskfilter_stems<LOG2W, false>(pl, x, mask, out, n_clips, n_samples, n_stems);
+template <bool RAGGED>
+static hipError_t dispatch_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, int64_t n,
+                                            int64_t n_samples, int n_stems) {
+    hipError_t e = hipErrorInvalidValue;
+    if (!dispatch_log2w(pl.log2nf, [&](auto lw) {
+            constexpr int L = decltype(lw)::value;
+            e = pl.kind == ZAFX_MASKFILTER_REST ? run_maskfilter_stems<L, true, RAGGED>(pl, x, mask, out, d_units, n, n_samples, n_stems)
+                                                : run_maskfilter_stems<L, false, RAGGED>(pl, x, mask, out, d_units, n, n_samples, n_stems);
+        }))
+        set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return e;
 }
 
 hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int64_t n_stems) {
@@ -282,54 +272,13 @@ hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const fl
         set_error(why);
         return hipErrorInvalidValue;
     }
-    switch (pl.log2nf) {
-        case 8: return run_maskfilter_stems_kind<8>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
-        case 9: return run_maskfilter_stems_kind<9>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
-        case 10: return run_maskfilter_stems_kind<10>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
-        case 11: return run_maskfilter_stems_kind<11>(pl, x, mask, out, n_clips, n_samples, (int)n_stems);
-    }
-    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
-    return hipErrorInvalidValue;
-}
-
-// ---------------------------------------------------------------------------------
-// ragged batches (zafx_execute_masked_stems_ragged): the units come cut and ordered from the host (maskfilter_cut_units under the stems' slots)
-// ---------------------------------------------------------------------------------
-static const char* const kMaskfilterStemsRaggedName = "k_maskfilter_stems_ragged";
-
-template <int LOG2W, bool REST>
-static hipError_t run_maskfilter_stems_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
-                                              int n_stems) {
-    using K = MaskfilterCfg<LOG2W, true>;
-    auto kern = k_maskfilter_stems<LOG2W, REST, true>;
-    const size_t smem = maskfilter_stems_smem<LOG2W>(n_stems);
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, smem); e != hipSuccess) return e;
-    pl.ran = kMaskfilterStemsRaggedName;
-    if (n_units <= 0) return hipSuccess;
-    const long long grid = std::min<long long>(n_units, maskfilter_stems_slots<LOG2W>(pl, n_stems));
-    const float gain = 1.f / ((float)K::W * pl.cola_gain);   // as run_maskfilter's
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NT), smem, pl.stream, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, n_stems, 0, 0, 0, n_units, gain);
-    return hipGetLastError();
-}
-
-template <int LOG2W>
-static hipError_t run_maskfilter_stems_ragged_kind(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
-                                                   int n_stems) {
-    return pl.kind == ZAFX_MASKFILTER_REST ? run_maskfilter_stems_ragged<LOG2W, true>(pl, x, mask, out, d_units, n_units, n_stems)
-                                           : run_maskfilter_stems_ragged<LOG2W, false>(pl, x, mask, out, d_units, n_units, n_stems);
+    return dispatch_maskfilter_stems<false>(pl, x, mask, out, nullptr, n_clips, n_samples, (int)n_stems);
 }
 
 bool maskfilter_stems_launch_shape(const zafx_plan& pl, int n_stems, int* tile_transforms, long long* slots) {
     if (n_stems < 1 || n_stems > kMaskfilterMaxStems) return false;
-    switch (pl.log2nf) {
-        case 8: *slots = maskfilter_stems_slots<8>(pl, n_stems); break;
-        case 9: *slots = maskfilter_stems_slots<9>(pl, n_stems); break;
-        case 10: *slots = maskfilter_stems_slots<10>(pl, n_stems); break;
-        case 11: *slots = maskfilter_stems_slots<11>(pl, n_stems); break;
-        default: return false;
-    }
     *tile_transforms = maskfilter_tile_transforms(pl.log2nf);
-    return true;
+    return dispatch_log2w(pl.log2nf, [&](auto lw) { *slots = lds_slots(pl.n_cus, maskfilter_stems_smem<decltype(lw)::value>(n_stems)); });
 }
 
 hipError_t launch_maskfilter_stems_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
@@ -342,14 +291,7 @@ hipError_t launch_maskfilter_stems_ragged(const zafx_plan& pl, const float* x, c
         set_error("mask filter stems: ragged batch too large for one launch (units >= 2^31)");
         return hipErrorInvalidValue;
     }
-    switch (pl.log2nf) {
-        case 8: return run_maskfilter_stems_ragged_kind<8>(pl, x, mask, out, d_units, n_units, (int)n_stems);
-        case 9: return run_maskfilter_stems_ragged_kind<9>(pl, x, mask, out, d_units, n_units, (int)n_stems);
-        case 10: return run_maskfilter_stems_ragged_kind<10>(pl, x, mask, out, d_units, n_units, (int)n_stems);
-        case 11: return run_maskfilter_stems_ragged_kind<11>(pl, x, mask, out, d_units, n_units, (int)n_stems);
-    }
-    set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
-    return hipErrorInvalidValue;
+    return dispatch_maskfilter_stems<true>(pl, x, mask, out, d_units, n_units, 0, (int)n_stems);
 }
 
 }  // namespace zafx

@@ -1,7 +1,8 @@
 // zafx_units.hpp -- a ragged batch cut into the units a RAGGED kernel form walks: k_center's (zafx_center.hip, zafx_execute_center_ragged),
 // k_maskfilter's (zafx_maskfilter.hip, zafx_execute_masked_ragged) and k_maskfilter_stems' (zafx_maskfilter_stems.hip,
 // zafx_execute_masked_stems_ragged: the same records and cut, the slots of the stems' LDS size), k_imdct's (zafx_mdct.hip, zafx_execute_imdct_ragged) and k_istft_ft16's
-// (zafx_stft.hip, zafx_execute_istft_ragged).
+// (zafx_stft.hip, zafx_execute_istft_ragged).  Beside it the cuts of equal-length batches: center_equal_segments / maskfilter_equal_segments for
+// k_center, k_maskfilter and k_maskfilter_stems (their launchers call them), carry_segments for the carry kernels.
 //
 // A clip is a run of pieces: blocks of H = W / 2 sample frames for k_center, pairs of such blocks (one packed transform) for k_maskfilter, tiles
 // of `tile_frames` frames for k_imdct and k_istft_ft16.  One unit = pieces [a, b) of one clip.  A unit that does not start its clip pays a fixed
@@ -24,7 +25,8 @@
 //     k_imdct:  m = 2 tiles:                                                                               floor = 2 x 2 - 1 = 3;
 //     k_istft_ft16: the carry-only tile transforms at most `halo` < 16 of its 16 frames, m = 2 tiles:      floor = 2 x 2 - 1 = 3.
 //
-// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,maskfilter,tile}_units_emu.cpp and the host layer's sanitizer build.
+// Plain C++17, no HIP: hipcc compiles it into the library, g++ into tests/host_emu/{center,maskfilter,tile}_units_emu.cpp, equal_segments_emu.cpp, carry_segments_emu.cpp and the
+// host layer's sanitizer build.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -144,6 +146,33 @@ inline std::vector<MaskfilterUnit> maskfilter_cut_units(const int64_t* lengths, 
                          mask_pitches ? (int)mask_pitches[s.clip] : 0, 0});
     }
     return units;
+}
+
+// ---- k_center, k_maskfilter and k_maskfilter_stems on equal-length batches: every clip has the same n_blocks > 0, cut into `segs` segments of
+// `seg_blocks` blocks (the last one shorter, never empty); unit u = clip * segs + seg.  Whole clips when there are enough of them to load
+// every workgroup slot (n_clips >= slots); otherwise about two units per slot.
+struct EqualSegments { int64_t seg_blocks; long long segs; };
+
+// k_center: never below two tiles (2 F - 1 blocks) a segment -- each pays one halo frame.
+inline EqualSegments center_equal_segments(int64_t n_blocks, int64_t n_clips, int F, long long slots) {
+    long long segs = std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
+    if (n_clips >= slots) segs = 1;
+    segs = std::min<long long>(segs, std::max<long long>(1, n_blocks / (2 * F - 1)));
+    const int64_t seg_blocks = (n_blocks + segs - 1) / segs;
+    return {seg_blocks, (long long)((n_blocks + seg_blocks - 1) / seg_blocks)};
+}
+
+// k_maskfilter, k_maskfilter_stems: seg_blocks is even (a segment starts on a transform of its own), and a cut clip goes into runs of
+// 2 F m - 2 blocks, m >= 2: such a run ends on an even block, and its F m transforms -- the halo included -- fill m tiles exactly.
+inline EqualSegments maskfilter_equal_segments(int64_t n_blocks, int64_t n_clips, int F, long long slots) {
+    const long long want = n_clips >= slots ? 1 : std::max<long long>(1, (2 * slots + n_clips - 1) / n_clips);
+    int64_t seg_blocks = (n_blocks + 1) & ~(int64_t)1;
+    if (want > 1) {
+        const int64_t ideal = (n_blocks + want - 1) / want;
+        const int64_t m = std::max<int64_t>(2, (ideal + 2 + 2 * F - 1) / (2 * F));
+        seg_blocks = std::min<int64_t>(seg_blocks, 2 * (int64_t)F * m - 2);
+    }
+    return {seg_blocks, (long long)((n_blocks + seg_blocks - 1) / seg_blocks)};
 }
 
 // ---- k_imdct and k_istft_ft16: tiles.  One record of the device table, the same for both kernels.  The host deals the rounds (deal_table).

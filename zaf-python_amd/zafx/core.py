@@ -420,20 +420,26 @@ class Plan:
         d_in (clips, n_in) float32 samples, d_mask float32 of mask_shape(n_clips, n_in), d_out of out_shape(n_clips, n_in).  Buffers of another
         dtype or too small for these clips raise ValueError before anything is enqueued."""
         n_clips, n_in = int(n_clips), int(n_in)
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST)   # (another kind: the library says so)
+        self._check_masked("execute_masked", "a float32 mask", "mask_shape(n_clips, n_in)", "these clips", d_in, d_mask, d_out, n_clips, n_in,
+                           ok and (lambda: (self.mask_shape(n_clips, n_in), self.out_shape(n_clips, n_in))))
+        _lib.check(_lib.load().zafx_execute_masked(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked")
+
+    def _check_masked(self, name, masks, shape_call, for_what, d_in, d_mask, d_out, n_clips, n_in, shapes):
+        """execute_masked / execute_masked_stems: the checks of the three buffers.  `shapes`: false where the library itself refuses the call,
+        else a function giving the shapes of the masks and of the output; `name`, `masks`, `shape_call`, `for_what`: the messages' words."""
         if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
-            raise ValueError("execute_masked takes float32 samples, a float32 mask and a float32 output buffer")
+            raise ValueError(f"{name} takes float32 samples, {masks} and a float32 output buffer")
         if n_clips < 0 or n_in < 0:
             raise ValueError("n_clips and n_in must not be negative")
-        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST):   # (another kind: the library says so)
-            need_mask = int(np.prod(self.mask_shape(n_clips, n_in), dtype=np.int64)) * 4
-            need_out = int(np.prod(self.out_shape(n_clips, n_in), dtype=np.int64)) * 4
+        if shapes:
+            mask_shape, out_shape = shapes()
             if d_in.nbytes < n_clips * n_in * 4:
                 raise ValueError("d_in holds fewer than clips x n_in samples")
-            if d_mask.nbytes != need_mask:
-                raise ValueError(f"d_mask must hold mask_shape(n_clips, n_in) = {self.mask_shape(n_clips, n_in)} float32, got {d_mask.nbytes} bytes")
-            if d_out.nbytes < need_out:
-                raise ValueError("d_out is smaller than the plan's output for these clips")
-        _lib.check(_lib.load().zafx_execute_masked(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked")
+            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * 4:
+                raise ValueError(f"d_mask must hold {shape_call} = {mask_shape} float32, got {d_mask.nbytes} bytes")
+            if d_out.nbytes < int(np.prod(out_shape, dtype=np.int64)) * 4:
+                raise ValueError(f"d_out is smaller than the plan's output for {for_what}")
 
     def stems_mask_shape(self, n_clips, n_in, n_stems):
         """Shape of the float32 device array execute_masked_stems() reads its masks from: (clips, stems, frames, W/2 + 1) compact -- a clip's
@@ -453,20 +459,9 @@ class Plan:
         has the bits execute_masked gives that clip with mask s alone.  Buffers of another dtype or of the wrong size raise ValueError before
         anything is enqueued."""
         n_clips, n_in, n_stems = int(n_clips), int(n_in), int(n_stems)
-        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
-            raise ValueError("execute_masked_stems takes float32 samples, float32 masks and a float32 output buffer")
-        if n_clips < 0 or n_in < 0:
-            raise ValueError("n_clips and n_in must not be negative")
-        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:   # (otherwise: the library says so)
-            shape = self.stems_mask_shape(n_clips, n_in, n_stems)
-            need_mask = int(np.prod(shape, dtype=np.int64)) * 4
-            need_out = int(np.prod(self.stems_out_shape(n_clips, n_in, n_stems), dtype=np.int64)) * 4
-            if d_in.nbytes < n_clips * n_in * 4:
-                raise ValueError("d_in holds fewer than clips x n_in samples")
-            if d_mask.nbytes != need_mask:
-                raise ValueError(f"d_mask must hold stems_mask_shape(n_clips, n_in, n_stems) = {shape} float32, got {d_mask.nbytes} bytes")
-            if d_out.nbytes < need_out:
-                raise ValueError("d_out is smaller than the plan's output for these clips and stems")
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS   # (otherwise: the library says so)
+        self._check_masked("execute_masked_stems", "float32 masks", "stems_mask_shape(n_clips, n_in, n_stems)", "these clips and stems", d_in, d_mask, d_out,
+                           n_clips, n_in, ok and (lambda: (self.stems_mask_shape(n_clips, n_in, n_stems), self.stems_out_shape(n_clips, n_in, n_stems))))
         _lib.check(_lib.load().zafx_execute_masked_stems(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, n_stems), "zafx_execute_masked_stems")
 
     def ragged_layout(self, lengths):
@@ -537,33 +532,48 @@ class Plan:
         clip i is lengths[i] samples at element in_offsets[i] of d_in, its mask (shape and pitch as in mask_ragged_layout) starts at element
         mask_offsets[i] of d_mask, its filtered samples go to element out_offsets[i] of d_out and, for a plan with rest, the rest directly
         behind.  mask_offsets may carry the total mask_ragged_layout appends.  Output blocks that overlap are not detected."""
-        in_offsets, lengths, out_offsets = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths"), _as_int64(out_offsets, "out_offsets")
-        mask_offsets = _as_int64(mask_offsets, "mask_offsets")
+        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args("execute_masked_ragged", None, d_in, in_offsets, lengths, d_mask, mask_offsets,
+                                                                                  d_out, out_offsets)
+        _lib.check(_lib.load().zafx_execute_masked_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
+                                                          d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_ragged")
+
+    def _masked_ragged_args(self, name, n_stems, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets):
+        """execute_masked_ragged (n_stems None) / execute_masked_stems_ragged: the per-clip arrays as int64 without the totals the layout calls
+        append, and the checks of the three buffers -> (in_offsets, lengths, mask_offsets, out_offsets).  `name`: the method in the messages."""
+        stems = n_stems is not None
+        in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
+        out_offsets, mask_offsets = _as_int64(out_offsets, "out_offsets"), _as_int64(mask_offsets, "mask_offsets")
         if len(mask_offsets) == len(lengths) + 1:
             mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
+        if stems and len(out_offsets) == len(lengths) + 1:
+            out_offsets = np.ascontiguousarray(out_offsets[:-1])
         if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
             raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
         if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
-            raise ValueError("execute_masked_ragged takes float32 samples, a float32 mask and a float32 output buffer")
-        blocks = 2 if self.kind == _lib.MASKFILTER_REST else 1
-        if (self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and len(lengths)   # (another kind, negative values: the library says so)
-                and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0):
+            raise ValueError(f"{name} takes float32 samples, {'float32 masks' if stems else 'a float32 mask'} and a float32 output buffer")
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and len(lengths)   # (another kind, negative values: the library says so)
+        if stems:   # (... as it does of a stem count or a clip it refuses)
+            ok = ok and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS
+        if ok and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0 and not (
+                stems and int(lengths.max()) >= 1 << 28):
             h = int(self.params.window_length) // 2
             frames = (lengths + h - 1) // h + 1
-            if self.layout == _lib.LAYOUT_FT:   # the last element the kernel may read: row H, the clip's last frame
+            if stems:   # compact "TF" masks back to back
+                mask_ends = mask_offsets + n_stems * frames * (h + 1)
+            elif self.layout == _lib.LAYOUT_FT:   # the last element the kernel may read: row H, the clip's last frame
                 a = max(self.row_align, 1)
                 mask_ends = mask_offsets + h * ((frames + a - 1) // a * a) + frames
             else:
                 mask_ends = mask_offsets + frames * (h + 1)
-            live = lengths > 0   # (a clip of length 0 is skipped: its mask is never read)
+            blocks = (n_stems if stems else 1) + (1 if self.kind == _lib.MASKFILTER_REST else 0)
+            live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
             if int((in_offsets + lengths).max()) * 4 > d_in.nbytes:
                 raise ValueError("a clip reaches past the end of d_in")
             if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
-                raise ValueError("a clip's mask reaches past the end of d_mask")
+                raise ValueError(f"a clip's {'masks reach' if stems else 'mask reaches'} past the end of d_mask")
             if int((out_offsets + blocks * lengths).max()) * 4 > d_out.nbytes:
                 raise ValueError("a clip's result reaches past the end of d_out")
-        _lib.check(_lib.load().zafx_execute_masked_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
-                                                          d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_ragged")
+        return in_offsets, lengths, mask_offsets, out_offsets
 
     def stems_ragged_layout(self, lengths, n_stems):
         """Placement of a ragged stems batch (zafx_plan_stems_ragged_layout, mask filter plans of layout "TF") for clips of `lengths` samples
@@ -585,29 +595,8 @@ class Plan:
         arrays with their totals are accepted as they are).  Clip i's block has the bits execute_masked_stems gives that clip and its masks
         alone.  Output blocks that overlap are not detected."""
         n_stems = int(n_stems)
-        in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
-        mask_offsets, out_offsets = _as_int64(mask_offsets, "mask_offsets"), _as_int64(out_offsets, "out_offsets")
-        if len(mask_offsets) == len(lengths) + 1:
-            mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
-        if len(out_offsets) == len(lengths) + 1:
-            out_offsets = np.ascontiguousarray(out_offsets[:-1])
-        if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
-            raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
-        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
-            raise ValueError("execute_masked_stems_ragged takes float32 samples, float32 masks and a float32 output buffer")
-        if (self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS and len(lengths)   # (otherwise: the library says so)
-                and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0
-                and int(lengths.max()) < 1 << 28):
-            h = int(self.params.window_length) // 2
-            blocks = n_stems + (1 if self.kind == _lib.MASKFILTER_REST else 0)
-            mask_ends = mask_offsets + n_stems * ((lengths + h - 1) // h + 1) * (h + 1)
-            live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
-            if int((in_offsets + lengths).max()) * 4 > d_in.nbytes:
-                raise ValueError("a clip reaches past the end of d_in")
-            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
-                raise ValueError("a clip's masks reach past the end of d_mask")
-            if int((out_offsets + blocks * lengths).max()) * 4 > d_out.nbytes:
-                raise ValueError("a clip's result reaches past the end of d_out")
+        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args("execute_masked_stems_ragged", n_stems, d_in, in_offsets, lengths, d_mask,
+                                                                                  mask_offsets, d_out, out_offsets)
         _lib.check(_lib.load().zafx_execute_masked_stems_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
                                                                 d_out.ptr, _i64p(out_offsets), len(lengths), n_stems), "zafx_execute_masked_stems_ragged")
 
@@ -1373,19 +1362,25 @@ def maskfilter_batch(clips, window_function, masks, step_length=None, rest=False
         raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
     if out.size:
         plan = maskfilter_plan(w, rest, layout, device)
-        x = np.ascontiguousarray(a, dtype=np.float32)
-        d_in, d_mask, d_out = DeviceBuffer(x.shape, np.float32, device), DeviceBuffer(want, np.float32, device), DeviceBuffer(shape, np.float32, device)
-        try:
-            d_in.upload(x)
-            d_mask.upload(np.ascontiguousarray(m, dtype=np.float32))
-            with plan.lock:
-                plan.execute_masked(d_in, d_mask, d_out, n_clips, n)
-                plan.sync()
-                d_out.download(out=out)
-        finally:
-            for b in (d_in, d_mask, d_out):
-                b.free()
+        _masked_round_trip(plan, a, m, out, lambda d_in, d_mask, d_out: plan.execute_masked(d_in, d_mask, d_out, n_clips, n))
     return (out[:, 0], out[:, 1]) if rest else out
+
+
+def _masked_round_trip(plan, clips, masks, out, execute):
+    """maskfilter_batch / maskfilter_stems_batch: clips and masks up as float32, execute(d_in, d_mask, d_out) and the wait under the plan's
+    lock, the result down into `out`."""
+    x, m = np.ascontiguousarray(clips, dtype=np.float32), np.ascontiguousarray(masks, dtype=np.float32)
+    d_in, d_mask, d_out = (DeviceBuffer(b.shape, np.float32, plan.device) for b in (x, m, out))
+    try:
+        d_in.upload(x)
+        d_mask.upload(m)
+        with plan.lock:
+            execute(d_in, d_mask, d_out)
+            plan.sync()
+            d_out.download(out=out)
+    finally:
+        for b in (d_in, d_mask, d_out):
+            b.free()
 
 
 def maskfilter_stems_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
@@ -1421,19 +1416,8 @@ def maskfilter_stems_batch(clips, window_function, masks, step_length=None, rest
         raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
     if out.size:
         plan = maskfilter_plan(w, rest, "TF", device)
-        x = np.ascontiguousarray(a, dtype=np.float32)
-        mt = np.ascontiguousarray(m.transpose(0, 1, 3, 2) if ft else m, dtype=np.float32)
-        d_in, d_mask, d_out = DeviceBuffer(x.shape, np.float32, device), DeviceBuffer(mt.shape, np.float32, device), DeviceBuffer(shape, np.float32, device)
-        try:
-            d_in.upload(x)
-            d_mask.upload(mt)
-            with plan.lock:
-                plan.execute_masked_stems(d_in, d_mask, d_out, n_clips, n, n_stems)
-                plan.sync()
-                d_out.download(out=out)
-        finally:
-            for b in (d_in, d_mask, d_out):
-                b.free()
+        _masked_round_trip(plan, a, m.transpose(0, 1, 3, 2) if ft else m, out,
+                           lambda d_in, d_mask, d_out: plan.execute_masked_stems(d_in, d_mask, d_out, n_clips, n, n_stems))
     return (out[:, :n_stems], out[:, n_stems]) if rest else out
 
 
@@ -1931,19 +1915,25 @@ def centersides_ragged(clips, window_function, step_length=None, sides=True, dev
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
 
 
+def _ragged_mask_items(masks, lengths, window_length, ndim, batch, items):
+    """pack_ragged_masks / pack_ragged_stems_masks: -> (the masks as `ndim`-D arrays, one per clip of `lengths`, H = W/2, the clips' frame counts
+    ceil(N_i / H) + 1); `batch`, `items`: the messages' words."""
+    h = int(window_length) // 2
+    arrays = _as_ragged_items(masks, ndim, batch, items, "mask", empty_ok=True)
+    if len(arrays) != len(lengths):
+        raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
+    return arrays, h, (lengths + h - 1) // h + 1
+
+
 def pack_ragged_masks(masks, lengths, window_length, layout="FT", row_align=0):
     """One contiguous float32 array of a ragged batch's masks: a sequence of real (W/2 + 1, T_i) arrays -- (T_i, W/2 + 1) with layout "TF" --,
     T_i = ceil(lengths[i] / (W/2)) + 1 -> (packed 1-D, mask_offsets of len(lengths) + 1), the layout of Plan.mask_ragged_layout for a plan of
     that window_length, layout and row_align: the masks back to back, "FT" rows at the frame count rounded up to row_align (the pad columns
     are zeros).  A mask of another shape raises ValueError with the clip's index."""
     lengths = _as_lengths(lengths)
-    w, ft = int(window_length), _LAYOUTS[layout] == _lib.LAYOUT_FT
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
     a = max(_as_row_align(row_align, layout), 1)
-    h = w // 2
-    arrays = _as_ragged_items(masks, 2, "ragged mask batch", "2-D masks", "mask", empty_ok=True)
-    if len(arrays) != len(lengths):
-        raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
-    frames = (lengths + h - 1) // h + 1
+    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 2, "ragged mask batch", "2-D masks")
     pitch = (frames + a - 1) // a * a if ft else np.full(len(lengths), h + 1, np.int64)
     offsets = np.zeros(len(lengths) + 1, np.int64)
     offsets[1:] = np.cumsum((h + 1) * pitch if ft else frames * (h + 1))
@@ -1968,23 +1958,30 @@ def maskfilter_ragged(clips, window_function, masks, step_length=None, rest=Fals
     arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
     lengths = np.array([len(a) for a in arrays], np.int64)
     m, mask_offsets = pack_ragged_masks(masks, lengths, len(w), layout)
-    in_offsets, total = _back_to_back(lengths)   # back to back: the kernel pads every clip through a descriptor of its own
-    x = np.empty(max(total, 1), np.float32)
-    for a, o in zip(arrays, in_offsets.tolist()):
-        x[o:o + len(a)] = a
     plan = maskfilter_plan(w, rest, layout, device)
-    blocks = 2 if rest else 1
-    out_offsets = blocks * in_offsets
-    d_mask = DeviceBuffer(m.shape, np.float32, device)
-    try:
-        d_mask.upload(m)
-        res = _round_trip(plan, x, blocks * len(x),
-                          lambda d_in, d_out: plan.execute_masked_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets))
-    finally:
-        d_mask.free()
+    res, out_offsets = _masked_ragged_round_trip(plan, arrays, lengths, m, 2 if rest else 1, lambda d_in, in_offsets, d_mask, d_out, out_offsets:
+                                                 plan.execute_masked_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets))
     if not rest:
         return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+
+
+def _masked_ragged_round_trip(plan, arrays, lengths, packed_masks, blocks, execute):
+    """maskfilter_ragged / maskfilter_stems_ragged: the clips packed back to back (the kernel pads every clip through a descriptor of its own) and
+    the packed masks up, execute(d_in, in_offsets, d_mask, d_out, out_offsets), the result -- `blocks` output blocks of its length per clip,
+    the clips back to back -- down -> (result, out_offsets)."""
+    in_offsets, total = _back_to_back(lengths)
+    x = np.empty(max(total, 1), np.float32)
+    for a, o in zip(arrays, in_offsets.tolist()):
+        x[o:o + len(a)] = a
+    out_offsets = blocks * in_offsets
+    d_mask = DeviceBuffer(packed_masks.shape, np.float32, plan.device)
+    try:
+        d_mask.upload(packed_masks)
+        res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: execute(d_in, in_offsets, d_mask, d_out, out_offsets))
+    finally:
+        d_mask.free()
+    return res, out_offsets
 
 
 def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
@@ -1994,14 +1991,11 @@ def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
     "FT" masks are transposed here, on the host, as maskfilter_stems_batch does.  A mask of another shape, or a stem count that differs from
     the first clip's, raises ValueError with the clip's index."""
     lengths = _as_lengths(lengths)
-    h, ft = int(window_length) // 2, _LAYOUTS[layout] == _lib.LAYOUT_FT
-    arrays = _as_ragged_items(masks, 3, "ragged stems mask batch", "3-D masks, (stems, ...)", "mask", empty_ok=True)
-    if len(arrays) != len(lengths):
-        raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 3, "ragged stems mask batch", "3-D masks, (stems, ...)")
     n_stems = arrays[0].shape[0] if arrays else 1
     if not 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:
         raise ValueError(f"the number of stems, masks[0].shape[0], must be in 1 .. {_lib.MASKFILTER_MAX_STEMS}, got {n_stems}")
-    frames = (lengths + h - 1) // h + 1
     offsets = np.zeros(len(lengths) + 1, np.int64)
     offsets[1:] = np.cumsum(n_stems * frames * (h + 1))
     packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
@@ -2028,20 +2022,10 @@ def maskfilter_stems_ragged(clips, window_function, masks, step_length=None, res
     m, mask_offsets = pack_ragged_stems_masks(masks, lengths, len(w), layout)
     h = len(w) // 2
     n_stems = int(mask_offsets[1]) // (((int(lengths[0]) + h - 1) // h + 1) * (h + 1))
-    in_offsets, total = _back_to_back(lengths)   # back to back: the kernel pads every clip through a descriptor of its own
-    x = np.empty(max(total, 1), np.float32)
-    for a, o in zip(arrays, in_offsets.tolist()):
-        x[o:o + len(a)] = a
     plan = maskfilter_plan(w, rest, "TF", device)
     blocks = n_stems + (1 if rest else 0)
-    out_offsets = blocks * in_offsets
-    d_mask = DeviceBuffer(m.shape, np.float32, device)
-    try:
-        d_mask.upload(m)
-        res = _round_trip(plan, x, blocks * len(x),
-                          lambda d_in, d_out: plan.execute_masked_stems_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems))
-    finally:
-        d_mask.free()
+    res, out_offsets = _masked_ragged_round_trip(plan, arrays, lengths, m, blocks, lambda d_in, in_offsets, d_mask, d_out, out_offsets:
+                                                 plan.execute_masked_stems_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems))
     out = [res[o:o + blocks * n].reshape(blocks, n) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
     return [(b[:n_stems], b[n_stems]) for b in out] if rest else out
 
