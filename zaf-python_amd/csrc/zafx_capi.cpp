@@ -1587,14 +1587,16 @@ int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, 
 // ---------------------------------------------------------------------------------
 // ragged batches: clips of different lengths in one call
 // ---------------------------------------------------------------------------------
-static bool ragged_kind(int kind) {
-    return kind == ZAFX_STFT || kind == ZAFX_MDCT || kind == ZAFX_MEL || kind == ZAFX_MFCC || kind == ZAFX_CQT || kind == ZAFX_CHROMA;
+// What is wrong with a plan of `kind` as the plan of a forward ragged batch (null: nothing -- it takes samples and gives frames)
+static const char* ragged_wrong_kind(int kind) {
+    switch (kind) {
+        case ZAFX_STFT: case ZAFX_MDCT: case ZAFX_MEL: case ZAFX_MFCC: case ZAFX_CQT: case ZAFX_CHROMA: return nullptr;
+    }
+    if (is_center_kind(kind)) return "center / sides plans take clips of one length (ragged stereo batches are not implemented)";
+    return is_maskfilter_kind(kind) ? kMaskedOnly : "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)";
 }
 
-static int64_t out_elem_bytes(const zafx_plan* pl) {
-    const int64_t real = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
-    return pl->kind == ZAFX_STFT && pl->prm.spectrum < ZAFX_SPECTRUM_MAGNITUDE ? 2 * real : real;
-}
+static int64_t out_elem_bytes(const zafx_plan* pl) { return zafx::out_elem_bytes(pl->kind, pl->prm.precision, pl->prm.spectrum); }
 
 // One clip's block of the output (elements) and its frames / row pitch.  Blocks lie back to back, so with rows of whole 128-byte lines every
 // block starts on a line when the array does.
@@ -1610,9 +1612,7 @@ static int ragged_block(const zafx_plan* pl, int64_t len, int64_t* elems, int64_
 int zafx_plan_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int64_t* out_offsets) {
     if (!pl || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
     if (n_clips < 0) return fail_msg("negative size");
-    if (is_center_kind(pl->kind)) return fail_msg("ragged batches: center / sides plans take clips of one length (ragged stereo batches are not implemented)");
-    if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("ragged batches: ") + kMaskedOnly);
-    if (!ragged_kind(pl->kind)) return fail_msg("ragged batches: forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)");
+    if (const char* why = ragged_wrong_kind(pl->kind)) return fail_msg(std::string("ragged batches: ") + why);
     out_offsets[0] = 0;
     for (int64_t i = 0; i < n_clips; ++i) {
         if (lengths[i] < 0) return fail_msg("ragged batch: negative length of clip " + std::to_string(i));
@@ -1701,37 +1701,32 @@ static int ragged_args(const char* fn, const zafx_plan* pl, int64_t n_clips, con
     return 0;
 }
 
-static const char* ragged_wrong_kind(const zafx_plan* pl) {
-    return !pl || ragged_kind(pl->kind) ? nullptr : is_maskfilter_kind(pl->kind) ? kMaskedOnly : !is_center_kind(pl->kind) ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma)"
-                                        : "center / sides plans take clips of one length (ragged stereo batches are not implemented)";
-}
-
 // zafx_execute_ragged (pcm 0) and the one launch of zafx_execute_ragged_pcm (pcm 1 / 2: d_in holds int16 mono / stereo, offsets and lengths
 // count sample frames) behind their argument checks.  pcm != 0 runs a native launch or nothing: *launched tells which (there is no
-// per-clip path for integers; the caller converts first then).
+// per-clip path for integers; the caller converts first then).  Which launch: ragged_route, zafx_routes.hpp.
 static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips,
                                   int pcm, bool* launched) {
-    // every clip's place in the output, frames and pitch; the 16-frame tiles of the batch
+    // 1. every clip's place in the output, frames and pitch, and what the kernels ask of the clips
     std::vector<zafx::RgClip> recs((size_t)n_clips);
+    zafx::RaggedBatch batch;
     const int64_t eb = out_elem_bytes(pl);
-    int64_t out_off = 0, tiles = 0;
-    bool lines = reinterpret_cast<uintptr_t>(d_out) % 128 == 0, short_clips = true, even = pl->H % 2 == 0 && reinterpret_cast<uintptr_t>(d_in) % 8 == 0;
+    int64_t out_off = 0;
     for (int64_t i = 0; i < n_clips; ++i) {
         int64_t elems = 0, frames = 0, pitch = 0;
         if (int rc = ragged_block(pl, lengths[i], &elems, &frames, &pitch)) return rc;
-        zafx::RgClip& r = recs[(size_t)i];
-        r = {in_offsets[i], lengths[i], out_off, (int)std::min<int64_t>(frames, INT32_MAX), (int)std::min<int64_t>(pitch, INT32_MAX), (int)std::min<int64_t>(tiles, INT32_MAX), 0};
-        lines = lines && pl->layout == ZAFX_LAYOUT_FT && (pitch * eb) % 128 == 0 && pitch < INT32_MAX;
-        short_clips = short_clips && lengths[i] < (1LL << 29);
-        // (int16: the fast paths of k_mel2 and k_stft_ft16 test s0 + W <= n per frame / last <= n per tile, so every multi-sample load lies
-        // inside the clip whatever its length's parity, and the tail goes sample by sample: the offsets alone must be even.  The float
-        // route keeps the condition on the lengths it was measured with.)
-        even = even && in_offsets[i] % 2 == 0 && (pcm != 0 || lengths[i] % 2 == 0);
+        recs[(size_t)i] = {in_offsets[i], lengths[i], out_off, (int)std::min<int64_t>(frames, INT32_MAX), (int)std::min<int64_t>(pitch, INT32_MAX),
+                           (int)std::min<int64_t>(batch.tiles16, INT32_MAX), 0};   // (first_tile: of 16-frame tiles, what rg_assign_tiles gives)
+        batch.add(in_offsets[i], lengths[i], frames, pitch, eb);
         out_off += elems;
-        tiles += (frames + 15) / 16;
-        if (tiles >= (1LL << 31)) return fail_msg(std::string(fn) + ": batch too large for one launch (16-frame tiles >= 2^31)");
+        if (batch.too_large()) return fail_msg(std::string(fn) + ": batch too large for one launch (16-frame tiles >= 2^31)");
     }
     ZAFX_HIP(hipSetDevice(pl->device));
+    // 2. the launch (the switches in the environment: measurements only, include/zafx.h -- tools/ragged_rates.py times both sides in one
+    // process; each is read only by the plans whose route asks it: float MDCT batches, float64 plans)
+    const bool f64 = pl->prm.precision == ZAFX_PRECISION_F64;
+    const zafx::RaggedAnswer route = zafx::ragged_route(zafx::route_call(*pl, d_in, d_out, n_clips, 0, 0), batch, pcm,
+                                                        pl->kind != ZAFX_MDCT || f64 || pcm != 0 || env_on("ZAFX_RAGGED_MDCT_NATIVE"),
+                                                        !f64 || env_on("ZAFX_RAGGED_F64_NATIVE"));
     // (int16 in the loads: the launcher takes the calling thread's mode, as under zafx_execute_pcm; a launcher that did not read integers fails hard)
     auto launch_pcm = [&](auto&& launch) {
         zafx::set_pcm_mode(pcm);
@@ -1742,69 +1737,25 @@ static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_i
         if (rc == 0 && pcm != 0 && !taken) return fail_msg(std::string("internal: the ragged launch did not take the int16 input it was promised to (") + fn + ")");
         return rc;
     };
-    // native, MDCT: k_mdct_ft32 in its RAGGED form (float32, reference layout, W = 512 / 1024 / 2048, every clip's rows whole 128-byte lines).
-    // Its tiles are 32 frames: the records' first_tile and the batch's tile count are redone for them (the 16-frame count summed above
-    // still bounds the call, as it does for every kind: 2^31 sixteen-frame tiles are 2^35 frames, no batch that fits a device).  Every
-    // clip is read through a buffer descriptor of its own with 32-bit byte offsets: a batch with a clip of 2^28 samples (1 GiB) or more stays
-    // per clip.  16-byte loads when the array is on 16 bytes and every offset and length is a multiple of 4 samples (a piece is inside or
-    // outside its clip as a whole); 4-byte loads for any other batch.  ZAFX_RAGGED_MDCT_NATIVE=0 in the environment keeps the batch on the
-    // per-clip path (measurements only, include/zafx.h: tools/ragged_rates.py times both in one process).
-    if (pl->kind == ZAFX_MDCT && pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->bs_log2m == 0 && lines &&
-        zafx::mdct_ragged_native(*pl)) {
-        const long long tiles32 = zafx::rg_assign_tiles(recs.data(), recs.size(), zafx::kMdctRaggedTile);
-        bool aligned = reinterpret_cast<uintptr_t>(d_in) % 16 == 0, short_enough = reinterpret_cast<uintptr_t>(d_in) % 4 == 0;
-        for (const zafx::RgClip& r : recs) {
-            aligned = aligned && r.in_off % 4 == 0 && r.n_samples % 4 == 0;
-            short_enough = short_enough && r.n_samples < (1LL << 28);
-        }
-        // int16 (W = 2048 only): the 16-byte-piece form alone -- whole pieces inside or outside a clip, here 8 bytes mono and 16 stereo; the
-        // range check of a partial piece is not relied on.  Its switch is ZAFX_RAGGED_PCM_NATIVE, read by the caller.
-        const bool route = pcm != 0 ? aligned && pl->log2nf == 9 : env_on("ZAFX_RAGGED_MDCT_NATIVE");
-        if (tiles32 < (1LL << 31) && short_enough && route) {
-            if (int rc = upload_ragged_table(pl, recs, tiles32, zafx::kMdctRaggedTile)) return rc;
-            return launch_pcm([&] {
-                return zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, static_cast<const zafx::RgClip*>(pl->d_ragged.get()), n_clips, tiles32, aligned);
-            });
-        }
-    }
-    // native, float64: the tiled kernels of W = 2048 in their RAGGED forms -- k_stft_ft8_f64 (the complex kinds; 8-frame tiles), k_mdct_ft16_f64,
-    // k_mel_ft8_f64 (mel and mfcc; 16-frame tiles) -- for the plans their equal-length launchers send there (one predicate each, zafx_f64.hip),
-    // on the reference layout with every clip's rows whole 128-byte lines, d_out on 128 bytes and d_in on 16.  Offsets and lengths are free:
-    // a frame that starts an even number of samples into d_in and lies inside its clip comes by 16-byte loads, every other one sample by
-    // sample.  The STFT's tiles are 8 frames: first_tile and the tile count are redone for them, and that count is the one bounded.
-    // ZAFX_RAGGED_F64_NATIVE=0 in the environment keeps the batch on the per-clip path (measurements only, include/zafx.h).
-    if (pcm == 0 && pl->prm.precision == ZAFX_PRECISION_F64 && pl->d_window64 && lines && reinterpret_cast<uintptr_t>(d_in) % 16 == 0 &&
-        (pl->kind == ZAFX_STFT   ? zafx::stft_f64_tiled(*pl)
-         : pl->kind == ZAFX_MDCT ? zafx::mdct_f64_tiled(*pl)
-                                 : (pl->kind == ZAFX_MEL || pl->kind == ZAFX_MFCC) && zafx::mel_f64_tiled(*pl)) &&
-        env_on("ZAFX_RAGGED_F64_NATIVE")) {
-        const int tile_frames = pl->kind == ZAFX_STFT ? zafx::kStft64RaggedTile : zafx::kMd64RaggedTile;
-        const long long tiles64 = zafx::rg_assign_tiles(recs.data(), recs.size(), tile_frames);
-        if (tiles64 < (1LL << 31)) {
-            if (int rc = upload_ragged_table(pl, recs, tiles64, tile_frames)) return rc;
-            const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged.get());
-            *launched = true;
-            return launch_rc(fn, pl->kind == ZAFX_STFT   ? zafx::launch_stft_f64_ragged(*pl, (const double*)d_in, (double2*)d_out, tab, n_clips, tiles64)
-                                 : pl->kind == ZAFX_MDCT ? zafx::launch_mdct_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles64)
-                                                         : zafx::launch_mel_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles64));
-        }
-    }
-    if (pcm != 0 && pl->kind == ZAFX_MDCT) return 0;
-    // native: k_stft_ft16 / k_mel2 in their RAGGED forms (float32, reference layout, every clip's rows whole 128-byte lines)
-    const bool on_mel2 = zafx::mel_ragged_native(*pl);
-    const bool native = pl->prm.precision == ZAFX_PRECISION_F32 && pl->layout == ZAFX_LAYOUT_FT && pl->d_window && lines &&
-                        (pl->kind == ZAFX_STFT ? zafx::stft_ragged_native(*pl) && (!on_mel2 || short_clips) : on_mel2 && short_clips);
-    // (int16: W = 2048 -- k_mel2's geometry, the complex kinds of k_stft_ft16 --, even hop and offsets, d_in on 8 bytes, clips below 2^29 frames)
-    if (pcm != 0 && !(native && pl->log2nf == 10 && even && short_clips)) return 0;
-    if (native) {
-        if (int rc = upload_ragged_table(pl, recs, tiles)) return rc;
+    // 3. a native launch: the table for the answered tile size (the records came counting 16-frame tiles), then the kernel's RAGGED form
+    if (route.k == zafx::RaggedRoute::PcmNotTaken) return 0;
+    if (route.k != zafx::RaggedRoute::PerClip) {
+        const long long tiles = route.tile_frames == 16 ? batch.tiles16 : zafx::rg_assign_tiles(recs.data(), recs.size(), route.tile_frames);
+        if (int rc = upload_ragged_table(pl, recs, tiles, route.tile_frames)) return rc;
         const zafx::RgClip* tab = static_cast<const zafx::RgClip*>(pl->d_ragged.get());
         return launch_pcm([&] {
-            return pl->kind == ZAFX_STFT ? zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, even)
-                                         : zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, even);
+            switch (route.k) {
+                case zafx::RaggedRoute::MdctNative: return zafx::launch_mdct_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, route.aligned);
+                case zafx::RaggedRoute::StftNative: return zafx::launch_stft_ragged(*pl, (const float*)d_in, (float2*)d_out, tab, n_clips, tiles, route.aligned);
+                case zafx::RaggedRoute::MelNative: return zafx::launch_mel_ragged(*pl, (const float*)d_in, (float*)d_out, tab, n_clips, tiles, route.aligned);
+                default: break;   // F64Native: k_stft_ft8_f64 (the complex kinds), k_mdct_ft16_f64, k_mel_ft8_f64 (mel and mfcc)
+            }
+            return pl->kind == ZAFX_STFT   ? zafx::launch_stft_f64_ragged(*pl, (const double*)d_in, (double2*)d_out, tab, n_clips, tiles)
+                   : pl->kind == ZAFX_MDCT ? zafx::launch_mdct_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles)
+                                           : zafx::launch_mel_f64_ragged(*pl, (const double*)d_in, (double*)d_out, tab, n_clips, tiles);
         });
     }
-    // everything else: one zafx_execute per clip on the plan's stream, into the same blocks
+    // 4. everything else: one zafx_execute per clip on the plan's stream, into the same blocks
     const int64_t ib = pl->prm.precision == ZAFX_PRECISION_F64 ? 8 : 4;
     pl->ran.store(nullptr, std::memory_order_release);
     for (int64_t i = 0; i < n_clips; ++i) {
@@ -1818,7 +1769,7 @@ static int execute_ragged_checked(const char* fn, zafx_plan* pl, const void* d_i
 
 int zafx_execute_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, void* d_out, int64_t n_clips) {
     bool empty = false, launched = false;
-    if (int rc = ragged_args("zafx_execute_ragged", pl, n_clips, ragged_wrong_kind(pl), d_in, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
+    if (int rc = ragged_args("zafx_execute_ragged", pl, n_clips, pl ? ragged_wrong_kind(pl->kind) : nullptr, d_in, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
     if (empty) return 0;
     return execute_ragged_checked("zafx_execute_ragged", pl, d_in, in_offsets, lengths, d_out, n_clips, 0, &launched);
 }
@@ -1958,8 +1909,8 @@ struct TileRagged {
     const char* zero_gain;                   // what it says of a COLA gain of zero (null: the kind divides by none)
     const char *env_native, *env_per_slot;   // the measurement switches (include/zafx.h) ...
     int per_slot;                            // ... and what the second is preset to
-    bool (*plan_native)(const zafx_plan&);                    // the plan has the RAGGED form
-    bool (*block_native)(const zafx_plan&, int64_t frames);   // ... and a block of `frames` frames can go into its launch
+    bool (*plan_native)(const zafx::RouteCall&);    // the plan has the RAGGED form (zafx_routes.hpp) ...
+    bool (*block_native)(const zafx::RouteCall&);   // ... and a block of T frames can go into its launch
     bool (*launch_shape)(const zafx_plan&, int* tile_frames, long long* slots);
     std::vector<zafx::TileUnit> (*cut)(const zafx_plan&, const int64_t* frames, int64_t n_clips, int tile_frames, long long slots, int per_slot);
     long long (*out_len)(const zafx_plan&, long long frames);   // samples a block gives (none: the per-clip path passes over it)
@@ -1975,8 +1926,12 @@ static int execute_tile_ragged(const TileRagged& k, zafx_plan* pl, const void* d
     if (empty) return 0;
     if (!pl->d_window && !pl->d_window64) return fail_msg("window constant not set");
     if (k.zero_gain && pl->cola_gain == 0.f) return fail_msg(k.zero_gain);
-    bool native = k.plan_native(*pl) && reinterpret_cast<uintptr_t>(d_in) % 4 == 0 && env_on(k.env_native);
-    for (int64_t i = 0; native && i < n_clips; ++i) native = k.block_native(*pl, frames[i]);
+    zafx::RouteCall call = zafx::route_call(*pl, d_in, d_out, n_clips, 0, 0);
+    bool native = k.plan_native(call) && zafx::ragged_blocks_base_ok(call) && env_on(k.env_native);
+    for (int64_t i = 0; native && i < n_clips; ++i) {
+        call.T = (int)std::min<int64_t>(frames[i], INT32_MAX);
+        native = k.block_native(call);
+    }
     ZAFX_HIP(hipSetDevice(pl->device));
     int tile_frames = 0;
     long long slots = 0;
@@ -2003,17 +1958,15 @@ static int execute_tile_ragged(const TileRagged& k, zafx_plan* pl, const void* d
 }
 
 // Ragged batches of the IMDCT: coefficient blocks of different frame counts.  The host cuts the blocks into units (imdct_cut_units), k_imdct's
-// RAGGED form walks them in one launch: float32, reference layout, W = 512 / 1024 / 2048, no Bluestein part, every block's pitch a multiple of
-// 4 floats (the 16-byte gather), every block below 2^32 bytes (a buffer descriptor per clip), units below 2^31.  Everything else -- the
-// frame-major layout, float64, W = 4096 / 8192, W <= 256, compact pitches off the 4-float grid -- runs one zafx_execute per clip on the plan's
-// stream and reports that kernel; the blocks it passes over are those of at most one frame (an MDCT window has W >= 4, so M (T - 1) - 1 > 0
-// from T = 2 on).  ZAFX_RAGGED_IMDCT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only, include/zafx.h);
-// ZAFX_IMDCT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+// RAGGED form walks them in one launch for the plans and blocks zafx_routes.hpp names (imdct_ragged_native, imdct_ragged_block).  Everything
+// else runs one zafx_execute per clip on the plan's stream and reports that kernel; the blocks it passes over are those of at most one frame
+// (an MDCT window has W >= 4, so M (T - 1) - 1 > 0 from T = 2 on).  ZAFX_RAGGED_IMDCT_NATIVE=0 in the environment keeps a batch on the per-clip
+// path, ZAFX_IMDCT_UNITS_PER_SLOT sets the units per workgroup slot the segment length aims at (1 ... 64; both measurements only, include/zafx.h).
 static const TileRagged kImdctRagged = {
     "zafx_execute_imdct_ragged", ZAFX_IMDCT, "inverse MDCT plans (ZAFX_IMDCT) only (zafx_execute_ragged takes the forward kinds)", nullptr,
     "ZAFX_RAGGED_IMDCT_NATIVE", "ZAFX_IMDCT_UNITS_PER_SLOT", zafx::kImdctUnitsPerSlot,
     zafx::imdct_ragged_native,
-    [](const zafx_plan& pl, int64_t frames) { return row_pitch(pl, frames) % 4 == 0 && (long long)(pl.W / 2) * row_pitch(pl, frames) * 4 < (1LL << 32); },
+    zafx::imdct_ragged_block,
     zafx::imdct_launch_shape,
     [](const zafx_plan&, const int64_t* frames, int64_t n, int tile_frames, long long slots, int per_slot) { return zafx::imdct_cut_units(frames, n, tile_frames, slots, per_slot); },
     [](const zafx_plan& pl, long long frames) { return zafx::imdct_out_len(frames, pl.W / 2); },
@@ -2027,17 +1980,15 @@ int zafx_execute_imdct_ragged(zafx_plan* pl, const void* d_coefs, const int64_t*
 }
 
 // Ragged batches of the inverse STFT: spectra of different frame counts.  The host cuts the blocks into units (istft_cut_units), k_istft_ft16's
-// RAGGED form walks them in one launch: float32, reference layout, W = 256 ... 2048, no Bluestein part, halo < 16, every block below 2^31
-// bytes counted as W rows (a buffer descriptor per clip, signed 32-bit byte offsets: run_istft's bound), units below 2^31.  Everything else
-// -- the frame-major layout, float64, W = 4096 / 8192, W < 256, Bluestein windows, smaller hops -- runs one zafx_execute per clip on the plan's
-// stream and reports that kernel.  ZAFX_RAGGED_ISTFT_NATIVE=0 in the environment keeps a batch on the per-clip path (measurements only,
-// include/zafx.h); ZAFX_ISTFT_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only).
+// RAGGED form walks them in one launch for the plans and blocks zafx_routes.hpp names (istft_ragged_native, istft_ragged_block).  Everything
+// else runs one zafx_execute per clip on the plan's stream and reports that kernel.  ZAFX_RAGGED_ISTFT_NATIVE=0 in the environment keeps a
+// batch on the per-clip path, ZAFX_ISTFT_UNITS_PER_SLOT sets the units per workgroup slot (1 ... 64; both measurements only, include/zafx.h).
 static const TileRagged kIstftRagged = {
     "zafx_execute_istft_ragged", ZAFX_ISTFT, "inverse STFT plans (ZAFX_ISTFT) only (zafx_execute_ragged takes the forward kinds)",
     "istft: sum(window[0:W:H]) is zero (zaf.py:241 would divide by zero)",
     "ZAFX_RAGGED_ISTFT_NATIVE", "ZAFX_ISTFT_UNITS_PER_SLOT", zafx::kIstftUnitsPerSlot,
     zafx::istft_ragged_native,
-    [](const zafx_plan& pl, int64_t frames) { return frames < (1LL << 28) && (long long)pl.W * row_pitch(pl, frames) * 8 < (1LL << 31); },
+    zafx::istft_ragged_block,
     zafx::istft_launch_shape,
     [](const zafx_plan& pl, const int64_t* frames, int64_t n, int tile_frames, long long slots, int per_slot) { return zafx::istft_cut_units(frames, n, pl.W, pl.H, tile_frames, slots, per_slot); },
     [](const zafx_plan& pl, long long frames) { return zafx::istft_out_len(frames, pl.W, pl.H); },
@@ -2190,16 +2141,16 @@ int zafx_execute_ragged_pcm(zafx_plan* pl, const void* d_pcm, const int64_t* in_
                             int sample_bytes) {
     const char* fn = "zafx_execute_ragged_pcm";
     const char* wrong_kind = !pl ? nullptr : pl->kind == ZAFX_DCT ? "forward kinds that take samples only (stft, mdct, mel, mfcc, cqt, chroma): a DCT plan takes zafx_execute_pcm"
-                                                                  : ragged_wrong_kind(pl);
+                                                                  : ragged_wrong_kind(pl->kind);
     bool empty = false;
     if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_pcm, d_out, {lengths, in_offsets}, "length", &empty)) return rc;
     if (n_channels < 1 || n_channels > 64) return fail_msg("n_channels must be in [1, 64]");
     if (sample_bytes != 2 && sample_bytes != 4) return fail_msg("sample_bytes must be 2 (int16) or 4 (int32)");
     if (pl->prm.precision != ZAFX_PRECISION_F32) return fail_msg("PCM ingest feeds the float32 plans");
     if (empty) return 0;
-    if (sample_bytes == 2 && n_channels <= 2 && env_on("ZAFX_RAGGED_PCM_NATIVE")) {
+    if (const int pcm = zafx::ragged_pcm_mode(n_channels, sample_bytes, env_on("ZAFX_RAGGED_PCM_NATIVE"))) {
         bool launched = false;
-        const int rc = execute_ragged_checked(fn, pl, d_pcm, in_offsets, lengths, d_out, n_clips, n_channels, &launched);
+        const int rc = execute_ragged_checked(fn, pl, d_pcm, in_offsets, lengths, d_out, n_clips, pcm, &launched);
         if (rc || launched) return rc;
     }
     ZAFX_HIP(hipSetDevice(pl->device));

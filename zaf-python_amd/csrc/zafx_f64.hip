@@ -1844,7 +1844,7 @@ hipError_t launch_stft_f64_ragged(const zafx_plan& pl, const double* x, double2*
     const size_t smem8 = (size_t)kF64Frames * kF64Pitch * sizeof(double2) + kF64Frames * sizeof(double);
     auto k8 = pl.prm.spectrum == ZAFX_SPECTRUM_ONE_SIDED ? k_stft_ft8_f64<true, true> : k_stft_ft8_f64<false, true>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k8), pl.device, smem8); e != hipSuccess) return e;
-    pl.ran = "k_stft_ft8_f64_ragged";
+    pl.ran = kernel_name(RaggedKernel::Stft64);
     hipLaunchKernelGGL(k8, dim3((unsigned)std::min<long long>(total_tiles, (long long)pl.n_cus * (kF64Frames <= 4 ? 2 : 1))), dim3(kF64Frames * 64), smem8, pl.stream, x, pl.d_window64,
                        pl.d_tw64, pl.d_tws64, out, d_tab, pl.H, 0, 0, (int)n_clips, (int)total_tiles);
     return hipGetLastError();
@@ -1854,7 +1854,7 @@ hipError_t launch_mdct_f64_ragged(const zafx_plan& pl, const double* x, double* 
     const size_t smem16 = (size_t)kMd64Frames * kMd64Pitch * sizeof(double2);
     auto k16 = k_mdct_ft16_f64<true>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k16), pl.device, smem16); e != hipSuccess) return e;
-    pl.ran = "k_mdct_ft16_f64_ragged";
+    pl.ran = kernel_name(RaggedKernel::Mdct64);
     hipLaunchKernelGGL(k16, dim3((unsigned)std::min<long long>(total_tiles, pl.n_cus)), dim3(kMd64Frames * 64), smem16, pl.stream, x, pl.d_window64, pl.d_tw64, pl.d_tws64, out,
                        d_tab, 0, 0, (int)n_clips, (int)total_tiles);
     return hipGetLastError();
@@ -1865,7 +1865,7 @@ hipError_t launch_mel_f64_ragged(const zafx_plan& pl, const double* x, double* o
     const size_t smem8 = (size_t)kF64Frames * kF64Pitch * sizeof(double2) + (size_t)kMel64Rows * kMel64OutPitch * sizeof(double);
     auto k8 = mfcc ? k_mel_ft8_f64<true, true> : k_mel_ft8_f64<false, true>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k8), pl.device, smem8); e != hipSuccess) return e;
-    pl.ran = "k_mel_ft8_f64_ragged";
+    pl.ran = kernel_name(RaggedKernel::Mel64);
     hipLaunchKernelGGL(k8, dim3((unsigned)std::min<long long>(total_tiles, pl.n_cus)), dim3(kF64Frames * 64), smem8, pl.stream, x, pl.d_window64, pl.d_tw64, pl.d_tws64,
                        pl.d_mel64_stream, pl.d_mel64_fin, pl.d_mel64_dctT, out, d_tab, pl.H, 0, 0, (int)n_clips, (int)total_tiles, pl.prm.n_filters,
                        mfcc ? pl.prm.n_coefs : 0, pl.mel64_steps, pl.mel64_slots, pl.mel64_max_parts, pl.mel64_cpitch, pl.mel64_dct_half);

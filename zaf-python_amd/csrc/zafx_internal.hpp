@@ -284,18 +284,20 @@ template <bool RAGGED>
 using UnitTableArg = std::conditional_t<RAGGED, const TileUnit*, long long>;
 hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
-bool spec2_ragged(const zafx_plan& pl);   // |X| / |X|^2 at W = 2048 on k_mel2 (what launch_spec2 takes)
-bool stft_ragged_native(const zafx_plan& pl);   // the plans whose ragged batches have a kernel of their own (zafx_execute_ragged)
-bool mel_ragged_native(const zafx_plan& pl);
-// k_mdct_ft32's RAGGED form: the table counts 32-frame tiles (kMdctTile); `aligned`: 16-byte buffer loads (d_in on 16 bytes, every offset and
-// length a multiple of 4 samples), else 4-byte buffer loads (any offsets and lengths); every length below 2^28 in both
-constexpr int kMdctRaggedTile = 32;
-bool mdct_ragged_native(const zafx_plan& pl);
+// (the plans whose ragged batches have a kernel of their own: stft_ragged_native, mel_ragged_native, mdct_ragged_native of zafx_routes.hpp)
+// k_mdct_ft32's RAGGED form: the table counts 32-frame tiles (kMdctRaggedTile); `aligned`: 16-byte buffer loads (d_in on 16 bytes, every offset
+// and length a multiple of 4 samples), else 4-byte buffer loads (any offsets and lengths); every length below 2^28 in both
 hipError_t launch_mdct_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles, bool aligned);
 
 // Every launcher enqueues on plan.stream and returns hipGetLastError().
 // Frames between the starts of consecutive rows of a plan's (F, T) array: the rule of zafx_routes.hpp.
 inline int64_t row_pitch(const zafx_plan& pl, int64_t T) { return row_pitch(pl.layout, pl.prm.row_align, T); }
+
+// The tiled float64 kernels (W = 2048, reference layout): the plans each takes -- one predicate per kernel (zafx_f64.hip), shared by the
+// equal-length launcher and, through RouteCall::f64_tiled, the ragged route
+bool stft_f64_tiled(const zafx_plan& pl);
+bool mdct_f64_tiled(const zafx_plan& pl);
+bool mel_f64_tiled(const zafx_plan& pl);
 
 // What the route conditions (zafx_routes.hpp) read of one call on this plan.  `n`: samples of a clip (the inverses: unused), `T`: frames.
 inline RouteCall route_call(const zafx_plan& pl, const void* in, const void* out, int64_t n_clips, int64_t n, int T, int64_t out_len = 0) {
@@ -308,6 +310,11 @@ inline RouteCall route_call(const zafx_plan& pl, const void* in, const void* out
     c.window16 = reinterpret_cast<uintptr_t>(pl.d_window.get()) % 16 == 0;
     c.claim = pl.stft_dynamic && pl.d_claim.get() != nullptr;
     c.mel2 = pl.fb.whole_ok && pl.fb.n_waves == 16 && (pl.kind != ZAFX_MFCC || pl.dct.dct2_ok);
+    c.window = pl.d_window.get() != nullptr, c.wfold = pl.d_wfold.get() != nullptr;
+    c.f64_tiled = pl.prm.precision == ZAFX_PRECISION_F64 && pl.d_window64.get() != nullptr &&
+                  (pl.kind == ZAFX_STFT   ? stft_f64_tiled(pl)
+                   : pl.kind == ZAFX_MDCT ? mdct_f64_tiled(pl)
+                                          : (pl.kind == ZAFX_MEL || pl.kind == ZAFX_MFCC) && mel_f64_tiled(pl));
     c.n_clips = n_clips, c.n = n, c.T = T, c.out_len = out_len;
     c.in = reinterpret_cast<uintptr_t>(in), c.out = reinterpret_cast<uintptr_t>(out);
     return c;
@@ -320,13 +327,8 @@ hipError_t launch_istft_f64(zafx_plan& pl, const double2* spec, double* y, int64
 hipError_t launch_cqt_f64(zafx_plan& pl, const double* x, double* out, int64_t n_clips, int64_t n_samples, int T);
 hipError_t launch_mel_f64(const zafx_plan& pl, const double* x, double* out, int64_t n_clips, int64_t n_samples, int T);
 hipError_t launch_mdct_f64(const zafx_plan& pl, const double* x, double* out, int64_t n_clips, int64_t n_samples, int T);
-// The tiled float64 kernels (W = 2048, reference layout): the plans each takes -- one predicate per kernel, shared by the equal-length launcher
-// and the ragged route -- and zafx_execute_ragged's launches of their RAGGED forms.  The table counts tiles of kStft64RaggedTile frames for
-// the STFT and of kMd64RaggedTile frames for the MDCT, mel and mfcc; x on 16 bytes, every clip's output block on 128, total_tiles < 2^31.
-constexpr int kStft64RaggedTile = 8, kMd64RaggedTile = 16;
-bool stft_f64_tiled(const zafx_plan& pl);
-bool mdct_f64_tiled(const zafx_plan& pl);
-bool mel_f64_tiled(const zafx_plan& pl);
+// zafx_execute_ragged's launches of the tiled float64 kernels' RAGGED forms.  The table counts tiles of kStft64RaggedTile frames for the STFT
+// and of kMd64RaggedTile frames for the MDCT, mel and mfcc; x on 16 bytes, every clip's output block on 128, total_tiles < 2^31.
 hipError_t launch_stft_f64_ragged(const zafx_plan& pl, const double* x, double2* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles);
 hipError_t launch_mdct_f64_ragged(const zafx_plan& pl, const double* x, double* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles);
 hipError_t launch_mel_f64_ragged(const zafx_plan& pl, const double* x, double* out, const RgClip* d_tab, int64_t n_clips, long long total_tiles);
@@ -395,15 +397,11 @@ hipError_t launch_center_ragged(const zafx_plan& pl, const float* x, float* out,
 // zafx_execute_imdct_ragged: k_imdct's RAGGED form (float32, reference layout, W = 512 / 1024 / 2048) -- the plans that have it, the tile
 // frames and the workgroup slots of its launch (what imdct_cut_units takes), and the launch on `n_units` records of the device table
 // (zafx_units.hpp; every block's pitch a multiple of 4 floats, every block below 2^32 bytes, coefs on 4 bytes, units below 2^31)
-constexpr int kImdctRaggedTile = 32;
-bool imdct_ragged_native(const zafx_plan& pl);
 bool imdct_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
 hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const TileUnit* d_units, long long n_units);
 // zafx_execute_istft_ragged: k_istft_ft16's RAGGED form (float32, reference layout, W = 256 ... 2048, halo < 16) -- the plans that have it, the
 // tile frames and the workgroup slots of its launch (what istft_cut_units takes), and the launch on `n_units` records of the device table
 // (zafx_units.hpp; every block below 2^31 bytes, spec on 4 bytes, units below 2^31)
-constexpr int kIstftRaggedTile = 16;
-bool istft_ragged_native(const zafx_plan& pl);
 bool istft_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
 hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const TileUnit* d_units, long long n_units);
 hipError_t launch_pcm_to_float(hipStream_t stream, const void* pcm, float* out, int64_t n_total, int n_channels, int sample_bytes);

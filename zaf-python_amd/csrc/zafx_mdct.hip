@@ -1605,11 +1605,8 @@ static hipError_t run_mdct_p(const zafx_plan& pl, const Route<MdctRoute>& r, con
 // reference layout, float32, every clip's rows whole 128-byte lines (the caller checked).  One form runs the whole batch: `aligned`, the
 // 16-byte buffer loads (a descriptor per clip; the caller vouches for d_in on 16 bytes and for offsets and lengths that are multiples of 4
 // samples), else the edge form: the same descriptor read in 4-byte loads, any offsets and lengths.  Both: every clip below 2^28 samples.  The table counts tiles of kMdctTile frames.
+// The plans: mdct_ragged_native, zafx_routes.hpp.
 static_assert(kMdctRaggedTile == kMdctTile, "zafx_execute_ragged builds the table for the kernel's tile");
-bool mdct_ragged_native(const zafx_plan& pl) {
-    return pl.kind == ZAFX_MDCT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.layout == ZAFX_LAYOUT_FT &&
-           mdct_use_persistent(pl.log2nf, pl.layout) && pl.d_wfold && pl.d_tw_pass && pl.d_tw_aux;
-}
 
 template <int LOG2NF, bool ALIGNED>
 static hipError_t run_mdct_p_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* tab, int64_t n_clips, long long total_tiles) {
@@ -1626,14 +1623,14 @@ static hipError_t run_mdct_p_ragged(const zafx_plan& pl, const float* x, float* 
     if (total_tiles <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / G::SMEM);   // (the grid of run_mdct_p)
     const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus * std::max(per_cu, 1));
-    pl.ran = "k_mdct_ft32_ragged";
+    pl.ran = kernel_name(RaggedKernel::Mdct);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NSLOT * 64), G::SMEM, pl.stream, x, pl.d_wfold, pl.d_tw_pass, pl.d_tw_aux, out, tab, 0, 0,
                        (int)n_clips, (int)total_tiles, 1, 0, 0);
     return hipGetLastError();
 }
 
 hipError_t launch_mdct_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
-    if (!mdct_ragged_native(pl) || n_clips >= (1LL << 31) || total_tiles >= (1LL << 31)) return hipErrorInvalidValue;
+    if (!mdct_ragged_native(route_call(pl, x, out, n_clips, 0, 0)) || n_clips >= (1LL << 31) || total_tiles >= (1LL << 31)) return hipErrorInvalidValue;
     switch (pl.log2nf) {
 #define X(L) \
     case L: return aligned ? run_mdct_p_ragged<L, true>(pl, x, out, tab, n_clips, total_tiles) : run_mdct_p_ragged<L, false>(pl, x, out, tab, n_clips, total_tiles);
@@ -2007,11 +2004,6 @@ struct ImdctRaggedCfg {
     }
 };
 
-bool imdct_ragged_native(const zafx_plan& pl) {
-    return pl.kind == ZAFX_IMDCT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.layout == ZAFX_LAYOUT_FT && pl.log2nf >= 7 &&
-           pl.log2nf <= 9 && pl.d_window && pl.d_tw_pass && pl.d_tw_aux;
-}
-
 bool imdct_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots) {
     switch (pl.log2nf) {
         case 7: *slots = ImdctRaggedCfg<7>::slots(pl); break;
@@ -2028,7 +2020,7 @@ static hipError_t run_imdct_ragged(const zafx_plan& pl, const float* coefs, floa
     using G = ImdctRaggedCfg<LOG2NF>;
     auto kern = k_imdct<LOG2NF, G::LOG2E, G::FPB, G::NSLOT, ZAFX_LAYOUT_FT, G::WINL, true>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, G::SMEM); e != hipSuccess) return e;
-    pl.ran = "k_imdct_ragged";
+    pl.ran = kernel_name(RaggedKernel::Imdct);
     if (n_units <= 0) return hipSuccess;
     const long long grid = std::min<long long>(n_units, G::slots(pl));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NSLOT * G::C::P), G::SMEM, pl.stream, coefs, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, y, 0, 0, d_units,
@@ -2037,7 +2029,8 @@ static hipError_t run_imdct_ragged(const zafx_plan& pl, const float* coefs, floa
 }
 
 hipError_t launch_imdct_ragged(const zafx_plan& pl, const float* coefs, float* y, const TileUnit* d_units, long long n_units) {
-    if (!imdct_ragged_native(pl) || n_units >= (1LL << 31) || reinterpret_cast<uintptr_t>(coefs) % 4 != 0) return hipErrorInvalidValue;
+    const RouteCall c = route_call(pl, coefs, y, 0, 0, 0);
+    if (!imdct_ragged_native(c) || n_units >= (1LL << 31) || !ragged_blocks_base_ok(c)) return hipErrorInvalidValue;
     switch (pl.log2nf) {
         case 7: return run_imdct_ragged<7>(pl, coefs, y, d_units, n_units);
         case 8: return run_imdct_ragged<8>(pl, coefs, y, d_units, n_units);

@@ -1192,22 +1192,9 @@ bool pcm_direct_ok(const zafx_plan& pl, int64_t n_frames, int n_channels, int sa
 // ---------------------------------------------------------------------------------
 // zafx_execute_ragged on k_mel2 (RAGGED form): mel / mfcc / the one-pass form of the geometries run_mel sends to k_mel2, and |X| / |X|^2 of an
 // STFT plan at W = 2048 (MODE 2 / 3, what launch_spec2 takes).  Float32, reference layout; the caller checked that every clip's rows are whole
-// 128-byte lines and that the clips are below 2^29 samples (the aligned form's 32-bit offsets inside a clip's buffer descriptor).
+// 128-byte lines and that the clips are below 2^29 samples (the aligned form's 32-bit offsets inside a clip's buffer descriptor).  The plans:
+// mel_ragged_native and spec2_ragged, zafx_routes.hpp.
 // ---------------------------------------------------------------------------------
-bool spec2_ragged(const zafx_plan& pl) {
-    return ZAFX_SPEC2 && pl.kind == ZAFX_STFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.log2nf == 10 && pl.log2e == 4 &&
-           pl.layout == ZAFX_LAYOUT_FT && kMelFpb == 16 && kMelThreads == 1024 && pl.d_tw_pass && pl.d_tw_aux &&
-           (pl.prm.spectrum == ZAFX_SPECTRUM_MAGNITUDE || pl.prm.spectrum == ZAFX_SPECTRUM_POWER);
-}
-
-bool mel_ragged_native(const zafx_plan& pl) {
-    if (pl.kind == ZAFX_STFT) return spec2_ragged(pl);
-    if (pl.kind != ZAFX_MEL && pl.kind != ZAFX_MFCC) return false;
-    if (!ZAFX_MEL2 || pl.prm.precision != ZAFX_PRECISION_F32 || pl.bs_log2m > 0 || pl.layout != ZAFX_LAYOUT_FT || mel_takes_wide_route(pl)) return false;
-    if (pl.log2nf != 10 || pl.log2e != 4 || kMelFpb != 16 || kMelThreads != 1024) return false;
-    return pl.fb.whole_ok && pl.fb.n_waves == 16 && (pl.kind == ZAFX_MEL || pl.dct.dct2_ok);
-}
-
 // PCM 1 / 2 (zafx_execute_ragged_pcm, int16 mono / stereo): the records' in_off and n_samples count sample frames -- 2 bytes mono, the 4 bytes of
 // one (left, right) pair stereo, which is why PCM 2 indexes exactly as the float form does.
 template <bool ALIGNED, int PCM = 0>
@@ -1222,6 +1209,7 @@ static auto mel2_ragged_kernel(int mode) {
 }
 
 hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
+    static_assert(!kMel2Tile || kMelFpb == kStftRaggedTile, "zafx_execute_ragged builds the table for k_mel2's tile");
     using C = FftCfg<10, 4>;
     const bool spec = pl.kind == ZAFX_STFT, mfcc = pl.kind == ZAFX_MFCC, dual = mfcc && pl.prm.with_mel;
     const int mode = spec ? (pl.prm.spectrum == ZAFX_SPECTRUM_POWER ? 3 : 2) : dual ? 4 : mfcc ? 1 : 0;
@@ -1234,7 +1222,7 @@ hipError_t launch_mel_ragged(const zafx_plan& pl, const float* x, float* out, co
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(k2), pl.device, smem); e != hipSuccess) return e;
     if (total_tiles <= 0) return hipSuccess;
     const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus);
-    pl.ran = "k_mel2_ragged";
+    pl.ran = kernel_name(RaggedKernel::Mel2);
     hipLaunchKernelGGL(k2, dim3((unsigned)grid), dim3(1024), smem, pl.stream, x, pl.d_window, pl.d_tw_pass, pl.d_tw_aux, spec ? nullptr : pl.fb.d_pack,
                        spec ? nullptr : pl.fb.d_whole, spec ? nullptr : pl.dct.d_dct2, spec ? nullptr : pl.dct.d_owner2, out, tab, pl.H, 0, 0, (int)n_clips,
                        (int)total_tiles, spec ? 0 : pl.prm.n_filters, mfcc ? pl.prm.n_coefs : 0, (int)ZAFX_LAYOUT_FT);

@@ -1,13 +1,14 @@
-// zafx_routes.hpp -- which kernel an equal-length float32 call runs: the one place that decides it.
+// zafx_routes.hpp -- which kernel an equal-length float32 call runs, and which launch a ragged batch takes: the one place that decides it.
 //
-// Plain C++17, no HIP: hipcc compiles it into the library (the launchers of zafx_stft.hip, zafx_mdct.hip, zafx_mel.hip, zafx_cqt.hip and
-// zafx_center.hip fill a RouteCall -- route_call, zafx_internal.hpp -- ask the family's function once and switch on the answer), g++ compiles
-// it into tests/host_emu/routes_emu.cpp, and tests/test_routes_host.py holds that program to the conditions restated in Python
-// (tests/long_clips.py BOUNDS) and to the kernels recorded on the GPU (tests/golden/call_routes.json).
+// Plain C++17, no HIP, no getenv: hipcc compiles it into the library (the launchers of zafx_stft.hip, zafx_mdct.hip, zafx_mel.hip, zafx_cqt.hip
+// and zafx_center.hip fill a RouteCall -- route_call, zafx_internal.hpp -- ask the family's function once and switch on the answer; the ragged
+// entry points of zafx_capi.cpp add a RaggedBatch, filled in the pass that builds the clips' records), g++ compiles it into
+// tests/host_emu/routes_emu.cpp, and tests/test_routes_host.py holds that program to the conditions restated in Python (tests/long_clips.py
+// BOUNDS) and to the kernels recorded on the GPU (tests/golden/call_routes.json, tests/golden/ragged_routes.json).
 //
 // Every condition stands here once, under a name; a condition two routes share is one function both call.  The inequalities, constants
 // and the order of the tests are those the launchers had inline (profiles/routes_notes.md lists the ones that look inconsistent).
-// Out of scope: the ragged dispatch, the float64 and Bluestein launchers, and everything a kernel decides for itself.
+// Out of scope: the equal-length float64 and Bluestein launchers, and everything a kernel decides for itself.
 #pragma once
 #include <cstdint>
 
@@ -94,6 +95,10 @@
 #ifndef ZAFX_MEL_FPB
 #define ZAFX_MEL_FPB 16
 #endif
+// k_stft_ft16 at W = 2048: 1024 points as two radix-32 passes (its own twiddle table; run_stft_fat has the measurements)
+#ifndef ZAFX_STFT_R32
+#define ZAFX_STFT_R32 1
+#endif
 
 namespace zafx {
 
@@ -109,6 +114,9 @@ struct RouteCall {
     // k_stft_ft16's claim word with the run-time split enabled, and the filterbank (and DCT) packed for k_mel2
     bool tw_pass = false, tw_aux = false, tw_r32 = false, tw_sub = false, tw_quad = false, tw_band = false, fbw = false, window16 = false,
          claim = false, mel2 = false;
+    // the float32 window and the MDCT's folded one, and -- float64 plans -- the float64 window with the kind's tiled kernel (the
+    // *_f64_tiled predicate of the equal-length float64 launchers, zafx_f64.hip)
+    bool window = false, wfold = false, f64_tiled = false;
     int64_t n_clips = 0;
     int64_t n = 0;         // samples (center: sample frames; int16 PCM: frames) of a clip; unused by the inverses
     int T = 0;             // frames
@@ -237,13 +245,13 @@ inline bool quad_addressable(const RouteCall& c) {
 // a complex array whose row count fits the unit counters of the carry kernels
 inline bool complex_out_countable(const RouteCall& c) { return c.out % 8 == 0 && c.n_clips * (long long)c.T < (1LL << 31); }
 
-// |X| / |X|^2 at W = 2048 in the reference layout on k_mel2 (launch_spec2)
-inline bool spec2_usable(const RouteCall& c) {
-    if (!ZAFX_SPEC2 || c.log2nf != 10 || c.log2e != 4 || c.layout != ZAFX_LAYOUT_FT || !kMel2Tile || !c.tw_pass || !c.tw_aux) return false;
-    if (c.spectrum != ZAFX_SPECTRUM_MAGNITUDE && c.spectrum != ZAFX_SPECTRUM_POWER) return false;
-    if (!clip_below_2_29(c)) return false;
-    return (long long)tiles16(c) * c.n_clips < (1LL << 31);
+// |X| / |X|^2 at W = 2048 in the reference layout on k_mel2 (launch_spec2): the plan's part ...
+inline bool spec2_geometry(const RouteCall& c) {
+    return ZAFX_SPEC2 && c.log2nf == 10 && c.log2e == 4 && ft(c) && kMel2Tile && c.tw_pass && c.tw_aux &&
+           (c.spectrum == ZAFX_SPECTRUM_MAGNITUDE || c.spectrum == ZAFX_SPECTRUM_POWER);
 }
+// ... and the call's: the clip and the tile count (a ragged batch asks the same of every clip and of its own tiles, ragged_route)
+inline bool spec2_usable(const RouteCall& c) { return spec2_geometry(c) && clip_below_2_29(c) && (long long)tiles16(c) * c.n_clips < (1LL << 31); }
 
 // forward STFT (float32, power-of-two window): launch_stft
 inline Route<StftRoute> stft_route(const RouteCall& c) {
@@ -414,7 +422,8 @@ inline Route<MelRoute> mel_route(const RouteCall& c) {
 }
 
 // int16 PCM (one or two channels) read by the kernels' own loads (zafx_execute_pcm); everything else converts into a float32 staging array first
-inline bool pcm_int16(const RouteCall& c) { return c.sample_bytes == 2 && (c.channels == 1 || c.channels == 2); }
+constexpr bool pcm_int16(int channels, int sample_bytes) { return sample_bytes == 2 && (channels == 1 || channels == 2); }
+inline bool pcm_int16(const RouteCall& c) { return pcm_int16(c.channels, c.sample_bytes); }
 // ... on k_mel2: mel / mfcc and |X| / |X|^2 at W = 2048 (the caller checks the array's 8-byte alignment)
 inline bool pcm_direct_ok(const RouteCall& c) {
     if (!pcm_int16(c) || c.precision != ZAFX_PRECISION_F32 || c.bluestein) return false;
@@ -463,5 +472,125 @@ inline const char* maskfilter_stems_ragged_refusal(int kind, int layout, int64_t
     }
     return nullptr;
 }
+
+// ---------------------------------------------------------------------------------
+// ragged batches: clips of different lengths in one call (zafx_execute_ragged, zafx_execute_ragged_pcm, zafx_execute_imdct_ragged,
+// zafx_execute_istft_ragged).  The tests run in the order, and with the inequalities, the entry points had inline
+// (profiles/routes_notes.md lists the ones that look inconsistent).
+// ---------------------------------------------------------------------------------
+// frames per tile of the RAGGED kernel forms: what the host's tables count (each launcher static_asserts its own against the kernel's)
+constexpr int kStftRaggedTile = 16;                           // k_stft_ft16, k_mel2
+constexpr int kMdctRaggedTile = 32;                           // k_mdct_ft32
+constexpr int kStft64RaggedTile = 8, kMd64RaggedTile = 16;    // k_stft_ft8_f64; k_mdct_ft16_f64, k_mel_ft8_f64
+constexpr int kImdctRaggedTile = 32, kIstftRaggedTile = 16;   // k_imdct, k_istft_ft16
+
+enum class RaggedRoute { MdctNative, F64Native, StftNative, MelNative, PerClip, PcmNotTaken };
+// the RAGGED forms' names (what pl.ran reads after a native launch)
+enum class RaggedKernel { Stft, Mel2, Mdct, Istft, Imdct, Stft64, Mdct64, Mel64 };
+constexpr const char* kRaggedKernels[] = {"k_stft_ft16_ragged", "k_mel2_ragged",          "k_mdct_ft32_ragged",     "k_istft_ragged",
+                                          "k_imdct_ragged",     "k_stft_ft8_f64_ragged", "k_mdct_ft16_f64_ragged", "k_mel_ft8_f64_ragged"};
+constexpr const char* kernel_name(RaggedKernel k) { return kRaggedKernels[(int)k]; }
+
+// bytes of an element of a forward plan's output: complex for the two complex kinds of the STFT
+constexpr int64_t out_elem_bytes(int kind, int precision, int spectrum) {
+    return (precision == ZAFX_PRECISION_F64 ? 8 : 4) * (kind == ZAFX_STFT && spectrum < ZAFX_SPECTRUM_MAGNITUDE ? 2 : 1);
+}
+// What the kernels ask of the clips of a batch, one field per question: add() takes one clip -- its offset and length in the input array,
+// its frames, the pitch of its rows and the bytes of an output element.
+struct RaggedBatch {
+    bool whole_lines = true;                       // every block's rows are whole 128-byte lines, at a pitch below 2^31
+    bool below_2_29 = true, below_2_28 = true;     // every clip's length
+    bool offsets_even = true, lengths_even = true;
+    bool quads = true;                             // every offset and length a multiple of 4
+    int64_t tiles8 = 0, tiles16 = 0, tiles32 = 0;  // the batch's tiles of 8 / 16 / 32 frames (whole_lines: every frame count fits the record's int)
+    int64_t n_clips = 0;
+    void add(int64_t offset, int64_t length, int64_t frames, int64_t pitch, int64_t elem_bytes) {
+        whole_lines = whole_lines && (pitch * elem_bytes) % 128 == 0 && pitch < INT32_MAX;
+        below_2_29 = below_2_29 && length < (1LL << 29);
+        below_2_28 = below_2_28 && length < (1LL << 28);
+        offsets_even = offsets_even && offset % 2 == 0;
+        lengths_even = lengths_even && length % 2 == 0;
+        quads = quads && offset % 4 == 0 && length % 4 == 0;
+        tiles8 += (frames + 7) / 8, tiles16 += (frames + 15) / 16, tiles32 += (frames + 31) / 32;
+        ++n_clips;
+    }
+    // "batch too large for one launch": checked after every clip, so the first clip that reaches the bound is the one reported
+    bool too_large() const { return tiles16 >= (1LL << 31); }
+};
+
+// The plans that have a RAGGED kernel form (RouteCall: the plan's fields; the launchers' own guards ask the same functions).
+// |X| / |X|^2 at W = 2048 on k_mel2: spec2_usable's geometry
+inline bool spec2_ragged(const RouteCall& c) { return c.kind == ZAFX_STFT && f32_pow2(c) && spec2_geometry(c); }
+// k_stft_ft16: W = 256 ... 2048 in the reference layout (W = 1024 two-sided too, where the equal-length route prefers the carry form)
+inline bool stft_ragged_native(const RouteCall& c) {
+    if (spec2_ragged(c)) return true;
+    return c.kind == ZAFX_STFT && f32_pow2(c) && stft_use_fat(c.log2nf, c.layout) && c.tw_pass && c.tw_aux && (c.log2nf != 10 || !ZAFX_STFT_R32 || c.tw_r32);
+}
+// k_mel2: mel / mfcc of the geometries mel_route sends there, and the STFT plans of spec2_ragged
+inline bool mel_ragged_native(const RouteCall& c) {
+    if (c.kind == ZAFX_STFT) return spec2_ragged(c);
+    if (c.kind != ZAFX_MEL && c.kind != ZAFX_MFCC) return false;
+    if (!ZAFX_MEL2 || !f32_pow2(c) || !ft(c) || mel_wide(c.log2nf, c.bluestein, c.n_filters)) return false;
+    return c.log2nf == 10 && c.log2e == 4 && kMel2Tile && c.mel2;
+}
+// k_mdct_ft32: W = 512, 1024, 2048 in the reference layout
+inline bool mdct_ragged_native(const RouteCall& c) {
+    return c.kind == ZAFX_MDCT && f32_pow2(c) && ft(c) && mdct_use_persistent(c.log2nf, c.layout) && c.wfold && c.tw_pass && c.tw_aux;
+}
+// k_imdct: W = 512, 1024, 2048 in the reference layout
+inline bool imdct_ragged_native(const RouteCall& c) {
+    return c.kind == ZAFX_IMDCT && f32_pow2(c) && ft(c) && mdct_use_persistent(c.log2nf, c.layout) && c.window && c.tw_pass && c.tw_aux;
+}
+// k_istft_ft16: W = 256 ... 2048 in the reference layout, any hop whose halo stays inside one tile
+inline bool istft_ragged_native(const RouteCall& c) {
+    return c.kind == ZAFX_ISTFT && f32_pow2(c) && stft_use_fat(c.log2nf, c.layout) && c.tw_pass && c.tw_aux && c.H >= 1 &&
+           (c.W + c.H - 1) / c.H - 1 < kIstftRaggedTile;
+}
+
+// zafx_execute_ragged_pcm: the int16 mode its one launch runs in (1 mono, 2 stereo; 0: the batch converts to float32 first).
+// pcm_native: ZAFX_RAGGED_PCM_NATIVE
+inline int ragged_pcm_mode(int channels, int sample_bytes, bool pcm_native) { return pcm_int16(channels, sample_bytes) && pcm_native ? channels : 0; }
+
+// The launch of a forward batch, the `aligned` argument of a native one and the frames per tile its table is built for.
+struct RaggedAnswer { RaggedRoute k; bool aligned = false; int tile_frames = 0; };
+// pcm: ragged_pcm_mode's answer (0: float samples) -- an int16 batch runs a native launch or none (PcmNotTaken; there is no per-clip path
+// for integers).  mdct_native, f64_native: ZAFX_RAGGED_MDCT_NATIVE, ZAFX_RAGGED_F64_NATIVE (measurements only, include/zafx.h).
+inline RaggedAnswer ragged_route(const RouteCall& c, const RaggedBatch& b, int pcm, bool mdct_native, bool f64_native) {
+    const bool lines = c.out % 128 == 0 && ft(c) && b.whole_lines;
+    // k_mdct_ft32: every clip through a buffer descriptor of its own with 32-bit byte offsets (clips below 2^28 samples, d_in on 4 bytes);
+    // 16-byte loads when the array is on 16 bytes and every offset and length is a multiple of 4 samples, 4-byte loads for any other
+    // batch.  int16 (W = 2048 only): the 16-byte-piece form alone, and no switch of its own (ZAFX_RAGGED_PCM_NATIVE is the caller's).
+    if (lines && mdct_ragged_native(c)) {
+        const bool aligned = c.in % 16 == 0 && b.quads, short_enough = c.in % 4 == 0 && b.below_2_28;
+        const bool route = pcm != 0 ? aligned && c.log2nf == 9 : mdct_native;
+        if (b.tiles32 < (1LL << 31) && short_enough && route) return {RaggedRoute::MdctNative, aligned, kMdctRaggedTile};
+    }
+    // the tiled float64 kernels of W = 2048: d_in on 16 bytes, offsets and lengths free; the STFT's tiles are 8 frames
+    if (pcm == 0 && c.precision == ZAFX_PRECISION_F64 && c.f64_tiled && lines && c.in % 16 == 0 && f64_native) {
+        const bool stft = c.kind == ZAFX_STFT;
+        if ((stft ? b.tiles8 : b.tiles16) < (1LL << 31)) return {RaggedRoute::F64Native, false, stft ? kStft64RaggedTile : kMd64RaggedTile};
+    }
+    if (pcm != 0 && c.kind == ZAFX_MDCT) return {RaggedRoute::PcmNotTaken};
+    // k_stft_ft16 / k_mel2: k_mel2's aligned form addresses a clip with 32-bit byte offsets (clips below 2^29 samples)
+    const bool on_mel2 = mel_ragged_native(c);
+    const bool native = c.precision == ZAFX_PRECISION_F32 && ft(c) && c.window && lines &&
+                        (c.kind == ZAFX_STFT ? stft_ragged_native(c) && (!on_mel2 || b.below_2_29) : on_mel2 && b.below_2_29);
+    // (int16: the fast paths of k_mel2 and k_stft_ft16 test s0 + W <= n per frame / last <= n per tile, so every multi-sample load lies
+    // inside the clip whatever its length's parity, and the tail goes sample by sample: the offsets alone must be even.  The float
+    // route keeps the condition on the lengths it was measured with.)
+    const bool even = c.H % 2 == 0 && c.in % 8 == 0 && b.offsets_even && (pcm != 0 || b.lengths_even);
+    // (int16: W = 2048 -- k_mel2's geometry, the complex kinds of k_stft_ft16 --, even hop and offsets, d_in on 8 bytes, clips below 2^29 frames)
+    if (pcm != 0 && !(native && c.log2nf == 10 && even && b.below_2_29)) return {RaggedRoute::PcmNotTaken};
+    if (native) return {c.kind == ZAFX_STFT ? RaggedRoute::StftNative : RaggedRoute::MelNative, even, kStftRaggedTile};
+    return {RaggedRoute::PerClip};
+}
+
+// The inverse entry points: the batch is native when the plan has the form, the array is on 4 bytes and every block passes the kind's
+// test (RouteCall: T = the block's frames, as an int -- a count beyond it fails either test as INT_MAX does).
+inline bool ragged_blocks_base_ok(const RouteCall& c) { return c.in % 4 == 0; }
+// k_imdct: 16-byte gathers (a pitch that is a multiple of 4 floats), a block below 2^32 bytes behind its buffer descriptor
+inline bool imdct_ragged_block(const RouteCall& c) { return row_pitch(c) % 4 == 0 && (long long)(c.W / 2) * row_pitch(c) * 4 < (1LL << 32); }
+// k_istft_ft16: a block counted as W rows behind signed 32-bit byte offsets (istft_route's bound), frames below 2^28
+inline bool istft_ragged_block(const RouteCall& c) { return c.T < (1LL << 28) && spectrum_addressable(c, c.W); }
 
 }  // namespace zafx

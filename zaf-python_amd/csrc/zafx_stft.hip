@@ -2521,10 +2521,7 @@ constexpr int stft_fpb(int log2n, int layout) {
 // (stft_use_fat, stft_use_tf -- the kernel family by window and layout --: zafx_routes.hpp)
 template <int LOG2N, bool ALIGNED, int SPEC>
 static hipError_t run_stft_fat(const zafx_plan& pl, const float* x, float2* out, int64_t n_clips, int64_t n_samples, int T, bool claimed) {
-#ifndef ZAFX_STFT_R32
-#define ZAFX_STFT_R32 1
-#endif
-    // 1024 points as two radix-32 passes (32 points per thread, a frame per half wavefront) instead of 16 x 16 x 4:
+    // ZAFX_STFT_R32 (zafx_routes.hpp): 1024 points as two radix-32 passes (32 points per thread, a frame per half wavefront) instead of 16 x 16 x 4:
     // 495 instead of 604 instructions per frame, one LDS exchange instead of two; FFT phase 9.6 k -> 7.4 k cycles per
     // tile.  The two-sided kernel is bound by its store drain and does not move (1.95 ms either way); the one-sided /
     // magnitude / power outputs gain 4-5 %.  (The fused mel kernel is better off with 16 waves x radix 16: 1.48 vs 1.67 ms.)
@@ -3414,15 +3411,10 @@ hipError_t launch_stft(const zafx_plan& pl, const float* x, float2* out, int64_t
 
 // zafx_execute_ragged: clips of different lengths on k_stft_ft16's RAGGED form, W = 256 ... 2048 in the reference layout, float32, every
 // clip's rows whole 128-byte lines (the caller checked).  W = 1024 two-sided runs here too, where the equal-length path prefers the carry
-// form k_stft_ft16c; |X| / |X|^2 at W = 2048 go to k_mel2 as they do there (launch_mel_ragged).
-bool stft_ragged_native(const zafx_plan& pl) {
-    if (spec2_ragged(pl)) return true;
-    return pl.kind == ZAFX_STFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && pl.layout == ZAFX_LAYOUT_FT && pl.log2nf >= 7 &&
-           pl.log2nf <= 10 && pl.d_tw_pass && pl.d_tw_aux && (pl.log2nf != 10 || !ZAFX_STFT_R32 || pl.d_tw_r32);
-}
-
+// form k_stft_ft16c; |X| / |X|^2 at W = 2048 go to k_mel2 as they do there (launch_mel_ragged).  The plans: stft_ragged_native, zafx_routes.hpp.
 template <int LOG2N, bool ALIGNED, int SPEC>
 static hipError_t run_stft_fat_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* tab, int64_t n_clips, long long total_tiles) {
+    static_assert(kFatFrames == kStftRaggedTile, "zafx_execute_ragged builds the table for the kernel's tile");
     constexpr int LOG2E = (ZAFX_STFT_R32 && LOG2N == 10) ? 5 : default_log2e(LOG2N);   // (as run_stft_fat)
     using F = FatCfg<LOG2N, LOG2E>;
     auto kern = k_stft_ft16<LOG2N, LOG2E, ALIGNED, SPEC, kFatFrames, 0, true>;
@@ -3437,7 +3429,7 @@ static hipError_t run_stft_fat_ragged(const zafx_plan& pl, const float* x, float
     if (total_tiles <= 0) return hipSuccess;
     const int per_cu = (int)std::min<size_t>(2, (size_t)kMaxLdsBytes / F::SMEM);
     const long long grid = std::min<long long>(total_tiles, (long long)pl.n_cus * std::max(per_cu, 1));
-    pl.ran = "k_stft_ft16_ragged";
+    pl.ran = kernel_name(RaggedKernel::Stft);
     if (pl.stft_dynamic && pl.d_claim) {   // tiles claimed at run time (DYN): the tile count is rarely a multiple of the grid here
         static_assert(F::SMEM + kClaimLdsBytes <= (size_t)kMaxLdsBytes, "tile + tables + claim words exceed LDS");
         if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(dyn), pl.device, F::SMEM + kClaimLdsBytes); e != hipSuccess) return e;
@@ -3464,7 +3456,7 @@ static hipError_t dispatch_stft_ragged(const zafx_plan& pl, const float* x, floa
 }
 
 hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, const RgClip* tab, int64_t n_clips, long long total_tiles, bool aligned) {
-    if (spec2_ragged(pl)) return launch_mel_ragged(pl, x, reinterpret_cast<float*>(out), tab, n_clips, total_tiles, aligned);
+    if (spec2_ragged(route_call(pl, x, out, n_clips, 0, 0))) return launch_mel_ragged(pl, x, reinterpret_cast<float*>(out), tab, n_clips, total_tiles, aligned);
     switch (pl.log2nf) {
         case 7: return dispatch_stft_ragged<7>(pl, x, out, tab, n_clips, total_tiles, aligned);
         case 8: return dispatch_stft_ragged<8>(pl, x, out, tab, n_clips, total_tiles, aligned);
@@ -3479,12 +3471,7 @@ hipError_t launch_stft_ragged(const zafx_plan& pl, const float* x, float2* out, 
 // ---------------------------------------------------------------------------------
 // k_istft_ft16's RAGGED form: W = 256 ... 2048 in the reference layout, float32, any hop with halo < 16 -- what run_istft_fat runs.  The
 // geometry (LDS, workgroups per CU, the 16-byte gather when the array is on 8 bytes: block offsets count complex64 elements, so every block
-// shares the array's alignment) is run_istft_fat's.
-bool istft_ragged_native(const zafx_plan& pl) {
-    return pl.kind == ZAFX_ISTFT && pl.prm.precision == ZAFX_PRECISION_F32 && pl.bs_log2m == 0 && stft_use_fat(pl.log2nf, pl.layout) && pl.d_tw_pass &&
-           pl.d_tw_aux && pl.H >= 1 && (pl.W + pl.H - 1) / pl.H - 1 < kFatFrames;
-}
-
+// shares the array's alignment) is run_istft_fat's.  The plans: istft_ragged_native, zafx_routes.hpp.
 template <int LOG2N>
 static long long istft_fat_slots(const zafx_plan& pl) {   // resident workgroups: run_istft_fat's grid bound
     using F = FatCfg<LOG2N, default_log2e(LOG2N)>;
@@ -3514,7 +3501,7 @@ static hipError_t run_istft_ragged(const zafx_plan& pl, const float2* spec, floa
     constexpr int D1 = ONE ? 4 : 2, D2 = ONE ? 4 : 1;
     auto kern = vec ? k_istft_ft16<LOG2N, LOG2E, can_vec ? D2 : D1, ONE, can_vec ? 2 : 1, false, true> : k_istft_ft16<LOG2N, LOG2E, D1, ONE, 1, false, true>;
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), pl.device, F::SMEM); e != hipSuccess) return e;
-    pl.ran = "k_istft_ragged";
+    pl.ran = kernel_name(RaggedKernel::Istft);
     if (n_units <= 0) return hipSuccess;
     const int W = 2 << LOG2N;
     const int halo = (W + pl.H - 1) / pl.H - 1;
@@ -3526,7 +3513,8 @@ static hipError_t run_istft_ragged(const zafx_plan& pl, const float2* spec, floa
 }
 
 hipError_t launch_istft_ragged(const zafx_plan& pl, const float2* spec, float* y, const TileUnit* d_units, long long n_units) {
-    if (!istft_ragged_native(pl) || n_units >= (1LL << 31) || reinterpret_cast<uintptr_t>(spec) % 4 != 0) return hipErrorInvalidValue;
+    const RouteCall c = route_call(pl, spec, y, 0, 0, 0);
+    if (!istft_ragged_native(c) || n_units >= (1LL << 31) || !ragged_blocks_base_ok(c)) return hipErrorInvalidValue;
     const bool one = pl.prm.spectrum == ZAFX_SPECTRUM_ONE_SIDED;
     switch (pl.log2nf) {
 #define X(L) \
