@@ -35,6 +35,9 @@
  *                                  (clips of different lengths in one launch: zafx_execute_masked_ragged, zafx_plan_mask_ragged_layout;
  *                                  several masks per clip over one forward transform: zafx_execute_masked_stems;
  *                                  both at once: zafx_execute_masked_stems_ragged, zafx_plan_stems_ragged_layout)
+ *   ZAFX_MASKFILTER / _REST with   the same with a COMPLEX mask, extended to its Hermitian mirror:
+ *   zafx_execute_masked_complex    np.concatenate((M, np.conj(M[-2:0:-1]))) * audio_stft, istft :194-195 (the real part, :223); complex64
+ *                                  masks in ZAFX_LAYOUT_TF; clips of different lengths in one launch: zafx_execute_masked_complex_ragged
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -261,6 +264,7 @@ int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
  *   ZAFX_CQT / ZAFX_CHROMA (float32)          n_in >= 2^29 samples (3.4 h at 44.1 kHz): cut the signal
  *   ZAFX_CENTER / ZAFX_CENTER_SIDES           n_in >= 2^28 sample frames (1.7 h at 44.1 kHz)
  *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked; zafx_execute_masked_ragged, zafx_execute_masked_stems_ragged: any clip of the batch)
+ *                                             complex masks: n_in >= 2^27 samples (zafx_execute_masked_complex; zafx_execute_masked_complex_ragged: any clip of the batch)
  * zafx_execute_pcm reads int16 in the kernels' own loads below the same lengths (n_frames < 2^29; the MDCT: < 2^28) and converts first above them.
  * Not run at its bound by any test yet: the two-sided complex STFT at window 8192 (k_stft_ft16q takes whole-line rows only; its |X| kind is run).
  * The ragged and PCM entry points state their own per-clip limits below. */
@@ -298,6 +302,39 @@ int zafx_plan_mask_ragged_layout(const zafx_plan* plan, const int64_t* lengths, 
  * zero.  NOT checked: that the output blocks do not overlap -- placing them is the caller's business. */
 int zafx_execute_masked_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips);
+/* The mask filter under a COMPLEX mask: zafx_execute_masked with one complex64 mask M per clip (interleaved re, im), enqueued on the plan's
+ * stream (asynchronous; ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_complex"):
+ *     y = istft(concat(M, conj(M[-2:0:-1])) * stft(x, w, H), w, H)[0:n_in]        (zaf.py:185-195; istft keeps the real part, zaf.py:223)
+ * -- phase-aware masks, any per-bin linear filter.  d_in (B, n_in) float32; d_mask (B, frames, rows) complex64 compact, rows x frames =
+ * zafx_plan_mask_dims counted in complex elements; d_out (B, n_in) float32, under ZAFX_MASKFILTER_REST (B, 2, n_in) with block 1 =
+ * input - block 0 in float32, bit-equal to the subtraction of the block 0 that was written.  All three arrays need 4-byte alignment only,
+ * the complex mask included.  The imaginary parts of mask rows 0 and W/2 have no effect: those bins are their own mirror, the kernel
+ * discards the values (it does not multiply them by zero), and they may hold anything, NaN included.  CONTRACT, as zafx_execute_masked's:
+ * two neighbouring frames of one clip share a transform, so rounding and non-finite values couple frames 2j and 2j+1 of one clip and never
+ * reach another clip; nothing is read in front of a clip's sample 0, from its sample n_in on or behind a mask's last frame, nothing is
+ * written at or beyond n_in; a clip has the same bits alone, anywhere in a batch, however it is cut and under any ZAFX_COMPUTE_UNITS; a mask
+ * of zeros gives exact zeros, and so does silence under any finite mask.  NOT promised: the bits of zafx_execute_masked where every
+ * imaginary part is zero -- the library is built with -ffp-contract=fast and the two pair functions contract differently; the results
+ * agree within the accuracy of either.  Rejected with a message, nothing enqueued or written: a null plan or pointer, negative sizes,
+ * another kind, a plan in ZAFX_LAYOUT_FT (the mask stage in LDS would double; the message names ZAFX_LAYOUT_TF), a window that is not set
+ * or whose sum(window[0:W:H]) is zero, clips of 2^27 samples and more (the mask -- 8 bytes a bin -- lies behind signed 32-bit byte
+ * offsets).  The other entry points on the same plan are not affected. */
+int zafx_execute_masked_complex(zafx_plan* plan, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in);
+/* zafx_execute_masked_complex for n_clips mono clips of different lengths in ONE launch (ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans
+ * created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_complex_ragged").  in_offsets, lengths and out_offsets count float32
+ * elements as in zafx_execute_masked_ragged, and the output blocks are placed as there (the rest directly behind, at out_offsets[i] +
+ * lengths[i]); mask_offsets counts COMPLEX64 elements: the mask of clip i, (T_i, W/2 + 1) compact, starts at complex element
+ * mask_offsets[i] of d_mask.  Any placement will do; zafx_plan_mask_ragged_layout on the plan gives the compact one as it stands (rows x
+ * frames elements per clip) -- which is also the layout zafx_plan_ragged_layout gives a one-sided complex ZAFX_LAYOUT_TF STFT plan, so the
+ * spectra a ragged STFT writes can be turned into masks where they lie.  The arrays need 4-byte alignment only.  CONTRACT: clip i's block is
+ * bit-identical to zafx_execute_masked_complex on that clip and mask alone, whatever the batch and however the clip is cut; no clip sees
+ * another's samples or mask; the imaginary parts of mask rows 0 and W/2 have no effect, as above.  A clip of length 0 is skipped, an empty
+ * batch is fine.  Rejected with a message, nothing enqueued or written: a null plan, pointer or host array, a negative count, another kind,
+ * a plan in ZAFX_LAYOUT_FT, negative lengths or offsets (with the clip's index), a clip of 2^27 samples or more (with its index; decided on
+ * `lengths` before anything is read), a window that is not set or whose COLA sum is zero.  ZAFX_MASKFILTER_UNITS_PER_SLOT in the
+ * environment applies as it does to zafx_execute_masked_ragged (measurements only). */
+int zafx_execute_masked_complex_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips);
 /* Stems: n_stems masks per clip over ONE forward transform, n_stems inverse transforms, in one launch (ZAFX_MASKFILTER and
  * ZAFX_MASKFILTER_REST plans created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_stems", for n_stems == 1 too), enqueued on the
  * plan's stream (asynchronous).  d_in (B, n_in) float32 samples; d_mask (B, n_stems, frames, rows) float32 compact, frames x rows =

@@ -2,7 +2,8 @@
 one -- matched by demangled name and template arguments, with the trailing `false` of a template parameter added since (RAGGED) dropped (a kernel
 that was no template before is matched to its <false>) --
 compared by the metadata notes (VGPRs, SGPRs, spills, LDS, scratch; llvm-readelf --notes) and by the disassembled instruction stream.
-Also lists the NEW object's instantiations whose last template argument is `true`, with their notes.  Needs no GPU.
+Also lists the NEW object's instantiations that are no twin of an OLD one -- a RAGGED form, a kernel added beside the old ones --, with their
+notes.  Needs no GPU.
 
     python tools/code_object_diff.py OLD.o NEW.o 'k_stft_ft16<'
     (OLD.o: e.g. make -C zaf-python_amd/csrc OBJDIR=/tmp/old_build on the parent commit)
@@ -79,11 +80,13 @@ def main(old_obj, new_obj, pattern):
     old = {key(dm[s]): s for s in no if pattern in dm[s]}
     new = {key(dm[s]): s for s in nn if pattern in dm[s]}
     same_notes = same_code = 0
+    twins = set()
     for k, so in sorted(old.items()):
         sn = new.get(k[:-1] + ("false>" if k.endswith("<>") else ", false>")) or new.get(k)   # (k_mdct_ft16_f64 was no template before its RAGGED form)
         if sn is None:
             print(f"MISSING  {k}")
             continue
+        twins.add(sn)
         nt, code = no[so] == nn[sn], do.get(so) == dn.get(sn)
         same_notes += nt
         same_code += code
@@ -91,9 +94,9 @@ def main(old_obj, new_obj, pattern):
         print(f"{'notes same' if nt else 'NOTES DIFFER'}  {'code same' if code else 'code differs'}  {k}  {no[so]}"
               + ("" if nt else f" -> {nn[sn]}") + diff)
     print(f"{len(old)} instantiations: notes identical {same_notes}, instruction streams identical {same_code}")
-    added = {k: s for k, s in new.items() if re.search(r"[<, ]true>$", k)}
+    added = {k: s for k, s in new.items() if s not in twins}
     if added:
-        print("new instantiations (last template argument true):")
+        print("new instantiations (no twin in the old object):")
         for k, s in sorted(added.items()):
             print(f"  {k}  {nn[s]}")
 

@@ -1481,31 +1481,51 @@ static int check_window_gain(const zafx_plan* pl, const char* what) {
     return 0;
 }
 
-int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
+// What zafx_execute_masked, zafx_execute_masked_stems and zafx_execute_masked_complex ask first, in this order: the plan, its kind (`note`: what
+// the message adds behind it), the sizes ...
+static int masked_plan_checks(const char* fn, const zafx_plan* pl, const char* note, int64_t n_clips, int64_t n_in) {
     if (!pl) return fail_msg("null plan");
-    if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_execute_masked: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only (every other kind takes zafx_execute)");
+    if (!is_maskfilter_kind(pl->kind)) return fail_msg(std::string(fn) + ": ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only" + note);
     if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
-    if (n_clips == 0) return 0;
+    return 0;
+}
+// ... and, behind the kind's own refusals and for a batch that is not empty, the three arrays, the window and the device.
+static int masked_launch_checks(const zafx_plan* pl, const void* d_in, const void* d_mask, const void* d_out) {
     if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
     if (int rc = check_window_gain(pl, "mask filter")) return rc;
     ZAFX_HIP(hipSetDevice(pl->device));
+    return 0;
+}
+
+int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
+    if (int rc = masked_plan_checks("zafx_execute_masked", pl, " (every other kind takes zafx_execute)", n_clips, n_in)) return rc;
+    if (n_clips == 0) return 0;
+    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
     return launch_rc("zafx_execute_masked", zafx::launch_maskfilter(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in));
 }
 
 static_assert(ZAFX_MASKFILTER_MAX_STEMS == zafx::kMaskfilterMaxStems, "the header's stem bound is the launcher's");
 
 int zafx_execute_masked_stems(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t n_stems) {
-    if (!pl) return fail_msg("null plan");
-    if (!is_maskfilter_kind(pl->kind)) return fail_msg("zafx_execute_masked_stems: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only");
-    if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
+    if (int rc = masked_plan_checks("zafx_execute_masked_stems", pl, "", n_clips, n_in)) return rc;
     zafx::RouteCall c;   // the launcher's refusals, for an empty batch too
     c.layout = pl->layout, c.n = n_in;
     if (const char* why = zafx::maskfilter_stems_refusal(c, n_stems)) return fail_msg(std::string("zafx_execute_masked_stems: ") + why);
     if (n_clips == 0) return 0;
-    if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
-    if (int rc = check_window_gain(pl, "mask filter")) return rc;
-    ZAFX_HIP(hipSetDevice(pl->device));
+    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
     return launch_rc("zafx_execute_masked_stems", zafx::launch_maskfilter_stems(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in, n_stems));
+}
+
+// Complex64 masks (B, T, W/2+1) on k_maskfilter_c: TF plans, clips below 2^27 samples (maskfilter_complex_refusal), refused for an empty batch too.
+int zafx_execute_masked_complex(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
+    const char* const fn = "zafx_execute_masked_complex";
+    if (int rc = masked_plan_checks(fn, pl, "", n_clips, n_in)) return rc;
+    zafx::RouteCall c;
+    c.kind = pl->kind, c.layout = pl->layout, c.n = n_in;
+    if (const char* why = zafx::maskfilter_complex_refusal(c)) return fail_msg(std::string(fn) + ": " + why);
+    if (n_clips == 0) return 0;
+    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
+    return launch_rc(fn, zafx::launch_maskfilter_complex(*pl, (const float*)d_in, (const float2*)d_mask, (float*)d_out, n_clips, n_in));
 }
 
 int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in) {
@@ -1825,11 +1845,13 @@ int zafx_plan_mask_ragged_layout(const zafx_plan* pl, const int64_t* lengths, in
     return 0;
 }
 
-// The tail of zafx_execute_masked_ragged (n_stems = 0: k_maskfilter, masks in the plan's layout) and zafx_execute_masked_stems_ragged
-// (k_maskfilter_stems, compact TF masks: no pitch), behind their argument checks: the window, the kernel's launch shape, the cut, the upload
-// of the units and the launch.
+// The tail of zafx_execute_masked_ragged (n_stems = 0: k_maskfilter, masks in the plan's layout), zafx_execute_masked_stems_ragged
+// (k_maskfilter_stems, compact TF masks: no pitch) and zafx_execute_masked_complex_ragged (n_stems = 0, complex_mask: k_maskfilter_c on a TF
+// plan, whose launch shape and units are k_maskfilter's; mask_offsets count complex64 elements), behind their argument checks: the window,
+// the kernel's launch shape, the cut, the upload of the units and the launch.
 static int cut_and_launch_masked(const char* fn, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
-                                 const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems) {
+                                 const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems,
+                                 bool complex_mask = false) {
     if (int rc = check_window_gain(pl, "mask filter")) return rc;
     int tile_transforms = 0;
     long long slots = 0;
@@ -1848,6 +1870,7 @@ static int cut_and_launch_masked(const char* fn, zafx_plan* pl, const void* d_in
     if (int rc = upload_records(pl, units)) return rc;
     const auto* d_units = static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get());
     const float *x = (const float*)d_in, *m = (const float*)d_mask;
+    if (complex_mask) return launch_rc(fn, zafx::launch_maskfilter_complex_ragged(*pl, x, (const float2*)d_mask, (float*)d_out, d_units, (long long)units.size()));
     return launch_rc(fn, n_stems ? zafx::launch_maskfilter_stems_ragged(*pl, x, m, (float*)d_out, d_units, (long long)units.size(), n_stems)
                                  : zafx::launch_maskfilter_ragged(*pl, x, m, (float*)d_out, d_units, (long long)units.size()));
 }
@@ -1862,6 +1885,21 @@ int zafx_execute_masked_ragged(zafx_plan* pl, const void* d_in, const int64_t* i
     if (empty) return 0;
     if (int rc = check_clips_below_2_28(fn, lengths, n_clips, "samples")) return rc;
     return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0);
+}
+
+// Ragged batches under complex64 masks: the kind, the layout (refused for an empty batch too, as zafx_execute_masked_complex does) and every
+// clip's length are decided on the host arrays before anything else is read (maskfilter_complex_ragged_refusal); the rest is the real kind's tail.
+int zafx_execute_masked_complex_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips) {
+    const char* const fn = "zafx_execute_masked_complex_ragged";
+    int64_t clip = -1;
+    const char* wrong_kind = pl ? zafx::maskfilter_complex_ragged_refusal(pl->kind, pl->layout, nullptr, 0, &clip) : nullptr;
+    bool empty = false;
+    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    if (const char* why = zafx::maskfilter_complex_ragged_refusal(pl->kind, pl->layout, lengths, n_clips, &clip))
+        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
+    return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0, true);
 }
 
 // Stems of a ragged batch: a clip's n_stems masks back to back, each as a TF plan's mask_block, and its n_stems (+ 1 with rest) output blocks

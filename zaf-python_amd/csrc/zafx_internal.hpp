@@ -383,6 +383,10 @@ hipError_t launch_maskfilter_stems(const zafx_plan& pl, const float* x, const fl
 struct MaskfilterUnit;
 bool maskfilter_launch_shape(const zafx_plan& pl, int* tile_transforms, long long* slots);
 hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units);
+// zafx_execute_masked_complex / _ragged: k_maskfilter_c on complex64 masks (B, T, W/2+1), TF plans only (maskfilter_complex_refusal, zafx_routes.hpp);
+// RAGGED: the units and the launch shape are k_maskfilter's TF ones, a unit's mask_off counts complex64 elements
+hipError_t launch_maskfilter_complex(const zafx_plan& pl, const float* x, const float2* mask, float* out, int64_t n_clips, int64_t n_samples);
+hipError_t launch_maskfilter_complex_ragged(const zafx_plan& pl, const float* x, const float2* mask, float* out, const MaskfilterUnit* d_units, long long n_units);
 // zafx_execute_masked_stems_ragged: the same for k_maskfilter_stems -- the slots follow the stems' LDS size (false as well for a stem count
 // outside 1 .. 8) -- and the launch on a device table of unit records: a clip's n_stems masks back to back at mask_off, its n_stems (+ 1 with
 // rest) output blocks back to back at out_off

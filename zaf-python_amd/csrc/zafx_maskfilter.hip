@@ -303,4 +303,227 @@ hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const f
     return dispatch_maskfilter<true>(pl, x, mask, out, d_units, n_units, 0);
 }
 
+// ---- k_maskfilter_c: the same walk under a COMPLEX mask (zafx_execute_masked_complex, zafx_execute_masked_complex_ragged), ZAFX_LAYOUT_TF only.
+//
+// A kernel of its own, not a fifth template parameter of k_maskfilter: that one's 32 instantiations keep their code objects (DESIGN.md 4.12
+// "Complex masks").  What differs from k_maskfilter's TF form: the mask is complex64, element (bin k, frame t) of a clip at t (H + 1) + k, so a
+// lane's pair k = lane + P m of a frame is ONE 8-byte buffer load (64 lanes: 512 consecutive bytes of the frame's row; the array itself needs
+// 4-byte alignment only), issued behind the samples and in front of the forward transform; the pair function is maskfilter_pair_c; and the
+// imaginary parts of bins 0 and H -- they pair with themselves -- are dropped from the registers before it, whatever they hold.
+// RAGGED: MaskfilterUnit::mask_off counts complex64 elements and mask_pitch is not read.  The launcher keeps every clip below 2^27 samples:
+// its mask then lies behind signed 32-bit byte offsets (maskfilter_complex_refusal, zafx_routes.hpp).
+template <int LOG2W, bool REST, bool RAGGED>
+__global__ __launch_bounds__((MaskfilterCfg<LOG2W, true>::NT)) void k_maskfilter_c(const float* __restrict__ x, const float2* __restrict__ mask,
+                                                                              const float* __restrict__ window, const float2* __restrict__ tw_g,
+                                                                              float* __restrict__ out, MaskfilterSamplesArg<RAGGED> n_samples, long long mask_clip,
+                                                                              int n_blocks, int seg_blocks, int n_segs, long long n_units, float gain) {
+    using K = MaskfilterCfg<LOG2W, true>;
+    using C = typename K::C;
+    constexpr int E = K::E, H = K::H, W = K::W, F = K::F, P = K::P, HE = E / 2;
+    extern __shared__ float2 smem[];
+    const int tid = threadIdx.x, lane = tid & (P - 1), f = __builtin_amdgcn_readfirstlane(tid / P);   // lane: the thread's place among its transform's P
+    float2* const buf = smem + f * C::PITCH;
+    float* const carry = reinterpret_cast<float*>(smem + K::OFF_CARRY);
+    float2* const tw = smem + K::OFF_TW;
+    for (int i = tid; i < C::TW; i += K::NT) tw[i] = tw_g[i];
+    __syncthreads();
+#define CLIP_N rg_pick<RAGGED>(rc.n_samples, n_samples)
+    unsigned clip_bytes = 0, mask_bytes = 0;
+    constexpr int sk = 8, st = (H + 1) * 8;   // bytes from bin to bin and from frame to frame
+    if constexpr (!RAGGED) {
+        clip_bytes = (unsigned)(n_samples * 4);
+        mask_bytes = (unsigned)(mask_clip * 8);
+    }
+
+    // The deal (zafx_overlap_walk.hpp), counted as k_maskfilter counts it.
+    using Cnt = std::conditional_t<RAGGED, unsigned, long long>;
+    const Cnt n_all = (Cnt)n_units, n_deal = deal_rounds<RAGGED>(n_all);
+    unsigned round = 0;
+    for (Cnt w = blockIdx.x; w < n_deal; w += gridDim.x, ++round) {
+        Cnt u;
+        if (!deal_unit<RAGGED>(w, round, n_all, u)) continue;
+        MaskfilterUnit rc{};   // (RAGGED only) uniform: read with scalar loads
+        int b0, b1;
+        const float* xc;
+        long long mo;   // the first complex element of the clip's mask
+        float* oc;
+        if constexpr (RAGGED) {
+            rc = read_unit(n_samples, u);
+            if (rc.b1 <= rc.b0) continue;   // a value-initialised record: no blocks (uniform)
+            b0 = rc.b0, b1 = rc.b1;
+            n_blocks = (int)((rc.n_samples + H - 1) / H);
+            xc = x + rc.in_off, mo = rc.mask_off, oc = out + rc.out_off;
+            clip_bytes = (unsigned)(rc.n_samples * 4);
+            mask_bytes = (unsigned)(n_blocks + 1) * (unsigned)st;   // the mask ends with bin H of frame n_blocks
+        } else {
+            const EqualUnit eu = equal_unit(u, n_segs, seg_blocks, n_blocks);
+            b0 = eu.b0, b1 = eu.b1;
+            xc = x + eu.clip * n_samples;
+            oc = out + eu.clip * n_samples * (REST ? 2 : 1);
+            mo = eu.clip * mask_clip;
+        }
+        const int q0 = b0 >> 1, q1 = b1 >> 1;   // transforms q0 .. q1 hold the frames b0 .. b1 that blocks [b0, b1) need
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(xc, clip_bytes);
+        const __amdgpu_buffer_rsrc_t rm = make_rsrc(mask + mo, mask_bytes);
+        for (int qt = q0; qt <= q1; qt += F) {
+            const int q = qt + f;            // this wave's transform: frames 2q and 2q + 1
+            const bool live = q <= q1;       // (wave-uniform)
+            float2 v[E], ma[HE], mb[HE], mah = make_float2(0.f, 0.f), mbh = make_float2(0.f, 0.f);
+            float raw[E];
+            {
+                // samples in front of the clip and at or behind its end read as zero, and a transform that is not needed reads nothing but
+                // zeros: the descriptor's range check, as in k_maskfilter
+                const int s0 = (2 * q - 1) * H + lane;
+                float xr[E + HE];
+#pragma unroll
+                for (int i = 0; i < E + HE; ++i) xr[i] = buf_load_f32(rs, live ? (s0 + P * i) * 4 : -4);
+                // the mask of this lane's pairs, in flight under the forward transform.  Frames beyond the clip's last (n_blocks) have none:
+                // the offset -8 reads zero, as does everything outside the clip's mask.
+                const bool has_a = live && 2 * q <= n_blocks, has_b = live && 2 * q + 1 <= n_blocks;
+                const int m0 = lane * sk + 2 * q * st;
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    ma[m] = buf_load_f32x2(rm, has_a ? m0 + P * m * sk : -8);
+                    mb[m] = buf_load_f32x2(rm, has_b ? m0 + P * m * sk + st : -8);
+                }
+                if (lane == 0) {   // bin H
+                    mah = buf_load_f32x2(rm, has_a ? H * sk + 2 * q * st : -8);
+                    mbh = buf_load_f32x2(rm, has_b ? H * sk + 2 * q * st + st : -8);
+                }
+#pragma unroll
+                for (int i = 0; i < E; ++i) {
+                    const float wv = window[lane + P * i];
+                    v[i] = make_float2(xr[i] * wv, xr[i + HE] * wv);
+                }
+                if constexpr (REST) {
+#pragma unroll
+                    for (int i = 0; i < E; ++i) raw[i] = xr[i];   // the inputs of blocks 2q - 1 (i < HE) and 2q, which this wave writes
+                }
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+                // bins 0 and H pair with themselves: their imaginary parts are discarded (a select, not a product: NaN there does nothing)
+                if (lane == 0) ma[0].y = 0.f, mb[0].y = 0.f;
+                mah.y = 0.f, mbh.y = 0.f;
+                // pairs (k, W - k), k = lane + P m < H; lane 0 takes k = H as well
+#pragma unroll
+                for (int m = 0; m < HE; ++m) {
+                    const int k = lane + P * m, kn = (W - k) & (W - 1);
+                    const int pk = phys_t<C::PS>(k), pn = phys_t<C::PS>(kn);
+                    float2 ck, cn;
+                    maskfilter_pair_c(buf[pk], buf[pn], ma[m], mb[m], ck, cn);
+                    buf[pk] = center_swap(ck);
+                    buf[pn] = center_swap(cn);
+                }
+                if (lane == 0) {
+                    const int ph = phys_t<C::PS>(H);
+                    float2 ck, cn;
+                    maskfilter_pair_c(buf[ph], buf[ph], mah, mbh, ck, cn);
+                    buf[ph] = center_swap(ck);
+                }
+                frame_sync<P>();
+                regs_read<LOG2W, K::LOG2E>(v, buf, lane);
+                frame_sync<P>();
+                fft_frame<LOG2W, K::LOG2E>(v, buf, lane, tw);
+            }
+            lds_barrier();   // A: every transform of the tile lies in LDS, swapped: .y = masked frame 2q, .x = masked frame 2q + 1
+            const bool writes_odd = live && q > q0;          // block 2q - 1 = second half of frame 2q - 1 + first half of frame 2q
+            const bool writes_even = live && 2 * q < b1;     // block 2q     = second half of frame 2q + first half of frame 2q + 1
+            const bool hands_on = f == F - 1 && live && q < q1;   // the tile's last transform: its imaginary second half is the next tile's carry
+            float yo[HE], ye[HE], keep[HE];
+            if (writes_odd) {
+                const float2* const prev = f > 0 ? buf - C::PITCH : nullptr;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    const int n = lane + P * i;
+                    const float a = f > 0 ? prev[phys_t<C::PS>(H + n)].x : carry[n];
+                    yo[i] = (a + buf[phys_t<C::PS>(n)].y) * gain;
+                }
+            }
+            if (writes_even) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    const int n = lane + P * i;
+                    ye[i] = (buf[phys_t<C::PS>(H + n)].y + buf[phys_t<C::PS>(n)].x) * gain;
+                }
+            }
+            if (hands_on) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) keep[i] = buf[phys_t<C::PS>(H + lane + P * i)].x;
+            }
+            lds_barrier();   // B: the frames and the carry have been read
+            if (hands_on) {
+#pragma unroll
+                for (int i = 0; i < HE; ++i) carry[lane + P * i] = keep[i];
+            }
+            if (writes_odd) {
+                const long long s = (long long)(2 * q - 1) * H + lane;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    if (s + P * i < CLIP_N) {   // nothing is written at or beyond sample N
+                        oc[s + P * i] = yo[i];
+                        if constexpr (REST) oc[CLIP_N + s + P * i] = raw[i] - yo[i];
+                    }
+                }
+            }
+            if (writes_even) {
+                const long long s = (long long)(2 * q) * H + lane;
+#pragma unroll
+                for (int i = 0; i < HE; ++i) {
+                    if (s + P * i < CLIP_N) {
+                        oc[s + P * i] = ye[i];
+                        if constexpr (REST) oc[CLIP_N + s + P * i] = raw[HE + i] - ye[i];
+                    }
+                }
+            }
+        }
+        lds_barrier();   // the next unit's first tile writes the frames this one's last tile may still be reading
+    }
+#undef CLIP_N
+}
+
+// One launch of k_maskfilter_c<LOG2W, REST, RAGGED>: equal-length clips cut here as run_maskfilter cuts them, or (RAGGED) the n units of d_units.
+template <int LOG2W, bool REST, bool RAGGED>
+static hipError_t run_maskfilter_c(const zafx_plan& pl, const float* x, const float2* mask, float* out, const MaskfilterUnit* d_units, int64_t n, int64_t n_samples) {
+    using K = MaskfilterCfg<LOG2W, true>;
+    auto kern = k_maskfilter_c<LOG2W, REST, RAGGED>;
+    const long long slots = lds_slots(pl.n_cus, K::SMEM);
+    if constexpr (RAGGED) {
+        return launch_walk<LOG2W>(pl, kern, kMaskfilterComplexRaggedKernel, K::NT, K::SMEM, n, slots, x, mask, pl.d_window, pl.d_tw_pass, out, d_units, 0LL, 0, 0, 0);
+    } else {
+        const int64_t n_blocks = n <= 0 ? 0 : (n_samples + K::H - 1) / K::H;
+        const int64_t mask_clip = (n_blocks + 1) * (K::H + 1);
+        const EqualSegments cut = n_blocks <= 0 ? EqualSegments{0, 0} : maskfilter_equal_segments(n_blocks, n, K::F, slots);
+        return launch_walk<LOG2W>(pl, kern, kMaskfilterComplexKernel, K::NT, K::SMEM, cut.segs * n, slots, x, mask, pl.d_window, pl.d_tw_pass, out, (long long)n_samples,
+                                  (long long)mask_clip, (int)n_blocks, (int)cut.seg_blocks, (int)cut.segs);
+    }
+}
+
+template <bool RAGGED>
+static hipError_t dispatch_maskfilter_c(const zafx_plan& pl, const float* x, const float2* mask, float* out, const MaskfilterUnit* d_units, int64_t n, int64_t n_samples) {
+    const bool rest = pl.kind == ZAFX_MASKFILTER_REST;
+    hipError_t e = hipErrorInvalidValue;
+    if (!dispatch_log2w(pl.log2nf, [&](auto lw) {
+            constexpr int L = decltype(lw)::value;
+            e = rest ? run_maskfilter_c<L, true, RAGGED>(pl, x, mask, out, d_units, n, n_samples) : run_maskfilter_c<L, false, RAGGED>(pl, x, mask, out, d_units, n, n_samples);
+        }))
+        set_error("mask filter: window_length must be 256, 512, 1024 or 2048");
+    return e;
+}
+
+// The launchers ask the refusal themselves as well as the entry points: no caller reaches the kernel with an FT plan or a clip of 2^27 samples.
+hipError_t launch_maskfilter_complex(const zafx_plan& pl, const float* x, const float2* mask, float* out, int64_t n_clips, int64_t n_samples) {
+    if (const char* why = maskfilter_complex_refusal(route_call(pl, x, out, n_clips, n_samples, 0))) {
+        set_error(why);
+        return hipErrorInvalidValue;
+    }
+    return dispatch_maskfilter_c<false>(pl, x, mask, out, nullptr, n_clips, n_samples);
+}
+
+hipError_t launch_maskfilter_complex_ragged(const zafx_plan& pl, const float* x, const float2* mask, float* out, const MaskfilterUnit* d_units, long long n_units) {
+    if (pl.layout != ZAFX_LAYOUT_TF || n_units >= (1LL << 31)) {
+        set_error(pl.layout != ZAFX_LAYOUT_TF ? "complex mask filter: masks in ZAFX_LAYOUT_TF only" : "mask filter: ragged batch too large for one launch (units >= 2^31)");
+        return hipErrorInvalidValue;
+    }
+    return dispatch_maskfilter_c<true>(pl, x, mask, out, d_units, n_units, 0);
+}
+
 }  // namespace zafx

@@ -33,6 +33,21 @@ ZAFX_HD void maskfilter_pair(float2 zk, float2 zn, float ma, float mb, float2& c
     cn = make_float2(ca.x + cb.y, cb.x - ca.y);
 }
 
+// The same pair under a COMPLEX mask M of the caller's, extended to its Hermitian mirror (M[W-k] = conj M[k]): ma, mb = M[k, 2j], M[k, 2j+1].
+// M_a A and M_b B are Hermitian again, so the re-pack is the one above with two complex products in place of the two scalings:
+//     ck = M_a A[k] + i M_b B[k],   cn = conj(M_a A[k]) + i conj(M_b B[k]).
+// k = 0 and k = W/2 pair with themselves, and their mirror is themselves: only Re M acts there (zaf.istft keeps the real part, zaf.py:223).
+// The CALLER hands those two bins' masks in with .y = 0 -- the value it was given is discarded, not multiplied by zero, so it may be
+// anything, NaN included --; then A, B and both products are real and ck == cn.
+// Not the bits of maskfilter_pair at Im M = 0: under -ffp-contract=fast the products contract differently.
+ZAFX_HD void maskfilter_pair_c(float2 zk, float2 zn, float2 ma, float2 mb, float2& ck, float2& cn) {
+    const float2 a2 = cadd_conj(zk, zn);            // 2 A[k]
+    const float2 b2 = mul_mi(csub_conj(zk, zn));    // 2 B[k]
+    const float2 ca = cmul(a2, cscale(ma, 0.5f)), cb = cmul(b2, cscale(mb, 0.5f));
+    ck = make_float2(ca.x - cb.y, ca.y + cb.x);
+    cn = make_float2(ca.x + cb.y, cb.x - ca.y);
+}
+
 // frames of a clip of n samples at hop H = W/2 (zaf.py:99-109): ceil(n / H) + 1
 constexpr long long maskfilter_frames(long long n_samples, int W) { return (n_samples + W / 2 - 1) / (W / 2) + 1; }
 

@@ -152,7 +152,9 @@ constexpr const char* kMelKernels[] = {"k_mel2", "k_mel", "k_mel_ft16b", "k_melf
 constexpr const char* kCqtKernel = "k_cqt";
 constexpr const char* kCenterKernel = "k_center";
 constexpr const char* kMaskfilterKernel = "k_maskfilter";
-constexpr const char* kMaskfilterStemsKernel = "k_maskfilter_stems";   // zafx_execute_masked_stems, whatever the stem count
+constexpr const char* kMaskfilterComplexKernel = "k_maskfilter_complex";                 // zafx_execute_masked_complex
+constexpr const char* kMaskfilterComplexRaggedKernel = "k_maskfilter_complex_ragged";   // zafx_execute_masked_complex_ragged
+constexpr const char* kMaskfilterStemsKernel ="k_maskfilter_stems";   // zafx_execute_masked_stems, whatever the stem count
 constexpr int kMaskfilterMaxStems = 8;                                 // (ZAFX_MASKFILTER_MAX_STEMS: a carry of W/2 floats per stem in LDS)
 constexpr const char* kernel_name(StftRoute r) { return kStftKernels[(int)r]; }
 constexpr const char* kernel_name(IstftRoute r) { return kIstftKernels[(int)r]; }
@@ -468,6 +470,40 @@ inline const char* maskfilter_stems_ragged_refusal(int kind, int layout, int64_t
         if (maskfilter_clip_refused(c)) {
             *clip = i;
             return "mask filter stems: a clip has 2^28 samples or more (not supported)";
+        }
+    }
+    return nullptr;
+}
+// zafx_execute_masked_complex: complex64 masks in ZAFX_LAYOUT_TF only (the FT stage in LDS would double: 148 KB at W = 2048 beside the
+// frames), and clips below 2^27 samples: a clip's mask -- 8 bytes a bin, T (W/2 + 1) bins -- lies behind one buffer descriptor with signed
+// 32-bit byte offsets.  Reads kind, layout and n.  nullptr: the call is taken.
+constexpr int64_t kMaskfilterComplexMaxSamples = 1LL << 27;
+// bytes of the compact TF complex64 mask of a clip of n samples
+constexpr int64_t maskfilter_complex_mask_bytes(int64_t n, int W) { return ((n + W / 2 - 1) / (W / 2) + 1) * (W / 2 + 1) * 8; }
+static_assert(maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 256) < (1LL << 31) &&
+                  maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 512) < (1LL << 31) &&
+                  maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 1024) < (1LL << 31) &&
+                  maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 2048) < (1LL << 31),
+              "complex mask filter: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+inline bool maskfilter_complex_clip_refused(const RouteCall& c) { return c.n >= kMaskfilterComplexMaxSamples; }
+inline const char* maskfilter_complex_refusal(const RouteCall& c) {
+    if (c.kind != ZAFX_MASKFILTER && c.kind != ZAFX_MASKFILTER_REST) return "complex mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only";
+    if (c.layout != ZAFX_LAYOUT_TF) return "complex mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)";
+    if (maskfilter_complex_clip_refused(c)) return "complex mask filter: clips of 2^27 samples and more are not supported";
+    return nullptr;
+}
+// zafx_execute_masked_complex_ragged: the kind and the layout as above, then every clip's length against the bound, before anything is read.
+// nullptr: the call is taken; otherwise *clip is the index of the clip refused, or -1 where the refusal is none of a clip's.
+inline const char* maskfilter_complex_ragged_refusal(int kind, int layout, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
+    *clip = -1;
+    RouteCall c;
+    c.kind = kind, c.layout = layout;
+    if (const char* why = maskfilter_complex_refusal(c)) return why;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        c.n = lengths[i];
+        if (maskfilter_complex_clip_refused(c)) {
+            *clip = i;
+            return "complex mask filter: a clip has 2^27 samples or more (not supported)";
         }
     }
     return nullptr;

@@ -92,6 +92,8 @@ SYMBOLS = {
     "zafx_plan_mask_dims": (_i, [_vp, _i64, ctypes.POINTER(_i64)]),
     "zafx_plan_mask_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
     "zafx_execute_masked_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
+    "zafx_execute_masked_complex": (_i, [_vp, _vp, _vp, _vp, _i64, _i64]),
+    "zafx_execute_masked_complex_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64]),
     "zafx_execute_masked_stems": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32]),
     "zafx_plan_stems_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "zafx_execute_masked_stems_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64,

@@ -425,10 +425,12 @@ class Plan:
                            ok and (lambda: (self.mask_shape(n_clips, n_in), self.out_shape(n_clips, n_in))))
         _lib.check(_lib.load().zafx_execute_masked(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked")
 
-    def _check_masked(self, name, masks, shape_call, for_what, d_in, d_mask, d_out, n_clips, n_in, shapes):
-        """execute_masked / execute_masked_stems: the checks of the three buffers.  `shapes`: false where the library itself refuses the call,
-        else a function giving the shapes of the masks and of the output; `name`, `masks`, `shape_call`, `for_what`: the messages' words."""
-        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
+    def _check_masked(self, name, masks, shape_call, for_what, d_in, d_mask, d_out, n_clips, n_in, shapes, mask_dtype=np.float32):
+        """execute_masked / execute_masked_stems / execute_masked_complex: the checks of the three buffers.  `shapes`: false where the library
+        itself refuses the call, else a function giving the shapes of the masks and of the output; `name`, `masks`, `shape_call`, `for_what`:
+        the messages' words; mask_dtype: the masks' (complex64 for execute_masked_complex)."""
+        mask_dtype = np.dtype(mask_dtype)
+        if d_in.dtype != np.float32 or d_mask.dtype != mask_dtype or d_out.dtype != np.float32:
             raise ValueError(f"{name} takes float32 samples, {masks} and a float32 output buffer")
         if n_clips < 0 or n_in < 0:
             raise ValueError("n_clips and n_in must not be negative")
@@ -436,8 +438,8 @@ class Plan:
             mask_shape, out_shape = shapes()
             if d_in.nbytes < n_clips * n_in * 4:
                 raise ValueError("d_in holds fewer than clips x n_in samples")
-            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * 4:
-                raise ValueError(f"d_mask must hold {shape_call} = {mask_shape} float32, got {d_mask.nbytes} bytes")
+            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * mask_dtype.itemsize:
+                raise ValueError(f"d_mask must hold {shape_call} = {mask_shape} {mask_dtype.name}, got {d_mask.nbytes} bytes")
             if d_out.nbytes < int(np.prod(out_shape, dtype=np.int64)) * 4:
                 raise ValueError(f"d_out is smaller than the plan's output for {for_what}")
 
@@ -463,6 +465,18 @@ class Plan:
         self._check_masked("execute_masked_stems", "float32 masks", "stems_mask_shape(n_clips, n_in, n_stems)", "these clips and stems", d_in, d_mask, d_out,
                            n_clips, n_in, ok and (lambda: (self.stems_mask_shape(n_clips, n_in, n_stems), self.stems_out_shape(n_clips, n_in, n_stems))))
         _lib.check(_lib.load().zafx_execute_masked_stems(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, n_stems), "zafx_execute_masked_stems")
+
+    def execute_masked_complex(self, d_in, d_mask, d_out, n_clips, n_in):
+        """Enqueue the mask filter under complex masks on the plan's stream (asynchronous; zafx_execute_masked_complex, mask filter plans of
+        layout "TF" only; last_kernel: k_maskfilter_complex): y = istft(concat(M, conj(M[-2:0:-1])) * stft(x))[0:n_in].  d_in (clips, n_in)
+        float32 samples, d_mask complex64 of mask_shape(n_clips, n_in) = (clips, frames, W/2 + 1), d_out of out_shape(n_clips, n_in).  The
+        imaginary parts of mask rows 0 and W/2 have no effect.  Buffers of another dtype or too small for these clips raise ValueError before
+        anything is enqueued."""
+        n_clips, n_in = int(n_clips), int(n_in)
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and self.layout == _lib.LAYOUT_TF   # (otherwise: the library says so)
+        self._check_masked("execute_masked_complex", "a complex64 mask", "mask_shape(n_clips, n_in)", "these clips", d_in, d_mask, d_out, n_clips, n_in,
+                           ok and (lambda: (self.mask_shape(n_clips, n_in), self.out_shape(n_clips, n_in))), mask_dtype=np.complex64)
+        _lib.check(_lib.load().zafx_execute_masked_complex(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked_complex")
 
     def ragged_layout(self, lengths):
         """Placement of a ragged batch's results (zafx_plan_ragged_layout) for clips of `lengths` samples: -> (out_offsets, frames, pitch), int64
@@ -537,10 +551,12 @@ class Plan:
         _lib.check(_lib.load().zafx_execute_masked_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
                                                           d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_ragged")
 
-    def _masked_ragged_args(self, name, n_stems, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets):
-        """execute_masked_ragged (n_stems None) / execute_masked_stems_ragged: the per-clip arrays as int64 without the totals the layout calls
-        append, and the checks of the three buffers -> (in_offsets, lengths, mask_offsets, out_offsets).  `name`: the method in the messages."""
+    def _masked_ragged_args(self, name, n_stems, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, complex_mask=False):
+        """execute_masked_ragged (n_stems None) / execute_masked_stems_ragged / execute_masked_complex_ragged (n_stems None, complex_mask: the mask
+        array is complex64 and mask_offsets count its elements): the per-clip arrays as int64 without the totals the layout calls append, and
+        the checks of the three buffers -> (in_offsets, lengths, mask_offsets, out_offsets).  `name`: the method in the messages."""
         stems = n_stems is not None
+        mask_dtype = np.dtype(np.complex64 if complex_mask else np.float32)
         in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
         out_offsets, mask_offsets = _as_int64(out_offsets, "out_offsets"), _as_int64(mask_offsets, "mask_offsets")
         if len(mask_offsets) == len(lengths) + 1:
@@ -549,13 +565,15 @@ class Plan:
             out_offsets = np.ascontiguousarray(out_offsets[:-1])
         if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
             raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
-        if any(b.dtype != np.float32 for b in (d_in, d_mask, d_out)):
-            raise ValueError(f"{name} takes float32 samples, {'float32 masks' if stems else 'a float32 mask'} and a float32 output buffer")
+        if d_in.dtype != np.float32 or d_mask.dtype != mask_dtype or d_out.dtype != np.float32:
+            raise ValueError(f"{name} takes float32 samples, {'float32 masks' if stems else f'a {mask_dtype.name} mask'} and a float32 output buffer")
         ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and len(lengths)   # (another kind, negative values: the library says so)
         if stems:   # (... as it does of a stem count or a clip it refuses)
             ok = ok and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS
+        if complex_mask:   # (... or of a plan in "FT")
+            ok = ok and self.layout == _lib.LAYOUT_TF
         if ok and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0 and not (
-                stems and int(lengths.max()) >= 1 << 28):
+                stems and int(lengths.max()) >= 1 << 28) and not (complex_mask and int(lengths.max()) >= 1 << 27):
             h = int(self.params.window_length) // 2
             frames = (lengths + h - 1) // h + 1
             if stems:   # compact "TF" masks back to back
@@ -569,11 +587,23 @@ class Plan:
             live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
             if int((in_offsets + lengths).max()) * 4 > d_in.nbytes:
                 raise ValueError("a clip reaches past the end of d_in")
-            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
+            if live.any() and int(mask_ends[live].max()) * mask_dtype.itemsize > d_mask.nbytes:
                 raise ValueError(f"a clip's {'masks reach' if stems else 'mask reaches'} past the end of d_mask")
             if int((out_offsets + blocks * lengths).max()) * 4 > d_out.nbytes:
                 raise ValueError("a clip's result reaches past the end of d_out")
         return in_offsets, lengths, mask_offsets, out_offsets
+
+    def execute_masked_complex_ragged(self, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets):
+        """Enqueue the mask filter under complex masks for mono clips of different lengths as one launch on the plan's stream (asynchronous;
+        zafx_execute_masked_complex_ragged, mask filter plans of layout "TF" only; last_kernel: k_maskfilter_complex_ragged).  in_offsets,
+        lengths and out_offsets count float32 elements as in execute_masked_ragged; mask_offsets counts complex64 elements: clip i's mask,
+        (T_i, W/2 + 1) compact, starts at complex element mask_offsets[i] of d_mask (mask_ragged_layout gives the compact placement; its total
+        may stay on).  Clip i's block has the bits execute_masked_complex gives that clip and mask alone.  Output blocks that overlap are not
+        detected."""
+        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args("execute_masked_complex_ragged", None, d_in, in_offsets, lengths, d_mask,
+                                                                                  mask_offsets, d_out, out_offsets, complex_mask=True)
+        _lib.check(_lib.load().zafx_execute_masked_complex_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
+                                                                  d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_complex_ragged")
 
     def stems_ragged_layout(self, lengths, n_stems):
         """Placement of a ragged stems batch (zafx_plan_stems_ragged_layout, mask filter plans of layout "TF") for clips of `lengths` samples
@@ -1366,11 +1396,11 @@ def maskfilter_batch(clips, window_function, masks, step_length=None, rest=False
     return (out[:, 0], out[:, 1]) if rest else out
 
 
-def _masked_round_trip(plan, clips, masks, out, execute):
-    """maskfilter_batch / maskfilter_stems_batch: clips and masks up as float32, execute(d_in, d_mask, d_out) and the wait under the plan's
-    lock, the result down into `out`."""
-    x, m = np.ascontiguousarray(clips, dtype=np.float32), np.ascontiguousarray(masks, dtype=np.float32)
-    d_in, d_mask, d_out = (DeviceBuffer(b.shape, np.float32, plan.device) for b in (x, m, out))
+def _masked_round_trip(plan, clips, masks, out, execute, mask_dtype=np.float32):
+    """maskfilter_batch / maskfilter_stems_batch / maskfilter_complex_batch: clips up as float32 and masks as mask_dtype, execute(d_in, d_mask,
+    d_out) and the wait under the plan's lock, the result down into `out`."""
+    x, m = np.ascontiguousarray(clips, dtype=np.float32), np.ascontiguousarray(masks, dtype=mask_dtype)
+    d_in, d_mask, d_out = (DeviceBuffer(b.shape, b.dtype, plan.device) for b in (x, m, out))
     try:
         d_in.upload(x)
         d_mask.upload(m)
@@ -1419,6 +1449,46 @@ def maskfilter_stems_batch(clips, window_function, masks, step_length=None, rest
         _masked_round_trip(plan, a, m.transpose(0, 1, 3, 2) if ft else m, out,
                            lambda d_in, d_mask, d_out: plan.execute_masked_stems(d_in, d_mask, d_out, n_clips, n, n_stems))
     return (out[:, :n_stems], out[:, n_stems]) if rest else out
+
+
+def _as_complex_masks(masks):
+    """The masks of the complex mask filter as an array: real or complex numbers (cast to complex64 at the upload); anything else raises."""
+    m = np.asarray(masks)
+    if m.dtype.kind not in "biufc":
+        raise ValueError(f"masks must be real or complex numbers, got dtype {m.dtype}")
+    return m
+
+
+def maskfilter_complex_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
+    """The mask filter under COMPLEX masks for a batch of mono clips in one kernel (k_maskfilter_complex): clips (B, N) real and masks
+    (B, W/2 + 1, T), the reference's order -- (B, T, W/2 + 1) with layout "TF" --, real or complex (cast to complex64), T = ceil(N / (W/2)) + 1
+    -> y = istft(concat(M, conj(M[-2:0:-1])) * stft(x))[0:N] (zaf.py:185-195 with the mask's Hermitian mirror; istft keeps the real part),
+    float32 (B, N); with rest=True (y, rest = x - y), views of one (B, 2, N) result (which `out`, if given, is).  The imaginary parts of mask
+    rows 0 and W/2 have no effect.  The device reads "TF" masks only: "FT" masks are transposed on the host before the upload, as
+    maskfilter_stems_batch does.  step_length: None or window_length / 2."""
+    w = _maskfilter_window(window_function, step_length)
+    a, m = np.asarray(clips), _as_complex_masks(masks)
+    if a.ndim != 2:
+        raise ValueError(f"clips must be mono, (clips, samples), got shape {a.shape}")
+    if np.iscomplexobj(a):
+        raise ValueError("clips must be real")
+    n_clips, n = a.shape
+    h = len(w) // 2
+    frames, rows = (n + h - 1) // h + 1, h + 1
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    want = (n_clips, rows, frames) if ft else (n_clips, frames, rows)
+    if m.shape != want:
+        raise ValueError(f"masks must have shape {want} for clips of {n} samples (layout {layout!r}), got {m.shape}")
+    shape = (n_clips, 2, n) if rest else (n_clips, n)
+    if out is None:
+        out = np.empty(shape, np.float32)
+    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
+    if out.size:
+        plan = maskfilter_plan(w, rest, "TF", device)
+        _masked_round_trip(plan, a, m.transpose(0, 2, 1) if ft else m, out,
+                           lambda d_in, d_mask, d_out: plan.execute_masked_complex(d_in, d_mask, d_out, n_clips, n), mask_dtype=np.complex64)
+    return (out[:, 0], out[:, 1]) if rest else out
 
 
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
@@ -1915,11 +1985,11 @@ def centersides_ragged(clips, window_function, step_length=None, sides=True, dev
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
 
 
-def _ragged_mask_items(masks, lengths, window_length, ndim, batch, items):
-    """pack_ragged_masks / pack_ragged_stems_masks: -> (the masks as `ndim`-D arrays, one per clip of `lengths`, H = W/2, the clips' frame counts
-    ceil(N_i / H) + 1); `batch`, `items`: the messages' words."""
+def _ragged_mask_items(masks, lengths, window_length, ndim, batch, items, complex_ok=False):
+    """pack_ragged_masks / pack_ragged_stems_masks / pack_ragged_complex_masks (complex_ok): -> (the masks as `ndim`-D arrays, one per clip of
+    `lengths`, H = W/2, the clips' frame counts ceil(N_i / H) + 1); `batch`, `items`: the messages' words."""
     h = int(window_length) // 2
-    arrays = _as_ragged_items(masks, ndim, batch, items, "mask", empty_ok=True)
+    arrays = _as_ragged_items(masks, ndim, batch, items, "mask", empty_ok=True, complex_ok=complex_ok)
     if len(arrays) != len(lengths):
         raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
     return arrays, h, (lengths + h - 1) // h + 1
@@ -1975,13 +2045,51 @@ def _masked_ragged_round_trip(plan, arrays, lengths, packed_masks, blocks, execu
     for a, o in zip(arrays, in_offsets.tolist()):
         x[o:o + len(a)] = a
     out_offsets = blocks * in_offsets
-    d_mask = DeviceBuffer(packed_masks.shape, np.float32, plan.device)
+    d_mask = DeviceBuffer(packed_masks.shape, packed_masks.dtype, plan.device)
     try:
         d_mask.upload(packed_masks)
         res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: execute(d_in, in_offsets, d_mask, d_out, out_offsets))
     finally:
         d_mask.free()
     return res, out_offsets
+
+
+def pack_ragged_complex_masks(masks, lengths, window_length, layout="FT"):
+    """One contiguous complex64 array of a ragged batch's complex masks: a sequence of real or complex (W/2 + 1, T_i) arrays -- (T_i, W/2 + 1)
+    with layout "TF" --, T_i = ceil(lengths[i] / (W/2)) + 1 -> (packed 1-D complex64, mask_offsets of len(lengths) + 1 in complex64 elements),
+    the layout of Plan.mask_ragged_layout for a "TF" plan of that window_length: clip i's mask as (T_i, W/2 + 1) compact, the clips back to
+    back.  The device reads "TF" masks only: "FT" masks are transposed here, on the host.  A mask of another shape raises ValueError with
+    the clip's index."""
+    lengths = _as_lengths(lengths)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 2, "ragged mask batch", "2-D masks", complex_ok=True)
+    offsets = np.zeros(len(lengths) + 1, np.int64)
+    offsets[1:] = np.cumsum(frames * (h + 1))
+    packed = np.zeros(max(int(offsets[-1]), 1), np.complex64)
+    for i, (m, o, t) in enumerate(zip(arrays, offsets.tolist(), frames.tolist())):
+        want = (h + 1, t) if ft else (t, h + 1)
+        if m.shape != want:
+            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} samples (layout {layout!r}), got {m.shape}")
+        packed[o:o + t * (h + 1)].reshape(t, h + 1)[...] = m.T if ft else m
+    return packed, offsets
+
+
+def maskfilter_complex_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
+    """maskfilter_complex_batch of mono clips of different lengths in one launch: a sequence of 1-D real clips and one of real or complex masks,
+    (W/2 + 1, T_i) -- (T_i, W/2 + 1) with layout "TF" --, T_i = ceil(N_i / (W/2)) + 1 -> a list of float32 (N_i,) arrays, or of (y_i, rest_i)
+    pairs with rest=True, each a view of the one result buffer; every clip's result has the bits maskfilter_complex_batch gives for that clip
+    alone.  One upload each of clips and masks, one launch (k_maskfilter_complex_ragged), one download.  "FT" masks are transposed on the
+    host (pack_ragged_complex_masks).  Window and step_length as in maskfilter_batch."""
+    w = _maskfilter_window(window_function, step_length)
+    arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
+    lengths = np.array([len(a) for a in arrays], np.int64)
+    m, mask_offsets = pack_ragged_complex_masks(masks, lengths, len(w), layout)
+    plan = maskfilter_plan(w, rest, "TF", device)
+    res, out_offsets = _masked_ragged_round_trip(plan, arrays, lengths, m, 2 if rest else 1, lambda d_in, in_offsets, d_mask, d_out, out_offsets:
+                                                 plan.execute_masked_complex_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets))
+    if not rest:
+        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
 
 
 def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
@@ -2234,6 +2342,18 @@ def maskfilter(audio_signal, window_function, step_length, mask):
     if m.ndim != 2:
         raise ValueError(f"mask must be 2-D (window_length / 2 + 1, number_times), got shape {m.shape}")
     return maskfilter_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
+
+
+def maskfilter_complex(audio_signal, window_function, step_length, mask):
+    """zaf.istft(np.concatenate((mask, np.conj(mask[-2:0:-1]))) * zaf.stft(audio_signal, window_function, step_length), window_function,
+    step_length)[0:N] in one call: a 1-D signal and a complex (or real) (W/2 + 1, T) mask -> float64 (N,); step_length must be
+    window_length / 2 (see maskfilter_complex_batch)."""
+    a, m = np.asarray(audio_signal), np.asarray(mask)
+    if a.ndim != 1:
+        raise ValueError(f"audio_signal must be 1-D, got shape {a.shape}")
+    if m.ndim != 2:
+        raise ValueError(f"mask must be 2-D (window_length / 2 + 1, number_times), got shape {m.shape}")
+    return maskfilter_complex_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
 
 
 def maskfilter_stems(audio_signal, window_function, step_length, masks):
