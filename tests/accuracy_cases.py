@@ -7,6 +7,7 @@ import numpy as np
 
 import const_probe as cp
 import linear_cases as lc
+import maskfilter_cases as mc
 import plain
 import route_cases as rc
 from oracle import zaf_oracle as orc
@@ -236,6 +237,23 @@ def linear_case(name):
     rows, cols, count = lc.CASES[LINEAR_NAMES.index(name)]
     x, m, pick = lc.clips(rows, cols, count), lc.matrix(rows, cols), lc.judged(count)
     return x, m, pick, lc.reference(x[pick], m), lc.kernel(rows, cols, count)
+
+
+# ------------------------------------------------------------------------------------------------ tests/maskfilter_cases.py
+# The six fused STFT-mask-ISTFT kernels: 5 forms x W = 256 ... 2048 x T = 62 / 63 x with and without the rest, each through its equal-length
+# launch ("maskfilter/<case>") and, with clips of 1, H, 3 H + 7 and 0 samples between the same clips, through its ragged one
+# ("maskfilter/<case>/ragged").  Reference: the float64 oracle's composition; yardstick: plain.maskfilter* at float32 -- unpacked, one frame per
+# transform, where the kernels ride two frames in one transform and split them.  Every stem of every clip, and the rest, is a 1-D result of its
+# own; the block length of e_row / e_col is the hop.  Family factors, no entry in OWN_FACTORS.
+MASKFILTER_NAMES = list(mc.ACCURACY_CASES)
+
+
+def maskfilter_case(name):
+    """-> (form, W, rest, the batch, its ragged twin, the twin's index of each clip of the batch)."""
+    form, wl, _, rest = mc.ACCURACY_CASES[name]
+    b, e = mc.accuracy_batch(name)
+    twin, where = mc.ragged_twin(b, e)
+    return form, wl, rest, b, twin, where
 
 
 # Cases built like those of tests/const_probe.py.  float64 Bluestein at W = 1000: the library's only device-side trigonometry (sincospi in

@@ -36,8 +36,8 @@ def mask_error(y, ref, x):
 
 
 def make_mask(kind, wl, n, seed=0):
-    """The test masks, all in [0, 1], float32 (W/2 + 1, T): "ones", "uniform" in [0.25, 1], "sparse" (2 % ones, the rest zeros), "unit"
-    (uniform in [0, 1])."""
+    """The test masks, float32 (W/2 + 1, T): "ones", "uniform" in [0.25, 1], "sparse" (2 % ones, the rest zeros), "unit" (uniform in [0, 1])
+    -- all in [0, 1] -- and "signed_wide", uniform in [-2, 2]: both signs and moduli above one."""
     shape = (wl // 2 + 1, mask_frames(n, wl))
     g = np.random.default_rng([77, seed, wl, n])
     if kind == "ones":
@@ -48,6 +48,8 @@ def make_mask(kind, wl, n, seed=0):
         return (g.random(shape) < 0.02).astype(np.float32)
     if kind == "unit":
         return g.random(shape).astype(np.float32)
+    if kind == "signed_wide":
+        return g.uniform(-2.0, 2.0, shape).astype(np.float32)
     raise ValueError(kind)
 
 

@@ -121,6 +121,48 @@ def istft(spec, window, hop, dtype, onesided=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ mask filter  (zaf.py:185-195)
+def _maskfilter(x, window, mirrored, dtype):
+    """x (N,), mirrored (W, T): the two-sided mask -> (N,): istft(mirrored * stft(x)) at hop W / 2, unpacked, one frame per transform."""
+    dtype = real_of(dtype)
+    x = np.asarray(x)
+    assert x.ndim == 1 and mirrored.shape[0] == len(window), (x.shape, mirrored.shape)
+    hop = len(window) // 2
+    spec = stft(x[None], window, hop, dtype)
+    assert spec.shape[1:] == mirrored.shape, (spec.shape, mirrored.shape)
+    prod = spec * mirrored[None]   # (mirrored: already `dtype` or its complex type)
+    assert prod.dtype == complex_of(dtype)
+    out = istft(prod, window, hop, dtype)[0, :len(x)]
+    assert out.dtype == dtype
+    return out
+
+
+def maskfilter(x, window, mask, dtype):
+    """x (N,), mask (W/2 + 1, T) real -> (N,): y = istft(concat(m, m[-2:0:-1]) * stft(x, w, W/2), w, W/2)[0:N]."""
+    m = np.asarray(mask).astype(real_of(dtype))
+    return _maskfilter(x, window, np.concatenate((m, m[-2:0:-1])), dtype)
+
+
+def maskfilter_complex(x, window, mask, dtype):
+    """The same under a complex mask (W/2 + 1, T) and its Hermitian mirror, concat(M, conj(M[-2:0:-1])); istft keeps the real part."""
+    m = np.asarray(mask).astype(complex_of(dtype))
+    return _maskfilter(x, window, np.concatenate((m, np.conj(m[-2:0:-1]))), dtype)
+
+
+def maskfilter_stems(x, window, masks, dtype, rest=False):
+    """x (N,), masks (S, W/2 + 1, T) real -> (S, N), with rest (S + 1, N): the last row is ((x - y_0) - y_1) - ... in `dtype`, left to right."""
+    dtype = real_of(dtype)
+    rows = [maskfilter(x, window, m, dtype) for m in masks]
+    if rest:
+        r = np.asarray(x).astype(dtype)
+        for y in rows:
+            r = r - y
+        rows.append(r)
+    out = np.stack(rows)
+    assert out.dtype == dtype
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ mdct / imdct  (zaf.py:984-1184)
 def mdct_num_frames(n, wl):
     return -(-n // (wl // 2)) + 1

@@ -6,7 +6,7 @@ the refusals.
 
 Bound: max|y - ref| <= 1e-5 max(max|ref|, max|x|) -- the project's TOL_FFT for a float32 transform chain against float64, at the larger of
 the reference's and the input's level (a sparse mask leaves a reference far below the input whose rounding error it inherits).  Test masks
-lie in [0, 1].  F is the number of packed transforms per tile, so a tile is 2 F frames."""
+lie in [0, 1] but "signed_wide", uniform in [-2, 2].  F is the number of packed transforms per tile, so a tile is 2 F frames."""
 import ctypes
 import os
 import subprocess
@@ -102,18 +102,21 @@ def edge_lengths(wl):
     return [1, h - 1, h, h + 1, 2 * h - 1, 2 * h, 2 * h + 1, 2 * f * h - 1, 2 * f * h, 2 * f * h + 1, 4 * f * h + 3, 44100]
 
 
+EDGE_MASKS = ("ones", "uniform", "sparse", "signed_wide")   # ones, uniform [0.25, 1], 2 % sparse, uniform [-2, 2]
+
+
 @pytest.fixture(scope="module")
 def edge_cases():
-    """Per W: [(N, x (3, N), masks (3, W/2 + 1, T): ones, uniform [0.25, 1], 2 % sparse, refs)], the oracle computed once."""
+    """Per W: [(N, x (4, N), masks (4, W/2 + 1, T): EDGE_MASKS, refs)], the oracle computed once."""
     import zafx
     cases = {}
     for wl in WINDOWS:
         w = zafx.hamming(wl)
         cases[wl] = []
         for n in edge_lengths(wl):
-            x = np.stack([clip(k, n) for k in range(3)])
-            m = np.stack([make_mask(kind, wl, n) for kind in ("ones", "uniform", "sparse")])
-            cases[wl].append((n, x, m, [oracle_maskfilter(x[k], w, m[k]) for k in range(3)]))
+            x = np.stack([clip(k, n) for k in range(len(EDGE_MASKS))])
+            m = np.stack([make_mask(kind, wl, n) for kind in EDGE_MASKS])
+            cases[wl].append((n, x, m, [oracle_maskfilter(x[k], w, m[k]) for k in range(len(EDGE_MASKS))]))
     return cases
 
 
@@ -125,7 +128,7 @@ def test_oracle_parity_at_the_edges(edge_cases, wl, layout, row_align):
     worst = 0.0
     for n, x, m, refs in edge_cases[wl]:
         y = run_plan(x, m, w, layout=layout, row_align=row_align)
-        for k, kind in enumerate(("ones", "uniform", "sparse")):
+        for k, kind in enumerate(EDGE_MASKS):
             worst = max(worst, check(y[k], refs[k], x[k], f"W={wl} N={n} {layout}/{row_align} {kind}"))
     print(f"W={wl} {layout}/{row_align}: worst {worst:.3e}")
 
@@ -180,6 +183,41 @@ def test_batch_independence(layout, row_align):
     for i in (0, 5, 17, 36):
         assert np.array_equal(bits(run_plan(x[i:i + 1], m[i:i + 1], w, True, layout, row_align)[0]), bits(out[i])), i
     check(out[17, 0], oracle_maskfilter(x[17], w, m[17]), x[17], "clip 17 of 37")
+
+
+def touched(n, h, frames):
+    """The samples of a clip of n that frames `frames` reach, partners included: frames 2j and 2j + 1 share a transform, frame t covers
+    samples (t - 1) H .. (t + 1) H - 1."""
+    hit = np.zeros(n, bool)
+    for t in frames:
+        for u in (t, t ^ 1):
+            hit[max((u - 1) * h, 0):min((u + 1) * h, n)] = True
+    return hit
+
+
+@pytest.mark.parametrize("layout, row_align", LAYOUTS)
+@pytest.mark.parametrize("wl", [256, 2048])
+def test_containment(wl, layout, row_align):
+    """A NaN sample and a NaN mask value in clip 1 of three (the "FT" forms stage several frames of mask in LDS): clips 0 and 2 have the bits of
+    their runs alone and of the clean batch; inside clip 1 the samples of the frames that hold the NaN sample or mask value, and of the frames
+    paired with them, may be non-finite -- every other sample has the bits of the clean run."""
+    import zafx
+    w, h = zafx.hamming(wl), wl // 2
+    n = 20 * h + 9
+    x = np.stack([clip(30 + k, n) for k in range(3)])
+    m = np.stack([make_mask("unit", wl, n, seed=30 + k) for k in range(3)])
+    clean = run_plan(x, m, w, layout=layout, row_align=row_align)
+    s, (k, t) = 5 * h + 17, (h // 3, 13)   # sample s lies in frames 5 and 6; the mask value in frame 13
+    xp, mp = x.copy(), m.copy()
+    xp[1, s] = np.nan
+    mp[1, k, t] = np.nan
+    got = run_plan(xp, mp, w, layout=layout, row_align=row_align)
+    for c in (0, 2):
+        alone = run_plan(x[c:c + 1], m[c:c + 1], w, layout=layout, row_align=row_align)[0]
+        assert np.array_equal(bits(got[c]), bits(alone)) and np.array_equal(bits(got[c]), bits(clean[c])), (wl, layout, c)
+    may = touched(n, h, [s // h, s // h + 1, t])
+    assert not np.isfinite(got[1][may]).all() and np.isfinite(got[1][~may]).all()
+    assert np.array_equal(bits(got[1][~may]), bits(clean[1][~may])) and 0 < may.sum() < n
 
 
 def test_segments_give_the_bits_of_whole_clips():

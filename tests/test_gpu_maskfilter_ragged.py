@@ -250,6 +250,45 @@ def test_permutation():
             assert np.array_equal(bits(permuted[k]), bits(straight[i])), (layout, k, i)
 
 
+# ------------------------------------------------------------------------------------------------------------------ 5b
+def touched(n, h, frames):
+    """The samples of a clip of n that frames `frames` reach, partners included: frames 2j and 2j + 1 share a transform, frame t covers
+    samples (t - 1) H .. (t + 1) H - 1."""
+    hit = np.zeros(n, bool)
+    for t in frames:
+        for u in (t, t ^ 1):
+            hit[max((u - 1) * h, 0):min((u + 1) * h, n)] = True
+    return hit
+
+
+@pytest.mark.parametrize("wl", [256, 2048])
+def test_containment(wl):
+    """A NaN sample and a NaN mask value in one clip of a ragged batch, in every mask layout, with the rest: every other clip has the bits of its
+    run alone and of the clean batch; inside that clip only the samples of the frames that hold the NaN sample or mask value, and of the frames
+    paired with them, may be non-finite -- every other sample has the bits of the clean run."""
+    h = wl // 2
+    n = 20 * h + 9
+    lengths = [7 * h + 3, 0, n, 1, 20 * h + 9]
+    clips, masks = batch_of(wl, lengths, seed=80)
+    s, (k, t), at = 5 * h + 17, (h // 3, 13), 2   # sample s lies in frames 5 and 6; the mask value in frame 13
+    bad_clips, bad_masks = [c.copy() for c in clips], [m.copy() for m in masks]
+    bad_clips[at][s] = np.nan
+    bad_masks[at][k, t] = np.nan
+    may = touched(n, h, [s // h, s // h + 1, t])
+    assert 0 < may.sum() < n
+    for layout, row_align in LAYOUTS:
+        plan = plan_of(wl, True, layout, row_align)
+        clean = results(*run_ragged(plan, clips, masks)[:3], 2)
+        got = results(*run_ragged(plan, bad_clips, bad_masks)[:3], 2)
+        others = [i for i in range(len(clips)) if i != at]
+        assert_equal_alone([got[i] for i in others], [clips[i] for i in others], [masks[i] for i in others], wl, True, layout, row_align, what="containment")
+        for i in others:
+            assert np.array_equal(bits(got[i]), bits(clean[i])), (wl, layout, row_align, i)
+        for j in range(2):
+            assert not np.isfinite(got[at][j][may]).all() and np.isfinite(got[at][j][~may]).all(), (wl, layout, row_align, j)
+            assert np.array_equal(bits(got[at][j][~may]), bits(clean[at][j][~may])), (wl, layout, row_align, j)
+
+
 # ------------------------------------------------------------------------------------------------------------------ 6
 def test_back_to_back_calls_each_see_their_own_table():
     wl = 1024

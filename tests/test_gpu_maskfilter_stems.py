@@ -98,7 +98,7 @@ def singles(x, m, w):
 
 @pytest.fixture(scope="module")
 def cases():
-    """Per W: [(N, x (3, N), masks (3, 8, T, W/2 + 1) "unit" with a seed per (clip, stem), refs (3, 8, N) float64, one (3, 8, N): the one-mask
+    """Per W: [(N, x (3, N), masks (3, 8, T, W/2 + 1) "unit" -- stem 1 "signed_wide", uniform in [-2, 2] -- with a seed per (clip, stem), refs (3, 8, N) float64, one (3, 8, N): the one-mask
     kind's bits)]; S stems are the first S masks.  The oracle and the one-mask kind run once."""
     import zafx
     out = {}
@@ -107,7 +107,7 @@ def cases():
         out[wl] = []
         for n in lengths(wl):
             x = np.stack([clip(k, n) for k in range(3)])
-            m = np.stack([np.stack([make_mask("unit", wl, n, seed=10 * k + s) for s in range(8)]) for k in range(3)])
+            m = np.stack([np.stack([make_mask("signed_wide" if s == 1 else "unit", wl, n, seed=10 * k + s) for s in range(8)]) for k in range(3)])
             refs = np.stack([np.stack([oracle_maskfilter(x[k], w, m[k, s]) for s in range(8)]) for k in range(3)])
             mt = tf(m)
             out[wl].append((n, x, mt, refs, singles(x, mt, w)))
@@ -175,6 +175,71 @@ def test_fixed_values():
         bad[0, n // 2] = np.nan   # a non-finite value stays within its own clip
         out = run_stems(bad, m, w, True)
         assert np.isnan(out[0]).any() and np.array_equal(bits(out[1]), bits(full[1]))
+
+
+def touched(n, h, frames):
+    """The samples of a clip of n that frames `frames` reach, partners included: frames 2j and 2j + 1 share a transform, frame t covers
+    samples (t - 1) H .. (t + 1) H - 1."""
+    hit = np.zeros(n, bool)
+    for t in frames:
+        for u in (t, t ^ 1):
+            hit[max((u - 1) * h, 0):min((u + 1) * h, n)] = True
+    return hit
+
+
+def containment_case(wl):
+    """-> (h, n, x (3, N), masks (3, 3, T, W/2 + 1) "unit")."""
+    h = wl // 2
+    n = 20 * h + 9
+    x = np.stack([clip(30 + k, n) for k in range(3)])
+    return h, n, x, tf(np.stack([np.stack([make_mask("unit", wl, n, seed=10 * (30 + k) + j) for j in range(3)]) for k in range(3)]))
+
+
+@pytest.mark.parametrize("wl", [256, 2048])
+def test_containment(wl):
+    """A NaN sample in clip 1 of three and a NaN in the mask of its stem 0, with the rest: clips 0 and 2 have the bits of their runs alone and of
+    the clean batch; inside clip 1 only the samples of the frames that hold the NaN sample or mask value, and of the frames paired with them,
+    may be non-finite, in any stem or the rest -- every other sample has the bits of the clean run."""
+    import zafx
+    w = zafx.hamming(wl)
+    h, n, x, m = containment_case(wl)
+    clean = run_stems(x, m, w, True)
+    s, (k, t) = 5 * h + 17, (h // 3, 13)   # sample s lies in frames 5 and 6; the mask value in frame 13
+    xp, mp = x.copy(), m.copy()
+    xp[1, s] = np.nan
+    mp[1, 0, t, k] = np.nan
+    got = run_stems(xp, mp, w, True)
+    for c in (0, 2):
+        assert np.array_equal(bits(got[c]), bits(run_stems(x[c:c + 1], m[c:c + 1], w, True)[0])) and np.array_equal(bits(got[c]), bits(clean[c])), (wl, c)
+    may = touched(n, h, [s // h, s // h + 1, t])
+    assert 0 < may.sum() < n
+    for j in range(4):
+        assert not np.isfinite(got[1, j][may]).all() and np.isfinite(got[1, j][~may]).all(), (wl, j)
+        assert np.array_equal(bits(got[1, j][~may]), bits(clean[1, j][~may])), (wl, j)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf], ids=["nan", "inf"])
+@pytest.mark.parametrize("wl", [256, 2048])
+def test_a_stem_s_mask_stays_out_of_the_other_stems(wl, bad):
+    """The stems share ONE forward transform.  A NaN, then +inf, in the mask of stem 1 of clip 1 alone: stems 0 and 2 of every clip have the bits
+    of the clean run everywhere; stem 1 and the rest are non-finite only in the samples of that frame and of its partner."""
+    import zafx
+    w = zafx.hamming(wl)
+    h, n, x, m = containment_case(wl)
+    clean = run_stems(x, m, w, True)
+    k, t = h // 3, 13
+    mp = m.copy()
+    mp[1, 1, t, k] = bad
+    got = run_stems(x, mp, w, True)
+    for c in (0, 2):
+        assert np.array_equal(bits(got[c]), bits(clean[c])), (wl, c)
+    for j in (0, 2):
+        assert np.array_equal(bits(got[1, j]), bits(clean[1, j])), (wl, "stem", j)
+    may = touched(n, h, [t])
+    assert 0 < may.sum() < n
+    for j in (1, 3):
+        assert not np.isfinite(got[1, j][may]).all() and np.isfinite(got[1, j][~may]).all(), (wl, j)
+        assert np.array_equal(bits(got[1, j][~may]), bits(clean[1, j][~may])), (wl, j)
 
 
 def test_segments_give_the_bits_of_whole_clips():

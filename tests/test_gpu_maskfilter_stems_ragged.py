@@ -517,3 +517,56 @@ def test_layout_is_stems_times_the_one_mask_layout():
                 assert mask_offs.tolist() == (s * one).tolist(), (wl, s)
                 assert out_offs.tolist() == np.concatenate([[0], np.cumsum((s + int(rest)) * lengths)]).tolist(), (wl, s, rest)
     assert one[3] - one[2] == wl // 2 + 1   # a clip of length 0: one frame
+
+
+# ------------------------------------------------------------------------------------------------------------------ 10
+def touched(n, h, frames):
+    """The samples of a clip of n that frames `frames` reach, partners included: frames 2j and 2j + 1 share a transform, frame t covers
+    samples (t - 1) H .. (t + 1) H - 1."""
+    hit = np.zeros(n, bool)
+    for t in frames:
+        for u in (t, t ^ 1):
+            hit[max((u - 1) * h, 0):min((u + 1) * h, n)] = True
+    return hit
+
+
+@pytest.mark.parametrize("wl", [256, 2048])
+def test_containment(wl):
+    """Three stems and the rest over a ragged batch.  A NaN sample in one clip and a NaN in the mask of its stem 0: every other clip has the bits
+    of its run alone and of the clean batch; inside that clip only the samples of the frames that hold the NaN sample or mask value, and of
+    the frames paired with them, may be non-finite, in any stem or the rest.  Then a NaN, and +inf, in the mask of stem 1 alone -- the stems
+    share one forward transform --: stems 0 and 2 keep the clean bits everywhere, stem 1 and the rest are non-finite only in the samples of
+    that frame and of its partner."""
+    h = wl // 2
+    n = 20 * h + 9
+    clips, masks = batch_of(wl, [7 * h + 3, 0, n, 1, n], n_stems=3, seed=80)
+    plan = plan_of(wl, True)
+    at, s, (k, t) = 2, 5 * h + 17, (h // 3, 13)   # sample s lies in frames 5 and 6; the mask value in frame 13
+    others = [i for i in range(len(clips)) if i != at]
+    clean = results(*run_ragged(plan, clips, masks)[:3], 4)
+
+    def rerun(sample, stem, value):
+        bad_clips, bad_masks = [c.copy() for c in clips], [m.copy() for m in masks]
+        if sample:
+            bad_clips[at][s] = np.nan
+        bad_masks[at][stem, t, k] = value
+        got = results(*run_ragged(plan, bad_clips, bad_masks)[:3], 4)
+        for i in others:
+            assert np.array_equal(bits(got[i]), bits(clean[i])), (wl, stem, i)
+        return got
+
+    got = rerun(True, 0, np.nan)
+    assert_equal_alone([got[i] for i in others], [clips[i] for i in others], [masks[i] for i in others], wl, True, what="containment")
+    may = touched(n, h, [s // h, s // h + 1, t])
+    assert 0 < may.sum() < n
+    for j in range(4):
+        assert not np.isfinite(got[at][j][may]).all() and np.isfinite(got[at][j][~may]).all(), (wl, j)
+        assert np.array_equal(bits(got[at][j][~may]), bits(clean[at][j][~may])), (wl, j)
+    may = touched(n, h, [t])
+    for value in (np.nan, np.inf):
+        got = rerun(False, 1, value)
+        for j in (0, 2):
+            assert np.array_equal(bits(got[at][j]), bits(clean[at][j])), (wl, value, "stem", j)
+        for j in (1, 3):
+            assert not np.isfinite(got[at][j][may]).all() and np.isfinite(got[at][j][~may]).all(), (wl, value, j)
+            assert np.array_equal(bits(got[at][j][~may]), bits(clean[at][j][~may])), (wl, value, j)

@@ -23,6 +23,12 @@ Two bounds per output, both written here:
     bin (7e-9).  Silence has floor 0: every output must be exactly zero, and the MFCCs of silence, DCT(log(eps)) (zaf.py:444-446), may
     differ from the reference's 1e-14 by the rounding of a float32 dot product over 128 equal levels.
 
+  * the fused mask filters (test_signal_through_the_mask_filters; tests/maskfilter_cases.py): mask_error <= 1e-5 and, per hop of H samples,
+    |y - ref| <= 10 tol max_hop|ref| + 2 eps32 max(max|ref|, max|x|) -- the level with the input's peak, as mask_error takes it; silence and
+    masks of zeros exact.  Two frames ride in one transform, so a quiet frame paired with a loud one inherits its rounding ("loud_quiet").
+    Measured on MI355X: worst hop 0.20 of its bound (dc, sparse mask, W = 2048), loud_quiet 0.099 (the unpacked float32 chain: 0.003), worst
+    normwise 5.2e-7.
+
 Kernel forms.  The STFT / ISTFT / MDCT / IMDCT checks run in both row padding modes: "compact" (fixture `zafx`) keeps the reference's memory
 order, so a frame count off the 128-byte line grid (T = 4, 71) runs the kernels' off-grid forms (k_stft_ft16c, the carry k_mdct_ft32, ...);
 "auto" (fixture `zafx_padded`, the *_padded twin of each test), the *_batch default and the drop-ins' path, pads such rows to whole lines and
@@ -722,3 +728,59 @@ def test_signals_in_one_ragged_imdct_batch(zafx_lib, wl):
         bound = TOL_ROUND_TRIP * (10.0 ** (-90.0 / 20.0) if name == "noise_m90" else 1.0)   # (the one signal far below unit level: held to its own)
         _report[f"k_imdct_ragged.{name}_{n}_{wl}.round_trip"] = {"max_abs": err, "bound": bound}
         assert err <= bound, (name, n, err, bound)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the fused mask filters
+def maskfilter_rows(tag, res, case, h):
+    """Every stem and the rest of every clip: mask_error <= TOL_FFT and the per-hop bound of tests/maskfilter_cases.hop_share, whose level takes
+    max|x| as mask_error's does.  The figures go into the report before they are asserted."""
+    import maskfilter_cases as mc
+    for i, (r, ref, x) in enumerate(zip(res, case["refs"], case["clips"])):
+        assert r.shape == ref.shape and np.isfinite(r).all(), (tag, i)
+        for j in range(len(r)):
+            g, share = mc.mask_error(r[j], ref[j], x), mc.hop_share(r[j], ref[j], x, h)
+            _report[f"maskfilter/{tag}.clip{i}.row{j}"] = {"normwise": g, "hop_share": share, "peak": float(np.abs(ref[j]).max())}
+            assert g <= TOL_FFT, (tag, i, j, "normwise", g)
+            assert share <= 1.0, (tag, i, j, "hop bound", share)
+        if not np.any(x):
+            assert not np.any(r), (tag, i, "silence must give exact zeros, the rest included")
+
+
+@pytest.mark.parametrize("name", sig.NAMES + ("loud_quiet",))
+@pytest.mark.parametrize("wl", [2048, 256])
+def test_signal_through_the_mask_filters(zafx_lib, wl, name):
+    """k_maskfilter ("TF" and "FT" compact), k_maskfilter_stems (S = 2: "uniform" and "sparse"), k_maskfilter_complex ("disc") and the ragged twin
+    of each, the rest on, on a clip of 20 H + 9 samples of every signal and on "loud_quiet" -- unit noise in front of noise at -90 dB, where the
+    frame pair across the step rides in ONE transform and the quiet frame inherits the loud one's rounding.  Bounds: mask_error <= TOL_FFT and,
+    per hop of H samples, |y - ref| <= 10 TOL_FFT max_hop|ref| + C_FLOOR eps32 max(max|ref|, max|x|) (tests/test_accuracy_host.py holds the
+    unpacked float32 chain to half of it on the same inputs); silence gives exact zeros.  The ragged launch gives the full-length clips the
+    bits of the equal-length one."""
+    import maskfilter_cases as mc
+    import maskfilter_run as mr
+    assert name in mc.SIGNAL_NAMES and wl in mc.SIGNAL_WINDOWS and mc.C_FLOOR == C_FLOOR and mc.TOL_FFT == TOL_FFT
+    case = mc.signal_case(name, wl)
+    for form in mc.SIGNAL_FORMS:
+        c = case[mc.family_of(form)]
+        same = {k: [c[k][i] for i in c["equal"]] for k in ("clips", "masks", "refs")}
+        got = mr.run(form, case["w"], same["clips"], same["masks"], True, ragged=False)
+        rag = mr.run(form, case["w"], c["clips"], c["masks"], True, ragged=True)
+        for k, i in enumerate(c["equal"]):
+            assert np.array_equal(mr.bits(rag[i]), mr.bits(got[k])), (name, wl, form, "ragged clip", i)
+        maskfilter_rows(f"{form}.{name}_{wl}", got, same, wl // 2)
+        maskfilter_rows(f"{form}_ragged.{name}_{wl}", rag, c, wl // 2)
+
+
+@pytest.mark.parametrize("wl", [2048, 256])
+def test_stems_of_zero_masks(zafx_lib, wl):
+    """Masks of zeros in every stem: every stem is exact zeros and the rest has the bits of x -- equal-length and ragged (the one-mask kinds:
+    tests/test_gpu_maskfilter.py::test_zeros, tests/test_gpu_maskfilter_complex.py::test_fixed_values)."""
+    import maskfilter_cases as mc
+    import maskfilter_run as mr
+    h = wl // 2
+    w = mc.window_of("hamming", wl)
+    clips = [mc.clip(k, n) for k, n in enumerate((20 * h + 9, 7 * h + 3, 20 * h + 9))]
+    masks = [np.zeros((mc.N_STEMS, h + 1, mc.mask_frames(len(x), wl)), np.float32) for x in clips]
+    for res, xs in ((mr.run("stems", w, clips[::2], masks[::2], True, ragged=False), clips[::2]), (mr.run("stems", w, clips, masks, True, ragged=True), clips)):
+        for r, x in zip(res, xs):
+            assert r.shape == (mc.N_STEMS + 1, len(x)) and not r[:mc.N_STEMS].any(), (wl, len(x))
+            assert np.array_equal(mr.bits(r[mc.N_STEMS]), mr.bits(x)), (wl, len(x), "rest")

@@ -19,7 +19,13 @@ n % 4 != 0, k_stft_ft16's run-time-claim form by rows of whole lines (its static
 Shapes: the smallest that hold a whole tile and an edge tile of the form under test.  ISTFT and center leave out `random`, whose COLA sum
 zaf.istft divides by is 0.026 at W = 4096, hop W / 2 (tests/test_windows_host.py::test_cola_sums_of_the_istft_and_center_cases).
 
-Measured on MI355X, 2026-10-18 (242 tests, 3 s), worst normwise error per group (the test functions' first argument to held()) and window, over
+The six fused mask-filter kernels read the window itself, and their blind spot is the PERIODIC mirror: periodic Hamming, their other tests' only
+window, satisfies w[n] == w[(W - n) % W].  test_maskfilter runs every form of tests/maskfilter_cases.py under the (window, W) pairs of
+windows.MASKFILTER_WINDOWS -- skew and signed at W = 256 ... 2048, random at 512 and 2048, where its COLA sum, the kernels' `gain`, is negative.
+A library whose mask-filter kernels read window[(W - n) & (W - 1)] fails all ten cases on the MI355X and passes the 160 accuracy cases, the signal
+cases and the ragged, complex and ragged-stems modules, which run under Hamming.
+
+Measured on MI355X, 2026-10-18 (242 tests, 3 s; the maskfilter row 2026-10-21), worst normwise error per group (the test functions' first argument to held()) and window, over
 every form and row padding mode of the group -- f64: the float64 kernels of every group; set ZAFX_WINDOWS_REPORT=path to have a run write its own:
     mdct_2048     random 1.46e-07, signed 1.83e-07, skew 1.72e-07
     mdct_4096     random 1.94e-07, signed 1.63e-07, skew 1.80e-07
@@ -37,6 +43,7 @@ every form and row padding mode of the group -- f64: the float64 kernels of ever
     istft_ragged  signed 1.34e-07, skew 1.48e-07
     center        skew 4.22e-07, worst hop 0.0045 of its bound
     cache         skew 2.17e-07
+    maskfilter    random 1.82e-07, signed 2.15e-07, skew 3.38e-07   (mask_error; the six fused kernels, every form: test_maskfilter)
 Every float32 transform sits at 1.3e-7 ... 3.0e-7 -- where the same kernels sit under Hamming and KBD (tests/test_gpu_signals.py) -- and no form
 was found with a mirrored tap.  That the module would see one: a library whose fold table has components 0 and 3 swapped (2m < W/4) passes the
 MDCT tests of test_gpu_signals.py, test_gpu_mdct_ragged.py and test_gpu_pcm_ragged.py (KBD) on the MI355X and fails 57 of these (test_mdct_2048, _frame_major_and_row_align, test_mdct_4096, the W = 512 /
@@ -577,6 +584,44 @@ def test_center(zafx, wl, n, signal):
         f = assert_center_contract(f"k_center_ragged.skew.{signal}_{wl}_{k}", ck, sk, xk, oracle_center(xk, w), wl // 2)
         _report["center.skew"] = max(_report["center.skew"], f["normwise"])
         _report["center.skew.hop"] = max(_report["center.skew.hop"], f["hop"])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the fused mask filters
+@pytest.mark.parametrize("name,wl", win.MASKFILTER_WINDOWS)
+def test_maskfilter(zafx, name, wl):
+    """The six fused mask-filter kernels under a window that is not its own periodic mirror (periodic Hamming is: a window read at
+    (W - n) % W passes every other mask-filter test) and, where `random` runs, under a negative COLA gain.  Three clips of 20 H + 9 samples,
+    "unit" / "disc" masks, the rest on: every form of tests/maskfilter_cases.py through its equal-length launch and -- with clips of 1, H,
+    3 H + 7 and 0 samples between the same three -- through its ragged one, every stem and the rest within TOL_FFT (mask_error) of the float64
+    oracle; the ragged launch gives the shared clips the bits of the equal-length one, and each stem has the bits of the one-mask kind."""
+    import maskfilter_cases as mc
+    import maskfilter_run as mr
+    assert (wl, wl // 2) in win.MASKFILTER_GEOMETRIES
+    n = 20 * (wl // 2) + 9
+    worst = 0.0
+    for form in mc.FORMS:
+        family = mc.family_of(form)
+        b = mc.batch(family, wl, n, name, "unit")
+        twin, where = mc.ragged_twin(b, mc.extras(family, wl, name))
+        got = mr.run(form, b["w"], b["clips"], b["masks"], True, ragged=False)
+        rag = mr.run(form, twin["w"], twin["clips"], twin["masks"], True, ragged=True)
+        for k, i in enumerate(where):
+            assert np.array_equal(mr.bits(rag[i]), mr.bits(got[k])), (name, wl, form, "ragged clip", i)
+        for res, case in ((got, b), (rag, twin)):
+            for r, ref, x in zip(res, case["refs"], case["clips"]):
+                assert r.shape == ref.shape and np.isfinite(r).all(), (name, wl, form, len(x))
+                for j in range(len(r)):
+                    err = mc.mask_error(r[j], ref[j], x)
+                    worst = max(worst, err)
+                    assert err <= TOL_FFT, (name, wl, form, len(x), j, err)
+        if form == "stems":   # stem s of clip k against the one-mask kind ("TF") under mask s alone
+            for s in range(mc.N_STEMS):
+                one = mr.run("tf", b["w"], b["clips"], [m[s] for m in b["masks"]], False, ragged=False)
+                for k in range(len(one)):
+                    assert np.array_equal(mr.bits(got[k][s]), mr.bits(one[k][0])), (name, wl, "stem", s, "clip", k)
+    key = f"maskfilter.{name}"
+    _report[key] = max(_report.get(key, 0.0), worst)
+    print(f"maskfilter {name} W={wl}: {worst:.3e}")
 
 
 # ------------------------------------------------------------------------------------------------------------------ the plan cache

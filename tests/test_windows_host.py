@@ -136,6 +136,50 @@ def test_cola_sums_of_the_istft_and_center_cases():
     assert abs(win.cola_gain(win.random(4096), 2048)) < win.MIN_COLA
 
 
+# ---------------------------------------------------------------------------------------------------------------- the mask filter's windows
+COLA_TABLE = {"skew": (0.949, 0.925, 0.908, 0.898), "signed": (0.529, 0.536, 0.540, 0.543), "random": (-0.195, -0.438, 0.024, -0.374)}
+
+
+def test_cola_sums_of_the_mask_filter_cases():
+    """The table of tests/windows.py: skew and signed are used at all four lengths, random at W = 512 and 2048 -- at two lengths at least, and
+    with a NEGATIVE sum there, which the kernels are handed as `gain`.  A recipe that silently dropped out of the GPU module fails here."""
+    lengths = [wl for wl, _ in win.MASKFILTER_GEOMETRIES]
+    assert lengths == [256, 512, 1024, 2048] and all(hop == wl // 2 for wl, hop in win.MASKFILTER_GEOMETRIES)
+    for name, row in COLA_TABLE.items():
+        for (wl, hop), want in zip(win.MASKFILTER_GEOMETRIES, row):
+            g = win.cola_gain(win.window(name, wl), hop)
+            assert abs(g - want) < 5e-4, (name, wl, g, want)
+            assert ((name, wl) in win.MASKFILTER_WINDOWS) == (abs(g) >= win.MIN_COLA), (name, wl, g)
+    used = {name: [wl for n, wl in win.MASKFILTER_WINDOWS if n == name] for name in win.NAMES}
+    assert used["skew"] == lengths and used["signed"] == lengths and used["random"] == [512, 2048], used
+    assert len(used["random"]) >= 2 and all(win.cola_gain(win.random(wl), wl // 2) < -win.MIN_COLA for wl in used["random"])
+    assert len(win.MASKFILTER_WINDOWS) == 10
+
+
+def _periodic_mirror(w):
+    return w[(len(w) - np.arange(len(w))) % len(w)]
+
+
+@pytest.mark.parametrize("name,wl", win.MASKFILTER_WINDOWS)
+def test_a_mirrored_window_moves_the_mask_filter(name, wl):
+    """The oracle's mask filter, real and complex masks, under w[::-1] and under the periodic mirror w[(W - n) % W] moves by at least 5 % for
+    every (window, W) the GPU module uses; under periodic Hamming the periodic mirror moves it by at most 1e-12 -- the blind spot of every
+    mask-filter test before tests/test_gpu_windows.py's, asserted so that it stays documented."""
+    import maskfilter_cases as mc
+    h = wl // 2
+    n = 20 * h + 9
+    x = mc.clip(0, n).astype(np.float64)
+    filters = {"real": lambda v: mc.oracle_maskfilter(x, v, mc.masks_for("real", wl, n, 0, "unit")),
+               "complex": lambda v: mc.oracle_maskfilter_complex(x, v, mc.masks_for("complex", wl, n, 0, None))}
+    w, ham = win.window(name, wl), mc.window_of("hamming", wl)
+    for kind, fn in filters.items():
+        full, periodic = relerr(fn(w[::-1]), fn(w)), relerr(fn(_periodic_mirror(w)), fn(w))
+        blind = relerr(fn(_periodic_mirror(ham)), fn(ham))
+        print(f"W={wl} {name} {kind}: mirrored {full:.3f}, periodic mirror {periodic:.3f}; periodic mirror under Hamming {blind:.1e}")
+        assert full >= 0.05 and periodic >= 0.05, (name, wl, kind, full, periodic)
+        assert blind <= 1e-12, (wl, kind, blind)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the tolerance yardstick
 def mdct_in_float32(x, w):
     """The reference MDCT (zaf.py:1025-1075, as oracle.zaf_oracle.mdct restates it) in float32: scipy.fft on complex64, the same twiddles."""

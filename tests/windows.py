@@ -69,3 +69,11 @@ ISTFT_GEOMETRIES = ((2048, 1024), (2048, 512), (4096, 2048), (4096, 1024), (8192
 CENTER_WINDOWS = ("skew",)
 CENTER_GEOMETRIES = ((2048, 1024), (256, 128))
 MIN_COLA = 0.25
+
+# The fused mask-filter kernels (hop W / 2 only).  Periodic Hamming, their tests' only window so far, satisfies w[n] == w[(W - n) % W]: a window
+# read at that periodic mirror -- one `& (W - 1)` away from the bin pairing kn = (W - k) & (W - 1) the kernels compute -- is invisible under it.
+# A recipe is used at a length only where zaf.istft can divide by its COLA sum: skew 0.949 / 0.925 / 0.908 / 0.898 and signed 0.529 / 0.536 /
+# 0.540 / 0.543 at W = 256 / 512 / 1024 / 2048 everywhere, random -0.195 / -0.438 / 0.024 / -0.374 at W = 512 and 2048 -- where its sum is
+# NEGATIVE, a gain these kernels had never been handed (tests/test_windows_host.py::test_cola_sums_of_the_mask_filter_cases).
+MASKFILTER_GEOMETRIES = ((256, 128), (512, 256), (1024, 512), (2048, 1024))
+MASKFILTER_WINDOWS = tuple((name, wl) for wl, hop in MASKFILTER_GEOMETRIES for name in NAMES if abs(cola_gain(window(name, wl), hop)) >= MIN_COLA)
