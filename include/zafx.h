@@ -38,6 +38,9 @@
  *   ZAFX_MASKFILTER / _REST with   the same with a COMPLEX mask, extended to its Hermitian mirror:
  *   zafx_execute_masked_complex    np.concatenate((M, np.conj(M[-2:0:-1]))) * audio_stft, istft :194-195 (the real part, :223); complex64
  *                                  masks in ZAFX_LAYOUT_TF; clips of different lengths in one launch: zafx_execute_masked_complex_ragged
+ *   ZAFX_MASKFILTER / _REST with   the same for an interleaved stereo clip (N, 2), as the example has it: one real mask for both channels
+ *   zafx_execute_masked_stereo     or one per channel, masks in ZAFX_LAYOUT_TF; clips of different lengths in one launch:
+ *                                  zafx_execute_masked_stereo_ragged, zafx_plan_stereo_ragged_layout
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -265,6 +268,8 @@ int zafx_plan_row_pitch(const zafx_plan* plan, int64_t n_in, int64_t* pitch);
  *   ZAFX_CENTER / ZAFX_CENTER_SIDES           n_in >= 2^28 sample frames (1.7 h at 44.1 kHz)
  *   ZAFX_MASKFILTER / ZAFX_MASKFILTER_REST    n_in >= 2^28 samples (zafx_execute_masked; zafx_execute_masked_ragged, zafx_execute_masked_stems_ragged: any clip of the batch)
  *                                             complex masks: n_in >= 2^27 samples (zafx_execute_masked_complex; zafx_execute_masked_complex_ragged: any clip of the batch)
+ *                                             stereo clips: n_in >= 2^28 sample frames, 2^27 with a mask per channel (zafx_execute_masked_stereo;
+ *                                             zafx_execute_masked_stereo_ragged: any clip of the batch)
  * zafx_execute_pcm reads int16 in the kernels' own loads below the same lengths (n_frames < 2^29; the MDCT: < 2^28) and converts first above them.
  * Not run at its bound by any test yet: the two-sided complex STFT at window 8192 (k_stft_ft16q takes whole-line rows only; its |X| kind is run).
  * The ragged and PCM entry points state their own per-clip limits below. */
@@ -379,6 +384,49 @@ int zafx_plan_stems_ragged_layout(const zafx_plan* plan, const int64_t* lengths,
  * applies as it does to zafx_execute_masked_ragged (measurements only). */
 int zafx_execute_masked_stems_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                      const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems);
+/* The mask filter for INTERLEAVED STEREO clips under masks of the caller's, enqueued on the plan's stream (asynchronous; ZAFX_MASKFILTER and
+ * ZAFX_MASKFILTER_REST plans created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_stereo"):
+ *     y[:, c] = istft(concat(m_c, m_c[-2:0:-1]) * stft(x[:, c], w, H), w, H)[0:n_in],  c = L, R        (zaf.py:176-198 with the caller's masks)
+ * mask_channels == 1: one mask for both channels, m_L = m_R; mask_channels == 2: one per channel.  d_in (B, n_in, 2) float32, n_in counted in
+ * sample frames; d_mask float32 compact, (B, frames, rows) for mask_channels == 1 and (B, frames, 2, rows) for 2 -- a frame's L row lies
+ * directly in front of its R row --, rows x frames = zafx_plan_mask_dims; d_out (B, n_in, 2), under ZAFX_MASKFILTER_REST (B, 2, n_in, 2) with
+ * block 1 = input - block 0 in float32, bit-equal to the subtraction of the block 0 that was written (the layout of ZAFX_CENTER_SIDES).  The
+ * arrays need 4-byte alignment only.  CONTRACT: the two channels of a frame share one transform, so rounding (a quiet channel beside a loud
+ * one carries about eps32 of the loud level) and a non-finite sample or mask value of one channel reach the other channel of the same frames
+ * -- output blocks j - 1 and j for frame j -- and never another frame pair or another clip; nothing is read in front of a clip's sample
+ * frame 0, from its sample frame n_in on or behind a mask's last frame, nothing is written at or beyond n_in; a clip has the same bits alone,
+ * anywhere in a batch, however it is cut and under any ZAFX_COMPUTE_UNITS; a mask of zeros gives exact zeros, and so does silence on both
+ * channels under any finite mask.  NOT promised: that two equal per-channel masks give the bits of the shared form (that one scales the
+ * packed spectrum without splitting it), nor that a channel has the bits zafx_execute_masked gives it as a mono clip (the packing differs);
+ * all agree within the accuracy of either.  Rejected with a message, nothing enqueued or written: a null plan or pointer, negative sizes,
+ * another kind, a plan in ZAFX_LAYOUT_FT (the message names ZAFX_LAYOUT_TF), mask_channels outside {1, 2}, a window that is not set or whose
+ * sum(window[0:W:H]) is zero, clips of 2^28 sample frames and more (8 bytes a sample frame behind one descriptor) -- 2^27 with
+ * mask_channels == 2 (two masks per frame are 8 bytes a bin, the complex kind's arithmetic).  The other entry points on the same plan are
+ * not affected. */
+int zafx_execute_masked_stereo(zafx_plan* plan, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in,
+                               int32_t mask_channels);
+/* Placement of a ragged stereo batch (ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans of ZAFX_LAYOUT_TF, mask_channels 1 or 2), both arrays
+ * of n_clips + 1 entries: the masks of clip i, (T_i, mask_channels, W/2 + 1), start at float32 element mask_offsets[i] of the mask array, the
+ * clips back to back -- mask_channels x what zafx_plan_mask_ragged_layout gives --; its output block of lengths[i] sample frames, under
+ * ZAFX_MASKFILTER_REST two of them, starts at SAMPLE FRAME out_offsets[i], the blocks back to back.  Entry n_clips of either array is the
+ * total.  A clip of length 0 has T = 1 (its masks are never read) and an empty output block. */
+int zafx_plan_stereo_ragged_layout(const zafx_plan* plan, const int64_t* lengths, int64_t n_clips, int32_t mask_channels, int64_t* mask_offsets,
+                                   int64_t* out_offsets);
+/* zafx_execute_masked_stereo for n_clips stereo clips of different lengths in ONE launch (ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans
+ * created with ZAFX_LAYOUT_TF only; last kernel "k_maskfilter_stereo_ragged").  in_offsets, lengths and out_offsets count SAMPLE FRAMES, as in
+ * zafx_execute_center_ragged: clip i is lengths[i] sample frames at sample frame in_offsets[i] of d_in, its output block starts at sample
+ * frame out_offsets[i] of d_out and, under ZAFX_MASKFILTER_REST, the rest follows at out_offsets[i] + lengths[i].  mask_offsets counts float32
+ * elements: the masks of clip i, (T_i, mask_channels, W/2 + 1) compact, start at element mask_offsets[i] of d_mask.  Any placement will do
+ * (zafx_plan_stereo_ragged_layout gives the compact one); the arrays need 4-byte alignment only.  CONTRACT: clip i's block is bit-identical
+ * to zafx_execute_masked_stereo on that clip and its masks alone, whatever the batch, its cut and ZAFX_COMPUTE_UNITS; no clip sees another's
+ * samples or masks.  A clip of length 0 is skipped, an empty batch is fine.  The four host arrays are copied before return.  Rejected with a
+ * message, nothing enqueued or written: a null plan, pointer or host array, a negative count, another kind, a plan in ZAFX_LAYOUT_FT,
+ * mask_channels outside {1, 2}, negative lengths or offsets (with the clip's index), a clip of 2^28 sample frames or more, 2^27 with
+ * mask_channels == 2 (with its index; decided on `lengths` before anything is read), a window that is not set or whose COLA sum is zero.
+ * NOT checked: that the output blocks do not overlap.  ZAFX_CENTER_UNITS_PER_SLOT in the environment applies as it does to
+ * zafx_execute_center_ragged (measurements only). */
+int zafx_execute_masked_stereo_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                      const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t mask_channels);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
  * with_mel included, _CQT, _CHROMA; float32 and float64).

@@ -1528,6 +1528,19 @@ int zafx_execute_masked_complex(zafx_plan* pl, const void* d_in, const void* d_m
     return launch_rc(fn, zafx::launch_maskfilter_complex(*pl, (const float*)d_in, (const float2*)d_mask, (float*)d_out, n_clips, n_in));
 }
 
+// Interleaved stereo clips (B, N, 2) under one mask for both channels (B, T, W/2+1) or one per channel (B, T, 2, W/2+1) on k_maskfilter_stereo:
+// TF plans, mask_channels 1 or 2, clips below 2^28 / 2^27 sample frames (maskfilter_stereo_refusal), refused for an empty batch too.
+int zafx_execute_masked_stereo(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t mask_channels) {
+    const char* const fn = "zafx_execute_masked_stereo";
+    if (int rc = masked_plan_checks(fn, pl, "", n_clips, n_in)) return rc;
+    zafx::RouteCall c;
+    c.kind = pl->kind, c.layout = pl->layout, c.n = n_in;
+    if (const char* why = zafx::maskfilter_stereo_refusal(c, mask_channels)) return fail_msg(std::string(fn) + ": " + why);
+    if (n_clips == 0) return 0;
+    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
+    return launch_rc(fn, zafx::launch_maskfilter_stereo(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in, mask_channels));
+}
+
 int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in) {
     if (!pl) return fail_msg("null plan");
     if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("zafx_execute: ") + kMaskedOnly);
@@ -1936,6 +1949,53 @@ int zafx_execute_masked_stems_ragged(zafx_plan* pl, const void* d_in, const int6
     if (const char* why = zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, lengths, n_clips, &clip))
         return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
     return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, n_stems);
+}
+
+// Stereo clips of a ragged batch: a clip's mask(s) are mask_channels x a TF plan's mask_block, its output one block of sample frames, two with
+// the rest (out_offsets count sample frames)
+int zafx_plan_stereo_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t mask_channels, int64_t* mask_offsets, int64_t* out_offsets) {
+    const char* const fn = "zafx_plan_stereo_ragged_layout";
+    if (!pl || !mask_offsets || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
+    if (n_clips < 0) return fail_msg("negative size");
+    int64_t clip = -1;
+    if (const char* why = zafx::maskfilter_stereo_ragged_refusal(pl->kind, pl->layout, mask_channels, nullptr, 0, &clip)) return fail_msg(std::string(fn) + ": " + why);
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] < 0) return fail_msg(std::string(fn) + ": negative length of clip " + std::to_string(i));
+    const int64_t blocks = pl->kind == ZAFX_MASKFILTER_REST ? 2 : 1;
+    mask_offsets[0] = out_offsets[0] = 0;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        int64_t elems = 0, pitch = 0;
+        mask_block(pl, lengths[i], &elems, &pitch);
+        mask_offsets[i + 1] = mask_offsets[i] + mask_channels * elems;
+        out_offsets[i + 1] = out_offsets[i] + blocks * lengths[i];
+    }
+    return 0;
+}
+
+// Ragged stereo batches under the caller's masks: the kind, the layout, mask_channels (refused for an empty batch too) and every clip's length
+// are decided on the host arrays before anything else is read (maskfilter_stereo_ragged_refusal); the units are k_center's blocks in
+// MaskfilterUnit records (maskfilter_stereo_cut_units), k_maskfilter_stereo's RAGGED form walks them.
+int zafx_execute_masked_stereo_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                      const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t mask_channels) {
+    const char* const fn = "zafx_execute_masked_stereo_ragged";
+    int64_t clip = -1;
+    const char* wrong_kind = pl ? zafx::maskfilter_stereo_ragged_refusal(pl->kind, pl->layout, mask_channels, nullptr, 0, &clip) : nullptr;
+    bool empty = false;
+    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    if (const char* why = zafx::maskfilter_stereo_ragged_refusal(pl->kind, pl->layout, mask_channels, lengths, n_clips, &clip))
+        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
+    if (int rc = check_window_gain(pl, "mask filter")) return rc;
+    int tile_frames = 0;
+    long long slots = 0;
+    if (!zafx::maskfilter_stereo_launch_shape(*pl, &tile_frames, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
+    // ZAFX_CENTER_UNITS_PER_SLOT in the environment, as for zafx_execute_center_ragged: the cut is that one's (measurements only)
+    const int per_slot = env_units_per_slot("ZAFX_CENTER_UNITS_PER_SLOT", zafx::kCenterUnitsPerSlot);
+    const std::vector<zafx::MaskfilterUnit> units = zafx::maskfilter_stereo_cut_units(lengths, in_offsets, out_offsets, mask_offsets, n_clips, pl->W, tile_frames, slots, per_slot);
+    ZAFX_HIP(hipSetDevice(pl->device));
+    if (int rc = upload_records(pl, units)) return rc;
+    return launch_rc(fn, zafx::launch_maskfilter_stereo_ragged(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out,
+                                                               static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size(), mask_channels));
 }
 
 // What zafx_execute_imdct_ragged and zafx_execute_istft_ragged differ in: both cut their blocks into units of tiles (zafx_units.hpp) that the

@@ -387,6 +387,13 @@ hipError_t launch_maskfilter_ragged(const zafx_plan& pl, const float* x, const f
 // RAGGED: the units and the launch shape are k_maskfilter's TF ones, a unit's mask_off counts complex64 elements
 hipError_t launch_maskfilter_complex(const zafx_plan& pl, const float* x, const float2* mask, float* out, int64_t n_clips, int64_t n_samples);
 hipError_t launch_maskfilter_complex_ragged(const zafx_plan& pl, const float* x, const float2* mask, float* out, const MaskfilterUnit* d_units, long long n_units);
+// zafx_maskfilter_stereo.hip: zafx_execute_masked_stereo / _ragged: k_maskfilter_stereo on interleaved stereo clips (B, N, 2), float32 masks (B, T, W/2+1)
+// (mask_channels 1) or (B, T, 2, W/2+1) (2), TF plans only (maskfilter_stereo_refusal, zafx_routes.hpp).  RAGGED: the tile frames and slots
+// (k_center's) that maskfilter_stereo_cut_units takes; a unit's offsets and length count sample frames, its mask_off float32 elements
+hipError_t launch_maskfilter_stereo(const zafx_plan& pl, const float* x, const float* mask, float* out, int64_t n_clips, int64_t n_samples, int mask_channels);
+bool maskfilter_stereo_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
+hipError_t launch_maskfilter_stereo_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
+                                           int mask_channels);
 // zafx_execute_masked_stems_ragged: the same for k_maskfilter_stems -- the slots follow the stems' LDS size (false as well for a stem count
 // outside 1 .. 8) -- and the launch on a device table of unit records: a clip's n_stems masks back to back at mask_off, its n_stems (+ 1 with
 // rest) output blocks back to back at out_off

@@ -508,6 +508,50 @@ inline const char* maskfilter_complex_ragged_refusal(int kind, int layout, const
     }
     return nullptr;
 }
+// zafx_execute_masked_stereo: interleaved stereo clips under one real mask for both channels (mask_channels 1) or one per channel (2), masks
+// in ZAFX_LAYOUT_TF only (the kernel is k_center's walk: no FT stage in its LDS).  The samples lie behind one descriptor of 8 N bytes:
+// N < 2^28 sample frames; two masks per frame are 8 T (W/2 + 1) bytes -- the complex kind's arithmetic --: N < 2^27 then.  Reads kind,
+// layout and n.  nullptr: the call is taken.
+constexpr int64_t maskfilter_stereo_max_frames(int64_t mask_channels) { return mask_channels == 2 ? 1LL << 27 : 1LL << 28; }
+// bytes of the compact TF float32 mask(s) of a clip of n sample frames: T frames of mask_channels rows of W/2 + 1 bins
+constexpr int64_t maskfilter_stereo_mask_bytes(int64_t n, int W, int64_t mask_channels) { return ((n + W / 2 - 1) / (W / 2) + 1) * mask_channels * (W / 2 + 1) * 4; }
+static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 256, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 256, 2) < (1LL << 31),
+              "stereo mask filter, W = 256: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 512, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 512, 2) < (1LL << 31),
+              "stereo mask filter, W = 512: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 1024, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 1024, 2) < (1LL << 31),
+              "stereo mask filter, W = 1024: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 2048, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 2048, 2) < (1LL << 31),
+              "stereo mask filter, W = 2048: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+constexpr const char* kMaskfilterStereoKernel = "k_maskfilter_stereo";                 // zafx_execute_masked_stereo
+constexpr const char* kMaskfilterStereoRaggedKernel = "k_maskfilter_stereo_ragged";   // zafx_execute_masked_stereo_ragged
+inline bool maskfilter_stereo_clip_refused(const RouteCall& c, int64_t mask_channels) { return c.n >= maskfilter_stereo_max_frames(mask_channels); }
+inline const char* maskfilter_stereo_refusal(const RouteCall& c, int64_t mask_channels) {
+    if (c.kind != ZAFX_MASKFILTER && c.kind != ZAFX_MASKFILTER_REST) return "stereo mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only";
+    if (c.layout != ZAFX_LAYOUT_TF) return "stereo mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)";
+    if (mask_channels != 1 && mask_channels != 2) return "stereo mask filter: mask_channels must be 1 (one mask for both channels) or 2 (one per channel)";
+    if (maskfilter_stereo_clip_refused(c, mask_channels))
+        return mask_channels == 2 ? "stereo mask filter: with a mask per channel clips of 2^27 sample frames and more are not supported"
+                                  : "stereo mask filter: clips of 2^28 sample frames and more are not supported";
+    return nullptr;
+}
+// zafx_execute_masked_stereo_ragged: the kind, the layout and mask_channels as above, then every clip's length against the bound, before
+// anything is read.  nullptr: the call is taken; otherwise *clip is the index of the clip refused, or -1 where the refusal is none of a clip's.
+inline const char* maskfilter_stereo_ragged_refusal(int kind, int layout, int64_t mask_channels, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
+    *clip = -1;
+    RouteCall c;
+    c.kind = kind, c.layout = layout;
+    if (const char* why = maskfilter_stereo_refusal(c, mask_channels)) return why;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        c.n = lengths[i];
+        if (maskfilter_stereo_clip_refused(c, mask_channels)) {
+            *clip = i;
+            return mask_channels == 2 ? "stereo mask filter: with a mask per channel a clip has 2^27 sample frames or more (not supported)"
+                                      : "stereo mask filter: a clip has 2^28 sample frames or more (not supported)";
+        }
+    }
+    return nullptr;
+}
 
 // ---------------------------------------------------------------------------------
 // ragged batches: clips of different lengths in one call (zafx_execute_ragged, zafx_execute_ragged_pcm, zafx_execute_imdct_ragged,

@@ -148,6 +148,19 @@ inline std::vector<MaskfilterUnit> maskfilter_cut_units(const int64_t* lengths, 
     return units;
 }
 
+// ---- k_maskfilter_stereo (zafx_maskfilter_stereo.hip, zafx_execute_masked_stereo_ragged): k_center's pieces and rule -- blocks, the halo frame
+// in front of a unit that does not start its clip, floor 4 F - 3 -- in MaskfilterUnit records, which carry what k_center's lack: mask_off, the
+// first float32 element of the clip's mask(s).  Offsets and lengths of samples in sample frames; b0 is any block, mask_pitch is not used.
+inline std::vector<MaskfilterUnit> maskfilter_stereo_cut_units(const int64_t* lengths, const int64_t* in_offsets, const int64_t* out_offsets, const int64_t* mask_offsets,
+                                                               int64_t n_clips, int W, int F, long long slots, int per_slot = kCenterUnitsPerSlot) {
+    const auto counts = piece_counts(lengths, n_clips, [W](long long n) { return center_blocks(n, W); });
+    std::vector<MaskfilterUnit> units;
+    for (const Segment& s : cut_segments(counts.data(), n_clips, 4LL * F - 3, slots, per_slot))
+        units.push_back({in_offsets ? (long long)in_offsets[s.clip] : 0LL, (long long)lengths[s.clip], out_offsets ? (long long)out_offsets[s.clip] : 0LL,
+                         mask_offsets ? (long long)mask_offsets[s.clip] : 0LL, (int)s.a, (int)s.b, 0, 0});
+    return units;
+}
+
 // ---- k_center, k_maskfilter and k_maskfilter_stems on equal-length batches: every clip has the same n_blocks > 0, cut into `segs` segments of
 // `seg_blocks` blocks (the last one shorter, never empty); unit u = clip * segs + seg.  Whole clips when there are enough of them to load
 // every workgroup slot (n_clips >= slots); otherwise about two units per slot.

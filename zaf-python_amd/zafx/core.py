@@ -478,6 +478,83 @@ class Plan:
                            ok and (lambda: (self.mask_shape(n_clips, n_in), self.out_shape(n_clips, n_in))), mask_dtype=np.complex64)
         _lib.check(_lib.load().zafx_execute_masked_complex(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked_complex")
 
+    def stereo_mask_shape(self, n_clips, n_in, mask_channels):
+        """Shape of the float32 device array execute_masked_stereo() reads its masks from, compact: (clips, frames, W/2 + 1) for one mask for
+        both channels (mask_channels 1), (clips, frames, 2, W/2 + 1) for one per channel (2) -- a frame's L row directly in front of its R row."""
+        rows, frames = self.mask_dims(n_in)
+        return (int(n_clips), frames, rows) if int(mask_channels) == 1 else (int(n_clips), frames, int(mask_channels), rows)
+
+    def stereo_out_shape(self, n_clips, n_in):
+        """Shape of execute_masked_stereo()'s output: (clips, n_in, 2), or (clips, 2, n_in, 2) under a MASKFILTER_REST plan, whose block 1 of a
+        clip is the rest (the layout of a CENTER_SIDES plan)."""
+        return (int(n_clips), 2, int(n_in), 2) if self.kind == _lib.MASKFILTER_REST else (int(n_clips), int(n_in), 2)
+
+    def execute_masked_stereo(self, d_in, d_mask, d_out, n_clips, n_in, mask_channels):
+        """Enqueue the mask filter of interleaved stereo clips on the plan's stream (asynchronous; zafx_execute_masked_stereo, mask filter plans
+        of layout "TF" only; last_kernel: k_maskfilter_stereo): d_in (clips, n_in, 2) float32 sample frames, d_mask float32 of
+        stereo_mask_shape(n_clips, n_in, mask_channels), d_out of stereo_out_shape(n_clips, n_in).  mask_channels 1: one mask for both
+        channels; 2: one per channel.  Buffers of another dtype or of the wrong size raise ValueError before anything is enqueued."""
+        n_clips, n_in, mask_channels = int(n_clips), int(n_in), int(mask_channels)
+        if d_in.dtype != np.float32 or d_mask.dtype != np.float32 or d_out.dtype != np.float32:
+            raise ValueError("execute_masked_stereo takes float32 sample frames, float32 masks and a float32 output buffer")
+        if n_clips < 0 or n_in < 0:
+            raise ValueError("n_clips and n_in must not be negative")
+        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and mask_channels in (1, 2):   # (otherwise: the library says so)
+            mask_shape, out_shape = self.stereo_mask_shape(n_clips, n_in, mask_channels), self.stereo_out_shape(n_clips, n_in)
+            if d_in.nbytes < n_clips * n_in * 8:
+                raise ValueError("d_in holds fewer than clips x n_in sample frames")
+            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * 4:
+                raise ValueError(f"d_mask must hold stereo_mask_shape(n_clips, n_in, mask_channels) = {mask_shape} float32, got {d_mask.nbytes} bytes")
+            if d_out.nbytes < int(np.prod(out_shape, dtype=np.int64)) * 4:
+                raise ValueError("d_out is smaller than the plan's output for these clips")
+        _lib.check(_lib.load().zafx_execute_masked_stereo(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, mask_channels), "zafx_execute_masked_stereo")
+
+    def stereo_ragged_layout(self, lengths, mask_channels):
+        """Placement of a ragged stereo mask-filter batch (zafx_plan_stereo_ragged_layout, mask filter plans of layout "TF") for clips of `lengths`
+        sample frames: -> (mask_offsets, out_offsets), int64 of len(lengths) + 1.  Clip i's masks, (T_i, mask_channels, W/2 + 1), start at
+        float32 element mask_offsets[i] -- mask_channels x what mask_ragged_layout gives --, its output block, N_i sample frames or with rest
+        two such, starts at SAMPLE FRAME out_offsets[i]; the last entries are the totals."""
+        lengths = _as_lengths(lengths)
+        mask_offs, out_offs = np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths) + 1, np.int64)
+        _lib.check(_lib.load().zafx_plan_stereo_ragged_layout(self.handle, _i64p(lengths), len(lengths), int(mask_channels), _i64p(mask_offs), _i64p(out_offs)),
+                   "zafx_plan_stereo_ragged_layout")
+        return mask_offs, out_offs
+
+    def execute_masked_stereo_ragged(self, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, mask_channels):
+        """Enqueue the mask filter of stereo clips of different lengths as one launch on the plan's stream (asynchronous;
+        zafx_execute_masked_stereo_ragged, mask filter plans of layout "TF" only; last_kernel: k_maskfilter_stereo_ragged).  in_offsets,
+        lengths and out_offsets count sample frames (L, R), as in execute_center_ragged: clip i is lengths[i] sample frames at sample frame
+        in_offsets[i] of d_in, its result goes to sample frame out_offsets[i] of d_out and, for a plan with rest, the rest directly behind.
+        mask_offsets counts float32 elements: clip i's masks, (T_i, mask_channels, W/2 + 1) compact, start at element mask_offsets[i] of d_mask
+        (stereo_ragged_layout gives the compact placement; its totals may stay on).  Clip i's block has the bits execute_masked_stereo gives
+        that clip and its masks alone.  Output blocks that overlap are not detected."""
+        mask_channels = int(mask_channels)
+        in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
+        out_offsets, mask_offsets = _as_int64(out_offsets, "out_offsets"), _as_int64(mask_offsets, "mask_offsets")
+        if len(mask_offsets) == len(lengths) + 1:
+            mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
+        if len(out_offsets) == len(lengths) + 1:
+            out_offsets = np.ascontiguousarray(out_offsets[:-1])
+        if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
+            raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
+        if d_in.dtype != np.float32 or d_mask.dtype != np.float32 or d_out.dtype != np.float32:
+            raise ValueError("execute_masked_stereo_ragged takes float32 sample frames, float32 masks and a float32 output buffer")
+        # (another kind or layout, another mask_channels, negative values, a clip at the bound: the library says so)
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and self.layout == _lib.LAYOUT_TF and mask_channels in (1, 2) and len(lengths)
+        if ok and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0 and int(lengths.max()) < 1 << (29 - mask_channels):
+            h = int(self.params.window_length) // 2
+            mask_ends = mask_offsets + mask_channels * ((lengths + h - 1) // h + 1) * (h + 1)
+            blocks = 2 if self.kind == _lib.MASKFILTER_REST else 1
+            live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
+            if int((in_offsets + lengths).max()) * 8 > d_in.nbytes:
+                raise ValueError("a clip reaches past the end of d_in")
+            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
+                raise ValueError("a clip's masks reach past the end of d_mask")
+            if int((out_offsets + blocks * lengths).max()) * 8 > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_masked_stereo_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
+                                                                 d_out.ptr, _i64p(out_offsets), len(lengths), mask_channels), "zafx_execute_masked_stereo_ragged")
+
     def ragged_layout(self, lengths):
         """Placement of a ragged batch's results (zafx_plan_ragged_layout) for clips of `lengths` samples: -> (out_offsets, frames, pitch), int64
         arrays.  Clip i's block of the output array starts at element out_offsets[i] (out_offsets[-1]: elements in all) and holds F rows of
@@ -1491,6 +1568,52 @@ def maskfilter_complex_batch(clips, window_function, masks, step_length=None, re
     return (out[:, 0], out[:, 1]) if rest else out
 
 
+def _stereo_mask_channels(ndim, shared_ndim, what):
+    """1 for masks of `shared_ndim` dimensions (one mask for both channels), 2 for one more (one per channel); anything else raises."""
+    if ndim not in (shared_ndim, shared_ndim + 1):
+        raise ValueError(f"{what} must be {shared_ndim}-D (one mask for both channels) or {shared_ndim + 1}-D (one per channel), got {ndim} dimensions")
+    return 1 if ndim == shared_ndim else 2
+
+
+def maskfilter_stereo_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
+    """The mask filter for a batch of interleaved stereo clips in one kernel (k_maskfilter_stereo): clips (B, N, 2) and real masks, one for both
+    channels, (B, W/2 + 1, T) -- (B, T, W/2 + 1) with layout "TF" --, or one per channel, (B, 2, W/2 + 1, T) -- (B, T, 2, W/2 + 1) with "TF" --,
+    T = ceil(N / (W/2)) + 1 -> y[:, :, c] = istft(concat(m_c, m_c[-2:0:-1]) * stft(x[:, :, c]))[0:N] (zaf.py:176-198 with the caller's masks),
+    float32 (B, N, 2); with rest=True (y, rest = x - y), views of one (B, 2, N, 2) result (which `out`, if given, is).  Both channels of a
+    frame share one transform: rounding and non-finite values of one channel reach the other channel of the same frames, never another clip.
+    The device reads "TF" masks only: "FT" masks are transposed on the host before the upload, as maskfilter_stems_batch does.
+    step_length: None or window_length / 2."""
+    w = _maskfilter_window(window_function, step_length)
+    a, m = np.asarray(clips), np.asarray(masks)
+    if a.ndim != 3 or a.shape[2] != 2:
+        raise ValueError(f"clips must be stereo, (clips, sample frames, 2), got shape {a.shape}")
+    if np.iscomplexobj(a) or np.iscomplexobj(m):
+        raise ValueError("clips and masks must be real")
+    if m.dtype.kind not in "biuf":
+        raise ValueError(f"masks must be real numbers, got dtype {m.dtype}")
+    mc = _stereo_mask_channels(m.ndim, 3, "masks")
+    n_clips, n = a.shape[:2]
+    h = len(w) // 2
+    frames, rows = (n + h - 1) // h + 1, h + 1
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    if mc == 1:
+        want = (n_clips, rows, frames) if ft else (n_clips, frames, rows)
+    else:
+        want = (n_clips, 2, rows, frames) if ft else (n_clips, frames, 2, rows)
+    if m.shape != want:
+        raise ValueError(f"masks must have shape {want} for clips of {n} sample frames (layout {layout!r}), got {m.shape}")
+    shape = (n_clips, 2, n, 2) if rest else (n_clips, n, 2)
+    if out is None:
+        out = np.empty(shape, np.float32)
+    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
+    if out.size:
+        plan = maskfilter_plan(w, rest, "TF", device)
+        tf = m if not ft else (m.transpose(0, 2, 1) if mc == 1 else m.transpose(0, 3, 1, 2))
+        _masked_round_trip(plan, a, tf, out, lambda d_in, d_mask, d_out: plan.execute_masked_stereo(d_in, d_mask, d_out, n_clips, n, mc))
+    return (out[:, 0], out[:, 1]) if rest else out
+
+
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
     """(B, N) -> (B, W/2, T) float32 ["FT"] or (B, T, W/2) ["TF"]; f64: float64 arrays and arithmetic."""
     x = _as_clips(clips, dtype=np.float64 if f64 else np.float32)
@@ -2092,6 +2215,62 @@ def maskfilter_complex_ragged(clips, window_function, masks, step_length=None, r
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
 
 
+def pack_ragged_stereo_masks(masks, lengths, window_length, layout="FT"):
+    """One contiguous float32 array of a ragged stereo batch's masks: a sequence of real arrays, all (W/2 + 1, T_i) -- one mask for both
+    channels; (T_i, W/2 + 1) with layout "TF" -- or all (2, W/2 + 1, T_i) -- one per channel; (T_i, 2, W/2 + 1) with "TF" --,
+    T_i = ceil(lengths[i] / (W/2)) + 1 -> (packed 1-D, mask_offsets of len(lengths) + 1, mask_channels), the layout of Plan.stereo_ragged_layout:
+    clip i's masks as (T_i, mask_channels, W/2 + 1) compact, the clips back to back.  The device reads "TF" masks only: "FT" masks are
+    transposed here, on the host.  A mask of another shape than the first one's kind raises ValueError with the clip's index."""
+    lengths = _as_lengths(lengths)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    if isinstance(masks, np.ndarray) and masks.dtype != object:
+        raise ValueError("a ragged stereo mask batch is a sequence of 2-D or 3-D masks, not one array")
+    try:
+        masks = list(masks)
+    except TypeError:
+        raise ValueError("a ragged stereo mask batch is a sequence of 2-D or 3-D masks") from None
+    mc = _stereo_mask_channels(np.ndim(masks[0]), 2, "mask 0") if masks else 1
+    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 1 + mc, "ragged stereo mask batch", f"{1 + mc}-D masks")
+    offsets = np.zeros(len(lengths) + 1, np.int64)
+    offsets[1:] = np.cumsum(mc * frames * (h + 1))
+    packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
+    for i, (m, o, t) in enumerate(zip(arrays, offsets.tolist(), frames.tolist())):
+        if mc == 1:
+            want = (h + 1, t) if ft else (t, h + 1)
+        else:
+            want = (2, h + 1, t) if ft else (t, 2, h + 1)
+        if m.shape != want:
+            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} sample frames (layout {layout!r}), got {m.shape}")
+        tf = m if not ft else (m.T if mc == 1 else m.transpose(2, 0, 1))
+        packed[o:o + mc * t * (h + 1)].reshape(tf.shape)[...] = tf
+    return packed, offsets, mc
+
+
+def maskfilter_stereo_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
+    """maskfilter_stereo_batch of stereo clips of different lengths in one launch: a sequence of (N_i, 2) real clips and one of real masks, all
+    for both channels, (W/2 + 1, T_i) -- (T_i, W/2 + 1) with layout "TF" --, or all per channel, (2, W/2 + 1, T_i) -- (T_i, 2, W/2 + 1) --,
+    T_i = ceil(N_i / (W/2)) + 1 -> a list of float32 (N_i, 2) arrays, or of (y_i, rest_i) pairs with rest=True, each a view of the one result
+    buffer; every clip's result has the bits maskfilter_stereo_batch gives for that clip alone.  One upload each of clips and masks, one
+    launch (k_maskfilter_stereo_ragged), one download.  "FT" masks are transposed on the host (pack_ragged_stereo_masks).  Window and
+    step_length as in maskfilter_stereo_batch."""
+    w = _maskfilter_window(window_function, step_length)
+    x, in_offsets, lengths = pack_ragged_stereo(clips)
+    m, mask_offsets, mc = pack_ragged_stereo_masks(masks, lengths, len(w), layout)
+    plan = maskfilter_plan(w, rest, "TF", device)
+    blocks = 2 if rest else 1
+    out_offsets = blocks * in_offsets
+    d_mask = DeviceBuffer(m.shape, m.dtype, plan.device)
+    try:
+        d_mask.upload(m)
+        res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: plan.execute_masked_stereo_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets,
+                                                                                                         d_out, out_offsets, mc))
+    finally:
+        d_mask.free()
+    if not rest:
+        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+
+
 def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
     """One contiguous float32 array of a ragged stems batch's masks: a sequence of real (S, W/2 + 1, T_i) arrays -- (S, T_i, W/2 + 1) with
     layout "TF" --, T_i = ceil(lengths[i] / (W/2)) + 1, S the same for every clip -> (packed 1-D, mask_offsets of len(lengths) + 1), the layout
@@ -2354,6 +2533,17 @@ def maskfilter_complex(audio_signal, window_function, step_length, mask):
     if m.ndim != 2:
         raise ValueError(f"mask must be 2-D (window_length / 2 + 1, number_times), got shape {m.shape}")
     return maskfilter_complex_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
+
+
+def maskfilter_stereo(audio_signal, window_function, step_length, mask):
+    """The center / sides example's filter (zaf.py:176-198) with masks of the caller's in one call: an (N, 2) stereo signal and a real mask
+    (W/2 + 1, T) for both channels, or (2, W/2 + 1, T), one per channel -> float64 (N, 2), column c being zaf.istft(np.concatenate((m_c,
+    m_c[-2:0:-1])) * zaf.stft(audio_signal[:, c], ...), ...)[0:N]; step_length must be window_length / 2 (see maskfilter_stereo_batch)."""
+    a, m = np.asarray(audio_signal), np.asarray(mask)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"audio_signal must be stereo, (sample frames, 2), got shape {a.shape}")
+    _stereo_mask_channels(m.ndim, 2, "mask")
+    return maskfilter_stereo_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
 
 
 def maskfilter_stems(audio_signal, window_function, step_length, masks):
