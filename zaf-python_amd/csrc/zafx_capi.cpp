@@ -1481,66 +1481,6 @@ static int check_window_gain(const zafx_plan* pl, const char* what) {
     return 0;
 }
 
-// What zafx_execute_masked, zafx_execute_masked_stems and zafx_execute_masked_complex ask first, in this order: the plan, its kind (`note`: what
-// the message adds behind it), the sizes ...
-static int masked_plan_checks(const char* fn, const zafx_plan* pl, const char* note, int64_t n_clips, int64_t n_in) {
-    if (!pl) return fail_msg("null plan");
-    if (!is_maskfilter_kind(pl->kind)) return fail_msg(std::string(fn) + ": ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only" + note);
-    if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
-    return 0;
-}
-// ... and, behind the kind's own refusals and for a batch that is not empty, the three arrays, the window and the device.
-static int masked_launch_checks(const zafx_plan* pl, const void* d_in, const void* d_mask, const void* d_out) {
-    if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
-    if (int rc = check_window_gain(pl, "mask filter")) return rc;
-    ZAFX_HIP(hipSetDevice(pl->device));
-    return 0;
-}
-
-int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
-    if (int rc = masked_plan_checks("zafx_execute_masked", pl, " (every other kind takes zafx_execute)", n_clips, n_in)) return rc;
-    if (n_clips == 0) return 0;
-    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
-    return launch_rc("zafx_execute_masked", zafx::launch_maskfilter(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in));
-}
-
-static_assert(ZAFX_MASKFILTER_MAX_STEMS == zafx::kMaskfilterMaxStems, "the header's stem bound is the launcher's");
-
-int zafx_execute_masked_stems(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t n_stems) {
-    if (int rc = masked_plan_checks("zafx_execute_masked_stems", pl, "", n_clips, n_in)) return rc;
-    zafx::RouteCall c;   // the launcher's refusals, for an empty batch too
-    c.layout = pl->layout, c.n = n_in;
-    if (const char* why = zafx::maskfilter_stems_refusal(c, n_stems)) return fail_msg(std::string("zafx_execute_masked_stems: ") + why);
-    if (n_clips == 0) return 0;
-    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
-    return launch_rc("zafx_execute_masked_stems", zafx::launch_maskfilter_stems(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in, n_stems));
-}
-
-// Complex64 masks (B, T, W/2+1) on k_maskfilter_c: TF plans, clips below 2^27 samples (maskfilter_complex_refusal), refused for an empty batch too.
-int zafx_execute_masked_complex(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
-    const char* const fn = "zafx_execute_masked_complex";
-    if (int rc = masked_plan_checks(fn, pl, "", n_clips, n_in)) return rc;
-    zafx::RouteCall c;
-    c.kind = pl->kind, c.layout = pl->layout, c.n = n_in;
-    if (const char* why = zafx::maskfilter_complex_refusal(c)) return fail_msg(std::string(fn) + ": " + why);
-    if (n_clips == 0) return 0;
-    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
-    return launch_rc(fn, zafx::launch_maskfilter_complex(*pl, (const float*)d_in, (const float2*)d_mask, (float*)d_out, n_clips, n_in));
-}
-
-// Interleaved stereo clips (B, N, 2) under one mask for both channels (B, T, W/2+1) or one per channel (B, T, 2, W/2+1) on k_maskfilter_stereo:
-// TF plans, mask_channels 1 or 2, clips below 2^28 / 2^27 sample frames (maskfilter_stereo_refusal), refused for an empty batch too.
-int zafx_execute_masked_stereo(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t mask_channels) {
-    const char* const fn = "zafx_execute_masked_stereo";
-    if (int rc = masked_plan_checks(fn, pl, "", n_clips, n_in)) return rc;
-    zafx::RouteCall c;
-    c.kind = pl->kind, c.layout = pl->layout, c.n = n_in;
-    if (const char* why = zafx::maskfilter_stereo_refusal(c, mask_channels)) return fail_msg(std::string(fn) + ": " + why);
-    if (n_clips == 0) return 0;
-    if (int rc = masked_launch_checks(pl, d_in, d_mask, d_out)) return rc;
-    return launch_rc(fn, zafx::launch_maskfilter_stereo(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out, n_clips, n_in, mask_channels));
-}
-
 int zafx_execute(zafx_plan* pl, const void* d_in, void* d_out, int64_t n_clips, int64_t n_in) {
     if (!pl) return fail_msg("null plan");
     if (is_maskfilter_kind(pl->kind)) return fail_msg(std::string("zafx_execute: ") + kMaskedOnly);
@@ -1858,144 +1798,174 @@ int zafx_plan_mask_ragged_layout(const zafx_plan* pl, const int64_t* lengths, in
     return 0;
 }
 
-// The tail of zafx_execute_masked_ragged (n_stems = 0: k_maskfilter, masks in the plan's layout), zafx_execute_masked_stems_ragged
-// (k_maskfilter_stems, compact TF masks: no pitch) and zafx_execute_masked_complex_ragged (n_stems = 0, complex_mask: k_maskfilter_c on a TF
-// plan, whose launch shape and units are k_maskfilter's; mask_offsets count complex64 elements), behind their argument checks: the window,
-// the kernel's launch shape, the cut, the upload of the units and the launch.
-static int cut_and_launch_masked(const char* fn, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
-                                 const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems,
-                                 bool complex_mask = false) {
-    if (int rc = check_window_gain(pl, "mask filter")) return rc;
-    int tile_transforms = 0;
-    long long slots = 0;
-    if (!(n_stems ? zafx::maskfilter_stems_launch_shape(*pl, n_stems, &tile_transforms, &slots) : zafx::maskfilter_launch_shape(*pl, &tile_transforms, &slots)))
-        return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
-    std::vector<int64_t> pitches(n_stems ? 0 : (size_t)n_clips);
+// What the four kinds of the fused STFT -> mask -> ISTFT family differ in on the host, each with an equal-length and a ragged entry point:
+// real masks (k_maskfilter), stems (k_maskfilter_stems), complex masks (k_maskfilter_c) and interleaved stereo (k_maskfilter_stereo).  `count`
+// is the kind's extra argument -- n_stems, mask_channels; 0 for the kinds without one.
+struct MaskedForm {
+    const char *fn, *fn_ragged, *fn_layout;   // the entry points, as the messages name them (fn_layout: zafx_plan_*_ragged_layout; null: none of this shape)
+    const zafx::MaskfilterForm& routes;       // what the kind refuses (zafx_routes.hpp)
+    const char* note;                         // what the equal-length entry adds behind "... plans only"
+    // The oldest kind keeps its own sequence: the equal-length bound is asked by launch_maskfilter alone -- behind the empty-batch return and
+    // the pointer and window checks --, an empty batch of it is refused nothing, and the ragged entry names the clip in front ("clip i has
+    // 2^28 samples or more", check_clips_below_2_28) instead of asking the routes record.
+    bool bound_left_to_launcher;
+    const char* env_per_slot;                 // the measurement switch (include/zafx.h) ...
+    int per_slot;                             // ... and what it is preset to
+    bool stems_out;                           // a clip's output: `count` blocks (+ 1 with rest) instead of 1 (+ 1)
+    hipError_t (*launch)(const zafx_plan&, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int64_t count);
+    bool (*launch_shape)(const zafx_plan&, int64_t count, int* tile, long long* slots);
+    std::vector<zafx::MaskfilterUnit> (*cut)(const zafx_plan&, const int64_t* lengths, const int64_t* in_offsets, const int64_t* out_offsets, const int64_t* mask_offsets,
+                                             int64_t n_clips, int tile, long long slots, int per_slot);
+    hipError_t (*launch_ragged)(const zafx_plan&, const void* d_in, const void* d_mask, void* d_out, const zafx::MaskfilterUnit* d_units, long long n_units, int64_t count);
+};
+
+static_assert(ZAFX_MASKFILTER_MAX_STEMS == zafx::kMaskfilterMaxStems, "the header's stem bound is the launcher's");
+
+// k_maskfilter's cut: masks at the pitch of the plan's layout (every clip's mask_block; the complex kind's TF plans: W/2 + 1) or without pitches (the stems')
+static std::vector<zafx::MaskfilterUnit> cut_masked(const zafx_plan& pl, bool with_pitches, const int64_t* lengths, const int64_t* in_offsets, const int64_t* out_offsets,
+                                                    const int64_t* mask_offsets, int64_t n_clips, int tile, long long slots, int per_slot) {
+    std::vector<int64_t> pitches(with_pitches ? (size_t)n_clips : 0);
     for (size_t i = 0; i < pitches.size(); ++i) {
         int64_t elems = 0;
-        mask_block(pl, lengths[i], &elems, &pitches[i]);
+        mask_block(&pl, lengths[i], &elems, &pitches[i]);
     }
-    // ZAFX_MASKFILTER_UNITS_PER_SLOT in the environment: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
-    const int per_slot = env_units_per_slot("ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot);
-    const std::vector<zafx::MaskfilterUnit> units = zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, n_stems ? nullptr : pitches.data(), n_clips,
-                                                                               pl->W, tile_transforms, slots, per_slot);
+    return zafx::maskfilter_cut_units(lengths, in_offsets, out_offsets, mask_offsets, with_pitches ? pitches.data() : nullptr, n_clips, pl.W, tile, slots, per_slot);
+}
+#define ZAFX_CUT_ARGS const zafx_plan& pl, const int64_t* len, const int64_t* in, const int64_t* out, const int64_t* mask, int64_t n, int tile, long long slots, int per_slot
+#define ZAFX_MASKED_ARGS const zafx_plan& pl, const void* x, const void* m, void* y
+static const MaskedForm kMaskedForms[] = {
+    // real masks, in the plan's layout.  ZAFX_MASKFILTER_UNITS_PER_SLOT: the units per workgroup slot the segment length aims at (1 ... 64; measurements only)
+    {"zafx_execute_masked", "zafx_execute_masked_ragged", nullptr, zafx::kMaskfilterReal, " (every other kind takes zafx_execute)", true,
+     "ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot, false,
+     [](ZAFX_MASKED_ARGS, int64_t b, int64_t n, int64_t) { return zafx::launch_maskfilter(pl, (const float*)x, (const float*)m, (float*)y, b, n); },
+     [](const zafx_plan& pl, int64_t, int* tile, long long* slots) { return zafx::maskfilter_launch_shape(pl, tile, slots); },
+     [](ZAFX_CUT_ARGS) { return cut_masked(pl, true, len, in, out, mask, n, tile, slots, per_slot); },
+     [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t) { return zafx::launch_maskfilter_ragged(pl, (const float*)x, (const float*)m, (float*)y, u, nu); }},
+    // n_stems masks per clip, compact TF: the units are k_maskfilter's, cut for the slots the stems' LDS size leaves
+    {"zafx_execute_masked_stems", "zafx_execute_masked_stems_ragged", "zafx_plan_stems_ragged_layout", zafx::kMaskfilterStems, "", false,
+     "ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot, true,
+     [](ZAFX_MASKED_ARGS, int64_t b, int64_t n, int64_t s) { return zafx::launch_maskfilter_stems(pl, (const float*)x, (const float*)m, (float*)y, b, n, s); },
+     [](const zafx_plan& pl, int64_t s, int* tile, long long* slots) { return zafx::maskfilter_stems_launch_shape(pl, (int)s, tile, slots); },
+     [](ZAFX_CUT_ARGS) { return cut_masked(pl, false, len, in, out, mask, n, tile, slots, per_slot); },
+     [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t s) { return zafx::launch_maskfilter_stems_ragged(pl, (const float*)x, (const float*)m, (float*)y, u, nu, s); }},
+    // complex64 masks on k_maskfilter_c, TF plans: the launch shape and the units are the real kind's (no pitch); mask_offsets count complex64 elements
+    {"zafx_execute_masked_complex", "zafx_execute_masked_complex_ragged", nullptr, zafx::kMaskfilterComplex, "", false,
+     "ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot, false,
+     [](ZAFX_MASKED_ARGS, int64_t b, int64_t n, int64_t) { return zafx::launch_maskfilter_complex(pl, (const float*)x, (const float2*)m, (float*)y, b, n); },
+     [](const zafx_plan& pl, int64_t, int* tile, long long* slots) { return zafx::maskfilter_launch_shape(pl, tile, slots); },
+     [](ZAFX_CUT_ARGS) { return cut_masked(pl, true, len, in, out, mask, n, tile, slots, per_slot); },
+     [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t) { return zafx::launch_maskfilter_complex_ragged(pl, (const float*)x, (const float2*)m, (float*)y, u, nu); }},
+    // interleaved stereo clips, mask_channels masks per frame: the units are k_center's blocks in MaskfilterUnit records, offsets and lengths
+    // count sample frames.  ZAFX_CENTER_UNITS_PER_SLOT, as for zafx_execute_center_ragged: the cut is that one's (measurements only)
+    {"zafx_execute_masked_stereo", "zafx_execute_masked_stereo_ragged", "zafx_plan_stereo_ragged_layout", zafx::kMaskfilterStereo, "", false,
+     "ZAFX_CENTER_UNITS_PER_SLOT", zafx::kCenterUnitsPerSlot, false,
+     [](ZAFX_MASKED_ARGS, int64_t b, int64_t n, int64_t mc) { return zafx::launch_maskfilter_stereo(pl, (const float*)x, (const float*)m, (float*)y, b, n, (int)mc); },
+     [](const zafx_plan& pl, int64_t, int* tile, long long* slots) { return zafx::maskfilter_stereo_launch_shape(pl, tile, slots); },
+     [](ZAFX_CUT_ARGS) { return zafx::maskfilter_stereo_cut_units(len, in, out, mask, n, pl.W, tile, slots, per_slot); },
+     [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t mc) { return zafx::launch_maskfilter_stereo_ragged(pl, (const float*)x, (const float*)m, (float*)y, u, nu, (int)mc); }},
+};
+#undef ZAFX_CUT_ARGS
+#undef ZAFX_MASKED_ARGS
+static const MaskedForm &kMaskedReal = kMaskedForms[0], &kMaskedStems = kMaskedForms[1], &kMaskedComplex = kMaskedForms[2], &kMaskedStereo = kMaskedForms[3];
+
+// An equal-length entry point.  In this order: the plan, its kind, the sizes, the kind's own refusals (for an empty batch too), then -- for a
+// batch that is not empty -- the three arrays, the window, the device and the launch.
+static int execute_masked(const MaskedForm& k, zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int64_t count) {
+    if (!pl) return fail_msg("null plan");
+    if (!is_maskfilter_kind(pl->kind)) return fail_msg(std::string(k.fn) + ": ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only" + k.note);
+    if (n_clips < 0 || n_in < 0) return fail_msg("negative size");
+    if (!k.bound_left_to_launcher) {
+        zafx::RouteCall c;
+        c.kind = pl->kind, c.layout = pl->layout, c.n = n_in;
+        if (const char* why = zafx::maskfilter_form_refusal(k.routes, c, count)) return fail_msg(std::string(k.fn) + ": " + why);
+    }
+    if (n_clips == 0) return 0;
+    if (!d_in || !d_mask || !d_out) return fail_msg("null device pointer");
+    if (int rc = check_window_gain(pl, "mask filter")) return rc;
     ZAFX_HIP(hipSetDevice(pl->device));
-    if (int rc = upload_records(pl, units)) return rc;
-    const auto* d_units = static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get());
-    const float *x = (const float*)d_in, *m = (const float*)d_mask;
-    if (complex_mask) return launch_rc(fn, zafx::launch_maskfilter_complex_ragged(*pl, x, (const float2*)d_mask, (float*)d_out, d_units, (long long)units.size()));
-    return launch_rc(fn, n_stems ? zafx::launch_maskfilter_stems_ragged(*pl, x, m, (float*)d_out, d_units, (long long)units.size(), n_stems)
-                                 : zafx::launch_maskfilter_ragged(*pl, x, m, (float*)d_out, d_units, (long long)units.size()));
+    return launch_rc(k.fn, k.launch(*pl, d_in, d_mask, d_out, n_clips, n_in, count));
 }
 
-// Ragged batches of the mask-filter kinds: the host cuts the clips into units of block pairs (maskfilter_cut_units), k_maskfilter's RAGGED form walks them.
+// A ragged entry point: the kind, the layout and the count (refused for an empty batch too) and every clip's length are decided on the host
+// arrays before anything else is read (maskfilter_form_ragged_refusal); then the window, the kernel's launch shape, the cut of the clips into
+// units (zafx_units.hpp), their upload and the launch of the kernel's RAGGED form, which walks them.
+static int execute_masked_ragged(const MaskedForm& k, zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                 const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int64_t count) {
+    const char* const fn = k.fn_ragged;
+    int64_t clip = -1;
+    const char* wrong_kind = pl ? zafx::maskfilter_form_ragged_refusal(k.routes, pl->kind, pl->layout, count, nullptr, 0, &clip) : nullptr;
+    bool empty = false;
+    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
+    if (empty) return 0;
+    if (k.bound_left_to_launcher) {
+        if (int rc = check_clips_below_2_28(fn, lengths, n_clips, "samples")) return rc;
+    } else if (const char* why = zafx::maskfilter_form_ragged_refusal(k.routes, pl->kind, pl->layout, count, lengths, n_clips, &clip)) {
+        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
+    }
+    if (int rc = check_window_gain(pl, "mask filter")) return rc;
+    int tile = 0;
+    long long slots = 0;
+    if (!k.launch_shape(*pl, count, &tile, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
+    const std::vector<zafx::MaskfilterUnit> units = k.cut(*pl, lengths, in_offsets, out_offsets, mask_offsets, n_clips, tile, slots, env_units_per_slot(k.env_per_slot, k.per_slot));
+    ZAFX_HIP(hipSetDevice(pl->device));
+    if (int rc = upload_records(pl, units)) return rc;
+    return launch_rc(fn, k.launch_ragged(*pl, d_in, d_mask, d_out, static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size(), count));
+}
+
+// The compact placement of a ragged batch of a kind with a count: a clip's masks are `count` x a TF plan's mask_block, its output one block of
+// its length (stems: `count` blocks), one more with the rest; out_offsets count what the lengths count.
+static int plan_masked_ragged_layout(const MaskedForm& k, const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int64_t count, int64_t* mask_offsets,
+                                     int64_t* out_offsets) {
+    if (!pl || !mask_offsets || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
+    if (n_clips < 0) return fail_msg("negative size");
+    int64_t clip = -1;
+    if (const char* why = zafx::maskfilter_form_ragged_refusal(k.routes, pl->kind, pl->layout, count, nullptr, 0, &clip)) return fail_msg(std::string(k.fn_layout) + ": " + why);
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] < 0) return fail_msg(std::string(k.fn_layout) + ": negative length of clip " + std::to_string(i));
+    const int64_t blocks = (k.stems_out ? count : 1) + (pl->kind == ZAFX_MASKFILTER_REST ? 1 : 0);
+    mask_offsets[0] = out_offsets[0] = 0;
+    for (int64_t i = 0; i < n_clips; ++i) {
+        int64_t elems = 0, pitch = 0;
+        mask_block(pl, lengths[i], &elems, &pitch);
+        mask_offsets[i + 1] = mask_offsets[i] + count * elems;
+        out_offsets[i + 1] = out_offsets[i] + blocks * lengths[i];
+    }
+    return 0;
+}
+
+int zafx_execute_masked(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
+    return execute_masked(kMaskedReal, pl, d_in, d_mask, d_out, n_clips, n_in, 0);
+}
+int zafx_execute_masked_stems(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t n_stems) {
+    return execute_masked(kMaskedStems, pl, d_in, d_mask, d_out, n_clips, n_in, n_stems);
+}
+int zafx_execute_masked_complex(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in) {
+    return execute_masked(kMaskedComplex, pl, d_in, d_mask, d_out, n_clips, n_in, 0);
+}
+int zafx_execute_masked_stereo(zafx_plan* pl, const void* d_in, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_in, int32_t mask_channels) {
+    return execute_masked(kMaskedStereo, pl, d_in, d_mask, d_out, n_clips, n_in, mask_channels);
+}
 int zafx_execute_masked_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask, const int64_t* mask_offsets,
                                void* d_out, const int64_t* out_offsets, int64_t n_clips) {
-    const char* const fn = "zafx_execute_masked_ragged";
-    const char* wrong_kind = !pl || is_maskfilter_kind(pl->kind) ? nullptr : "ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only (zafx_execute_ragged takes the forward kinds)";
-    bool empty = false;
-    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
-    if (empty) return 0;
-    if (int rc = check_clips_below_2_28(fn, lengths, n_clips, "samples")) return rc;
-    return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0);
+    return execute_masked_ragged(kMaskedReal, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0);
 }
-
-// Ragged batches under complex64 masks: the kind, the layout (refused for an empty batch too, as zafx_execute_masked_complex does) and every
-// clip's length are decided on the host arrays before anything else is read (maskfilter_complex_ragged_refusal); the rest is the real kind's tail.
-int zafx_execute_masked_complex_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
-                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips) {
-    const char* const fn = "zafx_execute_masked_complex_ragged";
-    int64_t clip = -1;
-    const char* wrong_kind = pl ? zafx::maskfilter_complex_ragged_refusal(pl->kind, pl->layout, nullptr, 0, &clip) : nullptr;
-    bool empty = false;
-    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
-    if (empty) return 0;
-    if (const char* why = zafx::maskfilter_complex_ragged_refusal(pl->kind, pl->layout, lengths, n_clips, &clip))
-        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
-    return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0, true);
-}
-
-// Stems of a ragged batch: a clip's n_stems masks back to back, each as a TF plan's mask_block, and its n_stems (+ 1 with rest) output blocks
-int zafx_plan_stems_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t n_stems, int64_t* mask_offsets, int64_t* out_offsets) {
-    const char* const fn = "zafx_plan_stems_ragged_layout";
-    if (!pl || !mask_offsets || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
-    if (n_clips < 0) return fail_msg("negative size");
-    int64_t clip = -1;
-    if (const char* why = zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, nullptr, 0, &clip)) return fail_msg(std::string(fn) + ": " + why);
-    for (int64_t i = 0; i < n_clips; ++i)
-        if (lengths[i] < 0) return fail_msg(std::string(fn) + ": negative length of clip " + std::to_string(i));
-    const int64_t blocks = n_stems + (pl->kind == ZAFX_MASKFILTER_REST ? 1 : 0);
-    mask_offsets[0] = out_offsets[0] = 0;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        int64_t elems = 0, pitch = 0;
-        mask_block(pl, lengths[i], &elems, &pitch);
-        mask_offsets[i + 1] = mask_offsets[i] + n_stems * elems;
-        out_offsets[i + 1] = out_offsets[i] + blocks * lengths[i];
-    }
-    return 0;
-}
-
-// Ragged batches with n_stems masks per clip: the units are k_maskfilter's (maskfilter_cut_units), cut for the slots the stems' LDS size
-// leaves; k_maskfilter_stems' RAGGED form walks them.
 int zafx_execute_masked_stems_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                      const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_stems) {
-    const char* const fn = "zafx_execute_masked_stems_ragged";
-    int64_t clip = -1;
-    // the kind, the layout and the stem count: refused for an empty batch too, as zafx_execute_masked_stems does
-    const char* wrong_kind = pl ? zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, nullptr, 0, &clip) : nullptr;
-    bool empty = false;
-    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
-    if (empty) return 0;
-    if (const char* why = zafx::maskfilter_stems_ragged_refusal(pl->kind, pl->layout, n_stems, lengths, n_clips, &clip))
-        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
-    return cut_and_launch_masked(fn, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, n_stems);
+    return execute_masked_ragged(kMaskedStems, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, n_stems);
 }
-
-// Stereo clips of a ragged batch: a clip's mask(s) are mask_channels x a TF plan's mask_block, its output one block of sample frames, two with
-// the rest (out_offsets count sample frames)
-int zafx_plan_stereo_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t mask_channels, int64_t* mask_offsets, int64_t* out_offsets) {
-    const char* const fn = "zafx_plan_stereo_ragged_layout";
-    if (!pl || !mask_offsets || !out_offsets || (n_clips > 0 && !lengths)) return fail_msg("null argument");
-    if (n_clips < 0) return fail_msg("negative size");
-    int64_t clip = -1;
-    if (const char* why = zafx::maskfilter_stereo_ragged_refusal(pl->kind, pl->layout, mask_channels, nullptr, 0, &clip)) return fail_msg(std::string(fn) + ": " + why);
-    for (int64_t i = 0; i < n_clips; ++i)
-        if (lengths[i] < 0) return fail_msg(std::string(fn) + ": negative length of clip " + std::to_string(i));
-    const int64_t blocks = pl->kind == ZAFX_MASKFILTER_REST ? 2 : 1;
-    mask_offsets[0] = out_offsets[0] = 0;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        int64_t elems = 0, pitch = 0;
-        mask_block(pl, lengths[i], &elems, &pitch);
-        mask_offsets[i + 1] = mask_offsets[i] + mask_channels * elems;
-        out_offsets[i + 1] = out_offsets[i] + blocks * lengths[i];
-    }
-    return 0;
+int zafx_execute_masked_complex_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips) {
+    return execute_masked_ragged(kMaskedComplex, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, 0);
 }
-
-// Ragged stereo batches under the caller's masks: the kind, the layout, mask_channels (refused for an empty batch too) and every clip's length
-// are decided on the host arrays before anything else is read (maskfilter_stereo_ragged_refusal); the units are k_center's blocks in
-// MaskfilterUnit records (maskfilter_stereo_cut_units), k_maskfilter_stereo's RAGGED form walks them.
 int zafx_execute_masked_stereo_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t mask_channels) {
-    const char* const fn = "zafx_execute_masked_stereo_ragged";
-    int64_t clip = -1;
-    const char* wrong_kind = pl ? zafx::maskfilter_stereo_ragged_refusal(pl->kind, pl->layout, mask_channels, nullptr, 0, &clip) : nullptr;
-    bool empty = false;
-    if (int rc = ragged_args(fn, pl, n_clips, wrong_kind, d_in, d_mask ? d_out : nullptr, {lengths, in_offsets, mask_offsets, out_offsets}, "length", &empty)) return rc;
-    if (empty) return 0;
-    if (const char* why = zafx::maskfilter_stereo_ragged_refusal(pl->kind, pl->layout, mask_channels, lengths, n_clips, &clip))
-        return fail_msg(std::string(fn) + ": " + why + (clip >= 0 ? ": clip " + std::to_string(clip) : std::string()));
-    if (int rc = check_window_gain(pl, "mask filter")) return rc;
-    int tile_frames = 0;
-    long long slots = 0;
-    if (!zafx::maskfilter_stereo_launch_shape(*pl, &tile_frames, &slots)) return fail_msg("mask filter: window_length must be 256, 512, 1024 or 2048");
-    // ZAFX_CENTER_UNITS_PER_SLOT in the environment, as for zafx_execute_center_ragged: the cut is that one's (measurements only)
-    const int per_slot = env_units_per_slot("ZAFX_CENTER_UNITS_PER_SLOT", zafx::kCenterUnitsPerSlot);
-    const std::vector<zafx::MaskfilterUnit> units = zafx::maskfilter_stereo_cut_units(lengths, in_offsets, out_offsets, mask_offsets, n_clips, pl->W, tile_frames, slots, per_slot);
-    ZAFX_HIP(hipSetDevice(pl->device));
-    if (int rc = upload_records(pl, units)) return rc;
-    return launch_rc(fn, zafx::launch_maskfilter_stereo_ragged(*pl, (const float*)d_in, (const float*)d_mask, (float*)d_out,
-                                                               static_cast<const zafx::MaskfilterUnit*>(pl->d_ragged.get()), (long long)units.size(), mask_channels));
+    return execute_masked_ragged(kMaskedStereo, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, mask_channels);
+}
+int zafx_plan_stems_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t n_stems, int64_t* mask_offsets, int64_t* out_offsets) {
+    return plan_masked_ragged_layout(kMaskedStems, pl, lengths, n_clips, n_stems, mask_offsets, out_offsets);
+}
+int zafx_plan_stereo_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t mask_channels, int64_t* mask_offsets, int64_t* out_offsets) {
+    return plan_masked_ragged_layout(kMaskedStereo, pl, lengths, n_clips, mask_channels, mask_offsets, out_offsets);
 }
 
 // What zafx_execute_imdct_ragged and zafx_execute_istft_ragged differ in: both cut their blocks into units of tiles (zafx_units.hpp) that the

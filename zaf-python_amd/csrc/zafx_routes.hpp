@@ -448,109 +448,116 @@ inline bool mdct_pcm_direct_ok(const RouteCall& c) {
 // refusals: a clip is addressed through one buffer descriptor with 32-bit byte offsets
 inline bool cqt_clip_refused(const RouteCall& c) { return c.n >= (1LL << 29); }
 inline bool center_clip_refused(const RouteCall& c) { return c.n >= (1LL << 28); }   // (sample frames)
-inline bool maskfilter_clip_refused(const RouteCall& c) { return c.n >= (1LL << 28); }   // (samples; the clip's mask then stays below 2^31 bytes)
-// zafx_execute_masked_stems: masks in ZAFX_LAYOUT_TF only (k_maskfilter's FT stage and eight carries do not fit LDS at W = 2048), 1 .. 8 stems,
-// and the clip bound of the one-mask kind -- a descriptor per (clip, stem) addresses one mask, as there.  nullptr: the call is taken.
-inline const char* maskfilter_stems_refusal(const RouteCall& c, int64_t n_stems) {
-    if (c.layout != ZAFX_LAYOUT_TF) return "mask filter stems: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)";
-    if (n_stems < 1 || n_stems > kMaskfilterMaxStems) return "mask filter stems: n_stems must be in 1 .. 8 (ZAFX_MASKFILTER_MAX_STEMS)";
-    if (maskfilter_clip_refused(c)) return "mask filter: clips of 2^28 samples and more are not supported";
+// ---------------------------------------------------------------------------------
+// The fused STFT -> mask -> ISTFT family: four kinds of mask, each with an equal-length and a ragged entry point (zafx_execute_masked*).
+// What the refusals of a kind read stands in one record; zafx_capi.cpp (kMaskedForms) and zafx/core.py (_MaskedForm) hold the rest of a kind.
+// The strings and the order of the tests are those the per-kind functions had (profiles/maskfilter_forms_notes.md: the irregularities kept).
+// ---------------------------------------------------------------------------------
+struct MaskfilterForm {
+    const char* wrong_kind;        // what a plan of another kind is told ...
+    bool equal_asks_kind;          // ... by the equal-length refusal too (stems: no -- its entry point has asked in its own words)
+    const char* wrong_layout;      // masks in ZAFX_LAYOUT_TF only (null: ZAFX_LAYOUT_FT too)
+    int64_t count_min, count_max;  // the count argument -- n_stems, mask_channels -- ...
+    const char* wrong_count;       // ... and what a value outside is told (null: the kind has no count)
+    int64_t max_units;             // clips of this many samples (stereo: sample frames) and more are refused ...
+    int64_t halved_at;             // ... of half as many at this count (0: at none)
+    const char* too_long[2];       // the equal-length call's refusal of such a clip, [1]: at the halved bound
+    const char* clip_too_long[2];  // the ragged call's (the caller appends the clip's index)
+    int mask_bytes;                // of a mask element
+    bool count_in_descriptor;      // the count's masks of a frame lie behind ONE buffer descriptor (stems: one descriptor per stem)
+    constexpr int halved(int64_t count) const { return halved_at != 0 && count == halved_at; }
+    constexpr int64_t bound(int64_t count) const { return max_units >> halved(count); }
+};
+// k_maskfilter: one real mask in the plan's layout.  Its entry points ask the kind in their own words and leave the equal-length bound to the
+// launcher (maskfilter_clip_refused); the ragged one names the clip in front (check_clips_below_2_28, zafx_capi.cpp): clip_too_long is not used.
+constexpr MaskfilterForm kMaskfilterReal = {
+    "ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only (zafx_execute_ragged takes the forward kinds)", false, nullptr, 0, 0, nullptr, 1LL << 28, 0,
+    {"mask filter: clips of 2^28 samples and more are not supported", nullptr}, {nullptr, nullptr}, 4, false};
+// k_maskfilter_stems: masks in ZAFX_LAYOUT_TF only (k_maskfilter's FT stage and eight carries do not fit LDS at W = 2048), 1 .. 8 stems, and the
+// clip bound of the one-mask kind -- a descriptor per (clip, stem) addresses one mask, as there -- in that kind's words.
+constexpr MaskfilterForm kMaskfilterStems = {
+    "mask filter stems: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only", false,
+    "mask filter stems: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)", 1, kMaskfilterMaxStems,
+    "mask filter stems: n_stems must be in 1 .. 8 (ZAFX_MASKFILTER_MAX_STEMS)", 1LL << 28, 0,
+    {kMaskfilterReal.too_long[0], nullptr}, {"mask filter stems: a clip has 2^28 samples or more (not supported)", nullptr}, 4, false};
+// k_maskfilter_c: complex64 masks in ZAFX_LAYOUT_TF only (the FT stage in LDS would double: 148 KB at W = 2048 beside the frames), and clips
+// below 2^27 samples: a clip's mask -- 8 bytes a bin, T (W/2 + 1) bins -- lies behind one buffer descriptor with signed 32-bit byte offsets.
+constexpr MaskfilterForm kMaskfilterComplex = {
+    "complex mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only", true,
+    "complex mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)", 0, 0, nullptr, 1LL << 27, 0,
+    {"complex mask filter: clips of 2^27 samples and more are not supported", nullptr},
+    {"complex mask filter: a clip has 2^27 samples or more (not supported)", nullptr}, 8, false};
+// k_maskfilter_stereo: interleaved stereo clips under one real mask for both channels (mask_channels 1) or one per channel (2), masks in
+// ZAFX_LAYOUT_TF only (the kernel is k_center's walk: no FT stage in its LDS).  The samples lie behind one descriptor of 8 N bytes: N < 2^28
+// sample frames; two masks per frame are 8 T (W/2 + 1) bytes -- the complex kind's arithmetic --: N < 2^27 then.
+constexpr MaskfilterForm kMaskfilterStereo = {
+    "stereo mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only", true,
+    "stereo mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)", 1, 2,
+    "stereo mask filter: mask_channels must be 1 (one mask for both channels) or 2 (one per channel)", 1LL << 28, 2,
+    {"stereo mask filter: clips of 2^28 sample frames and more are not supported",
+     "stereo mask filter: with a mask per channel clips of 2^27 sample frames and more are not supported"},
+    {"stereo mask filter: a clip has 2^28 sample frames or more (not supported)",
+     "stereo mask filter: with a mask per channel a clip has 2^27 sample frames or more (not supported)"}, 4, true};
+
+// bytes of the compact TF mask(s) behind one descriptor of a clip of n samples (sample frames): T frames of W/2 + 1 bins
+constexpr int64_t maskfilter_mask_bytes(const MaskfilterForm& f, int64_t n, int W, int64_t count) {
+    return ((n + W / 2 - 1) / (W / 2) + 1) * (f.count_in_descriptor ? count : 1) * (W / 2 + 1) * f.mask_bytes;
+}
+constexpr bool maskfilter_masks_addressable(const MaskfilterForm& f) {
+    for (int W = 256; W <= 2048; W *= 2)
+        for (int64_t count = f.count_min; count <= f.count_max; ++count)
+            if (maskfilter_mask_bytes(f, f.bound(count) - 1, W, count) >= (1LL << 31)) return false;
+    return true;
+}
+static_assert(maskfilter_masks_addressable(kMaskfilterReal) && maskfilter_masks_addressable(kMaskfilterStems) &&
+                  maskfilter_masks_addressable(kMaskfilterComplex) && maskfilter_masks_addressable(kMaskfilterStereo),
+              "mask filter, every window, kind and count: the mask(s) of the longest clip taken stay behind signed 32-bit byte offsets");
+
+// The equal-length call: reads kind (where the form asks it), layout and n.  nullptr: the call is taken.
+inline const char* maskfilter_form_refusal(const MaskfilterForm& f, const RouteCall& c, int64_t count, bool ask_kind) {
+    if (ask_kind && c.kind != ZAFX_MASKFILTER && c.kind != ZAFX_MASKFILTER_REST) return f.wrong_kind;
+    if (f.wrong_layout && c.layout != ZAFX_LAYOUT_TF) return f.wrong_layout;
+    if (f.wrong_count && (count < f.count_min || count > f.count_max)) return f.wrong_count;
+    if (c.n >= f.bound(count)) return f.too_long[f.halved(count)];
     return nullptr;
 }
-// zafx_execute_masked_stems_ragged: the kind, the layout and the stem count as above, then every clip's length against the clip bound.
+inline const char* maskfilter_form_refusal(const MaskfilterForm& f, const RouteCall& c, int64_t count) { return maskfilter_form_refusal(f, c, count, f.equal_asks_kind); }
+// The ragged call: the kind, the layout and the count as above, then every clip's length against the bound, before anything is read.
 // nullptr: the call is taken; otherwise *clip is the index of the clip refused, or -1 where the refusal is none of a clip's.
+inline const char* maskfilter_form_ragged_refusal(const MaskfilterForm& f, int kind, int layout, int64_t count, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
+    *clip = -1;
+    RouteCall c;
+    c.kind = kind, c.layout = layout;
+    if (const char* why = maskfilter_form_refusal(f, c, count, true)) return why;
+    for (int64_t i = 0; i < n_clips; ++i)
+        if (lengths[i] >= f.bound(count)) {
+            *clip = i;
+            return f.clip_too_long[f.halved(count)];
+        }
+    return nullptr;
+}
+
+// The names the launchers, the entry points and tests/host_emu reach for: each a call onto its kind's record.
+inline bool maskfilter_clip_refused(const RouteCall& c) { return c.n >= kMaskfilterReal.bound(0); }   // (samples; the clip's mask then stays below 2^31 bytes)
+inline const char* maskfilter_stems_refusal(const RouteCall& c, int64_t n_stems) { return maskfilter_form_refusal(kMaskfilterStems, c, n_stems); }
 inline const char* maskfilter_stems_ragged_refusal(int kind, int layout, int64_t n_stems, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
-    *clip = -1;
-    if (kind != ZAFX_MASKFILTER && kind != ZAFX_MASKFILTER_REST) return "mask filter stems: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only";
-    RouteCall c;
-    c.kind = kind, c.layout = layout;
-    if (const char* why = maskfilter_stems_refusal(c, n_stems)) return why;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        c.n = lengths[i];
-        if (maskfilter_clip_refused(c)) {
-            *clip = i;
-            return "mask filter stems: a clip has 2^28 samples or more (not supported)";
-        }
-    }
-    return nullptr;
+    return maskfilter_form_ragged_refusal(kMaskfilterStems, kind, layout, n_stems, lengths, n_clips, clip);
 }
-// zafx_execute_masked_complex: complex64 masks in ZAFX_LAYOUT_TF only (the FT stage in LDS would double: 148 KB at W = 2048 beside the
-// frames), and clips below 2^27 samples: a clip's mask -- 8 bytes a bin, T (W/2 + 1) bins -- lies behind one buffer descriptor with signed
-// 32-bit byte offsets.  Reads kind, layout and n.  nullptr: the call is taken.
-constexpr int64_t kMaskfilterComplexMaxSamples = 1LL << 27;
-// bytes of the compact TF complex64 mask of a clip of n samples
-constexpr int64_t maskfilter_complex_mask_bytes(int64_t n, int W) { return ((n + W / 2 - 1) / (W / 2) + 1) * (W / 2 + 1) * 8; }
-static_assert(maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 256) < (1LL << 31) &&
-                  maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 512) < (1LL << 31) &&
-                  maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 1024) < (1LL << 31) &&
-                  maskfilter_complex_mask_bytes(kMaskfilterComplexMaxSamples - 1, 2048) < (1LL << 31),
-              "complex mask filter: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
-inline bool maskfilter_complex_clip_refused(const RouteCall& c) { return c.n >= kMaskfilterComplexMaxSamples; }
-inline const char* maskfilter_complex_refusal(const RouteCall& c) {
-    if (c.kind != ZAFX_MASKFILTER && c.kind != ZAFX_MASKFILTER_REST) return "complex mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only";
-    if (c.layout != ZAFX_LAYOUT_TF) return "complex mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)";
-    if (maskfilter_complex_clip_refused(c)) return "complex mask filter: clips of 2^27 samples and more are not supported";
-    return nullptr;
-}
-// zafx_execute_masked_complex_ragged: the kind and the layout as above, then every clip's length against the bound, before anything is read.
-// nullptr: the call is taken; otherwise *clip is the index of the clip refused, or -1 where the refusal is none of a clip's.
+constexpr int64_t kMaskfilterComplexMaxSamples = kMaskfilterComplex.max_units;
+constexpr int64_t maskfilter_complex_mask_bytes(int64_t n, int W) { return maskfilter_mask_bytes(kMaskfilterComplex, n, W, 0); }
+inline bool maskfilter_complex_clip_refused(const RouteCall& c) { return c.n >= kMaskfilterComplex.bound(0); }
+inline const char* maskfilter_complex_refusal(const RouteCall& c) { return maskfilter_form_refusal(kMaskfilterComplex, c, 0); }
 inline const char* maskfilter_complex_ragged_refusal(int kind, int layout, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
-    *clip = -1;
-    RouteCall c;
-    c.kind = kind, c.layout = layout;
-    if (const char* why = maskfilter_complex_refusal(c)) return why;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        c.n = lengths[i];
-        if (maskfilter_complex_clip_refused(c)) {
-            *clip = i;
-            return "complex mask filter: a clip has 2^27 samples or more (not supported)";
-        }
-    }
-    return nullptr;
+    return maskfilter_form_ragged_refusal(kMaskfilterComplex, kind, layout, 0, lengths, n_clips, clip);
 }
-// zafx_execute_masked_stereo: interleaved stereo clips under one real mask for both channels (mask_channels 1) or one per channel (2), masks
-// in ZAFX_LAYOUT_TF only (the kernel is k_center's walk: no FT stage in its LDS).  The samples lie behind one descriptor of 8 N bytes:
-// N < 2^28 sample frames; two masks per frame are 8 T (W/2 + 1) bytes -- the complex kind's arithmetic --: N < 2^27 then.  Reads kind,
-// layout and n.  nullptr: the call is taken.
-constexpr int64_t maskfilter_stereo_max_frames(int64_t mask_channels) { return mask_channels == 2 ? 1LL << 27 : 1LL << 28; }
-// bytes of the compact TF float32 mask(s) of a clip of n sample frames: T frames of mask_channels rows of W/2 + 1 bins
-constexpr int64_t maskfilter_stereo_mask_bytes(int64_t n, int W, int64_t mask_channels) { return ((n + W / 2 - 1) / (W / 2) + 1) * mask_channels * (W / 2 + 1) * 4; }
-static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 256, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 256, 2) < (1LL << 31),
-              "stereo mask filter, W = 256: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
-static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 512, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 512, 2) < (1LL << 31),
-              "stereo mask filter, W = 512: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
-static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 1024, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 1024, 2) < (1LL << 31),
-              "stereo mask filter, W = 1024: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
-static_assert(maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(1) - 1, 2048, 1) < (1LL << 31) && maskfilter_stereo_mask_bytes(maskfilter_stereo_max_frames(2) - 1, 2048, 2) < (1LL << 31),
-              "stereo mask filter, W = 2048: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+constexpr int64_t maskfilter_stereo_max_frames(int64_t mask_channels) { return kMaskfilterStereo.bound(mask_channels); }
+constexpr int64_t maskfilter_stereo_mask_bytes(int64_t n, int W, int64_t mask_channels) { return maskfilter_mask_bytes(kMaskfilterStereo, n, W, mask_channels); }
 constexpr const char* kMaskfilterStereoKernel = "k_maskfilter_stereo";                 // zafx_execute_masked_stereo
 constexpr const char* kMaskfilterStereoRaggedKernel = "k_maskfilter_stereo_ragged";   // zafx_execute_masked_stereo_ragged
-inline bool maskfilter_stereo_clip_refused(const RouteCall& c, int64_t mask_channels) { return c.n >= maskfilter_stereo_max_frames(mask_channels); }
-inline const char* maskfilter_stereo_refusal(const RouteCall& c, int64_t mask_channels) {
-    if (c.kind != ZAFX_MASKFILTER && c.kind != ZAFX_MASKFILTER_REST) return "stereo mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only";
-    if (c.layout != ZAFX_LAYOUT_TF) return "stereo mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)";
-    if (mask_channels != 1 && mask_channels != 2) return "stereo mask filter: mask_channels must be 1 (one mask for both channels) or 2 (one per channel)";
-    if (maskfilter_stereo_clip_refused(c, mask_channels))
-        return mask_channels == 2 ? "stereo mask filter: with a mask per channel clips of 2^27 sample frames and more are not supported"
-                                  : "stereo mask filter: clips of 2^28 sample frames and more are not supported";
-    return nullptr;
-}
-// zafx_execute_masked_stereo_ragged: the kind, the layout and mask_channels as above, then every clip's length against the bound, before
-// anything is read.  nullptr: the call is taken; otherwise *clip is the index of the clip refused, or -1 where the refusal is none of a clip's.
+inline bool maskfilter_stereo_clip_refused(const RouteCall& c, int64_t mask_channels) { return c.n >= kMaskfilterStereo.bound(mask_channels); }
+inline const char* maskfilter_stereo_refusal(const RouteCall& c, int64_t mask_channels) { return maskfilter_form_refusal(kMaskfilterStereo, c, mask_channels); }
 inline const char* maskfilter_stereo_ragged_refusal(int kind, int layout, int64_t mask_channels, const int64_t* lengths, int64_t n_clips, int64_t* clip) {
-    *clip = -1;
-    RouteCall c;
-    c.kind = kind, c.layout = layout;
-    if (const char* why = maskfilter_stereo_refusal(c, mask_channels)) return why;
-    for (int64_t i = 0; i < n_clips; ++i) {
-        c.n = lengths[i];
-        if (maskfilter_stereo_clip_refused(c, mask_channels)) {
-            *clip = i;
-            return mask_channels == 2 ? "stereo mask filter: with a mask per channel a clip has 2^27 sample frames or more (not supported)"
-                                      : "stereo mask filter: a clip has 2^28 sample frames or more (not supported)";
-        }
-    }
-    return nullptr;
+    return maskfilter_form_ragged_refusal(kMaskfilterStereo, kind, layout, mask_channels, lengths, n_clips, clip);
 }
 
 // ---------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 Layering: Python host code -> ctypes -> libzafx.so (C-ABI, include/zafx.h)
 -> hand-written HIP kernels.  No PyTorch, no CPU fallback.
 """
+import collections
 import ctypes
 import threading
 import weakref
@@ -300,6 +301,123 @@ def _line_elements(dtype):
     return 128 // np.dtype(dtype).itemsize
 
 
+class _MaskedForm(collections.namedtuple("_MaskedForm", (
+        "suffix mask_dtype tf_only count_name count_range unit_bytes stems_out per_clip_bound units masks shape_call for_what "
+        "equal_sizes_need_tf ragged_sizes_need_tf mask_shape out_shape as_masks batch_count ragged_count_first ragged_count batch_words"))):
+    """What the four kinds of the mask filter -- real masks, stems, complex masks, interleaved stereo -- differ in on this side of the library
+    (zafx_routes.hpp MaskfilterForm and zafx_capi.cpp kMaskedForms hold the other two thirds):
+      suffix         of the method, function and entry-point names ("", "_stems", "_complex", "_stereo")
+      mask_dtype     of the device's mask array; tf_only: the device reads "TF" masks only ("FT" ones are transposed on the host)
+      count_name     the extra argument (None: the kind has none) and count_range, the values the library takes
+      unit_bytes     of what a length or a sample offset counts: 4 (samples), 8 (sample frames)
+      stems_out      a clip's output is `count` blocks (+ 1 with rest) instead of 1 (+ 1)
+      per_clip_bound count -> the clip length from which the range checks step aside and leave the refusal to the library (None: never)
+      units, masks, shape_call, for_what: the messages' words
+      equal_sizes_need_tf, ragged_sizes_need_tf: the size checks of the Plan methods step aside for a plan in "FT" (kept as they grew:
+                     the complex kind both, the stereo kind for ragged batches only, the stems never)
+      mask_shape, out_shape: (plan, n_clips, n_in, count) -> the shapes of the equal-length device arrays
+      as_masks       the host masks of a *_batch call as an array
+      batch_count    the *_batch masks -> count, or the ValueError of masks it cannot be read from
+      ragged_count_first / ragged_count: the same for a sequence of masks, asked before / after the masks are looked at one by one
+      batch_words    (what a ragged batch of masks is called, what its items are called; the latter a function of the count)."""
+    __slots__ = ()
+
+    def mask_blocks(self, count):
+        """Masks of T x (W/2 + 1) a clip brings."""
+        return count if self.count_name else 1
+
+    def out_blocks(self, count, rest):
+        return (count if self.stems_out else 1) + (1 if rest else 0)
+
+    def count_ok(self, count):
+        return self.count_name is None or self.count_range[0] <= count <= self.count_range[1]
+
+    def tf_shape(self, count, frames, rows):
+        """One clip's masks as the device reads them in "TF"."""
+        if self.stems_out:
+            return (count, frames, rows)
+        return (frames, count, rows) if self.count_name and count == 2 else (frames, rows)
+
+    def ft_axes(self, count):
+        """The transposition that takes one clip's "FT" host masks, the reference's order, to tf_shape."""
+        if self.stems_out:
+            return (0, 2, 1)
+        return (2, 0, 1) if self.count_name and count == 2 else (1, 0)
+
+    def host_shape(self, count, frames, rows, ft):
+        tf = self.tf_shape(count, frames, rows)
+        return tuple(tf[self.ft_axes(count).index(i)] for i in range(len(tf))) if ft else tf
+
+
+def _stems_of(shape_text):
+    def count(n_stems):
+        if not 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:
+            raise ValueError(f"the number of stems, {shape_text}, must be in 1 .. {_lib.MASKFILTER_MAX_STEMS}, got {n_stems}")
+        return n_stems
+    return count
+
+
+def _stems_batch_count(m):
+    if m.ndim != 4:
+        raise ValueError(f"masks must be 4-D, (clips, stems, ...), got shape {m.shape}")
+    return _stems_of("masks.shape[1]")(m.shape[1])
+
+
+def _stereo_mask_channels(ndim, shared_ndim, what):
+    """1 for masks of `shared_ndim` dimensions (one mask for both channels), 2 for one more (one per channel); anything else raises."""
+    if ndim not in (shared_ndim, shared_ndim + 1):
+        raise ValueError(f"{what} must be {shared_ndim}-D (one mask for both channels) or {shared_ndim + 1}-D (one per channel), got {ndim} dimensions")
+    return 1 if ndim == shared_ndim else 2
+
+
+def _stereo_batch_count(m):
+    if m.dtype.kind not in "biuf":
+        raise ValueError(f"masks must be real numbers, got dtype {m.dtype}")
+    return _stereo_mask_channels(m.ndim, 3, "masks")
+
+
+def _stereo_ragged_count(masks):
+    if isinstance(masks, np.ndarray) and masks.dtype != object:
+        raise ValueError("a ragged stereo mask batch is a sequence of 2-D or 3-D masks, not one array")
+    try:
+        masks = list(masks)
+    except TypeError:
+        raise ValueError("a ragged stereo mask batch is a sequence of 2-D or 3-D masks") from None
+    return masks, (_stereo_mask_channels(np.ndim(masks[0]), 2, "mask 0") if masks else 1)
+
+
+def _as_complex_masks(masks):
+    """The masks of the complex mask filter as an array: real or complex numbers (cast to complex64 at the upload); anything else raises."""
+    m = np.asarray(masks)
+    if m.dtype.kind not in "biufc":
+        raise ValueError(f"masks must be real or complex numbers, got dtype {m.dtype}")
+    return m
+
+
+_MASKED_REAL = _MaskedForm(
+    "", np.dtype(np.float32), False, None, None, 4, False, None, "samples", "a float32 mask", "mask_shape(n_clips, n_in)", "these clips", False, False,
+    lambda p, b, n, c: p.mask_shape(b, n), lambda p, b, n, c: p.out_shape(b, n), np.asarray, None, None, None, ("ragged mask batch", lambda c: "2-D masks"))
+_MASKED_STEMS = _MaskedForm(
+    "_stems", np.dtype(np.float32), True, "n_stems", (1, _lib.MASKFILTER_MAX_STEMS), 4, True, lambda c: 1 << 28, "samples", "float32 masks",
+    "stems_mask_shape(n_clips, n_in, n_stems)", "these clips and stems", False, False,
+    lambda p, b, n, c: p.stems_mask_shape(b, n, c), lambda p, b, n, c: p.stems_out_shape(b, n, c), np.asarray, _stems_batch_count, None,
+    lambda arrays: _stems_of("masks[0].shape[0]")(arrays[0].shape[0] if arrays else 1), ("ragged stems mask batch", lambda c: "3-D masks, (stems, ...)"))
+_MASKED_COMPLEX = _MaskedForm(
+    "_complex", np.dtype(np.complex64), True, None, None, 4, False, lambda c: 1 << 27, "samples", "a complex64 mask", "mask_shape(n_clips, n_in)", "these clips",
+    True, True, lambda p, b, n, c: p.mask_shape(b, n), lambda p, b, n, c: p.out_shape(b, n), _as_complex_masks, None, None, None,
+    ("ragged mask batch", lambda c: "2-D masks"))
+_MASKED_STEREO = _MaskedForm(
+    "_stereo", np.dtype(np.float32), True, "mask_channels", (1, 2), 8, False, lambda c: 1 << (29 - c), "sample frames", "float32 masks",
+    "stereo_mask_shape(n_clips, n_in, mask_channels)", "these clips", False, True,
+    lambda p, b, n, c: p.stereo_mask_shape(b, n, c), lambda p, b, n, c: p.stereo_out_shape(b, n), np.asarray, _stereo_batch_count, _stereo_ragged_count, None,
+    ("ragged stereo mask batch", lambda c: f"{1 + c}-D masks"))
+
+
+def _check_masked_dtypes(form, name, d_in, d_mask, d_out):
+    if d_in.dtype != np.float32 or d_mask.dtype != form.mask_dtype or d_out.dtype != np.float32:
+        raise ValueError(f"{name} takes float32 {form.units}, {form.masks} and a float32 output buffer")
+
+
 class Plan:
     """One transform kind bound to one device and one HIP stream (zafx_plan)."""
 
@@ -419,29 +537,30 @@ class Plan:
         """Enqueue the mask filter on the plan's stream (asynchronous; zafx_execute_masked, mask filter plans only; last_kernel: k_maskfilter):
         d_in (clips, n_in) float32 samples, d_mask float32 of mask_shape(n_clips, n_in), d_out of out_shape(n_clips, n_in).  Buffers of another
         dtype or too small for these clips raise ValueError before anything is enqueued."""
-        n_clips, n_in = int(n_clips), int(n_in)
-        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST)   # (another kind: the library says so)
-        self._check_masked("execute_masked", "a float32 mask", "mask_shape(n_clips, n_in)", "these clips", d_in, d_mask, d_out, n_clips, n_in,
-                           ok and (lambda: (self.mask_shape(n_clips, n_in), self.out_shape(n_clips, n_in))))
-        _lib.check(_lib.load().zafx_execute_masked(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked")
+        self._execute_masked(_MASKED_REAL, d_in, d_mask, d_out, n_clips, n_in)
 
-    def _check_masked(self, name, masks, shape_call, for_what, d_in, d_mask, d_out, n_clips, n_in, shapes, mask_dtype=np.float32):
-        """execute_masked / execute_masked_stems / execute_masked_complex: the checks of the three buffers.  `shapes`: false where the library
-        itself refuses the call, else a function giving the shapes of the masks and of the output; `name`, `masks`, `shape_call`, `for_what`:
-        the messages' words; mask_dtype: the masks' (complex64 for execute_masked_complex)."""
-        mask_dtype = np.dtype(mask_dtype)
-        if d_in.dtype != np.float32 or d_mask.dtype != mask_dtype or d_out.dtype != np.float32:
-            raise ValueError(f"{name} takes float32 samples, {masks} and a float32 output buffer")
+    def _execute_masked(self, form, d_in, d_mask, d_out, n_clips, n_in, count=None):
+        """The equal-length entry point of a kind behind _check_masked."""
+        n_clips, n_in, tail = int(n_clips), int(n_in), () if count is None else (int(count),)
+        self._check_masked(form, d_in, d_mask, d_out, n_clips, n_in, *tail)
+        entry = "zafx_execute_masked" + form.suffix
+        _lib.check(getattr(_lib.load(), entry)(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, *tail), entry)
+
+    def _check_masked(self, form, d_in, d_mask, d_out, n_clips, n_in, count=None):
+        """The checks of the three buffers of an equal-length call of `form`, before anything is enqueued."""
+        name = "execute_masked" + form.suffix
+        _check_masked_dtypes(form, name, d_in, d_mask, d_out)
         if n_clips < 0 or n_in < 0:
             raise ValueError("n_clips and n_in must not be negative")
-        if shapes:
-            mask_shape, out_shape = shapes()
-            if d_in.nbytes < n_clips * n_in * 4:
-                raise ValueError("d_in holds fewer than clips x n_in samples")
-            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * mask_dtype.itemsize:
-                raise ValueError(f"d_mask must hold {shape_call} = {mask_shape} {mask_dtype.name}, got {d_mask.nbytes} bytes")
+        # (another kind, count or -- where the shapes depend on it -- layout: the library says so)
+        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and form.count_ok(count) and not (form.equal_sizes_need_tf and self.layout != _lib.LAYOUT_TF):
+            mask_shape, out_shape = form.mask_shape(self, n_clips, n_in, count), form.out_shape(self, n_clips, n_in, count)
+            if d_in.nbytes < n_clips * n_in * form.unit_bytes:
+                raise ValueError(f"d_in holds fewer than clips x n_in {form.units}")
+            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * form.mask_dtype.itemsize:
+                raise ValueError(f"d_mask must hold {form.shape_call} = {mask_shape} {form.mask_dtype.name}, got {d_mask.nbytes} bytes")
             if d_out.nbytes < int(np.prod(out_shape, dtype=np.int64)) * 4:
-                raise ValueError(f"d_out is smaller than the plan's output for {for_what}")
+                raise ValueError(f"d_out is smaller than the plan's output for {form.for_what}")
 
     def stems_mask_shape(self, n_clips, n_in, n_stems):
         """Shape of the float32 device array execute_masked_stems() reads its masks from: (clips, stems, frames, W/2 + 1) compact -- a clip's
@@ -460,11 +579,7 @@ class Plan:
         samples, d_mask float32 of stems_mask_shape(n_clips, n_in, n_stems), d_out of stems_out_shape(n_clips, n_in, n_stems).  Stem s of a clip
         has the bits execute_masked gives that clip with mask s alone.  Buffers of another dtype or of the wrong size raise ValueError before
         anything is enqueued."""
-        n_clips, n_in, n_stems = int(n_clips), int(n_in), int(n_stems)
-        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS   # (otherwise: the library says so)
-        self._check_masked("execute_masked_stems", "float32 masks", "stems_mask_shape(n_clips, n_in, n_stems)", "these clips and stems", d_in, d_mask, d_out,
-                           n_clips, n_in, ok and (lambda: (self.stems_mask_shape(n_clips, n_in, n_stems), self.stems_out_shape(n_clips, n_in, n_stems))))
-        _lib.check(_lib.load().zafx_execute_masked_stems(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, n_stems), "zafx_execute_masked_stems")
+        self._execute_masked(_MASKED_STEMS, d_in, d_mask, d_out, n_clips, n_in, n_stems)
 
     def execute_masked_complex(self, d_in, d_mask, d_out, n_clips, n_in):
         """Enqueue the mask filter under complex masks on the plan's stream (asynchronous; zafx_execute_masked_complex, mask filter plans of
@@ -472,11 +587,7 @@ class Plan:
         float32 samples, d_mask complex64 of mask_shape(n_clips, n_in) = (clips, frames, W/2 + 1), d_out of out_shape(n_clips, n_in).  The
         imaginary parts of mask rows 0 and W/2 have no effect.  Buffers of another dtype or too small for these clips raise ValueError before
         anything is enqueued."""
-        n_clips, n_in = int(n_clips), int(n_in)
-        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and self.layout == _lib.LAYOUT_TF   # (otherwise: the library says so)
-        self._check_masked("execute_masked_complex", "a complex64 mask", "mask_shape(n_clips, n_in)", "these clips", d_in, d_mask, d_out, n_clips, n_in,
-                           ok and (lambda: (self.mask_shape(n_clips, n_in), self.out_shape(n_clips, n_in))), mask_dtype=np.complex64)
-        _lib.check(_lib.load().zafx_execute_masked_complex(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in), "zafx_execute_masked_complex")
+        self._execute_masked(_MASKED_COMPLEX, d_in, d_mask, d_out, n_clips, n_in)
 
     def stereo_mask_shape(self, n_clips, n_in, mask_channels):
         """Shape of the float32 device array execute_masked_stereo() reads its masks from, compact: (clips, frames, W/2 + 1) for one mask for
@@ -494,30 +605,20 @@ class Plan:
         of layout "TF" only; last_kernel: k_maskfilter_stereo): d_in (clips, n_in, 2) float32 sample frames, d_mask float32 of
         stereo_mask_shape(n_clips, n_in, mask_channels), d_out of stereo_out_shape(n_clips, n_in).  mask_channels 1: one mask for both
         channels; 2: one per channel.  Buffers of another dtype or of the wrong size raise ValueError before anything is enqueued."""
-        n_clips, n_in, mask_channels = int(n_clips), int(n_in), int(mask_channels)
-        if d_in.dtype != np.float32 or d_mask.dtype != np.float32 or d_out.dtype != np.float32:
-            raise ValueError("execute_masked_stereo takes float32 sample frames, float32 masks and a float32 output buffer")
-        if n_clips < 0 or n_in < 0:
-            raise ValueError("n_clips and n_in must not be negative")
-        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and mask_channels in (1, 2):   # (otherwise: the library says so)
-            mask_shape, out_shape = self.stereo_mask_shape(n_clips, n_in, mask_channels), self.stereo_out_shape(n_clips, n_in)
-            if d_in.nbytes < n_clips * n_in * 8:
-                raise ValueError("d_in holds fewer than clips x n_in sample frames")
-            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * 4:
-                raise ValueError(f"d_mask must hold stereo_mask_shape(n_clips, n_in, mask_channels) = {mask_shape} float32, got {d_mask.nbytes} bytes")
-            if d_out.nbytes < int(np.prod(out_shape, dtype=np.int64)) * 4:
-                raise ValueError("d_out is smaller than the plan's output for these clips")
-        _lib.check(_lib.load().zafx_execute_masked_stereo(self.handle, d_in.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, mask_channels), "zafx_execute_masked_stereo")
+        self._execute_masked(_MASKED_STEREO, d_in, d_mask, d_out, n_clips, n_in, mask_channels)
 
     def stereo_ragged_layout(self, lengths, mask_channels):
         """Placement of a ragged stereo mask-filter batch (zafx_plan_stereo_ragged_layout, mask filter plans of layout "TF") for clips of `lengths`
         sample frames: -> (mask_offsets, out_offsets), int64 of len(lengths) + 1.  Clip i's masks, (T_i, mask_channels, W/2 + 1), start at
         float32 element mask_offsets[i] -- mask_channels x what mask_ragged_layout gives --, its output block, N_i sample frames or with rest
         two such, starts at SAMPLE FRAME out_offsets[i]; the last entries are the totals."""
+        return self._masked_ragged_layout(_MASKED_STEREO, lengths, mask_channels)
+
+    def _masked_ragged_layout(self, form, lengths, count):
         lengths = _as_lengths(lengths)
         mask_offs, out_offs = np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths) + 1, np.int64)
-        _lib.check(_lib.load().zafx_plan_stereo_ragged_layout(self.handle, _i64p(lengths), len(lengths), int(mask_channels), _i64p(mask_offs), _i64p(out_offs)),
-                   "zafx_plan_stereo_ragged_layout")
+        entry = f"zafx_plan{form.suffix}_ragged_layout"
+        _lib.check(getattr(_lib.load(), entry)(self.handle, _i64p(lengths), len(lengths), int(count), _i64p(mask_offs), _i64p(out_offs)), entry)
         return mask_offs, out_offs
 
     def execute_masked_stereo_ragged(self, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, mask_channels):
@@ -528,32 +629,7 @@ class Plan:
         mask_offsets counts float32 elements: clip i's masks, (T_i, mask_channels, W/2 + 1) compact, start at element mask_offsets[i] of d_mask
         (stereo_ragged_layout gives the compact placement; its totals may stay on).  Clip i's block has the bits execute_masked_stereo gives
         that clip and its masks alone.  Output blocks that overlap are not detected."""
-        mask_channels = int(mask_channels)
-        in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
-        out_offsets, mask_offsets = _as_int64(out_offsets, "out_offsets"), _as_int64(mask_offsets, "mask_offsets")
-        if len(mask_offsets) == len(lengths) + 1:
-            mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
-        if len(out_offsets) == len(lengths) + 1:
-            out_offsets = np.ascontiguousarray(out_offsets[:-1])
-        if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
-            raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
-        if d_in.dtype != np.float32 or d_mask.dtype != np.float32 or d_out.dtype != np.float32:
-            raise ValueError("execute_masked_stereo_ragged takes float32 sample frames, float32 masks and a float32 output buffer")
-        # (another kind or layout, another mask_channels, negative values, a clip at the bound: the library says so)
-        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and self.layout == _lib.LAYOUT_TF and mask_channels in (1, 2) and len(lengths)
-        if ok and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0 and int(lengths.max()) < 1 << (29 - mask_channels):
-            h = int(self.params.window_length) // 2
-            mask_ends = mask_offsets + mask_channels * ((lengths + h - 1) // h + 1) * (h + 1)
-            blocks = 2 if self.kind == _lib.MASKFILTER_REST else 1
-            live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
-            if int((in_offsets + lengths).max()) * 8 > d_in.nbytes:
-                raise ValueError("a clip reaches past the end of d_in")
-            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
-                raise ValueError("a clip's masks reach past the end of d_mask")
-            if int((out_offsets + blocks * lengths).max()) * 8 > d_out.nbytes:
-                raise ValueError("a clip's result reaches past the end of d_out")
-        _lib.check(_lib.load().zafx_execute_masked_stereo_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
-                                                                 d_out.ptr, _i64p(out_offsets), len(lengths), mask_channels), "zafx_execute_masked_stereo_ragged")
+        self._execute_masked_ragged(_MASKED_STEREO, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, mask_channels)
 
     def ragged_layout(self, lengths):
         """Placement of a ragged batch's results (zafx_plan_ragged_layout) for clips of `lengths` samples: -> (out_offsets, frames, pitch), int64
@@ -623,50 +699,48 @@ class Plan:
         clip i is lengths[i] samples at element in_offsets[i] of d_in, its mask (shape and pitch as in mask_ragged_layout) starts at element
         mask_offsets[i] of d_mask, its filtered samples go to element out_offsets[i] of d_out and, for a plan with rest, the rest directly
         behind.  mask_offsets may carry the total mask_ragged_layout appends.  Output blocks that overlap are not detected."""
-        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args("execute_masked_ragged", None, d_in, in_offsets, lengths, d_mask, mask_offsets,
-                                                                                  d_out, out_offsets)
-        _lib.check(_lib.load().zafx_execute_masked_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
-                                                          d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_ragged")
+        self._execute_masked_ragged(_MASKED_REAL, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets)
 
-    def _masked_ragged_args(self, name, n_stems, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, complex_mask=False):
-        """execute_masked_ragged (n_stems None) / execute_masked_stems_ragged / execute_masked_complex_ragged (n_stems None, complex_mask: the mask
-        array is complex64 and mask_offsets count its elements): the per-clip arrays as int64 without the totals the layout calls append, and
-        the checks of the three buffers -> (in_offsets, lengths, mask_offsets, out_offsets).  `name`: the method in the messages."""
-        stems = n_stems is not None
-        mask_dtype = np.dtype(np.complex64 if complex_mask else np.float32)
+    def _execute_masked_ragged(self, form, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, count=None):
+        """The ragged entry point of a kind behind _masked_ragged_args."""
+        tail = () if count is None else (int(count),)
+        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args(form, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, *tail)
+        entry = f"zafx_execute_masked{form.suffix}_ragged"
+        _lib.check(getattr(_lib.load(), entry)(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets), d_out.ptr, _i64p(out_offsets),
+                                               len(lengths), *tail), entry)
+
+    def _masked_ragged_args(self, form, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, count=None):
+        """A ragged call of `form`: the per-clip arrays as int64 without the totals the layout calls append (out_offsets: of the kinds that have
+        a layout call giving them), and the checks of the three buffers -> (in_offsets, lengths, mask_offsets, out_offsets).  mask_offsets count
+        elements of the form's mask dtype, the other three what the form's lengths count."""
         in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
         out_offsets, mask_offsets = _as_int64(out_offsets, "out_offsets"), _as_int64(mask_offsets, "mask_offsets")
         if len(mask_offsets) == len(lengths) + 1:
             mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
-        if stems and len(out_offsets) == len(lengths) + 1:
+        if form.count_name and len(out_offsets) == len(lengths) + 1:
             out_offsets = np.ascontiguousarray(out_offsets[:-1])
         if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
             raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
-        if d_in.dtype != np.float32 or d_mask.dtype != mask_dtype or d_out.dtype != np.float32:
-            raise ValueError(f"{name} takes float32 samples, {'float32 masks' if stems else f'a {mask_dtype.name} mask'} and a float32 output buffer")
-        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and len(lengths)   # (another kind, negative values: the library says so)
-        if stems:   # (... as it does of a stem count or a clip it refuses)
-            ok = ok and 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS
-        if complex_mask:   # (... or of a plan in "FT")
-            ok = ok and self.layout == _lib.LAYOUT_TF
+        _check_masked_dtypes(form, f"execute_masked{form.suffix}_ragged", d_in, d_mask, d_out)
+        # (another kind or count, negative values, a clip the library refuses, a plan in "FT" where the form asks here: the library says so)
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and len(lengths) and form.count_ok(count)
+        ok = ok and not (form.ragged_sizes_need_tf and self.layout != _lib.LAYOUT_TF)
         if ok and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0 and not (
-                stems and int(lengths.max()) >= 1 << 28) and not (complex_mask and int(lengths.max()) >= 1 << 27):
+                form.per_clip_bound and int(lengths.max()) >= form.per_clip_bound(count)):
             h = int(self.params.window_length) // 2
             frames = (lengths + h - 1) // h + 1
-            if stems:   # compact "TF" masks back to back
-                mask_ends = mask_offsets + n_stems * frames * (h + 1)
-            elif self.layout == _lib.LAYOUT_FT:   # the last element the kernel may read: row H, the clip's last frame
+            if self.layout == _lib.LAYOUT_FT and not form.tf_only:   # the last element the kernel may read: row H, the clip's last frame
                 a = max(self.row_align, 1)
                 mask_ends = mask_offsets + h * ((frames + a - 1) // a * a) + frames
-            else:
-                mask_ends = mask_offsets + frames * (h + 1)
-            blocks = (n_stems if stems else 1) + (1 if self.kind == _lib.MASKFILTER_REST else 0)
+            else:   # compact "TF" masks back to back
+                mask_ends = mask_offsets + form.mask_blocks(count) * frames * (h + 1)
+            blocks = form.out_blocks(count, self.kind == _lib.MASKFILTER_REST)
             live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
-            if int((in_offsets + lengths).max()) * 4 > d_in.nbytes:
+            if int((in_offsets + lengths).max()) * form.unit_bytes > d_in.nbytes:
                 raise ValueError("a clip reaches past the end of d_in")
-            if live.any() and int(mask_ends[live].max()) * mask_dtype.itemsize > d_mask.nbytes:
-                raise ValueError(f"a clip's {'masks reach' if stems else 'mask reaches'} past the end of d_mask")
-            if int((out_offsets + blocks * lengths).max()) * 4 > d_out.nbytes:
+            if live.any() and int(mask_ends[live].max()) * form.mask_dtype.itemsize > d_mask.nbytes:
+                raise ValueError(f"a clip's {'masks reach' if form.count_name else 'mask reaches'} past the end of d_mask")
+            if int((out_offsets + blocks * lengths).max()) * form.unit_bytes > d_out.nbytes:
                 raise ValueError("a clip's result reaches past the end of d_out")
         return in_offsets, lengths, mask_offsets, out_offsets
 
@@ -677,21 +751,14 @@ class Plan:
         (T_i, W/2 + 1) compact, starts at complex element mask_offsets[i] of d_mask (mask_ragged_layout gives the compact placement; its total
         may stay on).  Clip i's block has the bits execute_masked_complex gives that clip and mask alone.  Output blocks that overlap are not
         detected."""
-        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args("execute_masked_complex_ragged", None, d_in, in_offsets, lengths, d_mask,
-                                                                                  mask_offsets, d_out, out_offsets, complex_mask=True)
-        _lib.check(_lib.load().zafx_execute_masked_complex_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
-                                                                  d_out.ptr, _i64p(out_offsets), len(lengths)), "zafx_execute_masked_complex_ragged")
+        self._execute_masked_ragged(_MASKED_COMPLEX, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets)
 
     def stems_ragged_layout(self, lengths, n_stems):
         """Placement of a ragged stems batch (zafx_plan_stems_ragged_layout, mask filter plans of layout "TF") for clips of `lengths` samples
         with n_stems masks each: -> (mask_offsets, out_offsets), int64 of len(lengths) + 1, in float32 elements.  Clip i's masks lie back to
         back as (n_stems, T_i, W/2 + 1) from element mask_offsets[i] -- n_stems x what mask_ragged_layout gives --, its output block,
         (n_stems, N_i) or with rest (n_stems + 1, N_i), starts at element out_offsets[i]; the last entries are the totals."""
-        lengths = _as_lengths(lengths)
-        mask_offs, out_offs = np.zeros(len(lengths) + 1, np.int64), np.zeros(len(lengths) + 1, np.int64)
-        _lib.check(_lib.load().zafx_plan_stems_ragged_layout(self.handle, _i64p(lengths), len(lengths), int(n_stems), _i64p(mask_offs), _i64p(out_offs)),
-                   "zafx_plan_stems_ragged_layout")
-        return mask_offs, out_offs
+        return self._masked_ragged_layout(_MASKED_STEMS, lengths, n_stems)
 
     def execute_masked_stems_ragged(self, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems):
         """Enqueue the mask filter with n_stems masks per clip for mono clips of different lengths as one launch on the plan's stream
@@ -701,11 +768,7 @@ class Plan:
         (n_stems + 1, N_i) -- starts at element out_offsets[i] of d_out; any placement will do (stems_ragged_layout: the compact one, whose
         arrays with their totals are accepted as they are).  Clip i's block has the bits execute_masked_stems gives that clip and its masks
         alone.  Output blocks that overlap are not detected."""
-        n_stems = int(n_stems)
-        in_offsets, lengths, mask_offsets, out_offsets = self._masked_ragged_args("execute_masked_stems_ragged", n_stems, d_in, in_offsets, lengths, d_mask,
-                                                                                  mask_offsets, d_out, out_offsets)
-        _lib.check(_lib.load().zafx_execute_masked_stems_ragged(self.handle, d_in.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets),
-                                                                d_out.ptr, _i64p(out_offsets), len(lengths), n_stems), "zafx_execute_masked_stems_ragged")
+        self._execute_masked_ragged(_MASKED_STEMS, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems)
 
     def execute_imdct_ragged(self, d_coefs, in_offsets, frames, d_out, out_offsets):
         """Enqueue the IMDCT of coefficient blocks of different frame counts on the plan's stream (asynchronous; zafx_execute_imdct_ragged,
@@ -1450,32 +1513,49 @@ def maskfilter_batch(clips, window_function, masks, step_length=None, rest=False
     """The mask filter for a batch of mono clips in one kernel: clips (B, N) and real masks (B, W/2 + 1, T) -- (B, T, W/2 + 1) with layout "TF" --,
     T = ceil(N / (W/2)) + 1 as zaf.stft gives -> y = istft(concat(m, m[-2:0:-1]) * stft(x))[0:N] (zaf.py:185-195), float32 (B, N); with rest=True
     (y, rest = x - y), views of one (B, 2, N) result (which `out`, if given, is).  step_length: None or window_length / 2."""
+    return _maskfilter_batch(_MASKED_REAL, clips, window_function, masks, step_length, rest, layout, device, out)
+
+
+def _maskfilter_batch(form, clips, window_function, masks, step_length, rest, layout, device, out):
+    """maskfilter_batch and its stems, complex and stereo forms: the checks of clips, masks and `out` ahead of any device call, "FT" masks of a
+    kind the device reads in "TF" only transposed, the round trip, and the result split into (filtered, rest) views."""
     w = _maskfilter_window(window_function, step_length)
-    a, m = np.asarray(clips), np.asarray(masks)
-    if a.ndim != 2:
-        raise ValueError(f"clips must be mono, (clips, samples), got shape {a.shape}")
-    if np.iscomplexobj(a) or np.iscomplexobj(m):
+    a, m = np.asarray(clips), form.as_masks(masks)
+    stereo = form.unit_bytes == 8
+    if a.ndim != (3 if stereo else 2) or (stereo and a.shape[2] != 2):
+        raise ValueError(f"clips must be {'stereo, (clips, sample frames, 2)' if stereo else 'mono, (clips, samples)'}, got shape {a.shape}")
+    if form.mask_dtype.kind == "c":
+        if np.iscomplexobj(a):
+            raise ValueError("clips must be real")
+    elif np.iscomplexobj(a) or np.iscomplexobj(m):
         raise ValueError("clips and masks must be real")
-    n_clips, n = a.shape
+    count = form.batch_count(m) if form.batch_count else None
+    n_clips, n = a.shape[:2]
     h = len(w) // 2
-    frames, rows = (n + h - 1) // h + 1, h + 1
-    want = (n_clips, rows, frames) if _LAYOUTS[layout] == _lib.LAYOUT_FT else (n_clips, frames, rows)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    want = (n_clips,) + form.host_shape(count, (n + h - 1) // h + 1, h + 1, ft)
     if m.shape != want:
-        raise ValueError(f"masks must have shape {want} for clips of {n} samples (layout {layout!r}), got {m.shape}")
-    shape = (n_clips, 2, n) if rest else (n_clips, n)
+        raise ValueError(f"masks must have shape {want} for clips of {n} {form.units} (layout {layout!r}), got {m.shape}")
+    blocks = form.out_blocks(count, rest)
+    shape = (n_clips,) + ((blocks,) if form.stems_out or rest else ()) + a.shape[1:]
     if out is None:
         out = np.empty(shape, np.float32)
     elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
         raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
     if out.size:
-        plan = maskfilter_plan(w, rest, layout, device)
-        _masked_round_trip(plan, a, m, out, lambda d_in, d_mask, d_out: plan.execute_masked(d_in, d_mask, d_out, n_clips, n))
+        plan = maskfilter_plan(w, rest, "TF" if form.tf_only else layout, device)
+        if ft and form.tf_only:
+            m = m.transpose((0,) + tuple(i + 1 for i in form.ft_axes(count)))
+        tail = () if count is None else (count,)
+        _masked_round_trip(plan, a, m, out, lambda d_in, d_mask, d_out: plan._execute_masked(form, d_in, d_mask, d_out, n_clips, n, *tail), form.mask_dtype)
+    if form.stems_out:
+        return (out[:, :count], out[:, count]) if rest else out
     return (out[:, 0], out[:, 1]) if rest else out
 
 
-def _masked_round_trip(plan, clips, masks, out, execute, mask_dtype=np.float32):
-    """maskfilter_batch / maskfilter_stems_batch / maskfilter_complex_batch: clips up as float32 and masks as mask_dtype, execute(d_in, d_mask,
-    d_out) and the wait under the plan's lock, the result down into `out`."""
+def _masked_round_trip(plan, clips, masks, out, execute, mask_dtype):
+    """_maskfilter_batch: clips up as float32 and masks as mask_dtype, execute(d_in, d_mask, d_out) and the wait under the plan's lock, the
+    result down into `out`."""
     x, m = np.ascontiguousarray(clips, dtype=np.float32), np.ascontiguousarray(masks, dtype=mask_dtype)
     d_in, d_mask, d_out = (DeviceBuffer(b.shape, b.dtype, plan.device) for b in (x, m, out))
     try:
@@ -1498,42 +1578,7 @@ def maskfilter_stems_batch(clips, window_function, masks, step_length=None, rest
     of one (B, S + 1, N) result (which `out`, if given, is).  The device reads "TF" masks only: "FT" masks are transposed on the host before
     the upload -- one more pass over the masks in host memory, B S T (W/2 + 1) floats copied with a strided read; hand over "TF" masks where
     that matters.  step_length: None or window_length / 2."""
-    w = _maskfilter_window(window_function, step_length)
-    a, m = np.asarray(clips), np.asarray(masks)
-    if a.ndim != 2:
-        raise ValueError(f"clips must be mono, (clips, samples), got shape {a.shape}")
-    if np.iscomplexobj(a) or np.iscomplexobj(m):
-        raise ValueError("clips and masks must be real")
-    if m.ndim != 4:
-        raise ValueError(f"masks must be 4-D, (clips, stems, ...), got shape {m.shape}")
-    n_clips, n = a.shape
-    n_stems = m.shape[1]
-    if not 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:
-        raise ValueError(f"the number of stems, masks.shape[1], must be in 1 .. {_lib.MASKFILTER_MAX_STEMS}, got {n_stems}")
-    h = len(w) // 2
-    frames, rows = (n + h - 1) // h + 1, h + 1
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    want = (n_clips, n_stems, rows, frames) if ft else (n_clips, n_stems, frames, rows)
-    if m.shape != want:
-        raise ValueError(f"masks must have shape {want} for clips of {n} samples (layout {layout!r}), got {m.shape}")
-    shape = (n_clips, n_stems + 1, n) if rest else (n_clips, n_stems, n)
-    if out is None:
-        out = np.empty(shape, np.float32)
-    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
-        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
-    if out.size:
-        plan = maskfilter_plan(w, rest, "TF", device)
-        _masked_round_trip(plan, a, m.transpose(0, 1, 3, 2) if ft else m, out,
-                           lambda d_in, d_mask, d_out: plan.execute_masked_stems(d_in, d_mask, d_out, n_clips, n, n_stems))
-    return (out[:, :n_stems], out[:, n_stems]) if rest else out
-
-
-def _as_complex_masks(masks):
-    """The masks of the complex mask filter as an array: real or complex numbers (cast to complex64 at the upload); anything else raises."""
-    m = np.asarray(masks)
-    if m.dtype.kind not in "biufc":
-        raise ValueError(f"masks must be real or complex numbers, got dtype {m.dtype}")
-    return m
+    return _maskfilter_batch(_MASKED_STEMS, clips, window_function, masks, step_length, rest, layout, device, out)
 
 
 def maskfilter_complex_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
@@ -1543,36 +1588,7 @@ def maskfilter_complex_batch(clips, window_function, masks, step_length=None, re
     float32 (B, N); with rest=True (y, rest = x - y), views of one (B, 2, N) result (which `out`, if given, is).  The imaginary parts of mask
     rows 0 and W/2 have no effect.  The device reads "TF" masks only: "FT" masks are transposed on the host before the upload, as
     maskfilter_stems_batch does.  step_length: None or window_length / 2."""
-    w = _maskfilter_window(window_function, step_length)
-    a, m = np.asarray(clips), _as_complex_masks(masks)
-    if a.ndim != 2:
-        raise ValueError(f"clips must be mono, (clips, samples), got shape {a.shape}")
-    if np.iscomplexobj(a):
-        raise ValueError("clips must be real")
-    n_clips, n = a.shape
-    h = len(w) // 2
-    frames, rows = (n + h - 1) // h + 1, h + 1
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    want = (n_clips, rows, frames) if ft else (n_clips, frames, rows)
-    if m.shape != want:
-        raise ValueError(f"masks must have shape {want} for clips of {n} samples (layout {layout!r}), got {m.shape}")
-    shape = (n_clips, 2, n) if rest else (n_clips, n)
-    if out is None:
-        out = np.empty(shape, np.float32)
-    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
-        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
-    if out.size:
-        plan = maskfilter_plan(w, rest, "TF", device)
-        _masked_round_trip(plan, a, m.transpose(0, 2, 1) if ft else m, out,
-                           lambda d_in, d_mask, d_out: plan.execute_masked_complex(d_in, d_mask, d_out, n_clips, n), mask_dtype=np.complex64)
-    return (out[:, 0], out[:, 1]) if rest else out
-
-
-def _stereo_mask_channels(ndim, shared_ndim, what):
-    """1 for masks of `shared_ndim` dimensions (one mask for both channels), 2 for one more (one per channel); anything else raises."""
-    if ndim not in (shared_ndim, shared_ndim + 1):
-        raise ValueError(f"{what} must be {shared_ndim}-D (one mask for both channels) or {shared_ndim + 1}-D (one per channel), got {ndim} dimensions")
-    return 1 if ndim == shared_ndim else 2
+    return _maskfilter_batch(_MASKED_COMPLEX, clips, window_function, masks, step_length, rest, layout, device, out)
 
 
 def maskfilter_stereo_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None):
@@ -1583,35 +1599,7 @@ def maskfilter_stereo_batch(clips, window_function, masks, step_length=None, res
     frame share one transform: rounding and non-finite values of one channel reach the other channel of the same frames, never another clip.
     The device reads "TF" masks only: "FT" masks are transposed on the host before the upload, as maskfilter_stems_batch does.
     step_length: None or window_length / 2."""
-    w = _maskfilter_window(window_function, step_length)
-    a, m = np.asarray(clips), np.asarray(masks)
-    if a.ndim != 3 or a.shape[2] != 2:
-        raise ValueError(f"clips must be stereo, (clips, sample frames, 2), got shape {a.shape}")
-    if np.iscomplexobj(a) or np.iscomplexobj(m):
-        raise ValueError("clips and masks must be real")
-    if m.dtype.kind not in "biuf":
-        raise ValueError(f"masks must be real numbers, got dtype {m.dtype}")
-    mc = _stereo_mask_channels(m.ndim, 3, "masks")
-    n_clips, n = a.shape[:2]
-    h = len(w) // 2
-    frames, rows = (n + h - 1) // h + 1, h + 1
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    if mc == 1:
-        want = (n_clips, rows, frames) if ft else (n_clips, frames, rows)
-    else:
-        want = (n_clips, 2, rows, frames) if ft else (n_clips, frames, 2, rows)
-    if m.shape != want:
-        raise ValueError(f"masks must have shape {want} for clips of {n} sample frames (layout {layout!r}), got {m.shape}")
-    shape = (n_clips, 2, n, 2) if rest else (n_clips, n, 2)
-    if out is None:
-        out = np.empty(shape, np.float32)
-    elif tuple(out.shape) != shape or out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable:
-        raise ValueError(f"out must be a writeable C-contiguous float32 array of shape {shape}")
-    if out.size:
-        plan = maskfilter_plan(w, rest, "TF", device)
-        tf = m if not ft else (m.transpose(0, 2, 1) if mc == 1 else m.transpose(0, 3, 1, 2))
-        _masked_round_trip(plan, a, tf, out, lambda d_in, d_mask, d_out: plan.execute_masked_stereo(d_in, d_mask, d_out, n_clips, n, mc))
-    return (out[:, 0], out[:, 1]) if rest else out
+    return _maskfilter_batch(_MASKED_STEREO, clips, window_function, masks, step_length, rest, layout, device, out)
 
 
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
@@ -2108,14 +2096,38 @@ def centersides_ragged(clips, window_function, step_length=None, sides=True, dev
     return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
 
 
-def _ragged_mask_items(masks, lengths, window_length, ndim, batch, items, complex_ok=False):
-    """pack_ragged_masks / pack_ragged_stems_masks / pack_ragged_complex_masks (complex_ok): -> (the masks as `ndim`-D arrays, one per clip of
-    `lengths`, H = W/2, the clips' frame counts ceil(N_i / H) + 1); `batch`, `items`: the messages' words."""
+def _pack_ragged_masks(form, masks, lengths, window_length, layout, row_align=0):
+    """The four pack_ragged_*masks: the masks of a ragged batch, one item per clip of `lengths`, validated and packed as the device reads them
+    -> (packed 1-D of the form's mask dtype, mask_offsets of len(lengths) + 1, count).  Masks of a kind the device reads in "TF" only are
+    transposed here; the real kind's "FT" masks keep their rows, at the frame count rounded up to row_align."""
+    lengths = _as_lengths(lengths)
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    a = max(_as_row_align(row_align, layout), 1)
+    masks, count = form.ragged_count_first(masks) if form.ragged_count_first else (masks, None)
     h = int(window_length) // 2
-    arrays = _as_ragged_items(masks, ndim, batch, items, "mask", empty_ok=True, complex_ok=complex_ok)
+    arrays = _as_ragged_items(masks, len(form.tf_shape(count, 0, 0)), form.batch_words[0], form.batch_words[1](count), "mask", empty_ok=True,
+                              complex_ok=form.mask_dtype.kind == "c")
     if len(arrays) != len(lengths):
         raise ValueError(f"masks and lengths must have one entry per clip, got {len(arrays)} masks for {len(lengths)} clips")
-    return arrays, h, (lengths + h - 1) // h + 1
+    if form.ragged_count:
+        count = form.ragged_count(arrays)
+    frames = (lengths + h - 1) // h + 1
+    pitched = ft and not form.tf_only
+    pitch = (frames + a - 1) // a * a if pitched else frames
+    offsets = np.zeros(len(lengths) + 1, np.int64)
+    offsets[1:] = np.cumsum(form.mask_blocks(count) * pitch * (h + 1))
+    packed = np.zeros(max(int(offsets[-1]), 1), form.mask_dtype)
+    for i, (m, o, t, p) in enumerate(zip(arrays, offsets.tolist(), frames.tolist(), pitch.tolist())):
+        if form.stems_out and m.shape[0] != count:
+            raise ValueError(f"mask {i} has {m.shape[0]} stems, mask 0 has {count}: the stem count is one for the batch")
+        want = form.host_shape(count, t, h + 1, ft)
+        if m.shape != want:
+            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} {form.units} (layout {layout!r}), got {m.shape}")
+        if pitched:
+            packed[o:o + (h + 1) * p].reshape(h + 1, p)[:, :t] = m
+        else:
+            packed[o:offsets[i + 1]].reshape(form.tf_shape(count, t, h + 1))[...] = m.transpose(form.ft_axes(count)) if ft else m
+    return packed, offsets, count
 
 
 def pack_ragged_masks(masks, lengths, window_length, layout="FT", row_align=0):
@@ -2123,23 +2135,7 @@ def pack_ragged_masks(masks, lengths, window_length, layout="FT", row_align=0):
     T_i = ceil(lengths[i] / (W/2)) + 1 -> (packed 1-D, mask_offsets of len(lengths) + 1), the layout of Plan.mask_ragged_layout for a plan of
     that window_length, layout and row_align: the masks back to back, "FT" rows at the frame count rounded up to row_align (the pad columns
     are zeros).  A mask of another shape raises ValueError with the clip's index."""
-    lengths = _as_lengths(lengths)
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    a = max(_as_row_align(row_align, layout), 1)
-    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 2, "ragged mask batch", "2-D masks")
-    pitch = (frames + a - 1) // a * a if ft else np.full(len(lengths), h + 1, np.int64)
-    offsets = np.zeros(len(lengths) + 1, np.int64)
-    offsets[1:] = np.cumsum((h + 1) * pitch if ft else frames * (h + 1))
-    packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
-    for i, (m, o, t, p) in enumerate(zip(arrays, offsets.tolist(), frames.tolist(), pitch.tolist())):
-        want = (h + 1, t) if ft else (t, h + 1)
-        if m.shape != want:
-            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} samples (layout {layout!r}), got {m.shape}")
-        if ft:
-            packed[o:o + (h + 1) * p].reshape(h + 1, p)[:, :t] = m
-        else:
-            packed[o:o + t * (h + 1)] = np.ravel(m)
-    return packed, offsets
+    return _pack_ragged_masks(_MASKED_REAL, masks, lengths, window_length, layout, row_align)[:2]
 
 
 def maskfilter_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
@@ -2147,34 +2143,39 @@ def maskfilter_ragged(clips, window_function, masks, step_length=None, rest=Fals
     (T_i, W/2 + 1) with layout "TF" --, T_i = ceil(N_i / (W/2)) + 1 -> a list of float32 (N_i,) arrays, or of (y_i, rest_i) pairs with
     rest=True, each a view of the one result buffer; every clip's result has the bits maskfilter_batch gives for that clip alone.  One upload
     each of clips and masks, one launch (k_maskfilter_ragged), one download.  Window and step_length as in maskfilter_batch."""
+    return _maskfilter_ragged(_MASKED_REAL, clips, window_function, masks, step_length, rest, layout, device)
+
+
+def _maskfilter_ragged(form, clips, window_function, masks, step_length, rest, layout, device):
+    """maskfilter_ragged and its stems, complex and stereo forms: the clips packed back to back (the kernel pads every clip through a descriptor
+    of its own) and the packed masks up, one launch, the result -- the clips back to back, each with its output blocks -- down, and the
+    per-clip views of it."""
     w = _maskfilter_window(window_function, step_length)
-    arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
-    lengths = np.array([len(a) for a in arrays], np.int64)
-    m, mask_offsets = pack_ragged_masks(masks, lengths, len(w), layout)
-    plan = maskfilter_plan(w, rest, layout, device)
-    res, out_offsets = _masked_ragged_round_trip(plan, arrays, lengths, m, 2 if rest else 1, lambda d_in, in_offsets, d_mask, d_out, out_offsets:
-                                                 plan.execute_masked_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets))
-    if not rest:
-        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
-    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
-
-
-def _masked_ragged_round_trip(plan, arrays, lengths, packed_masks, blocks, execute):
-    """maskfilter_ragged / maskfilter_stems_ragged: the clips packed back to back (the kernel pads every clip through a descriptor of its own) and
-    the packed masks up, execute(d_in, in_offsets, d_mask, d_out, out_offsets), the result -- `blocks` output blocks of its length per clip,
-    the clips back to back -- down -> (result, out_offsets)."""
-    in_offsets, total = _back_to_back(lengths)
-    x = np.empty(max(total, 1), np.float32)
-    for a, o in zip(arrays, in_offsets.tolist()):
-        x[o:o + len(a)] = a
+    if form.unit_bytes == 8:
+        x, in_offsets, lengths = pack_ragged_stereo(clips)
+    else:
+        arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
+        lengths = np.array([len(a) for a in arrays], np.int64)
+        in_offsets, total = _back_to_back(lengths)
+        x = np.empty(max(total, 1), np.float32)
+        for a, o in zip(arrays, in_offsets.tolist()):
+            x[o:o + len(a)] = a
+    m, mask_offsets, count = _pack_ragged_masks(form, masks, lengths, len(w), layout)
+    plan = maskfilter_plan(w, rest, "TF" if form.tf_only else layout, device)
+    blocks = form.out_blocks(count, rest)
     out_offsets = blocks * in_offsets
-    d_mask = DeviceBuffer(packed_masks.shape, packed_masks.dtype, plan.device)
+    tail = () if count is None else (count,)
+    d_mask = DeviceBuffer(m.shape, m.dtype, plan.device)
     try:
-        d_mask.upload(packed_masks)
-        res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: execute(d_in, in_offsets, d_mask, d_out, out_offsets))
+        d_mask.upload(m)
+        res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: plan._execute_masked_ragged(form, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out,
+                                                                                                   out_offsets, *tail))
     finally:
         d_mask.free()
-    return res, out_offsets
+    out = [res[o:o + n].reshape((blocks, n // blocks) + res.shape[1:]) for o, n in zip(out_offsets.tolist(), (blocks * lengths).tolist())]
+    if form.stems_out:
+        return [(b[:count], b[count]) for b in out] if rest else out
+    return [(b[0], b[1]) for b in out] if rest else [b[0] for b in out]
 
 
 def pack_ragged_complex_masks(masks, lengths, window_length, layout="FT"):
@@ -2183,18 +2184,7 @@ def pack_ragged_complex_masks(masks, lengths, window_length, layout="FT"):
     the layout of Plan.mask_ragged_layout for a "TF" plan of that window_length: clip i's mask as (T_i, W/2 + 1) compact, the clips back to
     back.  The device reads "TF" masks only: "FT" masks are transposed here, on the host.  A mask of another shape raises ValueError with
     the clip's index."""
-    lengths = _as_lengths(lengths)
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 2, "ragged mask batch", "2-D masks", complex_ok=True)
-    offsets = np.zeros(len(lengths) + 1, np.int64)
-    offsets[1:] = np.cumsum(frames * (h + 1))
-    packed = np.zeros(max(int(offsets[-1]), 1), np.complex64)
-    for i, (m, o, t) in enumerate(zip(arrays, offsets.tolist(), frames.tolist())):
-        want = (h + 1, t) if ft else (t, h + 1)
-        if m.shape != want:
-            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} samples (layout {layout!r}), got {m.shape}")
-        packed[o:o + t * (h + 1)].reshape(t, h + 1)[...] = m.T if ft else m
-    return packed, offsets
+    return _pack_ragged_masks(_MASKED_COMPLEX, masks, lengths, window_length, layout)[:2]
 
 
 def maskfilter_complex_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
@@ -2203,16 +2193,7 @@ def maskfilter_complex_ragged(clips, window_function, masks, step_length=None, r
     pairs with rest=True, each a view of the one result buffer; every clip's result has the bits maskfilter_complex_batch gives for that clip
     alone.  One upload each of clips and masks, one launch (k_maskfilter_complex_ragged), one download.  "FT" masks are transposed on the
     host (pack_ragged_complex_masks).  Window and step_length as in maskfilter_batch."""
-    w = _maskfilter_window(window_function, step_length)
-    arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
-    lengths = np.array([len(a) for a in arrays], np.int64)
-    m, mask_offsets = pack_ragged_complex_masks(masks, lengths, len(w), layout)
-    plan = maskfilter_plan(w, rest, "TF", device)
-    res, out_offsets = _masked_ragged_round_trip(plan, arrays, lengths, m, 2 if rest else 1, lambda d_in, in_offsets, d_mask, d_out, out_offsets:
-                                                 plan.execute_masked_complex_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets))
-    if not rest:
-        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
-    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return _maskfilter_ragged(_MASKED_COMPLEX, clips, window_function, masks, step_length, rest, layout, device)
 
 
 def pack_ragged_stereo_masks(masks, lengths, window_length, layout="FT"):
@@ -2221,29 +2202,7 @@ def pack_ragged_stereo_masks(masks, lengths, window_length, layout="FT"):
     T_i = ceil(lengths[i] / (W/2)) + 1 -> (packed 1-D, mask_offsets of len(lengths) + 1, mask_channels), the layout of Plan.stereo_ragged_layout:
     clip i's masks as (T_i, mask_channels, W/2 + 1) compact, the clips back to back.  The device reads "TF" masks only: "FT" masks are
     transposed here, on the host.  A mask of another shape than the first one's kind raises ValueError with the clip's index."""
-    lengths = _as_lengths(lengths)
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    if isinstance(masks, np.ndarray) and masks.dtype != object:
-        raise ValueError("a ragged stereo mask batch is a sequence of 2-D or 3-D masks, not one array")
-    try:
-        masks = list(masks)
-    except TypeError:
-        raise ValueError("a ragged stereo mask batch is a sequence of 2-D or 3-D masks") from None
-    mc = _stereo_mask_channels(np.ndim(masks[0]), 2, "mask 0") if masks else 1
-    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 1 + mc, "ragged stereo mask batch", f"{1 + mc}-D masks")
-    offsets = np.zeros(len(lengths) + 1, np.int64)
-    offsets[1:] = np.cumsum(mc * frames * (h + 1))
-    packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
-    for i, (m, o, t) in enumerate(zip(arrays, offsets.tolist(), frames.tolist())):
-        if mc == 1:
-            want = (h + 1, t) if ft else (t, h + 1)
-        else:
-            want = (2, h + 1, t) if ft else (t, 2, h + 1)
-        if m.shape != want:
-            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} sample frames (layout {layout!r}), got {m.shape}")
-        tf = m if not ft else (m.T if mc == 1 else m.transpose(2, 0, 1))
-        packed[o:o + mc * t * (h + 1)].reshape(tf.shape)[...] = tf
-    return packed, offsets, mc
+    return _pack_ragged_masks(_MASKED_STEREO, masks, lengths, window_length, layout)
 
 
 def maskfilter_stereo_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
@@ -2253,22 +2212,7 @@ def maskfilter_stereo_ragged(clips, window_function, masks, step_length=None, re
     buffer; every clip's result has the bits maskfilter_stereo_batch gives for that clip alone.  One upload each of clips and masks, one
     launch (k_maskfilter_stereo_ragged), one download.  "FT" masks are transposed on the host (pack_ragged_stereo_masks).  Window and
     step_length as in maskfilter_stereo_batch."""
-    w = _maskfilter_window(window_function, step_length)
-    x, in_offsets, lengths = pack_ragged_stereo(clips)
-    m, mask_offsets, mc = pack_ragged_stereo_masks(masks, lengths, len(w), layout)
-    plan = maskfilter_plan(w, rest, "TF", device)
-    blocks = 2 if rest else 1
-    out_offsets = blocks * in_offsets
-    d_mask = DeviceBuffer(m.shape, m.dtype, plan.device)
-    try:
-        d_mask.upload(m)
-        res = _round_trip(plan, x, blocks * len(x), lambda d_in, d_out: plan.execute_masked_stereo_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets,
-                                                                                                         d_out, out_offsets, mc))
-    finally:
-        d_mask.free()
-    if not rest:
-        return [res[o:o + n] for o, n in zip(out_offsets.tolist(), lengths.tolist())]
-    return [(res[o:o + n], res[o + n:o + 2 * n]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return _maskfilter_ragged(_MASKED_STEREO, clips, window_function, masks, step_length, rest, layout, device)
 
 
 def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
@@ -2277,23 +2221,7 @@ def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
     of Plan.stems_ragged_layout: clip i's masks back to back as (S, T_i, W/2 + 1), the clips back to back.  The device reads "TF" masks only:
     "FT" masks are transposed here, on the host, as maskfilter_stems_batch does.  A mask of another shape, or a stem count that differs from
     the first clip's, raises ValueError with the clip's index."""
-    lengths = _as_lengths(lengths)
-    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
-    arrays, h, frames = _ragged_mask_items(masks, lengths, window_length, 3, "ragged stems mask batch", "3-D masks, (stems, ...)")
-    n_stems = arrays[0].shape[0] if arrays else 1
-    if not 1 <= n_stems <= _lib.MASKFILTER_MAX_STEMS:
-        raise ValueError(f"the number of stems, masks[0].shape[0], must be in 1 .. {_lib.MASKFILTER_MAX_STEMS}, got {n_stems}")
-    offsets = np.zeros(len(lengths) + 1, np.int64)
-    offsets[1:] = np.cumsum(n_stems * frames * (h + 1))
-    packed = np.zeros(max(int(offsets[-1]), 1), np.float32)
-    for i, (m, o, t) in enumerate(zip(arrays, offsets.tolist(), frames.tolist())):
-        if m.shape[0] != n_stems:
-            raise ValueError(f"mask {i} has {m.shape[0]} stems, mask 0 has {n_stems}: the stem count is one for the batch")
-        want = (n_stems, h + 1, t) if ft else (n_stems, t, h + 1)
-        if m.shape != want:
-            raise ValueError(f"mask {i} must have shape {want} for clip {i} of {int(lengths[i])} samples (layout {layout!r}), got {m.shape}")
-        packed[o:o + n_stems * t * (h + 1)].reshape(n_stems, t, h + 1)[...] = m.transpose(0, 2, 1) if ft else m
-    return packed, offsets
+    return _pack_ragged_masks(_MASKED_STEMS, masks, lengths, window_length, layout)[:2]
 
 
 def maskfilter_stems_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0):
@@ -2303,18 +2231,7 @@ def maskfilter_stems_ragged(clips, window_function, masks, step_length=None, res
     one result buffer; every clip's result has the bits maskfilter_stems_batch gives for that clip alone.  One upload each of clips and
     masks, one launch (k_maskfilter_stems_ragged), one download.  "FT" masks are transposed on the host (pack_ragged_stems_masks).  Window and
     step_length as in maskfilter_batch."""
-    w = _maskfilter_window(window_function, step_length)
-    arrays = _as_ragged_items(clips, 1, "ragged batch", "1-D clips", "clip")
-    lengths = np.array([len(a) for a in arrays], np.int64)
-    m, mask_offsets = pack_ragged_stems_masks(masks, lengths, len(w), layout)
-    h = len(w) // 2
-    n_stems = int(mask_offsets[1]) // (((int(lengths[0]) + h - 1) // h + 1) * (h + 1))
-    plan = maskfilter_plan(w, rest, "TF", device)
-    blocks = n_stems + (1 if rest else 0)
-    res, out_offsets = _masked_ragged_round_trip(plan, arrays, lengths, m, blocks, lambda d_in, in_offsets, d_mask, d_out, out_offsets:
-                                                 plan.execute_masked_stems_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_stems))
-    out = [res[o:o + blocks * n].reshape(blocks, n) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
-    return [(b[:n_stems], b[n_stems]) for b in out] if rest else out
+    return _maskfilter_ragged(_MASKED_STEMS, clips, window_function, masks, step_length, rest, layout, device)
 
 
 def cqtspectrogram_batch(clips, sampling_frequency, time_resolution, cqt_kernel, layout="FT", device=0, f64=False, out=None):
