@@ -41,6 +41,9 @@
  *   ZAFX_MASKFILTER / _REST with   the same for an interleaved stereo clip (N, 2), as the example has it: one real mask for both channels
  *   zafx_execute_masked_stereo     or one per channel, masks in ZAFX_LAYOUT_TF; clips of different lengths in one launch:
  *                                  zafx_execute_masked_stereo_ragged, zafx_plan_stereo_ragged_layout
+ *   ZAFX_MASKFILTER / _REST with   zafx_execute_masked (n_channels 1, masks in ZAFX_LAYOUT_TF) and zafx_execute_masked_stereo (2) on 16-bit PCM:
+ *   zafx_execute_masked_pcm        int16 samples in, s / 32768 (wavread, zaf.py:1202), int16 or float32 samples out; clips of different
+ *                                  lengths in one launch: zafx_execute_masked_pcm_ragged
  *   zafx_plan_set_constant         operands built by melfilterbank zaf.py:246-321 and
  *                                  cqtkernel zaf.py:457-559 (scipy.sparse CSR, consumed
  *                                  at zaf.py:373, :445, :631)
@@ -427,6 +430,38 @@ int zafx_plan_stereo_ragged_layout(const zafx_plan* plan, const int64_t* lengths
  * zafx_execute_center_ragged (measurements only). */
 int zafx_execute_masked_stereo_ragged(zafx_plan* plan, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t mask_channels);
+/* The mask filter on 16-BIT PCM, enqueued on the plan's stream (asynchronous; ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans created with
+ * ZAFX_LAYOUT_TF only): the kernels read int16 samples in their own loads and, with out_sample_bytes == 2, write int16 samples in their own
+ * stores -- no float32 staging array on either side.  n_channels == 1: mono clips, d_pcm (B, n_frames) int16, mask_channels must be 1, d_mask
+ * as zafx_execute_masked takes it in ZAFX_LAYOUT_TF, (B, frames, rows) float32 (last kernel "k_maskfilter_pcm").  n_channels == 2:
+ * interleaved stereo, d_pcm (B, n_frames, 2) int16, mask_channels 1 or 2 and d_mask as zafx_execute_masked_stereo takes them (last kernel
+ * "k_maskfilter_stereo_pcm").  d_out has the shape of the float entry point's output -- with rest (B, 2, n_frames[, 2]) -- in float32
+ * (out_sample_bytes == 4) or int16 (2).  ARITHMETIC: sample s enters as s / 32768 (zaf.py:1202), exact in float32.
+ *   out_sample_bytes == 4: the result is BIT-IDENTICAL to zafx_execute_masked / zafx_execute_masked_stereo on the clip normalised that way,
+ *     the rest x / 32768 - y included.
+ *   out_sample_bytes == 2: q(y) of that float32 result, with t = y * 32768 in float32: NaN -> 0; t >= 32767 (+inf too) -> 32767;
+ *     t <= -32768 (-inf too) -> -32768; anything else rint(t), ties to even.  The rest is integer arithmetic on what was written:
+ *     rest = clamp(x - q(y), -32768, 32767), so q(y) + rest == x to the bit wherever the rest did not saturate.
+ * Everything else is the float entry point's contract: nothing read in front of sample frame 0 or from n_frames on, nothing written at or
+ * beyond n_frames, the same bits alone, anywhere in a batch, however cut and under any ZAFX_COMPUTE_UNITS.  Alignment: mono int16 arrays 2
+ * bytes; stereo int16 arrays 4 bytes, the sample-frame grid; float32 arrays (the masks, a float32 output) 4 bytes.  Rejected with a message,
+ * nothing enqueued or written: a null plan or pointer, negative sizes, another kind, a plan in ZAFX_LAYOUT_FT, n_channels outside {1, 2},
+ * mask_channels 2 with one channel or outside {1, 2}, out_sample_bytes outside {2, 4}, an array off its grid, clips at the bound of the
+ * float entry point (2^28 sample frames; 2^27 with two masks), a window that is not set or whose sum(window[0:W:H]) is zero.
+ * zafx_execute_pcm, zafx_run_host_pcm and zafx_execute_ragged_pcm go on refusing mask-filter plans. */
+int zafx_execute_masked_pcm(zafx_plan* plan, const void* d_pcm, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_frames,
+                            int32_t n_channels, int32_t mask_channels, int32_t out_sample_bytes /* 2: int16, 4: float32 */);
+/* zafx_execute_masked_pcm for n_clips clips of different lengths in ONE launch (last kernel "k_maskfilter_pcm_ragged" /
+ * "k_maskfilter_stereo_pcm_ragged").  in_offsets, lengths and out_offsets count SAMPLE FRAMES: clip i is lengths[i] sample frames at sample
+ * frame in_offsets[i] of d_pcm, its output block starts at sample frame out_offsets[i] of d_out and, under ZAFX_MASKFILTER_REST, the rest
+ * follows at out_offsets[i] + lengths[i].  mask_offsets counts float32 elements, placed as zafx_plan_mask_ragged_layout (n_channels 1) or
+ * zafx_plan_stereo_ragged_layout (2) give them, or anywhere else.  CONTRACT: clip i's block is bit-identical to zafx_execute_masked_pcm on
+ * that clip and its masks alone.  A clip of length 0 is skipped, an empty batch is fine.  The four host arrays are copied before return.
+ * Rejected as zafx_execute_masked_pcm rejects, and: a null host array, negative lengths or offsets (with the clip's index), a clip at the
+ * bound (with its index; decided on `lengths` before anything is read).  NOT checked: that the output blocks do not overlap. */
+int zafx_execute_masked_pcm_ragged(zafx_plan* plan, const void* d_pcm, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                   const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_channels,
+                                   int32_t mask_channels, int32_t out_sample_bytes);
 int zafx_sync(zafx_plan* plan);
 /* Ragged batches: clips of different lengths in one call (forward kinds that take samples: ZAFX_STFT, _MDCT, _MEL, _MFCC
  * with_mel included, _CQT, _CHROMA; float32 and float64).

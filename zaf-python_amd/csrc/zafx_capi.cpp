@@ -1863,6 +1863,27 @@ static const MaskedForm kMaskedForms[] = {
      [](const zafx_plan& pl, int64_t, int* tile, long long* slots) { return zafx::maskfilter_stereo_launch_shape(pl, tile, slots); },
      [](ZAFX_CUT_ARGS) { return zafx::maskfilter_stereo_cut_units(len, in, out, mask, n, pl.W, tile, slots, per_slot); },
      [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t mc) { return zafx::launch_maskfilter_stereo_ragged(pl, (const float*)x, (const float*)m, (float*)y, u, nu, (int)mc); }},
+    // 16-bit PCM in, int16 (OUT16 true) or float32 out (zafx_execute_masked_pcm[_ragged]): mono on k_maskfilter_pcm with the real kind's TF
+    // launch shape and cut, stereo on k_maskfilter_stereo_pcm with the stereo kind's and that kind's refusals; `count` is mask_channels (mono: 0)
+#define ZAFX_PCM_MONO(OUT16)                                                                                                                              \
+    {"zafx_execute_masked_pcm", "zafx_execute_masked_pcm_ragged", nullptr, zafx::kMaskfilterPcmMono, "", false,                                        \
+     "ZAFX_MASKFILTER_UNITS_PER_SLOT", zafx::kMaskfilterUnitsPerSlot, false,                                                                           \
+     [](ZAFX_MASKED_ARGS, int64_t b, int64_t n, int64_t) { return zafx::launch_maskfilter_pcm(pl, x, (const float*)m, y, b, n, 1, 1, OUT16); },        \
+     [](const zafx_plan& pl, int64_t, int* tile, long long* slots) { return zafx::maskfilter_launch_shape(pl, tile, slots); },                        \
+     [](ZAFX_CUT_ARGS) { return cut_masked(pl, true, len, in, out, mask, n, tile, slots, per_slot); },                                                \
+     [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t) { return zafx::launch_maskfilter_pcm_ragged(pl, x, (const float*)m, y, u, nu, 1, 1, OUT16); }}
+#define ZAFX_PCM_STEREO(OUT16)                                                                                                                            \
+    {"zafx_execute_masked_pcm", "zafx_execute_masked_pcm_ragged", nullptr, zafx::kMaskfilterStereo, "", false,                                         \
+     "ZAFX_CENTER_UNITS_PER_SLOT", zafx::kCenterUnitsPerSlot, false,                                                                                   \
+     [](ZAFX_MASKED_ARGS, int64_t b, int64_t n, int64_t mc) { return zafx::launch_maskfilter_pcm(pl, x, (const float*)m, y, b, n, 2, (int)mc, OUT16); }, \
+     [](const zafx_plan& pl, int64_t, int* tile, long long* slots) { return zafx::maskfilter_stereo_launch_shape(pl, tile, slots); },                 \
+     [](ZAFX_CUT_ARGS) { return zafx::maskfilter_stereo_cut_units(len, in, out, mask, n, pl.W, tile, slots, per_slot); },                             \
+     [](ZAFX_MASKED_ARGS, const zafx::MaskfilterUnit* u, long long nu, int64_t mc) {                                                                   \
+         return zafx::launch_maskfilter_pcm_ragged(pl, x, (const float*)m, y, u, nu, 2, (int)mc, OUT16);                                               \
+     }}
+    ZAFX_PCM_MONO(false), ZAFX_PCM_MONO(true), ZAFX_PCM_STEREO(false), ZAFX_PCM_STEREO(true),
+#undef ZAFX_PCM_MONO
+#undef ZAFX_PCM_STEREO
 };
 #undef ZAFX_CUT_ARGS
 #undef ZAFX_MASKED_ARGS
@@ -1960,6 +1981,33 @@ int zafx_execute_masked_complex_ragged(zafx_plan* pl, const void* d_in, const in
 int zafx_execute_masked_stereo_ragged(zafx_plan* pl, const void* d_in, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
                                       const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t mask_channels) {
     return execute_masked_ragged(kMaskedStereo, pl, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, mask_channels);
+}
+// The PCM entry points: what the sample types add -- the channel counts, the output type, the arrays' grids -- is asked here
+// (zafx_routes.hpp), then the call goes down the family's path with the form record of its channels and output type.
+static int masked_pcm_form(const char* fn, const zafx_plan* pl, const void* d_pcm, const void* d_mask, const void* d_out, int32_t n_channels, int32_t mask_channels,
+                           int32_t out_sample_bytes, const MaskedForm** form, int64_t* count) {
+    if (!pl) return fail_msg("null plan");
+    if (const char* why = zafx::maskfilter_pcm_call_refusal(n_channels, mask_channels, out_sample_bytes, (uintptr_t)d_pcm, (uintptr_t)d_mask, (uintptr_t)d_out))
+        return fail_msg(std::string(fn) + ": " + why);
+    *count = n_channels == 2 ? mask_channels : 0;
+    static_assert(sizeof(kMaskedForms) / sizeof(kMaskedForms[0]) == 8, "kMaskedForms: the four float kinds, then PCM mono f32 / i16, PCM stereo f32 / i16");
+    *form = &kMaskedForms[4 + 2 * (n_channels - 1) + (out_sample_bytes == 2 ? 1 : 0)];
+    return 0;
+}
+int zafx_execute_masked_pcm(zafx_plan* pl, const void* d_pcm, const void* d_mask, void* d_out, int64_t n_clips, int64_t n_frames, int32_t n_channels,
+                            int32_t mask_channels, int32_t out_sample_bytes) {
+    const MaskedForm* k = nullptr;
+    int64_t count = 0;
+    if (int rc = masked_pcm_form("zafx_execute_masked_pcm", pl, d_pcm, d_mask, d_out, n_channels, mask_channels, out_sample_bytes, &k, &count)) return rc;
+    return execute_masked(*k, pl, d_pcm, d_mask, d_out, n_clips, n_frames, count);
+}
+int zafx_execute_masked_pcm_ragged(zafx_plan* pl, const void* d_pcm, const int64_t* in_offsets, const int64_t* lengths, const void* d_mask,
+                                   const int64_t* mask_offsets, void* d_out, const int64_t* out_offsets, int64_t n_clips, int32_t n_channels,
+                                   int32_t mask_channels, int32_t out_sample_bytes) {
+    const MaskedForm* k = nullptr;
+    int64_t count = 0;
+    if (int rc = masked_pcm_form("zafx_execute_masked_pcm_ragged", pl, d_pcm, d_mask, d_out, n_channels, mask_channels, out_sample_bytes, &k, &count)) return rc;
+    return execute_masked_ragged(*k, pl, d_pcm, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_clips, count);
 }
 int zafx_plan_stems_ragged_layout(const zafx_plan* pl, const int64_t* lengths, int64_t n_clips, int32_t n_stems, int64_t* mask_offsets, int64_t* out_offsets) {
     return plan_masked_ragged_layout(kMaskedStems, pl, lengths, n_clips, n_stems, mask_offsets, out_offsets);

@@ -394,6 +394,14 @@ hipError_t launch_maskfilter_stereo(const zafx_plan& pl, const float* x, const f
 bool maskfilter_stereo_launch_shape(const zafx_plan& pl, int* tile_frames, long long* slots);
 hipError_t launch_maskfilter_stereo_ragged(const zafx_plan& pl, const float* x, const float* mask, float* out, const MaskfilterUnit* d_units, long long n_units,
                                            int mask_channels);
+// zafx_maskfilter_pcm.hip: zafx_execute_masked_pcm / _ragged: k_maskfilter_pcm (channels 1: int16 samples (B, N), a TF mask (B, T, W/2+1)) and
+// k_maskfilter_stereo_pcm (channels 2: int16 sample frames (B, N, 2), masks as launch_maskfilter_stereo takes them); out16: int16 samples out
+// instead of float32 ones.  TF plans only.  RAGGED: the launch shapes and the units are those of the float kernels (maskfilter_launch_shape,
+// maskfilter_stereo_launch_shape), offsets and lengths count sample frames
+hipError_t launch_maskfilter_pcm(const zafx_plan& pl, const void* x, const float* mask, void* out, int64_t n_clips, int64_t n_samples, int channels,
+                                 int mask_channels, bool out16);
+hipError_t launch_maskfilter_pcm_ragged(const zafx_plan& pl, const void* x, const float* mask, void* out, const MaskfilterUnit* d_units, long long n_units,
+                                        int channels, int mask_channels, bool out16);
 // zafx_execute_masked_stems_ragged: the same for k_maskfilter_stems -- the slots follow the stems' LDS size (false as well for a stem count
 // outside 1 .. 8) -- and the launch on a device table of unit records: a clip's n_stems masks back to back at mask_off, its n_stems (+ 1 with
 // rest) output blocks back to back at out_off

@@ -21,24 +21,11 @@
 //     mask_off, the first float32 element of the clip's mask(s).  Offsets and lengths of samples count sample frames.
 #include <algorithm>
 
-#include "zafx_maskfilter_stereo.hpp"
+#include "zafx_maskfilter_cfg.hpp"
 #include "zafx_units.hpp"
 #include "zafx_overlap_walk.hpp"
 
 namespace zafx {
-
-// k_center's geometry and LDS layout (CenterCfg, zafx_center.hip), restated: that translation unit stays as it is.
-template <int LOG2W>
-struct MaskfilterStereoCfg {
-    static constexpr int LOG2E = maskfilter_stereo_log2e(LOG2W);
-    using C = FftCfg<LOG2W, LOG2E>;
-    static constexpr int W = 1 << LOG2W, H = W / 2, E = C::E, P = C::P, F = maskfilter_stereo_tile_frames(LOG2W), NT = P * F;
-    static_assert(P == 64 || P == 128, "k_maskfilter_stereo: one or two wavefronts per frame");
-    // LDS (float2 slots): F padded frames | the carry (second half of the tile's last frame, H points) | the pass tables
-    static constexpr int OFF_CARRY = F * C::PITCH, OFF_TW = OFF_CARRY + H, SLOTS = OFF_TW + C::TW;
-    static constexpr size_t SMEM = (size_t)SLOTS * 8;
-    static_assert(SMEM <= (size_t)kMaxLdsBytes, "k_maskfilter_stereo: frames + carry + tables exceed LDS");
-};
 
 // One segment = blocks [seg * seg_blocks, min(n_blocks, (seg + 1) * seg_blocks)) of one clip; unit u = clip * n_segs + seg; the masks of a clip
 // are (n_blocks + 1) x (PER_CHANNEL ? 2 : 1) rows of H + 1 floats, clips back to back.

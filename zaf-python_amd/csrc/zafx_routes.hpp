@@ -560,6 +560,50 @@ inline const char* maskfilter_stereo_ragged_refusal(int kind, int layout, int64_
     return maskfilter_form_ragged_refusal(kMaskfilterStereo, kind, layout, mask_channels, lengths, n_clips, clip);
 }
 
+// The PCM forms (zafx_execute_masked_pcm, zafx_execute_masked_pcm_ragged; zafx_maskfilter_pcm.hip): int16 samples in, int16 or float32 samples
+// out, on k_maskfilter_pcm (n_channels 1) and k_maskfilter_stereo_pcm (2).  The stereo form refuses what the float stereo kind refuses, from
+// that kind's record.  The mono form has the real kind's bound in the real kind's words and masks in ZAFX_LAYOUT_TF only (the FT stage of
+// k_maskfilter has no PCM form).
+constexpr const char* kMaskfilterPcmKernel = "k_maskfilter_pcm";
+constexpr const char* kMaskfilterPcmRaggedKernel = "k_maskfilter_pcm_ragged";
+constexpr const char* kMaskfilterStereoPcmKernel = "k_maskfilter_stereo_pcm";
+constexpr const char* kMaskfilterStereoPcmRaggedKernel = "k_maskfilter_stereo_pcm_ragged";
+constexpr MaskfilterForm kMaskfilterPcmMono = {
+    "PCM mask filter: ZAFX_MASKFILTER and ZAFX_MASKFILTER_REST plans only", true,
+    "PCM mask filter: masks in ZAFX_LAYOUT_TF only (create the plan with layout = ZAFX_LAYOUT_TF)", 0, 0, nullptr, kMaskfilterReal.max_units, 0,
+    {kMaskfilterReal.too_long[0], nullptr}, {"PCM mask filter: a clip has 2^28 samples or more (not supported)", nullptr}, 4, false};
+static_assert(maskfilter_masks_addressable(kMaskfilterPcmMono), "PCM mask filter: the mask of the longest clip taken stays behind signed 32-bit byte offsets");
+constexpr const MaskfilterForm& maskfilter_pcm_form(int n_channels) { return n_channels == 2 ? kMaskfilterStereo : kMaskfilterPcmMono; }
+// n_channels 1 (mask_channels 1 then) or 2 (mask_channels 1 or 2, which the stereo record asks again); nullptr: taken
+inline const char* maskfilter_pcm_channels_refusal(int64_t n_channels, int64_t mask_channels) {
+    if (n_channels != 1 && n_channels != 2) return "PCM mask filter: n_channels must be 1 (mono) or 2 (interleaved stereo)";
+    if (mask_channels != 1 && mask_channels != 2) return "PCM mask filter: mask_channels must be 1 or 2";
+    if (n_channels == 1 && mask_channels != 1) return "PCM mask filter: mask_channels must be 1 with one channel (a mask per channel takes n_channels 2)";
+    return nullptr;
+}
+inline const char* maskfilter_pcm_out_refusal(int64_t out_sample_bytes) {
+    return out_sample_bytes == 2 || out_sample_bytes == 4 ? nullptr : "PCM mask filter: out_sample_bytes must be 2 (int16) or 4 (float32)";
+}
+// The arrays: int16 samples on the sample-frame grid (2 bytes mono, 4 stereo), float32 samples and masks on 4 bytes.  A stereo array off its
+// grid would turn every dword of the kernel into a misaligned one; it is refused, not rounded.
+inline const char* maskfilter_pcm_alignment_refusal(uintptr_t in, uintptr_t mask, uintptr_t out, int n_channels, int out_sample_bytes) {
+    if (in % (uintptr_t)(2 * n_channels) != 0)
+        return n_channels == 2 ? "PCM mask filter: d_pcm must be 4-byte aligned (stereo int16: the sample-frame grid)" : "PCM mask filter: d_pcm must be 2-byte aligned";
+    if (mask % 4 != 0) return "PCM mask filter: d_mask must be 4-byte aligned";
+    if (out % (uintptr_t)(out_sample_bytes == 2 ? 2 * n_channels : 4) != 0)
+        return out_sample_bytes == 4 ? "PCM mask filter: d_out must be 4-byte aligned (float32)"
+               : n_channels == 2     ? "PCM mask filter: d_out must be 4-byte aligned (stereo int16: the sample-frame grid)"
+                                     : "PCM mask filter: d_out must be 2-byte aligned";
+    return nullptr;
+}
+// What the sample types add to a call, in the order the entry points ask it: the channels, the output type, the arrays' grids.  nullptr: the
+// call goes on to the refusals of maskfilter_pcm_form(n_channels) with count = mask_channels (stereo) or 0 (mono).
+inline const char* maskfilter_pcm_call_refusal(int64_t n_channels, int64_t mask_channels, int64_t out_sample_bytes, uintptr_t in, uintptr_t mask, uintptr_t out) {
+    if (const char* why = maskfilter_pcm_channels_refusal(n_channels, mask_channels)) return why;
+    if (const char* why = maskfilter_pcm_out_refusal(out_sample_bytes)) return why;
+    return maskfilter_pcm_alignment_refusal(in, mask, out, (int)n_channels, (int)out_sample_bytes);
+}
+
 // ---------------------------------------------------------------------------------
 // ragged batches: clips of different lengths in one call (zafx_execute_ragged, zafx_execute_ragged_pcm, zafx_execute_imdct_ragged,
 // zafx_execute_istft_ragged).  The tests run in the order, and with the inequalities, the entry points had inline

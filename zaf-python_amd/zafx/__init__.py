@@ -24,6 +24,9 @@ The same with a mask of the caller's (STFT, real mask, ISTFT of mono clips in on
     interleaved stereo clips under one mask for both channels or one per channel, in one kernel; maskfilter_stereo_ragged (clips and masks
     of different lengths in one launch), pack_ragged_stereo_masks, Plan.execute_masked_stereo / Plan.execute_masked_stereo_ragged /
     Plan.stereo_mask_shape / Plan.stereo_out_shape / Plan.stereo_ragged_layout
+    maskfilter_pcm (int16 (N,) or (N, 2) -> int16 or float32), maskfilter_pcm_batch ((B, N) or (B, N, 2) int16), maskfilter_pcm_ragged: the
+    mono and the stereo mask filter on 16-bit PCM, the integers read and written by the kernel (s / 32768 in; rint, saturating, out; the rest
+    in integers); Plan.execute_masked_pcm / Plan.execute_masked_pcm_ragged
 Batched extension ((clips, samples) in, float32 / complex64 out):
     stft_batch, istft_batch, mdct_batch, imdct_batch, melspectrogram_batch, mfcc_batch,
     cqtspectrogram_batch, cqtchromagram_batch, dct_batch, dst_batch, mel_mfcc_batch (melspectrogram + mfcc from one set of transforms);
@@ -43,13 +46,13 @@ spawn_ranks (file rendezvous + self-launcher, no torch.distributed).
 from ._lib import (CENTER, CENTER_SIDES, CHROMA, CQT, DCT, IMDCT, ISTFT, LAYOUT_FT, LAYOUT_TF, LINEAR, MASKFILTER, MASKFILTER_MAX_STEMS, MASKFILTER_REST, MDCT, MEL, MFCC, STFT, ZafxError,
                    center_tile_frames, device_count, device_name, library_path, maskfilter_tile_transforms)
 from .constants import cqtkernel, dct2_rows, dct_matrix, dst_matrix, hamming, kaiser_bessel_derived, melfilterbank, sine
-from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersides_batch, maskfilter, maskfilter_batch, maskfilter_plan, maskfilter_stems, maskfilter_stems_batch, maskfilter_complex, maskfilter_complex_batch, maskfilter_stereo, maskfilter_stereo_batch, clear_plan_cache, cqt_plan, cqtchromagram, cqtchromagram_batch, dct, dct_batch, dst,
+from .core import (Comm, DeviceBuffer, Plan, center_plan, centersides, centersides_batch, maskfilter, maskfilter_batch, maskfilter_plan, maskfilter_stems, maskfilter_stems_batch, maskfilter_complex, maskfilter_complex_batch, maskfilter_stereo, maskfilter_stereo_batch, maskfilter_pcm, maskfilter_pcm_batch, clear_plan_cache, cqt_plan, cqtchromagram, cqtchromagram_batch, dct, dct_batch, dst,
                    dst_batch, linear_plan, dct_plan, dct_fft_length,
                    cqtspectrogram, cqtspectrogram_batch, imdct, imdct_batch, istft, istft_batch, istft_plan, mdct,
                    mdct_batch, mdct_plan, mel_plan, melspectrogram, melspectrogram_batch, mfcc, mfcc_batch, pcm_to_mono, pinned_empty,
                    get_precision, set_precision, stft, stft_batch, stft_pcm_batch, stft_plan, mdct_pcm_batch, melspectrogram_pcm_batch, mfcc_pcm_batch,
                    cqtspectrogram_pcm_batch, cqtchromagram_pcm_batch, mel_mfcc_batch, mel_mfcc_pcm_batch, mel_mfcc_supported, set_row_padding, get_row_padding,
-                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, maskfilter_ragged, pack_ragged_masks, maskfilter_stems_ragged, pack_ragged_stems_masks, maskfilter_complex_ragged, pack_ragged_complex_masks, maskfilter_stereo_ragged, pack_ragged_stereo_masks, imdct_ragged, istft_ragged,
+                   stft_ragged, mdct_ragged, melspectrogram_ragged, mfcc_ragged, mel_mfcc_ragged, pack_ragged, centersides_ragged, pack_ragged_stereo, maskfilter_ragged, pack_ragged_masks, maskfilter_stems_ragged, pack_ragged_stems_masks, maskfilter_complex_ragged, pack_ragged_complex_masks, maskfilter_stereo_ragged, pack_ragged_stereo_masks, maskfilter_pcm_ragged, imdct_ragged, istft_ragged,
                    stft_pcm_ragged, mdct_pcm_ragged, melspectrogram_pcm_ragged, mfcc_pcm_ragged, mel_mfcc_pcm_ragged, pack_ragged_pcm)
 from .launch import Rendezvous, rank_env, spawn_ranks
 from .shard import clip_range, run_sharded, shard_sizes

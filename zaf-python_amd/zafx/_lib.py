@@ -102,6 +102,9 @@ SYMBOLS = {
     "zafx_plan_stereo_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "zafx_execute_masked_stereo_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64,
                                                ctypes.c_int32]),
+    "zafx_execute_masked_pcm": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "zafx_execute_masked_pcm_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64), _i64,
+                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "zafx_sync": (_i, [_vp]),
     "zafx_plan_ragged_layout": (_i, [_vp, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64)]),
     "zafx_execute_ragged": (_i, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _i64]),

@@ -412,6 +412,9 @@ _MASKED_STEREO = _MaskedForm(
     lambda p, b, n, c: p.stereo_mask_shape(b, n, c), lambda p, b, n, c: p.stereo_out_shape(b, n), np.asarray, _stereo_batch_count, _stereo_ragged_count, None,
     ("ragged stereo mask batch", lambda c: f"{1 + c}-D masks"))
 
+# the mono PCM form (execute_masked_pcm with one channel): the real kind's shapes, but the device reads "TF" masks only, and clips below 2^28
+_MASKED_PCM_MONO = _MASKED_REAL._replace(tf_only=True, per_clip_bound=lambda c: 1 << 28)
+
 
 def _check_masked_dtypes(form, name, d_in, d_mask, d_out):
     if d_in.dtype != np.float32 or d_mask.dtype != form.mask_dtype or d_out.dtype != np.float32:
@@ -752,6 +755,76 @@ class Plan:
         may stay on).  Clip i's block has the bits execute_masked_complex gives that clip and mask alone.  Output blocks that overlap are not
         detected."""
         self._execute_masked_ragged(_MASKED_COMPLEX, d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets)
+
+    def _pcm_masked_args(self, name, d_pcm, d_mask, d_out, n_channels, mask_channels):
+        """The dtype checks of the PCM mask-filter calls -> (the form whose shapes the call has, its count or None, out_sample_bytes)."""
+        if d_pcm.dtype != np.int16:
+            raise ValueError(f"{name} takes int16 samples, got {d_pcm.dtype} (no silent cast: int32 and 24-bit material stay with the caller)")
+        if d_mask.dtype != np.float32:
+            raise ValueError(f"{name} takes float32 masks, got {d_mask.dtype}")
+        if d_out.dtype not in (np.int16, np.float32):
+            raise ValueError(f"{name} writes int16 or float32 samples, got an output buffer of {d_out.dtype}")
+        n_channels, mask_channels = int(n_channels), int(mask_channels)
+        form = _MASKED_STEREO if n_channels == 2 else _MASKED_PCM_MONO
+        return form, (mask_channels if n_channels == 2 else None), d_out.dtype.itemsize
+
+    def execute_masked_pcm(self, d_pcm, d_mask, d_out, n_clips, n_in, n_channels=1, mask_channels=1):
+        """Enqueue the mask filter on 16-bit PCM on the plan's stream (asynchronous; zafx_execute_masked_pcm, mask filter plans of layout "TF"
+        only; last_kernel: k_maskfilter_pcm / k_maskfilter_stereo_pcm): d_pcm int16, (clips, n_in) for n_channels 1 and (clips, n_in, 2)
+        interleaved for 2; d_mask float32 of mask_shape(n_clips, n_in) (n_channels 1, mask_channels 1) or of
+        stereo_mask_shape(n_clips, n_in, mask_channels); d_out of out_shape / stereo_out_shape, int16 or float32 -- the output type is read
+        from d_out.dtype.  A sample s enters as s / 32768; a float32 output has the bits of execute_masked / execute_masked_stereo on the
+        clip normalised that way, an int16 one is its quantisation (rint, ties to even, saturating, NaN -> 0) and the rest is
+        clip(x - y_q) in integers.  Buffers of another dtype or too small for these clips raise ValueError before anything is enqueued."""
+        form, count, out_bytes = self._pcm_masked_args("execute_masked_pcm", d_pcm, d_mask, d_out, n_channels, mask_channels)
+        n_clips, n_in = int(n_clips), int(n_in)
+        if n_clips < 0 or n_in < 0:
+            raise ValueError("n_clips and n_in must not be negative")
+        # (another kind, channel count or layout: the library says so)
+        if self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and self.layout == _lib.LAYOUT_TF and int(n_channels) in (1, 2) and form.count_ok(count):
+            mask_shape, out_shape = form.mask_shape(self, n_clips, n_in, count), form.out_shape(self, n_clips, n_in, count)
+            if d_pcm.nbytes < n_clips * n_in * 2 * int(n_channels):
+                raise ValueError("d_pcm holds fewer than clips x n_in sample frames")
+            if d_mask.nbytes != int(np.prod(mask_shape, dtype=np.int64)) * 4:
+                raise ValueError(f"d_mask must hold {form.shape_call} = {mask_shape} float32, got {d_mask.nbytes} bytes")
+            if d_out.nbytes < int(np.prod(out_shape, dtype=np.int64)) * out_bytes:
+                raise ValueError("d_out is smaller than the plan's output for these clips")
+        _lib.check(_lib.load().zafx_execute_masked_pcm(self.handle, d_pcm.ptr, d_mask.ptr, d_out.ptr, n_clips, n_in, int(n_channels), int(mask_channels), out_bytes),
+                   "zafx_execute_masked_pcm")
+
+    def execute_masked_pcm_ragged(self, d_pcm, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, n_channels=1, mask_channels=1):
+        """Enqueue the mask filter on 16-bit PCM clips of different lengths as one launch on the plan's stream (asynchronous;
+        zafx_execute_masked_pcm_ragged, mask filter plans of layout "TF" only; last_kernel: k_maskfilter_pcm_ragged /
+        k_maskfilter_stereo_pcm_ragged).  in_offsets, lengths and out_offsets count sample frames: clip i is lengths[i] sample frames at
+        sample frame in_offsets[i] of d_pcm (int16), its result goes to sample frame out_offsets[i] of d_out (int16 or float32, read from
+        d_out.dtype) and, for a plan with rest, the rest directly behind.  mask_offsets counts float32 elements, as mask_ragged_layout
+        (n_channels 1) or stereo_ragged_layout (2) place them; their totals may stay on.  Clip i's block has the bits execute_masked_pcm
+        gives that clip and its masks alone.  Output blocks that overlap are not detected."""
+        form, count, out_bytes = self._pcm_masked_args("execute_masked_pcm_ragged", d_pcm, d_mask, d_out, n_channels, mask_channels)
+        in_offsets, lengths = _as_int64(in_offsets, "in_offsets"), _as_int64(lengths, "lengths")
+        out_offsets, mask_offsets = _as_int64(out_offsets, "out_offsets"), _as_int64(mask_offsets, "mask_offsets")
+        if len(mask_offsets) == len(lengths) + 1:
+            mask_offsets = np.ascontiguousarray(mask_offsets[:-1])
+        if len(out_offsets) == len(lengths) + 1:
+            out_offsets = np.ascontiguousarray(out_offsets[:-1])
+        if not len(in_offsets) == len(lengths) == len(out_offsets) == len(mask_offsets):
+            raise ValueError("in_offsets, lengths, mask_offsets and out_offsets must have one entry per clip")
+        # (another kind, channel count or layout, negative values, a clip the library refuses: the library says so)
+        ok = self.kind in (_lib.MASKFILTER, _lib.MASKFILTER_REST) and self.layout == _lib.LAYOUT_TF and len(lengths) and int(n_channels) in (1, 2) and form.count_ok(count)
+        if ok and min(int(lengths.min()), int(in_offsets.min()), int(out_offsets.min()), int(mask_offsets.min())) >= 0 and int(lengths.max()) < form.per_clip_bound(count):
+            h = int(self.params.window_length) // 2
+            mask_ends = mask_offsets + form.mask_blocks(count) * ((lengths + h - 1) // h + 1) * (h + 1)
+            blocks = 2 if self.kind == _lib.MASKFILTER_REST else 1
+            live = lengths > 0   # (a clip of length 0 is skipped: its masks are never read)
+            if int((in_offsets + lengths).max()) * 2 * int(n_channels) > d_pcm.nbytes:
+                raise ValueError("a clip reaches past the end of d_pcm")
+            if live.any() and int(mask_ends[live].max()) * 4 > d_mask.nbytes:
+                raise ValueError("a clip's masks reach past the end of d_mask")
+            if int((out_offsets + blocks * lengths).max()) * out_bytes * int(n_channels) > d_out.nbytes:
+                raise ValueError("a clip's result reaches past the end of d_out")
+        _lib.check(_lib.load().zafx_execute_masked_pcm_ragged(self.handle, d_pcm.ptr, _i64p(in_offsets), _i64p(lengths), d_mask.ptr, _i64p(mask_offsets), d_out.ptr,
+                                                              _i64p(out_offsets), len(lengths), int(n_channels), int(mask_channels), out_bytes),
+                   "zafx_execute_masked_pcm_ragged")
 
     def stems_ragged_layout(self, lengths, n_stems):
         """Placement of a ragged stems batch (zafx_plan_stems_ragged_layout, mask filter plans of layout "TF") for clips of `lengths` samples
@@ -1602,6 +1675,71 @@ def maskfilter_stereo_batch(clips, window_function, masks, step_length=None, res
     return _maskfilter_batch(_MASKED_STEREO, clips, window_function, masks, step_length, rest, layout, device, out)
 
 
+def _as_pcm_out_dtype(out_dtype):
+    dt = np.dtype(out_dtype)
+    if dt not in (np.int16, np.float32):
+        raise ValueError(f"out_dtype must be int16 or float32, got {dt}")
+    return dt
+
+
+def _as_int16_clips(a, what):
+    """`a` as it is if it holds int16; anything else raises (no silent cast: a float or int32 array handed in by mistake would be wrapped)."""
+    a = np.asarray(a)
+    if a.dtype != np.int16:
+        raise ValueError(f"{what} must be int16 PCM, got dtype {a.dtype} (int32 and 24-bit material: convert to float32 and use the float functions)")
+    return a
+
+
+def maskfilter_pcm_batch(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out=None, out_dtype=np.int16):
+    """The mask filter for a batch of 16-bit PCM clips in one kernel, the integers read and written by the kernel itself (k_maskfilter_pcm,
+    k_maskfilter_stereo_pcm): clips int16, (B, N) mono or (B, N, 2) interleaved stereo, uploaded as integers; masks as maskfilter_batch takes
+    them for mono clips and as maskfilter_stereo_batch takes them for stereo ones (one for both channels or one per channel).  A sample s
+    enters as s / 32768 (zaf.wavread).  out_dtype float32: the bits of maskfilter_batch / maskfilter_stereo_batch on
+    clips.astype(float32) / 32768.  out_dtype int16 (the default): that result quantised -- rint(y * 32768), ties to even, saturating at
+    -32768 and 32767, NaN -> 0 -- and, with rest=True, rest = clip(x - y_q, -32768, 32767) in integers, so y_q + rest == x wherever the rest
+    did not saturate.  -> (B, N[, 2]) of out_dtype; with rest=True (y, rest), views of one (B, 2, N[, 2]) result (which `out`, if given, is).
+    The device reads "TF" masks only: "FT" masks are transposed on the host before the upload.  Clips of any other dtype raise ValueError."""
+    w = _maskfilter_window(window_function, step_length)
+    a = _as_int16_clips(clips, "clips")
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 2):
+        raise ValueError(f"clips must be mono, (clips, samples), or interleaved stereo, (clips, sample frames, 2), got shape {a.shape}")
+    stereo = a.ndim == 3
+    form = _MASKED_STEREO if stereo else _MASKED_PCM_MONO
+    dt = _as_pcm_out_dtype(out_dtype if out is None else out.dtype)
+    m = np.asarray(masks)
+    if np.iscomplexobj(m) or m.dtype.kind not in "biuf":
+        raise ValueError(f"masks must be real numbers, got dtype {m.dtype}")
+    count = form.batch_count(m) if form.batch_count else None
+    n_clips, n = a.shape[:2]
+    h = len(w) // 2
+    ft = _LAYOUTS[layout] == _lib.LAYOUT_FT
+    want = (n_clips,) + form.host_shape(count, (n + h - 1) // h + 1, h + 1, ft)
+    if m.shape != want:
+        raise ValueError(f"masks must have shape {want} for clips of {n} {form.units} (layout {layout!r}), got {m.shape}")
+    shape = (n_clips,) + ((2,) if rest else ()) + a.shape[1:]
+    if out is None:
+        out = np.empty(shape, dt)
+    elif tuple(out.shape) != shape or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError(f"out must be a writeable C-contiguous int16 or float32 array of shape {shape}")
+    if out.size:
+        plan = maskfilter_plan(w, rest, "TF", device)
+        if ft:
+            m = m.transpose((0,) + tuple(i + 1 for i in form.ft_axes(count)))
+        x, m = np.ascontiguousarray(a), np.ascontiguousarray(m, dtype=np.float32)
+        d_in, d_mask, d_out = (DeviceBuffer(b.shape, b.dtype, plan.device) for b in (x, m, out))
+        try:
+            d_in.upload(x)
+            d_mask.upload(m)
+            with plan.lock:
+                plan.execute_masked_pcm(d_in, d_mask, d_out, n_clips, n, 2 if stereo else 1, count or 1)
+                plan.sync()
+                d_out.download(out=out)
+        finally:
+            for b in (d_in, d_mask, d_out):
+                b.free()
+    return (out[:, 0], out[:, 1]) if rest else out
+
+
 def mdct_batch(clips, window_function, layout="FT", device=0, f64=False, out=None, row_align=None):
     """(B, N) -> (B, W/2, T) float32 ["FT"] or (B, T, W/2) ["TF"]; f64: float64 arrays and arithmetic."""
     x = _as_clips(clips, dtype=np.float64 if f64 else np.float32)
@@ -2215,6 +2353,53 @@ def maskfilter_stereo_ragged(clips, window_function, masks, step_length=None, re
     return _maskfilter_ragged(_MASKED_STEREO, clips, window_function, masks, step_length, rest, layout, device)
 
 
+def maskfilter_pcm_ragged(clips, window_function, masks, step_length=None, rest=False, layout="FT", device=0, out_dtype=np.int16):
+    """maskfilter_pcm_batch of 16-bit PCM clips of different lengths in one launch: a sequence of int16 clips, all 1-D (mono) or all (N_i, 2)
+    (interleaved stereo), and one of real masks as maskfilter_ragged / maskfilter_stereo_ragged take them -> a list of (N_i[, 2]) arrays of
+    out_dtype (int16 or float32), or of (y_i, rest_i) pairs with rest=True, each a view of the one result buffer; every clip's result has
+    the bits maskfilter_pcm_batch gives for that clip alone.  One upload each of clips (as integers) and masks, one launch
+    (k_maskfilter_pcm_ragged / k_maskfilter_stereo_pcm_ragged), one download.  Clips of any other dtype raise ValueError."""
+    w = _maskfilter_window(window_function, step_length)
+    dt = _as_pcm_out_dtype(out_dtype)
+    try:
+        arrays = [np.asarray(c) for c in clips] if not (isinstance(clips, np.ndarray) and clips.dtype != object) else None
+    except TypeError:
+        arrays = None
+    if arrays is None:
+        raise ValueError("a ragged PCM batch is a sequence of int16 clips, 1-D or (N, 2), not one array")
+    if not arrays:
+        raise ValueError("a ragged PCM batch needs at least one clip")
+    stereo = arrays[0].ndim == 2
+    for i, c in enumerate(arrays):
+        _as_int16_clips(c, f"clip {i} of the ragged PCM batch")
+        if c.ndim != (2 if stereo else 1) or (stereo and c.shape[1] != 2):
+            raise ValueError(f"clip {i} of the ragged PCM batch must be {'(sample frames, 2)' if stereo else '1-D'} as clip 0 is, got shape {c.shape}")
+    form = _MASKED_STEREO if stereo else _MASKED_PCM_MONO
+    lengths = np.array([len(c) for c in arrays], np.int64)
+    in_offsets, total = _back_to_back(lengths)
+    x = np.zeros((max(total, 1),) + ((2,) if stereo else ()), np.int16)
+    for c, o in zip(arrays, in_offsets.tolist()):
+        x[o:o + len(c)] = c
+    m, mask_offsets, count = _pack_ragged_masks(form, masks, lengths, len(w), layout)
+    plan = maskfilter_plan(w, rest, "TF", device)
+    blocks = 2 if rest else 1
+    out_offsets = blocks * in_offsets
+    res = np.empty((max(blocks * total, 1),) + x.shape[1:], dt)
+    d_in, d_mask, d_out = (DeviceBuffer(b.shape, b.dtype, plan.device) for b in (x, m, res))
+    try:
+        d_in.upload(x)
+        d_mask.upload(m)
+        with plan.lock:
+            plan.execute_masked_pcm_ragged(d_in, in_offsets, lengths, d_mask, mask_offsets, d_out, out_offsets, 2 if stereo else 1, count or 1)
+            plan.sync()
+            d_out.download(out=res)
+    finally:
+        for b in (d_in, d_mask, d_out):
+            b.free()
+    out = [res[o:o + blocks * n].reshape((blocks, n) + res.shape[1:]) for o, n in zip(out_offsets.tolist(), lengths.tolist())]
+    return [(b[0], b[1]) for b in out] if rest else [b[0] for b in out]
+
+
 def pack_ragged_stems_masks(masks, lengths, window_length, layout="FT"):
     """One contiguous float32 array of a ragged stems batch's masks: a sequence of real (S, W/2 + 1, T_i) arrays -- (S, T_i, W/2 + 1) with
     layout "TF" --, T_i = ceil(lengths[i] / (W/2)) + 1, S the same for every clip -> (packed 1-D, mask_offsets of len(lengths) + 1), the layout
@@ -2461,6 +2646,21 @@ def maskfilter_stereo(audio_signal, window_function, step_length, mask):
         raise ValueError(f"audio_signal must be stereo, (sample frames, 2), got shape {a.shape}")
     _stereo_mask_channels(m.ndim, 2, "mask")
     return maskfilter_stereo_batch(a[None], window_function, m[None], step_length)[0].astype(np.float64)
+
+
+def maskfilter_pcm(audio_pcm, window_function, step_length, mask, out_dtype=np.int16):
+    """maskfilter / maskfilter_stereo on 16-bit PCM as zaf.wavread finds it on disk, in one call: an int16 signal, (N,) mono or (N, 2) stereo,
+    and a real mask (W/2 + 1, T) -- for a stereo signal also (2, W/2 + 1, T), one per channel -> (N[, 2]) of out_dtype: int16 (the default;
+    what zaf.wavwrite takes) or float32 (the filtered signal at the level of audio_pcm / 32768).  step_length must be window_length / 2;
+    any dtype other than int16 raises ValueError (see maskfilter_pcm_batch)."""
+    a, m = _as_int16_clips(audio_pcm, "audio_pcm"), np.asarray(mask)
+    if a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] != 2):
+        raise ValueError(f"audio_pcm must be mono, (samples,), or interleaved stereo, (sample frames, 2), got shape {a.shape}")
+    if a.ndim == 2:
+        _stereo_mask_channels(m.ndim, 2, "mask")
+    elif m.ndim != 2:
+        raise ValueError(f"mask must be 2-D, (W/2 + 1, frames), got {m.ndim} dimensions")
+    return maskfilter_pcm_batch(a[None], window_function, m[None], step_length, out_dtype=out_dtype)[0]
 
 
 def maskfilter_stems(audio_signal, window_function, step_length, masks):
