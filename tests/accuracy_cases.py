@@ -240,11 +240,12 @@ def linear_case(name):
 
 
 # ------------------------------------------------------------------------------------------------ tests/maskfilter_cases.py
-# The six fused STFT-mask-ISTFT kernels: 5 forms x W = 256 ... 2048 x T = 62 / 63 x with and without the rest, each through its equal-length
-# launch ("maskfilter/<case>") and, with clips of 1, H, 3 H + 7 and 0 samples between the same clips, through its ragged one
-# ("maskfilter/<case>/ragged").  Reference: the float64 oracle's composition; yardstick: plain.maskfilter* at float32 -- unpacked, one frame per
-# transform, where the kernels ride two frames in one transform and split them.  Every stem of every clip, and the rest, is a 1-D result of its
-# own; the block length of e_row / e_col is the hop.  Family factors, no entry in OWN_FACTORS.
+# The eight fused float32 STFT-mask-ISTFT kernels: 7 forms (the stereo kind's two among them) x W = 256 ... 2048 x T = 62 / 63 x with and
+# without the rest, each through its equal-length launch ("maskfilter/<case>") and, with clips of 1, H, 3 H + 7 and 0 samples between the same
+# clips, through its ragged one ("maskfilter/<case>/ragged").  Reference: the float64 oracle's composition; yardstick: plain.maskfilter* at
+# float32 -- unpacked, one frame per transform, where the kernels ride two frames (the stereo kernels: the two channels of a frame) in one
+# transform and split them.  Every stem of every clip, every channel of a stereo clip, and the rest, is a 1-D result of its own; the block
+# length of e_row / e_col is the hop.  Family factors, no entry in OWN_FACTORS.
 MASKFILTER_NAMES = list(mc.ACCURACY_CASES)
 
 

@@ -163,6 +163,15 @@ def maskfilter_stems(x, window, masks, dtype, rest=False):
     return out
 
 
+def maskfilter_stereo(x, window, masks, dtype, rest=False):
+    """x (N, 2), masks (W/2 + 1, T) for both channels or (2, W/2 + 1, T) -> (2, N): y_L, y_R, each channel alone through maskfilter -- no
+    packing of the two into one transform; with rest (4, N): rest_L, rest_R = x - y in `dtype` behind them."""
+    x, masks = np.asarray(x), np.asarray(masks)
+    assert x.ndim == 2 and x.shape[1] == 2 and masks.ndim in (2, 3), (x.shape, masks.shape)
+    per = [maskfilter_stems(np.ascontiguousarray(x[:, c]), window, (masks if masks.ndim == 2 else masks[c])[None], dtype, rest=rest) for c in (0, 1)]
+    return np.stack([per[c][j] for j in range(1 + int(rest)) for c in (0, 1)])
+
+
 # ------------------------------------------------------------------------------------------------ mdct / imdct  (zaf.py:984-1184)
 def mdct_num_frames(n, wl):
     return -(-n // (wl // 2)) + 1

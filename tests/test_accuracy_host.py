@@ -23,6 +23,7 @@ import const_probe as cp
 import maskfilter_cases as mc
 import plain
 import route_cases as rc
+import signals as sig
 from conftest import relerr
 from oracle import zaf_oracle as orc
 
@@ -357,3 +358,91 @@ def test_the_new_checks_see_what_the_old_bound_cannot(wl):
     assert _model_errors(b, rounded) <= mc.TOL_FFT
     assert set(acc.over(k, y, acc.factors())) == set(acc.METRICS), acc.ratios(k, y)
     assert acc.over(*_model_judged(b, _model_batch(b, None), h), acc.factors()) == []
+
+
+# ------------------------------------------------------------------------------------------------ the stereo mask filter
+def _stereo_batch(form, b, defect):
+    return [mc.stereo_model_rows(x, b["w"], m, defect) for x, m in zip(b["clips"], b["masks"])]
+
+
+def _stereo_errors(b, got):
+    """The worst mask_error of y_L and y_R, the level over both channels (tests/test_gpu_accuracy.py's bound on top)."""
+    return max(mc.mask_error(g[j], r[j], mc.row_level(r, x, j, 2)) for g, r, x in zip(got, b["refs"], b["clips"]) for j in (0, 1))
+
+
+def _stereo_judged(b, got, h, rest=True):
+    rows = lambda v: mc.rows_of(v, rest, 2)   # noqa: E731
+    return acc.measure(rows(got), rows(b["refs"]), h), acc.measure(rows(b["yard"]), rows(b["refs"]), h)
+
+
+@pytest.mark.parametrize("form", sorted(mc.STEREO_DATA))
+@pytest.mark.parametrize("wl", mc.WINDOWS)
+def test_the_stereo_model_is_within_the_family_factors(wl, form):
+    """Two channels in one transform, the per-channel form's split and re-pack and the shared form's none, in NumPy float32: within the
+    family's factors of the unpacked yardstick on the catalogue's own batches and on their ragged extras, the rest included."""
+    for blocks in mc.BLOCKS:
+        b, e = mc.accuracy_batch(f"{form}_{wl}_{blocks}_rest")
+        twin, _ = mc.ragged_twin(b, e)
+        k, y = _stereo_judged(twin, _stereo_batch(form, twin, None), wl // 2)
+        print(acc.line(f"stereo model {form} W={wl} T={blocks + 2}", "-", k, y))
+        assert acc.over(k, y, acc.factors()) == [], acc.ratios(k, y)
+        assert _stereo_errors(twin, _stereo_batch(form, twin, None)) <= mc.TOL_FFT
+
+
+def test_the_stereo_model_and_yardstick_keep_the_hop_bound():
+    """hop_share_stereo is a condition on k_maskfilter_stereo (tests/test_gpu_signals.py::test_stereo_signal_through_the_mask_filters), so it is
+    held here first: on all eleven stereo signals, W = 2048 and 256, both forms, both clips, y and the rest, the unpacked float32 chain stays
+    within 0.5 of it and the model of the packing within 1 -- a failure on the GPU then points at the kernel.  The silent channel of
+    left_only is where the model comes closest: it inherits the loud channel's rounding and has nothing but the floor to be held to."""
+    worst, packed = (-1.0, ()), (-1.0, ())
+    assert len(sig.STEREO_NAMES) == 11 and mc.SIGNAL_WINDOWS == (2048, 256)
+    for wl in mc.SIGNAL_WINDOWS:
+        h = wl // 2
+        for name in sig.STEREO_NAMES:
+            case = mc.stereo_signal_case(name, wl)
+            for form in mc.STEREO_SIGNAL_FORMS:
+                c = case[form]
+                for i, (yard, ref, x, m) in enumerate(zip(c["yard"], c["refs"], c["clips"], c["masks"])):
+                    model = mc.stereo_model_rows(x, case["w"], m)
+                    for j in (0, 2):   # the pair y_L, y_R and the pair rest_L, rest_R
+                        for ch, (s_yard, s_model) in enumerate(zip(mc.hop_share_stereo(yard[j:j + 2], ref[j:j + 2], x, h),
+                                                                   mc.hop_share_stereo(model[j:j + 2], ref[j:j + 2], x, h))):
+                            at = (name, wl, form, i, j + ch)
+                            worst, packed = max(worst, (s_yard, at)), max(packed, (s_model, at))
+                            assert s_yard <= 0.5 and s_model <= 1.0, (at, s_yard, s_model)
+                    if not np.any(x):
+                        assert not np.any(yard) and not np.any(model), (name, wl, form)
+    print(f"worst share of the stereo hop bound: unpacked {worst[0]:.3f} {worst[1]}, stereo model {packed[0]:.3f} {packed[1]}")
+
+
+@pytest.mark.parametrize("wl", [256, 2048])
+def test_the_stereo_checks_see_each_defect(wl):
+    """One defect at a time in the stereo model, through the checks of the GPU modules:
+      * the window read at (W - n) % W: past TOL_FFT under `skew`, both forms -- and, under periodic Hamming, the bits of the sound model;
+      * m_0 and m_1 exchanged: past TOL_FFT in stereo2, under either window; stereo1 has one mask and keeps the sound model's bits;
+      * bin H's mask taken from bin H - 1: past TOL_FFT and outside the accuracy factors;
+      * Z rounded to 16 mantissa bits before the masks: inside TOL_FFT, outside the accuracy factors in every metric."""
+    h = wl // 2
+    for form in sorted(mc.STEREO_DATA):
+        ham, skew = mc.batch(form, wl, 20 * h + 9, "hamming", "unit"), mc.batch(form, wl, 20 * h + 9, "skew", "unit")
+        sound = _stereo_batch(form, ham, None)
+        assert _stereo_errors(ham, sound) <= mc.TOL_FFT and _stereo_errors(skew, _stereo_batch(form, skew, None)) <= mc.TOL_FFT
+        mirrored = _stereo_batch(form, ham, "window_mirror")
+        assert all(np.array_equal(a, b) for a, b in zip(mirrored, sound))
+        assert _stereo_errors(skew, _stereo_batch(form, skew, "window_mirror")) >= 0.05
+        for b in (ham, skew):
+            swapped = _stereo_batch(form, b, "channel_swap")
+            if form == "stereo2":
+                assert _stereo_errors(b, swapped) >= 0.05, (wl, _stereo_errors(b, swapped))
+            else:
+                assert all(np.array_equal(a, c) for a, c in zip(swapped, _stereo_batch(form, b, None)))
+        assert _stereo_errors(ham, _stereo_batch(form, ham, "bin_h")) > mc.TOL_FFT
+        b = mc.batch(form, wl, 61 * h + 5, rotate=0)
+        assert acc.over(*_stereo_judged(b, _stereo_batch(form, b, None), h), acc.factors()) == []
+        k, y = _stereo_judged(b, _stereo_batch(form, b, "bin_h"), h)
+        assert acc.over(k, y, acc.factors()) != [], acc.ratios(k, y)
+        rounded = _stereo_batch(form, b, "round16")
+        k, y = _stereo_judged(b, rounded, h, rest=False)
+        print(acc.line(f"{form}: Z at 16 mantissa bits, W={wl}", "-", k, y))
+        assert _stereo_errors(b, rounded) <= mc.TOL_FFT
+        assert set(acc.over(k, y, acc.factors())) == set(acc.METRICS), acc.ratios(k, y)

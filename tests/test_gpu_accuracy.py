@@ -11,9 +11,11 @@ The cases: constants A of every route of tests/const_probe.py but the center mas
 its hashes were recorded with (kernel names held to tests/golden/call_routes.json); float64 Bluestein STFT and MDCT at W = 1000 (the only
 device-side trigonometry), k_mel's melspectrogram at W = 1024, and dct / dst of types 1-4 at 64, 1024 (k_dct), 100, 132 (k_dct_bsh) and 134 (k_dct_bs32), 8 rows each; k_linear and k_linear128 at the shapes of tests/linear_cases.py and the dense dct-II at
 N = 8224, 16 clips each, whose yardstick is one k-ordered float32 chain per output (plain.linear_chain: what the matrix core computes; BLAS is
-4 ... 9 times below any single chain at thousands of columns); the six fused mask-filter kernels at the 80 cases of tests/maskfilter_cases.py
-(real masks in three layouts, three stems, complex masks; W = 256 ... 2048; T = 62 and 63; with and without the rest), each through its
-equal-length and its ragged launch, whose shared clips must agree bit for bit, against plain.maskfilter* -- unpacked, one frame per transform.
+4 ... 9 times below any single chain at thousands of columns); the eight fused float32 mask-filter kernels at the 112 cases of
+tests/maskfilter_cases.py (real masks in three layouts, three stems, complex masks, interleaved stereo under one mask and under one per
+channel; W = 256 ... 2048; T = 62 and 63; with and without the rest), each through its equal-length and its ragged launch, whose shared clips
+must agree bit for bit, against plain.maskfilter* -- unpacked, one frame and one channel per transform.  (The four PCM kernels' float32
+output is held to the float kernels' bits in tests/test_gpu_maskfilter_pcm.py and tests/test_gpu_windows.py, which carries the judgment over.)
 
 One line per case: kernel, the eight numbers, the four ratios.  ZAFX_ACCURACY_REPORT=path writes them as JSON (profiles/accuracy_ratios.json)."""
 import json
@@ -136,10 +138,12 @@ def test_dct_dst_are_as_accurate_as_a_plain_transform(zafx, name):
 
 @pytest.mark.parametrize("name", ac.MASKFILTER_NAMES)
 def test_maskfilter_is_as_accurate_as_a_plain_chain(zafx, name):
-    """The six fused mask-filter kernels (tests/maskfilter_cases.py): each case through its equal-length launch and, with four short clips between
-    the same three, through its ragged one; the ragged launch must give every shared clip the bits of the equal-length one."""
+    """The eight fused float32 mask-filter kernels (tests/maskfilter_cases.py): each case through its equal-length launch and, with four short
+    clips between the same three, through its ragged one; the ragged launch must give every shared clip the bits of the equal-length one.  A
+    stereo form's rows are its channels, and the level of the old bound is taken over both."""
     form, wl, rest, b, twin, where = ac.maskfilter_case(name)
     kernels = mc.KERNELS[mc.family_of(form)]
+    tail = mc.rest_rows(form)
     got = mr.run(form, b["w"], b["clips"], b["masks"], rest, ragged=False)
     rag = mr.run(form, twin["w"], twin["clips"], twin["masks"], rest, ragged=True)
     for k, i in enumerate(where):
@@ -148,9 +152,9 @@ def test_maskfilter_is_as_accurate_as_a_plain_chain(zafx, name):
         for r, ref, x in zip(res, case["refs"], case["clips"]):   # the old bound, on top: every stem and the rest
             assert np.isfinite(r).all(), (tag, "the output was not written everywhere")
             for j in range(len(r)):
-                err = mc.mask_error(r[j], ref[j], x)   # (the references' rows: the stems, then the rest)
+                err = mc.mask_error(r[j], ref[j], mc.row_level(ref, x, j, tail))   # (the references' rows: the stems, then the rest)
                 assert err <= mc.TOL_FFT, (tag, len(x), j, err)
-        judge(f"maskfilter/{tag}", kernel, "MASKFILTER", mc.all_rows(res), mc.rows_of(case["refs"], rest), mc.rows_of(case["yard"], rest), wl // 2)
+        judge(f"maskfilter/{tag}", kernel, "MASKFILTER", mc.all_rows(res), mc.rows_of(case["refs"], rest, tail), mc.rows_of(case["yard"], rest, tail), wl // 2)
 
 
 @pytest.mark.parametrize("name", ac.LINEAR_NAMES)

@@ -17,13 +17,16 @@ for the center; the bit comparisons take none.  One case per family (const_probe
 still in the stream, before its result is downloaded: zafx_plan_set_constant waits for the plan's stream before it frees anything, so step 1's
 result is still A's.
 
+The fused mask-filter kernels take a second device input, the masks, which the Case machinery of tests/const_probe.py has no place for: their
+A -> B -> A -> zero gain -> A runs through tests/maskfilter_run.py on a private plan (test_maskfilter_window_replaced_on_a_used_plan, at the end).
+
 k_cqt's two forms (matrix-core for a numerically real matrix, lane reduction otherwise) share the name k_cqt; zafx_plan_cqt_form
 (Plan.cqt_form) tells which one a launch took, and every float32 CQT case holds it to the fresh plan's and, after A again, to step 1's."""
 import numpy as np
 import pytest
 
 import const_probe as cp
-from conftest import relerr, synth_clip
+from conftest import excess, relerr, synth_clip
 
 pytestmark = pytest.mark.gpu
 
@@ -458,3 +461,103 @@ def test_refused_cqt_uploads_leave_the_plan_as_it_was(zafx, route):
         if d_in is not None:
             d_in.free()
         plan.destroy()
+
+
+# ------------------------------------------------------------------------------------------------ the fused mask filters on a reused plan
+# Every mask-filter kernel whose own module has no A -> B -> A (k_maskfilter and k_maskfilter_stems have:
+# test_window_replaced_on_a_used_plan): they share check_window_gain and the plan's cola_gain through zafx_overlap_walk.hpp, and each reads
+# the window on its own.  (form of tests/maskfilter_cases.py, ragged, the PCM entry points' output type or None for the float32 ones)
+MASKFILTER_SWAPS = [("tf", True, None), ("stems", True, None), ("complex", False, None), ("complex", True, None),
+                    ("stereo1", False, None), ("stereo1", True, None), ("stereo2", False, None), ("stereo2", True, None)]
+MASKFILTER_SWAPS += [(form, ragged, out) for form in ("tf", "stereo1", "stereo2") for ragged in (False, True) for out in (np.int16, np.float32)]
+PCM_SCALE = 4096   # unit noise as int16 with peaks near 18000: under masks in [0, 1] the reference stays inside the int16 range (asserted)
+
+
+def _swap_id(v):
+    form, ragged, out = v
+    return f"{form}{'_pcm_' + np.dtype(out).name if out else ''}{'_ragged' if ragged else ''}"
+
+
+@pytest.mark.parametrize("wl", [2048, 256])
+@pytest.mark.parametrize("swap_case", MASKFILTER_SWAPS, ids=_swap_id)
+def test_maskfilter_window_replaced_on_a_used_plan(zafx, swap_case, wl):
+    """A = periodic Hamming, B = tests/windows.py's skew, on a private MASKFILTER_REST plan, three clips of 9 H + 3 under "unit" / "disc" masks:
+    every step against the float64 oracle under its window (mask_error <= TOL_FFT, a stereo form's level over both channels; an int16 output
+    within 0.5 LSB + 32768 x the per-hop bound, its rest clip(x - y_q) in integers); B has the bits and the last_kernel of a fresh plan made
+    with B; A again has step 1's bits; then A with w[0] = -w[H] is refused in the reference's words and leaves the filled output as it was,
+    and A once more has step 1's bits.  Before any launch: B's reference differs from A's by MIN_CHANGE or more in every row of every clip."""
+    import maskfilter_cases as mc
+    import maskfilter_run as mr
+    import windows as win
+    from test_gpu_maskfilter_pcm import int_rest
+    form, ragged, out = swap_case
+    h = wl // 2
+    n = 9 * h + 3
+    data, tail = mc.data_of(form), mc.rest_rows(form)
+    windows = {"a": cp.window_a(wl), "b": win.skew(wl)}
+    batches = {tag: mc.batch(data, wl, n, name, "unit") for tag, name in (("a", "hamming"), ("b", "skew"))}
+    clips, masks = batches["a"]["clips"], batches["a"]["masks"]
+    assert all(np.array_equal(x, y) for x, y in zip(clips, batches["b"]["clips"])) and len(clips) == 3
+    if out is None:
+        refs = {tag: batches[tag]["refs"] for tag in windows}
+    else:
+        pcm = [mc.to_int16(x, PCM_SCALE) for x in clips]
+        clips = [mc.normalised(q) for q in pcm]
+        refs = {tag: [mc.reference(data, xn, w, m) for xn, m in zip(clips, masks)] for tag, w in windows.items()}
+    for ra, rb in zip(refs["a"], refs["b"]):   # teeth, on the host
+        change = min(relerr(rb[j], ra[j]) for j in range(len(ra)))
+        assert change >= cp.MIN_CHANGE, (form, wl, change)
+    bounds = None
+    if out == np.int16:
+        bounds = {tag: [mc.int16_bound(r[:tail], xn, h) for r, xn in zip(refs[tag], clips)] for tag in windows}
+        for tag in windows:
+            for r, b in zip(refs[tag], bounds[tag]):
+                assert (np.abs(32768.0 * r[:tail]) + b < 32767).all(), (form, wl, tag, "the reference leaves the int16 range")
+
+    def make(w):
+        p = zafx.Plan(zafx.MASKFILTER_REST, window_length=wl, step_length=h, layout="TF")
+        p.set_window(w)
+        return p
+
+    def go(plan, refusal=None):
+        if out is None:
+            return mr.run(form, None, clips, masks, True, ragged, plan=plan, refusal=refusal)
+        return mr.run_pcm(form, None, pcm, masks, True, ragged, out, plan=plan, refusal=refusal)
+
+    def held(res, tag):
+        worst = 0.0
+        for i, (r, ref, x) in enumerate(zip(res, refs[tag], clips)):
+            assert r.shape == ref.shape and np.isfinite(r).all(), (form, wl, tag, i)
+            if out == np.int16:
+                share = excess(r[:tail].astype(np.float64), 32768.0 * ref[:tail], bounds[tag][i])
+                assert share <= 1.0, (form, wl, tag, i, "int16 out against the oracle", share)
+                planar = pcm[i].T if pcm[i].ndim == 2 else pcm[i][None]
+                assert np.array_equal(r[tail:], int_rest(planar, r[:tail])), (form, wl, tag, i, "rest")
+                worst = max(worst, share)
+            else:
+                for j in range(len(r)):
+                    err = mc.mask_error(r[j], ref[j], mc.row_level(ref, x, j, tail))
+                    assert err <= cp.TOL_FFT, (form, wl, tag, i, j, err)
+                    worst = max(worst, err)
+        print(f"{_swap_id(swap_case)} W={wl} {tag.upper()}: worst {'share of the int16 bound' if out == np.int16 else 'mask_error'} {worst:.3g}")
+
+    same = lambda p, q: len(p) == len(q) and all(same_bits(a, b) for a, b in zip(p, q))   # noqa: E731
+    fresh = make(windows["b"])
+    used = make(windows["a"])
+    try:
+        out_f, kernel_f = go(fresh), fresh.last_kernel
+        out_1 = go(used)
+        held(out_1, "a")
+        used.set_window(windows["b"])
+        out_2 = go(used)
+        held(out_2, "b")
+        assert same(out_2, out_f) and used.last_kernel == kernel_f and not same(out_2, out_1), (form, wl, used.last_kernel, kernel_f)
+        used.set_window(windows["a"])
+        assert same(go(used), out_1), (form, wl, "A again")
+        used.set_window(cp.window_zero_gain(wl, h))
+        assert go(used, refusal="sum(window[0:W:H]) is zero") is None
+        used.set_window(windows["a"])
+        assert same(go(used), out_1), (form, wl, "A after the refused window")
+    finally:
+        fresh.destroy()
+        used.destroy()

@@ -50,6 +50,15 @@ def edge_lengths(wl):
     return [1, h - 1, h, h + 1, wl, 3 * h + 7]
 
 
+def long_lengths(wl):
+    """60 H + 5 at the smallest and the largest window: several tiles, so the carry is handed on, and a batch this small is cut into segments."""
+    return [60 * (wl // 2) + 5] if wl in (256, 2048) else []
+
+
+def matrix_lengths(wl):
+    return edge_lengths(wl) + long_lengths(wl)
+
+
 def noise(seed, n, ch, sigma=None):
     """int16 noise, (n,) or (n, 2): full range, or (sigma) Gaussian at that level."""
     g = np.random.default_rng([707, seed, n, ch])
@@ -158,14 +167,16 @@ def matrix(wl, form, rest, n):
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("wl", WINDOWS)
 def test_float_out_has_the_bits_of_the_float_kernel(wl, form, rest):
-    for n in edge_lengths(wl):
+    """The edge lengths -- one tile, no carry -- and, at W = 256 and 2048, 60 H + 5: the PCM instantiations against the float ones across tile
+    boundaries, a handed-on carry and segment cuts, equal-length and inside the ragged batch beside the edge lengths."""
+    for n in matrix_lengths(wl):
         x, m, yf, pf, pq = matrix(wl, form, rest, n)
         assert pf.dtype == np.float32 and same(pf, yf), (wl, form, rest, n)
     # ragged: every edge length in one launch, per mask kind, against the equal-length call
     for k in range(len(KINDS)):
-        clips = [matrix(wl, form, rest, n)[0][k] for n in edge_lengths(wl)]
-        masks = [matrix(wl, form, rest, n)[1][k] for n in edge_lengths(wl)]
-        for n, r in zip(edge_lengths(wl), run_pcm_ragged(clips, masks, wl, form, rest, np.float32)):
+        clips = [matrix(wl, form, rest, n)[0][k] for n in matrix_lengths(wl)]
+        masks = [matrix(wl, form, rest, n)[1][k] for n in matrix_lengths(wl)]
+        for n, r in zip(matrix_lengths(wl), run_pcm_ragged(clips, masks, wl, form, rest, np.float32)):
             assert same(r.reshape(matrix(wl, form, rest, n)[2][k].shape), matrix(wl, form, rest, n)[2][k]), (wl, form, rest, n, KINDS[k])
 
 
@@ -173,7 +184,7 @@ def test_float_out_has_the_bits_of_the_float_kernel(wl, form, rest):
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("wl", WINDOWS)
 def test_int16_out_is_the_quantised_float_output(wl, form, rest):
-    for n in edge_lengths(wl):
+    for n in matrix_lengths(wl):
         x, m, yf, pf, pq = matrix(wl, form, rest, n)
         assert pq.dtype == np.int16
         y = yf[:, 0] if rest else yf
@@ -182,9 +193,9 @@ def test_int16_out_is_the_quantised_float_output(wl, form, rest):
         if rest:
             assert np.array_equal(pq[:, 1], int_rest(x, yq)), (wl, form, n)
     for k in range(len(KINDS)):
-        clips = [matrix(wl, form, rest, n)[0][k] for n in edge_lengths(wl)]
-        masks = [matrix(wl, form, rest, n)[1][k] for n in edge_lengths(wl)]
-        for n, r in zip(edge_lengths(wl), run_pcm_ragged(clips, masks, wl, form, rest, np.int16)):
+        clips = [matrix(wl, form, rest, n)[0][k] for n in matrix_lengths(wl)]
+        masks = [matrix(wl, form, rest, n)[1][k] for n in matrix_lengths(wl)]
+        for n, r in zip(matrix_lengths(wl), run_pcm_ragged(clips, masks, wl, form, rest, np.int16)):
             assert same(r.reshape(matrix(wl, form, rest, n)[4][k].shape), matrix(wl, form, rest, n)[4][k]), (wl, form, rest, n, KINDS[k])
 
 

@@ -784,3 +784,75 @@ def test_stems_of_zero_masks(zafx_lib, wl):
         for r, x in zip(res, xs):
             assert r.shape == (mc.N_STEMS + 1, len(x)) and not r[:mc.N_STEMS].any(), (wl, len(x))
             assert np.array_equal(mr.bits(r[mc.N_STEMS]), mr.bits(x)), (wl, len(x), "rest")
+
+
+def stereo_maskfilter_rows(tag, res, case, h):
+    """Every channel of y and of the rest of every stereo clip: mask_error <= TOL_FFT, the level over both channels, and the per-hop bound of
+    tests/maskfilter_cases.hop_share_stereo -- max_hop|ref| per channel, the floor's level over both.  The figures go into the report before
+    they are asserted; silence gives exact zeros."""
+    import maskfilter_cases as mc
+    for i, (r, ref, x) in enumerate(zip(res, case["refs"], case["clips"])):
+        assert r.shape == ref.shape == (4, len(x)) and np.isfinite(r).all(), (tag, i)
+        figures = []
+        for j in (0, 2):
+            shares = mc.hop_share_stereo(r[j:j + 2], ref[j:j + 2], x, h)
+            for c in (0, 1):
+                g = mc.mask_error(r[j + c], ref[j + c], mc.row_level(ref, x, j + c, 2))
+                talk = float(np.abs(r[j + c].astype(np.float64) - ref[j + c]).max()) / max(float(np.abs(x).max()), 1e-300)
+                _report[f"maskfilter/{tag}.clip{i}.row{j + c}"] = {"normwise": g, "hop_share": shares[c], "peak": float(np.abs(ref[j + c]).max()),
+                                                                  "error_of_the_loud_level": talk}
+                figures.append((j + c, g, shares[c]))
+        for row, g, share in figures:
+            assert g <= TOL_FFT, (tag, i, row, "normwise", g)
+            assert share <= 1.0, (tag, i, row, "hop bound", share)
+        if not np.any(x):
+            assert not np.any(r), (tag, i, "silence must give exact zeros, the rest included")
+
+
+@pytest.mark.parametrize("name", sig.STEREO_NAMES)
+@pytest.mark.parametrize("wl", [2048, 256])
+def test_stereo_signal_through_the_mask_filters(zafx_lib, wl, name):
+    """k_maskfilter_stereo under one mask ("uniform") and under one per channel ("uniform" on L, "sparse" on R) and its ragged twin, the rest
+    on, on every stereo signal at 20 H + 9 sample frames and its first 7 H + 3: left_only -- a silent channel in the same transform as a loud
+    one, whose every figure is reported --, loud_quiet, tones, DC, an impulse.  Bounds: mask_error <= TOL_FFT and hop_share_stereo <= 1
+    (tests/test_accuracy_host.py holds the unpacked chain to half of it and a float32 model of the packing to it on the same inputs);
+    silence gives exact zeros.  The ragged launch gives the full-length clip the bits of the equal-length one.
+
+    The same signals through the PCM kernels, quantised to rint(16384 x) -- half of full scale, so that the reference alone stays inside the
+    int16 range under masks in [0, 1], asserted on the host before the launch: float32 out has the bits of the float kernel on the clip / 32768,
+    int16 out is held to |y_q - 32768 ref| <= 0.5 + 32768 (the per-hop bound)."""
+    import maskfilter_cases as mc
+    import maskfilter_run as mr
+    assert wl in mc.SIGNAL_WINDOWS and mc.C_FLOOR == C_FLOOR and mc.TOL_FFT == TOL_FFT
+    h = wl // 2
+    case = mc.stereo_signal_case(name, wl)
+    for form in mc.STEREO_SIGNAL_FORMS:
+        c = case[form]
+        same = {k: [c[k][i] for i in c["equal"]] for k in ("clips", "masks", "refs")}
+        got = mr.run(form, case["w"], same["clips"], same["masks"], True, ragged=False)
+        rag = mr.run(form, case["w"], c["clips"], c["masks"], True, ragged=True)
+        for k, i in enumerate(c["equal"]):
+            assert np.array_equal(mr.bits(rag[i]), mr.bits(got[k])), (name, wl, form, "ragged clip", i)
+        stereo_maskfilter_rows(f"{form}.{name}_{wl}", got, same, h)
+        stereo_maskfilter_rows(f"{form}_ragged.{name}_{wl}", rag, c, h)
+        # int16 PCM: the references of the quantised clips, in range before anything is launched
+        pcm = [mc.to_int16(x, 16384) for x in c["clips"]]
+        norm = [mc.normalised(q) for q in pcm]
+        refs = [mc.reference(form, xn, case["w"], m) for xn, m in zip(norm, c["masks"])]
+        bounds = [mc.int16_bound(ref[:2], xn, h) for xn, ref in zip(norm, refs)]
+        for ref, bound in zip(refs, bounds):
+            assert (np.abs(32768.0 * ref[:2]) + bound < 32767).all(), (name, wl, form, "the reference leaves the int16 range")
+        for ragged in (False, True):
+            pick = list(c["equal"]) if not ragged else list(range(len(pcm)))
+            sel = lambda v: [v[i] for i in pick]   # noqa: E731
+            f32 = mr.run(form, case["w"], sel(norm), sel(c["masks"]), True, ragged=ragged)
+            p32 = mr.run_pcm(form, case["w"], sel(pcm), sel(c["masks"]), True, ragged, np.float32)
+            p16 = mr.run_pcm(form, case["w"], sel(pcm), sel(c["masks"]), True, ragged, np.int16)
+            for i, a, b, q in zip(pick, f32, p32, p16):
+                tag = f"{form}_pcm{'_ragged' if ragged else ''}.{name}_{wl}.clip{i}"
+                assert np.array_equal(mr.bits(a), mr.bits(b)), (tag, "float32 out against the float kernel")
+                share = excess(q[:2].astype(np.float64), 32768.0 * refs[i][:2], bounds[i])
+                _report[f"maskfilter/{tag}"] = {"int16_share": share}
+                assert share <= 1.0, (tag, "int16 out against the oracle", share)
+                if not np.any(pcm[i]):
+                    assert not np.any(q) and not np.any(b), (tag, "silence")

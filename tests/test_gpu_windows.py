@@ -19,13 +19,13 @@ n % 4 != 0, k_stft_ft16's run-time-claim form by rows of whole lines (its static
 Shapes: the smallest that hold a whole tile and an edge tile of the form under test.  ISTFT and center leave out `random`, whose COLA sum
 zaf.istft divides by is 0.026 at W = 4096, hop W / 2 (tests/test_windows_host.py::test_cola_sums_of_the_istft_and_center_cases).
 
-The six fused mask-filter kernels read the window itself, and their blind spot is the PERIODIC mirror: periodic Hamming, their other tests' only
+The fused mask-filter kernels -- the six mono ones, k_maskfilter_stereo and its ragged twin, the four PCM kernels -- read the window itself, and their blind spot is the PERIODIC mirror: periodic Hamming, their other tests' only
 window, satisfies w[n] == w[(W - n) % W].  test_maskfilter runs every form of tests/maskfilter_cases.py under the (window, W) pairs of
 windows.MASKFILTER_WINDOWS -- skew and signed at W = 256 ... 2048, random at 512 and 2048, where its COLA sum, the kernels' `gain`, is negative.
 A library whose mask-filter kernels read window[(W - n) & (W - 1)] fails all ten cases on the MI355X and passes the 160 accuracy cases, the signal
 cases and the ragged, complex and ragged-stems modules, which run under Hamming.
 
-Measured on MI355X, 2026-10-18 (242 tests, 3 s; the maskfilter row 2026-10-21), worst normwise error per group (the test functions' first argument to held()) and window, over
+Measured on MI355X, 2026-10-18 (242 tests, 3 s; the maskfilter rows 2026-10-21), worst normwise error per group (the test functions' first argument to held()) and window, over
 every form and row padding mode of the group -- f64: the float64 kernels of every group; set ZAFX_WINDOWS_REPORT=path to have a run write its own:
     mdct_2048     random 1.46e-07, signed 1.83e-07, skew 1.72e-07
     mdct_4096     random 1.94e-07, signed 1.63e-07, skew 1.80e-07
@@ -43,7 +43,10 @@ every form and row padding mode of the group -- f64: the float64 kernels of ever
     istft_ragged  signed 1.34e-07, skew 1.48e-07
     center        skew 4.22e-07, worst hop 0.0045 of its bound
     cache         skew 2.17e-07
-    maskfilter    random 1.82e-07, signed 2.15e-07, skew 3.38e-07   (mask_error; the six fused kernels, every form: test_maskfilter)
+    maskfilter    random 1.82e-07, signed 2.15e-07, skew 3.38e-07   (mask_error; the six fused mono kernels, every form: test_maskfilter)
+    maskfilter_stereo           random 1.56e-07, signed 1.71e-07, skew 2.02e-07   (k_maskfilter_stereo and _ragged, one mask and two; the level over both channels)
+    maskfilter_stereo_vs_mono   random 1.81e-07, signed 1.69e-07, skew 2.00e-07   (two masks: channel c against k_maskfilter on the planar channel c under mask c)
+    maskfilter_pcm              no figure of its own: the four PCM kernels' float32 output has the float kernels' BITS under every window, int16 is its quantiser
 Every float32 transform sits at 1.3e-7 ... 3.0e-7 -- where the same kernels sit under Hamming and KBD (tests/test_gpu_signals.py) -- and no form
 was found with a mirrored tap.  That the module would see one: a library whose fold table has components 0 and 3 swapped (2m < W/4) passes the
 MDCT tests of test_gpu_signals.py, test_gpu_mdct_ragged.py and test_gpu_pcm_ragged.py (KBD) on the MI355X and fails 57 of these (test_mdct_2048, _frame_major_and_row_align, test_mdct_4096, the W = 512 /
@@ -593,16 +596,24 @@ def test_maskfilter(zafx, name, wl):
     (W - n) % W passes every other mask-filter test) and, where `random` runs, under a negative COLA gain.  Three clips of 20 H + 9 samples,
     "unit" / "disc" masks, the rest on: every form of tests/maskfilter_cases.py through its equal-length launch and -- with clips of 1, H,
     3 H + 7 and 0 samples between the same three -- through its ragged one, every stem and the rest within TOL_FFT (mask_error) of the float64
-    oracle; the ragged launch gives the shared clips the bits of the equal-length one, and each stem has the bits of the one-mask kind."""
+    oracle; the ragged launch gives the shared clips the bits of the equal-length one, and each stem has the bits of the one-mask kind.
+
+    The stereo forms (k_maskfilter_stereo, one mask and two) are forms of the same loop, the level of their bound taken over both channels;
+    with two different masks channel c must also lie within TOL_FFT of k_maskfilter on the planar channel c under mask c.  The four PCM
+    kernels run on the same windows and masks -- mono "TF" and the two stereo forms, the clips rint(16384 x) clipped to int16 --: float32 out
+    has the bits of the float kernel on the clip / 32768, int16 out is the quantiser of that output and the rest clip(x - y_q) in integers,
+    equal-length and ragged."""
     import maskfilter_cases as mc
     import maskfilter_run as mr
+    from test_gpu_maskfilter_pcm import int_rest, numpy_quantise
     assert (wl, wl // 2) in win.MASKFILTER_GEOMETRIES
     n = 20 * (wl // 2) + 9
-    worst = 0.0
+    worst = {"maskfilter": 0.0, "maskfilter_stereo": 0.0, "maskfilter_stereo_vs_mono": 0.0}
     for form in mc.FORMS:
-        family = mc.family_of(form)
-        b = mc.batch(family, wl, n, name, "unit")
-        twin, where = mc.ragged_twin(b, mc.extras(family, wl, name))
+        family, data, tail = mc.family_of(form), mc.data_of(form), mc.rest_rows(form)
+        group = "maskfilter_stereo" if family == "stereo" else "maskfilter"
+        b = mc.batch(data, wl, n, name, "unit")
+        twin, where = mc.ragged_twin(b, mc.extras(data, wl, name))
         got = mr.run(form, b["w"], b["clips"], b["masks"], True, ragged=False)
         rag = mr.run(form, twin["w"], twin["clips"], twin["masks"], True, ragged=True)
         for k, i in enumerate(where):
@@ -611,17 +622,40 @@ def test_maskfilter(zafx, name, wl):
             for r, ref, x in zip(res, case["refs"], case["clips"]):
                 assert r.shape == ref.shape and np.isfinite(r).all(), (name, wl, form, len(x))
                 for j in range(len(r)):
-                    err = mc.mask_error(r[j], ref[j], x)
-                    worst = max(worst, err)
+                    err = mc.mask_error(r[j], ref[j], mc.row_level(ref, x, j, tail))
+                    worst[group] = max(worst[group], err)
                     assert err <= TOL_FFT, (name, wl, form, len(x), j, err)
         if form == "stems":   # stem s of clip k against the one-mask kind ("TF") under mask s alone
             for s in range(mc.N_STEMS):
                 one = mr.run("tf", b["w"], b["clips"], [m[s] for m in b["masks"]], False, ragged=False)
                 for k in range(len(one)):
                     assert np.array_equal(mr.bits(got[k][s]), mr.bits(one[k][0])), (name, wl, "stem", s, "clip", k)
-    key = f"maskfilter.{name}"
-    _report[key] = max(_report.get(key, 0.0), worst)
-    print(f"maskfilter {name} W={wl}: {worst:.3e}")
+        if form == "stereo2":   # channel c against the mono kind on the planar channel c under mask c: within the bound, not bitwise
+            assert all(not np.array_equal(m[0], m[1]) for m in b["masks"])
+            for c in (0, 1):
+                mono = mr.run("tf", b["w"], [np.ascontiguousarray(x[:, c]) for x in b["clips"]], [m[c] for m in b["masks"]], True, ragged=False)
+                for k, x in enumerate(b["clips"]):
+                    for blk in (0, 1):   # y, the rest
+                        level = max(float(np.abs(mono[k][blk]).max()), float(np.abs(x).max()))
+                        err = float(np.abs(got[k][2 * blk + c].astype(np.float64) - mono[k][blk]).max()) / level
+                        worst["maskfilter_stereo_vs_mono"] = max(worst["maskfilter_stereo_vs_mono"], err)
+                        assert err <= TOL_FFT, (name, wl, "channel", c, "clip", k, "block", blk, err)
+        if form in mc.PCM_FORMS:
+            for ragged, case in ((False, b), (True, twin)):
+                pcm = [mc.to_int16(x, 16384) for x in case["clips"]]
+                ref32 = mr.run(form, case["w"], [mc.normalised(q) for q in pcm], case["masks"], True, ragged=ragged)
+                as32 = mr.run_pcm(form, case["w"], pcm, case["masks"], True, ragged, np.float32)
+                as16 = mr.run_pcm(form, case["w"], pcm, case["masks"], True, ragged, np.int16)
+                for i, (q, f, p32, p16) in enumerate(zip(pcm, ref32, as32, as16)):
+                    what = (name, wl, form, "ragged" if ragged else "equal-length", "clip", i)
+                    assert p32.dtype == np.float32 and p32.shape == f.shape and np.array_equal(mr.bits(p32), mr.bits(f)), what
+                    assert p16.dtype == np.int16 and np.array_equal(p16[:tail], numpy_quantise(f[:tail])), what
+                    planar = q.T if q.ndim == 2 else q[None]   # (channels, N): the rows' order
+                    assert np.array_equal(p16[tail:], int_rest(planar, p16[:tail])), what
+    for group, err in worst.items():
+        key = f"{group}.{name}"
+        _report[key] = max(_report.get(key, 0.0), err)
+    print(f"maskfilter {name} W={wl}: " + ", ".join(f"{g} {e:.3e}" for g, e in worst.items()))
 
 
 # ------------------------------------------------------------------------------------------------------------------ the plan cache

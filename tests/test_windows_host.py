@@ -154,6 +154,12 @@ def test_cola_sums_of_the_mask_filter_cases():
     assert used["skew"] == lengths and used["signed"] == lengths and used["random"] == [512, 2048], used
     assert len(used["random"]) >= 2 and all(win.cola_gain(win.random(wl), wl // 2) < -win.MIN_COLA for wl in used["random"])
     assert len(win.MASKFILTER_WINDOWS) == 10
+    # the stereo forms ride the same table: both are forms of test_maskfilter's loop, and the gain their model divides by is the table's sum
+    import maskfilter_cases as mc
+    assert {"stereo1", "stereo2"} <= set(mc.FORMS) and mc.KERNELS["stereo"] == ("k_maskfilter_stereo", "k_maskfilter_stereo_ragged")
+    for name, wl in win.MASKFILTER_WINDOWS:
+        w32 = mc.window_of(name, wl).astype(np.float32)
+        assert abs(float(w32[0] + w32[wl // 2]) - COLA_TABLE[name][[256, 512, 1024, 2048].index(wl)]) < 5e-4, (name, wl)
 
 
 def _periodic_mirror(w):
@@ -169,8 +175,11 @@ def test_a_mirrored_window_moves_the_mask_filter(name, wl):
     h = wl // 2
     n = 20 * h + 9
     x = mc.clip(0, n).astype(np.float64)
+    xs = mc.stereo_clip(0, n)
     filters = {"real": lambda v: mc.oracle_maskfilter(x, v, mc.masks_for("real", wl, n, 0, "unit")),
-               "complex": lambda v: mc.oracle_maskfilter_complex(x, v, mc.masks_for("complex", wl, n, 0, None))}
+               "complex": lambda v: mc.oracle_maskfilter_complex(x, v, mc.masks_for("complex", wl, n, 0, None)),
+               "stereo1": lambda v: mc.oracle_maskfilter_stereo(xs, v, mc.masks_for("stereo1", wl, n, 0, "unit")),
+               "stereo2": lambda v: mc.oracle_maskfilter_stereo(xs, v, mc.masks_for("stereo2", wl, n, 0, "unit"))}
     w, ham = win.window(name, wl), mc.window_of("hamming", wl)
     for kind, fn in filters.items():
         full, periodic = relerr(fn(w[::-1]), fn(w)), relerr(fn(_periodic_mirror(w)), fn(w))
@@ -178,6 +187,30 @@ def test_a_mirrored_window_moves_the_mask_filter(name, wl):
         print(f"W={wl} {name} {kind}: mirrored {full:.3f}, periodic mirror {periodic:.3f}; periodic mirror under Hamming {blind:.1e}")
         assert full >= 0.05 and periodic >= 0.05, (name, wl, kind, full, periodic)
         assert blind <= 1e-12, (wl, kind, blind)
+
+
+@pytest.mark.parametrize("name,wl", win.MASKFILTER_WINDOWS)
+def test_a_mirrored_window_in_the_stereo_model_fails_the_gpu_check(name, wl):
+    """tests/test_gpu_windows.py::test_maskfilter's check -- mask_error <= TOL_FFT on its own batches, the level over both channels -- applied
+    to the float32 model of the stereo packing (maskfilter_cases.stereo_model): sound, it passes every (window, W), `random` with its negative
+    gain included; with the window read at (W - n) % W it fails every one, both forms, y and the rest -- and has the sound model's bits
+    under periodic Hamming, the only window the stereo and PCM kernels had met."""
+    import maskfilter_cases as mc
+    n = 20 * (wl // 2) + 9
+    for form in sorted(mc.STEREO_DATA):
+        assert form in mc.FORMS and mc.family_of(form) == "stereo"
+        b, ham = mc.batch(form, wl, n, name, "unit"), mc.batch(form, wl, n, "hamming", "unit")
+        for x, m, ref in zip(b["clips"], b["masks"], b["refs"]):
+            sound, bad = mc.stereo_model_rows(x, b["w"], m), mc.stereo_model_rows(x, b["w"], m, "window_mirror")
+            swapped = mc.stereo_model_rows(x, b["w"], m, "channel_swap")   # (the masks exchanged: seen under any window, by stereo2 alone)
+            assert np.array_equal(swapped, sound) == (form == "stereo1"), (name, wl, form)
+            for j in range(4):
+                level = mc.row_level(ref, x, j, 2)
+                assert mc.mask_error(sound[j], ref[j], level) <= mc.TOL_FFT, (name, wl, form, j)
+                assert mc.mask_error(bad[j], ref[j], level) >= 1e3 * mc.TOL_FFT, (name, wl, form, j, mc.mask_error(bad[j], ref[j], level))
+                assert form == "stereo1" or mc.mask_error(swapped[j], ref[j], level) >= 1e3 * mc.TOL_FFT, (name, wl, j)
+        x, m = ham["clips"][0], ham["masks"][0]
+        assert np.array_equal(mc.stereo_model_rows(x, ham["w"], m), mc.stereo_model_rows(x, ham["w"], m, "window_mirror"))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the tolerance yardstick
